@@ -8,11 +8,16 @@ resident in HBM.  One process per GPU; ranks share nothing on the data path (wea
 streams shard across ranks); torch.distributed (RCCL) is only the control plane: barrier and
 max/sum of the per-rank counters.
 
-Prints ONE JSON line: metric macroblocks/s (whole job), plus `roofline` for the dominant
-kernel (HIP-event timed), `cpu_baseline` (the reference's own C functions from oracle/_ref/libref.so —
+Prints ONE JSON line: metric macroblocks/s (whole job), `ms_per_step`, and `roofline` for the dominant
+kernel (HIP-event timed in the timed steps).  A plain run does only that: set up, warm up, time --steps steps, write
+the outputs (--dump-outputs) and print the line.  --full adds what takes runs of its own: `roofline.alone_*` (the
+dominant kernel alone over the whole batch), `cpu_baseline` (the reference's own C functions from oracle/_ref/libref.so —
 kind "reference" — or, where that object is missing, the scalar oracle — kind "port" — on ALL hardware threads of
 this box, pinned, on a bounded sample of the same workload) and `extra`: further measured points of the same path
 (64 pictures per step, all-intra pictures, content on which the loop filter fires, swscale config 5, HEVC config 3).
+
+--dump-outputs DIR writes what the timed path decoded in its last step (dump_outputs) so that two builds can be
+compared output for output: the inputs are generated from fixed seeds, identical from run to run.
 
 The workload generator is the one tests/test_frame_gpu.py::test_full_size_1080p_batch_matches_oracle checks
 bit-exactly against the oracle at full size; the bench itself does not check outputs.
@@ -89,10 +94,14 @@ def main():
                     "another reconstruction, only beside the other pipelines' loop filters)")
     ap.add_argument("--mb-width", type=int, default=120)
     ap.add_argument("--mb-height", type=int, default=68)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure what takes runs of its own: the dominant kernel alone "
+                    "(roofline.alone_*), the CPU baseline and the extra points (N=1 only); each can be left out again with --no-alone, --no-cpu-baseline, --no-extra")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the pictures the timed path decoded in its last step to DIR/<name>.npy (float32; "
+                    "rank 0's: a fixed sample of at most 4 pictures, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
-    ap.add_argument("--no-extra", action="store_true", help="skip the additional measured points (rank 0, N=1 only)")
-    ap.add_argument("--no-alone", action="store_true", help="skip the three whole-batch launches of the dominant kernel after the timed region (roofline.alone_*): what the "
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the additional measured points (rank 0, N=1 only)")
+    ap.add_argument("--no-alone", action="store_true", help="with --full: skip the three whole-batch launches of the dominant kernel after the timed region (roofline.alone_*): what the "
                     "counter passes use (tools/gpu_traffic.sh), so that every launch of the profiled command is a share-sized one")
     ap.add_argument("--notes", action="store_true", help="keep the long `note` / `sample` texts of the extra points in the JSON line (without them "
                     "the whole line stays under the 16 KB the driver's record keeps; what each point is: README.md, DESIGN.md 6)")
@@ -124,6 +133,8 @@ def main():
         sys.exit("bench.py: --gpus %d but the launcher started %d rank(s) (WORLD_SIZE): the two must agree" % (args.gpus, world))
     if args.backend == "gloo" and not args.dry:
         sys.exit("bench.py: --backend gloo is the CPU control-plane test and needs --dry")
+    if args.dry and args.dump_outputs:
+        sys.exit("bench.py: --dry runs no kernel: there are no outputs to dump")
     ctl = "cpu" if (world == 1 or args.backend == "gloo") else "cuda"      # where the control plane's small tensors live
     dist = None
     if world > 1:
@@ -257,6 +268,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     my_steps = len(evs)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dev, F)
 
     # per LAUNCH (one pipeline's share of the batch): with P > 1 the launches of different pipelines run side by side, so the passes' times do not add up to the step
     if pipe is not None:
@@ -310,7 +323,7 @@ def main():
                          "launches_per_step": launches, "avg_launch_us": t_pass * 1e3,
                          "algorithmic_bytes_per_launch": bytes_pass / launches},
         }
-        if P > 1 and not args.no_alone:
+        if P > 1 and args.full and not args.no_alone:
             # the same kernel ALONE, outside the timed region: one launch over the whole batch, nothing beside it (what rounds 1-4's lines and the extra point
             # config2_f2048_one_pipeline measure)
             e0, e1 = lib.mi355_event_create(), lib.mi355_event_create()
@@ -332,14 +345,14 @@ def main():
         # HBM bytes per launch of the dominant kernel from the PMC passes of the same command
         # (tools/gpu_traffic.sh -> profiles/*hbm_traffic*.json; cannot be collected from inside this process)
         out["roofline"]["traffic"], out["roofline"]["traffic_source"] = measured_traffic(dom, per)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(fs, args.cpu_seconds)
         dev.free()
         dev = None
         # every measured point's fraction of the HBM roofline as a short scalar inside `config` (the driver's record keeps
         # `config` whole and only the NAMES of other top-level keys): headline first
         points = {"config2_f%d" % F: round(value / world * B_FUSED / HBM_PEAK, 4)}
-        if world == 1 and not args.no_extra:
+        if world == 1 and args.full and not args.no_extra:
             out["extra"] = extra_points(lib, prov, mbw, mbh, tiled)
             for p in out["extra"]:
                 for key in ("fused_fraction_of_hbm_roofline", "fraction_of_hbm_roofline"):
@@ -373,6 +386,27 @@ def main():
         dev.free()
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60 * 10 ** 6                 # --dump-outputs writes at most 64 MB: the pictures stay below this, the headers and indices fit beside them
+
+
+def dump_outputs(out_dir, dev, F):
+    """--dump-outputs: the decoded pictures (the dst surfaces the loop filter wrote, de-tiled to planes) of a fixed sample of
+    the batch — the first and the last picture and two drawn with a fixed seed, fewer where they coincide or would pass
+    DUMP_BYTES — as float32 y / cb / cr [n, rows, columns], and their indices in the batch (picture_index, float64)"""
+    import numpy as np
+    fs = dev.fs
+    per_picture = fs.W * fs.H * 3 // 2 * 4
+    if per_picture > DUMP_BYTES:
+        sys.exit("bench.py: one picture is more than the %d bytes --dump-outputs may write" % DUMP_BYTES)
+    idx = np.unique(np.concatenate([[0, F - 1], np.random.default_rng(0x264).choice(F, min(F, 2), replace=False)]))
+    idx = idx[:DUMP_BYTES // per_picture]
+    planes = [dev.fetch(dev.dst, first=int(f), count=1) for f in idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "picture_index.npy"), idx.astype(np.float64))
+    for k, name in enumerate(("y", "cb", "cr")):
+        np.save(os.path.join(out_dir, name + ".npy"), np.concatenate([p[k] for p in planes]).astype(np.float32))
 
 
 def dry_run(args, rank, world, dist, ctl):
@@ -639,7 +673,7 @@ def h264_real_stream_points(lib):
             pt[key]["macroblocks_per_s"] = st["pictures_per_s"] * 8160
         out.append(pt)
     exe1 = os.path.join(ROOT, "oracle", "_ref", "h264_tier1_gpu")
-    clip = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/realshort.mp4"
+    clip = os.path.join(ROOT, "tests", "golden", "realshort.mp4")
     if os.path.exists(exe1) and os.path.exists(clip):
         sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
         import mp4_samples

@@ -4,7 +4,7 @@
 Pipeline: the H.264 track of an .mp4 -> samples (mp4_samples.py) -> the REFERENCE's own decoder,
 built in place by oracle/Makefile and instrumented with two linker wraps
 (oracle/ref_h264_export.c) -> per-MB Tier-2 records + the reference's decoded pictures.
-The clip ships with the imageio Python package of this image (no network needed):
+The clip is imageio's sample clip, stored next to this script:
 realshort.mp4, H.264 High, 320x240 4:2:0, CABAC, 36 pictures (I/P, 8x8 transform, skip, intra-in-P).
 """
 import os
@@ -15,7 +15,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(HERE))
-CLIP = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/realshort.mp4"
+CLIP = os.path.join(HERE, "realshort.mp4")
 
 
 def main():

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLIP = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/realshort.mp4"
+CLIP = os.path.join(ROOT, "tests", "golden", "realshort.mp4")
 
 
 def samples_file(tmp_path, clip, n=None):

@@ -15,7 +15,7 @@ from test_bridge_emu import CLIP, ROOT, check_against_golden, samples_file
 
 pytestmark = pytest.mark.gpu
 EXE = os.path.join(ROOT, "oracle", "_ref", "h264_bridge_gpu")
-CLIP444 = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/cockatoo.mp4"
+CLIP444 = os.path.join(ROOT, "tests", "golden", "cockatoo.mp4")
 
 
 def _run(args, env_extra=None, timeout=600):

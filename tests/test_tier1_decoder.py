@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLIP = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/realshort.mp4"
+CLIP = os.path.join(ROOT, "tests", "golden", "realshort.mp4")
 
 
 @pytest.mark.skipif(not (os.path.isdir("/root/reference/libavcodec") and os.path.exists(CLIP)),
@@ -43,7 +43,7 @@ def test_reference_decoder_through_tier1_hooks(tmp_path, emu):
         assert np.array_equal(fr, want), "picture %d differs from the reference decoder's" % i
 
 
-CLIP444 = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/cockatoo.mp4"
+CLIP444 = os.path.join(ROOT, "tests", "golden", "cockatoo.mp4")
 
 
 @pytest.mark.skipif(not (os.path.isdir("/root/reference/libavcodec") and os.path.exists(CLIP444)),

@@ -1,7 +1,7 @@
 """GPU: the REFERENCE's own H.264 decoder, its five DSP tables overridden through the linker by
 this project's ff_*_init_mi355x hooks and bound to the real HIP library, decodes real clips on the MI355X.
 oracle/_ref/h264_tier1_gpu is built where /root/reference exists (oracle/Makefile, __graft_entry__.build()) and travels
-to the GPU box with the tree; the clips come with the image's imageio package.
+to the GPU box with the tree; the clips are imageio's sample clips, stored under tests/golden.
  * realshort.mp4 (High 4:2:0, 36 pictures): every picture equals what the unmodified reference decoder produced
    (tests/golden/h264_stream_realshort.npz).
  * cockatoo.mp4 (High 4:4:4 Predictive 1280x720, 280 pictures): hooked vs plain run of the same binary.  The first 24
@@ -19,8 +19,8 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "oracle", "_ref", "h264_tier1_gpu")
-CLIP = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/realshort.mp4"
-CLIP444 = "/opt/conda/lib/python3.9/site-packages/imageio/resources/images/cockatoo.mp4"
+CLIP = os.path.join(ROOT, "tests", "golden", "realshort.mp4")
+CLIP444 = os.path.join(ROOT, "tests", "golden", "cockatoo.mp4")
 
 
 def _samples_file(tmp_path, clip, n=None):

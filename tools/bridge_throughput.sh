@@ -12,7 +12,7 @@ sys.path.insert(0, "tests/golden")
 import mp4_samples
 import os
 clip = os.environ.get("CLIP", "realshort")
-avcc, samples = mp4_samples.extract("/opt/conda/lib/python3.9/site-packages/imageio/resources/images/%s.mp4" % clip)
+avcc, samples = mp4_samples.extract("tests/golden/%s.mp4" % clip)
 with open("/tmp/%s.samples" % clip, "wb") as f:
     f.write(struct.pack("<I", len(avcc)) + avcc + struct.pack("<I", len(samples)))
     for s in samples:
