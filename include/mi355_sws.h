@@ -71,6 +71,25 @@ int mi355_sws_scale(mi355_sws_ctx *ctx, const uint8_t *const src[3], const int s
 /* Tier 2: a batch of pictures resident in HBM, one launch; d_frames is a device array. */
 int mi355_sws_scale_frames_dev(mi355_sws_ctx *ctx, const mi355_sws_frame *d_frames, int nframes, void *stream);   /* 0, -1 bad argument, -2 launch failure */
 
+/* What mi355_sws_scale_frames_dev launches for a context (read only; the launch takes its kernel from the same helper). */
+enum {
+    MI355_SWS_K_C24 = 0,          /* the unscaled special converter (k_sws_c24) */
+    MI355_SWS_K_IDENT1_1 = 1,     /* no scaling, one luma tap, up to two chroma taps: yuv2rgb24_1 from the source bytes */
+    MI355_SWS_K_IDENT1_X = 2,     /* no scaling, one luma tap, three or four chroma taps: yuv2rgb24_X from the source bytes */
+    MI355_SWS_K_GENERIC_A = 3,    /* the generic tile kernel holding 28 luma / 16 chroma source lines */
+    MI355_SWS_K_GENERIC_B = 4,    /* ... 40 / 20 */
+    MI355_SWS_K_GENERIC_C = 5     /* ... 48 / 24 */
+};
+typedef struct mi355_sws_plan_info {
+    int kernel;                   /* MI355_SWS_K_* */
+    int th;                       /* output rows per tile of the generic kernel (0 for c24) */
+    int hstage;                   /* horizontal source spans staged in LDS (monotonic positions, every tap inside its line) */
+    int lum_lines, chr_lines;     /* the largest luma / chroma source span of a tile */
+    int narrow;                   /* generic kernel: every tile takes the narrow form (dstW < 128 or a vertical filter of more than 8 taps);
+                                   * 0: full tiles of an 8-byte aligned destination store from registers */
+} mi355_sws_plan_info;
+int mi355_sws_plan(const mi355_sws_ctx *ctx, mi355_sws_plan_info *plan);   /* 0, -1 bad argument */
+
 /* ---- the individual inner loops (Tier 1, host pointers), argument lists of the reference's
  * function-pointer types minus the SwsContext ------------------------------------------------ */
 /* hScale8To15_c swscale.c:133-147 (c->hyScale / c->hcScale) */

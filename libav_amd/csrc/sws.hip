@@ -1015,6 +1015,31 @@ extern "C" void mi355_sws_destroy(mi355_sws_ctx *c)
     delete c;
 }
 
+/* the kernel mi355_sws_scale_frames_dev launches for a context (MI355_SWS_K_*): the launch and mi355_sws_plan both ask here */
+static int sws_kernel(const SwsDev &h)
+{
+    if (h.special) return MI355_SWS_K_C24;
+    /* a context that does not scale: straight from the source bytes (k_sws_ident1; MI355_SWS_NO_IDENT1=1, developer switch: through the tile all the same) */
+    static const bool no_ident1 = std::getenv("MI355_SWS_NO_IDENT1") != nullptr;
+    if (!no_ident1 && h.hident_l && h.hident_c && h.vls == 1 && h.vcs <= 4 && !(h.dstW & 1) && h.srcW >= h.dstW && 2 * h.chrSrcW >= h.dstW)
+        return h.vcs <= 2 ? MI355_SWS_K_IDENT1_1 : MI355_SWS_K_IDENT1_X;      /* packed_mode() 1 / the X template */
+    /* a CU's 160 KB of LDS hold `wgs` workgroups, one wave of each per SIMD: the instance whose register budget matches */
+    if (h.lum_lines <= 28 && h.chr_lines <= 16) return MI355_SWS_K_GENERIC_A;
+    if (h.lum_lines <= 40 && h.chr_lines <= 20) return MI355_SWS_K_GENERIC_B;
+    return MI355_SWS_K_GENERIC_C;
+}
+
+extern "C" int mi355_sws_plan(const mi355_sws_ctx *c, mi355_sws_plan_info *p)
+{
+    if (!c || !p) return -1;
+    const SwsDev &h = c->h;
+    p->kernel = sws_kernel(h);
+    p->th = h.th; p->hstage = h.hstage; p->lum_lines = h.lum_lines; p->chr_lines = h.chr_lines;
+    /* k_sws_generic: the wide form needs a full tile (dstW - x0 >= TW) and vertical filters of at most eight taps */
+    p->narrow = !h.special && (h.dstW < TW || h.vls > 8 || h.vcs > 8);
+    return 0;
+}
+
 /* waves per SIMD the three instances' register allocation aims at (developer switches; the defaults are what their LDS tiles allow) */
 #ifndef MI355_SWS_WAVES_A
 #define MI355_SWS_WAVES_A 8
@@ -1031,23 +1056,19 @@ extern "C" int mi355_sws_scale_frames_dev(mi355_sws_ctx *c, const mi355_sws_fram
     hipStream_t s = static_cast<hipStream_t>(stream);
     const SwsDev &h = c->h;
     DeviceScope on(c->device);
-    if (h.special) {
+    const int k = sws_kernel(h);
+    if (k == MI355_SWS_K_C24) {
         hipLaunchKernelGGL(k_sws_c24, dim3((h.dstW + C24_COLS - 1) / C24_COLS, (h.srcH + C24_ROWS - 1) / C24_ROWS, nframes), dim3(NT), 0, s,
                            &c->d->luts, h.dstW, h.srcH, 0, d_frames);
+    } else if (k == MI355_SWS_K_IDENT1_1 || k == MI355_SWS_K_IDENT1_X) {
+        const dim3 grid((h.dstW + C24_COLS - 1) / C24_COLS, (h.dstH + IDENT_ROWS - 1) / IDENT_ROWS, nframes);
+        if (k == MI355_SWS_K_IDENT1_1) hipLaunchKernelGGL(k_sws_ident1<false>, grid, dim3(NT), 0, s, c->d, d_frames);
+        else hipLaunchKernelGGL(k_sws_ident1<true>, grid, dim3(NT), 0, s, c->d, d_frames);
     } else {
-        /* a CU's 160 KB of LDS hold `wgs` workgroups, one wave of each per SIMD: the instance whose register budget matches */
-        /* a context that does not scale: straight from the source bytes (k_sws_ident1; MI355_SWS_NO_IDENT1=1, developer switch: through the tile all the same) */
-        static const bool no_ident1 = std::getenv("MI355_SWS_NO_IDENT1") != nullptr;
-        if (!no_ident1 && h.hident_l && h.hident_c && h.vls == 1 && h.vcs <= 4 && !(h.dstW & 1) && h.srcW >= h.dstW && 2 * h.chrSrcW >= h.dstW) {
-            const dim3 grid((h.dstW + C24_COLS - 1) / C24_COLS, (h.dstH + IDENT_ROWS - 1) / IDENT_ROWS, nframes);
-            if (h.vcs <= 2) hipLaunchKernelGGL(k_sws_ident1<false>, grid, dim3(NT), 0, s, c->d, d_frames);       /* packed_mode() 1 */
-            else hipLaunchKernelGGL(k_sws_ident1<true>, grid, dim3(NT), 0, s, c->d, d_frames);
-            return hipGetLastError() == hipSuccess ? 0 : -2;
-        }
         const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
         static_assert(160 * 1024 / sws_lds_bytes(28, 16) >= 8 && 160 * 1024 / sws_lds_bytes(40, 20) == 7 && 160 * 1024 / sws_lds_bytes(MAXL, MAXC) == 6, "workgroups per CU of the instances");
-        if (h.lum_lines <= 28 && h.chr_lines <= 16) hipLaunchKernelGGL((k_sws_generic<28, 16, MI355_SWS_WAVES_A>), grid, dim3(NT), 0, s, c->d, d_frames);
-        else if (h.lum_lines <= 40 && h.chr_lines <= 20) hipLaunchKernelGGL((k_sws_generic<40, 20, MI355_SWS_WAVES_B>), grid, dim3(NT), 0, s, c->d, d_frames);
+        if (k == MI355_SWS_K_GENERIC_A) hipLaunchKernelGGL((k_sws_generic<28, 16, MI355_SWS_WAVES_A>), grid, dim3(NT), 0, s, c->d, d_frames);
+        else if (k == MI355_SWS_K_GENERIC_B) hipLaunchKernelGGL((k_sws_generic<40, 20, MI355_SWS_WAVES_B>), grid, dim3(NT), 0, s, c->d, d_frames);
         else hipLaunchKernelGGL((k_sws_generic<MAXL, MAXC, MI355_SWS_WAVES_C>), grid, dim3(NT), 0, s, c->d, d_frames);
     }
     return hipGetLastError() == hipSuccess ? 0 : -2;
