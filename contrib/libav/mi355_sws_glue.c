@@ -24,6 +24,11 @@
  *   mi355_sws_describe()   fills the plain descriptor of include/mi355_sws.h from a live SwsContext (filter banks and
  *                          yuv->rgb tables exactly as the reference built them): what mi355_sws_create() takes for the
  *                          whole-picture and batched entry points.
+ *   planar destinations    yuv420p -> yuv420p / yuv422p / yuv444p contexts of the generic scaler take the same two forms: whole
+ *                          pictures through mi355_sws_scale_planar (all three destination planes), inner loops through shims
+ *                          over mi355_sws_hscale8to15 / mi355_sws_yuv2planeX_8 / mi355_sws_yuv2plane1_8.
+ *                          mi355_sws_describe_planar() fills the descriptor mi355_sws_create_planar() takes; it declines
+ *                          SWS_FAST_BILINEAR, range conversion and the unscaled converters (planar_format()).
  * The device is MI355_DEVICE (default 0), as for the decoder bridges.
  */
 #include <pthread.h>
@@ -78,6 +83,38 @@ static int describe(struct SwsContext *c, mi355_sws_desc *d, int special)
  * builds any filter bank) */
 int mi355_sws_describe(struct SwsContext *c, mi355_sws_desc *d) { return describe(c, d, c->vLumFilter == NULL); }
 
+/* planar destinations: the MI355_SWS_DST_* of a yuv420p -> yuv420p / yuv422p / yuv444p context whose generic scaler (swscale.c:618-645) the
+ * planar kernel restates, else 0.  Declined: SWS_FAST_BILINEAR (hyscale_fast / hcscale_fast, swscale.c:737), range conversion
+ * (lumConvertRange / chrConvertRange, :748-763), a chroma line drop (vChrDrop), alpha, and any context without the generic scaler's
+ * filter banks (the unscaled converters and plane copies, utils.c:1043-1048). */
+static int planar_format(const SwsContext *c)
+{
+    if (c->srcFormat != AV_PIX_FMT_YUV420P || c->srcBpc != 8 || c->dstBpc != 8) return 0;
+    if (c->hyscale_fast || c->hcscale_fast || c->lumConvertRange || c->chrConvertRange || c->vChrDrop) return 0;
+    if (c->lumToYV12 || c->chrToYV12 || c->readLumPlanar || c->readChrPlanar || !c->vLumFilter || !c->vChrFilter || !c->hLumFilter || !c->hChrFilter) return 0;
+    switch (c->dstFormat) {
+    case AV_PIX_FMT_YUV420P: return MI355_SWS_DST_YUV420P;
+    case AV_PIX_FMT_YUV422P: return MI355_SWS_DST_YUV422P;
+    case AV_PIX_FMT_YUV444P: return MI355_SWS_DST_YUV444P;
+    default: return 0;
+    }
+}
+/* the descriptor of a planar context for mi355_sws_create_planar (0), -1 for a context it declines */
+int mi355_sws_describe_planar(struct SwsContext *c, mi355_sws_desc *d, int *dst_format)
+{
+    const int fmt = planar_format(c);
+    if (!fmt) return -1;
+    memset(d, 0, sizeof(*d));
+    d->srcW = c->srcW; d->srcH = c->srcH; d->dstW = c->dstW; d->dstH = c->dstH;
+    d->chrSrcW = c->chrSrcW; d->chrSrcH = c->chrSrcH; d->chrDstW = c->chrDstW;
+    d->hLum = (mi355_sws_filter){ c->hLumFilter, c->hLumFilterPos, c->hLumFilterSize, c->dstW };
+    d->hChr = (mi355_sws_filter){ c->hChrFilter, c->hChrFilterPos, c->hChrFilterSize, c->chrDstW };
+    d->vLum = (mi355_sws_filter){ c->vLumFilter, c->vLumFilterPos, c->vLumFilterSize, c->dstH };
+    d->vChr = (mi355_sws_filter){ c->vChrFilter, c->vChrFilterPos, c->vChrFilterSize, c->chrDstH };
+    *dst_format = fmt;
+    return 0;
+}
+
 #ifndef MI355_SWS_DESCRIBE_ONLY
 static void t1_hscale(SwsContext *c, int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
 {
@@ -115,8 +152,27 @@ static int device_ready(void)
     return mi355_init(dev ? atoi(dev) : 0) == 0;
 }
 
+/* yuv2planeX_8_c / yuv2plane1_8_c (output.c:242-266): the planar output's inner loops */
+static void t1_planeX(const int16_t *filter, int filterSize, const int16_t **src, uint8_t *dest, int dstW, const uint8_t *dither, int offset)
+{
+    n_calls++;
+    mi355_sws_yuv2planeX_8(filter, filterSize, src, dest, dstW, dither, offset);
+}
+static void t1_plane1(const int16_t *src, uint8_t *dest, int dstW, const uint8_t *dither, int offset)
+{
+    n_calls++;
+    mi355_sws_yuv2plane1_8(src, dest, dstW, dither, offset);
+}
+
 void ff_sws_init_mi355x(SwsContext *c)
 {
+    if (planar_format(c)) {
+        if (!device_ready() || !c->hyScale || !c->hcScale || !c->yuv2planeX || !c->yuv2plane1) return;
+        c->hyScale = c->hcScale = t1_hscale;
+        c->yuv2planeX = t1_planeX;
+        c->yuv2plane1 = t1_plane1;
+        return;
+    }
     if (!taken(c) || c->hyscale_fast) return;
     if (!device_ready()) return;                                /* no usable MI355X: the reference's functions stay */
     /* only what the reference set to the functions these shims restate (a context whose selectors left one of them empty
@@ -134,6 +190,7 @@ typedef struct Bound {
     SwsContext *c;
     SwsFunc real;                 /* what the reference chose */
     int special;                  /* ... through ff_yuv2rgb_get_func_ptr */
+    int planar;                   /* MI355_SWS_DST_* of a planar context (mi355_sws_scale_planar), 0 for rgb24 */
     mi355_sws_ctx *dev;
     int failed;                   /* the device side does not take this context: the reference's function from now on */
     int busy;                     /* calls of mi355_sws_scale in flight on `dev` (under bound_mu): the device context is destroyed only at 0 */
@@ -180,12 +237,13 @@ static Bound *bound_find(SwsContext *c, int create)
 /* a selector runs for this context: sws_init_context() of a new context — possibly at the address of one that was freed */
 static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
 {
-    if (!real || !taken(c) || getenv("MI355_SWS_PLAIN")) return real;
+    const int planar = special ? 0 : planar_format(c);
+    if (!real || !(taken(c) || planar) || getenv("MI355_SWS_PLAIN")) return real;
     pthread_mutex_lock(&bound_mu);
     Bound *b = bound_find(c, 1);
     if (b) {
         slot_release(b);
-        b->c = c; b->real = real; b->special = special; b->stamp = ++n_stamp;
+        b->c = c; b->real = real; b->special = special; b->planar = planar; b->stamp = ++n_stamp;
     }
     pthread_mutex_unlock(&bound_mu);
     return b ? mi355_swsfunc_entry : real;
@@ -199,22 +257,28 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
     mi355_sws_ctx *dev = NULL;
     /* the device path takes whole pictures with positive strides (a 2-D copy has no negative pitch; sws_scale() itself also takes bottom-up
      * pictures — vf_vflip makes them — and those go to the reference's function) */
+    /* a planar context: all three destination planes; range conversion set since the context was bound (sws_setColorspaceDetails) is
+     * the reference's for that picture */
+    const int planar_ok = b && b->planar && dstStride[1] > 0 && dstStride[2] > 0 && planar_format(c) == b->planar;
     if (b && !b->failed && srcSliceY == 0 && srcSliceH == c->srcH &&
-        srcStride[0] > 0 && srcStride[1] > 0 && srcStride[2] > 0 && dstStride[0] > 0) {
-        if (b->dev && !b->busy && (memcmp(b->y_table, c->yuvTable, 1024) || b->gv0 != c->table_gV[0])) { mi355_sws_destroy(b->dev); b->dev = NULL; }
+        srcStride[0] > 0 && srcStride[1] > 0 && srcStride[2] > 0 && dstStride[0] > 0 && (!b->planar || planar_ok)) {
+        if (b->dev && !b->busy && !b->planar && (memcmp(b->y_table, c->yuvTable, 1024) || b->gv0 != c->table_gV[0])) { mi355_sws_destroy(b->dev); b->dev = NULL; }
         if (!b->dev) {
             mi355_sws_desc d;
-            if (device_ready() && describe(c, &d, b->special) == 0) b->dev = mi355_sws_create(&d);
-            if (b->dev) { memcpy(b->y_table, c->yuvTable, 1024); b->gv0 = c->table_gV[0]; }
-            else b->failed = 1;
+            int fmt;
+            if (b->planar) {
+                if (device_ready() && mi355_sws_describe_planar(c, &d, &fmt) == 0) b->dev = mi355_sws_create_planar(&d, fmt);
+            } else if (device_ready() && describe(c, &d, b->special) == 0) b->dev = mi355_sws_create(&d);
+            if (b->dev && !b->planar) { memcpy(b->y_table, c->yuvTable, 1024); b->gv0 = c->table_gV[0]; }
+            else if (!b->dev) b->failed = 1;
         }
         dev = b->dev;
         if (dev) { b->busy++; b->stamp = ++n_stamp; }          /* the context stays until this call is back (a bind() or free for its address waits) */
     }
     pthread_mutex_unlock(&bound_mu);
     if (dev) {
-        const int st[3] = { srcStride[0], srcStride[1], srcStride[2] };
-        const int n = mi355_sws_scale(dev, src, st, dst[0], dstStride[0]);
+        const int st[3] = { srcStride[0], srcStride[1], srcStride[2] }, dst_st[3] = { dstStride[0], dstStride[1], dstStride[2] };
+        const int n = b->planar ? mi355_sws_scale_planar(dev, src, st, dst, dst_st) : mi355_sws_scale(dev, src, st, dst[0], dstStride[0]);
         pthread_mutex_lock(&bound_mu);
         b->busy--;
         pthread_cond_broadcast(&bound_idle);

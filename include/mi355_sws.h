@@ -1,7 +1,7 @@
 /*
  * mi355_sws.h — C ABI of the libswscale part of the hot path:
  * horizontal 8->15 bit FIR, vertical FIR to planar 8 bit or through the yuv->rgb LUTs to RGB24,
- * and the unscaled yuv420p -> rgb24 converter.
+ * and the unscaled yuv420p -> rgb24 converter; whole pictures to RGB24 or to planar yuv420p / yuv422p / yuv444p.
  *
  * The reference keeps these behind function pointers of the (private) SwsContext
  * (libswscale/swscale_internal.h:253-540): hyScale/hcScale :526-531, yuv2plane1/yuv2planeX/
@@ -78,7 +78,10 @@ enum {
     MI355_SWS_K_IDENT1_X = 2,     /* no scaling, one luma tap, three or four chroma taps: yuv2rgb24_X from the source bytes */
     MI355_SWS_K_GENERIC_A = 3,    /* the generic tile kernel holding 28 luma / 16 chroma source lines */
     MI355_SWS_K_GENERIC_B = 4,    /* ... 40 / 20 */
-    MI355_SWS_K_GENERIC_C = 5     /* ... 48 / 24 */
+    MI355_SWS_K_GENERIC_C = 5,    /* ... 48 / 24 */
+    MI355_SWS_K_PLANAR_A = 6,     /* a planar destination (mi355_sws_create_planar): the tile kernel holding 28 luma / 16 chroma source lines */
+    MI355_SWS_K_PLANAR_B = 7,     /* ... 40 / 24 */
+    MI355_SWS_K_PLANAR_C = 8      /* ... 48 / 48 */
 };
 typedef struct mi355_sws_plan_info {
     int kernel;                   /* MI355_SWS_K_* */
@@ -86,9 +89,31 @@ typedef struct mi355_sws_plan_info {
     int hstage;                   /* horizontal source spans staged in LDS (monotonic positions, every tap inside its line) */
     int lum_lines, chr_lines;     /* the largest luma / chroma source span of a tile */
     int narrow;                   /* generic kernel: every tile takes the narrow form (dstW < 128 or a vertical filter of more than 8 taps);
-                                   * 0: full tiles of an 8-byte aligned destination store from registers */
+                                   * 0: full tiles of an 8-byte aligned destination store from registers.  Planar kernels: dstW < 128 (every
+                                   * tile partial) or a vertical filter of more than 8 taps (taps read from memory, not held in registers) */
 } mi355_sws_plan_info;
 int mi355_sws_plan(const mi355_sws_ctx *ctx, mi355_sws_plan_info *plan);   /* 0, -1 bad argument */
+
+/* ---- planar destinations: yuv420p -> yuv420p / yuv422p / yuv444p, 8 bit (the planar branch of swscale(), swscale.c:618-645) ----
+ * The descriptor is the one above with: chrDstW = the chroma output width (AV_CEIL_RSHIFT(dstW, chrDstHSubSample)), vChr.n = the chroma
+ * output rows (chrDstH = AV_CEIL_RSHIFT(dstH, chrDstVSubSample), utils.c:1039-1040), unscaled_special = 0; the LUTs are not used.
+ * The contexts of the RGB24 entry points and of these are not interchangeable: each entry point returns -1 on the other kind. */
+enum { MI355_SWS_DST_YUV420P = 1, MI355_SWS_DST_YUV422P = 2, MI355_SWS_DST_YUV444P = 3 };
+/* NULL (and a message) for banks the device tiles cannot hold, as mi355_sws_create */
+mi355_sws_ctx *mi355_sws_create_planar(const mi355_sws_desc *desc, int dst_format);
+/* one picture of a batch, device pointers; source planes as in mi355_sws_frame */
+typedef struct mi355_sws_planar_frame {
+    const uint8_t *src[3];
+    int src_stride[3];
+    uint8_t *dst[3];       /* Y, U, V planes of the destination */
+    int dst_stride[3];
+} mi355_sws_planar_frame;
+/* Tier 2: a batch resident in HBM, one launch (0, -1 bad argument or not a planar context, -2 launch failure) */
+int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *ctx, const mi355_sws_planar_frame *d_frames, int nframes, void *stream);
+/* Tier 1: a whole picture, host pointers, synchronous; writes the first dstW / chrDstW bytes of each row (the caller's padding stays
+ * untouched).  Returns the number of output lines, negative on failure. */
+int mi355_sws_scale_planar(mi355_sws_ctx *ctx, const uint8_t *const src[3], const int src_stride[3],
+                           uint8_t *const dst[3], const int dst_stride[3]);
 
 /* ---- the individual inner loops (Tier 1, host pointers), argument lists of the reference's
  * function-pointer types minus the SwsContext ------------------------------------------------ */

@@ -1,10 +1,12 @@
 /*
- * sws.hip — the libswscale part of the path for yuv420p -> rgb24:
+ * sws.hip — the libswscale part of the path for yuv420p -> rgb24 and yuv420p -> yuv420p / yuv422p / yuv444p:
  *   k_sws_generic   the generic scaler of swscale() (libswscale/swscale.c:343-722) for whole pictures,
  *                   fused per output tile: horizontal 8->15 bit FIR of the source lines the tile needs
  *                   (hScale8To15_c :133-147) into LDS, vertical FIR + yuv->rgb LUT
  *                   (yuv2rgb24_{1,2,X}_c output.c:937-1110) from LDS, RGB rows staged in LDS and
  *                   written as dwords.  No int16 intermediate ever goes to HBM.
+ *   k_sws_planar    the same loop's planar branch (swscale.c:618-645, yuv2planeX_8_c / yuv2plane1_8_c output.c:242-266): the
+ *                   horizontal pass into LDS as above, the vertical pass from LDS straight to the three destination planes.
  *   k_sws_c24       the unscaled converter yuv2rgb_c_24_rgb (yuv2rgb.c:335-363).
  *   k_sws_line_*    the individual inner loops for the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
@@ -22,6 +24,7 @@ constexpr int TW = 128;      /* output samples per tile row */
 constexpr int MAXTH = 16;    /* output rows per tile (upper bound) */
 constexpr int MAXL = 48;     /* source luma lines a tile may need (upper bound: the LDS tile is sized per context, sws_plan) */
 constexpr int MAXC = 24;     /* source chroma lines a tile may need */
+constexpr int MAXCP = 48;    /* ... of a planar destination (its tile holds no LUT and no output rows; a 4:2:0 chroma plane's filters are as long as the luma's) */
 constexpr int NT = 256;
 
 struct SwsDev {
@@ -35,6 +38,8 @@ struct SwsDev {
     int hident_l, hident_c;                 /* the horizontal filter of the plane is the identity (one tap of 1 << 14 at position i: an unscaled
                                              * conversion through the generic path): hScale8To15 is then src << 7 */
     mi355_sws_luts luts;
+    /* planar destinations (mi355_sws_create_planar): the MI355_SWS_DST_* format, its chroma subsampling and chroma rows (0 / 0 / 0 / dstH for rgb24) */
+    int planar, hshift, vshift, chrDstH;
 };
 
 struct LutLds {
@@ -175,11 +180,21 @@ __device__ __forceinline__ int sws_dot2(uint32_t a, uint32_t b, int c)
     return __builtin_amdgcn_sdot2(__builtin_bit_cast(sws_short2, a), __builtin_bit_cast(sws_short2, b), c, false);
 }
 #endif
+/* a value the optimiser may not combine with what follows (an empty asm in a vector register) */
+#ifdef MI355_HIP_EMU_H
+static inline uint32_t sws_opaque(uint32_t v) { return v; }
+#else
+__device__ __forceinline__ uint32_t sws_opaque(uint32_t v)
+{
+    asm volatile("" : "+v"(v));
+    return v;
+}
+#endif
 /* eight taps: the column's byte offset inside a dword is the same on every staged line, so a line's eight samples are
  * three aligned dwords funnel-shifted into two, expanded to four 16-bit pairs and multiplied with the coefficient pairs
  * (3 LDS reads and 10 arithmetic instructions per output instead of 8 byte reads and 8 multiply-adds).  Products and sums
  * are the same integers (samples 0..255, coefficients 16 bits, |sum| < 2^31). */
-template <int COLS>
+template <int COLS, int OP = COLS>
 __device__ __forceinline__ void hscale_lines8(const uint8_t *row0, int16_t *out0, const uint32_t *cp, int left)
 {
     constexpr int per = NT / COLS;
@@ -210,11 +225,11 @@ __device__ __forceinline__ void hscale_lines8(const uint8_t *row0, int16_t *out0
             v = sws_dot2(sws_pair(hi, 0), c45, v);
             v = sws_dot2(sws_pair(hi, 1), c67, v);
             v >>= 7;
-            out0[(g + q) * per * COLS] = (int16_t)(v < 32767 ? v : 32767);
+            out0[(g + q) * per * OP] = (int16_t)(v < 32767 ? v : 32767);
         }
     }
 }
-template <int COLS, int TAPS>
+template <int COLS, int TAPS, int OP = COLS>
 __device__ __forceinline__ void hscale_lines(const uint8_t *row0, int16_t *out0, const uint32_t *cp, int left)
 {
     constexpr int per = NT / COLS;
@@ -229,11 +244,12 @@ __device__ __forceinline__ void hscale_lines(const uint8_t *row0, int16_t *out0,
 #pragma unroll
         for (int j = 0; j < TAPS; j++) val += (int)row[j] * cf[j];
         val >>= 7;
-        out0[k * per * COLS] = (int16_t)(val < 32767 ? val : 32767);
+        out0[k * per * OP] = (int16_t)(val < 32767 ? val : 32767);
     }
 }
-template <int COLS>
-__device__ __forceinline__ void hscale_tile(int16_t (*out)[COLS], const uint8_t *src, int stride, int srcW, const int32_t *posT,
+/* OP: int16 samples per line of `out` (a line may hold two planes' tiles side by side) */
+template <int COLS, int OP = COLS>
+__device__ __forceinline__ void hscale_tile(int16_t (*out)[OP], const uint8_t *src, int stride, int srcW, const int32_t *posT,
                                             const int16_t *coefT, int fs, int gx0, int ncols, int lo, int hi,
                                             uint32_t *stage_mem, int tid, bool zero_tail, bool may_stage, bool identity)
 {
@@ -369,21 +385,21 @@ __device__ __forceinline__ void hscale_tile(int16_t (*out)[COLS], const uint8_t 
         const int left = uniform(hi - base - r0);            /* lines r0, r0 + per, ... while k * per <= left (r0: one value per wave) */
 #ifndef MI355_SWS_EXP_NOLINES
         if (col_ok) {
-            if (fs == 1) hscale_lines<COLS, 1>(row0, out0, cp, left);
-            else if (fs <= 2) hscale_lines<COLS, 2>(row0, out0, cp, left);
-            else if (fs <= 4) hscale_lines<COLS, 4>(row0, out0, cp, left);
-            else if (fs <= 8) hscale_lines8<COLS>(row0, out0, cp, left);
+            if (fs == 1) hscale_lines<COLS, 1, OP>(row0, out0, cp, left);
+            else if (fs <= 2) hscale_lines<COLS, 2, OP>(row0, out0, cp, left);
+            else if (fs <= 4) hscale_lines<COLS, 4, OP>(row0, out0, cp, left);
+            else if (fs <= 8) hscale_lines8<COLS, OP>(row0, out0, cp, left);
             else {
                 for (int k = 0; k < LINES / per && k * per <= left; k++) {
                     const uint8_t *row = row0 + k * per * (PITCH * 4);
                     int val = 0;
                     for (int j = 0; j < fs; j++) val += (int)row[j] * f[j];
                     val >>= 7;
-                    out0[k * per * COLS] = (int16_t)(val < 32767 ? val : 32767);
+                    out0[k * per * OP] = (int16_t)(val < 32767 ? val : 32767);
                 }
             }
         } else if (zero_tail) {
-            for (int k = 0; k < LINES / per && k * per <= left; k++) out0[k * per * COLS] = 0;
+            for (int k = 0; k < LINES / per && k * per <= left; k++) out0[k * per * OP] = 0;
         }
 #endif
         __syncthreads();
@@ -681,6 +697,142 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
 #undef MI355_VR
 }
 
+/* ---- planar destinations: yuv420p -> yuv420p / yuv422p / yuv444p ----------------------------------------------------------
+ * The planar branch of swscale() (swscale.c:618-645) for 8-bit samples.  should_dither is 0 for an 8-bit source (:389, :445): every
+ * dither value is 64.  A plane whose vertical filter has ONE tap takes yuv2plane1_8_c (output.c:257-266), (s + 64) >> 7 with the
+ * coefficient unused; the others yuv2planeX_8_c (:242-255), ((64 << 12) + sum s_j * f_j) >> 19; both clipped to 0..255.
+ * A thread takes eight neighbouring samples of one LDS line (one ds_read_b128 per tap) and stores their eight bytes at once.  Sixteen
+ * lanes cover one line's 256 bytes, so each 16-lane group of a ds_read_b128 meets every bank once, whichever lines the rows read.
+ * NTAP: 1 plane1; 2 / 4 / 8 planeX with the taps in registers (taps past fs carry a zero coefficient); 0 planeX with fs taps read as it goes.
+ * GPP: 16-byte groups of a plane's tile row; NP: planes side by side in an LDS line (chroma: U | V). */
+template <int NTAP, int GPP, int NP>
+__device__ __forceinline__ void planar_rows(const int16_t *s, int lo, int maxl, const int16_t *vC, const int32_t *vP, int fs, int row0, int nrows,
+                                            int gx0, int width, uint8_t *d0, int st0, uint8_t *d1, int st1, int tid)
+{
+    constexpr int G = GPP * NP;                        /* groups per LDS line */
+    for (int t = tid; t < nrows * G; t += NT) {
+        const int r = t / G, g = t % G, gx = gx0 + 8 * (g % GPP), y = row0 + r;
+        if (gx >= width) continue;
+        const int first = imax(1 - fs, vP[y]);
+        const int16_t *col = s + 8 * g;
+        auto line = [&](int j) { return *reinterpret_cast<const sws_u32x4 *>(col + (size_t)(clampi(first + j, 0, maxl) - lo) * (G * 8)); };
+        auto sample = [](const sws_u32x4 &a, int k) { return (int)(int16_t)(a[k >> 1] >> (16 * (k & 1))); };
+        int v[8];
+        if (NTAP == 1) {
+            const sws_u32x4 a = line(0);
+#pragma unroll
+            for (int k = 0; k < 8; k++) v[k] = (sample(a, k) + 64) >> 7;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++) v[k] = 64 << 12;
+            if (NTAP == 0) {
+                for (int j = 0; j < fs; j++) {
+                    const int f = vC[(size_t)y * fs + j];
+                    const sws_u32x4 a = line(j);
+#pragma unroll
+                    for (int k = 0; k < 8; k++) v[k] += sample(a, k) * f;
+                }
+            } else {
+                constexpr int N = NTAP > 1 ? NTAP : 2;
+                int lf[N];
+#pragma unroll
+                for (int j = 0; j < N; j++) lf[j] = vC[(size_t)y * fs + (j < fs ? j : 0)];   /* unconditional: in flight together */
+                /* two taps at a time: the same sample of two lines side by side in a dword against the tap pair (v_dot2_i32_i16: the
+                 * reference's integer sum, as vertical_rows) */
+#pragma unroll
+                for (int j = 0; j < N; j += 2) {
+                    const sws_u32x4 la = line(j < fs ? j : 0), lb = line(j + 1 < fs ? j + 1 : 0);
+                    const uint32_t cp = (j < fs ? (uint32_t)lf[j] & 0xFFFFu : 0u) | (j + 1 < fs ? (uint32_t)lf[j + 1] << 16 : 0u);
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        v[2 * q] = sws_dot2(sws_lo2(la[q], lb[q]), cp, v[2 * q]);
+                        v[2 * q + 1] = sws_dot2(sws_hi2(la[q], lb[q]), cp, v[2 * q + 1]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 8; k++) v[k] >>= 19;
+        }
+        /* the clipped bytes pass sws_opaque before they are packed: left to itself the compiler fuses shift, clip and packing of two of them into
+         * v_ashr_pk_u8_i32 and ORs the next two bytes over its destination's upper half as if it were zero — on the device that half kept
+         * what the register held before (wrong 7th / 8th samples of a group, depending on the data) */
+        uint32_t w0 = 0, w1 = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) { w0 |= sws_opaque((uint32_t)clip_u8(v[k])) << (8 * k); w1 |= sws_opaque((uint32_t)clip_u8(v[4 + k])) << (8 * k); }
+        const bool second = NP > 1 && g >= GPP;
+        uint8_t *d = (second ? d1 : d0) + (size_t)r * (second ? st1 : st0) + gx;
+        if (gx + 8 <= width && (reinterpret_cast<uintptr_t>(d) & 7) == 0) {
+            *reinterpret_cast<sws_u32x2 *>(d) = sws_u32x2{ w0, w1 };
+        } else {                                       /* the plane's right edge, or a row that is not 8-byte aligned */
+            const int n = imin(8, width - gx);
+            for (int k = 0; k < n; k++) d[k] = (uint8_t)((k < 4 ? w0 : w1) >> (8 * (k & 3)));
+        }
+    }
+}
+/* the vertical pass of one LDS tile: its tap count rounded up to 1 / 2 / 4 / 8, more from memory */
+template <int GPP, int NP>
+__device__ __forceinline__ void planar_pass(const int16_t *s, int lo, int maxl, const int16_t *vC, const int32_t *vP, int fs, int row0, int nrows,
+                                            int gx0, int width, uint8_t *d0, int st0, uint8_t *d1, int st1, int tid)
+{
+    if (fs == 1) planar_rows<1, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid);
+    else if (fs <= 2) planar_rows<2, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid);
+    else if (fs <= 4) planar_rows<4, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid);
+    else if (fs <= 8) planar_rows<8, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid);
+    else planar_rows<0, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid);
+}
+
+/* LDS of a planar workgroup: the luma lines, the chroma lines (U | V side by side, CW samples each) and the staging lines; no LUT, no output rows */
+__host__ __device__ constexpr int sws_planar_lds_bytes(int lum_lines, int chr_lines, int cw)
+{
+    return lum_lines * TW * 2 + chr_lines * 2 * cw * 2 + STAGE_BYTES;
+}
+__host__ __device__ constexpr int sws_planar_waves(int lum_lines, int chr_lines, int cw)
+{
+    return 160 * 1024 / sws_planar_lds_bytes(lum_lines, chr_lines, cw) < 8 ? 160 * 1024 / sws_planar_lds_bytes(lum_lines, chr_lines, cw) : 8;
+}
+
+/* One workgroup per output tile of TW luma columns x th luma rows (blockIdx.z: the picture of the batch).  The tile's chroma is CW = TW >> hshift
+ * columns and the chroma rows cy with cy << vshift inside the tile's rows (swscale.c:618-645: a chroma row is written with the luma row
+ * cy << vshift, chrSkipMask).  Horizontal pass of the source lines the tile needs into LDS (hscale_tile, as k_sws_generic), then the
+ * vertical pass from LDS straight to the three planes. */
+template <int LCAP, int CCAP, int CW>
+#ifndef MI355_HIP_EMU_H
+__attribute__((amdgpu_waves_per_eu(sws_planar_waves(LCAP, CCAP, CW), sws_planar_waves(LCAP, CCAP, CW))))
+#endif
+__global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355_sws_planar_frame *frames)
+{
+    __shared__ __attribute__((aligned(16))) int16_t s_lum[LCAP][TW];
+    __shared__ __attribute__((aligned(16))) int16_t s_chr[CCAP][2 * CW];
+    __shared__ __attribute__((aligned(16))) uint32_t s_stage[STAGE_BYTES / 4];
+    SwsDev c = *cp;
+    c.hLumC = mi355_global(c.hLumC); c.hChrC = mi355_global(c.hChrC); c.vLumC = mi355_global(c.vLumC); c.vChrC = mi355_global(c.vChrC);
+    c.hLumP = mi355_global(c.hLumP); c.hChrP = mi355_global(c.hChrP); c.vLumP = mi355_global(c.vLumP); c.vChrP = mi355_global(c.vChrP);
+    mi355_sws_planar_frame fr = frames[blockIdx.z];
+    for (int k = 0; k < 3; k++) { fr.src[k] = mi355_global(fr.src[k]); fr.dst[k] = mi355_global(fr.dst[k]); }
+    const int tid = threadIdx.x, th = c.th, hs = c.hshift, vs = c.vshift;
+    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * th, y1 = imin(y0 + th, c.dstH) - 1;
+    const int cy0 = (y0 + (1 << vs) - 1) >> vs, cy1 = y1 >> vs;       /* the tile's chroma rows (none: a one-row tile on an odd row of 4:2:0) */
+    const int ls = c.vls, cs = c.vcs;
+    /* source lines the tile needs (swscale.c:459-468 for the first tap, :571-616 for the clamping) */
+    const int llo = clampi(imax(1 - ls, c.vLumP[y0]), 0, c.srcH - 1), lhi = clampi(imax(1 - ls, c.vLumP[y1]) + ls - 1, 0, c.srcH - 1);
+    hscale_tile<TW>(s_lum, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi, s_stage, tid, false, c.hstage != 0, c.hident_l != 0);
+    int clo = 0;
+    if (cy0 <= cy1) {
+        clo = clampi(imax(1 - cs, c.vChrP[cy0]), 0, c.chrSrcH - 1);
+        const int chi = clampi(imax(1 - cs, c.vChrP[cy1]) + cs - 1, 0, c.chrSrcH - 1);
+        hscale_tile<CW, 2 * CW>(s_chr, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false,
+                                c.hstage != 0, c.hident_c != 0);
+        hscale_tile<CW, 2 * CW>(reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]), fr.src[2], fr.src_stride[2], c.chrSrcW, c.hChrP, c.hChrC, c.hcs,
+                                x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0);
+    }
+    __syncthreads();
+    planar_pass<TW / 8, 1>(&s_lum[0][0], llo, c.srcH - 1, c.vLumC, c.vLumP, ls, y0, y1 - y0 + 1, x0, c.dstW,
+                           fr.dst[0] + (size_t)y0 * fr.dst_stride[0], fr.dst_stride[0], nullptr, 0, tid);
+    if (cy0 <= cy1)
+        planar_pass<CW / 8, 2>(&s_chr[0][0], clo, c.chrSrcH - 1, c.vChrC, c.vChrP, cs, cy0, cy1 - cy0 + 1, x0 >> hs, c.chrDstW,
+                               fr.dst[1] + (size_t)cy0 * fr.dst_stride[1], fr.dst_stride[1], fr.dst[2] + (size_t)cy0 * fr.dst_stride[2], fr.dst_stride[2], tid);
+}
+
 #ifndef MI355_C24_ROWS
 #define MI355_C24_ROWS 16
 #endif
@@ -914,6 +1066,7 @@ struct mi355_sws_ctx {
     /* Tier-1 picture staging */
     uint8_t *d_src[3] = {}, *d_dst = nullptr;
     mi355_sws_frame *d_frame = nullptr;
+    mi355_sws_planar_frame *d_pframe = nullptr;      /* ... of a planar context (d_dst then holds its three planes) */
     hipStream_t stream = nullptr;
     int device = -1;            /* the device of the thread that created the context: its entry points switch to it */
 };
@@ -931,22 +1084,25 @@ template <typename T> static const T *upload_bank(mi355_sws_ctx *c, int slot, co
 /* rows per tile: the largest power of two <= MAXTH for which no tile needs more source lines than the
  * LDS tile may hold; 0 if even single rows do not fit (filters larger than the tile: not supported).  lines[2]: the largest
  * luma / chroma span of a tile — what the context's LDS tile is sized for. */
-static int choose_rows(const mi355_sws_desc *d, int lines[2])
+static int choose_rows(const mi355_sws_desc *d, int lines[2], int vshift = 0, int maxc = MAXC)
 {
     for (int th = MAXTH; th >= 1; th >>= 1) {
         bool ok = true;
         lines[0] = lines[1] = 1;
         for (int y0 = 0; y0 < d->dstH && ok; y0 += th) {
             const int y1 = (y0 + th < d->dstH ? y0 + th : d->dstH) - 1;
-            auto span = [&](const mi355_sws_filter &f, int srcH) {
-                int lo = f.pos[y0] > 1 - f.size ? f.pos[y0] : 1 - f.size, hi = (f.pos[y1] > 1 - f.size ? f.pos[y1] : 1 - f.size) + f.size - 1;
-                for (int y = y0; y < y1; y++) if (f.pos[y + 1] < f.pos[y]) return 1 << 30;   /* not monotonic */
+            /* the span of filter rows a..b (none: 0) */
+            auto span = [&](const mi355_sws_filter &f, int srcH, int a, int b) {
+                if (a > b) return 0;
+                int lo = f.pos[a] > 1 - f.size ? f.pos[a] : 1 - f.size, hi = (f.pos[b] > 1 - f.size ? f.pos[b] : 1 - f.size) + f.size - 1;
+                for (int y = a; y < b; y++) if (f.pos[y + 1] < f.pos[y]) return 1 << 30;   /* not monotonic */
                 lo = lo < 0 ? 0 : (lo > srcH - 1 ? srcH - 1 : lo);
                 hi = hi < 0 ? 0 : (hi > srcH - 1 ? srcH - 1 : hi);
                 return hi - lo + 1;
             };
-            const int sl = span(d->vLum, d->srcH), sc = span(d->vChr, d->chrSrcH);
-            ok = sl <= MAXL && sc <= MAXC;
+            /* chroma rows: those cy with cy << vshift in y0..y1 (rgb24: vshift 0, the tile's rows) */
+            const int sl = span(d->vLum, d->srcH, y0, y1), sc = span(d->vChr, d->chrSrcH, (y0 + (1 << vshift) - 1) >> vshift, y1 >> vshift);
+            ok = sl <= MAXL && sc <= maxc;
             lines[0] = sl > lines[0] ? sl : lines[0];
             lines[1] = sc > lines[1] ? sc : lines[1];
         }
@@ -955,9 +1111,9 @@ static int choose_rows(const mi355_sws_desc *d, int lines[2])
     return 0;
 }
 
-extern "C" mi355_sws_ctx *mi355_sws_create(const mi355_sws_desc *desc)
+/* what mi355_sws_create and mi355_sws_create_planar share: the descriptor's sizes and the horizontal banks' properties */
+static mi355_sws_ctx *ctx_new(const mi355_sws_desc *desc)
 {
-    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create without mi355_init(); no CPU fallback\n"); std::abort(); }
     mi355_sws_ctx *c = new mi355_sws_ctx;
     c->device = current_device();
     SwsDev &h = c->h;
@@ -967,7 +1123,6 @@ extern "C" mi355_sws_ctx *mi355_sws_create(const mi355_sws_desc *desc)
     h.luts = desc->luts;
     h.th = 0;
     h.lum_lines = h.chr_lines = 1;
-    int lines[2] = { 1, 1 };
     h.hstage = 1;
     for (int i = 1; i < desc->hLum.n && desc->hLum.pos; i++) if (desc->hLum.pos[i] < desc->hLum.pos[i - 1]) h.hstage = 0;
     for (int i = 1; i < desc->hChr.n && desc->hChr.pos; i++) if (desc->hChr.pos[i] < desc->hChr.pos[i - 1]) h.hstage = 0;
@@ -983,6 +1138,33 @@ extern "C" mi355_sws_ctx *mi355_sws_create(const mi355_sws_desc *desc)
     h.hident_c = identity(desc->hChr, h.chrSrcW);
     h.hLumC = h.hChrC = h.vLumC = h.vChrC = nullptr;
     h.hLumP = h.hChrP = h.vLumP = h.vChrP = nullptr;
+    h.planar = h.hshift = h.vshift = 0;
+    h.chrDstH = h.dstH;
+    return c;
+}
+static void upload_banks(mi355_sws_ctx *c, const mi355_sws_desc *desc)
+{
+    SwsDev &h = c->h;
+    h.hLumC = upload_bank(c, 0, desc->hLum.coef, (size_t)h.dstW * h.hls);    h.hLumP = upload_bank(c, 1, desc->hLum.pos, (size_t)h.dstW);
+    h.hChrC = upload_bank(c, 2, desc->hChr.coef, (size_t)h.chrDstW * h.hcs); h.hChrP = upload_bank(c, 3, desc->hChr.pos, (size_t)h.chrDstW);
+    h.vLumC = upload_bank(c, 4, desc->vLum.coef, (size_t)h.dstH * h.vls);    h.vLumP = upload_bank(c, 5, desc->vLum.pos, (size_t)h.dstH);
+    h.vChrC = upload_bank(c, 6, desc->vChr.coef, (size_t)h.chrDstH * h.vcs); h.vChrP = upload_bank(c, 7, desc->vChr.pos, (size_t)h.chrDstH);
+}
+static mi355_sws_ctx *ctx_upload(mi355_sws_ctx *c)
+{
+    const SwsDev &h = c->h;
+    MI355_CHECK(hipMalloc(reinterpret_cast<void **>(&c->d), sizeof(SwsDev)));
+    MI355_CHECK(hipMemcpy(c->d, &h, sizeof(SwsDev), hipMemcpyHostToDevice));
+    MI355_CHECK(hipStreamCreate(&c->stream));
+    return c;
+}
+
+extern "C" mi355_sws_ctx *mi355_sws_create(const mi355_sws_desc *desc)
+{
+    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create without mi355_init(); no CPU fallback\n"); std::abort(); }
+    mi355_sws_ctx *c = ctx_new(desc);
+    SwsDev &h = c->h;
+    int lines[2] = { 1, 1 };
     if (!h.special) {
         if (desc->hLum.n != h.dstW || desc->hChr.n != h.chrDstW || desc->vLum.n != h.dstH || desc->vChr.n != h.dstH ||
             h.hls < 1 || h.hcs < 1 || h.vls < 1 || h.vcs < 1 || !(h.th = choose_rows(desc, lines))) {
@@ -991,15 +1173,37 @@ extern "C" mi355_sws_ctx *mi355_sws_create(const mi355_sws_desc *desc)
             return nullptr;
         }
         h.lum_lines = lines[0]; h.chr_lines = lines[1];
-        h.hLumC = upload_bank(c, 0, desc->hLum.coef, (size_t)h.dstW * h.hls);    h.hLumP = upload_bank(c, 1, desc->hLum.pos, (size_t)h.dstW);
-        h.hChrC = upload_bank(c, 2, desc->hChr.coef, (size_t)h.chrDstW * h.hcs); h.hChrP = upload_bank(c, 3, desc->hChr.pos, (size_t)h.chrDstW);
-        h.vLumC = upload_bank(c, 4, desc->vLum.coef, (size_t)h.dstH * h.vls);    h.vLumP = upload_bank(c, 5, desc->vLum.pos, (size_t)h.dstH);
-        h.vChrC = upload_bank(c, 6, desc->vChr.coef, (size_t)h.dstH * h.vcs);    h.vChrP = upload_bank(c, 7, desc->vChr.pos, (size_t)h.dstH);
+        upload_banks(c, desc);
     }
-    MI355_CHECK(hipMalloc(reinterpret_cast<void **>(&c->d), sizeof(SwsDev)));
-    MI355_CHECK(hipMemcpy(c->d, &h, sizeof(SwsDev), hipMemcpyHostToDevice));
-    MI355_CHECK(hipStreamCreate(&c->stream));
-    return c;
+    return ctx_upload(c);
+}
+
+extern "C" mi355_sws_ctx *mi355_sws_create_planar(const mi355_sws_desc *desc, int dst_format)
+{
+    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_planar without mi355_init(); no CPU fallback\n"); std::abort(); }
+    if (!desc || dst_format < MI355_SWS_DST_YUV420P || dst_format > MI355_SWS_DST_YUV444P) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_planar: destination format %d is not yuv420p / yuv422p / yuv444p\n", dst_format);
+        return nullptr;
+    }
+    mi355_sws_ctx *c = ctx_new(desc);
+    SwsDev &h = c->h;
+    h.planar = dst_format;
+    h.hshift = dst_format == MI355_SWS_DST_YUV444P ? 0 : 1;
+    h.vshift = dst_format == MI355_SWS_DST_YUV420P ? 1 : 0;
+    h.chrDstH = (h.dstH + (1 << h.vshift) - 1) >> h.vshift;               /* AV_CEIL_RSHIFT, utils.c:1040 */
+    int lines[2] = { 1, 1 };
+    const bool banks = desc->hLum.coef && desc->hLum.pos && desc->hChr.coef && desc->hChr.pos && desc->vLum.coef && desc->vLum.pos &&
+                       desc->vChr.coef && desc->vChr.pos;
+    if (h.special || !banks || h.chrDstW != (h.dstW + (1 << h.hshift) - 1) >> h.hshift || desc->hLum.n != h.dstW || desc->hChr.n != h.chrDstW ||
+        desc->vLum.n != h.dstH || desc->vChr.n != h.chrDstH || h.hls < 1 || h.hcs < 1 || h.vls < 1 || h.vcs < 1 ||
+        !(h.th = choose_rows(desc, lines, h.vshift, MAXCP))) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_planar: filter banks do not fit this backend (sizes %d/%d/%d/%d)\n", h.hls, h.hcs, h.vls, h.vcs);
+        delete c;
+        return nullptr;
+    }
+    h.lum_lines = lines[0]; h.chr_lines = lines[1];
+    upload_banks(c, desc);
+    return ctx_upload(c);
 }
 
 extern "C" void mi355_sws_destroy(mi355_sws_ctx *c)
@@ -1010,6 +1214,7 @@ extern "C" void mi355_sws_destroy(mi355_sws_ctx *c)
     for (uint8_t *p : c->d_src) if (p) MI355_CHECK(hipFree(p));
     if (c->d_dst) MI355_CHECK(hipFree(c->d_dst));
     if (c->d_frame) MI355_CHECK(hipFree(c->d_frame));
+    if (c->d_pframe) MI355_CHECK(hipFree(c->d_pframe));
     if (c->d) MI355_CHECK(hipFree(c->d));
     if (c->stream) MI355_CHECK(hipStreamDestroy(c->stream));
     delete c;
@@ -1018,6 +1223,8 @@ extern "C" void mi355_sws_destroy(mi355_sws_ctx *c)
 /* the kernel mi355_sws_scale_frames_dev launches for a context (MI355_SWS_K_*): the launch and mi355_sws_plan both ask here */
 static int sws_kernel(const SwsDev &h)
 {
+    /* planar: the B instance's chroma lines cover the 2 x 7 + 8 of a 2:1 4:2:0 reduction at 16-row tiles (seven workgroups a CU) */
+    if (h.planar) return h.lum_lines <= 28 && h.chr_lines <= 16 ? MI355_SWS_K_PLANAR_A : (h.lum_lines <= 40 && h.chr_lines <= 24 ? MI355_SWS_K_PLANAR_B : MI355_SWS_K_PLANAR_C);
     if (h.special) return MI355_SWS_K_C24;
     /* a context that does not scale: straight from the source bytes (k_sws_ident1; MI355_SWS_NO_IDENT1=1, developer switch: through the tile all the same) */
     static const bool no_ident1 = std::getenv("MI355_SWS_NO_IDENT1") != nullptr;
@@ -1035,7 +1242,8 @@ extern "C" int mi355_sws_plan(const mi355_sws_ctx *c, mi355_sws_plan_info *p)
     const SwsDev &h = c->h;
     p->kernel = sws_kernel(h);
     p->th = h.th; p->hstage = h.hstage; p->lum_lines = h.lum_lines; p->chr_lines = h.chr_lines;
-    /* k_sws_generic: the wide form needs a full tile (dstW - x0 >= TW) and vertical filters of at most eight taps */
+    /* k_sws_generic: the wide form needs a full tile (dstW - x0 >= TW) and vertical filters of at most eight taps; k_sws_planar: every tile
+     * stores bytewise (dstW < TW) or reads its taps from memory (more than eight) */
     p->narrow = !h.special && (h.dstW < TW || h.vls > 8 || h.vcs > 8);
     return 0;
 }
@@ -1052,7 +1260,7 @@ extern "C" int mi355_sws_plan(const mi355_sws_ctx *c, mi355_sws_plan_info *p)
 #endif
 extern "C" int mi355_sws_scale_frames_dev(mi355_sws_ctx *c, const mi355_sws_frame *d_frames, int nframes, void *stream)
 {
-    if (!c || !d_frames || nframes <= 0) return -1;
+    if (!c || !d_frames || nframes <= 0 || c->h.planar) return -1;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const SwsDev &h = c->h;
     DeviceScope on(c->device);
@@ -1074,6 +1282,27 @@ extern "C" int mi355_sws_scale_frames_dev(mi355_sws_ctx *c, const mi355_sws_fram
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+extern "C" int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *c, const mi355_sws_planar_frame *d_frames, int nframes, void *stream)
+{
+    if (!c || !d_frames || nframes <= 0 || !c->h.planar) return -1;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const SwsDev &h = c->h;
+    DeviceScope on(c->device);
+    const int k = sws_kernel(h);
+    const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
+    static_assert(sws_planar_waves(28, 16, TW / 2) == 8 && sws_planar_waves(40, 24, TW / 2) == 7 && sws_planar_waves(MAXL, MAXCP, TW / 2) == 5 &&
+                  sws_planar_waves(MAXL, MAXCP, TW) == 3,
+                  "workgroups per CU of the planar instances");
+#define MI355_PLANAR(L, C) \
+    if (h.hshift) hipLaunchKernelGGL((k_sws_planar<L, C, TW / 2>), grid, dim3(NT), 0, s, c->d, d_frames); \
+    else hipLaunchKernelGGL((k_sws_planar<L, C, TW>), grid, dim3(NT), 0, s, c->d, d_frames);
+    if (k == MI355_SWS_K_PLANAR_A) { MI355_PLANAR(28, 16) }
+    else if (k == MI355_SWS_K_PLANAR_B) { MI355_PLANAR(40, 24) }
+    else { MI355_PLANAR(MAXL, MAXCP) }
+#undef MI355_PLANAR
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 /* copy a host plane into a tightly pitched device plane */
 static bool plane_h2d(uint8_t *d, int dpitch, const uint8_t *h, int hstride, int wbytes, int rows, hipStream_t s)
 {
@@ -1085,7 +1314,7 @@ extern "C" int mi355_sws_scale(mi355_sws_ctx *c, const uint8_t *const src[3], co
     /* Every failure comes back as a negative value and leaves the context usable: the caller (contrib/libav/mi355_sws_glue.c) falls
      * back to the reference's function for that picture.  Strides must be positive and cover a line: sws_scale() itself also
      * takes negative ones (bottom-up pictures, vf_vflip) — not this entry point (-1), a 2-D copy has no negative pitch. */
-    if (!c || !src || !src_stride || !dst) return -1;
+    if (!c || !src || !src_stride || !dst || c->h.planar) return -1;
     const SwsDev &h = c->h;
     const int cw = h.chrSrcW, ch = h.chrSrcH;
     const int w[3] = { h.srcW, cw, cw };
@@ -1124,6 +1353,51 @@ extern "C" int mi355_sws_scale(mi355_sws_ctx *c, const uint8_t *const src[3], co
     if (hipMemcpy2DAsync(dst, dst_stride, c->d_dst, dpitch, out_w, h.dstH, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4; }
     if (hipStreamSynchronize(c->stream) != hipSuccess) return -4;
     return h.special ? h.srcH : h.dstH;
+}
+
+extern "C" int mi355_sws_scale_planar(mi355_sws_ctx *c, const uint8_t *const src[3], const int src_stride[3], uint8_t *const dst[3], const int dst_stride[3])
+{
+    /* as mi355_sws_scale: every failure is a negative value and leaves the context usable; positive strides that cover a line only */
+    if (!c || !src || !src_stride || !dst || !dst_stride || !c->h.planar) return -1;
+    const SwsDev &h = c->h;
+    const int cw = h.chrSrcW, ch = h.chrSrcH;
+    const int w[3] = { h.srcW, cw, cw }, ow[3] = { h.dstW, h.chrDstW, h.chrDstW }, oh[3] = { h.dstH, h.chrDstH, h.chrDstH };
+    for (int p = 0; p < 3; p++) if (!src[p] || src_stride[p] < w[p] || !dst[p] || dst_stride[p] < ow[p]) return -1;
+    DeviceScope on(c->device);
+    const int pw[3] = { (h.srcW + 15) & ~15, (cw + 15) & ~15, (cw + 15) & ~15 }, ph[3] = { h.srcH, ch, ch };
+    const int dp[3] = { (ow[0] + 15) & ~15, (ow[1] + 15) & ~15, (ow[2] + 15) & ~15 };
+    const size_t doff[3] = { 0, (size_t)dp[0] * oh[0], (size_t)dp[0] * oh[0] + (size_t)dp[1] * oh[1] };
+    if (!c->d_dst) {
+        uint8_t *ns[3] = { nullptr, nullptr, nullptr }, *nd = nullptr;
+        mi355_sws_planar_frame *nf = nullptr;
+        bool ok = true;
+        for (int p = 0; p < 3 && ok; p++) ok = hipMalloc(reinterpret_cast<void **>(&ns[p]), (size_t)pw[p] * ph[p] + 64) == hipSuccess;
+        ok = ok && hipMalloc(reinterpret_cast<void **>(&nd), doff[2] + (size_t)dp[2] * oh[2] + 64) == hipSuccess;
+        ok = ok && hipMalloc(reinterpret_cast<void **>(&nf), sizeof(mi355_sws_planar_frame)) == hipSuccess;
+        if (ok) {
+            mi355_sws_planar_frame f;
+            for (int p = 0; p < 3; p++) { f.src[p] = ns[p]; f.src_stride[p] = pw[p]; f.dst[p] = nd + doff[p]; f.dst_stride[p] = dp[p]; }
+            ok = hipMemcpy(nf, &f, sizeof(f), hipMemcpyHostToDevice) == hipSuccess;
+        }
+        if (!ok) {
+            for (int p = 0; p < 3; p++) if (ns[p]) (void)hipFree(ns[p]);
+            if (nd) (void)hipFree(nd);
+            if (nf) (void)hipFree(nf);
+            (void)hipGetLastError();
+            return -4;
+        }
+        for (int p = 0; p < 3; p++) c->d_src[p] = ns[p];
+        c->d_dst = nd; c->d_pframe = nf;
+    }
+    for (int p = 0; p < 3; p++)
+        if (!plane_h2d(c->d_src[p], pw[p], src[p], src_stride[p], w[p], ph[p], c->stream)) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4; }
+    if (mi355_sws_scale_planar_frames_dev(c, c->d_pframe, 1, c->stream) != 0) { (void)hipStreamSynchronize(c->stream); return -2; }
+    for (int p = 0; p < 3; p++)
+        if (hipMemcpy2DAsync(dst[p], dst_stride[p], c->d_dst + doff[p], dp[p], ow[p], oh[p], hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+            (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4;
+        }
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return -4;
+    return h.dstH;
 }
 
 /* ---- Tier-1 line entry points ------------------------------------------------------------------------------ */
