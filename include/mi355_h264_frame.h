@@ -328,6 +328,25 @@ int mi355_h264_deblock_dev(const mi355_h264_frame *d_frames, int nframes, int ma
  * not have leave at once, ~1 us per 1000 macroblock-row bands): `layouts` = MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED, or one of them. */
 int mi355_h264_deblock_layouts_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int layouts, void *stream);
 
+/* The kernel forms the two entry points above launch for a batch (the developer switches MI355_DEBLOCK_FORM / MI355_DEBLOCK_WAVES included):
+ * tiled pictures go through ONE launch of k_deblock_tiled (one wave per band) or, when the batch has fewer than two bands per SIMD,
+ * k_deblock_tiled2 (two waves per band); linear pictures through ceil(bands / linear_bands) launches of k_deblock (1) or
+ * k_deblock_bands<linear_bands>, chosen by a cost model over the CU count, the number of pictures and their shape. */
+typedef struct mi355_h264_deblock_plan_info {
+    int32_t tiled_waves;      /* 0: no tiled launch; 1: k_deblock_tiled; 2: k_deblock_tiled2 */
+    int32_t linear_bands;     /* 0: no linear launch; 1: k_deblock; 2 / 3 / 4 / 6: k_deblock_bands<n> (bands per workgroup) */
+    int32_t skip_tiled;       /* 1: the linear kernels leave tiled pictures to the tiled launch; 0: they filter them too */
+    int32_t linear_launches;  /* launches of the linear kernel (the last one partial when linear_bands does not divide the bands) */
+} mi355_h264_deblock_plan_info;
+/* cus: the CU count the rule is evaluated for; 0 = this device (needs the library initialised).  Returns 0, or -1 (arguments). */
+int mi355_h264_deblock_plan(int nframes, int max_mb_width, int max_mb_height, int layouts, int cus, mi355_h264_deblock_plan_info *plan);
+/* The loop filter through the forms named here, whatever the rule above would pick (tests; measurement): tiled_waves 1 / 2 runs
+ * k_deblock_tiled / k_deblock_tiled2 for the tiled pictures, linear_bands 1 / 2 / 3 / 4 / 6 the linear kernel for the linear pictures —
+ * and for the tiled ones too when tiled_waves = 0 (what MI355_DEBLOCK_FORM does).  Returns 0; -1 invalid arguments, an unknown form or
+ * a layout of `layouts` that no named form takes; -2, -3, -4 as mi355_h264_decode_frames. */
+int mi355_h264_deblock_form_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int layouts,
+                                int tiled_waves, int linear_bands, void *stream);
+
 /* Host helper (plain CPU bookkeeping, no sample arithmetic): write the intra schedule of one picture:
  * `list` (capacity mb_width*mb_height) receives the intra MB indices sorted by level, `level_start`
  * (capacity mb_width + 2*mb_height + 1) the offsets.  Levels are computed in int (no 8-bit limit: any

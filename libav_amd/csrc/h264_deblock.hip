@@ -1185,47 +1185,53 @@ void mi355::sync_words_release(hipStream_t st)
         }
 }
 
-extern "C" int mi355_h264_deblock_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, void *stream)
+/* The forms of the loop filter.  deblock_plan() is the rule mi355_h264_deblock_layouts_dev follows and mi355_h264_deblock_plan reports;
+ * deblock_launch() runs a plan (also one that mi355_h264_deblock_form_dev names). */
+namespace {
+struct DeblockForms {
+    int tiled_waves;     /* 0: no tiled launch; 1: k_deblock_tiled; 2: k_deblock_tiled2 */
+    int linear_bands;    /* 0: no linear launch; 1: k_deblock; 2 / 3 / 4 / 6: k_deblock_bands<n> */
+    int skip_tiled;      /* the linear kernels leave tiled pictures to the tiled launch */
+};
+/* MI355_DEBLOCK_FORM / MI355_DEBLOCK_WAVES (developer switches), read once per process */
+int deblock_form_pin()
 {
-    return mi355_h264_deblock_layouts_dev(d_frames, nframes, max_mb_width, max_mb_height, MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED, stream);
-}
-
-extern "C" int mi355_h264_deblock_layouts_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int layouts, void *stream)
-{
-    if (!mi355::bind() || !d_frames || nframes <= 0 || !(layouts & (MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED))) return -1;
-    const int nbands = (max_mb_height + 3) / 4, nsteps = max_mb_width + 6;
-    if (nbands <= 0 || max_mb_width <= 0) return -1;
-    /* Tiled pictures: ONE launch for all bands of all pictures (k_deblock_tiled).  Pictures with line strides (field pictures, 4:4:4 plane
-     * passes, callers that keep AVFrame-like planes): the forms of rounds 1-3, whose chunked row pieces suit that layout — a launch per
-     * band, or 2 to 6 bands per workgroup when the pictures are few.  MI355_DEBLOCK_FORM (developer switch) = 1 / 2 / 3 / 4 / 6 pins the
-     * latter's bands per workgroup and sends tiled pictures through it as well (what round 3 measured). */
     static const int force = std::getenv("MI355_DEBLOCK_FORM") ? std::atoi(std::getenv("MI355_DEBLOCK_FORM")) : 0;
-    hipStream_t st = (hipStream_t)stream;
-    const bool tiled_launch = (layouts & MI355_LAYOUTS_TILED) && force == 0;
-    if (tiled_launch) {
-        if ((long long)nframes * nbands > 0x7FFFFFFFLL) return -3;
-        const size_t words = 16 + (size_t)nframes * (size_t)nbands;
-        uint32_t *sync = mi355::sync_words(st, words);
-        if (!sync) return -4;
-        MI355_TRY(hipMemsetAsync(sync, 0, words * sizeof(uint32_t), st), -4);
-        /* few bands in all (fewer than two per SIMD): two waves per band, the edge phases beside everything else (MI355_DEBLOCK_WAVES = 1 / 2 pins the form) */
-        static const int pin = std::getenv("MI355_DEBLOCK_WAVES") ? std::atoi(std::getenv("MI355_DEBLOCK_WAVES")) : 0;
-        static int simds = 0;
-        if (!simds) {
-            hipDeviceProp_t prop;
-            int dev = 0;
-            simds = 4 * (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256);
-        }
-        const bool two = pin == 2 || (pin != 1 && (long long)nframes * nbands < 2LL * simds);
-        if (two) hipLaunchKernelGGL(k_deblock_tiled2, dim3((unsigned)(nframes * nbands)), dim3(128), 0, st, d_frames, nframes, nbands, sync);
-        else hipLaunchKernelGGL(k_deblock_tiled, dim3((unsigned)(nframes * nbands)), dim3(64), 0, st, d_frames, nframes, nbands, sync);
-        if (!(layouts & MI355_LAYOUTS_LINEAR)) return hipGetLastError() == hipSuccess ? 0 : -2;
-    }
+    return force;
+}
+int deblock_waves_pin()
+{
+    static const int pin = std::getenv("MI355_DEBLOCK_WAVES") ? std::atoi(std::getenv("MI355_DEBLOCK_WAVES")) : 0;
+    return pin;
+}
+int device_cus()
+{
     static int cus = 0;
     if (!cus) {
         hipDeviceProp_t prop;
         int dev = 0;
         cus = hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    return cus;
+}
+bool linear_form(int kw) { return kw == 1 || kw == 2 || kw == 3 || kw == 4 || kw == 6; }
+
+DeblockForms deblock_plan(int nframes, int max_mb_width, int max_mb_height, int layouts, int cus)
+{
+    const int nbands = (max_mb_height + 3) / 4, nsteps = max_mb_width + 6;
+    /* Tiled pictures: ONE launch for all bands of all pictures (k_deblock_tiled).  Pictures with line strides (field pictures, 4:4:4 plane
+     * passes, callers that keep AVFrame-like planes): the forms of rounds 1-3, whose chunked row pieces suit that layout — a launch per
+     * band, or 2 to 6 bands per workgroup when the pictures are few.  MI355_DEBLOCK_FORM (developer switch) = 1 / 2 / 3 / 4 / 6 pins the
+     * latter's bands per workgroup and sends tiled pictures through it as well (what round 3 measured). */
+    const int force = deblock_form_pin();
+    DeblockForms p{ 0, 0, 0 };
+    const bool tiled_launch = (layouts & MI355_LAYOUTS_TILED) && force == 0;
+    if (tiled_launch) {
+        /* few bands in all (fewer than two per SIMD): two waves per band, the edge phases beside everything else (MI355_DEBLOCK_WAVES = 1 / 2 pins the form) */
+        const int pin = deblock_waves_pin();
+        const long long simds = 4LL * cus;
+        p.tiled_waves = pin == 2 || (pin != 1 && (long long)nframes * nbands < 2LL * simds) ? 2 : 1;
+        if (!(layouts & MI355_LAYOUTS_LINEAR)) return p;
     }
     /* sequential steps a form needs: launches x (steps of one walk), times the rounds it takes to get all pictures through the
      * CUs (8 band tiles fit a CU); a step of the multi-band form is dearer by its barrier (measured: 2.9 against 2.3 us) */
@@ -1239,17 +1245,77 @@ extern "C" int mi355_h264_deblock_layouts_dev(const mi355_h264_frame *d_frames, 
         const double cost = rounds * ((nbands + kw - 1) / kw) * (nsteps + DEBLOCK_LAG * (kw - 1)) * (kw > 1 ? 1.25 : 1.0);
         if (i == 0 || cost < best_cost) { best = kw; best_cost = cost; }
     }
-    if (force == 1 || force == 2 || force == 3 || force == 4 || force == 6) best = force;
-    const int skip = tiled_launch ? 1 : 0;
-    for (int band = 0; band < nbands; band += best) {
+    if (linear_form(force)) best = force;
+    p.linear_bands = best;
+    p.skip_tiled = tiled_launch ? 1 : 0;
+    return p;
+}
+
+int deblock_launch(const mi355_h264_frame *d_frames, int nframes, int nbands, const DeblockForms &p, hipStream_t st)
+{
+    if (p.tiled_waves) {
+        if ((long long)nframes * nbands > 0x7FFFFFFFLL) return -3;
+        const size_t words = 16 + (size_t)nframes * (size_t)nbands;
+        uint32_t *sync = mi355::sync_words(st, words);
+        if (!sync) return -4;
+        MI355_TRY(hipMemsetAsync(sync, 0, words * sizeof(uint32_t), st), -4);
+        if (p.tiled_waves == 2) hipLaunchKernelGGL(k_deblock_tiled2, dim3((unsigned)(nframes * nbands)), dim3(128), 0, st, d_frames, nframes, nbands, sync);
+        else hipLaunchKernelGGL(k_deblock_tiled, dim3((unsigned)(nframes * nbands)), dim3(64), 0, st, d_frames, nframes, nbands, sync);
+    }
+    for (int band = 0; p.linear_bands && band < nbands; band += p.linear_bands) {
         const dim3 grid((unsigned)nframes);
-        switch (best) {
-        case 2: hipLaunchKernelGGL(k_deblock_bands<2>, grid, dim3(128), 0, st, d_frames, band, skip); break;
-        case 3: hipLaunchKernelGGL(k_deblock_bands<3>, grid, dim3(192), 0, st, d_frames, band, skip); break;
-        case 4: hipLaunchKernelGGL(k_deblock_bands<4>, grid, dim3(256), 0, st, d_frames, band, skip); break;
-        case 6: hipLaunchKernelGGL(k_deblock_bands<6>, grid, dim3(384), 0, st, d_frames, band, skip); break;
-        default: hipLaunchKernelGGL(k_deblock, grid, dim3(64), 0, st, d_frames, band, skip); break;
+        switch (p.linear_bands) {
+        case 2: hipLaunchKernelGGL(k_deblock_bands<2>, grid, dim3(128), 0, st, d_frames, band, p.skip_tiled); break;
+        case 3: hipLaunchKernelGGL(k_deblock_bands<3>, grid, dim3(192), 0, st, d_frames, band, p.skip_tiled); break;
+        case 4: hipLaunchKernelGGL(k_deblock_bands<4>, grid, dim3(256), 0, st, d_frames, band, p.skip_tiled); break;
+        case 6: hipLaunchKernelGGL(k_deblock_bands<6>, grid, dim3(384), 0, st, d_frames, band, p.skip_tiled); break;
+        default: hipLaunchKernelGGL(k_deblock, grid, dim3(64), 0, st, d_frames, band, p.skip_tiled); break;
         }
     }
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+}  // namespace
+
+extern "C" int mi355_h264_deblock_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, void *stream)
+{
+    return mi355_h264_deblock_layouts_dev(d_frames, nframes, max_mb_width, max_mb_height, MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED, stream);
+}
+
+extern "C" int mi355_h264_deblock_layouts_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int layouts, void *stream)
+{
+    if (!mi355::bind() || !d_frames || nframes <= 0 || !(layouts & (MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED))) return -1;
+    const int nbands = (max_mb_height + 3) / 4;
+    if (nbands <= 0 || max_mb_width <= 0) return -1;
+    return deblock_launch(d_frames, nframes, nbands, deblock_plan(nframes, max_mb_width, max_mb_height, layouts, device_cus()), (hipStream_t)stream);
+}
+
+extern "C" int mi355_h264_deblock_plan(int nframes, int max_mb_width, int max_mb_height, int layouts, int cus, mi355_h264_deblock_plan_info *plan)
+{
+    if (!plan || nframes <= 0 || max_mb_width <= 0 || max_mb_height <= 0 || cus < 0 || !(layouts & (MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED))) return -1;
+    if (cus == 0) {
+        if (!mi355::bind()) return -1;
+        cus = device_cus();
+    }
+    const DeblockForms p = deblock_plan(nframes, max_mb_width, max_mb_height, layouts, cus);
+    const int nbands = (max_mb_height + 3) / 4;
+    plan->tiled_waves = p.tiled_waves;
+    plan->linear_bands = p.linear_bands;
+    plan->skip_tiled = p.skip_tiled;
+    plan->linear_launches = p.linear_bands ? (nbands + p.linear_bands - 1) / p.linear_bands : 0;
+    return 0;
+}
+
+extern "C" int mi355_h264_deblock_form_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int layouts, int tiled_waves,
+                                           int linear_bands, void *stream)
+{
+    if (!mi355::bind() || !d_frames || nframes <= 0 || !(layouts & (MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED))) return -1;
+    const int nbands = (max_mb_height + 3) / 4;
+    if (nbands <= 0 || max_mb_width <= 0) return -1;
+    if (tiled_waves < 0 || tiled_waves > 2 || (linear_bands != 0 && !linear_form(linear_bands))) return -1;
+    /* every layout of the batch must have a kernel that takes it: tiled pictures the tiled launch or linear kernels that do not skip them */
+    if ((layouts & MI355_LAYOUTS_LINEAR) && !linear_bands) return -1;
+    if ((layouts & MI355_LAYOUTS_TILED) && !tiled_waves && !linear_bands) return -1;
+    if (tiled_waves && !(layouts & MI355_LAYOUTS_TILED)) return -1;
+    const DeblockForms p{ tiled_waves, linear_bands, tiled_waves ? 1 : 0 };
+    return deblock_launch(d_frames, nframes, nbands, p, (hipStream_t)stream);
 }

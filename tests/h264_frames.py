@@ -164,9 +164,27 @@ def _avail_masks(top, left, topleft, topright):
     return tl, tr
 
 
+ALPHA = [0] * 16 + [4, 4, 5, 6, 7, 8, 9, 10, 12, 13, 15, 17, 20, 22, 25, 28, 32, 36, 40, 45, 50, 56, 63, 71, 80, 90, 101, 113, 127, 144, 162,
+                    182, 203, 226, 255, 255]
+BETA = [0] * 16 + [2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13, 14, 14, 15, 15, 16, 16, 17, 17, 18, 18]
+
+
 def _ref_plane(r, h, w, kind):
     if kind == "noise":
         return r.u8((h, w))
+    if kind == "steps":
+        # flat 4x4 blocks (2x2 in chroma planes: w, h < the luma's) whose steps to the neighbours lie around alpha(index) of a random
+        # index; a third of the blocks with a ramp inside around beta(index): the filter's decisions go both ways
+        b = 4
+        bh, bw = (h + b - 1) // b, (w + b - 1) // b
+        idx = r.randint(16, 51, (bh, bw))
+        step = (np.array(ALPHA)[idx] * (0.5 + r.uniform((bh, bw)))).astype(np.int64)
+        sign = np.where(r.uniform((bh, bw)) < 0.5, -1, 1)
+        val = 128 + sign * (step // 2) + r.randint(-3, 3, (bh, bw))
+        ramp = np.where(r.uniform((bh, bw)) < 0.33, (np.array(BETA)[idx] * (0.5 + r.uniform((bh, bw)))).astype(np.int64), 0)
+        yy, xx = np.mgrid[0:h, 0:w]
+        a = val[yy // b, xx // b] + ramp[yy // b, xx // b] * (np.where((yy // b + xx // b) % 2 == 0, xx, yy) % b) // 2
+        return np.clip(a, 0, 255).astype(np.uint8)
     # smooth: gentle gradient + small noise, so the loop-filter thresholds are actually met
     yy, xx = np.mgrid[0:h, 0:w]
     base = r.randint(60, 180)
@@ -175,8 +193,14 @@ def _ref_plane(r, h, w, kind):
 
 
 def synth_frames(nframes, mb_w, mb_h, seed=0x264, nrefs=4, mix="p16", intra_frac=0.0, bframes=False,
-                 weighted=0, dct8_frac=0.0, mv_range=64, offsets=False, pcm_frac=0.0, refs="noise", coef_b=24, coef_clip=2047):
-    """mix: 'p16' (all 16x16), 'mixed' (all partition shapes).  Returns a FrameSet."""
+                 weighted=0, dct8_frac=0.0, mv_range=64, offsets=False, pcm_frac=0.0, refs="noise", coef_b=24, coef_clip=2047,
+                 qp_range=(20, 40), slices=1, chroma_offsets=False, full_sample=False, near_mv=0.0, cbp0_frac=0.0):
+    """mix: 'p16' (all 16x16), 'mixed' (all partition shapes).  Returns a FrameSet.
+    Loop-filter content (all off by default; see _filter_content): qp_range = the QPs drawn; slices = raster-run slices per picture, each
+    with its own disable_deblocking_filter_idc and alpha / beta offsets; chroma_offsets: a Cb / Cr chroma_qp_index_offset pair per picture;
+    refs='steps': references of flat 4x4 blocks with steps around the filter's thresholds; full_sample: whole-sample vectors;
+    near_mv: the share of partitions whose vectors sit 0, 3 or 4 quarter samples from a neighbour's (B pictures: also the lists crossed);
+    cbp0_frac: the share of inter macroblocks without residual."""
     fs = FrameSet(nframes, mb_w, mb_h, nrefs)
     r = SplitMix64(seed)
     nmb = mb_w * mb_h
@@ -208,7 +232,7 @@ def synth_frames(nframes, mb_w, mb_h, seed=0x264, nrefs=4, mix="p16", intra_frac
         for m in range(nmb):
             mx, my = m % mb_w, m // mb_w
             rec = fs.mb[f, m]
-            rec["qp"] = qp = r.randint(20, 40)
+            rec["qp"] = qp = r.randint(*qp_range)
             rec["alpha"], rec["beta"] = a_off, b_off
             rec["flags"] = (F_LEFT if mx else 0) | (F_TOP if my else 0) | (F_WEIGHTED if weighted else 0)
             qpc = CHROMA_QP[qp]
@@ -383,7 +407,149 @@ def synth_frames(nframes, mb_w, mb_h, seed=0x264, nrefs=4, mix="p16", intra_frac
             rec["cbp"] = cbp
             rec["nnz_mask"] = mask
         fs.max_intra_level = max(fs.max_intra_level, intra_schedule(fs, f))
+    if slices > 1 or chroma_offsets or full_sample or near_mv or cbp0_frac:
+        _filter_content(fs, SplitMix64(seed ^ 0x5EB10C), slices, chroma_offsets, full_sample, near_mv, cbp0_frac)
     return fs
+
+
+def chroma_qp_table(off):
+    """pps->chroma_qp_table[t] for chroma_qp_index_offset `off` (Table 8-15 at clip(qp + off, 0, 51))"""
+    return [CHROMA_QP[min(max(q + off, 0), 51)] for q in range(52)]
+
+
+def _partitions(rec):
+    """the inter partitions of a macroblock record: (raster 4x4 blocks, quadrants, lists used, whole quadrants) in decoding order"""
+    t = int(rec["mb_type"])
+    rows = lambda y0, y1, x0, x1: [x + 4 * y for y in range(y0, y1) for x in range(x0, x1)]
+    uses = lambda k: [l for l in range(2) if t & (P0L0 << (2 * l + k))]
+    if t & T16x16:
+        return [(rows(0, 4, 0, 4), [0, 1, 2, 3], uses(0), True)]
+    if t & T16x8:
+        return [(rows(0, 2, 0, 4), [0, 1], uses(0), True), (rows(2, 4, 0, 4), [2, 3], uses(1), True)]
+    if t & T8x16:
+        return [(rows(0, 4, 0, 2), [0, 2], uses(0), True), (rows(0, 4, 2, 4), [1, 3], uses(1), True)]
+    out = []
+    for q in range(4):
+        sub = int(rec["sub"][q])
+        qx, qy = 2 * (q & 1), 2 * (q >> 1)
+        parts = {0: [(0, 0, 2, 2)], 1: [(0, 0, 2, 1), (0, 1, 2, 1)], 2: [(0, 0, 1, 2), (1, 0, 1, 2)],
+                 3: [(0, 0, 1, 1), (1, 0, 1, 1), (0, 1, 1, 1), (1, 1, 1, 1)]}[sub & 3]
+        ls = [l for l in range(2) if sub & (0x10 << l)]
+        for i, (px, py, pw, ph) in enumerate(parts):
+            out.append((rows(qy + py, qy + py + ph, qx + px, qx + px + pw), [q], ls, i == 0 and (sub & 3) == 0))
+    return out
+
+
+def _filter_content(fs, r, nslices, chroma_offsets, full_sample, near_mv, cbp0_frac):
+    """The loop filter's hard cases on top of synth_frames' pictures (drawn from their own generator, so the pictures without these options
+    stay as they were):
+      - raster-run slices, each with disable_deblocking_filter_idc 0 / 1 / 2 (1: MI355_MBF_NO_DEBLOCK; 2: MI355_MBF_FILTER_OWN_SLICE and
+        LEFT_EDGE / TOP_EDGE cleared towards other slices) and its own alpha / beta offsets over -12..12;
+      - one Cb / Cr chroma_qp_index_offset pair per picture (Cb != Cr), the same table in every slice of it (the reference refuses a PPS
+        change between slices, h264_slice.c:1743), qpc and the chroma DC multipliers to match;
+      - whole-sample vectors, and vectors 0, 3 or 4 quarter samples in x or y from the neighbouring block's across a partition edge, with
+        the same or another reference; in B pictures the neighbour's two lists crossed (the bS rule's crossed-pair comparison);
+      - inter macroblocks without residual (cbp 0, no 8x8 transform)."""
+    nmb = fs.mb_w * fs.mb_h
+    fs.chroma_offset = np.zeros((fs.F, 2), np.int64)
+    if nslices > 1:
+        sl = np.zeros((fs.F, nslices), SLICE_DT)
+        sl[:] = fs.slices[:, :1]
+        fs.slices = sl
+    deltas = [(0, 0), (3, 0), (-3, 0), (4, 0), (-4, 0), (0, 3), (0, -3), (0, 4), (0, -4), (2, 3), (-3, -4)]
+    for f in range(fs.F):
+        mb = fs.mb[f]
+        slc = fs.slices[f]
+        if chroma_offsets:
+            cb = r.randint(-12, 12)
+            cr = r.randint(-12, 11)
+            cr += cr >= cb
+            fs.chroma_offset[f] = (cb, cr)
+        tabs = [chroma_qp_table(int(o)) for o in fs.chroma_offset[f]]
+        slc["chroma_qp_table"][:, 0] = tabs[0]
+        slc["chroma_qp_table"][:, 1] = tabs[1]
+        # the chroma QPs and DC multipliers of every macroblock follow its QP through the picture's tables
+        for m in range(nmb):
+            rec = mb[m]
+            qp = int(rec["qp"])
+            rec["qpc"] = (tabs[0][qp], tabs[1][qp])
+            rec["dc_qmul"] = (dc_qmul(qp), dc_qmul(tabs[0][qp]), dc_qmul(tabs[1][qp]))
+        # slices: raster runs
+        sid = np.zeros(nmb, np.int64)
+        if nslices > 1 and nmb > 1:
+            cuts = sorted(set(int(c) for c in r.randint(1, nmb - 1, nslices - 1)))
+            for c in cuts:
+                sid[c:] += 1
+            for s in range(int(sid[-1]) + 1):
+                idc = [0, 0, 0, 1, 2, 2][r.randint(0, 5)]
+                a_off, b_off = 2 * r.randint(-6, 6), 2 * r.randint(-6, 6)
+                for m in np.nonzero(sid == s)[0]:
+                    rec = mb[m]
+                    mx, my = m % fs.mb_w, m // fs.mb_w
+                    left, top = mx > 0, my > 0
+                    if idc == 2:
+                        left = left and sid[m - 1] == s
+                        top = top and sid[m - fs.mb_w] == s
+                    rec["slice_id"] = s
+                    rec["alpha"], rec["beta"] = a_off, b_off
+                    rec["flags"] = (int(rec["flags"]) & F_WEIGHTED) | (F_LEFT if left else 0) | (F_TOP if top else 0) | \
+                        (F_NODB if idc == 1 else 0) | (0x80 if idc == 2 else 0)
+        inter = (mb["mb_type"] & 7) == 0
+        if cbp0_frac:
+            pick = inter & (r.uniform(nmb) < cbp0_frac)
+            mb["cbp"][pick] = 0
+            mb["nnz_mask"][pick] = 0
+            fs.coef[f][pick] = 0
+            # an inter macroblock without luma residual codes no transform_size_8x8_flag
+            mb["mb_type"][inter & ((mb["cbp"] & 15) == 0)] &= ~np.uint32(DCT8)
+        if full_sample:
+            fs.mv[:, f] = (fs.mv[:, f] >> 2) << 2
+        if near_mv:
+            sl0 = slc[0]
+            nrefs = fs.nrefs
+            ident = lambda l, ri: int(sl0["ref_slot"][l][ri]) if ri >= 0 else -1
+            for m in np.nonzero(inter)[0]:
+                rec = mb[m]
+                mx, my = m % fs.mb_w, m // fs.mb_w
+                for blocks, quads, lists, whole in _partitions(rec):
+                    if not lists or r.uniform() >= near_mv:
+                        continue
+                    x4, y4 = blocks[0] % 4, blocks[0] // 4
+                    cand = []
+                    if x4 > 0:
+                        cand.append((m, x4 - 1 + 4 * y4))
+                    elif mx > 0 and inter[m - 1]:
+                        cand.append((m - 1, 3 + 4 * y4))
+                    if y4 > 0:
+                        cand.append((m, x4 + 4 * (y4 - 1)))
+                    elif my > 0 and inter[m - fs.mb_w]:
+                        cand.append((m - fs.mb_w, x4 + 12))
+                    if not cand:
+                        continue
+                    nm, nb = cand[r.randint(0, len(cand) - 1)]
+                    nq = (nb % 4 >> 1) + 2 * (nb // 4 >> 1)
+                    nref = [int(mb[nm]["ref_idx"][l][nq]) for l in range(2)]
+                    cross = len(lists) == 2 and nref[0] >= 0 and nref[1] >= 0 and r.uniform() < 0.5
+                    for l in lists:
+                        src = 1 - l if cross else l
+                        if nref[src] < 0:
+                            continue
+                        dx, dy = deltas[r.randint(0, len(deltas) - 1)]
+                        mv = fs.mv[src, f, nm, nb].astype(np.int64) + (dx, dy)
+                        fs.mv[l, f, m, blocks] = mv.astype(np.int16)
+                        if whole and r.uniform() < 0.75:
+                            # the neighbour's picture, through this list's own reference indices
+                            want = ident(src, nref[src])
+                            hit = [i for i in range(nrefs) if ident(l, i) == want]
+                            if hit:
+                                for q in quads:
+                                    rec["ref_idx"][l][q] = hit[0]
+        for m in np.nonzero(inter)[0]:
+            rec = mb[m]
+            for l in range(2):
+                for q in range(4):
+                    ri = int(rec["ref_idx"][l][q])
+                    rec["i4mode"][4 * l + q] = np.uint8(slc[0]["ref_slot"][l][ri]).astype(np.int8) if ri >= 0 else -1
 
 
 def intra_schedule(fs, f):
@@ -495,6 +661,15 @@ def widen_records(fs, sh, idc=1):
     mb = fs.mb.copy()
     mb["qp"] += 6 * sh
     mb["qpc"] += 6 * sh
+    off = getattr(fs, "chroma_offset", None)
+    if sh and off is not None and off.any():
+        # a chroma_qp_index_offset: above 8 bits qp + offset clips at -QpBdOffsetC, not at 0 (Table 8-15 is the identity below 30), so where
+        # it is negative the chroma QP is not the 8-bit one raised; the chroma DC multipliers follow it (the DC levels carry << sh already)
+        for p in range(2):
+            x = np.clip(fs.mb["qp"].astype(np.int64) + off[:, p:p + 1], -6 * sh, 51)
+            qc = np.where(x < 0, x, np.array(CHROMA_QP)[np.clip(x, 0, 51)]) + 6 * sh
+            mb["qpc"][..., p] = qc
+            mb["dc_qmul"][..., 1 + p] = (np.array(DQ0)[qc % 6] * 16) << (qc // 6 + 2) >> sh
     pcm = (fs.mb["mb_type"] & 4) != 0
     if idc == 1:
         coef = fs.coef.astype(np.int32) << sh
@@ -713,6 +888,33 @@ class DeviceFrames:
                     np.ascontiguousarray(raw[:, ysz + csz:].reshape(n, self.hc, cs)[:, :, :fs.W]).view(np.uint16)]
         return [raw[:, :ysz].reshape(n, fs.H, ys)[:, :, :fs.W], raw[:, ysz:ysz + csz].reshape(n, fs.H // 2, cs)[:, :, :fs.W // 2],
                 raw[:, ysz + csz:].reshape(n, fs.H // 2, cs)[:, :, :fs.W // 2]]
+
+    def put(self, base, planes):
+        """the inverse of fetch for 8-bit surfaces: picture f of surface `base` (recon or dst) = picture f % fs.F of `planes`
+        (the copies of a replicated set on the device)"""
+        fs = self.fs
+        assert self.px == 1
+        G = fs.F
+        raw = np.zeros((G, self.fsz), np.uint8)
+        for g in range(G):
+            y, cb, cr = planes[0][g], planes[1][g], planes[2][g]
+            if self.tiled:
+                ysz = fs.mb_h * self.tys
+                ty, tc = tile_planes(y, cb, cr)
+                raw[g, :ysz].reshape(fs.mb_h, self.tys)[:, :fs.mb_w * 256] = ty.reshape(fs.mb_h, -1)
+                raw[g, ysz:].reshape(fs.mb_h, self.tcs)[:, :fs.mb_w * 128] = tc.reshape(fs.mb_h, -1)
+                continue
+            ys, cs = fs.W + self.pad, fs.W // 2 + self.pad // 2
+            ysz, csz = fs.H * ys, self.hc * cs
+            raw[g, :ysz].reshape(fs.H, ys)[:, :fs.W] = y
+            raw[g, ysz:ysz + csz].reshape(self.hc, cs)[:, :fs.W // 2] = cb
+            raw[g, ysz + csz:].reshape(self.hc, cs)[:, :fs.W // 2] = cr
+        self.lib.mi355_memcpy_h2d(base, raw.ctypes.data, raw.nbytes)
+        done = G
+        while done < self.F:
+            n = min(done, self.F - done)
+            self.lib.mi355_memcpy_d2d(base + done * self.fsz, base, n * self.fsz)
+            done += n
 
     def decode(self, stream=None, per_level=True):
         """per_level: intra passes sized by the per-level widths (mi355_h264_decode_frames_levels_dev); otherwise by the
