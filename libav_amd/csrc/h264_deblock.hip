@@ -6,7 +6,7 @@
  */
 #include <cstdlib>
 #include <vector>
-#include "h264_frame_dev.h"
+#include "h264_deblock_dev.h"
 
 using namespace mi355;
 
@@ -18,55 +18,6 @@ __device__ unsigned long long g_prof[16];
 #else
 #define PROF_MARK(i) do { } while (0)
 #endif
-
-/* ------------------------------------------------------------------------- */
-/* deblocking                                                                   */
-/* ------------------------------------------------------------------------- */
-/* Tables 8-16 / 8-17 of the standard (alpha', beta', tC0 for bS 1..3); indices clamp to 0..51,
- * which is what the reference's 52-entry guard bands implement (h264_loopfilter.c:41-101) */
-__device__ const uint8_t k_alpha[52] = {
-    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 4, 4, 5, 6, 7, 8, 9, 10, 12, 13, 15, 17, 20, 22, 25, 28,
-    32, 36, 40, 45, 50, 56, 63, 71, 80, 90, 101, 113, 127, 144, 162, 182, 203, 226, 255, 255 };
-__device__ const uint8_t k_beta[52] = {
-    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 6, 6, 7, 7, 8, 8,
-    9, 9, 10, 10, 11, 11, 12, 12, 13, 13, 14, 14, 15, 15, 16, 16, 17, 17, 18, 18 };
-__device__ const uint8_t k_tc0[52][3] = {
-    {0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},
-    {0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,1},{0,0,1},{0,0,1},{0,0,1},{0,1,1},{0,1,1},{1,1,1},{1,1,1},{1,1,1},
-    {1,1,1},{1,1,2},{1,1,2},{1,1,2},{1,1,2},{1,2,3},{1,2,3},{2,2,3},{2,2,4},{2,3,4},{2,3,4},{3,3,5},{3,4,6},
-    {3,4,6},{4,5,7},{4,5,8},{4,6,9},{5,7,10},{6,8,11},{6,8,13},{7,10,14},{8,11,16},{9,12,18},{10,13,20},
-    {11,15,23},{13,17,25} };
-
-/* motion of one 4x4 block as the loop filter sees it: picture identity per list (-1 = unused, what
- * ref_cache holds after the ref2frm mapping, h264_slice.c:2023-2029) and the packed mv words */
-struct BlkMotion {
-    int ref[2];
-    uint32_t mv[2];
-};
-__device__ __forceinline__ bool mv_far(uint32_t a, uint32_t b)
-{
-    return iabs((int16_t)(a & 0xFFFF) - (int16_t)(b & 0xFFFF)) >= 4 || iabs((int16_t)(a >> 16) - (int16_t)(b >> 16)) >= 4;
-}
-/* check_mv, h264_loopfilter.c:442-470, frame macroblocks (mvy_limit 4) */
-__device__ inline int check_mv(const BlkMotion &p, const BlkMotion &q, int list_count)
-{
-    bool v = p.ref[0] != q.ref[0];
-    if (!v && p.ref[0] != -1) v = mv_far(p.mv[0], q.mv[0]);
-    if (list_count == 2) {
-        if (!v) v = p.ref[1] != q.ref[1] || mv_far(p.mv[1], q.mv[1]);
-        if (v) {
-            if (p.ref[0] != q.ref[1] || p.ref[1] != q.ref[0]) return 1;
-            return mv_far(p.mv[0], q.mv[1]) || mv_far(p.mv[1], q.mv[0]);
-        }
-    }
-    return v;
-}
-__device__ __forceinline__ int ref_identity(const mi355_h264_mb &m, int list, int x4, int y4)
-{
-    if (m.mb_type & MI355_MB_INTRA) return -1;
-    const int r = m.u.inter.ref_pic[list][(x4 >> 1) + 2 * (y4 >> 1)];
-    return r == 0xFF ? -1 : r;
-}
 
 /* One wavefront deblocks a band of four macroblock rows of one picture, walking left to right:
  * lanes 16g..16g+15 own row 4*band+g and at step t work on macroblock x = t - 2g, so the
@@ -265,6 +216,63 @@ __device__ __forceinline__ bool chroma_row_edge(uint32_t &P, uint32_t &Q, int bs
     return true;
 }
 
+/* alpha / beta of a `parm` word 0 (alpha | beta << 8); byte e of a packed word */
+__device__ __forceinline__ int ab_alpha(uint32_t w) { return (int)(w & 0xFF); }
+__device__ __forceinline__ int ab_beta(uint32_t w) { return (int)((w >> 8) & 0xFF); }
+__device__ __forceinline__ int byte_of(uint32_t w, int e) { return (int)((w >> (8 * e)) & 0xFF); }
+
+/* Vertical edges of one luma row (rowp: its 16 samples in LDS, leftp: the four left of them, the previous macroblock's last
+ * columns) and one chroma row (crowp: 8 samples, cleftp: the four left of them), held as dwords.  Each edge evaluates the
+ * filterSamplesFlag conditions first and leaves when no line of the wave passes (the reference's own per-line `continue`,
+ * h264dsp_template.c:117-121, taken at wave granularity), and only what changed is written back: bit-identical either way.
+ * ab_*: alpha | beta << 8, tc*: tc0 per edge (bytes), of the left (l) and the inner (i) edges; c*: chroma */
+__device__ __forceinline__ void vertical_edges(uint8_t *rowp, uint8_t *leftp, uint8_t *crowp, uint8_t *cleftp, uint32_t bsw0, uint32_t bsc0,
+                                               uint32_t ab_l, uint32_t ab_i, uint32_t tcl0, uint32_t tci0, uint32_t cab_l, uint32_t cab_i, uint32_t ccl0, uint32_t cci0)
+{
+    const uint4 own = lds16(rowp);
+    const uint2 cown = *reinterpret_cast<const uint2 *>(crowp);
+    uint32_t wl = *reinterpret_cast<const uint32_t *>(leftp), w0 = own.x, w1 = own.y, w2 = own.z, w3 = own.w;
+    uint32_t cl = *reinterpret_cast<const uint32_t *>(cleftp), cw0 = cown.x, cw1 = cown.y;      /* columns -4..-1, 0..3, 4..7 */
+    const bool c0 = luma_row_edge<true>(wl, w0, byte_of(bsw0, 0), ab_alpha(ab_l), ab_beta(ab_l), byte_of(tcl0, 0));
+    const bool c1 = luma_row_edge<false>(w0, w1, byte_of(bsw0, 1), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci0, 1));
+    const bool c2 = luma_row_edge<false>(w1, w2, byte_of(bsw0, 2), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci0, 2));
+    const bool c3 = luma_row_edge<false>(w2, w3, byte_of(bsw0, 3), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci0, 3));
+    if (c0) *reinterpret_cast<uint32_t *>(leftp) = wl;
+    if (c0 || c1 || c2 || c3) lds16(rowp, make_uint4(w0, w1, w2, w3));
+    const bool d0 = chroma_row_edge(cl, cw0, byte_of(bsc0, 0), ab_alpha(cab_l), ab_beta(cab_l), byte_of(ccl0, 0));
+    const bool d1 = chroma_row_edge(cw0, cw1, byte_of(bsc0, 2), ab_alpha(cab_i), ab_beta(cab_i), byte_of(cci0, 2));
+    if (d0) *reinterpret_cast<uint32_t *>(cleftp) = cl;
+    if (d0 || d1) *reinterpret_cast<mi355_u32x2 *>(crowp) = mi355_u32x2{ cw0, cw1 };
+}
+/* What a lane fetches for one macroblock ahead of time (records and vectors: never written by the filter) */
+struct Pre {
+    MbInfo h, ht;
+    uint32_t p0[2], q0[2], p1[2], q1[2];
+};
+/* Side information never passes through LDS: the record at byte offset roff, its top neighbour's at toff, and the four vectors
+ * of this lane's boundary-strength role (o4: their byte offsets o_p0, o_q0, o_p1, o_q1 from the macroblock's first vector,
+ * 16-byte aligned) straight from memory.  Unpredicated loads from clamped addresses, so the compiler's wait counts stay exact:
+ * a neighbour that does not exist (x_left = 0: no left neighbour; no_top != 0) reads this macroblock's own vector (its strength
+ * is masked) */
+template <bool TWO_LISTS>
+__device__ __forceinline__ void mb_prefetch(Pre &p, const uint8_t *rec_base, const uint8_t *mv_base0, const uint8_t *mv_base1, uint32_t roff, uint32_t toff,
+                                            const uint32_t *o4, bool outer, int x_left, uint32_t no_top)
+{
+    p.h = mb_info_load<true>(rec_base, roff);
+    p.ht = mb_info_load<false>(rec_base, toff);
+    const mi355_u32x4 o = *reinterpret_cast<const mi355_u32x4 *>(o4);
+    const uint32_t a_p0 = roff + o[0], a_p1 = roff + o[2];
+    const uint32_t a_q0 = x_left > 0 || !outer ? roff + o[1] : a_p0;
+    const uint32_t a_q1 = !no_top || !outer ? roff + o[3] : a_p1;
+    p.p0[0] = *reinterpret_cast<const uint32_t *>(mv_base0 + a_p0); p.q0[0] = *reinterpret_cast<const uint32_t *>(mv_base0 + a_q0);
+    p.p1[0] = *reinterpret_cast<const uint32_t *>(mv_base0 + a_p1); p.q1[0] = *reinterpret_cast<const uint32_t *>(mv_base0 + a_q1);
+    p.p0[1] = p.q0[1] = p.p1[1] = p.q1[1] = 0;           /* constants without list 1 (no register, no write) */
+    if (TWO_LISTS) {
+        p.p0[1] = *reinterpret_cast<const uint32_t *>(mv_base1 + a_p0); p.q0[1] = *reinterpret_cast<const uint32_t *>(mv_base1 + a_q0);
+        p.p1[1] = *reinterpret_cast<const uint32_t *>(mv_base1 + a_p1); p.q1[1] = *reinterpret_cast<const uint32_t *>(mv_base1 + a_q1);
+    }
+}
+
 /* KW: waves per workgroup.  1 = a workgroup is one wave and one band (the throughput form: one launch per band, thousands of
  * pictures per launch).  KW > 1 = the small-batch form: KW waves of a workgroup walk KW consecutive bands of one picture
  * in the same launch, wave w starting DEBLOCK_LAG steps after wave w - 1, all waves meeting at a workgroup barrier after
@@ -311,28 +319,12 @@ __device__ __forceinline__ void deblock_band(DeblockLds &s, const mi355_h264_fra
     const uint8_t *const rec_base = reinterpret_cast<const uint8_t *>(mi355_global(fr.mb));
     const uint8_t *const mv_base0 = reinterpret_cast<const uint8_t *>(mi355_global(fr.mv[0]));
     const uint8_t *const mv_base1 = two_lists ? reinterpret_cast<const uint8_t *>(mi355_global(fr.mv[1])) : mv_base0;
-    /* what a lane fetches for one macroblock ahead of time (records and vectors: never written by the filter) */
-    struct Pre {
-        MbInfo h, ht;
-        uint32_t p0[2], q0[2], p1[2], q1[2];
-    };
+    alignas(16) const uint32_t o4[4] = { (uint32_t)o_p0, (uint32_t)o_q0, (uint32_t)o_p1, (uint32_t)o_q1 };
     auto prefetch = [&](Pre &p, int x) {
         const bool ok = row_ok && x >= 0 && x < W;
         const uint32_t xy = ok ? (uint32_t)(mb_y * W + x) : 0u;
         const uint32_t roff = xy * 64u, toff = ok && has_t ? roff - 64u * (uint32_t)W : roff;
-        p.h = mb_info_load<true>(rec_base, roff);
-        p.ht = mb_info_load<false>(rec_base, toff);
-        /* clamped addresses: a neighbour that does not exist reads this macroblock's own vector (its strength is masked) */
-        const uint32_t a_p0 = roff + (uint32_t)o_p0, a_p1 = roff + (uint32_t)o_p1;
-        const uint32_t a_q0 = (ok && x > 0) || !outer ? roff + (uint32_t)o_q0 : a_p0;
-        const uint32_t a_q1 = (ok && has_t) || !outer ? roff + (uint32_t)o_q1 : a_p1;
-        p.p0[0] = *reinterpret_cast<const uint32_t *>(mv_base0 + a_p0); p.q0[0] = *reinterpret_cast<const uint32_t *>(mv_base0 + a_q0);
-        p.p1[0] = *reinterpret_cast<const uint32_t *>(mv_base0 + a_p1); p.q1[0] = *reinterpret_cast<const uint32_t *>(mv_base0 + a_q1);
-        p.p0[1] = p.q0[1] = p.p1[1] = p.q1[1] = 0;           /* constants without list 1 (no register, no write) */
-        if (two_lists) {
-            p.p0[1] = *reinterpret_cast<const uint32_t *>(mv_base1 + a_p0); p.q0[1] = *reinterpret_cast<const uint32_t *>(mv_base1 + a_q0);
-            p.p1[1] = *reinterpret_cast<const uint32_t *>(mv_base1 + a_p1); p.q1[1] = *reinterpret_cast<const uint32_t *>(mv_base1 + a_q1);
-        }
+        mb_prefetch<TWO_LISTS>(p, rec_base, mv_base0, mv_base1, roff, toff, o4, outer, ok ? x : 0, ok && has_t ? 0u : 1u);
     };
     /* chunk I/O roles of a lane: piece p of a row pair */
     const int io_p = TILED ? l >> (4 - DCH_LOG) : l & (DCH - 1), io_r = TILED ? l & (DIO_ROWS - 1) : l >> DCH_LOG;
@@ -518,9 +510,6 @@ __device__ __forceinline__ void deblock_band(DeblockLds &s, const mi355_h264_fra
         const uint32_t tci1 = byte_perm(0, tr_i, bsw1 & 0x03030303u), tct1 = byte_perm(0, tr_t, bsw1 & 3u);
         const uint32_t cci0 = byte_perm(0, ctr_i, bsc0 & 0x03030303u), ccl0 = byte_perm(0, ctr_l, bsc0 & 3u);
         const uint32_t cci1 = byte_perm(0, ctr_i, bsc1 & 0x03030303u), cct1 = byte_perm(0, ctr_t, bsc1 & 3u);
-#define AB_A(w) ((int)((w) & 0xFF))
-#define AB_B(w) ((int)(((w) >> 8) & 0xFF))
-#define BYTE(w, e) ((int)(((w) >> (8 * (e))) & 0xFF))
 
         PROF_MARK(4);
         /* ---- vertical edges, one luma row + one chroma row per lane, in registers.  The four
@@ -528,22 +517,9 @@ __device__ __forceinline__ void deblock_band(DeblockLds &s, const mi355_h264_fra
         {
             uint8_t *rowp = &s.y[g][b][4 + l][16 * j];
             uint8_t *leftp = j ? rowp - 4 : &s.y[g][b ^ 1][4 + l][16 * (DCH - 1) + 12];
-            const uint4 own = lds16(rowp);
-            uint32_t wl = *reinterpret_cast<const uint32_t *>(leftp), w0 = own.x, w1 = own.y, w2 = own.z, w3 = own.w;
             uint8_t *crowp = &s.c[g][b][cp][2 + cr][8 * j];
             uint8_t *cleftp = j ? crowp - 4 : &s.c[g][b ^ 1][cp][2 + cr][8 * (DCH - 1) + 4];
-            const uint2 cown = *reinterpret_cast<const uint2 *>(crowp);
-            uint32_t cl = *reinterpret_cast<const uint32_t *>(cleftp), cw0 = cown.x, cw1 = cown.y;      /* columns -4..-1, 0..3, 4..7 */
-            const bool c0 = luma_row_edge<true>(wl, w0, BYTE(bsw0, 0), AB_A(ab_l), AB_B(ab_l), BYTE(tcl0, 0));
-            const bool c1 = luma_row_edge<false>(w0, w1, BYTE(bsw0, 1), AB_A(ab_i), AB_B(ab_i), BYTE(tci0, 1));
-            const bool c2 = luma_row_edge<false>(w1, w2, BYTE(bsw0, 2), AB_A(ab_i), AB_B(ab_i), BYTE(tci0, 2));
-            const bool c3 = luma_row_edge<false>(w2, w3, BYTE(bsw0, 3), AB_A(ab_i), AB_B(ab_i), BYTE(tci0, 3));
-            if (c0) *reinterpret_cast<uint32_t *>(leftp) = wl;
-            if (c0 || c1 || c2 || c3) lds16(rowp, make_uint4(w0, w1, w2, w3));
-            const bool d0 = chroma_row_edge(cl, cw0, BYTE(bsc0, 0), AB_A(cab_l), AB_B(cab_l), BYTE(ccl0, 0));
-            const bool d1 = chroma_row_edge(cw0, cw1, BYTE(bsc0, 2), AB_A(cab_i), AB_B(cab_i), BYTE(cci0, 2));
-            if (d0) *reinterpret_cast<uint32_t *>(cleftp) = cl;
-            if (d0 || d1) *reinterpret_cast<mi355_u32x2 *>(crowp) = mi355_u32x2{ cw0, cw1 };
+            vertical_edges(rowp, leftp, crowp, cleftp, bsw0, bsc0, ab_l, ab_i, tcl0, tci0, cab_l, cab_i, ccl0, cci0);
         }
         PROF_MARK(5);
         MI355_WAVE_SYNC();
@@ -558,31 +534,28 @@ __device__ __forceinline__ void deblock_band(DeblockLds &s, const mi355_h264_fra
             int y16 = colp[16 * DY_PITCH], y17 = colp[17 * DY_PITCH], y18 = colp[18 * DY_PITCH];
             int u0 = ccolp[0 * DC_PITCH], u1 = ccolp[1 * DC_PITCH], u2 = ccolp[2 * DC_PITCH], u3 = ccolp[3 * DC_PITCH];
             int u4 = ccolp[4 * DC_PITCH], u5 = ccolp[5 * DC_PITCH], u6 = ccolp[6 * DC_PITCH], u7 = ccolp[7 * DC_PITCH];
-            const int e0 = luma_line<true>(y0, y1, y2, y3, y4, y5, y6, y7, BYTE(bsw1, 0), AB_A(ab_t), AB_B(ab_t), BYTE(tct1, 0));
+            const int e0 = luma_line<true>(y0, y1, y2, y3, y4, y5, y6, y7, byte_of(bsw1, 0), ab_alpha(ab_t), ab_beta(ab_t), byte_of(tct1, 0));
             if (e0) {
                 if (e0 == 2) { colp[1 * DY_PITCH] = (uint8_t)y1; colp[6 * DY_PITCH] = (uint8_t)y6; }
                 colp[2 * DY_PITCH] = (uint8_t)y2; colp[3 * DY_PITCH] = (uint8_t)y3; colp[4 * DY_PITCH] = (uint8_t)y4; colp[5 * DY_PITCH] = (uint8_t)y5;
             }
-            if (luma_line<false>(y4, y5, y6, y7, y8, y9, y10, y11, BYTE(bsw1, 1), AB_A(ab_i), AB_B(ab_i), BYTE(tci1, 1))) {
+            if (luma_line<false>(y4, y5, y6, y7, y8, y9, y10, y11, byte_of(bsw1, 1), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci1, 1))) {
                 colp[6 * DY_PITCH] = (uint8_t)y6; colp[7 * DY_PITCH] = (uint8_t)y7; colp[8 * DY_PITCH] = (uint8_t)y8; colp[9 * DY_PITCH] = (uint8_t)y9;
             }
-            if (luma_line<false>(y8, y9, y10, y11, y12, y13, y14, y15, BYTE(bsw1, 2), AB_A(ab_i), AB_B(ab_i), BYTE(tci1, 2))) {
+            if (luma_line<false>(y8, y9, y10, y11, y12, y13, y14, y15, byte_of(bsw1, 2), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci1, 2))) {
                 colp[10 * DY_PITCH] = (uint8_t)y10; colp[11 * DY_PITCH] = (uint8_t)y11; colp[12 * DY_PITCH] = (uint8_t)y12; colp[13 * DY_PITCH] = (uint8_t)y13;
             }
             int y19 = 0;
-            if (luma_line<false>(y12, y13, y14, y15, y16, y17, y18, y19, BYTE(bsw1, 3), AB_A(ab_i), AB_B(ab_i), BYTE(tci1, 3))) {
+            if (luma_line<false>(y12, y13, y14, y15, y16, y17, y18, y19, byte_of(bsw1, 3), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci1, 3))) {
                 colp[14 * DY_PITCH] = (uint8_t)y14; colp[15 * DY_PITCH] = (uint8_t)y15; colp[16 * DY_PITCH] = (uint8_t)y16; colp[17 * DY_PITCH] = (uint8_t)y17;
             }
-            if (chroma_line(u0, u1, u2, u3, BYTE(bsc1, 0), AB_A(cab_t), AB_B(cab_t), BYTE(cct1, 0))) {
+            if (chroma_line(u0, u1, u2, u3, byte_of(bsc1, 0), ab_alpha(cab_t), ab_beta(cab_t), byte_of(cct1, 0))) {
                 ccolp[1 * DC_PITCH] = (uint8_t)u1; ccolp[2 * DC_PITCH] = (uint8_t)u2;
             }
-            if (chroma_line(u4, u5, u6, u7, BYTE(bsc1, 2), AB_A(cab_i), AB_B(cab_i), BYTE(cci1, 2))) {
+            if (chroma_line(u4, u5, u6, u7, byte_of(bsc1, 2), ab_alpha(cab_i), ab_beta(cab_i), byte_of(cci1, 2))) {
                 ccolp[5 * DC_PITCH] = (uint8_t)u5; ccolp[6 * DC_PITCH] = (uint8_t)u6;
             }
         }
-#undef AB_A
-#undef AB_B
-#undef BYTE
         PROF_MARK(6);
         MI355_WAVE_SYNC();   /* the tile is final for this macroblock: the group below and the next step may read it */
         hl = h;
@@ -615,22 +588,28 @@ __device__ __forceinline__ void deblock_band(DeblockLds &s, const mi355_h264_fra
 #endif
 }
 
+/* a picture's walker instance: list-1 vectors or not, surface layout.  skip_tiled: k_deblock_tiled takes the tiled pictures of the batch */
+template <int KW>
+__device__ __forceinline__ void deblock_band_of(DeblockLds &s, const mi355_h264_frame &fr, int band, int wave, int skip_tiled)
+{
+    if (uniform(fr.surface_layout) == MI355_SURFACE_TILED) {
+        if (skip_tiled) return;
+        if (mi355_global(fr.mv[1]) != nullptr) deblock_band<true, KW, true>(s, fr, band, wave);
+        else deblock_band<false, KW, true>(s, fr, band, wave);
+        return;
+    }
+    if (mi355_global(fr.mv[1]) != nullptr) deblock_band<true, KW, false>(s, fr, band, wave);
+    else deblock_band<false, KW, false>(s, fr, band, wave);
+}
+
 #ifdef MI355_DEBLOCK_WAVES
 __attribute__((amdgpu_waves_per_eu(MI355_DEBLOCK_WAVES, MI355_DEBLOCK_WAVES)))
 #endif
 __global__ void __launch_bounds__(64)
-k_deblock(const mi355_h264_frame *__restrict__ frames, int band, int skip_tiled)      /* skip_tiled: k_deblock_tiled takes the tiled pictures of the batch */
+k_deblock(const mi355_h264_frame *__restrict__ frames, int band, int skip_tiled)
 {
     __shared__ DeblockLds s;
-    const mi355_h264_frame &fr = frames[blockIdx.x];
-    if (uniform(fr.surface_layout) == MI355_SURFACE_TILED) {
-        if (skip_tiled) return;
-        if (mi355_global(fr.mv[1]) != nullptr) deblock_band<true, 1, true>(s, fr, band, 0);
-        else deblock_band<false, 1, true>(s, fr, band, 0);
-        return;
-    }
-    if (mi355_global(fr.mv[1]) != nullptr) deblock_band<true, 1, false>(s, fr, band, 0);
-    else deblock_band<false, 1, false>(s, fr, band, 0);
+    deblock_band_of<1>(s, frames[blockIdx.x], band, 0, skip_tiled);
 }
 
 /* the small-batch form: KW consecutive bands of a picture per workgroup, one wave each (see deblock_band) */
@@ -639,16 +618,8 @@ __global__ void __launch_bounds__(64 * KW)
 k_deblock_bands(const mi355_h264_frame *__restrict__ frames, int band0, int skip_tiled)
 {
     __shared__ DeblockLds s[KW];
-    const mi355_h264_frame &fr = frames[blockIdx.x];
     const int wave = (int)(threadIdx.x >> 6);
-    if (uniform(fr.surface_layout) == MI355_SURFACE_TILED) {
-        if (skip_tiled) return;
-        if (mi355_global(fr.mv[1]) != nullptr) deblock_band<true, KW, true>(s[wave], fr, band0 + wave, wave);
-        else deblock_band<false, KW, true>(s[wave], fr, band0 + wave, wave);
-        return;
-    }
-    if (mi355_global(fr.mv[1]) != nullptr) deblock_band<true, KW, false>(s[wave], fr, band0 + wave, wave);
-    else deblock_band<false, KW, false>(s[wave], fr, band0 + wave, wave);
+    deblock_band_of<KW>(s[wave], frames[blockIdx.x], band0 + wave, wave, skip_tiled);
 }
 
 
@@ -701,7 +672,11 @@ static_assert(sizeof(Deblock3Lds) <= 8192 + 288, "nineteen or twenty waves per C
 /* NW = 1: the wave does everything (the throughput form).  NW = 2 (few pictures: SIMDs stand idle and a lone wave's step is a serial chain
  * of ~1100 instructions): the band's workgroup is TWO waves — wave 0 runs only the edge phases of step t, wave 1 meanwhile writes out what
  * step t - 1 finished, issues the loads of step t + 1 and derives the strengths and parameters of step t + 1, which reach wave 0 through LDS
- * (`mail`, parm[step & 1]); two workgroup barriers per step (LDS only: the loads in flight stay in flight). */
+ * (`mail`, parm[step & 1]); two workgroup barriers per step (LDS only: the loads in flight stay in flight).
+ *
+ * mb_prefetch and vertical_edges are shared with deblock_band.  Table staging, lane roles, strengths, the parm lookup and its read-back and
+ * the horizontal edges are deblock_band's, restated: every shared form of them that was compiled gave k_deblock_tiled / k_deblock_tiled2
+ * another instruction stream, and the code of these two kernels is kept as it was measured. */
 #ifdef MI355_HIP_EMU_H
 #define MI355_WG_BARRIER_LDS() __syncthreads()
 #else
@@ -747,10 +722,6 @@ __device__ __forceinline__ void deblock3_band(Deblock3Lds &s, Deblock3Mail *mail
     }
     if (NW == 1) MI355_WAVE_SYNC(); else MI355_WG_BARRIER_LDS();
 
-    struct Pre {
-        MbInfo h, ht;
-        uint32_t p0[2], q0[2], p1[2], q1[2];
-    };
     /* Per-lane constants of the address arithmetic, computed once: a dozen registers against ~150 instructions per step (the first
      * version recomputed rows, tile offsets and swizzles from the lane number in every step: 637 VALU per step, the kernel bound by them).
      * LDS offsets are byte offsets from `s`, without the term of the ring slot; memory offsets are those of step 0, a step adds a tile. */
@@ -791,19 +762,7 @@ __device__ __forceinline__ void deblock3_band(Deblock3Lds &s, Deblock3Mail *mail
         const bool outer = (l & 3) == 0;
         const int xc = med3i(t1 - (int)k_g2, 0, W - 1);
         const uint32_t roff = k_rec + ((uint32_t)xc << 6), toff = roff - k_topd;
-        p.h = mb_info_load<true>(rec_base, roff);
-        p.ht = mb_info_load<false>(rec_base, toff);
-        const mi355_u32x4 o = *reinterpret_cast<const mi355_u32x4 *>(&s.role[l][8]);
-        const uint32_t a_p0 = roff + o[0], a_p1 = roff + o[2];
-        const uint32_t a_q0 = xc > 0 || !outer ? roff + o[1] : a_p0;
-        const uint32_t a_q1 = !kf(KF_ROW0) || !outer ? roff + o[3] : a_p1;
-        p.p0[0] = *reinterpret_cast<const uint32_t *>(mv_base0 + a_p0); p.q0[0] = *reinterpret_cast<const uint32_t *>(mv_base0 + a_q0);
-        p.p1[0] = *reinterpret_cast<const uint32_t *>(mv_base0 + a_p1); p.q1[0] = *reinterpret_cast<const uint32_t *>(mv_base0 + a_q1);
-        p.p0[1] = p.q0[1] = p.p1[1] = p.q1[1] = 0;
-        if (two_lists) {
-            p.p0[1] = *reinterpret_cast<const uint32_t *>(mv_base1 + a_p0); p.q0[1] = *reinterpret_cast<const uint32_t *>(mv_base1 + a_q0);
-            p.p1[1] = *reinterpret_cast<const uint32_t *>(mv_base1 + a_p1); p.q1[1] = *reinterpret_cast<const uint32_t *>(mv_base1 + a_q1);
-        }
+        mb_prefetch<TWO_LISTS>(p, rec_base, mv_base0, mv_base1, roff, toff, &s.role[l][8], outer, xc, k_flags & KF_ROW0);
     };
     /* the tiles of step t1 (group g: macroblock t1 - 2g, clamped into its row) into ring slot t1 & 3; group 0's macroblock above into above[t1 & 1] */
     auto dma_issue = [&](int t1) {
@@ -867,9 +826,6 @@ __device__ __forceinline__ void deblock3_band(Deblock3Lds &s, Deblock3Mail *mail
     };
     Pre pre = {}, pre_next = {};
     MbInfo hl = {};
-#define AB_A(w) ((int)((w) & 0xFF))
-#define AB_B(w) ((int)(((w) >> 8) & 0xFF))
-#define BYTE(w, e) ((int)(((w) >> (8 * (e))) & 0xFF))
     /* boundary strengths of step t's macroblocks from `pre` (their records and vectors) and `hl` (the previous macroblock's), packed per line:
      * byte e of bsw0 / bsw1 = the strength of vertical / horizontal edge e of this lane's luma row / column, bsc0 / bsc1 the same for its chroma
      * line; alpha / beta / tc0 of the step into parm[pb] */
@@ -918,20 +874,7 @@ __device__ __forceinline__ void deblock3_band(Deblock3Lds &s, Deblock3Mail *mail
             const uint32_t cci0 = byte_perm(0, ctr_i, bsc0 & 0x03030303u), ccl0 = byte_perm(0, ctr_l, bsc0 & 3u);
             uint8_t *rowp = lds + (k_rv + OY + 1024u * (uint32_t)(t & 3)), *leftp = lds + (k_rv + OY + 12u + 1024u * (uint32_t)((t - 1) & 3));
             uint8_t *crowp = lds + (k_cv + OC + 512u * (uint32_t)(t & 3)), *cleftp = lds + (k_cv + OC + 4u + 512u * (uint32_t)((t - 1) & 3));
-            const uint4 own = lds16(rowp);
-            const uint2 cown = *reinterpret_cast<const uint2 *>(crowp);
-            uint32_t wl = *reinterpret_cast<const uint32_t *>(leftp), w0 = own.x, w1 = own.y, w2 = own.z, w3 = own.w;
-            uint32_t cl = *reinterpret_cast<const uint32_t *>(cleftp), cw0 = cown.x, cw1 = cown.y;
-            const bool c0 = luma_row_edge<true>(wl, w0, BYTE(bsw0, 0), AB_A(ab_l), AB_B(ab_l), BYTE(tcl0, 0));
-            const bool c1 = luma_row_edge<false>(w0, w1, BYTE(bsw0, 1), AB_A(ab_i), AB_B(ab_i), BYTE(tci0, 1));
-            const bool c2 = luma_row_edge<false>(w1, w2, BYTE(bsw0, 2), AB_A(ab_i), AB_B(ab_i), BYTE(tci0, 2));
-            const bool c3 = luma_row_edge<false>(w2, w3, BYTE(bsw0, 3), AB_A(ab_i), AB_B(ab_i), BYTE(tci0, 3));
-            if (c0) *reinterpret_cast<uint32_t *>(leftp) = wl;
-            if (c0 || c1 || c2 || c3) lds16(rowp, make_uint4(w0, w1, w2, w3));
-            const bool d0 = chroma_row_edge(cl, cw0, BYTE(bsc0, 0), AB_A(cab_l), AB_B(cab_l), BYTE(ccl0, 0));
-            const bool d1 = chroma_row_edge(cw0, cw1, BYTE(bsc0, 2), AB_A(cab_i), AB_B(cab_i), BYTE(cci0, 2));
-            if (d0) *reinterpret_cast<uint32_t *>(cleftp) = cl;
-            if (d0 || d1) *reinterpret_cast<mi355_u32x2 *>(crowp) = mi355_u32x2{ cw0, cw1 };
+            vertical_edges(rowp, leftp, crowp, cleftp, bsw0, bsc0, ab_l, ab_i, tcl0, tci0, cab_l, cab_i, ccl0, cci0);
         }
     };
     auto edges_h = [&](int t, int pb, uint32_t bsw1, uint32_t bsc1) {
@@ -963,25 +906,25 @@ __device__ __forceinline__ void deblock3_band(Deblock3Lds &s, Deblock3Mail *mail
             int y4 = YR(0), y5 = YR(1), y6 = YR(2), y7 = YR(3), y8 = YR(4), y9 = YR(5), y10 = YR(6), y11 = YR(7);
             int y12 = YR(8), y13 = YR(9), y14 = YR(10), y15 = YR(11), y16 = YR(12), y17 = YR(13), y18 = YR(14);
             int u0 = CAR(6), u1 = CAR(7), u2 = CR(0), u3 = CR(1), u4 = CR(2), u5 = CR(3), u6 = CR(4), u7 = CR(5);
-            const int e0 = luma_line<true>(y0, y1, y2, y3, y4, y5, y6, y7, BYTE(bsw1, 0), AB_A(ab_t), AB_B(ab_t), BYTE(tct1, 0));
+            const int e0 = luma_line<true>(y0, y1, y2, y3, y4, y5, y6, y7, byte_of(bsw1, 0), ab_alpha(ab_t), ab_beta(ab_t), byte_of(tct1, 0));
             if (e0) {
                 if (e0 == 2) { AR(13) = (uint8_t)y1; YR(2) = (uint8_t)y6; }
                 AR(14) = (uint8_t)y2; AR(15) = (uint8_t)y3; YR(0) = (uint8_t)y4; YR(1) = (uint8_t)y5;
             }
-            if (luma_line<false>(y4, y5, y6, y7, y8, y9, y10, y11, BYTE(bsw1, 1), AB_A(ab_i), AB_B(ab_i), BYTE(tci1, 1))) {
+            if (luma_line<false>(y4, y5, y6, y7, y8, y9, y10, y11, byte_of(bsw1, 1), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci1, 1))) {
                 YR(2) = (uint8_t)y6; YR(3) = (uint8_t)y7; YR(4) = (uint8_t)y8; YR(5) = (uint8_t)y9;
             }
-            if (luma_line<false>(y8, y9, y10, y11, y12, y13, y14, y15, BYTE(bsw1, 2), AB_A(ab_i), AB_B(ab_i), BYTE(tci1, 2))) {
+            if (luma_line<false>(y8, y9, y10, y11, y12, y13, y14, y15, byte_of(bsw1, 2), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci1, 2))) {
                 YR(6) = (uint8_t)y10; YR(7) = (uint8_t)y11; YR(8) = (uint8_t)y12; YR(9) = (uint8_t)y13;
             }
             int y19 = 0;
-            if (luma_line<false>(y12, y13, y14, y15, y16, y17, y18, y19, BYTE(bsw1, 3), AB_A(ab_i), AB_B(ab_i), BYTE(tci1, 3))) {
+            if (luma_line<false>(y12, y13, y14, y15, y16, y17, y18, y19, byte_of(bsw1, 3), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci1, 3))) {
                 YR(10) = (uint8_t)y14; YR(11) = (uint8_t)y15; YR(12) = (uint8_t)y16; YR(13) = (uint8_t)y17;
             }
-            if (chroma_line(u0, u1, u2, u3, BYTE(bsc1, 0), AB_A(cab_t), AB_B(cab_t), BYTE(cct1, 0))) {
+            if (chroma_line(u0, u1, u2, u3, byte_of(bsc1, 0), ab_alpha(cab_t), ab_beta(cab_t), byte_of(cct1, 0))) {
                 CAR(7) = (uint8_t)u1; CR(0) = (uint8_t)u2;
             }
-            if (chroma_line(u4, u5, u6, u7, BYTE(bsc1, 2), AB_A(cab_i), AB_B(cab_i), BYTE(cci1, 2))) {
+            if (chroma_line(u4, u5, u6, u7, byte_of(bsc1, 2), ab_alpha(cab_i), ab_beta(cab_i), byte_of(cci1, 2))) {
                 CR(3) = (uint8_t)u5; CR(4) = (uint8_t)u6;
             }
 #undef YJ
@@ -1078,9 +1021,6 @@ __device__ __forceinline__ void deblock3_band(Deblock3Lds &s, Deblock3Mail *mail
         stores(nsteps - 1);
         return;
     }
-#undef AB_A
-#undef AB_B
-#undef BYTE
     if (hand) {
         agent_drain_stores();
         if (lane_id() == 0) agent_store_u32(mi355_global_v(prog_self), (uint32_t)W);
@@ -1156,22 +1096,21 @@ uint32_t *mi355::sync_words(hipStream_t st, size_t words)
 {
     std::vector<SyncBuf> &pool = sync_pool();
     const int device = mi355::current_device();
-    for (SyncBuf &b : pool) {
-        if (b.device != device || b.stream != st) continue;
-        if (b.words >= words) return b.dev;
-        (void)hipFree(b.dev);                  /* waits for what still uses it */
-        b.dev = nullptr; b.words = 0;
-        size_t n = 4096;
-        while (n < words) n *= 2;
-        if (hipMalloc(reinterpret_cast<void **>(&b.dev), n * sizeof(uint32_t)) != hipSuccess) return nullptr;
-        b.words = n;
-        return b.dev;
+    SyncBuf *b = nullptr;
+    for (SyncBuf &e : pool)
+        if (e.device == device && e.stream == st) { b = &e; break; }
+    if (!b) {
+        pool.push_back(SyncBuf{ device, st, nullptr, 0 });
+        b = &pool.back();
     }
-    SyncBuf b{ device, st, nullptr, 4096 };
-    while (b.words < words) b.words *= 2;
-    if (hipMalloc(reinterpret_cast<void **>(&b.dev), b.words * sizeof(uint32_t)) != hipSuccess) return nullptr;
-    pool.push_back(b);
-    return b.dev;
+    if (b->dev && b->words >= words) return b->dev;
+    if (b->dev) (void)hipFree(b->dev);         /* waits for what still uses it */
+    b->dev = nullptr; b->words = 0;
+    size_t n = 4096;
+    while (n < words) n *= 2;
+    if (hipMalloc(reinterpret_cast<void **>(&b->dev), n * sizeof(uint32_t)) != hipSuccess) { b->dev = nullptr; return nullptr; }   /* the entry stays, empty: the next call tries again */
+    b->words = n;
+    return b->dev;
 }
 void mi355::sync_words_release(hipStream_t st)
 {
@@ -1188,11 +1127,6 @@ void mi355::sync_words_release(hipStream_t st)
 /* The forms of the loop filter.  deblock_plan() is the rule mi355_h264_deblock_layouts_dev follows and mi355_h264_deblock_plan reports;
  * deblock_launch() runs a plan (also one that mi355_h264_deblock_form_dev names). */
 namespace {
-struct DeblockForms {
-    int tiled_waves;     /* 0: no tiled launch; 1: k_deblock_tiled; 2: k_deblock_tiled2 */
-    int linear_bands;    /* 0: no linear launch; 1: k_deblock; 2 / 3 / 4 / 6: k_deblock_bands<n> */
-    int skip_tiled;      /* the linear kernels leave tiled pictures to the tiled launch */
-};
 /* MI355_DEBLOCK_FORM / MI355_DEBLOCK_WAVES (developer switches), read once per process */
 int deblock_form_pin()
 {
@@ -1216,7 +1150,7 @@ int device_cus()
 }
 bool linear_form(int kw) { return kw == 1 || kw == 2 || kw == 3 || kw == 4 || kw == 6; }
 
-DeblockForms deblock_plan(int nframes, int max_mb_width, int max_mb_height, int layouts, int cus)
+mi355_h264_deblock_plan_info deblock_plan(int nframes, int max_mb_width, int max_mb_height, int layouts, int cus)
 {
     const int nbands = (max_mb_height + 3) / 4, nsteps = max_mb_width + 6;
     /* Tiled pictures: ONE launch for all bands of all pictures (k_deblock_tiled).  Pictures with line strides (field pictures, 4:4:4 plane
@@ -1224,7 +1158,7 @@ DeblockForms deblock_plan(int nframes, int max_mb_width, int max_mb_height, int 
      * band, or 2 to 6 bands per workgroup when the pictures are few.  MI355_DEBLOCK_FORM (developer switch) = 1 / 2 / 3 / 4 / 6 pins the
      * latter's bands per workgroup and sends tiled pictures through it as well (what round 3 measured). */
     const int force = deblock_form_pin();
-    DeblockForms p{ 0, 0, 0 };
+    mi355_h264_deblock_plan_info p{ 0, 0, 0, 0 };
     const bool tiled_launch = (layouts & MI355_LAYOUTS_TILED) && force == 0;
     if (tiled_launch) {
         /* few bands in all (fewer than two per SIMD): two waves per band, the edge phases beside everything else (MI355_DEBLOCK_WAVES = 1 / 2 pins the form) */
@@ -1248,10 +1182,11 @@ DeblockForms deblock_plan(int nframes, int max_mb_width, int max_mb_height, int 
     if (linear_form(force)) best = force;
     p.linear_bands = best;
     p.skip_tiled = tiled_launch ? 1 : 0;
+    p.linear_launches = (nbands + best - 1) / best;
     return p;
 }
 
-int deblock_launch(const mi355_h264_frame *d_frames, int nframes, int nbands, const DeblockForms &p, hipStream_t st)
+int deblock_launch(const mi355_h264_frame *d_frames, int nframes, int nbands, const mi355_h264_deblock_plan_info &p, hipStream_t st)
 {
     if (p.tiled_waves) {
         if ((long long)nframes * nbands > 0x7FFFFFFFLL) return -3;
@@ -1281,11 +1216,18 @@ extern "C" int mi355_h264_deblock_dev(const mi355_h264_frame *d_frames, int nfra
     return mi355_h264_deblock_layouts_dev(d_frames, nframes, max_mb_width, max_mb_height, MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED, stream);
 }
 
+/* the argument checks of the entry points that launch: the number of bands, or 0 */
+static int deblock_args(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int layouts)
+{
+    if (!mi355::bind() || !d_frames || nframes <= 0 || !(layouts & (MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED))) return 0;
+    const int nbands = (max_mb_height + 3) / 4;
+    return nbands <= 0 || max_mb_width <= 0 ? 0 : nbands;
+}
+
 extern "C" int mi355_h264_deblock_layouts_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int layouts, void *stream)
 {
-    if (!mi355::bind() || !d_frames || nframes <= 0 || !(layouts & (MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED))) return -1;
-    const int nbands = (max_mb_height + 3) / 4;
-    if (nbands <= 0 || max_mb_width <= 0) return -1;
+    const int nbands = deblock_args(d_frames, nframes, max_mb_width, max_mb_height, layouts);
+    if (!nbands) return -1;
     return deblock_launch(d_frames, nframes, nbands, deblock_plan(nframes, max_mb_width, max_mb_height, layouts, device_cus()), (hipStream_t)stream);
 }
 
@@ -1296,26 +1238,20 @@ extern "C" int mi355_h264_deblock_plan(int nframes, int max_mb_width, int max_mb
         if (!mi355::bind()) return -1;
         cus = device_cus();
     }
-    const DeblockForms p = deblock_plan(nframes, max_mb_width, max_mb_height, layouts, cus);
-    const int nbands = (max_mb_height + 3) / 4;
-    plan->tiled_waves = p.tiled_waves;
-    plan->linear_bands = p.linear_bands;
-    plan->skip_tiled = p.skip_tiled;
-    plan->linear_launches = p.linear_bands ? (nbands + p.linear_bands - 1) / p.linear_bands : 0;
+    *plan = deblock_plan(nframes, max_mb_width, max_mb_height, layouts, cus);
     return 0;
 }
 
 extern "C" int mi355_h264_deblock_form_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int layouts, int tiled_waves,
                                            int linear_bands, void *stream)
 {
-    if (!mi355::bind() || !d_frames || nframes <= 0 || !(layouts & (MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED))) return -1;
-    const int nbands = (max_mb_height + 3) / 4;
-    if (nbands <= 0 || max_mb_width <= 0) return -1;
+    const int nbands = deblock_args(d_frames, nframes, max_mb_width, max_mb_height, layouts);
+    if (!nbands) return -1;
     if (tiled_waves < 0 || tiled_waves > 2 || (linear_bands != 0 && !linear_form(linear_bands))) return -1;
     /* every layout of the batch must have a kernel that takes it: tiled pictures the tiled launch or linear kernels that do not skip them */
     if ((layouts & MI355_LAYOUTS_LINEAR) && !linear_bands) return -1;
     if ((layouts & MI355_LAYOUTS_TILED) && !tiled_waves && !linear_bands) return -1;
     if (tiled_waves && !(layouts & MI355_LAYOUTS_TILED)) return -1;
-    const DeblockForms p{ tiled_waves, linear_bands, tiled_waves ? 1 : 0 };
+    const mi355_h264_deblock_plan_info p{ tiled_waves, linear_bands, tiled_waves ? 1 : 0, linear_bands ? (nbands + linear_bands - 1) / linear_bands : 0 };
     return deblock_launch(d_frames, nframes, nbands, p, (hipStream_t)stream);
 }

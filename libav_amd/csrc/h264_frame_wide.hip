@@ -20,7 +20,7 @@
  */
 #include <cstdlib>
 #include <type_traits>
-#include "h264_frame_dev.h"
+#include "h264_deblock_dev.h"
 
 using namespace mi355;
 
@@ -863,19 +863,6 @@ k_wide_intra(const mi355_h264_frame *frames, int level, int width)
 /* ------------------------------------------------------------------------- */
 /* loop filter                                                                  */
 /* ------------------------------------------------------------------------- */
-__device__ const uint8_t kw_alpha[52] = {
-    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 4, 4, 5, 6, 7, 8, 9, 10, 12, 13, 15, 17, 20, 22, 25, 28,
-    32, 36, 40, 45, 50, 56, 63, 71, 80, 90, 101, 113, 127, 144, 162, 182, 203, 226, 255, 255 };
-__device__ const uint8_t kw_beta[52] = {
-    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 6, 6, 7, 7, 8, 8,
-    9, 9, 10, 10, 11, 11, 12, 12, 13, 13, 14, 14, 15, 15, 16, 16, 17, 17, 18, 18 };
-__device__ const uint8_t kw_tc0[52][3] = {
-    {0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,0},
-    {0,0,0},{0,0,0},{0,0,0},{0,0,0},{0,0,1},{0,0,1},{0,0,1},{0,0,1},{0,1,1},{0,1,1},{1,1,1},{1,1,1},{1,1,1},
-    {1,1,1},{1,1,2},{1,1,2},{1,1,2},{1,1,2},{1,2,3},{1,2,3},{2,2,3},{2,2,4},{2,3,4},{2,3,4},{3,3,5},{3,4,6},
-    {3,4,6},{4,5,7},{4,5,8},{4,6,9},{5,7,10},{6,8,11},{6,8,13},{7,10,14},{8,11,16},{9,12,18},{10,13,20},
-    {11,15,23},{13,17,25} };
-
 constexpr int DYP = 20, DCPW = 12;       /* pitches of the MBAFF filter's luma (-4..15) and chroma (-4..7) tiles */
 /* The frame / field filter's tiles hold a UNIT: up to WIDE_UNIT macroblocks side by side (round 6).  A lane's piece of a 10-bit luma row is 32 bytes of a 128-byte line; fetched
  * macroblock by macroblock the rest of the line came again for the next macroblock unless the L2 had kept it — it had not (3072 groups of sixteen lines each in flight per XCD's
@@ -1330,7 +1317,7 @@ k_wide_deblock(const mi355_h264_frame *frames, int nframes, int d, int y_first, 
     __shared__ uint8_t t_alpha[52], t_beta[52], t_lc[4][16];
     __shared__ __attribute__((aligned(4))) uint8_t t_tc0[52][4];       /* a row is read as one dword (wide_thr) */
     const int lane = lane_id(), g = lane >> 4, l = lane & 15;
-    if (lane < 52) { t_alpha[lane] = kw_alpha[lane]; t_beta[lane] = kw_beta[lane]; t_tc0[lane][0] = kw_tc0[lane][0]; t_tc0[lane][1] = kw_tc0[lane][1]; t_tc0[lane][2] = kw_tc0[lane][2]; t_tc0[lane][3] = 0; }
+    if (lane < 52) { t_alpha[lane] = k_alpha[lane]; t_beta[lane] = k_beta[lane]; t_tc0[lane][0] = k_tc0[lane][0]; t_tc0[lane][1] = k_tc0[lane][1]; t_tc0[lane][2] = k_tc0[lane][2]; t_tc0[lane][3] = 0; }
     /* the launch holds the rows that have a unit on this anti-diagonal (of the largest picture): y_first .. y_first + rows - 1 */
     const int f = 4 * ((int)blockIdx.x / rows) + g, mb_y = y_first + (int)blockIdx.x % rows, x0 = (d - 2 * mb_y) * unit;
     const WideDbPic pic = wide_db_pic(frames[f < nframes ? f : nframes - 1]);
@@ -1397,7 +1384,7 @@ k_wide_deblock_mbaff(const mi355_h264_frame *frames, int nframes, int d, int max
     __shared__ __attribute__((aligned(4))) uint8_t t_tc0[52][4];       /* a row is read as one dword (wide_thr) */
     const int lane = lane_id(), g = lane >> 4, l = lane & 15;
     WideMbaffLds &s = sh[g];
-    if (lane < 52) { t_alpha[lane] = kw_alpha[lane]; t_beta[lane] = kw_beta[lane]; t_tc0[lane][0] = kw_tc0[lane][0]; t_tc0[lane][1] = kw_tc0[lane][1]; t_tc0[lane][2] = kw_tc0[lane][2]; t_tc0[lane][3] = 0; }
+    if (lane < 52) { t_alpha[lane] = k_alpha[lane]; t_beta[lane] = k_beta[lane]; t_tc0[lane][0] = k_tc0[lane][0]; t_tc0[lane][1] = k_tc0[lane][1]; t_tc0[lane][2] = k_tc0[lane][2]; t_tc0[lane][3] = 0; }
     const int f = 4 * ((int)blockIdx.x / max_pr) + g, pr = (int)blockIdx.x % max_pr, x = d - 2 * pr;
     const mi355_h264_frame &fr = frames[f < nframes ? f : nframes - 1];
     const int W = fr.mb_width;
