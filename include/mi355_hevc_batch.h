@@ -357,7 +357,11 @@ int mi355_hevc_recon_levels_dev(const mi355_hevc_level *d_levels, int n_levels, 
  * height are multiples of 16 samples of their plane, and 16x16 / 32x32 inverse DCTs (MI355_HEVC_TU_IDCT) with 16-byte aligned
  * coefficients; everything else runs the bodies of the two batch kernels on the tile.  Precondition for the transform units, as for
  * mi355_hevc_residual_batch_dev and for the same reason (hevcdec.c:1249-1256): a unit's coefficients lie in rows AND columns
- * 0 .. col_limit + 3 of its block (the diagonal scan leaves none beyond either). */
+ * 0 .. col_limit + 3 of its block (the diagonal scan leaves none beyond either), and for the 16x16 / 32x32 matrix path nowhere the
+ * reference's pruned passes do not read (hevcdsp_template.c:140-236: the odd rows from the column's `end` on, the odd columns from
+ * col_limit on) — what any block made by the decoder's diagonal scan satisfies.  The matrix path transforms everything it fetches:
+ * on a block with coefficients at such positions its result differs from the reference's pruned one (tests/hevc_recon_tables.py:
+ * the "plain" rows stay out of the blocks, the "pruned" rows go in). */
 enum { MI355_HEVC_CTB_PARTIAL = 1 };
 typedef struct mi355_hevc_ctb_job {
     uint8_t *dst[3];              /* first sample of the CTB in the picture's three planes */

@@ -337,9 +337,11 @@ __device__ __forceinline__ void cf_mc_tile_n(CfWin &w, const uint8_t *src, const
     const uint64_t toep_h = cf_taps_at(ph.taps, 8 * g - off - j);
     const int ch = 128 * ph.sum, ch4[4] = { ch, ch, ch, ch };
     const uint64_t toep_v = cf_u64((uint32_t)cf_taps_at(pv.taps, 4 * g - j), (uint32_t)cf_taps_at(pv.taps, 16 + 4 * g - j));
-    /* ((sum >> shift) + rnd) >> sh14 with rnd = 1 << (sh14 - 1) is (sum + (rnd << shift)) >> (shift + sh14): one shift, the addend in the accumulator's start value */
-    const int sh14 = 14 - bd, maxv = (1 << bd) - 1, shv = pv.shift + sh14;
-    const int cv = 128 * pv.sum + ((1 << (sh14 - 1)) << pv.shift), cv4[4] = { cv, cv, cv, cv };
+    /* (sum >> shift) is the 14-bit intermediate, which the reference keeps in an int16_t: the 8-tap filter in both directions reaches 33150 on samples at the
+     * maximum under its positive taps and 0 under the negative ones, and wraps there (put_hevc_qpel_hv stores to int16_t; put_unweighted_pred reads that).  So
+     * the value is narrowed to 16 bits before put_unweighted_pred's ((x + rnd) >> sh14), as the batch kernels' intermediate buffer does */
+    const int sh14 = 14 - bd, maxv = (1 << bd) - 1, rnd14 = 1 << (sh14 - 1);
+    const int cv = 128 * pv.sum, cv4[4] = { cv, cv, cv, cv };
 #pragma unroll
     for (int pl = 0; pl < NPL; pl++)
 #pragma unroll
@@ -380,7 +382,7 @@ __device__ __forceinline__ void cf_mc_tile_n(CfWin &w, const uint8_t *src, const
             cf_mfma(cf_u64(thi[yt], thi[yt + 1]), toep_v, zero4, h);
             cf_mfma(cf_u64(tlo[yt], tlo[yt + 1]), toep_v, cv4, l);
 #pragma unroll
-            for (int t = 0; t < 4; t++) s[t] = med3i(((h[t] << 8) + l[t]) >> shv, 0, maxv);
+            for (int t = 0; t < 4; t++) s[t] = med3i(((int)(int16_t)(((h[t] << 8) + l[t]) >> pv.shift) + rnd14) >> sh14, 0, maxv);
             uint8_t *p = out + (16 * yt + j) * pitch + ((16 * xt + 4 * g) << (WIDE ? 1 : 0));
             if (WIDE) *reinterpret_cast<uint2 *>(p) = make_uint2((uint32_t)s[0] | ((uint32_t)s[1] << 16), (uint32_t)s[2] | ((uint32_t)s[3] << 16));
             else *reinterpret_cast<uint32_t *>(p) = (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | ((uint32_t)s[3] << 24);
