@@ -29,6 +29,11 @@
  *                          over mi355_sws_hscale8to15 / mi355_sws_yuv2planeX_8 / mi355_sws_yuv2plane1_8.
  *                          mi355_sws_describe_planar() fills the descriptor mi355_sws_create_planar() takes; it declines
  *                          SWS_FAST_BILINEAR, range conversion and the unscaled converters (planar_format()).
+ *   other sources          yuv420p / yuv422p / yuv444p at 8 bits and their 9le / 10le forms, to rgb24 or to 8-bit yuv420p / yuv422p / yuv444p,
+ *                          take the same two forms through mi355_sws_describe_src() / mi355_sws_create_src(): whole pictures, and with
+ *                          MI355_SWS_LINES=1 the inner loops (hyScale / hcScale of a deeper source: mi355_sws_hscale16to15).  Declined: what
+ *                          taken() / planar_format() decline, contexts with an input converter, big-endian sources and the plane copies
+ *                          (no filter banks: planarCopyWrapper).  mi355_sws_describe / _planar keep their answers (yuv420p only).
  * The device is MI355_DEVICE (default 0), as for the decoder bridges.
  */
 #include <pthread.h>
@@ -36,6 +41,7 @@
 #include <string.h>
 #include "libswscale/swscale.h"
 #include "libswscale/swscale_internal.h"
+#include "libavutil/pixdesc.h"
 #include "mi355_sws.h"
 #include "mi355dsp.h"
 
@@ -115,7 +121,82 @@ int mi355_sws_describe_planar(struct SwsContext *c, mi355_sws_desc *d, int *dst_
     return 0;
 }
 
+/* ---- any source of the path: planar yuv 4:2:0 / 4:2:2 / 4:4:4, 8 bits or 9 / 10 bits little endian ------------------------------------
+ * 0 and the source's depth and chroma shifts, -1 for another format */
+static int source_of(const SwsContext *c, mi355_sws_src *s)
+{
+    memset(s, 0, sizeof(*s));
+    switch (c->srcFormat) {
+    case AV_PIX_FMT_YUV420P:     s->depth = 8;  s->hsub = 1; s->vsub = 1; break;
+    case AV_PIX_FMT_YUV422P:     s->depth = 8;  s->hsub = 1; s->vsub = 0; break;
+    case AV_PIX_FMT_YUV444P:     s->depth = 8;  s->hsub = 0; s->vsub = 0; break;
+    case AV_PIX_FMT_YUV420P9LE:  s->depth = 9;  s->hsub = 1; s->vsub = 1; break;
+    case AV_PIX_FMT_YUV422P9LE:  s->depth = 9;  s->hsub = 1; s->vsub = 0; break;
+    case AV_PIX_FMT_YUV444P9LE:  s->depth = 9;  s->hsub = 0; s->vsub = 0; break;
+    case AV_PIX_FMT_YUV420P10LE: s->depth = 10; s->hsub = 1; s->vsub = 1; break;
+    case AV_PIX_FMT_YUV422P10LE: s->depth = 10; s->hsub = 1; s->vsub = 0; break;
+    case AV_PIX_FMT_YUV444P10LE: s->depth = 10; s->hsub = 0; s->vsub = 0; break;
+    default: return -1;
+    }
+    if (c->chrSrcHSubSample != s->hsub || c->chrSrcVSubSample != s->vsub) return -1;
+    memcpy(s->dither, ff_dither_8x8_128, sizeof(s->dither));      /* the rows should_dither selects (swscale.c:553-556) */
+    return 0;
+}
+/* 0: rgb24, MI355_SWS_DST_*: planar, -1: a context this path leaves to the reference.  special: the context's swscale is yuv2rgb_c_24_rgb */
+static int src_format(const SwsContext *c, mi355_sws_src *s, int special)
+{
+    if (source_of(c, s) != 0 || (c->flags & SWS_FULL_CHR_H_INT)) return -1;       /* (every destination below is 8 bits) */
+    if (c->lumToYV12 || c->chrToYV12 || c->readLumPlanar || c->readChrPlanar || c->alpToYV12 || c->readAlpPlanar) return -1;      /* an input converter */
+    if (special) return c->dstFormat == AV_PIX_FMT_RGB24 && s->depth == 8 && s->hsub == 1 ? 0 : -1;
+    /* the generic scaler: no fast bilinear, no range conversion, no chroma line drop, and its four banks (an unscaled converter or a
+     * plane copy has none, utils.c:1043-1048) */
+    if (c->hyscale_fast || c->hcscale_fast || c->lumConvertRange || c->chrConvertRange || c->vChrDrop) return -1;
+    if (!c->vLumFilter || !c->vChrFilter || !c->hLumFilter || !c->hChrFilter) return -1;
+    switch (c->dstFormat) {
+    case AV_PIX_FMT_RGB24:   return 0;
+    case AV_PIX_FMT_YUV420P: return MI355_SWS_DST_YUV420P;
+    case AV_PIX_FMT_YUV422P: return MI355_SWS_DST_YUV422P;
+    case AV_PIX_FMT_YUV444P: return MI355_SWS_DST_YUV444P;
+    default: return -1;
+    }
+}
+static int describe_src(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *dst_format, int special)
+{
+    const int fmt = src_format(c, s, special);
+    if (fmt < 0) return -1;
+    memset(d, 0, sizeof(*d));
+    d->srcW = c->srcW; d->srcH = c->srcH; d->dstW = c->dstW; d->dstH = c->dstH;
+    d->chrSrcW = c->chrSrcW; d->chrSrcH = c->chrSrcH; d->chrDstW = c->chrDstW;
+    d->unscaled_special = special;
+    if (!special) {
+        d->hLum = (mi355_sws_filter){ c->hLumFilter, c->hLumFilterPos, c->hLumFilterSize, c->dstW };
+        d->hChr = (mi355_sws_filter){ c->hChrFilter, c->hChrFilterPos, c->hChrFilterSize, c->chrDstW };
+        d->vLum = (mi355_sws_filter){ c->vLumFilter, c->vLumFilterPos, c->vLumFilterSize, c->dstH };
+        d->vChr = (mi355_sws_filter){ c->vChrFilter, c->vChrFilterPos, c->vChrFilterSize, fmt ? c->chrDstH : c->dstH };
+    }
+    if (!fmt) luts_of(c, &d->luts);
+    *dst_format = fmt;
+    return 0;
+}
+/* what mi355_sws_create_src takes for a live context (0), -1 for a context this path declines.  A context without the vertical banks whose
+ * swscale is the reference's yuv2rgb_c_24_rgb is the unscaled special converter; any other without them (a plane copy) is declined. */
+int mi355_sws_describe_src(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *dst_format)
+{
+    int special = 0;
+    if (!c->vLumFilter) {
+        if (c->dstFormat != AV_PIX_FMT_RGB24 || (c->flags & SWS_ACCURATE_RND) || (c->dstH & 1) || c->srcW != c->dstW || c->srcH != c->dstH ||
+            (c->srcFormat != AV_PIX_FMT_YUV420P && c->srcFormat != AV_PIX_FMT_YUV422P)) return -1;
+        special = 1;                                             /* swscale_unscaled.c:1051-1055 */
+    }
+    return describe_src(c, d, s, dst_format, special);
+}
+
 #ifndef MI355_SWS_DESCRIBE_ONLY
+static void t1_hscale16(SwsContext *c, int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
+{
+    n_calls++;
+    mi355_sws_hscale16to15(dst, dstW, src, filter, filterPos, filterSize, c->srcBpc);
+}
 static void t1_hscale(SwsContext *c, int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
 {
     (void)c; n_calls++;
@@ -166,19 +247,23 @@ static void t1_plane1(const int16_t *src, uint8_t *dest, int dstW, const uint8_t
 
 void ff_sws_init_mi355x(SwsContext *c)
 {
-    if (planar_format(c)) {
+    mi355_sws_src s;
+    const int fmt = src_format(c, &s, 0);
+    if (fmt > 0) {
         if (!device_ready() || !c->hyScale || !c->hcScale || !c->yuv2planeX || !c->yuv2plane1) return;
-        c->hyScale = c->hcScale = t1_hscale;
+        c->hyScale = c->hcScale = s.depth > 8 ? t1_hscale16 : t1_hscale;
         c->yuv2planeX = t1_planeX;
         c->yuv2plane1 = t1_plane1;
         return;
     }
-    if (!taken(c) || c->hyscale_fast) return;
+    /* rgb24: yuv420p as before (taken(): also contexts with range conversion, which swscale() applies between the loops); the other sources
+     * where src_format() takes them */
+    if (!(taken(c) || fmt == 0) || c->hyscale_fast) return;
     if (!device_ready()) return;                                /* no usable MI355X: the reference's functions stay */
     /* only what the reference set to the functions these shims restate (a context whose selectors left one of them empty
      * uses another template) */
     if (!c->hyScale || !c->hcScale || !c->yuv2packedX || !c->yuv2packed2 || !c->yuv2packed1) return;
-    c->hyScale = c->hcScale = t1_hscale;
+    c->hyScale = c->hcScale = s.depth > 8 ? t1_hscale16 : t1_hscale;
     c->yuv2packedX = t1_packedX;
     c->yuv2packed2 = t1_packed2;
     c->yuv2packed1 = t1_packed1;
@@ -191,6 +276,7 @@ typedef struct Bound {
     SwsFunc real;                 /* what the reference chose */
     int special;                  /* ... through ff_yuv2rgb_get_func_ptr */
     int planar;                   /* MI355_SWS_DST_* of a planar context (mi355_sws_scale_planar), 0 for rgb24 */
+    int other;                    /* a source other than 8-bit yuv420p: described by mi355_sws_describe_src, built by mi355_sws_create_src */
     mi355_sws_ctx *dev;
     int failed;                   /* the device side does not take this context: the reference's function from now on */
     int busy;                     /* calls of mi355_sws_scale in flight on `dev` (under bound_mu): the device context is destroyed only at 0 */
@@ -237,13 +323,19 @@ static Bound *bound_find(SwsContext *c, int create)
 /* a selector runs for this context: sws_init_context() of a new context — possibly at the address of one that was freed */
 static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
 {
-    const int planar = special ? 0 : planar_format(c);
-    if (!real || !(taken(c) || planar) || getenv("MI355_SWS_PLAIN")) return real;
+    int planar = special ? 0 : planar_format(c), other = 0;
+    if (!(taken(c) || planar)) {
+        mi355_sws_src s;
+        const int fmt = src_format(c, &s, special);
+        if (fmt < 0) return real;
+        other = 1; planar = fmt;
+    }
+    if (!real || getenv("MI355_SWS_PLAIN")) return real;
     pthread_mutex_lock(&bound_mu);
     Bound *b = bound_find(c, 1);
     if (b) {
         slot_release(b);
-        b->c = c; b->real = real; b->special = special; b->planar = planar; b->stamp = ++n_stamp;
+        b->c = c; b->real = real; b->special = special; b->planar = planar; b->other = other; b->stamp = ++n_stamp;
     }
     pthread_mutex_unlock(&bound_mu);
     return b ? mi355_swsfunc_entry : real;
@@ -259,14 +351,21 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
      * pictures — vf_vflip makes them — and those go to the reference's function) */
     /* a planar context: all three destination planes; range conversion set since the context was bound (sws_setColorspaceDetails) is
      * the reference's for that picture */
-    const int planar_ok = b && b->planar && dstStride[1] > 0 && dstStride[2] > 0 && planar_format(c) == b->planar;
+    mi355_sws_src s_now;
+    const int planar_ok = b && b->planar && dstStride[1] > 0 && dstStride[2] > 0 &&
+                          (b->other ? src_format(c, &s_now, 0) : planar_format(c)) == b->planar;
+    /* an rgb24 context of another source: range conversion set since it was bound is the reference's for that picture, as above */
+    const int other_ok = !b || !b->other || b->planar || src_format(c, &s_now, b->special) == 0;
     if (b && !b->failed && srcSliceY == 0 && srcSliceH == c->srcH &&
-        srcStride[0] > 0 && srcStride[1] > 0 && srcStride[2] > 0 && dstStride[0] > 0 && (!b->planar || planar_ok)) {
+        srcStride[0] > 0 && srcStride[1] > 0 && srcStride[2] > 0 && dstStride[0] > 0 && (!b->planar || planar_ok) && other_ok) {
         if (b->dev && !b->busy && !b->planar && (memcmp(b->y_table, c->yuvTable, 1024) || b->gv0 != c->table_gV[0])) { mi355_sws_destroy(b->dev); b->dev = NULL; }
         if (!b->dev) {
             mi355_sws_desc d;
             int fmt;
-            if (b->planar) {
+            if (b->other) {
+                mi355_sws_src s;
+                if (device_ready() && describe_src(c, &d, &s, &fmt, b->special) == 0 && fmt == b->planar) b->dev = mi355_sws_create_src(&d, &s, fmt);
+            } else if (b->planar) {
                 if (device_ready() && mi355_sws_describe_planar(c, &d, &fmt) == 0) b->dev = mi355_sws_create_planar(&d, fmt);
             } else if (device_ready() && describe(c, &d, b->special) == 0) b->dev = mi355_sws_create(&d);
             if (b->dev && !b->planar) { memcpy(b->y_table, c->yuvTable, 1024); b->gv0 = c->table_gV[0]; }

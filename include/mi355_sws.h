@@ -115,11 +115,42 @@ int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *ctx, const mi355_sws_planar
 int mi355_sws_scale_planar(mi355_sws_ctx *ctx, const uint8_t *const src[3], const int src_stride[3],
                            uint8_t *const dst[3], const int dst_stride[3]);
 
+/* ---- other sources: planar yuv 4:2:0 / 4:2:2 / 4:4:4 at 8, 9 or 10 bits (yuv420p ... yuv444p10le) -----------------------------------------
+ * The descriptor is the one above as the reference's init built it for that source (chrSrcW / chrSrcH and the four banks follow the
+ * subsampling, utils.c:1035-1040).  A source deeper than 8 bits takes hScale16To15_c (swscale.c:110-130) in place of hScale8To15_c, and an
+ * 8-bit planar destination is then dithered (should_dither :389, :553-556): the 8x8 rows are an input like the banks (ff_dither_8x8_128).
+ * Samples deeper than 8 bits are uint16_t, little endian, BELOW 1 << depth (what a decoder writes; the sums then stay inside an int as the
+ * reference's do) — larger values are outside the contract.  Source pointers stay const uint8_t * and strides are bytes; for 16-bit samples
+ * both must be even.  The alignment paragraph above mi355_sws_frame holds unchanged in bytes: a plane whose pointer and stride are multiples
+ * of 16 is fetched in aligned 16-byte pieces (eight samples) and must be readable over its whole stride; a plane on 4-byte multiples is
+ * staged in dwords; any other (2-byte multiples) is read sample by sample. */
+typedef struct mi355_sws_src {
+    int depth;                    /* 8, 9 or 10 */
+    int hsub, vsub;               /* chroma shifts: 1,1 4:2:0; 1,0 4:2:2; 0,0 4:4:4 */
+    uint8_t dither[8][8];         /* read for a planar destination with depth > 8 */
+} mi355_sws_src;
+/* dst_format 0: rgb24 (a context for mi355_sws_scale / mi355_sws_scale_frames_dev), else MI355_SWS_DST_* (for the planar entry points).
+ * NULL (and a message) for banks the device tiles cannot hold and for combinations outside the list above; the unscaled special converter
+ * (desc->unscaled_special) takes 8-bit 4:2:0 and 4:2:2 only.  depth 8, shifts 1,1 builds the context of mi355_sws_create /
+ * mi355_sws_create_planar. */
+mi355_sws_ctx *mi355_sws_create_src(const mi355_sws_desc *desc, const mi355_sws_src *src, int dst_format);
+/* the source side of a context (read only) */
+typedef struct mi355_sws_source_info {
+    int depth, hsub, vsub;
+    int hstaged;                  /* a tile kernel whose horizontal pass stages source spans in LDS for this context: monotonic positions, every tap
+                                   * inside its line, a plane whose filter is not the identity and a tile of it whose span fits a staged line
+                                   * (planes on 4-byte multiples; the others, and the other contexts, read sample by sample) */
+} mi355_sws_source_info;
+int mi355_sws_source(const mi355_sws_ctx *ctx, mi355_sws_source_info *info);   /* 0, -1 bad argument */
+
 /* ---- the individual inner loops (Tier 1, host pointers), argument lists of the reference's
  * function-pointer types minus the SwsContext ------------------------------------------------ */
 /* hScale8To15_c swscale.c:133-147 (c->hyScale / c->hcScale) */
 void mi355_sws_hscale8to15(int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter,
                            const int32_t *filterPos, int filterSize);
+/* hScale16To15_c swscale.c:110-130: uint16_t samples below 1 << depth (9 ... 15), the shift behind the sum is depth - 1 */
+void mi355_sws_hscale16to15(int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter,
+                            const int32_t *filterPos, int filterSize, int depth);
 /* yuv2planeX_8_c output.c:242-255, yuv2plane1_8_c :257-266 */
 void mi355_sws_yuv2planeX_8(const int16_t *filter, int filterSize, const int16_t **src, uint8_t *dest, int dstW,
                             const uint8_t *dither, int offset);

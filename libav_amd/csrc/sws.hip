@@ -1,5 +1,7 @@
 /*
- * sws.hip — the libswscale part of the path for yuv420p -> rgb24 and yuv420p -> yuv420p / yuv422p / yuv444p:
+ * sws.hip — the libswscale part of the path: planar yuv 4:2:0 / 4:2:2 / 4:4:4 sources at 8, 9 or 10 bits (16-bit
+ * little-endian samples above 8: hScale16To15_c swscale.c:110-130 in place of hScale8To15_c) -> rgb24 and -> 8-bit yuv420p / yuv422p / yuv444p
+ * (dithered from a deeper source, swscale.c:553-556):
  *   k_sws_generic   the generic scaler of swscale() (libswscale/swscale.c:343-722) for whole pictures,
  *                   fused per output tile: horizontal 8->15 bit FIR of the source lines the tile needs
  *                   (hScale8To15_c :133-147) into LDS, vertical FIR + yuv->rgb LUT
@@ -7,7 +9,10 @@
  *                   written as dwords.  No int16 intermediate ever goes to HBM.
  *   k_sws_planar    the same loop's planar branch (swscale.c:618-645, yuv2planeX_8_c / yuv2plane1_8_c output.c:242-266): the
  *                   horizontal pass into LDS as above, the vertical pass from LDS straight to the three destination planes.
- *   k_sws_c24       the unscaled converter yuv2rgb_c_24_rgb (yuv2rgb.c:335-363).
+ *   k_sws_c24       the unscaled converter yuv2rgb_c_24_rgb (yuv2rgb.c:335-363) for 8-bit yuv420p and yuv422p.
+ *   k_sws_ident1    the generic scaler on an 8-bit context that does not scale, from the source bytes.
+ * The tile kernels are instantiated per sample type: the uint16_t instances differ in the horizontal pass (its staging lines are twice
+ * as long, so is their LDS) and, for planar destinations, in the dither rows.
  *   k_sws_line_*    the individual inner loops for the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
  * Execution model: 256-thread workgroups (4 waves) sharing one LDS tile; integer only, no MFMA.
@@ -40,6 +45,10 @@ struct SwsDev {
     mi355_sws_luts luts;
     /* planar destinations (mi355_sws_create_planar): the MI355_SWS_DST_* format, its chroma subsampling and chroma rows (0 / 0 / 0 / dstH for rgb24) */
     int planar, hshift, vshift, chrDstH;
+    /* the source side (mi355_sws_create_src): bits per sample (8: bytes; 9 / 10: uint16_t little endian), its chroma shifts, and the 8x8
+     * dither rows a planar destination takes from a source deeper than 8 bits (swscale.c:553-556) */
+    int depth, src_hsub, src_vsub, pad_;
+    __attribute__((aligned(8))) uint8_t dither[8][8];
 };
 
 struct LutLds {
@@ -116,14 +125,19 @@ __device__ __forceinline__ void rgb24_store8(const LutLds &t, uint8_t *d, const 
 }
 __device__ __forceinline__ int packed_mode(int ls, int cs) { return (ls == 1 && cs <= 2) ? 1 : ((ls == 2 && cs == 2) ? 2 : 0); }  /* swscale.c:658-682 */
 
-/* hScale8To15_c swscale.c:133-147 for one output sample */
-__device__ __forceinline__ int hscale_one(const uint8_t *src, const int16_t *f, int pos, int fs)
+/* hScale8To15_c swscale.c:133-147 for one output sample; ST uint16_t: hScale16To15_c :110-130, sh = depth - 1 (samples below 1 << depth:
+ * the sum stays inside an int) */
+template <typename ST = uint8_t>
+__device__ __forceinline__ int hscale_one(const uint8_t *src, const int16_t *f, int pos, int fs, int sh = 7)
 {
+    const ST *s = reinterpret_cast<const ST *>(src);
     int val = 0;
-    for (int j = 0; j < fs; j++) val += (int)src[pos + j] * f[j];
-    val >>= 7;
+    for (int j = 0; j < fs; j++) val += (int)s[pos + j] * f[j];
+    val >>= sh;
     return val < 32767 ? val : 32767;
 }
+/* the shift behind the horizontal sum: 7 for bytes, depth - 1 for 16-bit samples */
+template <typename ST> __device__ __forceinline__ int hscale_shift(int depth) { return sizeof(ST) == 1 ? 7 : depth - 1; }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
@@ -153,10 +167,15 @@ constexpr int SRC_DW = 76;            /* dwords per staged line: 2:1 with 8 taps
 constexpr int STAGE_BYTES = (int)sizeof(uint32_t) * SG * SRC_DW;
 /* a chroma tile row is half as wide: its staged lines are about half as long (64 * 2 + 8 bytes + the 15 of a 16-byte aligned start) and a
  * round holds half as many again in the same storage (the 20 chroma lines of a 2:1 reduction: one round instead of two) */
-template <int COLS> struct StageGeom {
-    static constexpr int PITCH = COLS == TW ? SRC_DW : 40;             /* dwords per staged line: a multiple of four (16-byte LDS stores) */
+/* 16-bit samples: the same spans are twice as many bytes — (128 * 2 + 8) * 2 bytes + the 15 of an aligned start and the two dwords of slack;
+ * a chroma tile row (64 * 2 + 8) * 2 + 15.  The same number of lines per round, so a 16-bit instance's staging storage is its own size. */
+constexpr int SRC_DW16 = 140;
+constexpr int STAGE_BYTES16 = (int)sizeof(uint32_t) * SG * SRC_DW16;
+template <typename ST> __host__ __device__ constexpr int stage_bytes() { return sizeof(ST) == 1 ? STAGE_BYTES : STAGE_BYTES16; }
+template <int COLS, typename ST = uint8_t> struct StageGeom {
+    static constexpr int PITCH = sizeof(ST) == 1 ? (COLS == TW ? SRC_DW : 40) : (COLS == TW ? SRC_DW16 : 76);   /* dwords per staged line: a multiple of four (16-byte LDS stores) */
     static constexpr int LINES = COLS == TW ? SG : (3 * SG) / 2;       /* staged lines per round */
-    static_assert(PITCH % 4 == 0 && (size_t)PITCH * LINES * sizeof(uint32_t) <= (size_t)STAGE_BYTES, "a round fits the staging storage");
+    static_assert(PITCH % 4 == 0 && (size_t)PITCH * LINES * sizeof(uint32_t) <= (size_t)stage_bytes<ST>(), "a round fits the staging storage");
 };
 constexpr int OUT_ROWS = STAGE_BYTES / (TW * 3);            /* rows of a narrow tile written per pass (they reuse the staging lines) */
 static_assert(OUT_ROWS >= 8, "the narrow form needs at most two passes over a tile of MAXTH rows");
@@ -194,9 +213,41 @@ __device__ __forceinline__ uint32_t sws_opaque(uint32_t v)
  * three aligned dwords funnel-shifted into two, expanded to four 16-bit pairs and multiplied with the coefficient pairs
  * (3 LDS reads and 10 arithmetic instructions per output instead of 8 byte reads and 8 multiply-adds).  Products and sums
  * are the same integers (samples 0..255, coefficients 16 bits, |sum| < 2^31). */
-template <int COLS, int OP = COLS>
-__device__ __forceinline__ void hscale_lines8(const uint8_t *row0, int16_t *out0, const uint32_t *cp, int left)
+template <int COLS, int OP = COLS, typename ST = uint8_t>
+__device__ __forceinline__ void hscale_lines8(const uint8_t *row0, int16_t *out0, const uint32_t *cp, int left, int hsh = 7)
 {
+    if constexpr (sizeof(ST) == 2) {
+        /* 16-bit samples are already the lanes of the dot product: a line's eight samples are five aligned dwords funnel-shifted by
+         * the column's odd sample (two bytes) into four pairs */
+        constexpr int per = NT / COLS;
+        const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(row0) & 3);
+        const uint32_t *w0 = reinterpret_cast<const uint32_t *>(row0 - sh);
+        const uint32_t c01 = cp[0], c23 = cp[1], c45 = cp[2], c67 = cp[3];
+        constexpr int N = StageGeom<COLS, ST>::LINES / per, G = N % 4 == 0 ? 4 : 3, PITCH = StageGeom<COLS, ST>::PITCH;
+        static_assert(StageGeom<COLS, ST>::LINES % per == 0 && N % G == 0, "whole groups of lines");
+#pragma unroll
+        for (int g = 0; g < N; g += G) {
+            if (g * per > left) break;
+            uint32_t d[G][5];
+#pragma unroll
+            for (int q = 0; q < G; q++) {
+                const uint32_t *w = w0 + (g + q) * per * PITCH;
+#pragma unroll
+                for (int k = 0; k < 5; k++) d[q][k] = w[k];
+            }
+#pragma unroll
+            for (int q = 0; q < G; q++) {
+                if ((g + q) * per > left) break;
+                int v = sws_dot2(sws_alignbyte(d[q][1], d[q][0], sh), c01, 0);
+                v = sws_dot2(sws_alignbyte(d[q][2], d[q][1], sh), c23, v);
+                v = sws_dot2(sws_alignbyte(d[q][3], d[q][2], sh), c45, v);
+                v = sws_dot2(sws_alignbyte(d[q][4], d[q][3], sh), c67, v);
+                v >>= hsh;
+                out0[(g + q) * per * OP] = (int16_t)(v < 32767 ? v : 32767);
+            }
+        }
+        return;
+    }
     constexpr int per = NT / COLS;
     const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(row0) & 3);
     const uint32_t *w0 = reinterpret_cast<const uint32_t *>(row0 - sh);
@@ -229,32 +280,53 @@ __device__ __forceinline__ void hscale_lines8(const uint8_t *row0, int16_t *out0
         }
     }
 }
-template <int COLS, int TAPS, int OP = COLS>
-__device__ __forceinline__ void hscale_lines(const uint8_t *row0, int16_t *out0, const uint32_t *cp, int left)
+template <int COLS, int TAPS, int OP = COLS, typename ST = uint8_t>
+__device__ __forceinline__ void hscale_lines(const uint8_t *row0, int16_t *out0, const uint32_t *cp, int left, int hsh = 7)
 {
     constexpr int per = NT / COLS;
     int cf[TAPS];
 #pragma unroll
     for (int j = 0; j < TAPS; j++) cf[j] = (int16_t)(cp[j >> 1] >> (16 * (j & 1)));
 #pragma unroll
-    for (int k = 0; k < StageGeom<COLS>::LINES / per; k++) {
+    for (int k = 0; k < StageGeom<COLS, ST>::LINES / per; k++) {
         if (k * per > left) break;
-        const uint8_t *row = row0 + k * per * (StageGeom<COLS>::PITCH * 4);
+        const ST *row = reinterpret_cast<const ST *>(row0 + k * per * (StageGeom<COLS, ST>::PITCH * 4));
         int val = 0;
 #pragma unroll
         for (int j = 0; j < TAPS; j++) val += (int)row[j] * cf[j];
-        val >>= 7;
+        val >>= hsh;
         out0[k * per * OP] = (int16_t)(val < 32767 ? val : 32767);
     }
 }
 /* OP: int16 samples per line of `out` (a line may hold two planes' tiles side by side) */
-template <int COLS, int OP = COLS>
+/* ST: the source's sample type (uint8_t, or uint16_t for 9 / 10 bit: `depth`); srcW in samples, stride in bytes */
+template <int COLS, int OP = COLS, typename ST = uint8_t>
 __device__ __forceinline__ void hscale_tile(int16_t (*out)[OP], const uint8_t *src, int stride, int srcW, const int32_t *posT,
                                             const int16_t *coefT, int fs, int gx0, int ncols, int lo, int hi,
-                                            uint32_t *stage_mem, int tid, bool zero_tail, bool may_stage, bool identity)
+                                            uint32_t *stage_mem, int tid, bool zero_tail, bool may_stage, bool identity, int depth = 8)
 {
-    constexpr int PITCH = StageGeom<COLS>::PITCH, LINES = StageGeom<COLS>::LINES;
+    constexpr int PITCH = StageGeom<COLS, ST>::PITCH, LINES = StageGeom<COLS, ST>::LINES, B = (int)sizeof(ST);
+    const int hsh = hscale_shift<ST>(depth);
     uint32_t (*stage)[PITCH] = reinterpret_cast<uint32_t (*)[PITCH]>(stage_mem);
+    if constexpr (B == 2) if (identity) {
+        /* one tap of 1 << 14 at position i: (src * 16384) >> (depth - 1) = src << (15 - depth), below the clamp for samples below
+         * 1 << depth; two samples a dword, shifted in place.  Eight columns per thread: one 16-byte load, one 16-byte LDS write */
+        constexpr int TPL = COLS / 8;
+        const int xg = 8 * (tid % TPL), gxi = gx0 + xg, up = 15 - depth;
+        const bool al16 = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride | (uintptr_t)(2 * gx0)) & 15) == 0;
+        for (int l = lo + tid / TPL; l <= hi; l += NT / TPL) {
+            const uint8_t *p = src + (size_t)l * stride + 2 * gxi;
+            sws_u32x4 o = { 0u, 0u, 0u, 0u };
+            if (al16 && gxi + 8 <= srcW && gxi + 8 <= ncols) o = *reinterpret_cast<const sws_u32x4 *>(p);
+            else {
+                for (int k = 0; k < 8; k++)
+                    if (gxi + k < ncols && gxi + k < srcW) o[k >> 1] |= (uint32_t)reinterpret_cast<const uint16_t *>(p)[k] << (16 * (k & 1));
+            }
+            for (int k = 0; k < 4; k++) o[k] <<= up;
+            if (zero_tail || gxi < ncols) *reinterpret_cast<sws_u32x4 *>(&out[l - lo][xg]) = o;
+        }
+        return;
+    }
     if (identity) {
         /* one tap of 1 << 14 at position i: (src * 16384) >> 7 = src << 7 (below the 32767 clamp).  Eight columns per thread:
          * one 8-byte load (aligned planes, inside the line), one 16-byte LDS write */
@@ -291,7 +363,7 @@ __device__ __forceinline__ void hscale_tile(int16_t (*out)[OP], const uint8_t *s
     const int last = imin(gx0 + COLS, ncols) - 1;
     /* 16-byte pieces when the plane allows it, dwords otherwise */
     const bool al16 = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 15) == 0;
-    const int s0 = posT[gx0], s1 = posT[last] + fs, a0 = al16 ? (s0 & ~15) : (s0 & ~3), nd = (s1 - a0 + 3) >> 2;
+    const int s0 = B * posT[gx0], s1 = B * (posT[last] + fs), a0 = al16 ? (s0 & ~15) : (s0 & ~3), nd = (s1 - a0 + 3) >> 2;     /* bytes */
     /* the column's filter in registers as four pairs of 16-bit taps (taps past fs are zero): the line loops below multiply by
      * them instead of reloading.  Eight taps: the column's entry of the bank is one aligned 16-byte word (the banks are
      * hipMalloc'ed by mi355_sws_create) */
@@ -309,7 +381,7 @@ __device__ __forceinline__ void hscale_tile(int16_t (*out)[OP], const uint8_t *s
     const bool staged = may_stage && nd <= PITCH - 2 && s1 >= s0 && ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 3) == 0;
     if (!staged) {
         if (col_ok) {
-            for (int l = lo + tid / COLS; l <= hi; l += per) out[l - lo][x] = (int16_t)hscale_one(src + (size_t)l * stride, f, pos, fs);
+            for (int l = lo + tid / COLS; l <= hi; l += per) out[l - lo][x] = (int16_t)hscale_one<ST>(src + (size_t)l * stride, f, pos, fs, hsh);
         } else if (zero_tail) {
             for (int l = lo + tid / COLS; l <= hi; l += per) out[l - lo][x] = 0;
         }
@@ -332,7 +404,7 @@ __device__ __forceinline__ void hscale_tile(int16_t (*out)[OP], const uint8_t *s
     for (int j = 0; j < PF; j++) {
         const int idx = imin(tid + j * NT, LINES * np - 1), r = mi355_div20(idx, inv), d = idx - r * np, off = a0 + 16 * d;
         p_row[j] = r;
-        p_col[j] = imin(off, (srcW - 1) & ~15);
+        p_col[j] = imin(off, (B * srcW - 1) & ~15);
         p_lds[j] = &stage[r][4 * d];
     }
     auto fetch16 = [&](int base) {
@@ -364,10 +436,10 @@ __device__ __forceinline__ void hscale_tile(int16_t (*out)[OP], const uint8_t *s
             if (line > hi) continue;
             const uint8_t *p = src + (size_t)line * stride + a0 + 4 * d;
             uint32_t w;
-            if (a0 + 4 * d + 4 <= srcW) w = *reinterpret_cast<const uint32_t *>(p);
+            if (a0 + 4 * d + 4 <= B * srcW) w = *reinterpret_cast<const uint32_t *>(p);
             else {
                 w = 0;
-                for (int b = 0; b < 4; b++) if (a0 + 4 * d + b < srcW) w |= (uint32_t)p[b] << (8 * b);
+                for (int b = 0; b < 4; b++) if (a0 + 4 * d + b < B * srcW) w |= (uint32_t)p[b] << (8 * b);
             }
             stage[r][d] = w;
         }
@@ -380,21 +452,21 @@ __device__ __forceinline__ void hscale_tile(int16_t (*out)[OP], const uint8_t *s
          * immediate offsets from one base each; tap count rounded up to 1 / 2 / 4 / 8 (taps past fs are zero, the
          * bytes exist: slack) */
         const int r0 = tid / COLS;
-        const uint8_t *row0 = reinterpret_cast<const uint8_t *>(stage[r0]) + (pos - a0);
+        const uint8_t *row0 = reinterpret_cast<const uint8_t *>(stage[r0]) + (B * pos - a0);
         int16_t *out0 = &out[base + r0 - lo][x];
         const int left = uniform(hi - base - r0);            /* lines r0, r0 + per, ... while k * per <= left (r0: one value per wave) */
 #ifndef MI355_SWS_EXP_NOLINES
         if (col_ok) {
-            if (fs == 1) hscale_lines<COLS, 1, OP>(row0, out0, cp, left);
-            else if (fs <= 2) hscale_lines<COLS, 2, OP>(row0, out0, cp, left);
-            else if (fs <= 4) hscale_lines<COLS, 4, OP>(row0, out0, cp, left);
-            else if (fs <= 8) hscale_lines8<COLS, OP>(row0, out0, cp, left);
+            if (fs == 1) hscale_lines<COLS, 1, OP, ST>(row0, out0, cp, left, hsh);
+            else if (fs <= 2) hscale_lines<COLS, 2, OP, ST>(row0, out0, cp, left, hsh);
+            else if (fs <= 4) hscale_lines<COLS, 4, OP, ST>(row0, out0, cp, left, hsh);
+            else if (fs <= 8) hscale_lines8<COLS, OP, ST>(row0, out0, cp, left, hsh);
             else {
                 for (int k = 0; k < LINES / per && k * per <= left; k++) {
-                    const uint8_t *row = row0 + k * per * (PITCH * 4);
+                    const ST *row = reinterpret_cast<const ST *>(row0 + k * per * (PITCH * 4));
                     int val = 0;
                     for (int j = 0; j < fs; j++) val += (int)row[j] * f[j];
-                    val >>= 7;
+                    val >>= hsh;
                     out0[k * per * OP] = (int16_t)(val < 32767 ? val : 32767);
                 }
             }
@@ -558,9 +630,9 @@ __device__ __forceinline__ void vertical_rows(const SwsDev &c, const LutLds &lut
 
 /* LDS of a workgroup, sized per context (sws_plan): the horizontal pass's results for the source lines a tile needs, the tables, and one
  * block shared by the staging lines (horizontal pass) and the output rows of tiles that cannot store from registers (after it). */
-__host__ __device__ constexpr int sws_lds_bytes(int lum_lines, int chr_lines)
+__host__ __device__ constexpr int sws_lds_bytes(int lum_lines, int chr_lines, int stage = STAGE_BYTES)
 {
-    return lum_lines * TW * 2 + 2 * chr_lines * (TW / 2) * 2 + (int)sizeof(LutLds) + STAGE_BYTES;
+    return lum_lines * TW * 2 + 2 * chr_lines * (TW / 2) * 2 + (int)sizeof(LutLds) + stage;
 }
 
 /* the sixteen tap-count instances of vertical_rows (taps in registers, rounded up to 1 / 2 / 4 / 8) */
@@ -638,7 +710,8 @@ __device__ __forceinline__ void vertical_narrow(const SwsDev *cp, const LutLds *
 
 /* LCAP / CCAP: source lines the LDS tile holds — the context's largest tile span picks the instance (sws_launch), and with it how
  * many workgroups a CU's 160 KB hold (one wave of each per SIMD); WAVES: the waves per SIMD the register allocation then aims at */
-template <int LCAP, int CCAP, int WAVES>
+/* ST: the source's sample type; the uint16_t instances (9 / 10 bit sources) differ in the horizontal pass and its staging lines only */
+template <int LCAP, int CCAP, int WAVES, typename ST = uint8_t>
 #ifndef MI355_HIP_EMU_H
 __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
 #endif
@@ -648,7 +721,7 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
     __shared__ __attribute__((aligned(16))) int16_t s_cu[CCAP][TW / 2], s_cv[CCAP][TW / 2];
     __shared__ LutLds s_lut;
     /* the staging lines of the horizontal pass; the output rows of tiles that cannot store from registers reuse them after it */
-    __shared__ __attribute__((aligned(16))) uint8_t s_io[STAGE_BYTES];
+    __shared__ __attribute__((aligned(16))) uint8_t s_io[stage_bytes<ST>()];
     uint8_t (*s_out)[TW * 3] = reinterpret_cast<uint8_t (*)[TW * 3]>(s_io);
     SwsDev c = *cp;                                   /* pointers of the records: global address space (mi355_rt.h) */
     c.hLumC = mi355_global(c.hLumC); c.hChrC = mi355_global(c.hChrC); c.vLumC = mi355_global(c.vLumC); c.vChrC = mi355_global(c.vChrC);
@@ -669,9 +742,9 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
      * zero-initialised tail of the reference's line buffer, utils.c:1241-1262), then the chroma planes */
     uint32_t *s_stage = reinterpret_cast<uint32_t *>(s_io);
 #ifndef MI355_SWS_NO_H
-    hscale_tile<TW>(s_lum, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi, s_stage, tid, true, c.hstage != 0, c.hident_l != 0);
-    hscale_tile<TW / 2>(s_cu, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0);
-    hscale_tile<TW / 2>(s_cv, fr.src[2], fr.src_stride[2], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0);
+    hscale_tile<TW, TW, ST>(s_lum, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi, s_stage, tid, true, c.hstage != 0, c.hident_l != 0, c.depth);
+    hscale_tile<TW / 2, TW / 2, ST>(s_cu, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, c.depth);
+    hscale_tile<TW / 2, TW / 2, ST>(s_cv, fr.src[2], fr.src_stride[2], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, c.depth);
 #endif
     __syncthreads();
     /* vertical pass + LUT */
@@ -705,9 +778,12 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
  * lanes cover one line's 256 bytes, so each 16-lane group of a ds_read_b128 meets every bank once, whichever lines the rows read.
  * NTAP: 1 plane1; 2 / 4 / 8 planeX with the taps in registers (taps past fs carry a zero coefficient); 0 planeX with fs taps read as it goes.
  * GPP: 16-byte groups of a plane's tile row; NP: planes side by side in an LDS line (chroma: U | V). */
-template <int NTAP, int GPP, int NP>
+/* DITH (a source deeper than 8 bits, should_dither swscale.c:389): the row's eight dither values come from the context's 8x8 table — row
+ * y & 7 of the plane's own row counter (dstY for luma, chrDstY for chroma, :553-556), V read three columns on (:636-644); a group starts
+ * on a multiple of eight columns, so sample k of a group takes value (k + offset) & 7. */
+template <int NTAP, int GPP, int NP, bool DITH = false>
 __device__ __forceinline__ void planar_rows(const int16_t *s, int lo, int maxl, const int16_t *vC, const int32_t *vP, int fs, int row0, int nrows,
-                                            int gx0, int width, uint8_t *d0, int st0, uint8_t *d1, int st1, int tid)
+                                            int gx0, int width, uint8_t *d0, int st0, uint8_t *d1, int st1, int tid, const uint8_t (*dith)[8] = nullptr)
 {
     constexpr int G = GPP * NP;                        /* groups per LDS line */
     for (int t = tid; t < nrows * G; t += NT) {
@@ -717,14 +793,24 @@ __device__ __forceinline__ void planar_rows(const int16_t *s, int lo, int maxl, 
         const int16_t *col = s + 8 * g;
         auto line = [&](int j) { return *reinterpret_cast<const sws_u32x4 *>(col + (size_t)(clampi(first + j, 0, maxl) - lo) * (G * 8)); };
         auto sample = [](const sws_u32x4 &a, int k) { return (int)(int16_t)(a[k >> 1] >> (16 * (k & 1))); };
-        int v[8];
+        int v[8], dv[8];
+        if (DITH) {
+            const sws_u32x2 w = *reinterpret_cast<const sws_u32x2 *>(dith[y & 7]);
+            uint64_t q = ((uint64_t)w[1] << 32) | w[0];
+            if (NP > 1 && g >= GPP) q = (q >> 24) | (q << 40);      /* the V plane: offset 3 */
+#pragma unroll
+            for (int k = 0; k < 8; k++) dv[k] = (int)((q >> (8 * k)) & 0xFF);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++) dv[k] = 64;
+        }
         if (NTAP == 1) {
             const sws_u32x4 a = line(0);
 #pragma unroll
-            for (int k = 0; k < 8; k++) v[k] = (sample(a, k) + 64) >> 7;
+            for (int k = 0; k < 8; k++) v[k] = (sample(a, k) + dv[k]) >> 7;
         } else {
 #pragma unroll
-            for (int k = 0; k < 8; k++) v[k] = 64 << 12;
+            for (int k = 0; k < 8; k++) v[k] = dv[k] << 12;
             if (NTAP == 0) {
                 for (int j = 0; j < fs; j++) {
                     const int f = vC[(size_t)y * fs + j];
@@ -770,40 +856,41 @@ __device__ __forceinline__ void planar_rows(const int16_t *s, int lo, int maxl, 
     }
 }
 /* the vertical pass of one LDS tile: its tap count rounded up to 1 / 2 / 4 / 8, more from memory */
-template <int GPP, int NP>
+template <int GPP, int NP, bool DITH = false>
 __device__ __forceinline__ void planar_pass(const int16_t *s, int lo, int maxl, const int16_t *vC, const int32_t *vP, int fs, int row0, int nrows,
-                                            int gx0, int width, uint8_t *d0, int st0, uint8_t *d1, int st1, int tid)
+                                            int gx0, int width, uint8_t *d0, int st0, uint8_t *d1, int st1, int tid, const uint8_t (*dith)[8] = nullptr)
 {
-    if (fs == 1) planar_rows<1, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid);
-    else if (fs <= 2) planar_rows<2, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid);
-    else if (fs <= 4) planar_rows<4, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid);
-    else if (fs <= 8) planar_rows<8, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid);
-    else planar_rows<0, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid);
+    if (fs == 1) planar_rows<1, GPP, NP, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, dith);
+    else if (fs <= 2) planar_rows<2, GPP, NP, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, dith);
+    else if (fs <= 4) planar_rows<4, GPP, NP, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, dith);
+    else if (fs <= 8) planar_rows<8, GPP, NP, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, dith);
+    else planar_rows<0, GPP, NP, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, dith);
 }
 
 /* LDS of a planar workgroup: the luma lines, the chroma lines (U | V side by side, CW samples each) and the staging lines; no LUT, no output rows */
-__host__ __device__ constexpr int sws_planar_lds_bytes(int lum_lines, int chr_lines, int cw)
+__host__ __device__ constexpr int sws_planar_lds_bytes(int lum_lines, int chr_lines, int cw, int stage = STAGE_BYTES)
 {
-    return lum_lines * TW * 2 + chr_lines * 2 * cw * 2 + STAGE_BYTES;
+    return lum_lines * TW * 2 + chr_lines * 2 * cw * 2 + stage;
 }
-__host__ __device__ constexpr int sws_planar_waves(int lum_lines, int chr_lines, int cw)
+__host__ __device__ constexpr int sws_planar_waves(int lum_lines, int chr_lines, int cw, int stage = STAGE_BYTES)
 {
-    return 160 * 1024 / sws_planar_lds_bytes(lum_lines, chr_lines, cw) < 8 ? 160 * 1024 / sws_planar_lds_bytes(lum_lines, chr_lines, cw) : 8;
+    return 160 * 1024 / sws_planar_lds_bytes(lum_lines, chr_lines, cw, stage) < 8 ? 160 * 1024 / sws_planar_lds_bytes(lum_lines, chr_lines, cw, stage) : 8;
 }
 
 /* One workgroup per output tile of TW luma columns x th luma rows (blockIdx.z: the picture of the batch).  The tile's chroma is CW = TW >> hshift
  * columns and the chroma rows cy with cy << vshift inside the tile's rows (swscale.c:618-645: a chroma row is written with the luma row
  * cy << vshift, chrSkipMask).  Horizontal pass of the source lines the tile needs into LDS (hscale_tile, as k_sws_generic), then the
  * vertical pass from LDS straight to the three planes. */
-template <int LCAP, int CCAP, int CW>
+template <int LCAP, int CCAP, int CW, typename ST = uint8_t>
 #ifndef MI355_HIP_EMU_H
-__attribute__((amdgpu_waves_per_eu(sws_planar_waves(LCAP, CCAP, CW), sws_planar_waves(LCAP, CCAP, CW))))
+__attribute__((amdgpu_waves_per_eu(sws_planar_waves(LCAP, CCAP, CW, stage_bytes<ST>()), sws_planar_waves(LCAP, CCAP, CW, stage_bytes<ST>()))))
 #endif
 __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355_sws_planar_frame *frames)
 {
+    constexpr bool DITH = sizeof(ST) == 2;            /* a source deeper than 8 bits dithers its 8-bit planes */
     __shared__ __attribute__((aligned(16))) int16_t s_lum[LCAP][TW];
     __shared__ __attribute__((aligned(16))) int16_t s_chr[CCAP][2 * CW];
-    __shared__ __attribute__((aligned(16))) uint32_t s_stage[STAGE_BYTES / 4];
+    __shared__ __attribute__((aligned(16))) uint32_t s_stage[stage_bytes<ST>() / 4];
     SwsDev c = *cp;
     c.hLumC = mi355_global(c.hLumC); c.hChrC = mi355_global(c.hChrC); c.vLumC = mi355_global(c.vLumC); c.vChrC = mi355_global(c.vChrC);
     c.hLumP = mi355_global(c.hLumP); c.hChrP = mi355_global(c.hChrP); c.vLumP = mi355_global(c.vLumP); c.vChrP = mi355_global(c.vChrP);
@@ -815,22 +902,23 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
     const int ls = c.vls, cs = c.vcs;
     /* source lines the tile needs (swscale.c:459-468 for the first tap, :571-616 for the clamping) */
     const int llo = clampi(imax(1 - ls, c.vLumP[y0]), 0, c.srcH - 1), lhi = clampi(imax(1 - ls, c.vLumP[y1]) + ls - 1, 0, c.srcH - 1);
-    hscale_tile<TW>(s_lum, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi, s_stage, tid, false, c.hstage != 0, c.hident_l != 0);
+    hscale_tile<TW, TW, ST>(s_lum, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi, s_stage, tid, false, c.hstage != 0, c.hident_l != 0, c.depth);
     int clo = 0;
     if (cy0 <= cy1) {
         clo = clampi(imax(1 - cs, c.vChrP[cy0]), 0, c.chrSrcH - 1);
         const int chi = clampi(imax(1 - cs, c.vChrP[cy1]) + cs - 1, 0, c.chrSrcH - 1);
-        hscale_tile<CW, 2 * CW>(s_chr, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false,
-                                c.hstage != 0, c.hident_c != 0);
-        hscale_tile<CW, 2 * CW>(reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]), fr.src[2], fr.src_stride[2], c.chrSrcW, c.hChrP, c.hChrC, c.hcs,
-                                x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0);
+        hscale_tile<CW, 2 * CW, ST>(s_chr, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false,
+                                    c.hstage != 0, c.hident_c != 0, c.depth);
+        hscale_tile<CW, 2 * CW, ST>(reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]), fr.src[2], fr.src_stride[2], c.chrSrcW, c.hChrP, c.hChrC, c.hcs,
+                                    x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, c.depth);
     }
     __syncthreads();
-    planar_pass<TW / 8, 1>(&s_lum[0][0], llo, c.srcH - 1, c.vLumC, c.vLumP, ls, y0, y1 - y0 + 1, x0, c.dstW,
-                           fr.dst[0] + (size_t)y0 * fr.dst_stride[0], fr.dst_stride[0], nullptr, 0, tid);
+    const uint8_t (*dith)[8] = DITH ? mi355_global(cp)->dither : nullptr;
+    planar_pass<TW / 8, 1, DITH>(&s_lum[0][0], llo, c.srcH - 1, c.vLumC, c.vLumP, ls, y0, y1 - y0 + 1, x0, c.dstW,
+                                 fr.dst[0] + (size_t)y0 * fr.dst_stride[0], fr.dst_stride[0], nullptr, 0, tid, dith);
     if (cy0 <= cy1)
-        planar_pass<CW / 8, 2>(&s_chr[0][0], clo, c.chrSrcH - 1, c.vChrC, c.vChrP, cs, cy0, cy1 - cy0 + 1, x0 >> hs, c.chrDstW,
-                               fr.dst[1] + (size_t)cy0 * fr.dst_stride[1], fr.dst_stride[1], fr.dst[2] + (size_t)cy0 * fr.dst_stride[2], fr.dst_stride[2], tid);
+        planar_pass<CW / 8, 2, DITH>(&s_chr[0][0], clo, c.chrSrcH - 1, c.vChrC, c.vChrP, cs, cy0, cy1 - cy0 + 1, x0 >> hs, c.chrDstW,
+                                     fr.dst[1] + (size_t)cy0 * fr.dst_stride[1], fr.dst_stride[1], fr.dst[2] + (size_t)cy0 * fr.dst_stride[2], fr.dst_stride[2], tid, dith);
 }
 
 #ifndef MI355_C24_ROWS
@@ -851,6 +939,9 @@ __device__ __forceinline__ void c24_line(const LutLds &t, uint8_t *d, uint32_t y
 /* yuv2rgb_c_24_rgb (yuv2rgb.c:335-363): a block converts a 512 x 16 sample tile; a thread takes eight samples of two
  * lines per step (8-byte luma loads, 4-byte chroma loads, three 8-byte stores per line) — one (U,V) pair serves both
  * lines (LOADCHROMA :67-72, nearest chroma).  Unaligned planes and the right edge go pair by pair. */
+/* CS 1: an 8-bit yuv422p source — the reference doubles the chroma strides and so reads every other chroma line (yuv2rgb.c:133-136): line
+ * (y >> 1) << 1 at the frame's own stride */
+template <int CS = 0>
 __global__ void __launch_bounds__(NT) k_sws_c24(const mi355_sws_luts *luts, int dstW, int sliceH, int sliceY, const mi355_sws_frame *frames)
 {
     __shared__ LutLds s_lut;
@@ -876,8 +967,8 @@ __global__ void __launch_bounds__(NT) k_sws_c24(const mi355_sws_luts *luts, int 
         if (wide && y < sliceH) {
             const uint8_t *py1 = fr.src[0] + (size_t)y * fr.src_stride[0] + x;
             ya[q] = *reinterpret_cast<const sws_u32x2 *>(py1); yc[q] = *reinterpret_cast<const sws_u32x2 *>(py1 + fr.src_stride[0]);
-            u4[q] = *reinterpret_cast<const uint32_t *>(fr.src[1] + (size_t)(y >> 1) * fr.src_stride[1] + (x >> 1));
-            v4[q] = *reinterpret_cast<const uint32_t *>(fr.src[2] + (size_t)(y >> 1) * fr.src_stride[2] + (x >> 1));
+            u4[q] = *reinterpret_cast<const uint32_t *>(fr.src[1] + (size_t)((y >> 1) << CS) * fr.src_stride[1] + (x >> 1));
+            v4[q] = *reinterpret_cast<const uint32_t *>(fr.src[2] + (size_t)((y >> 1) << CS) * fr.src_stride[2] + (x >> 1));
         }
     }
     MI355_ISSUE_FENCE();
@@ -890,7 +981,7 @@ __global__ void __launch_bounds__(NT) k_sws_c24(const mi355_sws_luts *luts, int 
         const int y = blockIdx.y * C24_ROWS + 2 * rr;
         if (y >= sliceH) break;
         const uint8_t *py1 = fr.src[0] + (size_t)y * fr.src_stride[0] + x, *py2 = py1 + fr.src_stride[0];
-        const uint8_t *pu = fr.src[1] + (size_t)(y >> 1) * fr.src_stride[1] + (x >> 1), *pv = fr.src[2] + (size_t)(y >> 1) * fr.src_stride[2] + (x >> 1);
+        const uint8_t *pu = fr.src[1] + (size_t)((y >> 1) << CS) * fr.src_stride[1] + (x >> 1), *pv = fr.src[2] + (size_t)((y >> 1) << CS) * fr.src_stride[2] + (x >> 1);
         uint8_t *d1 = fr.dst + (size_t)(y + sliceY) * fr.dst_stride + (size_t)x * 3, *d2 = d1 + fr.dst_stride;
         if (wide) {
             const sws_u32x2 a = ya[q], c = yc[q];
@@ -1023,9 +1114,10 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
 }
 
 /* ---- Tier-1 line kernels ---------------------------------------------------------------------------- */
-__global__ void __launch_bounds__(NT) k_sws_line_hscale(int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *pos, int fs)
+template <typename ST = uint8_t>
+__global__ void __launch_bounds__(NT) k_sws_line_hscale(int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *pos, int fs, int sh)
 {
-    for (int i = threadIdx.x; i < dstW; i += NT) dst[i] = (int16_t)hscale_one(src, filter + (size_t)i * fs, pos[i], fs);
+    for (int i = threadIdx.x; i < dstW; i += NT) dst[i] = (int16_t)hscale_one<ST>(src, filter + (size_t)i * fs, pos[i], fs, sh);
 }
 /* yuv2planeX_8_c output.c:242-255 (fs >= 1 rows at `pitch` elements) / yuv2plane1_8_c :257-266 (fs == 0) */
 __global__ void __launch_bounds__(NT) k_sws_line_plane(const int16_t *filter, int fs, const int16_t *rows, int pitch, uint8_t *dest, int dstW,
@@ -1069,6 +1161,7 @@ struct mi355_sws_ctx {
     mi355_sws_planar_frame *d_pframe = nullptr;      /* ... of a planar context (d_dst then holds its three planes) */
     hipStream_t stream = nullptr;
     int device = -1;            /* the device of the thread that created the context: its entry points switch to it */
+    int hfit = 0;               /* a plane with a horizontal filter other than the identity has a tile whose source span fits a staged line (ctx_hfit) */
 };
 
 template <typename T> static const T *upload_bank(mi355_sws_ctx *c, int slot, const T *host, size_t n)
@@ -1140,11 +1233,45 @@ static mi355_sws_ctx *ctx_new(const mi355_sws_desc *desc)
     h.hLumP = h.hChrP = h.vLumP = h.vChrP = nullptr;
     h.planar = h.hshift = h.vshift = 0;
     h.chrDstH = h.dstH;
+    h.depth = 8; h.src_hsub = h.src_vsub = 1; h.pad_ = 0;
+    std::memset(h.dither, 64, sizeof(h.dither));
     return c;
+}
+/* the source side of a context (mi355_sws_create_src); false for a combination outside 8 / 9 / 10 bit 4:2:0 / 4:2:2 / 4:4:4 or a descriptor
+ * whose chroma size is not that subsampling's */
+static bool ctx_source(mi355_sws_ctx *c, const mi355_sws_src *src)
+{
+    SwsDev &h = c->h;
+    if (!src) return false;
+    if (src->depth < 8 || src->depth > 10 || (src->hsub | src->vsub) & ~1 || (src->vsub && !src->hsub)) return false;
+    if (h.chrSrcW != (h.srcW + (1 << src->hsub) - 1) >> src->hsub || h.chrSrcH != (h.srcH + (1 << src->vsub) - 1) >> src->vsub) return false;
+    /* the unscaled special converter: 8-bit 4:2:0 and 4:2:2 only (swscale_unscaled.c:1051-1055) */
+    if (h.special && (src->depth != 8 || !src->hsub)) return false;
+    h.depth = src->depth; h.src_hsub = src->hsub; h.src_vsub = src->vsub;
+    if (src->depth > 8) std::memcpy(h.dither, src->dither, sizeof(h.dither));
+    return true;
+}
+/* the tile kernels stage a plane's source spans when the context allows it (hstage), the plane's filter is not the identity and a tile's span
+ * fits the staged line (hscale_tile; planes and strides that are multiples of 16: the longest aligned start) */
+static void ctx_hfit(mi355_sws_ctx *c, const mi355_sws_desc *desc)
+{
+    const SwsDev &h = c->h;
+    const int B = h.depth > 8 ? 2 : 1, cw = h.planar ? TW >> h.hshift : TW / 2;
+    auto fits = [&](const mi355_sws_filter &f, int ident, int cols, int pitch) {
+        if (ident || !f.pos) return false;
+        for (int g = 0; g < f.n; g += cols) {
+            const int last = (g + cols < f.n ? g + cols : f.n) - 1, s0 = B * f.pos[g], s1 = B * (f.pos[last] + f.size);
+            if (s1 >= s0 && ((s1 - (s0 & ~15) + 3) >> 2) <= pitch - 2) return true;
+        }
+        return false;
+    };
+    const int pl = B == 1 ? SRC_DW : SRC_DW16, pc = cw == TW ? pl : (B == 1 ? 40 : 76);
+    c->hfit = fits(desc->hLum, h.hident_l, TW, pl) || fits(desc->hChr, h.hident_c, cw, pc);
 }
 static void upload_banks(mi355_sws_ctx *c, const mi355_sws_desc *desc)
 {
     SwsDev &h = c->h;
+    ctx_hfit(c, desc);
     h.hLumC = upload_bank(c, 0, desc->hLum.coef, (size_t)h.dstW * h.hls);    h.hLumP = upload_bank(c, 1, desc->hLum.pos, (size_t)h.dstW);
     h.hChrC = upload_bank(c, 2, desc->hChr.coef, (size_t)h.chrDstW * h.hcs); h.hChrP = upload_bank(c, 3, desc->hChr.pos, (size_t)h.chrDstW);
     h.vLumC = upload_bank(c, 4, desc->vLum.coef, (size_t)h.dstH * h.vls);    h.vLumP = upload_bank(c, 5, desc->vLum.pos, (size_t)h.dstH);
@@ -1159,16 +1286,21 @@ static mi355_sws_ctx *ctx_upload(mi355_sws_ctx *c)
     return c;
 }
 
-extern "C" mi355_sws_ctx *mi355_sws_create(const mi355_sws_desc *desc)
+static mi355_sws_ctx *create_rgb24(const mi355_sws_desc *desc, const mi355_sws_src *src, const char *who)
 {
-    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create without mi355_init(); no CPU fallback\n"); std::abort(); }
     mi355_sws_ctx *c = ctx_new(desc);
     SwsDev &h = c->h;
     int lines[2] = { 1, 1 };
+    if (src && !ctx_source(c, src)) {
+        std::fprintf(stderr, "mi355dsp: %s: source %d bit, chroma shifts %d/%d (chroma %dx%d of %dx%d) is outside this backend\n", who, src->depth, src->hsub, src->vsub,
+                     h.chrSrcW, h.chrSrcH, h.srcW, h.srcH);
+        delete c;
+        return nullptr;
+    }
     if (!h.special) {
         if (desc->hLum.n != h.dstW || desc->hChr.n != h.chrDstW || desc->vLum.n != h.dstH || desc->vChr.n != h.dstH ||
             h.hls < 1 || h.hcs < 1 || h.vls < 1 || h.vcs < 1 || !(h.th = choose_rows(desc, lines))) {
-            std::fprintf(stderr, "mi355dsp: mi355_sws_create: filter banks do not fit this backend (sizes %d/%d/%d/%d)\n", h.hls, h.hcs, h.vls, h.vcs);
+            std::fprintf(stderr, "mi355dsp: %s: filter banks do not fit this backend (sizes %d/%d/%d/%d)\n", who, h.hls, h.hcs, h.vls, h.vcs);
             delete c;
             return nullptr;
         }
@@ -1177,16 +1309,26 @@ extern "C" mi355_sws_ctx *mi355_sws_create(const mi355_sws_desc *desc)
     }
     return ctx_upload(c);
 }
-
-extern "C" mi355_sws_ctx *mi355_sws_create_planar(const mi355_sws_desc *desc, int dst_format)
+extern "C" mi355_sws_ctx *mi355_sws_create(const mi355_sws_desc *desc)
 {
-    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_planar without mi355_init(); no CPU fallback\n"); std::abort(); }
+    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create without mi355_init(); no CPU fallback\n"); std::abort(); }
+    return create_rgb24(desc, nullptr, "mi355_sws_create");
+}
+
+static mi355_sws_ctx *create_planar(const mi355_sws_desc *desc, const mi355_sws_src *src, int dst_format, const char *who)
+{
     if (!desc || dst_format < MI355_SWS_DST_YUV420P || dst_format > MI355_SWS_DST_YUV444P) {
-        std::fprintf(stderr, "mi355dsp: mi355_sws_create_planar: destination format %d is not yuv420p / yuv422p / yuv444p\n", dst_format);
+        std::fprintf(stderr, "mi355dsp: %s: destination format %d is not yuv420p / yuv422p / yuv444p\n", who, dst_format);
         return nullptr;
     }
     mi355_sws_ctx *c = ctx_new(desc);
     SwsDev &h = c->h;
+    if (src && !ctx_source(c, src)) {
+        std::fprintf(stderr, "mi355dsp: %s: source %d bit, chroma shifts %d/%d (chroma %dx%d of %dx%d) is outside this backend\n", who, src->depth, src->hsub, src->vsub,
+                     h.chrSrcW, h.chrSrcH, h.srcW, h.srcH);
+        delete c;
+        return nullptr;
+    }
     h.planar = dst_format;
     h.hshift = dst_format == MI355_SWS_DST_YUV444P ? 0 : 1;
     h.vshift = dst_format == MI355_SWS_DST_YUV420P ? 1 : 0;
@@ -1197,13 +1339,24 @@ extern "C" mi355_sws_ctx *mi355_sws_create_planar(const mi355_sws_desc *desc, in
     if (h.special || !banks || h.chrDstW != (h.dstW + (1 << h.hshift) - 1) >> h.hshift || desc->hLum.n != h.dstW || desc->hChr.n != h.chrDstW ||
         desc->vLum.n != h.dstH || desc->vChr.n != h.chrDstH || h.hls < 1 || h.hcs < 1 || h.vls < 1 || h.vcs < 1 ||
         !(h.th = choose_rows(desc, lines, h.vshift, MAXCP))) {
-        std::fprintf(stderr, "mi355dsp: mi355_sws_create_planar: filter banks do not fit this backend (sizes %d/%d/%d/%d)\n", h.hls, h.hcs, h.vls, h.vcs);
+        std::fprintf(stderr, "mi355dsp: %s: filter banks do not fit this backend (sizes %d/%d/%d/%d)\n", who, h.hls, h.hcs, h.vls, h.vcs);
         delete c;
         return nullptr;
     }
     h.lum_lines = lines[0]; h.chr_lines = lines[1];
     upload_banks(c, desc);
     return ctx_upload(c);
+}
+extern "C" mi355_sws_ctx *mi355_sws_create_planar(const mi355_sws_desc *desc, int dst_format)
+{
+    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_planar without mi355_init(); no CPU fallback\n"); std::abort(); }
+    return create_planar(desc, nullptr, dst_format, "mi355_sws_create_planar");
+}
+extern "C" mi355_sws_ctx *mi355_sws_create_src(const mi355_sws_desc *desc, const mi355_sws_src *src, int dst_format)
+{
+    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src without mi355_init(); no CPU fallback\n"); std::abort(); }
+    if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src: no descriptor\n"); return nullptr; }
+    return dst_format == 0 ? create_rgb24(desc, src, "mi355_sws_create_src") : create_planar(desc, src, dst_format, "mi355_sws_create_src");
 }
 
 extern "C" void mi355_sws_destroy(mi355_sws_ctx *c)
@@ -1228,7 +1381,7 @@ static int sws_kernel(const SwsDev &h)
     if (h.special) return MI355_SWS_K_C24;
     /* a context that does not scale: straight from the source bytes (k_sws_ident1; MI355_SWS_NO_IDENT1=1, developer switch: through the tile all the same) */
     static const bool no_ident1 = std::getenv("MI355_SWS_NO_IDENT1") != nullptr;
-    if (!no_ident1 && h.hident_l && h.hident_c && h.vls == 1 && h.vcs <= 4 && !(h.dstW & 1) && h.srcW >= h.dstW && 2 * h.chrSrcW >= h.dstW)
+    if (!no_ident1 && h.depth == 8 && h.hident_l && h.hident_c && h.vls == 1 && h.vcs <= 4 && !(h.dstW & 1) && h.srcW >= h.dstW && 2 * h.chrSrcW >= h.dstW)
         return h.vcs <= 2 ? MI355_SWS_K_IDENT1_1 : MI355_SWS_K_IDENT1_X;      /* packed_mode() 1 / the X template */
     /* a CU's 160 KB of LDS hold `wgs` workgroups, one wave of each per SIMD: the instance whose register budget matches */
     if (h.lum_lines <= 28 && h.chr_lines <= 16) return MI355_SWS_K_GENERIC_A;
@@ -1245,6 +1398,14 @@ extern "C" int mi355_sws_plan(const mi355_sws_ctx *c, mi355_sws_plan_info *p)
     /* k_sws_generic: the wide form needs a full tile (dstW - x0 >= TW) and vertical filters of at most eight taps; k_sws_planar: every tile
      * stores bytewise (dstW < TW) or reads its taps from memory (more than eight) */
     p->narrow = !h.special && (h.dstW < TW || h.vls > 8 || h.vcs > 8);
+    return 0;
+}
+
+extern "C" int mi355_sws_source(const mi355_sws_ctx *c, mi355_sws_source_info *p)
+{
+    if (!c || !p) return -1;
+    p->depth = c->h.depth; p->hsub = c->h.src_hsub; p->vsub = c->h.src_vsub;
+    p->hstaged = sws_kernel(c->h) >= MI355_SWS_K_GENERIC_A && c->h.hstage && c->hfit;
     return 0;
 }
 
@@ -1266,8 +1427,9 @@ extern "C" int mi355_sws_scale_frames_dev(mi355_sws_ctx *c, const mi355_sws_fram
     DeviceScope on(c->device);
     const int k = sws_kernel(h);
     if (k == MI355_SWS_K_C24) {
-        hipLaunchKernelGGL(k_sws_c24, dim3((h.dstW + C24_COLS - 1) / C24_COLS, (h.srcH + C24_ROWS - 1) / C24_ROWS, nframes), dim3(NT), 0, s,
-                           &c->d->luts, h.dstW, h.srcH, 0, d_frames);
+        const dim3 grid((h.dstW + C24_COLS - 1) / C24_COLS, (h.srcH + C24_ROWS - 1) / C24_ROWS, nframes);
+        if (h.src_vsub) hipLaunchKernelGGL(k_sws_c24<0>, grid, dim3(NT), 0, s, &c->d->luts, h.dstW, h.srcH, 0, d_frames);
+        else hipLaunchKernelGGL(k_sws_c24<1>, grid, dim3(NT), 0, s, &c->d->luts, h.dstW, h.srcH, 0, d_frames);      /* yuv422p: every other chroma line */
     } else if (k == MI355_SWS_K_IDENT1_1 || k == MI355_SWS_K_IDENT1_X) {
         const dim3 grid((h.dstW + C24_COLS - 1) / C24_COLS, (h.dstH + IDENT_ROWS - 1) / IDENT_ROWS, nframes);
         if (k == MI355_SWS_K_IDENT1_1) hipLaunchKernelGGL(k_sws_ident1<false>, grid, dim3(NT), 0, s, c->d, d_frames);
@@ -1275,7 +1437,15 @@ extern "C" int mi355_sws_scale_frames_dev(mi355_sws_ctx *c, const mi355_sws_fram
     } else {
         const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
         static_assert(160 * 1024 / sws_lds_bytes(28, 16) >= 8 && 160 * 1024 / sws_lds_bytes(40, 20) == 7 && 160 * 1024 / sws_lds_bytes(MAXL, MAXC) == 6, "workgroups per CU of the instances");
-        if (k == MI355_SWS_K_GENERIC_A) hipLaunchKernelGGL((k_sws_generic<28, 16, MI355_SWS_WAVES_A>), grid, dim3(NT), 0, s, c->d, d_frames);
+        /* the 16-bit instances' staging lines are STAGE_BYTES16: seven, five and five workgroups a CU */
+        static_assert(160 * 1024 / sws_lds_bytes(28, 16, STAGE_BYTES16) == 7 && 160 * 1024 / sws_lds_bytes(40, 20, STAGE_BYTES16) == 5 &&
+                      160 * 1024 / sws_lds_bytes(MAXL, MAXC, STAGE_BYTES16) == 5, "workgroups per CU of the 16-bit instances");
+        if (h.depth > 8) {
+            if (k == MI355_SWS_K_GENERIC_A) hipLaunchKernelGGL((k_sws_generic<28, 16, 7, uint16_t>), grid, dim3(NT), 0, s, c->d, d_frames);
+            else if (k == MI355_SWS_K_GENERIC_B) hipLaunchKernelGGL((k_sws_generic<40, 20, 5, uint16_t>), grid, dim3(NT), 0, s, c->d, d_frames);
+            else hipLaunchKernelGGL((k_sws_generic<MAXL, MAXC, 5, uint16_t>), grid, dim3(NT), 0, s, c->d, d_frames);
+        }
+        else if (k == MI355_SWS_K_GENERIC_A) hipLaunchKernelGGL((k_sws_generic<28, 16, MI355_SWS_WAVES_A>), grid, dim3(NT), 0, s, c->d, d_frames);
         else if (k == MI355_SWS_K_GENERIC_B) hipLaunchKernelGGL((k_sws_generic<40, 20, MI355_SWS_WAVES_B>), grid, dim3(NT), 0, s, c->d, d_frames);
         else hipLaunchKernelGGL((k_sws_generic<MAXL, MAXC, MI355_SWS_WAVES_C>), grid, dim3(NT), 0, s, c->d, d_frames);
     }
@@ -1293,8 +1463,15 @@ extern "C" int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *c, const mi355_s
     static_assert(sws_planar_waves(28, 16, TW / 2) == 8 && sws_planar_waves(40, 24, TW / 2) == 7 && sws_planar_waves(MAXL, MAXCP, TW / 2) == 5 &&
                   sws_planar_waves(MAXL, MAXCP, TW) == 3,
                   "workgroups per CU of the planar instances");
+    static_assert(sws_planar_waves(28, 16, TW / 2, STAGE_BYTES16) == 8 && sws_planar_waves(40, 24, TW / 2, STAGE_BYTES16) == 6 &&
+                  sws_planar_waves(MAXL, MAXCP, TW / 2, STAGE_BYTES16) == 4 && sws_planar_waves(MAXL, MAXCP, TW, STAGE_BYTES16) == 3,
+                  "workgroups per CU of the 16-bit planar instances");
 #define MI355_PLANAR(L, C) \
-    if (h.hshift) hipLaunchKernelGGL((k_sws_planar<L, C, TW / 2>), grid, dim3(NT), 0, s, c->d, d_frames); \
+    if (h.depth > 8) { \
+        if (h.hshift) hipLaunchKernelGGL((k_sws_planar<L, C, TW / 2, uint16_t>), grid, dim3(NT), 0, s, c->d, d_frames); \
+        else hipLaunchKernelGGL((k_sws_planar<L, C, TW, uint16_t>), grid, dim3(NT), 0, s, c->d, d_frames); \
+    } \
+    else if (h.hshift) hipLaunchKernelGGL((k_sws_planar<L, C, TW / 2>), grid, dim3(NT), 0, s, c->d, d_frames); \
     else hipLaunchKernelGGL((k_sws_planar<L, C, TW>), grid, dim3(NT), 0, s, c->d, d_frames);
     if (k == MI355_SWS_K_PLANAR_A) { MI355_PLANAR(28, 16) }
     else if (k == MI355_SWS_K_PLANAR_B) { MI355_PLANAR(40, 24) }
@@ -1317,12 +1494,13 @@ extern "C" int mi355_sws_scale(mi355_sws_ctx *c, const uint8_t *const src[3], co
     if (!c || !src || !src_stride || !dst || c->h.planar) return -1;
     const SwsDev &h = c->h;
     const int cw = h.chrSrcW, ch = h.chrSrcH;
-    const int w[3] = { h.srcW, cw, cw };
+    const int B = h.depth > 8 ? 2 : 1;                                  /* bytes per source sample */
+    const int w[3] = { h.srcW * B, cw * B, cw * B };
     const int out_w = h.special ? (h.dstW & ~1) * 3 : h.dstW * 3;      /* only the samples the converter writes go back: the caller's padding stays untouched */
     for (int p = 0; p < 3; p++) if (!src[p] || src_stride[p] < w[p]) return -1;
     if (dst_stride < out_w) return -1;
     DeviceScope on(c->device);
-    const int pw[3] = { (h.srcW + 15) & ~15, (cw + 15) & ~15, (cw + 15) & ~15 }, ph[3] = { h.srcH, ch, ch };
+    const int pw[3] = { (w[0] + 15) & ~15, (w[1] + 15) & ~15, (w[2] + 15) & ~15 }, ph[3] = { h.srcH, ch, ch };
     const int dpitch = (h.dstW * 3 + 15) & ~15;
     if (!c->d_dst) {
         uint8_t *ns[3] = { nullptr, nullptr, nullptr }, *nd = nullptr;
@@ -1361,10 +1539,11 @@ extern "C" int mi355_sws_scale_planar(mi355_sws_ctx *c, const uint8_t *const src
     if (!c || !src || !src_stride || !dst || !dst_stride || !c->h.planar) return -1;
     const SwsDev &h = c->h;
     const int cw = h.chrSrcW, ch = h.chrSrcH;
-    const int w[3] = { h.srcW, cw, cw }, ow[3] = { h.dstW, h.chrDstW, h.chrDstW }, oh[3] = { h.dstH, h.chrDstH, h.chrDstH };
+    const int B = h.depth > 8 ? 2 : 1;                                  /* bytes per source sample */
+    const int w[3] = { h.srcW * B, cw * B, cw * B }, ow[3] = { h.dstW, h.chrDstW, h.chrDstW }, oh[3] = { h.dstH, h.chrDstH, h.chrDstH };
     for (int p = 0; p < 3; p++) if (!src[p] || src_stride[p] < w[p] || !dst[p] || dst_stride[p] < ow[p]) return -1;
     DeviceScope on(c->device);
-    const int pw[3] = { (h.srcW + 15) & ~15, (cw + 15) & ~15, (cw + 15) & ~15 }, ph[3] = { h.srcH, ch, ch };
+    const int pw[3] = { (w[0] + 15) & ~15, (w[1] + 15) & ~15, (w[2] + 15) & ~15 }, ph[3] = { h.srcH, ch, ch };
     const int dp[3] = { (ow[0] + 15) & ~15, (ow[1] + 15) & ~15, (ow[2] + 15) & ~15 };
     const size_t doff[3] = { 0, (size_t)dp[0] * oh[0], (size_t)dp[0] * oh[0] + (size_t)dp[1] * oh[1] };
     if (!c->d_dst) {
@@ -1415,7 +1594,24 @@ extern "C" void mi355_sws_hscale8to15(int16_t *dst, int dstW, const uint8_t *src
     std::memcpy(a.h<int16_t>(o_f), filter, (size_t)dstW * filterSize * 2);
     std::memcpy(a.h<int32_t>(o_p), filterPos, (size_t)dstW * 4);
     a.upload();
-    LAUNCH_LINE(k_sws_line_hscale, a, a.d<int16_t>(o_d), dstW, a.d<const uint8_t>(o_src), a.d<const int16_t>(o_f), a.d<const int32_t>(o_p), filterSize);
+    LAUNCH_LINE(k_sws_line_hscale<uint8_t>, a, a.d<int16_t>(o_d), dstW, a.d<const uint8_t>(o_src), a.d<const int16_t>(o_f), a.d<const int32_t>(o_p), filterSize, 7);
+    a.download();
+    std::memcpy(dst, a.h<int16_t>(o_d), (size_t)dstW * 2);
+}
+/* hScale16To15_c swscale.c:110-130: uint16_t samples below 1 << depth */
+extern "C" void mi355_sws_hscale16to15(int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize, int depth)
+{
+    Arena &a = arena();
+    int last = 0;
+    for (int i = 0; i < dstW; i++) if (filterPos[i] > last) last = filterPos[i];
+    const size_t nsrc = ((size_t)last + filterSize) * 2;
+    a.reserve(nsrc + (size_t)dstW * filterSize * 2 + (size_t)dstW * 6 + 64);
+    const size_t o_src = a.take(nsrc), o_f = a.take((size_t)dstW * filterSize * 2), o_p = a.take((size_t)dstW * 4), o_d = a.take((size_t)dstW * 2);
+    std::memcpy(a.h<uint8_t>(o_src), src, nsrc);
+    std::memcpy(a.h<int16_t>(o_f), filter, (size_t)dstW * filterSize * 2);
+    std::memcpy(a.h<int32_t>(o_p), filterPos, (size_t)dstW * 4);
+    a.upload();
+    LAUNCH_LINE(k_sws_line_hscale<uint16_t>, a, a.d<int16_t>(o_d), dstW, a.d<const uint8_t>(o_src), a.d<const int16_t>(o_f), a.d<const int32_t>(o_p), filterSize, depth - 1);
     a.download();
     std::memcpy(dst, a.h<int16_t>(o_d), (size_t)dstW * 2);
 }
@@ -1509,7 +1705,7 @@ extern "C" int mi355_sws_yuv2rgb_c_24_rgb(const mi355_sws_luts *luts, int dstW, 
     f.dst = d_dst; f.dst_stride = dpitch;
     MI355_CHECK(hipMemcpyAsync(d_f, &f, sizeof(f), hipMemcpyHostToDevice, s));
     MI355_CHECK(hipMemcpyAsync(d_l, luts, sizeof(mi355_sws_luts), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_sws_c24, dim3((dstW + C24_COLS - 1) / C24_COLS, (rows + C24_ROWS - 1) / C24_ROWS, 1), dim3(NT), 0, s,
+    hipLaunchKernelGGL(k_sws_c24<0>, dim3((dstW + C24_COLS - 1) / C24_COLS, (rows + C24_ROWS - 1) / C24_ROWS, 1), dim3(NT), 0, s,
                        reinterpret_cast<const mi355_sws_luts *>(d_l), dstW, rows, 0, d_f);
     MI355_CHECK(hipMemcpy2DAsync(dst + (ptrdiff_t)srcSliceY * dstStride, dstStride, d_dst, dpitch, (dstW & ~1) * 3, rows, hipMemcpyDeviceToHost, s));
     MI355_CHECK(hipStreamSynchronize(s));
