@@ -1,1154 +1,17 @@
 /*
  * sws.hip — the libswscale part of the path: planar yuv 4:2:0 / 4:2:2 / 4:4:4 sources at 8, 9 or 10 bits (16-bit
  * little-endian samples above 8: hScale16To15_c swscale.c:110-130 in place of hScale8To15_c) -> rgb24 and -> 8-bit yuv420p / yuv422p / yuv444p
- * (dithered from a deeper source, swscale.c:553-556):
- *   k_sws_generic   the generic scaler of swscale() (libswscale/swscale.c:343-722) for whole pictures,
- *                   fused per output tile: horizontal 8->15 bit FIR of the source lines the tile needs
- *                   (hScale8To15_c :133-147) into LDS, vertical FIR + yuv->rgb LUT
- *                   (yuv2rgb24_{1,2,X}_c output.c:937-1110) from LDS, RGB rows staged in LDS and
- *                   written as dwords.  No int16 intermediate ever goes to HBM.
- *   k_sws_planar    the same loop's planar branch (swscale.c:618-645, yuv2planeX_8_c / yuv2plane1_8_c output.c:242-266): the
- *                   horizontal pass into LDS as above, the vertical pass from LDS straight to the three destination planes.
- *   k_sws_c24       the unscaled converter yuv2rgb_c_24_rgb (yuv2rgb.c:335-363) for 8-bit yuv420p and yuv422p.
- *   k_sws_ident1    the generic scaler on an 8-bit context that does not scale, from the source bytes.
- * The tile kernels are instantiated per sample type: the uint16_t instances differ in the horizontal pass (its staging lines are twice
- * as long, so is their LDS) and, for planar destinations, in the dither rows.
- *   k_sws_line_*    the individual inner loops for the Tier-1 entry points.
+ * (dithered from a deeper source, swscale.c:553-556).  This file: the context, the plan (which kernel a context gets) and the entry points of
+ * include/mi355_sws.h.  The device side is sws_dev.h: k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1 and the k_sws_line_* kernels of
+ * the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
- * Execution model: 256-thread workgroups (4 waves) sharing one LDS tile; integer only, no MFMA.
  */
 #include "mi355_rt.h"
+#include "sws_dev.h"
 #include "../../include/mi355_sws.h"
 #include "../../include/mi355dsp.h"
 
 using namespace mi355;
-
-namespace {
-
-constexpr int TW = 128;      /* output samples per tile row */
-constexpr int MAXTH = 16;    /* output rows per tile (upper bound) */
-constexpr int MAXL = 48;     /* source luma lines a tile may need (upper bound: the LDS tile is sized per context, sws_plan) */
-constexpr int MAXC = 24;     /* source chroma lines a tile may need */
-constexpr int MAXCP = 48;    /* ... of a planar destination (its tile holds no LUT and no output rows; a 4:2:0 chroma plane's filters are as long as the luma's) */
-constexpr int NT = 256;
-
-struct SwsDev {
-    int srcW, srcH, dstW, dstH, chrSrcW, chrSrcH, chrDstW, special;
-    int hls, hcs, vls, vcs;                 /* filter sizes */
-    const int16_t *hLumC, *hChrC, *vLumC, *vChrC;
-    const int32_t *hLumP, *hChrP, *vLumP, *vChrP;
-    int th;                                 /* output rows per tile chosen at create time */
-    int lum_lines, chr_lines;               /* source lines the LDS tile holds (the largest span of a tile of th rows) */
-    int hstage;                             /* horizontal filter positions never decrease: source spans can be staged in LDS */
-    int hident_l, hident_c;                 /* the horizontal filter of the plane is the identity (one tap of 1 << 14 at position i: an unscaled
-                                             * conversion through the generic path): hScale8To15 is then src << 7 */
-    mi355_sws_luts luts;
-    /* planar destinations (mi355_sws_create_planar): the MI355_SWS_DST_* format, its chroma subsampling and chroma rows (0 / 0 / 0 / dstH for rgb24) */
-    int planar, hshift, vshift, chrDstH;
-    /* the source side (mi355_sws_create_src): bits per sample (8: bytes; 9 / 10: uint16_t little endian), its chroma shifts, and the 8x8
-     * dither rows a planar destination takes from a source deeper than 8 bits (swscale.c:553-556) */
-    int depth, src_hsub, src_vsub, pad_;
-    __attribute__((aligned(8))) uint8_t dither[8][8];
-};
-
-struct LutLds {
-    uint8_t y[1024];
-    int16_t rV[256], gU[256], gV[256], bU[256];
-};
-__device__ __forceinline__ void lut_load(LutLds &s, const mi355_sws_luts *g, int tid, int nt)
-{
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(g);
-    uint32_t *dst = reinterpret_cast<uint32_t *>(&s);
-    static_assert(sizeof(LutLds) == 3 * 4 * NT, "three dwords per thread");
-    (void)nt;
-    const uint32_t a = src[tid], b = src[tid + NT], c = src[tid + 2 * NT];      /* in flight together */
-    dst[tid] = a; dst[tid + NT] = b; dst[tid + 2 * NT] = c;
-}
-__device__ __forceinline__ int clip_u8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-/* yuv2rgb_write, rgb24 branch (output.c:853-866) */
-__device__ __forceinline__ void write_pair(const LutLds &t, uint8_t *dest, int Y1, int Y2, int U, int V)
-{
-    const int r = t.rV[V], g = t.gU[U] + t.gV[V], b = t.bU[U];
-    dest[0] = t.y[r + Y1]; dest[1] = t.y[g + Y1]; dest[2] = t.y[b + Y1];
-    dest[3] = t.y[r + Y2]; dest[4] = t.y[g + Y2]; dest[5] = t.y[b + Y2];
-}
-
-/* one output pair of the three packed templates; rows are addressed through accessors so the same
- * code serves LDS tiles (whole pictures) and packed global rows (Tier-1 line calls) */
-template <typename Rows>
-__device__ __forceinline__ void rgb_pair(const LutLds &t, uint8_t *dest, const Rows &R, int i, int mode, const int16_t *lumF, int ls,
-                                         const int16_t *chrF, int cs, int yalpha, int uvalpha)
-{
-    int Y1, Y2, U, V;
-    if (mode == 1) {          /* yuv2rgb_1_c_template output.c:1043-1110 */
-        Y1 = clip_u8(R.lum(0, 2 * i) >> 7); Y2 = clip_u8(R.lum(0, 2 * i + 1) >> 7);
-        if (uvalpha < 2048) { U = clip_u8(R.cu(0, i) >> 7); V = clip_u8(R.cv(0, i) >> 7); }
-        else { U = clip_u8((R.cu(0, i) + R.cu(1, i)) >> 8); V = clip_u8((R.cv(0, i) + R.cv(1, i)) >> 8); }
-    } else if (mode == 2) {   /* yuv2rgb_2_c_template :998-1041 */
-        const int ya1 = 4096 - yalpha, ua1 = 4096 - uvalpha;
-        Y1 = clip_u8((R.lum(0, 2 * i) * ya1 + R.lum(1, 2 * i) * yalpha) >> 19);
-        Y2 = clip_u8((R.lum(0, 2 * i + 1) * ya1 + R.lum(1, 2 * i + 1) * yalpha) >> 19);
-        U = clip_u8((R.cu(0, i) * ua1 + R.cu(1, i) * uvalpha) >> 19);
-        V = clip_u8((R.cv(0, i) * ua1 + R.cv(1, i) * uvalpha) >> 19);
-    } else {                  /* yuv2rgb_X_c_template :937-996: clipped only if a value has bit 8 set */
-        Y1 = Y2 = U = V = 1 << 18;
-        for (int j = 0; j < ls; j++) { const int f = lumF[j]; Y1 += R.lum(j, 2 * i) * f; Y2 += R.lum(j, 2 * i + 1) * f; }
-        for (int j = 0; j < cs; j++) { const int f = chrF[j]; U += R.cu(j, i) * f; V += R.cv(j, i) * f; }
-        Y1 >>= 19; Y2 >>= 19; U >>= 19; V >>= 19;
-        if ((Y1 | Y2 | U | V) & 0x100) { Y1 = clip_u8(Y1); Y2 = clip_u8(Y2); U = clip_u8(U); V = clip_u8(V); }
-    }
-    write_pair(t, dest, Y1, Y2, U, V);
-}
-typedef uint32_t sws_u32x2 __attribute__((vector_size(8)));
-typedef uint32_t sws_u32x4 __attribute__((vector_size(16)));
-/* eight neighbouring samples of a line (four pairs sharing a chroma sample each): Y values 0..255 in Y[8], the pairs' LUT
- * row offsets in r/g/b -> 24 RGB bytes at d (8-byte aligned), three 8-byte stores */
-__device__ __forceinline__ void rgb24_store8(const LutLds &t, uint8_t *d, const int *Y, const int *r, const int *g, const int *b)
-{
-    uint32_t o[6];
-#pragma unroll
-    for (int p = 0; p < 4; p++) {
-        const int Y1 = Y[2 * p], Y2 = Y[2 * p + 1];
-        const uint32_t r1 = t.y[r[p] + Y1], g1 = t.y[g[p] + Y1], b1 = t.y[b[p] + Y1];
-        const uint32_t r2 = t.y[r[p] + Y2], g2 = t.y[g[p] + Y2], b2 = t.y[b[p] + Y2];
-        /* six bytes per pair: pairs 0,2 start on a dword, pairs 1,3 in the middle of one */
-        if ((p & 1) == 0) {
-            o[3 * (p >> 1)] = r1 | (g1 << 8) | (b1 << 16) | (r2 << 24);
-            o[3 * (p >> 1) + 1] = g2 | (b2 << 8);
-        } else {
-            o[3 * (p >> 1) + 1] |= (r1 << 16) | (g1 << 24);
-            o[3 * (p >> 1) + 2] = b1 | (r2 << 8) | (g2 << 16) | (b2 << 24);
-        }
-    }
-    sws_u32x2 *q = reinterpret_cast<sws_u32x2 *>(d);
-    q[0] = sws_u32x2{ o[0], o[1] }; q[1] = sws_u32x2{ o[2], o[3] }; q[2] = sws_u32x2{ o[4], o[5] };
-}
-__device__ __forceinline__ int packed_mode(int ls, int cs) { return (ls == 1 && cs <= 2) ? 1 : ((ls == 2 && cs == 2) ? 2 : 0); }  /* swscale.c:658-682 */
-
-/* hScale8To15_c swscale.c:133-147 for one output sample; ST uint16_t: hScale16To15_c :110-130, sh = depth - 1 (samples below 1 << depth:
- * the sum stays inside an int) */
-template <typename ST = uint8_t>
-__device__ __forceinline__ int hscale_one(const uint8_t *src, const int16_t *f, int pos, int fs, int sh = 7)
-{
-    const ST *s = reinterpret_cast<const ST *>(src);
-    int val = 0;
-    for (int j = 0; j < fs; j++) val += (int)s[pos + j] * f[j];
-    val >>= sh;
-    return val < 32767 ? val : 32767;
-}
-/* the shift behind the horizontal sum: 7 for bytes, depth - 1 for 16-bit samples */
-template <typename ST> __device__ __forceinline__ int hscale_shift(int depth) { return sizeof(ST) == 1 ? 7 : depth - 1; }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
-__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
-
-struct TileRows {
-    const int16_t (*lumT)[TW];
-    const int16_t (*cuT)[TW / 2];
-    const int16_t (*cvT)[TW / 2];
-    int lfirst, llo, lmax, cfirst, clo, cmax;   /* first tap line, first staged line, last picture line */
-    __device__ __forceinline__ int lum(int j, int x) const { return lumT[clampi(lfirst + j, 0, lmax) - llo][x]; }
-    __device__ __forceinline__ int cu(int j, int x) const { return cuT[clampi(cfirst + j, 0, cmax) - clo][x]; }
-    __device__ __forceinline__ int cv(int j, int x) const { return cvT[clampi(cfirst + j, 0, cmax) - clo][x]; }
-};
-
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-/* Horizontal pass of one plane for a tile: COLS output columns starting at gx0, source lines lo..hi, results
- * to out[line - lo][x].  The source span the columns need ([pos[gx0], pos[last] + fs), monotonic positions)
- * is staged in LDS SG lines at a time with aligned 16-byte (or dword) loads — a few coalesced loads per thread
- * instead of fs single-byte loads per output sample; spans wider than the stage, unaligned planes and non-monotonic
- * filters take the direct path. */
-#ifndef MI355_SWS_SG
-#define MI355_SWS_SG 16
-#endif
-constexpr int SG = MI355_SWS_SG;      /* source lines per staging round (a round costs two workgroup barriers) */
-constexpr int SRC_DW = 76;            /* dwords per staged line: 2:1 with 8 taps needs 128 * 2 + 8 bytes (+2 of slack for zero taps) */
-constexpr int STAGE_BYTES = (int)sizeof(uint32_t) * SG * SRC_DW;
-/* a chroma tile row is half as wide: its staged lines are about half as long (64 * 2 + 8 bytes + the 15 of a 16-byte aligned start) and a
- * round holds half as many again in the same storage (the 20 chroma lines of a 2:1 reduction: one round instead of two) */
-/* 16-bit samples: the same spans are twice as many bytes — (128 * 2 + 8) * 2 bytes + the 15 of an aligned start and the two dwords of slack;
- * a chroma tile row (64 * 2 + 8) * 2 + 15.  The same number of lines per round, so a 16-bit instance's staging storage is its own size. */
-constexpr int SRC_DW16 = 140;
-constexpr int STAGE_BYTES16 = (int)sizeof(uint32_t) * SG * SRC_DW16;
-template <typename ST> __host__ __device__ constexpr int stage_bytes() { return sizeof(ST) == 1 ? STAGE_BYTES : STAGE_BYTES16; }
-template <int COLS, typename ST = uint8_t> struct StageGeom {
-    static constexpr int PITCH = sizeof(ST) == 1 ? (COLS == TW ? SRC_DW : 40) : (COLS == TW ? SRC_DW16 : 76);   /* dwords per staged line: a multiple of four (16-byte LDS stores) */
-    static constexpr int LINES = COLS == TW ? SG : (3 * SG) / 2;       /* staged lines per round */
-    static_assert(PITCH % 4 == 0 && (size_t)PITCH * LINES * sizeof(uint32_t) <= (size_t)stage_bytes<ST>(), "a round fits the staging storage");
-};
-constexpr int OUT_ROWS = STAGE_BYTES / (TW * 3);            /* rows of a narrow tile written per pass (they reuse the staging lines) */
-static_assert(OUT_ROWS >= 8, "the narrow form needs at most two passes over a tile of MAXTH rows");
-/* byte funnel shift, byte permute and the two-term 16-bit dot product (v_alignbyte_b32, v_perm_b32, v_dot2_i32_i16); plain C
- * under the SIMT emulator */
-#ifdef MI355_HIP_EMU_H
-static inline uint32_t sws_alignbyte(uint32_t hi, uint32_t lo, uint32_t s) { return (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (8 * (s & 3))); }
-static inline uint32_t sws_pair(uint32_t w, int k) { return ((w >> (16 * k)) & 0xFFu) | (((w >> (16 * k + 8)) & 0xFFu) << 16); }
-static inline int sws_dot2(uint32_t a, uint32_t b, int c) { return c + (int16_t)(a & 0xFFFF) * (int16_t)(b & 0xFFFF) + (int16_t)(a >> 16) * (int16_t)(b >> 16); }
-static inline uint32_t sws_lo2(uint32_t a, uint32_t b) { return (a & 0xFFFFu) | (b << 16); }            /* (a.lo, b.lo) */
-static inline uint32_t sws_hi2(uint32_t a, uint32_t b) { return (a >> 16) | (b & 0xFFFF0000u); }        /* (a.hi, b.hi) */
-#else
-__device__ __forceinline__ uint32_t sws_alignbyte(uint32_t hi, uint32_t lo, uint32_t s) { return __builtin_amdgcn_alignbyte(hi, lo, s); }
-/* bytes 2k, 2k + 1 of w as two 16-bit values */
-__device__ __forceinline__ uint32_t sws_pair(uint32_t w, int k) { return __builtin_amdgcn_perm(0u, w, k ? 0x0C030C02u : 0x0C010C00u); }
-__device__ __forceinline__ uint32_t sws_lo2(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }      /* (a.lo, b.lo) */
-__device__ __forceinline__ uint32_t sws_hi2(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }      /* (a.hi, b.hi) */
-typedef short sws_short2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int sws_dot2(uint32_t a, uint32_t b, int c)
-{
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(sws_short2, a), __builtin_bit_cast(sws_short2, b), c, false);
-}
-#endif
-/* a value the optimiser may not combine with what follows (an empty asm in a vector register) */
-#ifdef MI355_HIP_EMU_H
-static inline uint32_t sws_opaque(uint32_t v) { return v; }
-#else
-__device__ __forceinline__ uint32_t sws_opaque(uint32_t v)
-{
-    asm volatile("" : "+v"(v));
-    return v;
-}
-#endif
-/* eight taps: the column's byte offset inside a dword is the same on every staged line, so a line's eight samples are
- * three aligned dwords funnel-shifted into two, expanded to four 16-bit pairs and multiplied with the coefficient pairs
- * (3 LDS reads and 10 arithmetic instructions per output instead of 8 byte reads and 8 multiply-adds).  Products and sums
- * are the same integers (samples 0..255, coefficients 16 bits, |sum| < 2^31). */
-template <int COLS, int OP = COLS, typename ST = uint8_t>
-__device__ __forceinline__ void hscale_lines8(const uint8_t *row0, int16_t *out0, const uint32_t *cp, int left, int hsh = 7)
-{
-    if constexpr (sizeof(ST) == 2) {
-        /* 16-bit samples are already the lanes of the dot product: a line's eight samples are five aligned dwords funnel-shifted by
-         * the column's odd sample (two bytes) into four pairs */
-        constexpr int per = NT / COLS;
-        const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(row0) & 3);
-        const uint32_t *w0 = reinterpret_cast<const uint32_t *>(row0 - sh);
-        const uint32_t c01 = cp[0], c23 = cp[1], c45 = cp[2], c67 = cp[3];
-        constexpr int N = StageGeom<COLS, ST>::LINES / per, G = N % 4 == 0 ? 4 : 3, PITCH = StageGeom<COLS, ST>::PITCH;
-        static_assert(StageGeom<COLS, ST>::LINES % per == 0 && N % G == 0, "whole groups of lines");
-#pragma unroll
-        for (int g = 0; g < N; g += G) {
-            if (g * per > left) break;
-            uint32_t d[G][5];
-#pragma unroll
-            for (int q = 0; q < G; q++) {
-                const uint32_t *w = w0 + (g + q) * per * PITCH;
-#pragma unroll
-                for (int k = 0; k < 5; k++) d[q][k] = w[k];
-            }
-#pragma unroll
-            for (int q = 0; q < G; q++) {
-                if ((g + q) * per > left) break;
-                int v = sws_dot2(sws_alignbyte(d[q][1], d[q][0], sh), c01, 0);
-                v = sws_dot2(sws_alignbyte(d[q][2], d[q][1], sh), c23, v);
-                v = sws_dot2(sws_alignbyte(d[q][3], d[q][2], sh), c45, v);
-                v = sws_dot2(sws_alignbyte(d[q][4], d[q][3], sh), c67, v);
-                v >>= hsh;
-                out0[(g + q) * per * OP] = (int16_t)(v < 32767 ? v : 32767);
-            }
-        }
-        return;
-    }
-    constexpr int per = NT / COLS;
-    const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(row0) & 3);
-    const uint32_t *w0 = reinterpret_cast<const uint32_t *>(row0 - sh);
-    const uint32_t c01 = cp[0], c23 = cp[1], c45 = cp[2], c67 = cp[3];
-    static_assert(COLS >= 64, "a wave's threads share their first line: `left` is the same on all of them");
-    /* four (chroma: three) lines at a time: their LDS reads go out together, then the arithmetic of the group (one read-wait-compute chain
-     * per line leaves the wave waiting for the LDS once per output).  A short last round ends at a branch of the wave, between
-     * groups or inside one (the reads of a group are unconditional: the staged lines exist). */
-    constexpr int N = StageGeom<COLS>::LINES / per, G = N % 4 == 0 ? 4 : 3, PITCH = StageGeom<COLS>::PITCH;
-    static_assert(StageGeom<COLS>::LINES % per == 0 && N % G == 0, "whole groups of lines");
-#pragma unroll
-    for (int g = 0; g < N; g += G) {
-        if (g * per > left) break;
-        uint32_t d[G][3];
-#pragma unroll
-        for (int q = 0; q < G; q++) {
-            const uint32_t *w = w0 + (g + q) * per * PITCH;
-            d[q][0] = w[0]; d[q][1] = w[1]; d[q][2] = w[2];
-        }
-#pragma unroll
-        for (int q = 0; q < G; q++) {
-            if ((g + q) * per > left) break;                 /* of the wave, like the one between groups */
-            const uint32_t lo = sws_alignbyte(d[q][1], d[q][0], sh), hi = sws_alignbyte(d[q][2], d[q][1], sh);
-            int v = sws_dot2(sws_pair(lo, 0), c01, 0);
-            v = sws_dot2(sws_pair(lo, 1), c23, v);
-            v = sws_dot2(sws_pair(hi, 0), c45, v);
-            v = sws_dot2(sws_pair(hi, 1), c67, v);
-            v >>= 7;
-            out0[(g + q) * per * OP] = (int16_t)(v < 32767 ? v : 32767);
-        }
-    }
-}
-template <int COLS, int TAPS, int OP = COLS, typename ST = uint8_t>
-__device__ __forceinline__ void hscale_lines(const uint8_t *row0, int16_t *out0, const uint32_t *cp, int left, int hsh = 7)
-{
-    constexpr int per = NT / COLS;
-    int cf[TAPS];
-#pragma unroll
-    for (int j = 0; j < TAPS; j++) cf[j] = (int16_t)(cp[j >> 1] >> (16 * (j & 1)));
-#pragma unroll
-    for (int k = 0; k < StageGeom<COLS, ST>::LINES / per; k++) {
-        if (k * per > left) break;
-        const ST *row = reinterpret_cast<const ST *>(row0 + k * per * (StageGeom<COLS, ST>::PITCH * 4));
-        int val = 0;
-#pragma unroll
-        for (int j = 0; j < TAPS; j++) val += (int)row[j] * cf[j];
-        val >>= hsh;
-        out0[k * per * OP] = (int16_t)(val < 32767 ? val : 32767);
-    }
-}
-/* OP: int16 samples per line of `out` (a line may hold two planes' tiles side by side) */
-/* ST: the source's sample type (uint8_t, or uint16_t for 9 / 10 bit: `depth`); srcW in samples, stride in bytes */
-template <int COLS, int OP = COLS, typename ST = uint8_t>
-__device__ __forceinline__ void hscale_tile(int16_t (*out)[OP], const uint8_t *src, int stride, int srcW, const int32_t *posT,
-                                            const int16_t *coefT, int fs, int gx0, int ncols, int lo, int hi,
-                                            uint32_t *stage_mem, int tid, bool zero_tail, bool may_stage, bool identity, int depth = 8)
-{
-    constexpr int PITCH = StageGeom<COLS, ST>::PITCH, LINES = StageGeom<COLS, ST>::LINES, B = (int)sizeof(ST);
-    const int hsh = hscale_shift<ST>(depth);
-    uint32_t (*stage)[PITCH] = reinterpret_cast<uint32_t (*)[PITCH]>(stage_mem);
-    if constexpr (B == 2) if (identity) {
-        /* one tap of 1 << 14 at position i: (src * 16384) >> (depth - 1) = src << (15 - depth), below the clamp for samples below
-         * 1 << depth; two samples a dword, shifted in place.  Eight columns per thread: one 16-byte load, one 16-byte LDS write */
-        constexpr int TPL = COLS / 8;
-        const int xg = 8 * (tid % TPL), gxi = gx0 + xg, up = 15 - depth;
-        const bool al16 = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride | (uintptr_t)(2 * gx0)) & 15) == 0;
-        for (int l = lo + tid / TPL; l <= hi; l += NT / TPL) {
-            const uint8_t *p = src + (size_t)l * stride + 2 * gxi;
-            sws_u32x4 o = { 0u, 0u, 0u, 0u };
-            if (al16 && gxi + 8 <= srcW && gxi + 8 <= ncols) o = *reinterpret_cast<const sws_u32x4 *>(p);
-            else {
-                for (int k = 0; k < 8; k++)
-                    if (gxi + k < ncols && gxi + k < srcW) o[k >> 1] |= (uint32_t)reinterpret_cast<const uint16_t *>(p)[k] << (16 * (k & 1));
-            }
-            for (int k = 0; k < 4; k++) o[k] <<= up;
-            if (zero_tail || gxi < ncols) *reinterpret_cast<sws_u32x4 *>(&out[l - lo][xg]) = o;
-        }
-        return;
-    }
-    if (identity) {
-        /* one tap of 1 << 14 at position i: (src * 16384) >> 7 = src << 7 (below the 32767 clamp).  Eight columns per thread:
-         * one 8-byte load (aligned planes, inside the line), one 16-byte LDS write */
-        constexpr int TPL = COLS / 8;                  /* threads per line */
-        const int xg = 8 * (tid % TPL), gxi = gx0 + xg;
-        const bool al8 = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride | (uintptr_t)gx0) & 7) == 0;
-        for (int l = lo + tid / TPL; l <= hi; l += NT / TPL) {
-            const uint8_t *p = src + (size_t)l * stride + gxi;
-            uint32_t b0 = 0, b1 = 0;
-            if (al8 && gxi + 8 <= srcW && gxi + 8 <= ncols) { const sws_u32x2 w = *reinterpret_cast<const sws_u32x2 *>(p); b0 = w[0]; b1 = w[1]; }
-            else {
-                for (int k = 0; k < 4; k++) {
-                    if (gxi + k < ncols && gxi + k < srcW) b0 |= (uint32_t)p[k] << (8 * k);
-                    if (gxi + 4 + k < ncols && gxi + 4 + k < srcW) b1 |= (uint32_t)p[4 + k] << (8 * k);
-                }
-            }
-            /* bytes -> int16 << 7, two per dword */
-            sws_u32x4 o;
-            o[0] = ((b0 & 0xFFu) << 7) | ((b0 & 0xFF00u) << 15);
-            o[1] = ((b0 >> 9) & 0x7F80u) | ((b0 >> 1) & 0x7F800000u);
-            o[2] = ((b1 & 0xFFu) << 7) | ((b1 & 0xFF00u) << 15);
-            o[3] = ((b1 >> 9) & 0x7F80u) | ((b1 >> 1) & 0x7F800000u);
-            if (zero_tail || gxi < ncols) *reinterpret_cast<sws_u32x4 *>(&out[l - lo][xg]) = o;
-        }
-        return;
-    }
-    const int x = tid & (COLS - 1), gx = gx0 + x, per = NT / COLS;
-    const bool col_ok = gx < ncols;
-    /* no load below sits under a lane condition (a conditional load is a branch, the load and a wait for it: a memory round
-     * trip per tap): columns past the picture read the last column's entries and do not use them */
-    const int gxc = col_ok ? gx : ncols - 1;
-    const int pos = posT[gxc];
-    const int16_t *f = coefT + (size_t)gxc * fs;
-    const int last = imin(gx0 + COLS, ncols) - 1;
-    /* 16-byte pieces when the plane allows it, dwords otherwise */
-    const bool al16 = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 15) == 0;
-    const int s0 = B * posT[gx0], s1 = B * (posT[last] + fs), a0 = al16 ? (s0 & ~15) : (s0 & ~3), nd = (s1 - a0 + 3) >> 2;     /* bytes */
-    /* the column's filter in registers as four pairs of 16-bit taps (taps past fs are zero): the line loops below multiply by
-     * them instead of reloading.  Eight taps: the column's entry of the bank is one aligned 16-byte word (the banks are
-     * hipMalloc'ed by mi355_sws_create) */
-    uint32_t cp[4];
-    if (fs == 8) {
-        const uint4 w = *reinterpret_cast<const uint4 *>(f);
-        cp[0] = w.x; cp[1] = w.y; cp[2] = w.z; cp[3] = w.w;
-    } else {
-        int t[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) t[j] = f[j < fs ? j : 0];
-#pragma unroll
-        for (int j = 0; j < 4; j++) cp[j] = (2 * j < fs ? (uint32_t)t[2 * j] & 0xFFFFu : 0u) | (2 * j + 1 < fs ? (uint32_t)t[2 * j + 1] << 16 : 0u);
-    }
-    const bool staged = may_stage && nd <= PITCH - 2 && s1 >= s0 && ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 3) == 0;
-    if (!staged) {
-        if (col_ok) {
-            for (int l = lo + tid / COLS; l <= hi; l += per) out[l - lo][x] = (int16_t)hscale_one<ST>(src + (size_t)l * stride, f, pos, fs, hsh);
-        } else if (zero_tail) {
-            for (int l = lo + tid / COLS; l <= hi; l += per) out[l - lo][x] = 0;
-        }
-        return;
-    }
-    /* idx / n as a 24-bit multiply and a shift (mi355_div20: exact for idx * n < 2^19; here idx < LINES * n, n <= PITCH) */
-    static_assert(LINES * PITCH * PITCH < (1 << 19), "mi355_div20 range");
-    const int np = al16 ? (nd + 3) >> 2 : nd, inv = mi355_inv20(np);
-    /* 16-byte pieces travel through registers, one round ahead: the loads of round r + 1 are issued before round r's
-     * arithmetic and stored to the staging lines after it (a round's loads would otherwise be waited for at its first
-     * barrier with nothing to do: a third of the kernel's time on a 2:1 reduction).  At most PF pieces per thread and round. */
-    constexpr int PF = (LINES * ((PITCH + 3) / 4) + NT - 1) / NT;
-    uint4 pre[PF];
-    /* which piece of a round a thread moves does not change from round to round: its staging row, source column and LDS address are
-     * worked out once per plane.  Nothing sits under a lane condition: a piece past the round's last repeats the last one, a line past
-     * the plane's last needed line repeats that one (the same bytes to the same place, or to a staging line nothing reads). */
-    int p_row[PF], p_col[PF];
-    uint32_t *p_lds[PF];
-#pragma unroll
-    for (int j = 0; j < PF; j++) {
-        const int idx = imin(tid + j * NT, LINES * np - 1), r = mi355_div20(idx, inv), d = idx - r * np, off = a0 + 16 * d;
-        p_row[j] = r;
-        p_col[j] = imin(off, (B * srcW - 1) & ~15);
-        p_lds[j] = &stage[r][4 * d];
-    }
-    auto fetch16 = [&](int base) {
-#pragma unroll
-        for (int j = 0; j < PF; j++) {
-            if (j * NT >= LINES * np) break;                 /* a narrow plane's round is fewer pieces than threads: the same for every thread */
-            /* the aligned 16 bytes lie inside the line's stride (both multiples of 16, column < srcW <= stride): always readable.
-             * Bytes at and past srcW (padding) are whatever the plane holds there: no tap with a non-zero coefficient reads them —
-             * mi355_sws_create stages only filter banks whose every position + size stays inside the line, as the reference's
-             * initFilter builds them (utils.c "fix borders") — and a tap past the filter's size multiplies them by zero. */
-            const uint4 w = *reinterpret_cast<const uint4 *>(src + (size_t)imin(base + p_row[j], hi) * stride + p_col[j]);
-            pre[j] = w;
-        }
-    };
-#ifndef MI355_SWS_EXP_NOSTAGE     /* developer experiments (tools/exp_sws_sg.sh): the pass without its loads / without its arithmetic */
-    if (al16) fetch16(lo);
-#endif
-    for (int base = lo; base <= hi; base += LINES) {
-#ifndef MI355_SWS_EXP_NOSTAGE
-        if (al16) {
-#pragma unroll
-            for (int j = 0; j < PF; j++) {
-                if (j * NT >= LINES * np) break;
-                *reinterpret_cast<uint4 *>(p_lds[j]) = pre[j];
-            }
-        } else
-        for (int idx = tid; idx < LINES * np; idx += NT) {
-            const int r = mi355_div20(idx, inv), d = idx - r * np, line = base + r;
-            if (line > hi) continue;
-            const uint8_t *p = src + (size_t)line * stride + a0 + 4 * d;
-            uint32_t w;
-            if (a0 + 4 * d + 4 <= B * srcW) w = *reinterpret_cast<const uint32_t *>(p);
-            else {
-                w = 0;
-                for (int b = 0; b < 4; b++) if (a0 + 4 * d + b < B * srcW) w |= (uint32_t)p[b] << (8 * b);
-            }
-            stage[r][d] = w;
-        }
-#endif
-        __syncthreads();
-#ifndef MI355_SWS_EXP_NOSTAGE
-        if (al16 && base + LINES <= hi) fetch16(base + LINES);
-#endif
-        /* the thread's column over the staged lines: fixed trip count, so line and output addresses are
-         * immediate offsets from one base each; tap count rounded up to 1 / 2 / 4 / 8 (taps past fs are zero, the
-         * bytes exist: slack) */
-        const int r0 = tid / COLS;
-        const uint8_t *row0 = reinterpret_cast<const uint8_t *>(stage[r0]) + (B * pos - a0);
-        int16_t *out0 = &out[base + r0 - lo][x];
-        const int left = uniform(hi - base - r0);            /* lines r0, r0 + per, ... while k * per <= left (r0: one value per wave) */
-#ifndef MI355_SWS_EXP_NOLINES
-        if (col_ok) {
-            if (fs == 1) hscale_lines<COLS, 1, OP, ST>(row0, out0, cp, left, hsh);
-            else if (fs <= 2) hscale_lines<COLS, 2, OP, ST>(row0, out0, cp, left, hsh);
-            else if (fs <= 4) hscale_lines<COLS, 4, OP, ST>(row0, out0, cp, left, hsh);
-            else if (fs <= 8) hscale_lines8<COLS, OP, ST>(row0, out0, cp, left, hsh);
-            else {
-                for (int k = 0; k < LINES / per && k * per <= left; k++) {
-                    const ST *row = reinterpret_cast<const ST *>(row0 + k * per * (PITCH * 4));
-                    int val = 0;
-                    for (int j = 0; j < fs; j++) val += (int)row[j] * f[j];
-                    val >>= hsh;
-                    out0[k * per * OP] = (int16_t)(val < 32767 ? val : 32767);
-                }
-            }
-        } else if (zero_tail) {
-            for (int k = 0; k < LINES / per && k * per <= left; k++) out0[k * per * OP] = 0;
-        }
-#endif
-        __syncthreads();
-    }
-}
-
-/* Vertical pass + LUT for the output rows of a tile with the row's filter taps and source-line indices in
- * registers: NL / NC = luma / chroma tap counts rounded up to 1, 2, 4 or 8 (taps past the real size carry a
- * zero coefficient and a valid line index).  A thread owns one output row and every 16th pair of it. */
-template <int NL, int NC, bool WIDE>
-__device__ __forceinline__ void vertical_rows(const SwsDev &c, const LutLds &lut, const int16_t (*s_lum)[TW], const int16_t (*s_cu)[TW / 2],
-                                              const int16_t (*s_cv)[TW / 2], uint8_t (*s_out)[TW * 3], int tid, int y0, int y1, int llo, int clo,
-                                              int npairs, int mode, uint8_t *wide_dst, int dst_stride, int out_row0)
-{
-    /* out_row0: first tile row of this pass of the narrow form (s_out holds OUT_ROWS rows at a time) */
-    const int row = tid >> 4, gy = y0 + row;
-    if (gy > y1 || (!WIDE && (row < out_row0 || row >= out_row0 + OUT_ROWS))) return;
-    const int ls = c.vls, cs = c.vcs;
-    const int lfirst = imax(1 - ls, c.vLumP[gy]), cfirst = imax(1 - cs, c.vChrP[gy]);
-    /* the taps: every load unconditional (a tap past the filter reads tap 0 and becomes zero), so that they are in flight together */
-    int lf[NL], li[NL], cf[NC], ci[NC];
-#pragma unroll
-    for (int j = 0; j < NL; j++) lf[j] = c.vLumC[(size_t)gy * ls + (j < ls ? j : 0)];
-#pragma unroll
-    for (int j = 0; j < NC; j++) cf[j] = c.vChrC[(size_t)gy * cs + (j < cs ? j : 0)];
-#pragma unroll
-    for (int j = 0; j < NL; j++) {
-        lf[j] = j < ls ? lf[j] : 0;
-        li[j] = clampi(lfirst + (j < ls ? j : 0), 0, c.srcH - 1) - llo;
-    }
-#pragma unroll
-    for (int j = 0; j < NC; j++) {
-        cf[j] = j < cs ? cf[j] : 0;
-        ci[j] = clampi(cfirst + (j < cs ? j : 0), 0, c.chrSrcH - 1) - clo;
-    }
-    if (WIDE) {
-        /* full tile, 8-byte aligned destination: a thread takes eight neighbouring samples (16 / 8 bytes per LDS read)
-         * and stores its 24 RGB bytes directly */
-        const int grp = tid & 15;
-        int Y[8], U[4], V[4];
-        if (mode == 1) {
-            const int uvalpha = cs == 1 ? 0 : cf[NC > 1 ? 1 : 0];
-            const sws_u32x4 l0 = *reinterpret_cast<const sws_u32x4 *>(&s_lum[li[0]][8 * grp]);
-            const sws_u32x2 u0 = *reinterpret_cast<const sws_u32x2 *>(&s_cu[ci[0]][4 * grp]), v0 = *reinterpret_cast<const sws_u32x2 *>(&s_cv[ci[0]][4 * grp]);
-            const sws_u32x2 u1 = *reinterpret_cast<const sws_u32x2 *>(&s_cu[ci[NC > 1 ? 1 : 0]][4 * grp]), v1 = *reinterpret_cast<const sws_u32x2 *>(&s_cv[ci[NC > 1 ? 1 : 0]][4 * grp]);
-#pragma unroll
-            for (int k = 0; k < 8; k++) Y[k] = clip_u8((int16_t)(l0[k >> 1] >> (16 * (k & 1))) >> 7);
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int a = (int16_t)(u0[k >> 1] >> (16 * (k & 1))), b = (int16_t)(v0[k >> 1] >> (16 * (k & 1)));
-                const int a1 = (int16_t)(u1[k >> 1] >> (16 * (k & 1))), b1 = (int16_t)(v1[k >> 1] >> (16 * (k & 1)));
-                if (uvalpha < 2048) { U[k] = clip_u8(a >> 7); V[k] = clip_u8(b >> 7); }
-                else { U[k] = clip_u8((a + a1) >> 8); V[k] = clip_u8((b + b1) >> 8); }
-            }
-        } else if (mode == 2) {
-            const int ya = lf[NL > 1 ? 1 : 0], ua = cf[NC > 1 ? 1 : 0], ya1 = 4096 - ya, ua1 = 4096 - ua;
-            const sws_u32x4 l0 = *reinterpret_cast<const sws_u32x4 *>(&s_lum[li[0]][8 * grp]), l1 = *reinterpret_cast<const sws_u32x4 *>(&s_lum[li[NL > 1 ? 1 : 0]][8 * grp]);
-            const sws_u32x2 u0 = *reinterpret_cast<const sws_u32x2 *>(&s_cu[ci[0]][4 * grp]), v0 = *reinterpret_cast<const sws_u32x2 *>(&s_cv[ci[0]][4 * grp]);
-            const sws_u32x2 u1 = *reinterpret_cast<const sws_u32x2 *>(&s_cu[ci[NC > 1 ? 1 : 0]][4 * grp]), v1 = *reinterpret_cast<const sws_u32x2 *>(&s_cv[ci[NC > 1 ? 1 : 0]][4 * grp]);
-#pragma unroll
-            for (int k = 0; k < 8; k++)
-                Y[k] = clip_u8(((int16_t)(l0[k >> 1] >> (16 * (k & 1))) * ya1 + (int16_t)(l1[k >> 1] >> (16 * (k & 1))) * ya) >> 19);
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                U[k] = clip_u8(((int16_t)(u0[k >> 1] >> (16 * (k & 1))) * ua1 + (int16_t)(u1[k >> 1] >> (16 * (k & 1))) * ua) >> 19);
-                V[k] = clip_u8(((int16_t)(v0[k >> 1] >> (16 * (k & 1))) * ua1 + (int16_t)(v1[k >> 1] >> (16 * (k & 1))) * ua) >> 19);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; k++) Y[k] = 1 << 18;
-#pragma unroll
-            for (int k = 0; k < 4; k++) U[k] = V[k] = 1 << 18;
-            /* two taps at a time: the same sample of two source lines side by side in a dword (one byte-permute) against the
-             * tap pair, v_dot2_i32_i16 — the same integer sum as the reference's per-tap multiply-add (15-bit samples,
-             * 16-bit coefficients, int accumulators) */
-            if (NL >= 2) {
-#pragma unroll
-                for (int j = 0; j + 1 < NL; j += 2) {
-                    const sws_u32x4 la = *reinterpret_cast<const sws_u32x4 *>(&s_lum[li[j]][8 * grp]), lb = *reinterpret_cast<const sws_u32x4 *>(&s_lum[li[j + 1]][8 * grp]);
-                    const uint32_t cp = ((uint32_t)lf[j] & 0xFFFFu) | ((uint32_t)lf[j + 1] << 16);
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        Y[2 * q] = sws_dot2(sws_lo2(la[q], lb[q]), cp, Y[2 * q]);
-                        Y[2 * q + 1] = sws_dot2(sws_hi2(la[q], lb[q]), cp, Y[2 * q + 1]);
-                    }
-                }
-            } else {
-                const sws_u32x4 l = *reinterpret_cast<const sws_u32x4 *>(&s_lum[li[0]][8 * grp]);
-#pragma unroll
-                for (int k = 0; k < 8; k++) Y[k] += (int16_t)(l[k >> 1] >> (16 * (k & 1))) * lf[0];
-            }
-            if (NC >= 2) {
-#pragma unroll
-                for (int j = 0; j + 1 < NC; j += 2) {
-                    const sws_u32x2 ua = *reinterpret_cast<const sws_u32x2 *>(&s_cu[ci[j]][4 * grp]), ub = *reinterpret_cast<const sws_u32x2 *>(&s_cu[ci[j + 1]][4 * grp]);
-                    const sws_u32x2 va = *reinterpret_cast<const sws_u32x2 *>(&s_cv[ci[j]][4 * grp]), vb = *reinterpret_cast<const sws_u32x2 *>(&s_cv[ci[j + 1]][4 * grp]);
-                    const uint32_t cp = ((uint32_t)cf[j] & 0xFFFFu) | ((uint32_t)cf[j + 1] << 16);
-#pragma unroll
-                    for (int q = 0; q < 2; q++) {
-                        U[2 * q] = sws_dot2(sws_lo2(ua[q], ub[q]), cp, U[2 * q]);
-                        U[2 * q + 1] = sws_dot2(sws_hi2(ua[q], ub[q]), cp, U[2 * q + 1]);
-                        V[2 * q] = sws_dot2(sws_lo2(va[q], vb[q]), cp, V[2 * q]);
-                        V[2 * q + 1] = sws_dot2(sws_hi2(va[q], vb[q]), cp, V[2 * q + 1]);
-                    }
-                }
-            } else {
-                const sws_u32x2 u = *reinterpret_cast<const sws_u32x2 *>(&s_cu[ci[0]][4 * grp]), v = *reinterpret_cast<const sws_u32x2 *>(&s_cv[ci[0]][4 * grp]);
-#pragma unroll
-                for (int k = 0; k < 4; k++) { U[k] += (int16_t)(u[k >> 1] >> (16 * (k & 1))) * cf[0]; V[k] += (int16_t)(v[k >> 1] >> (16 * (k & 1))) * cf[0]; }
-            }
-#pragma unroll
-            for (int p = 0; p < 4; p++) {       /* clipped per pair, only if one of its four values has bit 8 set (output.c:963) */
-                int &Y1 = Y[2 * p], &Y2 = Y[2 * p + 1], &Up = U[p], &Vp = V[p];
-                Y1 >>= 19; Y2 >>= 19; Up >>= 19; Vp >>= 19;
-                if ((Y1 | Y2 | Up | Vp) & 0x100) { Y1 = clip_u8(Y1); Y2 = clip_u8(Y2); Up = clip_u8(Up); Vp = clip_u8(Vp); }
-            }
-        }
-        int r[4], g[4], b[4];
-#pragma unroll
-        for (int p = 0; p < 4; p++) { r[p] = lut.rV[V[p]]; g[p] = lut.gU[U[p]] + lut.gV[V[p]]; b[p] = lut.bU[U[p]]; }
-        rgb24_store8(lut, wide_dst + (size_t)row * dst_stride + 24 * grp, Y, r, g, b);
-        return;
-    }
-    /* fixed trip count: the pairs of a thread are 16 apart, so every LDS address is one base plus an immediate */
-#pragma unroll
-    for (int k = 0; k < TW / 32; k++) {
-        const int i = (tid & 15) + 16 * k;
-        if (i >= npairs) continue;
-        int Y1, Y2, U, V;
-        if (mode == 1) {          /* yuv2rgb_1_c_template output.c:1043-1110 (ls == 1, cs <= 2) */
-            const int uvalpha = cs == 1 ? 0 : cf[NC > 1 ? 1 : 0];
-            Y1 = clip_u8(s_lum[li[0]][2 * i] >> 7); Y2 = clip_u8(s_lum[li[0]][2 * i + 1] >> 7);
-            if (uvalpha < 2048) { U = clip_u8(s_cu[ci[0]][i] >> 7); V = clip_u8(s_cv[ci[0]][i] >> 7); }
-            else { U = clip_u8((s_cu[ci[0]][i] + s_cu[ci[NC > 1 ? 1 : 0]][i]) >> 8); V = clip_u8((s_cv[ci[0]][i] + s_cv[ci[NC > 1 ? 1 : 0]][i]) >> 8); }
-        } else if (mode == 2) {   /* yuv2rgb_2_c_template :998-1041 (ls == cs == 2) */
-            const int ya = lf[NL > 1 ? 1 : 0], ua = cf[NC > 1 ? 1 : 0], ya1 = 4096 - ya, ua1 = 4096 - ua;
-            Y1 = clip_u8((s_lum[li[0]][2 * i] * ya1 + s_lum[li[NL > 1 ? 1 : 0]][2 * i] * ya) >> 19);
-            Y2 = clip_u8((s_lum[li[0]][2 * i + 1] * ya1 + s_lum[li[NL > 1 ? 1 : 0]][2 * i + 1] * ya) >> 19);
-            U = clip_u8((s_cu[ci[0]][i] * ua1 + s_cu[ci[NC > 1 ? 1 : 0]][i] * ua) >> 19);
-            V = clip_u8((s_cv[ci[0]][i] * ua1 + s_cv[ci[NC > 1 ? 1 : 0]][i] * ua) >> 19);
-        } else {                  /* yuv2rgb_X_c_template :937-996: clipped only if a value has bit 8 set */
-            Y1 = Y2 = U = V = 1 << 18;
-#pragma unroll
-            for (int j = 0; j < NL; j++) {
-                const uint32_t two = *reinterpret_cast<const uint32_t *>(&s_lum[li[j]][2 * i]);
-                Y1 += (int16_t)(two & 0xFFFF) * lf[j]; Y2 += (int16_t)(two >> 16) * lf[j];
-            }
-#pragma unroll
-            for (int j = 0; j < NC; j++) { U += s_cu[ci[j]][i] * cf[j]; V += s_cv[ci[j]][i] * cf[j]; }
-            Y1 >>= 19; Y2 >>= 19; U >>= 19; V >>= 19;
-            if ((Y1 | Y2 | U | V) & 0x100) { Y1 = clip_u8(Y1); Y2 = clip_u8(Y2); U = clip_u8(U); V = clip_u8(V); }
-        }
-        write_pair(lut, &s_out[row - out_row0][i * 6], Y1, Y2, U, V);
-    }
-}
-
-/* LDS of a workgroup, sized per context (sws_plan): the horizontal pass's results for the source lines a tile needs, the tables, and one
- * block shared by the staging lines (horizontal pass) and the output rows of tiles that cannot store from registers (after it). */
-__host__ __device__ constexpr int sws_lds_bytes(int lum_lines, int chr_lines, int stage = STAGE_BYTES)
-{
-    return lum_lines * TW * 2 + 2 * chr_lines * (TW / 2) * 2 + (int)sizeof(LutLds) + stage;
-}
-
-/* the sixteen tap-count instances of vertical_rows (taps in registers, rounded up to 1 / 2 / 4 / 8) */
-#define MI355_VR(NL, NC) vertical_rows<NL, NC, MI355_VR_WIDE>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, r0)
-#define MI355_VR_ALL \
-    switch (bl * 4 + bc) { \
-    case 0: MI355_VR(1, 1); break;   case 1: MI355_VR(1, 2); break;   case 2: MI355_VR(1, 4); break;   case 3: MI355_VR(1, 8); break; \
-    case 4: MI355_VR(2, 1); break;   case 5: MI355_VR(2, 2); break;   case 6: MI355_VR(2, 4); break;   case 7: MI355_VR(2, 8); break; \
-    case 8: MI355_VR(4, 1); break;   case 9: MI355_VR(4, 2); break;   case 10: MI355_VR(4, 4); break;  case 11: MI355_VR(4, 8); break; \
-    case 12: MI355_VR(8, 1); break;  case 13: MI355_VR(8, 2); break;  case 14: MI355_VR(8, 4); break;  default: MI355_VR(8, 8); break; \
-    }
-
-/* Tiles that cannot store from registers (the picture's right edge, a destination that is not 8-byte aligned, filters of more than
- * eight taps): the rows go through s_out, OUT_ROWS at a time. */
-__device__ __forceinline__ void vertical_narrow(const SwsDev *cp, const LutLds *lutp, const int16_t (*s_lum)[TW], const int16_t (*s_cu)[TW / 2],
-                                                          const int16_t (*s_cv)[TW / 2], uint8_t (*s_out)[TW * 3], uint8_t *tile_dst, int dst_stride,
-                                                          int x0, int y0, int y1, int llo, int clo)
-{
-    SwsDev c = *cp;
-    c.vLumC = mi355_global(c.vLumC); c.vChrC = mi355_global(c.vChrC); c.vLumP = mi355_global(c.vLumP); c.vChrP = mi355_global(c.vChrP);
-    const LutLds &s_lut = *lutp;
-    const int tid = threadIdx.x, ls = c.vls, cs = c.vcs, mode = packed_mode(ls, cs);
-    const int npairs = imin(TW, c.dstW - x0 + 1) >> 1;     /* (dstW + 1) >> 1 pairs in the picture */
-    const int nbytes = imin(TW, c.dstW - x0) * 3, nrows_all = y1 - y0 + 1;
-    const int bl = ls <= 1 ? 0 : (ls <= 2 ? 1 : (ls <= 4 ? 2 : 3)), bc = cs <= 1 ? 0 : (cs <= 2 ? 1 : (cs <= 4 ? 2 : 3));
-    uint8_t *const wide_dst = nullptr;
-    struct { int dst_stride; } fr{ dst_stride };
-    for (int r0 = 0; r0 < nrows_all; r0 += OUT_ROWS) {
-#ifndef MI355_SWS_NO_V
-        if (ls <= 8 && cs <= 8) {
-#define MI355_VR_WIDE false
-            MI355_VR_ALL
-#undef MI355_VR_WIDE
-        } else
-        for (int p = tid; p < OUT_ROWS * (TW / 2); p += NT) {
-            const int row = r0 + (p >> 6), i = p & 63, gy = y0 + row;
-            if (gy > y1 || i >= npairs) continue;
-            TileRows R{ s_lum, s_cu, s_cv, imax(1 - ls, c.vLumP[gy]), llo, c.srcH - 1, imax(1 - cs, c.vChrP[gy]), clo, c.chrSrcH - 1 };
-            int ya = 0, ua = 0;
-            if (mode == 1) ua = cs == 1 ? 0 : c.vChrC[2 * gy + 1];
-            else if (mode == 2) { ya = c.vLumC[2 * gy + 1]; ua = c.vChrC[2 * gy + 1]; }
-            rgb_pair(s_lut, &s_out[row - r0][i * 6], R, i, mode, c.vLumC + (size_t)gy * ls, ls, c.vChrC + (size_t)gy * cs, cs, ya, ua);
-        }
-#endif
-        __syncthreads();
-        /* rows out: only samples below dstW (for odd dstW the reference also writes the phantom partner of
-         * the last sample from uninitialised ring-buffer data; that sample is not reproduced) */
-#ifndef MI355_SWS_NO_OUT
-        {
-            uint8_t *d0 = tile_dst + (size_t)r0 * fr.dst_stride;
-            const int nrows = imin(OUT_ROWS, nrows_all - r0);
-            const unsigned al = (unsigned)(uintptr_t)d0 | (unsigned)fr.dst_stride | (unsigned)nbytes;
-            /* mi355_div20 below: idx < nrows * n with nrows <= 16 and n <= TW * 3 / 4 = 96: idx * n < 2^18 */
-            if ((al & 15) == 0) {                     /* 16 bytes per thread and store */
-                const int n = nbytes >> 4, inv = mi355_inv20(n);
-                for (int idx = tid; idx < nrows * n; idx += NT) {
-                    const int row = mi355_div20(idx, inv), k = idx - row * n;
-                    reinterpret_cast<uint4 *>(d0 + (size_t)row * fr.dst_stride)[k] = reinterpret_cast<const uint4 *>(s_out[row])[k];
-                }
-            } else if ((al & 3) == 0) {
-                const int n = nbytes >> 2, inv = mi355_inv20(n);
-                for (int idx = tid; idx < nrows * n; idx += NT) {
-                    const int row = mi355_div20(idx, inv), k = idx - row * n;
-                    reinterpret_cast<uint32_t *>(d0 + (size_t)row * fr.dst_stride)[k] = reinterpret_cast<const uint32_t *>(s_out[row])[k];
-                }
-            } else {
-                for (int row = 0; row < nrows; row++)
-                    for (int k = tid; k < nbytes; k += NT) d0[(size_t)row * fr.dst_stride + k] = s_out[row][k];
-            }
-        }
-#endif
-        __syncthreads();                           /* the next pass overwrites s_out */
-    }
-}
-
-/* LCAP / CCAP: source lines the LDS tile holds — the context's largest tile span picks the instance (sws_launch), and with it how
- * many workgroups a CU's 160 KB hold (one wave of each per SIMD); WAVES: the waves per SIMD the register allocation then aims at */
-/* ST: the source's sample type; the uint16_t instances (9 / 10 bit sources) differ in the horizontal pass and its staging lines only */
-template <int LCAP, int CCAP, int WAVES, typename ST = uint8_t>
-#ifndef MI355_HIP_EMU_H
-__attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
-#endif
-__global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi355_sws_frame *frames)
-{
-    __shared__ __attribute__((aligned(16))) int16_t s_lum[LCAP][TW];
-    __shared__ __attribute__((aligned(16))) int16_t s_cu[CCAP][TW / 2], s_cv[CCAP][TW / 2];
-    __shared__ LutLds s_lut;
-    /* the staging lines of the horizontal pass; the output rows of tiles that cannot store from registers reuse them after it */
-    __shared__ __attribute__((aligned(16))) uint8_t s_io[stage_bytes<ST>()];
-    uint8_t (*s_out)[TW * 3] = reinterpret_cast<uint8_t (*)[TW * 3]>(s_io);
-    SwsDev c = *cp;                                   /* pointers of the records: global address space (mi355_rt.h) */
-    c.hLumC = mi355_global(c.hLumC); c.hChrC = mi355_global(c.hChrC); c.vLumC = mi355_global(c.vLumC); c.vChrC = mi355_global(c.vChrC);
-    c.hLumP = mi355_global(c.hLumP); c.hChrP = mi355_global(c.hChrP); c.vLumP = mi355_global(c.vLumP); c.vChrP = mi355_global(c.vChrP);
-    mi355_sws_frame fr = frames[blockIdx.z];
-    for (int k = 0; k < 3; k++) fr.src[k] = mi355_global(fr.src[k]);
-    fr.dst = mi355_global(fr.dst);
-    const int tid = threadIdx.x, th = c.th;
-    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * th, y1 = imin(y0 + th, c.dstH) - 1;
-    const int ls = c.vls, cs = c.vcs;
-    /* source lines this tile needs (swscale.c:459-468 for the first tap, :571-616 for the clamping) */
-    const int lfirst0 = imax(1 - ls, c.vLumP[y0]), lfirst1 = imax(1 - ls, c.vLumP[y1]);
-    const int cfirst0 = imax(1 - cs, c.vChrP[y0]), cfirst1 = imax(1 - cs, c.vChrP[y1]);
-    const int llo = clampi(lfirst0, 0, c.srcH - 1), lhi = clampi(lfirst1 + ls - 1, 0, c.srcH - 1);
-    const int clo = clampi(cfirst0, 0, c.chrSrcH - 1), chi = clampi(cfirst1 + cs - 1, 0, c.chrSrcH - 1);
-    lut_load(s_lut, &cp->luts, tid, NT);
-    /* horizontal pass: luma (the phantom partner of the last sample of an odd-width picture reads the
-     * zero-initialised tail of the reference's line buffer, utils.c:1241-1262), then the chroma planes */
-    uint32_t *s_stage = reinterpret_cast<uint32_t *>(s_io);
-#ifndef MI355_SWS_NO_H
-    hscale_tile<TW, TW, ST>(s_lum, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi, s_stage, tid, true, c.hstage != 0, c.hident_l != 0, c.depth);
-    hscale_tile<TW / 2, TW / 2, ST>(s_cu, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, c.depth);
-    hscale_tile<TW / 2, TW / 2, ST>(s_cv, fr.src[2], fr.src_stride[2], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, c.depth);
-#endif
-    __syncthreads();
-    /* vertical pass + LUT */
-    const int mode = packed_mode(ls, cs);
-    const int npairs = imin(TW, c.dstW - x0 + 1) >> 1;     /* (dstW + 1) >> 1 pairs in the picture */
-    /* full tiles with an 8-byte aligned destination leave straight from registers; the others go through s_out, OUT_ROWS rows at a time */
-    uint8_t *const tile_dst = fr.dst + (size_t)y0 * fr.dst_stride + (size_t)x0 * 3;
-    uint8_t *const wide_dst = (ls <= 8 && cs <= 8 && c.dstW - x0 >= TW && ((reinterpret_cast<uintptr_t>(tile_dst) | (uintptr_t)fr.dst_stride) & 7) == 0)
-                                  ? tile_dst : nullptr;
-    /* tap counts in registers, rounded up to 1 / 2 / 4 / 8 */
-    const int bl = ls <= 1 ? 0 : (ls <= 2 ? 1 : (ls <= 4 ? 2 : 3)), bc = cs <= 1 ? 0 : (cs <= 2 ? 1 : (cs <= 4 ? 2 : 3));
-#ifndef MI355_SWS_NO_V
-    if (wide_dst) {                               /* uniform over the workgroup: every row leaves from registers */
-        const int r0 = 0;
-#define MI355_VR_WIDE true
-        MI355_VR_ALL
-#undef MI355_VR_WIDE
-        return;
-    }
-#endif
-    vertical_narrow(cp, &s_lut, s_lum, s_cu, s_cv, s_out, tile_dst, fr.dst_stride, x0, y0, y1, llo, clo);
-#undef MI355_VR_ALL
-#undef MI355_VR
-}
-
-/* ---- planar destinations: yuv420p -> yuv420p / yuv422p / yuv444p ----------------------------------------------------------
- * The planar branch of swscale() (swscale.c:618-645) for 8-bit samples.  should_dither is 0 for an 8-bit source (:389, :445): every
- * dither value is 64.  A plane whose vertical filter has ONE tap takes yuv2plane1_8_c (output.c:257-266), (s + 64) >> 7 with the
- * coefficient unused; the others yuv2planeX_8_c (:242-255), ((64 << 12) + sum s_j * f_j) >> 19; both clipped to 0..255.
- * A thread takes eight neighbouring samples of one LDS line (one ds_read_b128 per tap) and stores their eight bytes at once.  Sixteen
- * lanes cover one line's 256 bytes, so each 16-lane group of a ds_read_b128 meets every bank once, whichever lines the rows read.
- * NTAP: 1 plane1; 2 / 4 / 8 planeX with the taps in registers (taps past fs carry a zero coefficient); 0 planeX with fs taps read as it goes.
- * GPP: 16-byte groups of a plane's tile row; NP: planes side by side in an LDS line (chroma: U | V). */
-/* DITH (a source deeper than 8 bits, should_dither swscale.c:389): the row's eight dither values come from the context's 8x8 table — row
- * y & 7 of the plane's own row counter (dstY for luma, chrDstY for chroma, :553-556), V read three columns on (:636-644); a group starts
- * on a multiple of eight columns, so sample k of a group takes value (k + offset) & 7. */
-template <int NTAP, int GPP, int NP, bool DITH = false>
-__device__ __forceinline__ void planar_rows(const int16_t *s, int lo, int maxl, const int16_t *vC, const int32_t *vP, int fs, int row0, int nrows,
-                                            int gx0, int width, uint8_t *d0, int st0, uint8_t *d1, int st1, int tid, const uint8_t (*dith)[8] = nullptr)
-{
-    constexpr int G = GPP * NP;                        /* groups per LDS line */
-    for (int t = tid; t < nrows * G; t += NT) {
-        const int r = t / G, g = t % G, gx = gx0 + 8 * (g % GPP), y = row0 + r;
-        if (gx >= width) continue;
-        const int first = imax(1 - fs, vP[y]);
-        const int16_t *col = s + 8 * g;
-        auto line = [&](int j) { return *reinterpret_cast<const sws_u32x4 *>(col + (size_t)(clampi(first + j, 0, maxl) - lo) * (G * 8)); };
-        auto sample = [](const sws_u32x4 &a, int k) { return (int)(int16_t)(a[k >> 1] >> (16 * (k & 1))); };
-        int v[8], dv[8];
-        if (DITH) {
-            const sws_u32x2 w = *reinterpret_cast<const sws_u32x2 *>(dith[y & 7]);
-            uint64_t q = ((uint64_t)w[1] << 32) | w[0];
-            if (NP > 1 && g >= GPP) q = (q >> 24) | (q << 40);      /* the V plane: offset 3 */
-#pragma unroll
-            for (int k = 0; k < 8; k++) dv[k] = (int)((q >> (8 * k)) & 0xFF);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; k++) dv[k] = 64;
-        }
-        if (NTAP == 1) {
-            const sws_u32x4 a = line(0);
-#pragma unroll
-            for (int k = 0; k < 8; k++) v[k] = (sample(a, k) + dv[k]) >> 7;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; k++) v[k] = dv[k] << 12;
-            if (NTAP == 0) {
-                for (int j = 0; j < fs; j++) {
-                    const int f = vC[(size_t)y * fs + j];
-                    const sws_u32x4 a = line(j);
-#pragma unroll
-                    for (int k = 0; k < 8; k++) v[k] += sample(a, k) * f;
-                }
-            } else {
-                constexpr int N = NTAP > 1 ? NTAP : 2;
-                int lf[N];
-#pragma unroll
-                for (int j = 0; j < N; j++) lf[j] = vC[(size_t)y * fs + (j < fs ? j : 0)];   /* unconditional: in flight together */
-                /* two taps at a time: the same sample of two lines side by side in a dword against the tap pair (v_dot2_i32_i16: the
-                 * reference's integer sum, as vertical_rows) */
-#pragma unroll
-                for (int j = 0; j < N; j += 2) {
-                    const sws_u32x4 la = line(j < fs ? j : 0), lb = line(j + 1 < fs ? j + 1 : 0);
-                    const uint32_t cp = (j < fs ? (uint32_t)lf[j] & 0xFFFFu : 0u) | (j + 1 < fs ? (uint32_t)lf[j + 1] << 16 : 0u);
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        v[2 * q] = sws_dot2(sws_lo2(la[q], lb[q]), cp, v[2 * q]);
-                        v[2 * q + 1] = sws_dot2(sws_hi2(la[q], lb[q]), cp, v[2 * q + 1]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 8; k++) v[k] >>= 19;
-        }
-        /* the clipped bytes pass sws_opaque before they are packed: left to itself the compiler fuses shift, clip and packing of two of them into
-         * v_ashr_pk_u8_i32 and ORs the next two bytes over its destination's upper half as if it were zero — on the device that half kept
-         * what the register held before (wrong 7th / 8th samples of a group, depending on the data) */
-        uint32_t w0 = 0, w1 = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) { w0 |= sws_opaque((uint32_t)clip_u8(v[k])) << (8 * k); w1 |= sws_opaque((uint32_t)clip_u8(v[4 + k])) << (8 * k); }
-        const bool second = NP > 1 && g >= GPP;
-        uint8_t *d = (second ? d1 : d0) + (size_t)r * (second ? st1 : st0) + gx;
-        if (gx + 8 <= width && (reinterpret_cast<uintptr_t>(d) & 7) == 0) {
-            *reinterpret_cast<sws_u32x2 *>(d) = sws_u32x2{ w0, w1 };
-        } else {                                       /* the plane's right edge, or a row that is not 8-byte aligned */
-            const int n = imin(8, width - gx);
-            for (int k = 0; k < n; k++) d[k] = (uint8_t)((k < 4 ? w0 : w1) >> (8 * (k & 3)));
-        }
-    }
-}
-/* the vertical pass of one LDS tile: its tap count rounded up to 1 / 2 / 4 / 8, more from memory */
-template <int GPP, int NP, bool DITH = false>
-__device__ __forceinline__ void planar_pass(const int16_t *s, int lo, int maxl, const int16_t *vC, const int32_t *vP, int fs, int row0, int nrows,
-                                            int gx0, int width, uint8_t *d0, int st0, uint8_t *d1, int st1, int tid, const uint8_t (*dith)[8] = nullptr)
-{
-    if (fs == 1) planar_rows<1, GPP, NP, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, dith);
-    else if (fs <= 2) planar_rows<2, GPP, NP, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, dith);
-    else if (fs <= 4) planar_rows<4, GPP, NP, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, dith);
-    else if (fs <= 8) planar_rows<8, GPP, NP, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, dith);
-    else planar_rows<0, GPP, NP, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, dith);
-}
-
-/* LDS of a planar workgroup: the luma lines, the chroma lines (U | V side by side, CW samples each) and the staging lines; no LUT, no output rows */
-__host__ __device__ constexpr int sws_planar_lds_bytes(int lum_lines, int chr_lines, int cw, int stage = STAGE_BYTES)
-{
-    return lum_lines * TW * 2 + chr_lines * 2 * cw * 2 + stage;
-}
-__host__ __device__ constexpr int sws_planar_waves(int lum_lines, int chr_lines, int cw, int stage = STAGE_BYTES)
-{
-    return 160 * 1024 / sws_planar_lds_bytes(lum_lines, chr_lines, cw, stage) < 8 ? 160 * 1024 / sws_planar_lds_bytes(lum_lines, chr_lines, cw, stage) : 8;
-}
-
-/* One workgroup per output tile of TW luma columns x th luma rows (blockIdx.z: the picture of the batch).  The tile's chroma is CW = TW >> hshift
- * columns and the chroma rows cy with cy << vshift inside the tile's rows (swscale.c:618-645: a chroma row is written with the luma row
- * cy << vshift, chrSkipMask).  Horizontal pass of the source lines the tile needs into LDS (hscale_tile, as k_sws_generic), then the
- * vertical pass from LDS straight to the three planes. */
-template <int LCAP, int CCAP, int CW, typename ST = uint8_t>
-#ifndef MI355_HIP_EMU_H
-__attribute__((amdgpu_waves_per_eu(sws_planar_waves(LCAP, CCAP, CW, stage_bytes<ST>()), sws_planar_waves(LCAP, CCAP, CW, stage_bytes<ST>()))))
-#endif
-__global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355_sws_planar_frame *frames)
-{
-    constexpr bool DITH = sizeof(ST) == 2;            /* a source deeper than 8 bits dithers its 8-bit planes */
-    __shared__ __attribute__((aligned(16))) int16_t s_lum[LCAP][TW];
-    __shared__ __attribute__((aligned(16))) int16_t s_chr[CCAP][2 * CW];
-    __shared__ __attribute__((aligned(16))) uint32_t s_stage[stage_bytes<ST>() / 4];
-    SwsDev c = *cp;
-    c.hLumC = mi355_global(c.hLumC); c.hChrC = mi355_global(c.hChrC); c.vLumC = mi355_global(c.vLumC); c.vChrC = mi355_global(c.vChrC);
-    c.hLumP = mi355_global(c.hLumP); c.hChrP = mi355_global(c.hChrP); c.vLumP = mi355_global(c.vLumP); c.vChrP = mi355_global(c.vChrP);
-    mi355_sws_planar_frame fr = frames[blockIdx.z];
-    for (int k = 0; k < 3; k++) { fr.src[k] = mi355_global(fr.src[k]); fr.dst[k] = mi355_global(fr.dst[k]); }
-    const int tid = threadIdx.x, th = c.th, hs = c.hshift, vs = c.vshift;
-    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * th, y1 = imin(y0 + th, c.dstH) - 1;
-    const int cy0 = (y0 + (1 << vs) - 1) >> vs, cy1 = y1 >> vs;       /* the tile's chroma rows (none: a one-row tile on an odd row of 4:2:0) */
-    const int ls = c.vls, cs = c.vcs;
-    /* source lines the tile needs (swscale.c:459-468 for the first tap, :571-616 for the clamping) */
-    const int llo = clampi(imax(1 - ls, c.vLumP[y0]), 0, c.srcH - 1), lhi = clampi(imax(1 - ls, c.vLumP[y1]) + ls - 1, 0, c.srcH - 1);
-    hscale_tile<TW, TW, ST>(s_lum, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi, s_stage, tid, false, c.hstage != 0, c.hident_l != 0, c.depth);
-    int clo = 0;
-    if (cy0 <= cy1) {
-        clo = clampi(imax(1 - cs, c.vChrP[cy0]), 0, c.chrSrcH - 1);
-        const int chi = clampi(imax(1 - cs, c.vChrP[cy1]) + cs - 1, 0, c.chrSrcH - 1);
-        hscale_tile<CW, 2 * CW, ST>(s_chr, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false,
-                                    c.hstage != 0, c.hident_c != 0, c.depth);
-        hscale_tile<CW, 2 * CW, ST>(reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]), fr.src[2], fr.src_stride[2], c.chrSrcW, c.hChrP, c.hChrC, c.hcs,
-                                    x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, c.depth);
-    }
-    __syncthreads();
-    const uint8_t (*dith)[8] = DITH ? mi355_global(cp)->dither : nullptr;
-    planar_pass<TW / 8, 1, DITH>(&s_lum[0][0], llo, c.srcH - 1, c.vLumC, c.vLumP, ls, y0, y1 - y0 + 1, x0, c.dstW,
-                                 fr.dst[0] + (size_t)y0 * fr.dst_stride[0], fr.dst_stride[0], nullptr, 0, tid, dith);
-    if (cy0 <= cy1)
-        planar_pass<CW / 8, 2, DITH>(&s_chr[0][0], clo, c.chrSrcH - 1, c.vChrC, c.vChrP, cs, cy0, cy1 - cy0 + 1, x0 >> hs, c.chrDstW,
-                                     fr.dst[1] + (size_t)cy0 * fr.dst_stride[1], fr.dst_stride[1], fr.dst[2] + (size_t)cy0 * fr.dst_stride[2], fr.dst_stride[2], tid, dith);
-}
-
-#ifndef MI355_C24_ROWS
-#define MI355_C24_ROWS 16
-#endif
-#ifndef MI355_IDENT_ROWS
-#define MI355_IDENT_ROWS 16
-#endif
-constexpr int C24_ROWS = MI355_C24_ROWS, C24_COLS = 512, IDENT_ROWS = MI355_IDENT_ROWS;      /* rows of a tile of k_sws_c24 / of k_sws_ident1 */
-/* eight samples of one line: Y bytes in (y0, y1), the four pairs' LUT row offsets in r/g/b -> 24 RGB bytes */
-__device__ __forceinline__ void c24_line(const LutLds &t, uint8_t *d, uint32_t y0, uint32_t y1, const int *r, const int *g, const int *b)
-{
-    int Y[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) Y[k] = ((k < 4 ? y0 : y1) >> (8 * (k & 3))) & 0xFF;
-    rgb24_store8(t, d, Y, r, g, b);
-}
-/* yuv2rgb_c_24_rgb (yuv2rgb.c:335-363): a block converts a 512 x 16 sample tile; a thread takes eight samples of two
- * lines per step (8-byte luma loads, 4-byte chroma loads, three 8-byte stores per line) — one (U,V) pair serves both
- * lines (LOADCHROMA :67-72, nearest chroma).  Unaligned planes and the right edge go pair by pair. */
-/* CS 1: an 8-bit yuv422p source — the reference doubles the chroma strides and so reads every other chroma line (yuv2rgb.c:133-136): line
- * (y >> 1) << 1 at the frame's own stride */
-template <int CS = 0>
-__global__ void __launch_bounds__(NT) k_sws_c24(const mi355_sws_luts *luts, int dstW, int sliceH, int sliceY, const mi355_sws_frame *frames)
-{
-    __shared__ LutLds s_lut;
-    const int tid = threadIdx.x;
-    mi355_sws_frame fr = frames[blockIdx.z];
-    for (int k = 0; k < 3; k++) fr.src[k] = mi355_global(fr.src[k]);
-    fr.dst = mi355_global(fr.dst);
-    const int x = blockIdx.x * C24_COLS + (tid & 63) * 8;   /* first of the thread's eight samples */
-    const int npairs = dstW >> 1;                            /* pairs i < dstW >> 1 (8 + 4 + 2 sample groups, yuv2rgb.c:129-171) */
-    const bool mine = (x >> 1) < npairs;
-    const bool wide = mine && (x >> 1) + 4 <= npairs &&
-                      ((reinterpret_cast<uintptr_t>(fr.src[0]) | (uintptr_t)fr.src_stride[0] | reinterpret_cast<uintptr_t>(fr.dst) | (uintptr_t)fr.dst_stride) & 7) == 0 &&
-                      ((reinterpret_cast<uintptr_t>(fr.src[1]) | (uintptr_t)fr.src_stride[1] | reinterpret_cast<uintptr_t>(fr.src[2]) | (uintptr_t)fr.src_stride[2]) & 3) == 0;
-    /* the samples of both of the thread's line pairs are requested before the LUT copy below: the block pays one memory
-     * round trip, not three (LUT, first pair, second pair) */
-    constexpr int NR = C24_ROWS / 2 / (NT / 64);
-    sws_u32x2 ya[NR], yc[NR];
-    uint32_t u4[NR], v4[NR];
-#pragma unroll
-    for (int q = 0; q < NR; q++) {
-        const int y = blockIdx.y * C24_ROWS + 2 * ((tid >> 6) + q * (NT / 64));
-        ya[q] = yc[q] = sws_u32x2{ 0u, 0u }; u4[q] = v4[q] = 0;
-        if (wide && y < sliceH) {
-            const uint8_t *py1 = fr.src[0] + (size_t)y * fr.src_stride[0] + x;
-            ya[q] = *reinterpret_cast<const sws_u32x2 *>(py1); yc[q] = *reinterpret_cast<const sws_u32x2 *>(py1 + fr.src_stride[0]);
-            u4[q] = *reinterpret_cast<const uint32_t *>(fr.src[1] + (size_t)((y >> 1) << CS) * fr.src_stride[1] + (x >> 1));
-            v4[q] = *reinterpret_cast<const uint32_t *>(fr.src[2] + (size_t)((y >> 1) << CS) * fr.src_stride[2] + (x >> 1));
-        }
-    }
-    MI355_ISSUE_FENCE();
-    lut_load(s_lut, luts, tid, NT);
-    __syncthreads();
-    if (!mine) return;
-#pragma unroll
-    for (int q = 0; q < NR; q++) {
-        const int rr = (tid >> 6) + q * (NT / 64);
-        const int y = blockIdx.y * C24_ROWS + 2 * rr;
-        if (y >= sliceH) break;
-        const uint8_t *py1 = fr.src[0] + (size_t)y * fr.src_stride[0] + x, *py2 = py1 + fr.src_stride[0];
-        const uint8_t *pu = fr.src[1] + (size_t)((y >> 1) << CS) * fr.src_stride[1] + (x >> 1), *pv = fr.src[2] + (size_t)((y >> 1) << CS) * fr.src_stride[2] + (x >> 1);
-        uint8_t *d1 = fr.dst + (size_t)(y + sliceY) * fr.dst_stride + (size_t)x * 3, *d2 = d1 + fr.dst_stride;
-        if (wide) {
-            const sws_u32x2 a = ya[q], c = yc[q];
-            int r[4], g[4], b[4];
-#pragma unroll
-            for (int p = 0; p < 4; p++) {
-                const int U = (u4[q] >> (8 * p)) & 0xFF, V = (v4[q] >> (8 * p)) & 0xFF;
-                r[p] = s_lut.rV[V]; g[p] = s_lut.gU[U] + s_lut.gV[V]; b[p] = s_lut.bU[U];
-            }
-            c24_line(s_lut, d1, a[0], a[1], r, g, b);
-            c24_line(s_lut, d2, c[0], c[1], r, g, b);
-        } else {
-            for (int p = 0; p < 4 && (x >> 1) + p < npairs; p++) {
-                write_pair(s_lut, d1 + 6 * p, py1[2 * p], py1[2 * p + 1], pu[p], pv[p]);
-                write_pair(s_lut, d2 + 6 * p, py2[2 * p], py2[2 * p + 1], pu[p], pv[p]);
-            }
-        }
-    }
-}
-
-/* The generic scaler on a context that does not scale (round 6): identity horizontal filters (hident_l / hident_c) and ONE vertical luma tap — what swscale() runs for an
- * unscaled yuv420p -> rgb24 conversion that may not take the special converter (SWS_ACCURATE_RND): hScale8To15 is src << 7, and the vertical pass reads those 15-bit values of
- * one luma line and of the row's one to four chroma lines (bicubic: four taps on the chroma planes' half height).  The same integers k_sws_generic computes through its LDS tile
- * (vertical_rows), straight from the source bytes to the LUT:
- *   X false, yuv2rgb24_1_c (output.c:1043-1110; vChrFilterSize <= 2): Y = (src << 7) >> 7, U / V = the first chroma line's sample, or ((c0 << 7) + (c1 << 7)) >> 8 = the mean of
- *     the two lines when the row's second coefficient is >= 2048;
- *   X true, yuv2rgb24_X_c (:937-996; three or four chroma taps): Y = ((1 << 18) + (src << 7) * lumFilter[0]) >> 19, U / V = ((1 << 18) + sum (c_j << 7) * chrFilter[j]) >> 19,
- *     a pair's four values clipped only if one of them has bit 8 set.
- * 512 x 16 sample tiles, a thread eight samples of a line per step; the rows' table entries, then all the samples of a thread are requested before the LUT copy (two round
- * trips per workgroup instead of the tile's staging rounds and barriers).  Only for even dstW (the phantom partner of an odd width's last sample stays with k_sws_generic). */
-template <bool X>
-__global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355_sws_frame *frames)
-{
-    __shared__ LutLds s_lut;
-    constexpr int NC = X ? 4 : 2;
-    const int tid = threadIdx.x;
-    const int dstW = cp->dstW, dstH = cp->dstH, cs = cp->vcs, srcH = cp->srcH, chrSrcH = cp->chrSrcH;
-    const int32_t *vLumP = mi355_global(cp->vLumP), *vChrP = mi355_global(cp->vChrP);
-    const int16_t *vLumC = mi355_global(cp->vLumC), *vChrC = mi355_global(cp->vChrC);
-    mi355_sws_frame fr = frames[blockIdx.z];
-    for (int k = 0; k < 3; k++) fr.src[k] = mi355_global(fr.src[k]);
-    fr.dst = mi355_global(fr.dst);
-    const int x = blockIdx.x * C24_COLS + (tid & 63) * 8;   /* first of the thread's eight samples */
-    const int npairs = dstW >> 1;
-    const bool mine = (x >> 1) < npairs;
-    const bool wide = mine && (x >> 1) + 4 <= npairs &&
-                      ((reinterpret_cast<uintptr_t>(fr.src[0]) | (uintptr_t)fr.src_stride[0] | reinterpret_cast<uintptr_t>(fr.dst) | (uintptr_t)fr.dst_stride) & 7) == 0 &&
-                      ((reinterpret_cast<uintptr_t>(fr.src[1]) | (uintptr_t)fr.src_stride[1] | reinterpret_cast<uintptr_t>(fr.src[2]) | (uintptr_t)fr.src_stride[2]) & 3) == 0;
-    constexpr int NR = IDENT_ROWS / (NT / 64);
-    /* the rows' lines and taps: every load unconditional (rows past the picture repeat its last row and are not written; a tap past the filter reads tap 0 and becomes zero) */
-    int li[NR], lf[NR], c0[NR], cf[NR][NC];
-#pragma unroll
-    for (int q = 0; q < NR; q++) {
-        const int gy = imin(blockIdx.y * IDENT_ROWS + (tid >> 6) + q * (NT / 64), dstH - 1);
-        li[q] = vLumP[gy]; lf[q] = vLumC[gy]; c0[q] = vChrP[gy];
-#pragma unroll
-        for (int j = 0; j < NC; j++) cf[q][j] = vChrC[(size_t)gy * cs + (j < cs ? j : 0)];
-    }
-    sws_u32x2 ya[NR];
-    uint32_t u[NR][NC], v[NR][NC];
-    int ci[NR][NC];
-#pragma unroll
-    for (int q = 0; q < NR; q++) {
-        li[q] = clampi(imax(0, li[q]), 0, srcH - 1);
-        const int cfirst = imax(1 - cs, c0[q]);
-        ya[q] = sws_u32x2{ 0u, 0u };
-        if (wide) ya[q] = *reinterpret_cast<const sws_u32x2 *>(fr.src[0] + (size_t)li[q] * fr.src_stride[0] + x);
-#pragma unroll
-        for (int j = 0; j < NC; j++) {
-            cf[q][j] = j < cs ? cf[q][j] : 0;
-            ci[q][j] = clampi(cfirst + (j < cs ? j : 0), 0, chrSrcH - 1);
-            u[q][j] = v[q][j] = 0;
-            if (wide) {
-                u[q][j] = *reinterpret_cast<const uint32_t *>(fr.src[1] + (size_t)ci[q][j] * fr.src_stride[1] + (x >> 1));
-                v[q][j] = *reinterpret_cast<const uint32_t *>(fr.src[2] + (size_t)ci[q][j] * fr.src_stride[2] + (x >> 1));
-            }
-        }
-    }
-    MI355_ISSUE_FENCE();
-    lut_load(s_lut, &cp->luts, tid, NT);
-    __syncthreads();
-    if (!mine) return;
-#pragma unroll
-    for (int q = 0; q < NR; q++) {
-        const int gy = blockIdx.y * IDENT_ROWS + (tid >> 6) + q * (NT / 64);
-        if (gy >= dstH) break;
-        uint8_t *d = fr.dst + (size_t)gy * fr.dst_stride + (size_t)x * 3;
-        const bool mean = !X && cs > 1 && cf[q][1] >= 2048;
-        /* one pair of the row from its bytes: two luma samples, the pair's chroma sample of each tap line */
-        auto pair = [&](int y1, int y2, const int *us, const int *vs, int &Y1, int &Y2, int &U, int &V) {
-            if (!X) {
-                Y1 = y1; Y2 = y2;
-                U = mean ? (us[0] + us[1]) >> 1 : us[0];
-                V = mean ? (vs[0] + vs[1]) >> 1 : vs[0];
-                return;
-            }
-            Y1 = ((1 << 18) + (y1 << 7) * lf[q]) >> 19; Y2 = ((1 << 18) + (y2 << 7) * lf[q]) >> 19;
-            U = V = 1 << 18;
-#pragma unroll
-            for (int j = 0; j < NC; j++) { U += (us[j] << 7) * cf[q][j]; V += (vs[j] << 7) * cf[q][j]; }
-            U >>= 19; V >>= 19;
-            if ((Y1 | Y2 | U | V) & 0x100) { Y1 = clip_u8(Y1); Y2 = clip_u8(Y2); U = clip_u8(U); V = clip_u8(V); }
-        };
-        if (wide) {
-            int Y[8], r[4], g[4], b[4];
-#pragma unroll
-            for (int p = 0; p < 4; p++) {
-                int us[NC], vs[NC], U, V;
-#pragma unroll
-                for (int j = 0; j < NC; j++) { us[j] = (u[q][j] >> (8 * p)) & 0xFF; vs[j] = (v[q][j] >> (8 * p)) & 0xFF; }
-                const uint32_t w = ya[q][p >> 1] >> (16 * (p & 1));
-                pair((int)(w & 0xFF), (int)((w >> 8) & 0xFF), us, vs, Y[2 * p], Y[2 * p + 1], U, V);
-                r[p] = s_lut.rV[V]; g[p] = s_lut.gU[U] + s_lut.gV[V]; b[p] = s_lut.bU[U];
-            }
-            rgb24_store8(s_lut, d, Y, r, g, b);
-        } else {
-            const uint8_t *py = fr.src[0] + (size_t)li[q] * fr.src_stride[0] + x;
-            for (int p = 0; p < 4 && (x >> 1) + p < npairs; p++) {
-                int us[NC], vs[NC], Y1, Y2, U, V;
-#pragma unroll
-                for (int j = 0; j < NC; j++) {
-                    us[j] = fr.src[1][(size_t)ci[q][j] * fr.src_stride[1] + (x >> 1) + p];
-                    vs[j] = fr.src[2][(size_t)ci[q][j] * fr.src_stride[2] + (x >> 1) + p];
-                }
-                pair(py[2 * p], py[2 * p + 1], us, vs, Y1, Y2, U, V);
-                write_pair(s_lut, d + 6 * p, Y1, Y2, U, V);
-            }
-        }
-    }
-}
-
-/* ---- Tier-1 line kernels ---------------------------------------------------------------------------- */
-template <typename ST = uint8_t>
-__global__ void __launch_bounds__(NT) k_sws_line_hscale(int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *pos, int fs, int sh)
-{
-    for (int i = threadIdx.x; i < dstW; i += NT) dst[i] = (int16_t)hscale_one<ST>(src, filter + (size_t)i * fs, pos[i], fs, sh);
-}
-/* yuv2planeX_8_c output.c:242-255 (fs >= 1 rows at `pitch` elements) / yuv2plane1_8_c :257-266 (fs == 0) */
-__global__ void __launch_bounds__(NT) k_sws_line_plane(const int16_t *filter, int fs, const int16_t *rows, int pitch, uint8_t *dest, int dstW,
-                                                       const uint8_t *dither, int offset)
-{
-    for (int i = threadIdx.x; i < dstW; i += NT) {
-        if (fs == 0) { dest[i] = (uint8_t)clip_u8((rows[i] + dither[(i + offset) & 7]) >> 7); continue; }
-        int val = dither[(i + offset) & 7] << 12;
-        for (int j = 0; j < fs; j++) val += rows[(size_t)j * pitch + i] * filter[j];
-        dest[i] = (uint8_t)clip_u8(val >> 19);
-    }
-}
-struct PackedRows {
-    const int16_t *l, *u, *v;
-    int pitch;
-    __device__ __forceinline__ int lum(int j, int x) const { return l[(size_t)j * pitch + x]; }
-    __device__ __forceinline__ int cu(int j, int x) const { return u[(size_t)j * pitch + x]; }
-    __device__ __forceinline__ int cv(int j, int x) const { return v[(size_t)j * pitch + x]; }
-};
-__global__ void __launch_bounds__(NT) k_sws_line_rgb(const mi355_sws_luts *luts, int mode, const int16_t *lumF, const int16_t *l, int ls,
-                                                     const int16_t *chrF, const int16_t *u, const int16_t *v, int cs, int pitch, uint8_t *dest,
-                                                     int dstW, int yalpha, int uvalpha)
-{
-    __shared__ LutLds s_lut;
-    lut_load(s_lut, luts, threadIdx.x, NT);
-    __syncthreads();
-    PackedRows R{ l, u, v, pitch };
-    for (int i = threadIdx.x; i < ((dstW + 1) >> 1); i += NT) rgb_pair(s_lut, dest + (size_t)i * 6, R, i, mode, lumF, ls, chrF, cs, yalpha, uvalpha);
-}
-
-}  // namespace
 
 /* ---- context ------------------------------------------------------------------------------------------- */
 struct mi355_sws_ctx {
@@ -1257,16 +120,15 @@ static void ctx_hfit(mi355_sws_ctx *c, const mi355_sws_desc *desc)
 {
     const SwsDev &h = c->h;
     const int B = h.depth > 8 ? 2 : 1, cw = h.planar ? TW >> h.hshift : TW / 2;
-    auto fits = [&](const mi355_sws_filter &f, int ident, int cols, int pitch) {
+    auto fits = [&](const mi355_sws_filter &f, int ident, int cols) {
         if (ident || !f.pos) return false;
         for (int g = 0; g < f.n; g += cols) {
             const int last = (g + cols < f.n ? g + cols : f.n) - 1, s0 = B * f.pos[g], s1 = B * (f.pos[last] + f.size);
-            if (s1 >= s0 && ((s1 - (s0 & ~15) + 3) >> 2) <= pitch - 2) return true;
+            if (span_fits(span_dwords(s0 & ~15, s1), s0, s1, stage_pitch(cols, B))) return true;
         }
         return false;
     };
-    const int pl = B == 1 ? SRC_DW : SRC_DW16, pc = cw == TW ? pl : (B == 1 ? 40 : 76);
-    c->hfit = fits(desc->hLum, h.hident_l, TW, pl) || fits(desc->hChr, h.hident_c, cw, pc);
+    c->hfit = fits(desc->hLum, h.hident_l, TW) || fits(desc->hChr, h.hident_c, cw);
 }
 static void upload_banks(mi355_sws_ctx *c, const mi355_sws_desc *desc)
 {
@@ -1286,38 +148,11 @@ static mi355_sws_ctx *ctx_upload(mi355_sws_ctx *c)
     return c;
 }
 
-static mi355_sws_ctx *create_rgb24(const mi355_sws_desc *desc, const mi355_sws_src *src, const char *who)
+/* what the create entry points share: the source check, the destination family (rgb24, or planar: dst_format MI355_SWS_DST_*), the bank
+ * validation with its diagnostics.  The unscaled special converter (rgb24 only) has no banks. */
+static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src *src, bool planar, int dst_format, const char *who)
 {
-    mi355_sws_ctx *c = ctx_new(desc);
-    SwsDev &h = c->h;
-    int lines[2] = { 1, 1 };
-    if (src && !ctx_source(c, src)) {
-        std::fprintf(stderr, "mi355dsp: %s: source %d bit, chroma shifts %d/%d (chroma %dx%d of %dx%d) is outside this backend\n", who, src->depth, src->hsub, src->vsub,
-                     h.chrSrcW, h.chrSrcH, h.srcW, h.srcH);
-        delete c;
-        return nullptr;
-    }
-    if (!h.special) {
-        if (desc->hLum.n != h.dstW || desc->hChr.n != h.chrDstW || desc->vLum.n != h.dstH || desc->vChr.n != h.dstH ||
-            h.hls < 1 || h.hcs < 1 || h.vls < 1 || h.vcs < 1 || !(h.th = choose_rows(desc, lines))) {
-            std::fprintf(stderr, "mi355dsp: %s: filter banks do not fit this backend (sizes %d/%d/%d/%d)\n", who, h.hls, h.hcs, h.vls, h.vcs);
-            delete c;
-            return nullptr;
-        }
-        h.lum_lines = lines[0]; h.chr_lines = lines[1];
-        upload_banks(c, desc);
-    }
-    return ctx_upload(c);
-}
-extern "C" mi355_sws_ctx *mi355_sws_create(const mi355_sws_desc *desc)
-{
-    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create without mi355_init(); no CPU fallback\n"); std::abort(); }
-    return create_rgb24(desc, nullptr, "mi355_sws_create");
-}
-
-static mi355_sws_ctx *create_planar(const mi355_sws_desc *desc, const mi355_sws_src *src, int dst_format, const char *who)
-{
-    if (!desc || dst_format < MI355_SWS_DST_YUV420P || dst_format > MI355_SWS_DST_YUV444P) {
+    if (planar && (!desc || dst_format < MI355_SWS_DST_YUV420P || dst_format > MI355_SWS_DST_YUV444P)) {
         std::fprintf(stderr, "mi355dsp: %s: destination format %d is not yuv420p / yuv422p / yuv444p\n", who, dst_format);
         return nullptr;
     }
@@ -1329,16 +164,18 @@ static mi355_sws_ctx *create_planar(const mi355_sws_desc *desc, const mi355_sws_
         delete c;
         return nullptr;
     }
-    h.planar = dst_format;
-    h.hshift = dst_format == MI355_SWS_DST_YUV444P ? 0 : 1;
-    h.vshift = dst_format == MI355_SWS_DST_YUV420P ? 1 : 0;
-    h.chrDstH = (h.dstH + (1 << h.vshift) - 1) >> h.vshift;               /* AV_CEIL_RSHIFT, utils.c:1040 */
+    bool ok = true;                                   /* what only a planar destination asks for */
+    if (planar) {
+        h.planar = dst_format;
+        h.hshift = dst_format == MI355_SWS_DST_YUV444P ? 0 : 1;
+        h.vshift = dst_format == MI355_SWS_DST_YUV420P ? 1 : 0;
+        h.chrDstH = (h.dstH + (1 << h.vshift) - 1) >> h.vshift;               /* AV_CEIL_RSHIFT, utils.c:1040 */
+        ok = !h.special && desc->hLum.coef && desc->hLum.pos && desc->hChr.coef && desc->hChr.pos && desc->vLum.coef && desc->vLum.pos &&
+             desc->vChr.coef && desc->vChr.pos && h.chrDstW == (h.dstW + (1 << h.hshift) - 1) >> h.hshift;
+    } else if (h.special) return ctx_upload(c);
     int lines[2] = { 1, 1 };
-    const bool banks = desc->hLum.coef && desc->hLum.pos && desc->hChr.coef && desc->hChr.pos && desc->vLum.coef && desc->vLum.pos &&
-                       desc->vChr.coef && desc->vChr.pos;
-    if (h.special || !banks || h.chrDstW != (h.dstW + (1 << h.hshift) - 1) >> h.hshift || desc->hLum.n != h.dstW || desc->hChr.n != h.chrDstW ||
-        desc->vLum.n != h.dstH || desc->vChr.n != h.chrDstH || h.hls < 1 || h.hcs < 1 || h.vls < 1 || h.vcs < 1 ||
-        !(h.th = choose_rows(desc, lines, h.vshift, MAXCP))) {
+    if (!ok || desc->hLum.n != h.dstW || desc->hChr.n != h.chrDstW || desc->vLum.n != h.dstH || desc->vChr.n != h.chrDstH ||
+        h.hls < 1 || h.hcs < 1 || h.vls < 1 || h.vcs < 1 || !(h.th = choose_rows(desc, lines, h.vshift, planar ? MAXCP : MAXC))) {
         std::fprintf(stderr, "mi355dsp: %s: filter banks do not fit this backend (sizes %d/%d/%d/%d)\n", who, h.hls, h.hcs, h.vls, h.vcs);
         delete c;
         return nullptr;
@@ -1347,16 +184,21 @@ static mi355_sws_ctx *create_planar(const mi355_sws_desc *desc, const mi355_sws_
     upload_banks(c, desc);
     return ctx_upload(c);
 }
+extern "C" mi355_sws_ctx *mi355_sws_create(const mi355_sws_desc *desc)
+{
+    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create without mi355_init(); no CPU fallback\n"); std::abort(); }
+    return ctx_create(desc, nullptr, false, 0, "mi355_sws_create");
+}
 extern "C" mi355_sws_ctx *mi355_sws_create_planar(const mi355_sws_desc *desc, int dst_format)
 {
     if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_planar without mi355_init(); no CPU fallback\n"); std::abort(); }
-    return create_planar(desc, nullptr, dst_format, "mi355_sws_create_planar");
+    return ctx_create(desc, nullptr, true, dst_format, "mi355_sws_create_planar");
 }
 extern "C" mi355_sws_ctx *mi355_sws_create_src(const mi355_sws_desc *desc, const mi355_sws_src *src, int dst_format)
 {
     if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src without mi355_init(); no CPU fallback\n"); std::abort(); }
     if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src: no descriptor\n"); return nullptr; }
-    return dst_format == 0 ? create_rgb24(desc, src, "mi355_sws_create_src") : create_planar(desc, src, dst_format, "mi355_sws_create_src");
+    return ctx_create(desc, src, dst_format != 0, dst_format, "mi355_sws_create_src");
 }
 
 extern "C" void mi355_sws_destroy(mi355_sws_ctx *c)
@@ -1376,17 +218,19 @@ extern "C" void mi355_sws_destroy(mi355_sws_ctx *c)
 /* the kernel mi355_sws_scale_frames_dev launches for a context (MI355_SWS_K_*): the launch and mi355_sws_plan both ask here */
 static int sws_kernel(const SwsDev &h)
 {
-    /* planar: the B instance's chroma lines cover the 2 x 7 + 8 of a 2:1 4:2:0 reduction at 16-row tiles (seven workgroups a CU) */
-    if (h.planar) return h.lum_lines <= 28 && h.chr_lines <= 16 ? MI355_SWS_K_PLANAR_A : (h.lum_lines <= 40 && h.chr_lines <= 24 ? MI355_SWS_K_PLANAR_B : MI355_SWS_K_PLANAR_C);
+    /* the smallest instance of the table whose LDS tile holds the context's lines (the C instances hold whatever choose_rows accepted) */
+    auto instance = [&](const SwsShape (&shapes)[3]) {
+        for (int i = 0; i < 2; i++) if (h.lum_lines <= shapes[i].lcap && h.chr_lines <= shapes[i].ccap) return i;
+        return 2;
+    };
+    static_assert(MI355_SWS_K_GENERIC_C == MI355_SWS_K_GENERIC_A + 2 && MI355_SWS_K_PLANAR_C == MI355_SWS_K_PLANAR_A + 2, "A / B / C follow each other");
+    if (h.planar) return MI355_SWS_K_PLANAR_A + instance(PLANAR_SHAPES);
     if (h.special) return MI355_SWS_K_C24;
     /* a context that does not scale: straight from the source bytes (k_sws_ident1; MI355_SWS_NO_IDENT1=1, developer switch: through the tile all the same) */
     static const bool no_ident1 = std::getenv("MI355_SWS_NO_IDENT1") != nullptr;
     if (!no_ident1 && h.depth == 8 && h.hident_l && h.hident_c && h.vls == 1 && h.vcs <= 4 && !(h.dstW & 1) && h.srcW >= h.dstW && 2 * h.chrSrcW >= h.dstW)
         return h.vcs <= 2 ? MI355_SWS_K_IDENT1_1 : MI355_SWS_K_IDENT1_X;      /* packed_mode() 1 / the X template */
-    /* a CU's 160 KB of LDS hold `wgs` workgroups, one wave of each per SIMD: the instance whose register budget matches */
-    if (h.lum_lines <= 28 && h.chr_lines <= 16) return MI355_SWS_K_GENERIC_A;
-    if (h.lum_lines <= 40 && h.chr_lines <= 20) return MI355_SWS_K_GENERIC_B;
-    return MI355_SWS_K_GENERIC_C;
+    return MI355_SWS_K_GENERIC_A + instance(GENERIC_SHAPES);
 }
 
 extern "C" int mi355_sws_plan(const mi355_sws_ctx *c, mi355_sws_plan_info *p)
@@ -1409,16 +253,42 @@ extern "C" int mi355_sws_source(const mi355_sws_ctx *c, mi355_sws_source_info *p
     return 0;
 }
 
-/* waves per SIMD the three instances' register allocation aims at (developer switches; the defaults are what their LDS tiles allow) */
-#ifndef MI355_SWS_WAVES_A
-#define MI355_SWS_WAVES_A 8
-#endif
-#ifndef MI355_SWS_WAVES_B
-#define MI355_SWS_WAVES_B 7
-#endif
-#ifndef MI355_SWS_WAVES_C
-#define MI355_SWS_WAVES_C 6
-#endif
+/* the launch of instance I (0 / 1 / 2: A / B / C) of a tile kernel for samples of type ST; the generic kernel's waves per SIMD are what its
+ * LDS allows, like the planar kernel's own */
+template <int I, typename ST> static void launch_generic(dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
+{
+    constexpr SwsShape S = GENERIC_SHAPES[I];
+    hipLaunchKernelGGL((k_sws_generic<S.lcap, S.ccap, sws_waves(sws_lds_bytes(S.lcap, S.ccap, stage_bytes<ST>())), ST>), grid, dim3(NT), 0, s, d, frames);
+}
+template <int I, typename ST> static void launch_planar(int hshift, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+{
+    constexpr SwsShape S = PLANAR_SHAPES[I];
+    if (hshift) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, ST>), grid, dim3(NT), 0, s, d, frames);
+    else hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW, ST>), grid, dim3(NT), 0, s, d, frames);
+}
+/* the same for run-time instance i (0 / 1 / 2) */
+template <typename ST> static void launch_generic(int i, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
+{
+    if (i == 0) launch_generic<0, ST>(grid, s, d, frames);
+    else if (i == 1) launch_generic<1, ST>(grid, s, d, frames);
+    else launch_generic<2, ST>(grid, s, d, frames);
+}
+template <typename ST> static void launch_planar(int i, int hshift, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+{
+    if (i == 0) launch_planar<0, ST>(hshift, grid, s, d, frames);
+    else if (i == 1) launch_planar<1, ST>(hshift, grid, s, d, frames);
+    else launch_planar<2, ST>(hshift, grid, s, d, frames);
+}
+/* workgroups per CU of the instances (8-bit, then 16-bit: their staging lines are STAGE_BYTES16) */
+constexpr int generic_waves(int i, int stage) { return sws_waves(sws_lds_bytes(GENERIC_SHAPES[i].lcap, GENERIC_SHAPES[i].ccap, stage)); }
+constexpr int planar_waves(int i, int cw, int stage) { return sws_planar_waves(PLANAR_SHAPES[i].lcap, PLANAR_SHAPES[i].ccap, cw, stage); }
+static_assert(generic_waves(0, STAGE_BYTES) == 8 && generic_waves(1, STAGE_BYTES) == 7 && generic_waves(2, STAGE_BYTES) == 6, "workgroups per CU of the instances");
+static_assert(generic_waves(0, STAGE_BYTES16) == 7 && generic_waves(1, STAGE_BYTES16) == 5 && generic_waves(2, STAGE_BYTES16) == 5, "workgroups per CU of the 16-bit instances");
+static_assert(planar_waves(0, TW / 2, STAGE_BYTES) == 8 && planar_waves(1, TW / 2, STAGE_BYTES) == 7 && planar_waves(2, TW / 2, STAGE_BYTES) == 5 &&
+              planar_waves(2, TW, STAGE_BYTES) == 3, "workgroups per CU of the planar instances");
+static_assert(planar_waves(0, TW / 2, STAGE_BYTES16) == 8 && planar_waves(1, TW / 2, STAGE_BYTES16) == 6 && planar_waves(2, TW / 2, STAGE_BYTES16) == 4 &&
+              planar_waves(2, TW, STAGE_BYTES16) == 3, "workgroups per CU of the 16-bit planar instances");
+
 extern "C" int mi355_sws_scale_frames_dev(mi355_sws_ctx *c, const mi355_sws_frame *d_frames, int nframes, void *stream)
 {
     if (!c || !d_frames || nframes <= 0 || c->h.planar) return -1;
@@ -1436,18 +306,8 @@ extern "C" int mi355_sws_scale_frames_dev(mi355_sws_ctx *c, const mi355_sws_fram
         else hipLaunchKernelGGL(k_sws_ident1<true>, grid, dim3(NT), 0, s, c->d, d_frames);
     } else {
         const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
-        static_assert(160 * 1024 / sws_lds_bytes(28, 16) >= 8 && 160 * 1024 / sws_lds_bytes(40, 20) == 7 && 160 * 1024 / sws_lds_bytes(MAXL, MAXC) == 6, "workgroups per CU of the instances");
-        /* the 16-bit instances' staging lines are STAGE_BYTES16: seven, five and five workgroups a CU */
-        static_assert(160 * 1024 / sws_lds_bytes(28, 16, STAGE_BYTES16) == 7 && 160 * 1024 / sws_lds_bytes(40, 20, STAGE_BYTES16) == 5 &&
-                      160 * 1024 / sws_lds_bytes(MAXL, MAXC, STAGE_BYTES16) == 5, "workgroups per CU of the 16-bit instances");
-        if (h.depth > 8) {
-            if (k == MI355_SWS_K_GENERIC_A) hipLaunchKernelGGL((k_sws_generic<28, 16, 7, uint16_t>), grid, dim3(NT), 0, s, c->d, d_frames);
-            else if (k == MI355_SWS_K_GENERIC_B) hipLaunchKernelGGL((k_sws_generic<40, 20, 5, uint16_t>), grid, dim3(NT), 0, s, c->d, d_frames);
-            else hipLaunchKernelGGL((k_sws_generic<MAXL, MAXC, 5, uint16_t>), grid, dim3(NT), 0, s, c->d, d_frames);
-        }
-        else if (k == MI355_SWS_K_GENERIC_A) hipLaunchKernelGGL((k_sws_generic<28, 16, MI355_SWS_WAVES_A>), grid, dim3(NT), 0, s, c->d, d_frames);
-        else if (k == MI355_SWS_K_GENERIC_B) hipLaunchKernelGGL((k_sws_generic<40, 20, MI355_SWS_WAVES_B>), grid, dim3(NT), 0, s, c->d, d_frames);
-        else hipLaunchKernelGGL((k_sws_generic<MAXL, MAXC, MI355_SWS_WAVES_C>), grid, dim3(NT), 0, s, c->d, d_frames);
+        if (h.depth > 8) launch_generic<uint16_t>(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
+        else launch_generic<uint8_t>(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
     }
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -1458,25 +318,10 @@ extern "C" int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *c, const mi355_s
     hipStream_t s = static_cast<hipStream_t>(stream);
     const SwsDev &h = c->h;
     DeviceScope on(c->device);
-    const int k = sws_kernel(h);
     const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
-    static_assert(sws_planar_waves(28, 16, TW / 2) == 8 && sws_planar_waves(40, 24, TW / 2) == 7 && sws_planar_waves(MAXL, MAXCP, TW / 2) == 5 &&
-                  sws_planar_waves(MAXL, MAXCP, TW) == 3,
-                  "workgroups per CU of the planar instances");
-    static_assert(sws_planar_waves(28, 16, TW / 2, STAGE_BYTES16) == 8 && sws_planar_waves(40, 24, TW / 2, STAGE_BYTES16) == 6 &&
-                  sws_planar_waves(MAXL, MAXCP, TW / 2, STAGE_BYTES16) == 4 && sws_planar_waves(MAXL, MAXCP, TW, STAGE_BYTES16) == 3,
-                  "workgroups per CU of the 16-bit planar instances");
-#define MI355_PLANAR(L, C) \
-    if (h.depth > 8) { \
-        if (h.hshift) hipLaunchKernelGGL((k_sws_planar<L, C, TW / 2, uint16_t>), grid, dim3(NT), 0, s, c->d, d_frames); \
-        else hipLaunchKernelGGL((k_sws_planar<L, C, TW, uint16_t>), grid, dim3(NT), 0, s, c->d, d_frames); \
-    } \
-    else if (h.hshift) hipLaunchKernelGGL((k_sws_planar<L, C, TW / 2>), grid, dim3(NT), 0, s, c->d, d_frames); \
-    else hipLaunchKernelGGL((k_sws_planar<L, C, TW>), grid, dim3(NT), 0, s, c->d, d_frames);
-    if (k == MI355_SWS_K_PLANAR_A) { MI355_PLANAR(28, 16) }
-    else if (k == MI355_SWS_K_PLANAR_B) { MI355_PLANAR(40, 24) }
-    else { MI355_PLANAR(MAXL, MAXCP) }
-#undef MI355_PLANAR
+    const int i = sws_kernel(h) - MI355_SWS_K_PLANAR_A;
+    if (h.depth > 8) launch_planar<uint16_t>(i, h.hshift, grid, s, c->d, d_frames);
+    else launch_planar<uint8_t>(i, h.hshift, grid, s, c->d, d_frames);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -1486,33 +331,42 @@ static bool plane_h2d(uint8_t *d, int dpitch, const uint8_t *h, int hstride, int
     return hipMemcpy2DAsync(d, dpitch, h, hstride, wbytes, rows, hipMemcpyHostToDevice, s) == hipSuccess;
 }
 
-extern "C" int mi355_sws_scale(mi355_sws_ctx *c, const uint8_t *const src[3], const int src_stride[3], uint8_t *dst, int dst_stride)
+/* What mi355_sws_scale and mi355_sws_scale_planar share: a picture through the context's own device planes.  A packed picture is a planar one with
+ * ONE destination plane (ndst 1).  ow / oh: bytes per row and rows of each destination plane as the device writes them, back: the bytes of a row
+ * that go back to the caller (the caller's padding stays untouched), slack: rows (packed) or bytes (planar) behind the destination.
+ * Every failure comes back as a negative value and leaves the context usable: the caller (contrib/libav/mi355_sws_glue.c) falls
+ * back to the reference's function for that picture.  Strides must be positive and cover a line: sws_scale() itself also
+ * takes negative ones (bottom-up pictures, vf_vflip) — not these entry points (-1), a 2-D copy has no negative pitch. */
+static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int src_stride[3], int ndst, uint8_t *const dst[], const int dst_stride[],
+                        const int ow[], const int oh[], const int back[])
 {
-    /* Every failure comes back as a negative value and leaves the context usable: the caller (contrib/libav/mi355_sws_glue.c) falls
-     * back to the reference's function for that picture.  Strides must be positive and cover a line: sws_scale() itself also
-     * takes negative ones (bottom-up pictures, vf_vflip) — not this entry point (-1), a 2-D copy has no negative pitch. */
-    if (!c || !src || !src_stride || !dst || c->h.planar) return -1;
     const SwsDev &h = c->h;
-    const int cw = h.chrSrcW, ch = h.chrSrcH;
+    const bool planar = h.planar != 0;
     const int B = h.depth > 8 ? 2 : 1;                                  /* bytes per source sample */
-    const int w[3] = { h.srcW * B, cw * B, cw * B };
-    const int out_w = h.special ? (h.dstW & ~1) * 3 : h.dstW * 3;      /* only the samples the converter writes go back: the caller's padding stays untouched */
+    const int w[3] = { h.srcW * B, h.chrSrcW * B, h.chrSrcW * B }, ph[3] = { h.srcH, h.chrSrcH, h.chrSrcH };
     for (int p = 0; p < 3; p++) if (!src[p] || src_stride[p] < w[p]) return -1;
-    if (dst_stride < out_w) return -1;
+    for (int p = 0; p < ndst; p++) if (!dst[p] || dst_stride[p] < back[p]) return -1;
     DeviceScope on(c->device);
-    const int pw[3] = { (w[0] + 15) & ~15, (w[1] + 15) & ~15, (w[2] + 15) & ~15 }, ph[3] = { h.srcH, ch, ch };
-    const int dpitch = (h.dstW * 3 + 15) & ~15;
+    const int pw[3] = { (w[0] + 15) & ~15, (w[1] + 15) & ~15, (w[2] + 15) & ~15 };
+    int dp[3] = {};
+    size_t doff[4] = {};
+    for (int p = 0; p < ndst; p++) { dp[p] = (ow[p] + 15) & ~15; doff[p + 1] = doff[p] + (size_t)dp[p] * oh[p]; }
     if (!c->d_dst) {
         uint8_t *ns[3] = { nullptr, nullptr, nullptr }, *nd = nullptr;
-        mi355_sws_frame *nf = nullptr;
+        void *nf = nullptr;
         bool ok = true;
         for (int p = 0; p < 3 && ok; p++) ok = hipMalloc(reinterpret_cast<void **>(&ns[p]), (size_t)pw[p] * ph[p] + 64) == hipSuccess;
-        ok = ok && hipMalloc(reinterpret_cast<void **>(&nd), (size_t)dpitch * (h.dstH + 1)) == hipSuccess;
-        ok = ok && hipMalloc(reinterpret_cast<void **>(&nf), sizeof(mi355_sws_frame)) == hipSuccess;
-        if (ok) {
+        /* a packed destination has one row of slack, the planar planes 64 bytes */
+        ok = ok && hipMalloc(reinterpret_cast<void **>(&nd), planar ? doff[ndst] + 64 : (size_t)dp[0] * (oh[0] + 1)) == hipSuccess;
+        ok = ok && hipMalloc(&nf, planar ? sizeof(mi355_sws_planar_frame) : sizeof(mi355_sws_frame)) == hipSuccess;
+        if (ok && planar) {
+            mi355_sws_planar_frame f;
+            for (int p = 0; p < 3; p++) { f.src[p] = ns[p]; f.src_stride[p] = pw[p]; f.dst[p] = nd + doff[p]; f.dst_stride[p] = dp[p]; }
+            ok = hipMemcpy(nf, &f, sizeof(f), hipMemcpyHostToDevice) == hipSuccess;
+        } else if (ok) {
             mi355_sws_frame f;
             for (int p = 0; p < 3; p++) { f.src[p] = ns[p]; f.src_stride[p] = pw[p]; }
-            f.dst = nd; f.dst_stride = dpitch;
+            f.dst = nd; f.dst_stride = dp[0];
             ok = hipMemcpy(nf, &f, sizeof(f), hipMemcpyHostToDevice) == hipSuccess;
         }
         if (!ok) {
@@ -1523,97 +377,76 @@ extern "C" int mi355_sws_scale(mi355_sws_ctx *c, const uint8_t *const src[3], co
             return -4;
         }
         for (int p = 0; p < 3; p++) c->d_src[p] = ns[p];
-        c->d_dst = nd; c->d_frame = nf;
+        c->d_dst = nd;
+        if (planar) c->d_pframe = static_cast<mi355_sws_planar_frame *>(nf);
+        else c->d_frame = static_cast<mi355_sws_frame *>(nf);
     }
     for (int p = 0; p < 3; p++)
         if (!plane_h2d(c->d_src[p], pw[p], src[p], src_stride[p], w[p], ph[p], c->stream)) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4; }
-    if (mi355_sws_scale_frames_dev(c, c->d_frame, 1, c->stream) != 0) { (void)hipStreamSynchronize(c->stream); return -2; }
-    if (hipMemcpy2DAsync(dst, dst_stride, c->d_dst, dpitch, out_w, h.dstH, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4; }
+    if ((planar ? mi355_sws_scale_planar_frames_dev(c, c->d_pframe, 1, c->stream) : mi355_sws_scale_frames_dev(c, c->d_frame, 1, c->stream)) != 0) {
+        (void)hipStreamSynchronize(c->stream);
+        return -2;
+    }
+    for (int p = 0; p < ndst; p++)
+        if (hipMemcpy2DAsync(dst[p], dst_stride[p], c->d_dst + doff[p], dp[p], back[p], oh[p], hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+            (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4;
+        }
     if (hipStreamSynchronize(c->stream) != hipSuccess) return -4;
-    return h.special ? h.srcH : h.dstH;
+    return 0;
+}
+
+extern "C" int mi355_sws_scale(mi355_sws_ctx *c, const uint8_t *const src[3], const int src_stride[3], uint8_t *dst, int dst_stride)
+{
+    if (!c || !src || !src_stride || !dst || c->h.planar) return -1;
+    const SwsDev &h = c->h;
+    /* only the samples the converter writes go back */
+    const int ow = h.dstW * 3, back = h.special ? (h.dstW & ~1) * 3 : h.dstW * 3;
+    const int r = scale_staged(c, src, src_stride, 1, &dst, &dst_stride, &ow, &h.dstH, &back);
+    return r ? r : (h.special ? h.srcH : h.dstH);
 }
 
 extern "C" int mi355_sws_scale_planar(mi355_sws_ctx *c, const uint8_t *const src[3], const int src_stride[3], uint8_t *const dst[3], const int dst_stride[3])
 {
-    /* as mi355_sws_scale: every failure is a negative value and leaves the context usable; positive strides that cover a line only */
     if (!c || !src || !src_stride || !dst || !dst_stride || !c->h.planar) return -1;
     const SwsDev &h = c->h;
-    const int cw = h.chrSrcW, ch = h.chrSrcH;
-    const int B = h.depth > 8 ? 2 : 1;                                  /* bytes per source sample */
-    const int w[3] = { h.srcW * B, cw * B, cw * B }, ow[3] = { h.dstW, h.chrDstW, h.chrDstW }, oh[3] = { h.dstH, h.chrDstH, h.chrDstH };
-    for (int p = 0; p < 3; p++) if (!src[p] || src_stride[p] < w[p] || !dst[p] || dst_stride[p] < ow[p]) return -1;
-    DeviceScope on(c->device);
-    const int pw[3] = { (w[0] + 15) & ~15, (w[1] + 15) & ~15, (w[2] + 15) & ~15 }, ph[3] = { h.srcH, ch, ch };
-    const int dp[3] = { (ow[0] + 15) & ~15, (ow[1] + 15) & ~15, (ow[2] + 15) & ~15 };
-    const size_t doff[3] = { 0, (size_t)dp[0] * oh[0], (size_t)dp[0] * oh[0] + (size_t)dp[1] * oh[1] };
-    if (!c->d_dst) {
-        uint8_t *ns[3] = { nullptr, nullptr, nullptr }, *nd = nullptr;
-        mi355_sws_planar_frame *nf = nullptr;
-        bool ok = true;
-        for (int p = 0; p < 3 && ok; p++) ok = hipMalloc(reinterpret_cast<void **>(&ns[p]), (size_t)pw[p] * ph[p] + 64) == hipSuccess;
-        ok = ok && hipMalloc(reinterpret_cast<void **>(&nd), doff[2] + (size_t)dp[2] * oh[2] + 64) == hipSuccess;
-        ok = ok && hipMalloc(reinterpret_cast<void **>(&nf), sizeof(mi355_sws_planar_frame)) == hipSuccess;
-        if (ok) {
-            mi355_sws_planar_frame f;
-            for (int p = 0; p < 3; p++) { f.src[p] = ns[p]; f.src_stride[p] = pw[p]; f.dst[p] = nd + doff[p]; f.dst_stride[p] = dp[p]; }
-            ok = hipMemcpy(nf, &f, sizeof(f), hipMemcpyHostToDevice) == hipSuccess;
-        }
-        if (!ok) {
-            for (int p = 0; p < 3; p++) if (ns[p]) (void)hipFree(ns[p]);
-            if (nd) (void)hipFree(nd);
-            if (nf) (void)hipFree(nf);
-            (void)hipGetLastError();
-            return -4;
-        }
-        for (int p = 0; p < 3; p++) c->d_src[p] = ns[p];
-        c->d_dst = nd; c->d_pframe = nf;
-    }
-    for (int p = 0; p < 3; p++)
-        if (!plane_h2d(c->d_src[p], pw[p], src[p], src_stride[p], w[p], ph[p], c->stream)) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4; }
-    if (mi355_sws_scale_planar_frames_dev(c, c->d_pframe, 1, c->stream) != 0) { (void)hipStreamSynchronize(c->stream); return -2; }
-    for (int p = 0; p < 3; p++)
-        if (hipMemcpy2DAsync(dst[p], dst_stride[p], c->d_dst + doff[p], dp[p], ow[p], oh[p], hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
-            (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4;
-        }
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return -4;
-    return h.dstH;
+    const int ow[3] = { h.dstW, h.chrDstW, h.chrDstW }, oh[3] = { h.dstH, h.chrDstH, h.chrDstH };
+    const int r = scale_staged(c, src, src_stride, 3, dst, dst_stride, ow, oh, ow);
+    return r ? r : h.dstH;
 }
 
 /* ---- Tier-1 line entry points ------------------------------------------------------------------------------ */
-#define LAUNCH_LINE(kernel, a, ...) hipLaunchKernelGGL(kernel, dim3(1), dim3(NT), 0, (a).stream, __VA_ARGS__)
+/* a line kernel: one workgroup on the staging arena's stream */
+template <typename K, typename... A> static void launch_line(K kernel, Arena &a, A... args)
+{
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(NT), 0, a.stream, args...);
+}
 
-extern "C" void mi355_sws_hscale8to15(int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
+/* hScale8To15_c / hScale16To15_c (swscale.c:133-147 / :110-130) of one line: samples of type ST, the sum shifted down by sh */
+template <typename ST>
+static void hscale_line(int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize, int sh)
 {
     Arena &a = arena();
     int last = 0;
     for (int i = 0; i < dstW; i++) if (filterPos[i] > last) last = filterPos[i];
-    const size_t nsrc = (size_t)last + filterSize;
+    const size_t nsrc = ((size_t)last + filterSize) * sizeof(ST);
     a.reserve(nsrc + (size_t)dstW * filterSize * 2 + (size_t)dstW * 6 + 64);
     const size_t o_src = a.take(nsrc), o_f = a.take((size_t)dstW * filterSize * 2), o_p = a.take((size_t)dstW * 4), o_d = a.take((size_t)dstW * 2);
     std::memcpy(a.h<uint8_t>(o_src), src, nsrc);
     std::memcpy(a.h<int16_t>(o_f), filter, (size_t)dstW * filterSize * 2);
     std::memcpy(a.h<int32_t>(o_p), filterPos, (size_t)dstW * 4);
     a.upload();
-    LAUNCH_LINE(k_sws_line_hscale<uint8_t>, a, a.d<int16_t>(o_d), dstW, a.d<const uint8_t>(o_src), a.d<const int16_t>(o_f), a.d<const int32_t>(o_p), filterSize, 7);
+    launch_line(k_sws_line_hscale<ST>, a, a.d<int16_t>(o_d), dstW, a.d<const uint8_t>(o_src), a.d<const int16_t>(o_f), a.d<const int32_t>(o_p), filterSize, sh);
     a.download();
     std::memcpy(dst, a.h<int16_t>(o_d), (size_t)dstW * 2);
 }
-/* hScale16To15_c swscale.c:110-130: uint16_t samples below 1 << depth */
+extern "C" void mi355_sws_hscale8to15(int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
+{
+    hscale_line<uint8_t>(dst, dstW, src, filter, filterPos, filterSize, 7);
+}
+/* uint16_t samples below 1 << depth */
 extern "C" void mi355_sws_hscale16to15(int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize, int depth)
 {
-    Arena &a = arena();
-    int last = 0;
-    for (int i = 0; i < dstW; i++) if (filterPos[i] > last) last = filterPos[i];
-    const size_t nsrc = ((size_t)last + filterSize) * 2;
-    a.reserve(nsrc + (size_t)dstW * filterSize * 2 + (size_t)dstW * 6 + 64);
-    const size_t o_src = a.take(nsrc), o_f = a.take((size_t)dstW * filterSize * 2), o_p = a.take((size_t)dstW * 4), o_d = a.take((size_t)dstW * 2);
-    std::memcpy(a.h<uint8_t>(o_src), src, nsrc);
-    std::memcpy(a.h<int16_t>(o_f), filter, (size_t)dstW * filterSize * 2);
-    std::memcpy(a.h<int32_t>(o_p), filterPos, (size_t)dstW * 4);
-    a.upload();
-    LAUNCH_LINE(k_sws_line_hscale<uint16_t>, a, a.d<int16_t>(o_d), dstW, a.d<const uint8_t>(o_src), a.d<const int16_t>(o_f), a.d<const int32_t>(o_p), filterSize, depth - 1);
-    a.download();
-    std::memcpy(dst, a.h<int16_t>(o_d), (size_t)dstW * 2);
+    hscale_line<uint16_t>(dst, dstW, src, filter, filterPos, filterSize, depth - 1);
 }
 
 static size_t pack_rows(Arena &a, const int16_t **rows, int n, int elems, int pitch)
@@ -1632,7 +465,7 @@ static void plane_line(const int16_t *filter, int fs, const int16_t **rows, uint
     if (fs) std::memcpy(a.h<int16_t>(o_f), filter, (size_t)fs * 2);
     std::memcpy(a.h<uint8_t>(o_di), dither, 8);
     a.upload();
-    LAUNCH_LINE(k_sws_line_plane, a, a.d<const int16_t>(o_f), fs, a.d<const int16_t>(o_r), pitch, a.d<uint8_t>(o_d), dstW, a.d<const uint8_t>(o_di), offset);
+    launch_line(k_sws_line_plane, a, a.d<const int16_t>(o_f), fs, a.d<const int16_t>(o_r), pitch, a.d<uint8_t>(o_d), dstW, a.d<const uint8_t>(o_di), offset);
     a.download();
     std::memcpy(dest, a.h<uint8_t>(o_d), (size_t)dstW);
 }
@@ -1658,7 +491,7 @@ static void rgb_line(const mi355_sws_luts *luts, int mode, const int16_t *lumF, 
     if (lumF) std::memcpy(a.h<int16_t>(o_lf), lumF, (size_t)ls * 2);
     if (chrF) std::memcpy(a.h<int16_t>(o_cf), chrF, (size_t)cs * 2);
     a.upload();
-    LAUNCH_LINE(k_sws_line_rgb, a, a.d<const mi355_sws_luts>(o_t), mode, a.d<const int16_t>(o_lf), a.d<const int16_t>(o_l), ls, a.d<const int16_t>(o_cf),
+    launch_line(k_sws_line_rgb, a, a.d<const mi355_sws_luts>(o_t), mode, a.d<const int16_t>(o_lf), a.d<const int16_t>(o_l), ls, a.d<const int16_t>(o_cf),
                 a.d<const int16_t>(o_u), a.d<const int16_t>(o_v), cs, pitch, a.d<uint8_t>(o_d), dstW, yalpha, uvalpha);
     a.download();
     std::memcpy(dest, a.h<uint8_t>(o_d), (size_t)npair * 6);   /* like the reference: whole pairs, also for odd dstW */
