@@ -222,7 +222,9 @@ int mi355_hevc_deblock_pictures_dev(const mi355_hevc_lf_picture *d_pics, int npi
  *   d_pics[pic]  the picture as for mi355_hevc_deblock_pictures_dev, `data` = the RECONSTRUCTION, which is only read here;
  *   d_sao[sao[c]]  the block's job of component c as for mi355_hevc_sao_ctbs_dev: `dst` = the block's first sample in the OUTPUT picture, `src` is not used.
  * The jobs must be of the whole-region forms (every piece of the owner's type, no restored slice / tile / pcm edge in an edge-offset job, offsets within a signed
- * byte) — pictures whose slices forbid filtering across their edges take the two separate entry points.  A job of another form is refused on the device: that
+ * byte; a band- or edge-offset region a multiple of 8 samples wide — the 4-sample chroma region of the last block column of a picture whose width is 8 above a
+ * multiple of the block is taken with SAO off only, any region a multiple of 4 wide is) — pictures whose slices forbid filtering across their edges take the two
+ * separate entry points.  A job of another form is refused on the device: that
  * component of the block is left unwritten and MI355_ERR_FILTER_CTB_FORM is set in the device's error word (mi355_sync returns MI355_E_DEVICE_FAULT). */
 typedef struct mi355_hevc_filter_ctb_job {
     int32_t pic;              /* index into d_pics */
