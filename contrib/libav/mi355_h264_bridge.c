@@ -1155,7 +1155,33 @@ static int submit_picture(Bridge *b, H264Context *h)
     /* the finished picture goes to the frame the decoder hands out (coded size; the reference crops on output) */
     const AVFrame *fr = h->cur_pic_ptr->f;
     for (int k = 0; k < 3; k++) { s->frame_data[k] = fr->data[k]; s->frame_linesize[k] = fr->linesize[k]; }
-    if (getenv("MI355_BRIDGE_DEBUG")) {
+    const char *dbg = getenv("MI355_BRIDGE_DEBUG");
+    if (dbg && (!strcmp(dbg, "2") || strchr(dbg, '/'))) {
+        /* the records as the kernels get them, one line per picture and per macroblock, to stderr ("2") or appended to the file named (tests/test_h264_pair_content.py):
+         *   P picture mbaff mb_w rows bit_depth chroma_idc         (picture: the bridge's own count, which readers may ignore; the lines come in decoding order)
+         *   M x y mb_type flags slice_id qp qpc0 qpc1 cbp intra16x16_mode chroma_mode topleft_mask | 16 intra modes
+         *                                                                                           | per list: L list, 4 ref_idx, 4 ref_pic, 4 chroma_dy, 16 x (mvx mvy)
+         * The file is opened per picture: run it with ONE decoder thread, as the tests do (with several, the lines of different pictures could interleave). */
+        FILE *o = strchr(dbg, '/') ? fopen(dbg, "a") : stderr;
+        if (o) {
+            fprintf(o, "P %lu %d %d %d %d %d\n", b->pictures, b->mbaff_frame, b->mb_w, b->rows, b->bit_depth, b->idc);
+            for (int i = 0; i < b->nmb_pic; i++) {
+                const mi355_h264_mb *m = &s->mb[0][i];
+                fprintf(o, "M %d %d %u %d %d %d %d %d %d %d %d %d", i % b->mb_w, i / b->mb_w, m->mb_type, m->flags, m->slice_id, m->qp, m->qpc[0], m->qpc[1], m->cbp,
+                        m->intra16x16_pred_mode, m->chroma_pred_mode, m->topleft_samples_available);
+                if (m->mb_type & 7) for (int k = 0; k < 16; k++) fprintf(o, " %d", m->u.intra4x4_pred_mode[k]);
+                else for (int l = 0; l < 1 + b->uses_l1; l++) {
+                    fprintf(o, " L %d", l);
+                    for (int q = 0; q < 4; q++) fprintf(o, " %d", m->ref_idx[l][q]);
+                    for (int q = 0; q < 4; q++) fprintf(o, " %d", m->u.inter.ref_pic[l][q]);
+                    for (int q = 0; q < 4; q++) fprintf(o, " %d", m->u.inter.chroma_dy[l][q]);
+                    for (int k = 0; k < 32; k++) fprintf(o, " %d", s->mv[l][(size_t)i * 32 + k]);
+                }
+                fprintf(o, "\n");
+            }
+            if (o != stderr) fclose(o);
+        }
+    } else if (dbg) {
         fprintf(stderr, "picture %lu mbaff %d maxl %d\n", b->pictures, b->mbaff_frame, maxl);
         for (int y = 0; y < b->rows; y++) { for (int x = 0; x < b->mb_w; x++) { const mi355_h264_mb *m = &s->mb[0][y * b->mb_w + x]; fprintf(stderr, " %c%c%d", (m->mb_type & 0x80) ? 'F' : 'p', (m->mb_type & 7) ? ((m->mb_type & 1) ? ((m->mb_type & 0x01000000) ? '8' : '4') : ((m->mb_type & 2) ? 'I' : 'P')) : 'i', m->intra_level); } fprintf(stderr, "\n"); }
     }

@@ -221,7 +221,7 @@ class Rng:
 
 # ---------------------------------------------------------------- a stream
 class Stream:
-    def __init__(self, T, name, mb_w, mb_h, chroma_idc, depth, seed, nslices=1, deblock_idc=0, weighted=True, nrefs=2, npics=6, far=9, bmode=0, t8x8=False, lossless=False, crop=None, mixed=False, cip=False, paff=False, sparse=1.0, skip=0.15, reorder=False, npps=1, scaling=False, gaps=False, mmco=False):
+    def __init__(self, T, name, mb_w, mb_h, chroma_idc, depth, seed, nslices=1, deblock_idc=0, weighted=True, nrefs=2, npics=6, far=9, bmode=0, t8x8=False, lossless=False, crop=None, mixed=False, cip=False, paff=False, sparse=1.0, skip=0.15, reorder=False, npps=1, scaling=False, gaps=False, mmco=False, qp_walk=None, x264_build=None, pair_skips=False, above_left=False, profile=None):
         self.T, self.name, self.mb_w, self.mb_h, self.cidc, self.depth = T, name, mb_w, mb_h, chroma_idc, depth
         self.r = Rng(seed)
         self.nslices, self.deblock_idc, self.weighted, self.nrefs, self.npics, self.far = nslices, deblock_idc, weighted, nrefs, npics, far
@@ -239,10 +239,18 @@ class Stream:
         self.lossless = lossless                             # qpprime_y_zero_transform_bypass_flag and QP'Y = 0 throughout: transform bypass
         if lossless:
             self.qp_min = self.qp_max = -6 * (depth - 8)
+        # the parameters of tests/h264_pair_tables.py; every random draw they add is made only when they are set
+        self.qp_walk = qp_walk                               # (lo, hi): the slice's QP is drawn inside it and mb_qp_delta walks it in steps of up to 6
+        if qp_walk and not lossless:
+            self.qp_min, self.qp_max = qp_walk
+        self.x264_build = x264_build                         # a user-data SEI that makes the reference's parser set x264_build
+        self.pair_skips = pair_skips                         # MbaffStream: mb_skip_run > 0 (P_Skip / B_Skip), mb_field_decoding_flag inferred for skipped pairs
+        self.profile = profile                               # profile_idc instead of the format's own: 244 with 4:2:0 / 4:2:2 (High 4:4:4 Predictive allows them) = lossless PREDICTION with chroma modes
+        self.above_left = above_left                         # MbaffStream: the above-left neighbour D is derived (6.4.12.2) instead of counted as missing
 
     def sps(self):
         w = Bits()
-        profile = 244 if self.cidc == 3 else (122 if self.cidc == 2 else (110 if self.depth > 8 else 100))
+        profile = self.profile or (244 if self.cidc == 3 else (122 if self.cidc == 2 else (110 if self.depth > 8 else 100)))
         w.u(8, profile); w.u(8, 0); w.u(8, 40)
         w.ue(0)
         w.ue(self.cidc)
@@ -307,8 +315,16 @@ class Stream:
         w.trailing()
         return nal(3, 8, w.bytes())
 
+    def sei_x264(self):
+        """user_data_unregistered (payload type 5): 16 bytes of uuid, then the text the reference's parser scans with
+        sscanf(user_data + 16, "x264 - core %d", &build) (h264_sei.c:246)"""
+        text = b"x264 - core %d - generated test stream\0" % self.x264_build
+        payload = bytes(range(0xA0, 0xB0)) + text
+        assert len(payload) < 255
+        return nal(0, 6, bytes([5, len(payload)]) + payload + b"\x80")
+
     def param_sets(self):
-        return self.sps() + b"".join(self.pps(k) for k in range(self.npps))
+        return self.sps() + b"".join(self.pps(k) for k in range(self.npps)) + (self.sei_x264() if self.x264_build is not None else b"")
 
     # ---- neighbour bookkeeping of one picture
     def begin_picture(self):
@@ -420,6 +436,12 @@ class Stream:
         self.nnzc[:, self.cblk_h * mby:self.cblk_h * (mby + 1), 2 * mbx:2 * mbx + 2] = value
 
     def qp_delta(self, w):
+        if self.qp_walk and not self.lossless:
+            d = self.r.i(-6, 6) if self.r.p(0.8) else 0
+            d = min(max(self.qp + d, self.qp_min), self.qp_max) - self.qp
+            self.qp += d
+            w.se(d)
+            return
         d = self.r.i(-3, 3) if self.r.p(0.5) else 0
         if not self.qp_min <= self.qp + d <= self.qp_max:
             d = 0
@@ -691,6 +713,8 @@ class Stream:
         elif ref_idc:
             w.u(1, 0)
         self.qp = 26 + (0 if idx == 0 else r.i(-6, 6))
+        if self.qp_walk:
+            self.qp = r.i(*self.qp_walk)
         if self.lossless:
             self.qp = self.qp_min
         w.se(self.qp - 26)
@@ -817,18 +841,19 @@ class Stream:
 class MbaffStream(Stream):
     """MBAFF frames (mb_adaptive_frame_field_flag): macroblock PAIRS, each coded as two frame or two field macroblocks.  The grids
     keep one entry per macroblock (row 2 * pair row + position in the pair) in the macroblock's own block order; what changes is
-    WHERE the neighbours A (left) and B (above) of a block are (6.4.12.2, Table 6-4).  No skipped macroblocks (the inference rules
-    for mb_field_decoding_flag stay out of the picture), no modes that need the above-left neighbour macroblock."""
+    WHERE the neighbours A (left), B (above) and D (above-left) of a block are (6.4.12.2, Table 6-4).  The streams of STREAMS have no skipped
+    macroblocks and count neighbour D as missing; pair_skips adds P_Skip / B_Skip with the inference of mb_field_decoding_flag (skip_pairs),
+    above_left derives D (topleft_mb): the modes that need the above-left sample — tests/h264_pair_tables.py sets both."""
 
     def sps(self):
         w = Bits()
-        profile = 244 if self.cidc == 3 else (122 if self.cidc == 2 else (110 if self.depth > 8 else 100))
+        profile = self.profile or (244 if self.cidc == 3 else (122 if self.cidc == 2 else (110 if self.depth > 8 else 100)))
         w.u(8, profile); w.u(8, 0); w.u(8, 40)
         w.ue(0)
         w.ue(self.cidc)
         if self.cidc == 3:
             w.u(1, 0)
-        w.ue(self.depth - 8); w.ue(self.depth - 8); w.u(1, 0); w.u(1, 0)
+        w.ue(self.depth - 8); w.ue(self.depth - 8); w.u(1, 1 if self.lossless else 0); w.u(1, 0)
         w.ue(0)
         if self.bmode:
             w.ue(0); w.ue(2)                                 # pic_order_cnt_type 0, 6 bits of pic_order_cnt_lsb
@@ -924,7 +949,22 @@ class MbaffStream(Stream):
         else:
             nb_pos = 0 if (self.fld[py, px] and pos == 0 and self.fld[py - 1, px]) else 1
             top = self.usable(px, 2 * (py - 1) + nb_pos)
-        return left, top, False
+        return left, top, self.above_left and self.topleft_mb(px, py, pos, sid)
+
+    def topleft_mb(self, px, py, pos, sid):
+        """the macroblock that holds the sample above-left of this one's first (6.4.12.2, Table 6-4 for xN < 0, yN < 0; the reference:
+        fill_decode_neighbors, h264_mvpred.h): a frame macroblock at the bottom of its pair looks into the LEFT pair (its top macroblock,
+        or — left pair of field macroblocks — the bottom one, whose line 7 is frame line 15); every other one into the pair above-left:
+        its bottom macroblock, except a top field macroblock next to a field pair (same parity: the top one)"""
+        cur = int(self.fld[py, px])
+        if pos == 1 and not cur:
+            if not self.pair_ok(px - 1, py, sid):
+                return False
+            return self.usable(px - 1, 2 * py + int(self.fld[py, px - 1]))
+        if not self.pair_ok(px - 1, py - 1, sid):
+            return False
+        nb_pos = 0 if (cur and pos == 0 and self.fld[py - 1, px - 1]) else 1
+        return self.usable(px - 1, 2 * (py - 1) + nb_pos)
 
     def ref_range(self, nact):
         return 2 * nact if self.cur_field else nact
@@ -934,7 +974,7 @@ class MbaffStream(Stream):
         w = Bits()
         w.ue(first_pair)                                     # first_mb_in_slice counts pairs in an MBAFF frame
         w.ue(6 if is_b else (5 if is_p else 7))
-        w.ue(0)
+        w.ue(self.pic_pps)
         w.u(4, frame_num & 15)
         w.u(1, 0)                                            # field_pic_flag
         if idr:
@@ -959,11 +999,19 @@ class MbaffStream(Stream):
         elif ref_idc:
             w.u(1, 0)
         self.qp = 26 + (0 if idx == 0 else r.i(-6, 6))
+        if self.qp_walk:
+            self.qp = r.i(*self.qp_walk)
+        if self.lossless:
+            self.qp = self.qp_min
         w.se(self.qp - 26)
         idc = self.deblock_idc if self.deblock_idc >= 0 else r.i(0, 2)
         w.ue(idc)
         if idc != 1:
             w.se(r.i(-2, 2)); w.se(r.i(-2, 2))
+        if self.pair_skips and (is_p or is_b):
+            self.skip_pairs(w, first_pair, last_pair, sid, nact, is_p, is_b)
+            w.trailing()
+            return nal(ref_idc, 5 if idr else 1, w.bytes())
         for p_ in range(first_pair, last_pair):
             px, py = p_ % self.mb_w, p_ // self.mb_w
             self.fld[py, px] = self.cur_field = int(r.p(0.5))
@@ -982,6 +1030,47 @@ class MbaffStream(Stream):
                     self.inter_mb(w, px, mby, sid, nact)
         w.trailing()
         return nal(ref_idc, 5 if idr else 1, w.bytes())
+
+    def skip_pairs(self, w, first_pair, last_pair, sid, nact, is_p, is_b):
+        """the macroblocks of a P / B slice with skipped ones among them (7.3.4): mb_skip_run counts on across pairs; a pair's
+        mb_field_decoding_flag comes with its top macroblock, with the bottom one when only the top one is skipped, and is INFERRED when both
+        are: from pair A (left), else from pair B (above), each only inside the slice, else frame (7.4.4; the reference: the flag of the
+        pair before persists, predict_field_decoding_flag at the start of a row, h264_slice.c:2267-2276, 0 at the start of a slice)"""
+        r = self.r
+        run = 0
+        for p_ in range(first_pair, last_pair):
+            px, py = p_ % self.mb_w, p_ // self.mb_w
+            if p_ == first_pair:
+                inferred = 0
+            elif px > 0:
+                inferred = int(self.fld[py, px - 1])
+            else:
+                inferred = int(self.fld[py - 1, px]) if self.pair_ok(px, py - 1, sid) else 0
+            c = r.r.random()
+            skipped = (True, True) if c < 0.6 * self.skip else ((True, False) if c < self.skip else (False, r.p(self.skip)))
+            self.fld[py, px] = self.cur_field = inferred if all(skipped) else int(r.p(0.5))
+            flag_sent = False
+            for pos in (0, 1):
+                mby = 2 * py + pos
+                self.slice_of[mby, px] = sid
+                if skipped[pos]:
+                    run += 1
+                    self.clear_counts(px, mby)
+                    self.kind[mby][px] = "skip"
+                    continue
+                w.ue(run)                                    # mb_skip_run: the skipped macroblocks since the last coded one
+                run = 0
+                if not flag_sent:
+                    w.u(1, self.cur_field)                   # mb_field_decoding_flag
+                    flag_sent = True
+                if r.p(0.3 if is_p else 0.15):
+                    self.intra_mb(w, px, mby, sid, 5 if is_p else 23)
+                elif is_b:
+                    self.b_mb(w, px, mby, sid, nact)
+                else:
+                    self.inter_mb(w, px, mby, sid, nact)
+        if run:
+            w.ue(run)
 
     def build(self):
         if self.bmode:
@@ -1129,6 +1218,9 @@ def main():
         units = sum((make(k) for k in kw), []) if isinstance(kw, list) else make(kw)
         p = os.path.join(out, "h264_synth_%s.samples" % name)
         write_samples(p, units)
+        committed = os.path.join(os.path.dirname(os.path.abspath(__file__)), "h264_synth_%s.samples" % name)
+        if os.path.abspath(committed) != os.path.abspath(p) and os.path.exists(committed):      # the writer's new parameters must leave every committed stream byte for byte
+            assert hashlib.sha1(open(p, "rb").read()).hexdigest() == hashlib.sha1(open(committed, "rb").read()).hexdigest(), "%s no longer comes out as committed" % name
         with tempfile.TemporaryDirectory() as td:
             err = decode_plain(p, os.path.join(td, "o.yuv"))
             lines = [l for l in err.splitlines() if l.strip()]
