@@ -12,7 +12,7 @@
  *
  * This is the SECOND kernel set DESIGN.md §8 announces, in its first form: one wave per macroblock, samples widened to 16 bits
  * and coefficients to 32 bits in LDS whatever the picture holds, the arithmetic per sample as the templates write it (the
- * device functions the 9 / 10-bit Tier-1 tables already run, h264_tier1_hbd.hip, pinned against the reference's own objects).
+ * device functions the 9 / 10-bit Tier-1 tables already run, h264_tier1.hip, pinned against the reference's own objects).
  * Three passes as in the 8-bit set: every inter macroblock in one launch; intra macroblocks level by level
  * (mi355_h264_intra_schedule); the loop filter as one launch per anti-diagonal d = x + 2y (the reference's raster order only
  * needs left, top and top-right done).  Surfaces are planes with byte strides (MI355_SURFACE_LINEAR).  No byte packing, no

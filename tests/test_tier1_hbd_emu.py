@@ -1,4 +1,4 @@
-"""CPU: the 9- and 10-bit H.264 Tier-1 tables (libav_amd/csrc/h264_tier1_hbd.hip) under the SIMT emulator against
+"""CPU: the 9- and 10-bit H.264 Tier-1 tables (the 9 / 10-bit instances of libav_amd/csrc/h264_tier1.hip) under the SIMT emulator against
 1. the REFERENCE's own BIT_DEPTH 9 / 10 instantiations (oracle/_ref/libref.so; only where /root/reference exists): every
    output buffer byte for byte,
 2. the golden sha1s made from them (tests/golden/h264dsp_hbd_ref_sha1.json; anywhere)."""
