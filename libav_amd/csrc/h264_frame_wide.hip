@@ -1,22 +1,27 @@
 /*
- * h264_frame_wide.hip — Tier-2 for the H.264 formats outside the 8-bit 4:2:0 kernels (h264_frame.hip, h264_deblock.hip):
- * 9- and 10-bit samples (High 10) and 4:2:2 chroma (High 4:2:2), frame or field pictures without MBAFF and without
- * transform bypass.  C ABI: mi355_h264_decode_frames_wide_dev (include/mi355_h264_frame.h).
+ * h264_frame_wide.hip — the second H.264 kernel set: Tier-2 for what lies outside the 8-bit 4:2:0 kernels (h264_frame.hip, h264_deblock.hip):
+ * 9- and 10-bit samples (High 10), 4:2:2 chroma (High 4:2:2), MBAFF frames (macroblock pairs coded as frame or field macroblocks) and transform
+ * bypass (lossless macroblocks), in frame or field pictures.  C ABI: mi355_h264_decode_frames_wide_dev (include/mi355_h264_frame.h).
  *
- * Reference behaviour restated: hl_decode_mb with PIXEL_SHIFT / CHROMA422 (h264_mb_template.c:27-58, :174-232, :239-257),
- * mc_dir_part / mc_part_std / mc_part_weighted (h264_mb.c:204-471, the chroma_idc == 2 branches :284-315), hl_motion
+ * Reference behaviour restated: hl_decode_mb with PIXEL_SHIFT / CHROMA422 (h264_mb_template.c:27-58, :174-232, :239-257) and its MBAFF
+ * geometry (:61-76), mc_dir_part / mc_part_std / mc_part_weighted (h264_mb.c:204-471, the chroma_idc == 2 branches :284-315), hl_motion
  * (h264_mc_template.c:64-163), hl_decode_mb_predict_luma / _idct_luma (h264_mb.c:612-795), the BIT_DEPTH 9 / 10 templates of
  * h264idct_template.c:33-310 (chroma422_dc_dequant_idct :275-310, idct_add8_422 :216-238), h264qpel_template.c:77-300,
  * h264chroma_template.c:28-200, h264dsp_template.c:30-330 (weights, loop-filter lines, the sixteen-line chroma422 edge),
- * h264pred_template.c (pred8x16_* :502-846), ff_h264_filter_mb / filter_mb_dir / check_mv (h264_loopfilter.c:442-847).
+ * h264pred_template.c (pred8x16_* :502-846, the lossless *_add predictors :1209-1354), h264addpx_template.c:30-72, ff_h264_filter_mb /
+ * filter_mb_dir / check_mv (h264_loopfilter.c:442-847) with fill_filter_caches (h264_slice.c:2056-2196).
  *
- * This is the SECOND kernel set DESIGN.md §8 announces, in its first form: one wave per macroblock, samples widened to 16 bits
- * and coefficients to 32 bits in LDS whatever the picture holds, the arithmetic per sample as the templates write it (the
- * device functions the 9 / 10-bit Tier-1 tables already run, h264_tier1.hip, pinned against the reference's own objects).
- * Three passes as in the 8-bit set: every inter macroblock in one launch; intra macroblocks level by level
- * (mi355_h264_intra_schedule); the loop filter as one launch per anti-diagonal d = x + 2y (the reference's raster order only
- * needs left, top and top-right done).  Surfaces are planes with byte strides (MI355_SURFACE_LINEAR).  No byte packing, no
- * tiled surfaces, no single-launch loop filter yet: parity first (bench point config2_high10 in bench.py).
+ * One wave per macroblock in the two reconstruction kernels, samples widened to 16 bits and coefficients to 32 bits in LDS whatever the
+ * picture holds, the arithmetic per sample as the templates write it (the device functions the 9 / 10-bit Tier-1 tables run, h264_tier1.hip,
+ * pinned against the reference's own objects).  Four kernels, three passes as in the 8-bit set:
+ *   k_wide_inter          every inter macroblock in one launch;
+ *   k_wide_intra          intra macroblocks level by level (mi355_h264_intra_schedule);
+ *   k_wide_deblock        the loop filter of frame and field pictures: sixteen lanes per macroblock, four pictures per wave, units of 1 to 4
+ *                         macroblocks of a row per group, one launch per anti-diagonal of units (the reference's raster order only needs left,
+ *                         top and top-right done);
+ *   k_wide_deblock_mbaff  the loop filter of MBAFF frames: the same per macroblock PAIR, one launch per anti-diagonal of pairs.
+ * Both loop filters take their boundary strengths from wide_strength and their view of the motion from wide_fill_caches, once for both.
+ * Surfaces are planes with byte strides (MI355_SURFACE_LINEAR); no byte packing, no tiled surfaces (bench point config2_high10 in bench.py).
  */
 #include <cstdlib>
 #include <type_traits>
@@ -35,57 +40,74 @@ template <int BD, int CF> struct Fmt {
     static constexpr int MAXV = (1 << BD) - 1;
 };
 
-/* N samples between a picture row (4-byte aligned address, N * sizeof(PX) a multiple of 4) and 16-bit samples in LDS */
-/* AGENT: agent-scope accesses (another workgroup of the same launch wrote / will read these samples: the row hand-over of k_wide_deblock_rows) */
-/* LA: what the caller knows about the alignment of the LDS side (bytes).  With LA >= 8 a row piece moves as ONE memory instruction of
- * N * sizeof(PX) bytes (any alignment in memory: the hardware splits what straddles) and one or two LDS instructions — the loop filter's
+/* N samples of a picture row in registers, as memory holds them: one memory instruction of N * sizeof(PX) bytes (any alignment: the hardware
+ * splits what straddles) and, with the LDS side aligned to LA >= 8 bytes, one or two LDS instructions for the 16-bit samples — the loop filter's
  * tiles: a lane's piece is its own cache line, so every further instruction for the same piece is another pass of that line through the L1 */
-template <typename PX, int N, bool AGENT = false, int LA = 2>
+template <typename PX, int N> struct WidePiece { uint32_t w[N * sizeof(PX) / 4]; };
+template <typename PX, int N>
+__device__ __forceinline__ void wide_get(WidePiece<PX, N> &v, const uint8_t *p) { __builtin_memcpy(v.w, p, sizeof(v.w)); }      /* memory -> piece */
+template <typename PX, int N>
+__device__ __forceinline__ void wide_send(uint8_t *p, const WidePiece<PX, N> &v) { __builtin_memcpy(p, v.w, sizeof(v.w)); }     /* piece -> memory */
+template <typename PX, int N, int LA>
+__device__ __forceinline__ void wide_put(const WidePiece<PX, N> &v, uint16_t *d)                                                /* piece -> 16-bit samples in LDS */
+{
+    PX t[N];
+    uint16_t u[N];
+    __builtin_memcpy(t, v.w, sizeof(t));
+#pragma unroll
+    for (int k = 0; k < N; k++) u[k] = t[k];
+    __builtin_memcpy(__builtin_assume_aligned(d, LA), u, sizeof(u));
+}
+template <typename PX, int N, int LA>
+__device__ __forceinline__ void wide_take(WidePiece<PX, N> &v, const uint16_t *d)                                               /* 16-bit samples in LDS -> piece */
+{
+    PX t[N];
+    uint16_t u[N];
+    __builtin_memcpy(u, __builtin_assume_aligned(d, LA), sizeof(u));
+#pragma unroll
+    for (int k = 0; k < N; k++) t[k] = (PX)u[k];
+    __builtin_memcpy(v.w, t, sizeof(t));
+}
+/* N samples between a picture row (4-byte aligned address, N * sizeof(PX) a multiple of 4) and 16-bit samples in LDS.
+ * LA: what the caller knows about the alignment of the LDS side (bytes): >= 8 moves the row as a piece (above), less dword by dword */
+template <typename PX, int N, int LA = 2>
 __device__ __forceinline__ void wide_ld_row(const uint8_t *p, uint16_t *d)
 {
-    if (!AGENT && LA >= 8) {
-        PX v[N];
-        uint16_t t[N];
-        __builtin_memcpy(v, p, sizeof(v));
-#pragma unroll
-        for (int k = 0; k < N; k++) t[k] = v[k];
-        __builtin_memcpy(__builtin_assume_aligned(d, LA), t, sizeof(t));
+    if (LA >= 8) {
+        WidePiece<PX, N> v;
+        wide_get(v, p);
+        wide_put<PX, N, LA>(v, d);
         return;
     }
     const uint32_t *w = reinterpret_cast<const uint32_t *>(p);
     if (sizeof(PX) == 2) {
 #pragma unroll
-        for (int k = 0; k < N / 2; k++) { const uint32_t v = AGENT ? agent_load_u32(w + k) : w[k]; d[2 * k] = (uint16_t)(v & 0xFFFF); d[2 * k + 1] = (uint16_t)(v >> 16); }
+        for (int k = 0; k < N / 2; k++) { const uint32_t v = w[k]; d[2 * k] = (uint16_t)(v & 0xFFFF); d[2 * k + 1] = (uint16_t)(v >> 16); }
     } else {
 #pragma unroll
         for (int k = 0; k < N / 4; k++) {
-            const uint32_t v = AGENT ? agent_load_u32(w + k) : w[k];
+            const uint32_t v = w[k];
             d[4 * k] = (uint16_t)(v & 0xFF); d[4 * k + 1] = (uint16_t)((v >> 8) & 0xFF); d[4 * k + 2] = (uint16_t)((v >> 16) & 0xFF); d[4 * k + 3] = (uint16_t)(v >> 24);
         }
     }
 }
-template <typename PX, int N, bool AGENT = false, int LA = 2>
+template <typename PX, int N, int LA = 2>
 __device__ __forceinline__ void wide_st_row(uint8_t *p, const uint16_t *d)
 {
-    if (!AGENT && LA >= 8) {
-        PX v[N];
-        uint16_t t[N];
-        __builtin_memcpy(t, __builtin_assume_aligned(d, LA), sizeof(t));
-#pragma unroll
-        for (int k = 0; k < N; k++) v[k] = (PX)t[k];
-        __builtin_memcpy(p, v, sizeof(v));
+    if (LA >= 8) {
+        WidePiece<PX, N> v;
+        wide_take<PX, N, LA>(v, d);
+        wide_send(p, v);
         return;
     }
     uint32_t *w = reinterpret_cast<uint32_t *>(p);
     if (sizeof(PX) == 2) {
 #pragma unroll
-        for (int k = 0; k < N / 2; k++) { const uint32_t v = (uint32_t)d[2 * k] | ((uint32_t)d[2 * k + 1] << 16); if (AGENT) agent_store_u32(w + k, v); else w[k] = v; }
+        for (int k = 0; k < N / 2; k++) w[k] = (uint32_t)d[2 * k] | ((uint32_t)d[2 * k + 1] << 16);
     } else {
 #pragma unroll
-        for (int k = 0; k < N / 4; k++) {
-            const uint32_t v = (uint32_t)d[4 * k] | ((uint32_t)d[4 * k + 1] << 8) | ((uint32_t)d[4 * k + 2] << 16) | ((uint32_t)d[4 * k + 3] << 24);
-            if (AGENT) agent_store_u32(w + k, v); else w[k] = v;
-        }
+        for (int k = 0; k < N / 4; k++)
+            w[k] = (uint32_t)d[4 * k] | ((uint32_t)d[4 * k + 1] << 8) | ((uint32_t)d[4 * k + 2] << 16) | ((uint32_t)d[4 * k + 3] << 24);
     }
 }
 
@@ -280,12 +302,12 @@ __device__ inline void wide_add_raw(const int32_t *coef, int nblocks, int size, 
     }
     MI355_WAVE_SYNC();
 }
-/* the running sums of the lossless vertical / horizontal predictors over an n_cols x n_rows region whose 4x4 blocks lie in `coef` as the
- * plane's blocks (pred4x4_*_add chained by pred16x16_*_add / pred8x8_*_add / pred8x16_*_add, h264pred_template.c:1209-1354: a block starts
- * from the sample above / left of it, which the block before it has just written — one sum down each column / along each row).
- * start(k): the sample above column k / left of row k.  Lanes 0..n-1. */
+/* the running sums of the lossless vertical / horizontal predictors over an n_cols x n_rows region (pred4x4_*_add chained by pred16x16_*_add /
+ * pred8x8_*_add / pred8x16_*_add, pred8x8l_*_add, h264pred_template.c:1209-1354: a block starts from the sample above / left of it, which the
+ * block before it has just written — one sum down each column / along each row).  size 4: the region's 4x4 blocks lie in `coef` as the plane's
+ * blocks; size 8: one 8x8 block, its coefficients row by row.  start(k): the sample above column k / left of row k.  Lanes 0..n-1. */
 template <int BD, int CF, typename Start>
-__device__ inline void wide_lossless_run(const int32_t *coef, bool chroma, bool vertical, int n_cols, int n_rows, uint16_t *dst, int pitch, Start start)
+__device__ inline void wide_lossless_run(const int32_t *coef, int size, bool chroma, bool vertical, int n_cols, int n_rows, uint16_t *dst, int pitch, Start start)
 {
     const int lane = lane_id();
     if (lane < (vertical ? n_cols : n_rows)) {
@@ -293,7 +315,7 @@ __device__ inline void wide_lossless_run(const int32_t *coef, bool chroma, bool 
         for (int k = 0; k < (vertical ? n_rows : n_cols); k++) {
             const int x = vertical ? lane : k, y = vertical ? k : lane, x4 = x >> 2, y4 = y >> 2;
             const int b = chroma ? x4 + 2 * (y4 & 1) + 4 * (y4 >> 1) : blk_index(x4, y4);
-            v = wide_wrap<BD, CF>(v + coef[16 * b + 4 * (y & 3) + (x & 3)]);
+            v = wide_wrap<BD, CF>(v + coef[size == 8 ? 8 * y + x : 16 * b + 4 * (y & 3) + (x & 3)]);
             dst[y * pitch + x] = (uint16_t)v;
         }
     }
@@ -315,7 +337,7 @@ __device__ inline void wide_residual_chroma(int32_t *coef, const mi355_h264_mb &
             uint16_t *d = p ? cr : cb;
             if ((h.mb_type & MI355_MB_INTRA) && (h.flags & MI355_MBF_BYPASS_PRED) && (h.chroma_pred_mode == 1 || h.chroma_pred_mode == 2)) {
                 const bool vertical = h.chroma_pred_mode == 2;           /* VERT_PRED8x8 = 2, HOR_PRED8x8 = 1 */
-                wide_lossless_run<BD, CF>(c, true, vertical, 8, F::CH, d, pitch, [&](int k) { return (int)(vertical ? d[-pitch + k] : d[k * pitch - 1]); });
+                wide_lossless_run<BD, CF>(c, 4, true, vertical, 8, F::CH, d, pitch, [&](int k) { return (int)(vertical ? d[-pitch + k] : d[k * pitch - 1]); });
             } else
                 wide_add_raw<BD, CF>(c, F::NCB, 4, true, d, pitch);
         }
@@ -473,8 +495,36 @@ __device__ inline int wide_qpel_px(const uint16_t *win, const int16_t *tmp, int 
     return v;
 }
 
-/* one prediction direction of one partition: mc_dir_part, h264_mb.c:204-318.  Windows are fetched with clamped coordinates, which is
- * what emulated_edge_mc produces (videodsp_template.c:24-96).  dy / dcb / dcr: the macroblock's 16-pitch luma and 8-pitch chroma tiles */
+/* The ww x hh windows at (x0, y0) of NP planes W x H of a reference -> win (pitch wp, plane p at p * plane_pitch), fetched with clamped
+ * coordinates, which is what emulated_edge_mc produces (videodsp_template.c:24-96): a window inside the picture as one piece of eight samples
+ * per lane (any alignment; <= 21 rows x 3 pieces), else sample by sample */
+template <typename PX, int NP>
+__device__ __forceinline__ void wide_fetch_window(uint16_t *win, int wp, int plane_pitch, const uint8_t *const *planes, size_t stride,
+                                                  int x0, int y0, int ww, int hh, int W, int H)
+{
+    const int lane = lane_id(), nc = (ww + 7) >> 3;
+    if (x0 >= 0 && y0 >= 0 && x0 + 8 * nc <= W && y0 + hh <= H) {
+        const int r = (NP == 1 && nc == 3) ? lane / 3 : (nc == 2 ? lane >> 1 : lane), c = lane - r * nc;      /* (three pieces: the luma window alone) */
+#pragma unroll
+        for (int p = 0; p < NP; p++)
+            if (r < hh) {
+                PX v[8];
+                __builtin_memcpy(v, planes[p] + (size_t)(y0 + r) * stride + (size_t)(x0 + 8 * c) * sizeof(PX), sizeof(v));
+#pragma unroll
+                for (int k = 0; k < 8; k++) win[p * plane_pitch + r * wp + 8 * c + k] = v[k];
+            }
+    } else
+#pragma unroll
+    for (int p = 0; p < NP; p++)
+        for (int i = lane; i < ww * hh; i += 64) {
+            const int r = i / ww, c = i - r * ww;
+            const int xx = clip3(x0 + c, 0, W - 1), yy = clip3(y0 + r, 0, H - 1);
+            win[p * plane_pitch + r * wp + c] = reinterpret_cast<const PX *>(planes[p] + (size_t)yy * stride)[xx];
+        }
+    MI355_WAVE_SYNC();
+}
+
+/* one prediction direction of one partition: mc_dir_part, h264_mb.c:204-318.  dy / dcb / dcr: the macroblock's 16-pitch luma and 8-pitch chroma tiles */
 template <int BD, int CF>
 __device__ inline void wide_mc_dir(WideInterLds &s, const mi355_h264_frame &fr, int mb_x, const WideGeom &g, int list, int n_raster, int quadrant,
                                    int bx, int by, int w, int h, uint16_t *dy, uint16_t *dcb, uint16_t *dcr, int avg)
@@ -490,25 +540,9 @@ __device__ inline void wide_mc_dir(WideInterLds &s, const mi355_h264_frame &fr, 
     const int W = 16 * fr.mb_width, H = (16 * fr.mb_height) >> g.hs;
     const size_t rys = (size_t)fr.dst_stride[0] << g.hs, rcs = (size_t)fr.dst_stride[1] << g.hs;      /* a field macroblock of an MBAFF frame predicts from fields */
     const int lw = w == 16 ? 4 : (w == 8 ? 3 : 2);            /* log2 of the block's width */
-#ifndef MI355_WIDE_EXP_NOLUMA
     {
-        const int x0 = (mx >> 2) - 2, y0 = (my >> 2) - 2, ww = w + 5, hh = h + 5, nc = (ww + 7) >> 3;
-        if (x0 >= 0 && y0 >= 0 && x0 + 8 * nc <= W && y0 + hh <= H) {
-            /* the window lies inside the picture: one piece of eight samples per lane (any alignment), <= 21 rows x 3 pieces */
-            const int r = nc == 3 ? lane / 3 : (nc == 2 ? lane >> 1 : lane), c = lane - r * nc;
-            if (r < hh) {
-                PX v[8];
-                __builtin_memcpy(v, rp[0] + (size_t)(y0 + r) * rys + (size_t)(x0 + 8 * c) * sizeof(PX), sizeof(v));
-#pragma unroll
-                for (int k = 0; k < 8; k++) s.win[r * WP + 8 * c + k] = v[k];
-            }
-        } else
-        for (int i = lane; i < ww * hh; i += 64) {
-            const int r = i / ww, c = i - r * ww;
-            const int xx = clip3(x0 + c, 0, W - 1), yy = clip3(y0 + r, 0, H - 1);
-            s.win[r * WP + c] = reinterpret_cast<const PX *>(rp[0] + (size_t)yy * rys)[xx];
-        }
-        MI355_WAVE_SYNC();
+        const int x0 = (mx >> 2) - 2, y0 = (my >> 2) - 2;
+        wide_fetch_window<PX, 1>(s.win, WP, 0, rp, rys, x0, y0, w + 5, h + 5, W, H);
         if (((mx & 3) == 2 && (my & 3)) || ((my & 3) == 2 && (mx & 3))) {
             /* the 2-D positions: the horizontal 6-tap sums of rows -2..h+2 once, in 16 bits around the reference's bias (h264qpel_template.c:119-146) */
             const int pad = F::MAXV > 511 ? -10 * F::MAXV : 0;
@@ -527,32 +561,11 @@ __device__ inline void wide_mc_dir(WideInterLds &s, const mi355_h264_frame &fr, 
         }
         MI355_WAVE_SYNC();
     }
-#endif
-#ifdef MI355_WIDE_EXP_NOCHROMA
-    return;
-#endif
     /* chroma: eighth-sample bilinear (h264chroma_template.c:28-200); 4:2:2 keeps the luma's vertical resolution (h264_mb.c:284-315) */
     const int cw = w >> 1, ch = CF == 2 ? h : h >> 1, cby = CF == 2 ? by : by >> 1;
     const int myc = CF == 1 ? my + uniform((int)s.hdr.u.inter.chroma_dy[list][quadrant]) : my;
     const int cx = mx >> 3, cy = CF == 2 ? myc >> 2 : myc >> 3, fx = mx & 7, fy = CF == 2 ? (myc << 1) & 7 : myc & 7;
-    const int CWd = 8 * fr.mb_width, CHt = (F::CH * fr.mb_height) >> g.hs, cww = cw + 1, chh = ch + 1, ncc = (cww + 7) >> 3;
-    if (cx >= 0 && cy >= 0 && cx + 8 * ncc <= CWd && cy + chh <= CHt) {
-        const int r = ncc == 2 ? lane >> 1 : lane, c = lane - r * ncc;
-        for (int p = 0; p < 2; p++)
-            if (r < chh) {
-                PX v[8];
-                __builtin_memcpy(v, rp[1 + p] + (size_t)(cy + r) * rcs + (size_t)(cx + 8 * c) * sizeof(PX), sizeof(v));
-#pragma unroll
-                for (int k = 0; k < 8; k++) s.win[p * CWIN + r * CWP + 8 * c + k] = v[k];
-            }
-    } else
-    for (int p = 0; p < 2; p++)
-        for (int i = lane; i < cww * chh; i += 64) {
-            const int r = i / cww, c = i - r * cww;
-            const int xx = clip3(cx + c, 0, CWd - 1), yy = clip3(cy + r, 0, CHt - 1);
-            s.win[p * CWIN + r * CWP + c] = reinterpret_cast<const PX *>(rp[1 + p] + (size_t)yy * rcs)[xx];
-        }
-    MI355_WAVE_SYNC();
+    wide_fetch_window<PX, 2>(s.win, CWP, CWIN, rp + 1, rcs, cx, cy, cw + 1, ch + 1, 8 * fr.mb_width, (F::CH * fr.mb_height) >> g.hs);
     const int A = (8 - fx) * (8 - fy), B = fx * (8 - fy), C = (8 - fx) * fy, D = fx * fy;
     for (int p = 0; p < 2; p++)
         for (int i = lane; i < cw * ch; i += 64) {
@@ -609,30 +622,21 @@ __device__ inline void wide_mc_part(WideInterLds &s, const mi355_h264_frame &fr,
                             second && !weighted);
     }
     if (!weighted) return;
+    /* plane by plane: Y, Cb, Cr — the block's place in the prediction tiles, its size, and the slice's {weight, offset} of (reference, list) */
     const int cw = w >> 1, ch = CF == 2 ? h : h >> 1, co = (CF == 2 ? by : by >> 1) * 8 + (bx >> 1);
-    uint16_t *dy = s.py + by * 16 + bx, *dcb = s.pc[0] + co, *dcr = s.pc[1] + co;
-    if (two) {
-        const uint16_t *ty = s.qy + by * 16 + bx, *tcb = s.qc[0] + co, *tcr = s.qc[1] + co;
-        if (sl.use_weight == 2) {
-            const int w0 = iw, w1 = 64 - w0;
-            wide_biweight<BD>(dy, ty, 16, w, h, 5, w0, w1, 0);
-            wide_biweight<BD>(dcb, tcb, 8, cw, ch, 5, w0, w1, 0);
-            wide_biweight<BD>(dcr, tcr, 8, cw, ch, 5, w0, w1, 0);
-        } else {
-            wide_biweight<BD>(dy, ty, 16, w, h, sl.luma_log2_weight_denom, sl.luma_weight[r0][0][0], sl.luma_weight[r1][1][0],
-                              sl.luma_weight[r0][0][1] + sl.luma_weight[r1][1][1]);
-            wide_biweight<BD>(dcb, tcb, 8, cw, ch, sl.chroma_log2_weight_denom, sl.chroma_weight[r0][0][0][0], sl.chroma_weight[r1][1][0][0],
-                              sl.chroma_weight[r0][0][0][1] + sl.chroma_weight[r1][1][0][1]);
-            wide_biweight<BD>(dcr, tcr, 8, cw, ch, sl.chroma_log2_weight_denom, sl.chroma_weight[r0][0][1][0], sl.chroma_weight[r1][1][1][0],
-                              sl.chroma_weight[r0][0][1][1] + sl.chroma_weight[r1][1][1][1]);
-        }
-    } else {
-        const int list = l1 ? 1 : 0, refn = list ? r1 : r0;
-        wide_weight<BD>(dy, 16, w, h, sl.luma_log2_weight_denom, sl.luma_weight[refn][list][0], sl.luma_weight[refn][list][1]);
-        if (sl.use_weight_chroma) {
-            wide_weight<BD>(dcb, 8, cw, ch, sl.chroma_log2_weight_denom, sl.chroma_weight[refn][list][0][0], sl.chroma_weight[refn][list][0][1]);
-            wide_weight<BD>(dcr, 8, cw, ch, sl.chroma_log2_weight_denom, sl.chroma_weight[refn][list][1][0], sl.chroma_weight[refn][list][1][1]);
-        }
+    const int list = l1 ? 1 : 0, refn = list ? r1 : r0;            /* the one reference of a single-list partition */
+#pragma unroll
+    for (int p = 0; p < 3; p++) {
+        const int o = p ? co : by * 16 + bx, pitch = p ? 8 : 16, pw = p ? cw : w, ph = p ? ch : h;
+        uint16_t *d = (p ? s.pc[p - 1] : s.py) + o;
+        const uint16_t *t = (p ? s.qc[p - 1] : s.qy) + o;
+        const int ld = p ? sl.chroma_log2_weight_denom : sl.luma_log2_weight_denom;
+        auto wt = [&](int ref, int li) { return p ? sl.chroma_weight[ref][li][p - 1] : sl.luma_weight[ref][li]; };
+        if (two) {
+            if (sl.use_weight == 2) wide_biweight<BD>(d, t, pitch, pw, ph, 5, iw, 64 - iw, 0);
+            else wide_biweight<BD>(d, t, pitch, pw, ph, ld, wt(r0, 0)[0], wt(r1, 1)[0], wt(r0, 0)[1] + wt(r1, 1)[1]);
+        } else if (!p || sl.use_weight_chroma)
+            wide_weight<BD>(d, pitch, pw, ph, ld, wt(refn, list)[0], wt(refn, list)[1]);
     }
 }
 
@@ -688,10 +692,6 @@ k_wide_inter(const mi355_h264_frame *__restrict__ frames, int max_w, int max_h)
         wide_mc_part<BD, CF>(s, fr, sl, mb_x, g, n, quad, bx, by, w, h, l0, l1);
     }
 #undef DIRF
-#ifdef MI355_WIDE_EXP_NORES
-    wide_store_mb<BD, CF>(fr, mb_x, g, s.py, 16, s.pc[0], s.pc[1], 8);
-    return;
-#endif
     if (luma_coded || chroma_coded) wide_commit_coefs<BD, CF>(s.coef, cregs);       /* the windows' place is free now */
     /* hl_decode_mb_idct_luma (h264_mb.c:726-795): idct_add16 / idct8_add4 choose between full, DC-only and nothing per block; so does
      * wide_block4 / wide_add_blocks8, from the coefficients (a block whose count is 1 with a DC level holds nothing else) */
@@ -780,7 +780,7 @@ k_wide_intra(const mi355_h264_frame *frames, int level, int width)
         if (bypass) {                     /* h264_mb.c:712-722 (the DC levels are in their blocks already), :733-750 */
             if (bypass_pred && (h.intra16x16_pred_mode == 1 || h.intra16x16_pred_mode == 2)) {
                 const bool vertical = h.intra16x16_pred_mode == 2;
-                wide_lossless_run<BD, CF>(s.coef, false, vertical, 16, 16, &WTILE(0, 0), TPW, [&](int k) { return (int)(vertical ? WTILE(k, -1) : WTILE(-1, k)); });
+                wide_lossless_run<BD, CF>(s.coef, 4, false, vertical, 16, 16, &WTILE(0, 0), TPW, [&](int k) { return (int)(vertical ? WTILE(k, -1) : WTILE(-1, k)); });
             } else
                 wide_add_raw<BD, CF>(s.coef, 16, 4, false, &WTILE(0, 0), TPW);
         } else {
@@ -799,20 +799,12 @@ k_wide_intra(const mi355_h264_frame *frames, int level, int width)
                                           (h.topright_samples_available << i) & 0x4000, &WTILE(x0, y0), TPW);
             if (bypass) {                 /* h264_mb.c:628-643: the sums start from the filtered edge the predictor has just left in s.ps (pred8x8l_*_filter_add), or — x264 before build 151 — from the samples themselves */
                 if (bypass_pred && (dir == 0 || dir == 1)) {
-                    if (lane < 8) {
-                        const bool vertical = dir == 0;
-                        int v = x264old ? (int)(vertical ? WTILE(x0 + lane, y0 - 1) : WTILE(x0 - 1, y0 + lane)) : (int)(vertical ? s.ps.fT[1 + lane] : s.ps.fL[1 + lane]);
-                        for (int k = 0; k < 8; k++) {
-                            const int x = vertical ? lane : k, y = vertical ? k : lane;
-                            v = wide_wrap<BD, CF>(v + s.coef[64 * i8 + 8 * y + x]);
-                            WTILE(x0 + x, y0 + y) = (uint16_t)v;
-                        }
-                    }
-                    MI355_WAVE_SYNC();
-                } else {
-                    if (lane < 8) for (int k = 0; k < 8; k++) WTILE(x0 + k, y0 + lane) = wide_wrap<BD, CF>(WTILE(x0 + k, y0 + lane) + s.coef[64 * i8 + 8 * lane + k]);
-                    MI355_WAVE_SYNC();
-                }
+                    const bool vertical = dir == 0;
+                    wide_lossless_run<BD, CF>(s.coef + 64 * i8, 8, false, vertical, 8, 8, &WTILE(x0, y0), TPW, [&](int k) {
+                        return x264old ? (int)(vertical ? WTILE(x0 + k, y0 - 1) : WTILE(x0 - 1, y0 + k)) : (int)(vertical ? s.ps.fT[1 + k] : s.ps.fL[1 + k]);
+                    });
+                } else
+                    wide_add_raw<BD, CF>(s.coef + 64 * i8, 1, 8, false, &WTILE(x0, y0), TPW);
             } else
             wide_add_blocks8<BD, CF>(s.coef, s.t8, i8, 1, &WTILE(0, 0), TPW);
         }
@@ -827,18 +819,11 @@ k_wide_intra(const mi355_h264_frame *frames, int level, int width)
             const int dir = h.u.intra4x4_pred_mode[i];
             intra_pred_wave<uint16_t, BD>(s.ps, 0, dir, 0, 0, &WTILE(x0, y0), TPW);
             if (bypass) {                 /* h264_mb.c:665-669, :690-698 */
-                if (lane < 4) {
-                    if (bypass_pred && (dir == 0 || dir == 1)) {
-                        const bool vertical = dir == 0;
-                        int v = vertical ? WTILE(x0 + lane, y0 - 1) : WTILE(x0 - 1, y0 + lane);
-                        for (int k = 0; k < 4; k++) {
-                            const int x = vertical ? lane : k, y = vertical ? k : lane;
-                            v = wide_wrap<BD, CF>(v + s.coef[16 * i + 4 * y + x]);
-                            WTILE(x0 + x, y0 + y) = (uint16_t)v;
-                        }
-                    } else
-                        for (int k = 0; k < 4; k++) WTILE(x0 + k, y0 + lane) = wide_wrap<BD, CF>(WTILE(x0 + k, y0 + lane) + s.coef[16 * i + 4 * lane + k]);
-                }
+                if (bypass_pred && (dir == 0 || dir == 1)) {
+                    const bool vertical = dir == 0;
+                    wide_lossless_run<BD, CF>(s.coef + 16 * i, 4, false, vertical, 4, 4, &WTILE(x0, y0), TPW, [&](int k) { return (int)(vertical ? WTILE(x0 + k, y0 - 1) : WTILE(x0 - 1, y0 + k)); });
+                } else
+                    wide_add_raw<BD, CF>(s.coef + 16 * i, 1, 4, false, &WTILE(x0, y0), TPW);
             } else
             if (lane < 4) {
                 int r[16];
@@ -869,14 +854,12 @@ constexpr int DYP = 20, DCPW = 12;       /* pitches of the MBAFF filter's luma (
  * 4 MB): 20 GB crossed the fabric per 512 pictures for 4.6 GB of samples (profiles/r04zzz_wide_first_form_counters.txt).  Now a unit's rows come in ONCE, as runs of whole lines
  * (four macroblocks = 128 bytes of a luma row, 64 of a chroma row), the macroblocks are filtered where they lie — macroblock u at columns 16 u .., its left neighbour's columns
  * beside it — and the rows leave once. */
-#ifndef MI355_WIDE_UNIT_MAX
-#define MI355_WIDE_UNIT_MAX 4            /* developer switch: 2 = tiles of two macroblocks (half the LDS, half lines per piece) */
-#endif
-constexpr int WIDE_UNIT = MI355_WIDE_UNIT_MAX;
-#ifndef MI355_WIDE_TILE_MARGIN
-#define MI355_WIDE_TILE_MARGIN 4        /* columns left of the unit in a tile row: the four the filter reaches (8: a macroblock's sample 0 on a 16-byte boundary, 320 bytes more per group) */
-#endif
-constexpr int DBM = MI355_WIDE_TILE_MARGIN, DBLA = DBM % 8 == 0 ? 16 : 8;      /* ... and what that says about the alignment of a macroblock's row piece in LDS */
+/* four: macroblocks side by side that make 128 bytes of a 10-bit luma row (64 of a chroma row), so a unit's rows are runs of whole cache lines;
+ * the tiles below are sized by it, and the launcher clamps MI355_WIDE_UNIT to it */
+constexpr int WIDE_UNIT = 4;
+/* columns left of the unit in a tile row: the four the filter reaches; a macroblock's row piece then lies on an 8-byte boundary in LDS (DBLA).  Eight
+ * would put a macroblock's sample 0 on a 16-byte boundary for 320 bytes more per group */
+constexpr int DBM = 4, DBLA = 8;
 constexpr int DBYP = DBM + 16 * WIDE_UNIT, DBCP = DBM + 8 * WIDE_UNIT;      /* pitches: columns -DBM .. 16 * WIDE_UNIT - 1 / -DBM .. 8 * WIDE_UNIT - 1 */
 template <int CF> struct WideDbLds {
     mi355_h264_mb m[3];                  /* this macroblock, its left and its top neighbour */
@@ -950,39 +933,33 @@ __device__ __forceinline__ bool wide_chroma_line(int p1, int &p0, int &q0, int q
     p0 = np0; q0 = nq0;
     return true;
 }
-/* alpha, beta and the tc0 row (table 8-16 / 8-17; tc0 of strength bs: byte bs - 1) of an edge with average QP qp: three of them per plane of a
+/* tables 8-16 / 8-17 in LDS: the edge loops look alpha, beta and tc0 up per lane — from memory that is a dependent load of a microsecond */
+struct WideThrTables {
+    uint8_t alpha[52], beta[52];
+    alignas(4) uint8_t tc0[52][4];       /* a row is read as one dword (wide_thr) */
+};
+__device__ __forceinline__ void wide_thr_fill(WideThrTables &t, int lane)
+{
+    if (lane < 52) { t.alpha[lane] = k_alpha[lane]; t.beta[lane] = k_beta[lane]; t.tc0[lane][0] = k_tc0[lane][0]; t.tc0[lane][1] = k_tc0[lane][1]; t.tc0[lane][2] = k_tc0[lane][2]; t.tc0[lane][3] = 0; }
+}
+/* alpha, beta and the tc0 row (tc0 of strength bs: byte bs - 1) of an edge with average QP qp: three of them per plane of a
  * macroblock (left edge, top edge, inner edges), worked out once before the edge loop */
 struct WideThr { int alpha, beta; uint32_t tc0; };
 template <int BD>
-__device__ __forceinline__ WideThr wide_thr(const uint8_t *t_alpha, const uint8_t *t_beta, const uint8_t (*t_tc0)[4], int qp, int a_off, int b_off)
+__device__ __forceinline__ WideThr wide_thr(const WideThrTables &tab, int qp, int a_off, int b_off)
 {
     const int ia = med3i(qp - 6 * (BD - 8) + a_off, 0, 51), ib = med3i(qp - 6 * (BD - 8) + b_off, 0, 51);
     WideThr t;
-    t.alpha = t_alpha[ia] << (BD - 8);
-    t.beta = t_beta[ib] << (BD - 8);
-    t.tc0 = *reinterpret_cast<const uint32_t *>(t_tc0[ia]);
+    t.alpha = tab.alpha[ia] << (BD - 8);
+    t.beta = tab.beta[ib] << (BD - 8);
+    t.tc0 = *reinterpret_cast<const uint32_t *>(tab.tc0[ia]);
     return t;
 }
 template <int BD>
 __device__ __forceinline__ int wide_tc0(const WideThr &t, int bs) { return (int)((t.tc0 >> (8 * ((bs - 1) & 3))) & 0xFF) << (BD - 8); }
-/* check_mv, h264_loopfilter.c:442-470 */
+/* check_mv, h264_loopfilter.c:442-470, without branches: every lane evaluates one pair of blocks of the view s.ref / s.mv */
 template <typename LDS>
-__device__ inline int wide_check_mv(const LDS &s, int b, int bn, int list_count, int ylim)
-{
-    bool v = s.ref[0][b] != s.ref[0][bn];
-    if (!v && s.ref[0][b] != -1) v = wide_mv_far(s.mv[0][b], s.mv[0][bn], ylim);
-    if (list_count == 2) {
-        if (!v) v = s.ref[1][b] != s.ref[1][bn] || wide_mv_far(s.mv[1][b], s.mv[1][bn], ylim);
-        if (v) {
-            if (s.ref[0][b] != s.ref[1][bn] || s.ref[0][bn] != s.ref[1][b]) return 1;
-            return wide_mv_far(s.mv[0][b], s.mv[1][bn], ylim) || wide_mv_far(s.mv[1][b], s.mv[0][bn], ylim);
-        }
-    }
-    return v;
-}
-/* the same without branches (the frame / field filter's strengths: every lane evaluates one pair of blocks) */
-template <typename LDS>
-__device__ __forceinline__ int wide_check_mv_bf(const LDS &s, int b, int bn, bool two_lists, int ylim)
+__device__ __forceinline__ int wide_check_mv(const LDS &s, int b, int bn, bool two_lists, int ylim)
 {
     const int r0b = s.ref[0][b], r0n = s.ref[0][bn], r1b = s.ref[1][b], r1n = s.ref[1][bn];
     const uint32_t m0b = s.mv[0][b], m0n = s.mv[0][bn], m1b = s.mv[1][b], m1n = s.mv[1][bn];
@@ -998,6 +975,59 @@ __device__ __forceinline__ int wide_ref_identity(const mi355_h264_mb &m, int lis
     const int r = m.u.inter.ref_pic[list][(x4 >> 1) + 2 * (y4 >> 1)];
     return r == 0xFF ? -1 : r;
 }
+/* The filter's 5x5 view of the motion — picture identities, vectors and coefficient flags at (y + 1) * 5 + (x + 1), x, y = -1..3 (fill_filter_caches,
+ * h264_slice.c:2056-2196) — from the records s.m[cur], s.m[left], s.m[top] (an absent neighbour: cur).  Lane l of sixteen: block l of the macroblock;
+ * lanes 0..3 also block (3, l) of the left record, lanes 4..7 block (l - 4, 3) of the top one.  mv_of(list, k): the vector of the lane's own
+ * block (k = 0) / of its neighbour's block (k = 1). */
+template <typename LDS, typename Mv>
+__device__ __forceinline__ void wide_fill_caches(LDS &s, int cur, int left, int top, int l, Mv mv_of)
+{
+    for (int k = 0; k < 2; k++) {
+        if (k && l >= 8) break;
+        int which, x4, y4, cx, cy;
+        if (!k) { which = cur; x4 = l & 3; y4 = l >> 2; cx = x4; cy = y4; }
+        else if (l < 4) { which = left; x4 = 3; y4 = l; cx = -1; cy = y4; }
+        else { which = top; x4 = l - 4; y4 = 3; cx = x4; cy = -1; }
+        const int ci = (cy + 1) * 5 + cx + 1;
+        for (int list = 0; list < 2; list++) {
+            s.ref[list][ci] = wide_ref_identity(s.m[which], list, x4, y4);
+            s.mv[list][ci] = mv_of(list, k);
+        }
+        s.nnz[ci] = (uint8_t)((s.m[which].nnz_mask >> blk_index(x4, y4)) & 1);
+    }
+}
+/* The boundary strength of one pair of blocks: filter_mb_dir, h264_loopfilter.c:472-714.  Lane l of sixteen = 4 * edge + i: the i-th pair along
+ * edge `edge` of direction dir (0: vertical edges) of macroblock m, from the view wide_fill_caches left.  Without branches: the one pair of blocks
+ * whose motion decides (the lane's own pair, or the partition's first pair where the macroblock moves as a whole across the edge) is compared in
+ * any case, the cases of :553-607 / :638-690 pick among 0, 1, 2, 3 / 4 and that comparison.  What the caller knows of edge 0: whether it is
+ * filtered here at all (edge0_on), the neighbour's mb_type, the intra strength there (intra0: 4, or 3 on a horizontal edge of field lines) and
+ * whether the neighbour above is of the other frame / field coding (other_coding: 1 or 2 without a look at the vectors, :568-571). */
+template <int CF, typename LDS>
+__device__ __forceinline__ int wide_strength(const LDS &s, const mi355_h264_mb &m, int dir, int l, bool edge0_on, uint32_t nb_type, int intra0,
+                                             bool other_coding, int ylim, bool two_lists)
+{
+    const uint32_t t = m.mb_type;
+    const int edge = l >> 2, i = l & 3, tk = (t >> 3) & 7;
+    const bool e0 = edge == 0;
+    const int mask_edge = dir == 0 ? (tk == 0 ? 0 : (tk < 4 ? 3 : 1)) : (tk == 0 ? 0 : (tk == 1 ? 3 : (tk < 4 ? 1 : 3)));
+    const int edges = (mask_edge == 3 && !(m.cbp & 15)) ? 1 : 4;
+    const uint32_t par_types = MI355_MB_16x16 | (MI355_MB_8x16 >> dir);
+    const bool mask_par0 = (t & par_types) != 0;
+    const int x = dir == 0 ? edge : i, y = dir == 0 ? i : edge, step = dir ? 5 : 1;
+    const int b = (y + 1) * 5 + x + 1, bn = b - step;
+    const bool par = mask_par0 & (!e0 | ((nb_type & par_types) != 0));
+    const int b0 = e0 ? 6 : (dir == 0 ? 6 + edge : (edge + 1) * 5 + 1), cb = par ? b0 : b;
+    const int mvd = wide_check_mv(s, cb, cb - step, two_lists, ylim);
+    const bool nz = (s.nnz[b] | s.nnz[bn]) != 0;
+    const bool deblock_edge = !((t & MI355_MB_8x8DCT) && (edge & 1));
+    const bool active = e0 ? edge0_on : (edge < edges) & (deblock_edge | (CF == 2 && dir == 1));     /* 4:2:2: the chroma of the odd horizontal edges (:679-686) */
+    const bool intra = ((e0 ? t | nb_type : t) & MI355_MB_INTRA) != 0;
+    const int bs_intra = e0 ? intra0 : 3;
+    const int bs_inter = nz ? 2 : ((e0 & other_coding) ? 1 : ((!e0 & ((edge & mask_edge) != 0)) ? 0 : mvd));
+    return active ? (intra ? bs_intra : bs_inter) : 0;
+}
+/* ... and of the pair kernel's two extra edges, from coefficient flags alone (:497-540, :748-770): n between intra macroblocks */
+__device__ __forceinline__ int wide_strength_coded(uint32_t t, uint32_t nb_type, bool coded, int n) { return ((t | nb_type) & MI355_MB_INTRA) ? n : 1 + (int)coded; }
 
 /* ---- the frame / field loop filter: what a group of sixteen lanes needs of its picture, of a macroblock, and the macroblock itself ---------- */
 /* the picture's descriptor in registers: read once per wave (a field of `frames[f]` read inside the macroblock loop is a load again after every
@@ -1020,20 +1050,6 @@ __device__ __forceinline__ WideDbPic wide_db_pic(const mi355_h264_frame &fr)
     p.ys = fr.recon_stride[0]; p.cs = fr.recon_stride[1]; p.yd = fr.dst_stride[0]; p.cd = fr.dst_stride[1];
     p.mbw = fr.mb_width; p.mbh = fr.mb_height; p.field = fr.field_picture; p.nslices = fr.nslices;
     return p;
-}
-/* N samples of a picture row in registers, as memory holds them */
-template <typename PX, int N> struct WidePiece { uint32_t w[N * sizeof(PX) / 4]; };
-template <typename PX, int N>
-__device__ __forceinline__ void wide_get(WidePiece<PX, N> &v, const uint8_t *p) { __builtin_memcpy(v.w, p, sizeof(v.w)); }      /* one load, any alignment */
-template <typename PX, int N, int LA>
-__device__ __forceinline__ void wide_put(const WidePiece<PX, N> &v, uint16_t *d)                                                /* -> 16-bit samples in LDS */
-{
-    PX t[N];
-    uint16_t u[N];
-    __builtin_memcpy(t, v.w, sizeof(t));
-#pragma unroll
-    for (int k = 0; k < N; k++) u[k] = t[k];
-    __builtin_memcpy(__builtin_assume_aligned(d, LA), u, sizeof(u));
 }
 /* one macroblock's records and vectors as the loads deliver them: a group fetches those of the NEXT macroblock of its unit while it filters this one */
 template <int BD, int CF> struct WideDbIn {
@@ -1118,23 +1134,23 @@ __device__ __forceinline__ void wide_db_store_unit(const WideDbLds<CF> &s, const
     const int yd = pic.yd, cd = pic.cd;
     uint8_t *row = const_cast<uint8_t *>(pic.dst[0]) + (size_t)(16 * mb_y + l) * yd + 16 * x0 * PXB;
 #pragma unroll
-    for (int k = 0; k < WIDE_UNIT; k++) if (k < nu) wide_st_row<PX, 16, false, DBLA>(row + 16 * PXB * k, &DY(16 * k, l));
-    if (has_left) wide_st_row<PX, 4, false, 8>(row - 4 * PXB, &DY(-4, l));
+    for (int k = 0; k < WIDE_UNIT; k++) if (k < nu) wide_st_row<PX, 16, DBLA>(row + 16 * PXB * k, &DY(16 * k, l));
+    if (has_left) wide_st_row<PX, 4, 8>(row - 4 * PXB, &DY(-4, l));
     if (has_top && l < 12) {
         const int r = (l >> 2) - 3, k = l & 3;
-        if (k < nu) wide_st_row<PX, 16, false, DBLA>(const_cast<uint8_t *>(pic.dst[0]) + (size_t)(16 * mb_y + r) * yd + (16 * x0 + 16 * k) * PXB, &DY(16 * k, r));
+        if (k < nu) wide_st_row<PX, 16, DBLA>(const_cast<uint8_t *>(pic.dst[0]) + (size_t)(16 * mb_y + r) * yd + (16 * x0 + 16 * k) * PXB, &DY(16 * k, r));
     }
 #pragma unroll
     for (int q = 0; q < (CF == 2 ? 2 : 1); q++) {
         const int p = CF == 2 ? q : l >> 3, r = CF == 2 ? l : l & 7;
         uint8_t *crow = const_cast<uint8_t *>(p ? pic.dst[2] : pic.dst[1]) + (size_t)(F::CH * mb_y + r) * cd + 8 * x0 * PXB;
 #pragma unroll
-        for (int k = 0; k < WIDE_UNIT; k++) if (k < nu) wide_st_row<PX, 8, false, DBLA>(crow + 8 * PXB * k, &DC(p, 8 * k, r));
-        if (has_left) wide_st_row<PX, 4, false, 8>(crow - 4 * PXB, &DC(p, -4, r));
+        for (int k = 0; k < WIDE_UNIT; k++) if (k < nu) wide_st_row<PX, 8, DBLA>(crow + 8 * PXB * k, &DC(p, 8 * k, r));
+        if (has_left) wide_st_row<PX, 4, 8>(crow - 4 * PXB, &DC(p, -4, r));
     }
     if (has_top && l < 2 * WIDE_UNIT) {           /* chroma row -1: lane = plane * WIDE_UNIT + macroblock */
         const int p = l / WIDE_UNIT, k = l % WIDE_UNIT;
-        if (k < nu) wide_st_row<PX, 8, false, DBLA>(const_cast<uint8_t *>(p ? pic.dst[2] : pic.dst[1]) + (size_t)(F::CH * mb_y - 1) * cd + (8 * x0 + 8 * k) * PXB, &DC(p, 8 * k, -1));
+        if (k < nu) wide_st_row<PX, 8, DBLA>(const_cast<uint8_t *>(p ? pic.dst[2] : pic.dst[1]) + (size_t)(F::CH * mb_y - 1) * cd + (8 * x0 + 8 * k) * PXB, &DC(p, 8 * k, -1));
     }
 }
 
@@ -1144,7 +1160,7 @@ __device__ __forceinline__ void wide_db_store_unit(const WideDbLds<CF> &s, const
  * — from the tile's last columns; the macroblock, three columns and three rows (one of each in chroma) go back to `dst`.
  * `in`: what wide_db_fetch brought for this macroblock; once the tile is filled, `next` may fetch the following macroblock into it. */
 template <int BD, int CF, typename Next>
-__device__ __forceinline__ void wide_deblock_mb(WideDbLds<CF> &s, const uint8_t *t_alpha, const uint8_t *t_beta, const uint8_t (*t_tc0)[4], const uint8_t *t_lc,
+__device__ __forceinline__ void wide_deblock_mb(WideDbLds<CF> &s, const WideThrTables &tab, const uint8_t *t_lc,
                                                 const WideDbPic &pic, const WideDbIn<BD, CF> &in, bool ok, int u, int l, Next next)
 {
     typedef Fmt<BD, CF> F;
@@ -1152,11 +1168,8 @@ __device__ __forceinline__ void wide_deblock_mb(WideDbLds<CF> &s, const uint8_t 
     if (ok) {
 #pragma unroll
         for (int k = 0; k < 3; k++) reinterpret_cast<uint32_t *>(&s.m[k])[l] = in.rec[k];
-        /* the vectors' places in the filter's view of the motion: (y + 1) * 5 + (x + 1) */
-        const int c0 = ((l >> 2) + 1) * 5 + (l & 3) + 1, c1 = l < 4 ? (l + 1) * 5 : l - 3;
-#pragma unroll
-        for (int list = 0; list < 2; list++) { s.mv[list][c0] = in.mv[list][0]; if (l < 8) s.mv[list][c1] = in.mv[list][1]; }
     }
+    const uint32_t mv[2][2] = { { in.mv[0][0], in.mv[0][1] }, { in.mv[1][0], in.mv[1][1] } };      /* this macroblock's vectors: `next` overwrites `in` */
     MI355_WAVE_SYNC();
     next();                                      /* the next macroblock's loads leave now and arrive during the filter */
     const mi355_h264_mb &m = s.m[0];
@@ -1166,47 +1179,14 @@ __device__ __forceinline__ void wide_deblock_mb(WideDbLds<CF> &s, const uint8_t 
     if (filter) {
         /* the slice's list_count: of the picture's first sixteen slices in LDS since the wave began */
         list_count = m.slice_id < 16 ? t_lc[m.slice_id] : pic.slices[m.slice_id].list_count;
-        /* picture identities and coefficient flags the strengths are derived from (fill_filter_caches, h264_slice.c:2056-2196), from the records */
-        for (int k = 0; k < 2; k++) {
-            if (k && l >= 8) break;
-            int which, x4, y4, cx, cy;
-            if (!k) { which = 0; x4 = l & 3; y4 = l >> 2; cx = x4; cy = y4; }
-            else if (l < 4) { which = 1; x4 = 3; y4 = l; cx = -1; cy = y4; }
-            else { which = 2; x4 = l - 4; y4 = 3; cx = x4; cy = -1; }
-            const int ci = (cy + 1) * 5 + cx + 1;
-            for (int list = 0; list < 2; list++) s.ref[list][ci] = wide_ref_identity(s.m[which], list, x4, y4);
-            s.nnz[ci] = (uint8_t)((s.m[which].nnz_mask >> blk_index(x4, y4)) & 1);
-        }
+        wide_fill_caches(s, 0, 1, 2, l, [&](int list, int k) { return mv[list][k]; });
     }
     MI355_WAVE_SYNC();
     if (filter) {
-        /* boundary strengths: filter_mb_dir, h264_loopfilter.c:472-714; lane l = 4 * edge + i, both directions.  Without branches: the one
-         * pair of blocks whose motion decides (the lane's own pair, or the partition's first pair where the macroblock moves as a whole across
-         * the edge) is compared in any case, the cases of :553-607 / :638-690 pick among 0, 2, 3 / 4 and that comparison */
-        const uint32_t t = m.mb_type;
-        const int edge = l >> 2, i = l & 3, tk = (t >> 3) & 7;
-        const bool e0 = edge == 0, two = list_count == 2, intra_cur = (t & MI355_MB_INTRA) != 0;
 #pragma unroll
-        for (int dir = 0; dir < 2; dir++) {
-            const int mask_edge = dir == 0 ? (tk == 0 ? 0 : (tk < 4 ? 3 : 1)) : (tk == 0 ? 0 : (tk == 1 ? 3 : (tk < 4 ? 1 : 3)));
-            const int edges = (mask_edge == 3 && !(m.cbp & 15)) ? 1 : 4;
-            const uint32_t par_types = MI355_MB_16x16 | (MI355_MB_8x16 >> dir);
-            const bool mask_par0 = (t & par_types) != 0;
-            const int x = dir == 0 ? edge : i, y = dir == 0 ? i : edge, step = dir ? 5 : 1;
-            const int b = (y + 1) * 5 + x + 1, bn = b - step;
-            const uint32_t mmt = s.m[1 + dir].mb_type;
-            const bool par = mask_par0 & (!e0 | ((mmt & par_types) != 0));
-            const int b0 = e0 ? 6 : (dir == 0 ? 6 + edge : (edge + 1) * 5 + 1), cb = par ? b0 : b;
-            const int mvd = wide_check_mv_bf(s, cb, cb - step, two, ylim);
-            const bool nz = (s.nnz[b] | s.nnz[bn]) != 0;
-            const bool deblock_edge = !((t & MI355_MB_8x8DCT) && (edge & 1));
-            const bool active = e0 ? (m.flags & (dir ? MI355_MBF_TOP_EDGE : MI355_MBF_LEFT_EDGE)) != 0 : (edge < edges) & (deblock_edge | (CF == 2 && dir == 1));
-            const bool intra = e0 ? ((t | mmt) & MI355_MB_INTRA) != 0 : intra_cur;
-            const int bs_intra = e0 ? ((!pic.field || dir == 0) ? 4 : 3) : 3;
-            const int bs_inter = nz ? 2 : ((!e0 & ((edge & mask_edge) != 0)) ? 0 : mvd);
-            const int bs = active ? (intra ? bs_intra : bs_inter) : 0;
-            s.bs[i][4 * dir + edge] = (uint8_t)bs;
-        }
+        for (int dir = 0; dir < 2; dir++)
+            s.bs[l & 3][4 * dir + (l >> 2)] = (uint8_t)wide_strength<CF>(s, m, dir, l, (m.flags & (dir ? MI355_MBF_TOP_EDGE : MI355_MBF_LEFT_EDGE)) != 0, s.m[1 + dir].mb_type,
+                                                                         (!pic.field || dir == 0) ? 4 : 3, false, ylim, list_count == 2);
     }
     MI355_WAVE_SYNC();
     {
@@ -1214,10 +1194,10 @@ __device__ __forceinline__ void wide_deblock_mb(WideDbLds<CF> &s, const uint8_t 
         const int a_off = m.slice_alpha_c0_offset, b_off = m.slice_beta_offset, qp0 = m.qp;
         const bool dct8 = (m.mb_type & MI355_MB_8x8DCT) != 0;
         WideThr ty[3], tc[2][3];                 /* [inner, left, top]; chroma: [the plane(s) this lane filters] */
-        for (int e = 0; e < 3; e++) ty[e] = wide_thr<BD>(t_alpha, t_beta, t_tc0, e ? (qp0 + s.m[e].qp + 1) >> 1 : qp0, a_off, b_off);
+        for (int e = 0; e < 3; e++) ty[e] = wide_thr<BD>(tab, e ? (qp0 + s.m[e].qp + 1) >> 1 : qp0, a_off, b_off);
         for (int k = 0; k < (CF == 2 ? 2 : 1); k++) {
             const int p = CF == 2 ? k : l >> 3;
-            for (int e = 0; e < 3; e++) tc[k][e] = wide_thr<BD>(t_alpha, t_beta, t_tc0, e ? (m.qpc[p] + s.m[e].qpc[p] + 1) >> 1 : m.qpc[p], a_off, b_off);
+            for (int e = 0; e < 3; e++) tc[k][e] = wide_thr<BD>(tab, e ? (m.qpc[p] + s.m[e].qpc[p] + 1) >> 1 : m.qpc[p], a_off, b_off);
         }
         /* The edges, one direction at a time with the line in registers: lane l holds row l (then column l) of the luma tile, columns / rows
          * -4..15, and a row (then a column) of chroma; the four edges of a direction pass over it without a trip to LDS in between — what a lone
@@ -1313,11 +1293,10 @@ __global__ void __launch_bounds__(64)
 k_wide_deblock(const mi355_h264_frame *frames, int nframes, int d, int y_first, int rows, int unit)
 {
     __shared__ WideDbLds<CF> sh[4];
-    /* tables 8-16 / 8-17 in LDS: the edge loop looks alpha, beta and tc0 up per lane — from memory that is a dependent load of a microsecond */
-    __shared__ uint8_t t_alpha[52], t_beta[52], t_lc[4][16];
-    __shared__ __attribute__((aligned(4))) uint8_t t_tc0[52][4];       /* a row is read as one dword (wide_thr) */
+    __shared__ WideThrTables tab;
+    __shared__ uint8_t t_lc[4][16];
     const int lane = lane_id(), g = lane >> 4, l = lane & 15;
-    if (lane < 52) { t_alpha[lane] = k_alpha[lane]; t_beta[lane] = k_beta[lane]; t_tc0[lane][0] = k_tc0[lane][0]; t_tc0[lane][1] = k_tc0[lane][1]; t_tc0[lane][2] = k_tc0[lane][2]; t_tc0[lane][3] = 0; }
+    wide_thr_fill(tab, lane);
     /* the launch holds the rows that have a unit on this anti-diagonal (of the largest picture): y_first .. y_first + rows - 1 */
     const int f = 4 * ((int)blockIdx.x / rows) + g, mb_y = y_first + (int)blockIdx.x % rows, x0 = (d - 2 * mb_y) * unit;
     const WideDbPic pic = wide_db_pic(frames[f < nframes ? f : nframes - 1]);
@@ -1333,7 +1312,7 @@ k_wide_deblock(const mi355_h264_frame *frames, int nframes, int d, int y_first, 
     for (int u = 0; u < unit; u++) {
         const int mb_x = x0 + u;
         const bool ok = u < nu, more = u + 1 < nu;
-        wide_deblock_mb<BD, CF>(sh[g], t_alpha, t_beta, t_tc0, t_lc[g], pic, in, ok, u, l,
+        wide_deblock_mb<BD, CF>(sh[g], tab, t_lc[g], pic, in, ok, u, l,
                                 [&]() { if (more) wide_db_fetch<BD, CF>(in, pic, true, mb_x + 1, mb_y, l); });
         MI355_WAVE_SYNC();                       /* the next macroblock's records overwrite what this one's strengths read */
     }
@@ -1380,11 +1359,10 @@ k_wide_deblock_mbaff(const mi355_h264_frame *frames, int nframes, int d, int max
     typedef typename F::PX PX;
     constexpr int PXB = (int)sizeof(PX), CHP = 2 * F::CH;       /* chroma lines of a pair */
     __shared__ WideMbaffLds sh[4];
-    __shared__ uint8_t t_alpha[52], t_beta[52];
-    __shared__ __attribute__((aligned(4))) uint8_t t_tc0[52][4];       /* a row is read as one dword (wide_thr) */
+    __shared__ WideThrTables tab;
     const int lane = lane_id(), g = lane >> 4, l = lane & 15;
     WideMbaffLds &s = sh[g];
-    if (lane < 52) { t_alpha[lane] = k_alpha[lane]; t_beta[lane] = k_beta[lane]; t_tc0[lane][0] = k_tc0[lane][0]; t_tc0[lane][1] = k_tc0[lane][1]; t_tc0[lane][2] = k_tc0[lane][2]; t_tc0[lane][3] = 0; }
+    wide_thr_fill(tab, lane);
     const int f = 4 * ((int)blockIdx.x / max_pr) + g, pr = (int)blockIdx.x % max_pr, x = d - 2 * pr;
     const mi355_h264_frame &fr = frames[f < nframes ? f : nframes - 1];
     const int W = fr.mb_width;
@@ -1413,7 +1391,7 @@ k_wide_deblock_mbaff(const mi355_h264_frame *frames, int nframes, int d, int max
     MI355_WAVE_SYNC();
     /* the line filters of the frame / field kernel in their voteless form: these run inside lane-dependent control flow */
     auto luma_line = [&](uint16_t *q, int st, int bs, int qp, int a_off, int b_off) {
-        const WideThr t = wide_thr<BD>(t_alpha, t_beta, t_tc0, qp, a_off, b_off);
+        const WideThr t = wide_thr<BD>(tab, qp, a_off, b_off);
         /* (the fourth sample of a side only where bS 4 reads it: at the twice-filtered top edge it would lie outside the tile) */
         int p3 = bs == 4 ? q[-4 * st] : 0, p2 = q[-3 * st], p1 = q[-2 * st], p0 = q[-st], q0 = q[0], q1 = q[st], q2 = q[2 * st], q3 = bs == 4 ? q[3 * st] : 0;
         const int r = wide_luma_line<F::MAXV, true, false>(p3, p2, p1, p0, q0, q1, q2, q3, bs, t.alpha, t.beta, wide_tc0<BD>(t, bs));
@@ -1421,7 +1399,7 @@ k_wide_deblock_mbaff(const mi355_h264_frame *frames, int nframes, int d, int max
         if (r == 2) { q[-3 * st] = (uint16_t)p2; q[2 * st] = (uint16_t)q2; }
     };
     auto chroma_line = [&](uint16_t *q, int st, int bs, int qp, int a_off, int b_off) {
-        const WideThr t = wide_thr<BD>(t_alpha, t_beta, t_tc0, qp, a_off, b_off);
+        const WideThr t = wide_thr<BD>(tab, qp, a_off, b_off);
         int p1 = q[-2 * st], p0 = q[-st], q0 = q[0], q1 = q[st];
         wide_chroma_line<F::MAXV, false>(p1, p0, q0, q1, bs, t.alpha, t.beta, wide_tc0<BD>(t, bs) + 1);
         q[-st] = (uint16_t)p0; q[0] = (uint16_t)q0;
@@ -1446,58 +1424,25 @@ k_wide_deblock_mbaff(const mi355_h264_frame *frames, int nframes, int d, int max
         if (top_k >= 4 && own_slice && s.m[top_k].slice_id != m.slice_id) top_k = -1;
         const bool top_double = top_k == 5 && !cur_field && pos == 0 && (s.m[5].mb_type & 0x80u);       /* a frame macroblock under a field pair */
         const int top_xy = top_k == 0 ? xy0 : (top_k == 4 ? xy0 - 2 * W : xy0 - W);
-        int list_count = 1;
         const int ylim = cur_field ? 2 : 4;
         if (filter) {
-            list_count = fr.slices[m.slice_id].list_count;
-            for (int k = 0; k < 2; k++) {
-                if (k && l >= 8) break;
-                int which, nxy, x4, y4, cx, cy;
-                if (!k) { which = pos; nxy = mb_xy; x4 = l & 3; y4 = l >> 2; cx = x4; cy = y4; }
-                else if (l < 4) { which = 2 + pos; nxy = mb_xy - 1; x4 = 3; y4 = l; cx = -1; cy = y4; }
-                else { which = top_k < 0 ? pos : top_k; nxy = top_k < 0 ? mb_xy : top_xy; x4 = l - 4; y4 = 3; cx = x4; cy = -1; }
-                if (k && l < 4 && !has_left) { which = pos; nxy = mb_xy; }
-                const int ci = (cy + 1) * 5 + cx + 1;
-                for (int list = 0; list < 2; list++) {
-                    s.ref[list][ci] = wide_ref_identity(s.m[which], list, x4, y4);
-                    s.mv[list][ci] = fr.mv[list] ? reinterpret_cast<const uint32_t *>(fr.mv[list])[(size_t)nxy * 16 + x4 + 4 * y4] : 0u;
-                }
-                s.nnz[ci] = (uint8_t)((s.m[which].nnz_mask >> blk_index(x4, y4)) & 1);
-            }
+            /* the left macroblock of the same position in its pair; an absent neighbour's place in the view is filled from this macroblock */
+            const int left_k = has_left ? 2 + pos : pos, above_k = top_k < 0 ? pos : top_k;
+            const int left_xy = has_left ? mb_xy - 1 : mb_xy, above_xy = top_k < 0 ? mb_xy : top_xy;
+            wide_fill_caches(s, pos, left_k, above_k, l, [&](int list, int k) {
+                const size_t i = !k ? (size_t)mb_xy * 16 + l : (l < 4 ? (size_t)left_xy * 16 + 3 + 4 * l : (size_t)above_xy * 16 + 8 + l);
+                return fr.mv[list] ? reinterpret_cast<const uint32_t *>(fr.mv[list])[i] : 0u;
+            });
         }
         MI355_WAVE_SYNC();
         if (filter) {
-            const int edge = l >> 2, i = l & 3, tk = (t >> 3) & 7;
+            const bool two_lists = fr.slices[m.slice_id].list_count == 2;
             for (int dir = 0; dir < 2; dir++) {
-                const int mask_edge = dir == 0 ? (tk == 0 ? 0 : (tk < 4 ? 3 : 1)) : (tk == 0 ? 0 : (tk == 1 ? 3 : (tk < 4 ? 1 : 3)));
-                const int edges = (mask_edge == 3 && !(m.cbp & 15)) ? 1 : 4;
-                const uint32_t par_types = MI355_MB_16x16 | (MI355_MB_8x16 >> dir);
-                const bool mask_par0 = (t & par_types) != 0;
-                const int bx = dir == 0 ? edge : i, by = dir == 0 ? i : edge;
-                const int b = (by + 1) * 5 + bx + 1, bn = b - (dir ? 5 : 1);
-                int bs = 0;
-                if (edge == 0) {
-                    const bool avail = dir == 0 ? (left_ok && !left_mixed) : (top_k >= 0 && !top_double);     /* the mixed left edge and the twice-filtered top edge: below */
-                    if (avail) {
-                        const mi355_h264_mb &mm = dir == 0 ? s.m[2 + pos] : s.m[top_k];
-                        const uint32_t tm = mm.mb_type;
-                        if ((t | tm) & MI355_MB_INTRA) bs = (!((t | tm) & 0x80u) || dir == 0) ? 4 : 3;
-                        else if (dir == 1 && ((t ^ tm) & 0x80u)) bs = (s.nnz[b] | s.nnz[bn]) ? 2 : 1;                /* frame above field or field above frame: no look at the vectors */
-                        else if (s.nnz[b] | s.nnz[bn]) bs = 2;
-                        else if (mask_par0 && (tm & par_types)) bs = wide_check_mv(s, 6, 6 - (dir ? 5 : 1), list_count, ylim);
-                        else bs = wide_check_mv(s, b, bn, list_count, ylim);
-                    }
-                } else if (edge < edges) {
-                    const bool deblock_edge = !((t & MI355_MB_8x8DCT) && (edge & 1));
-                    if (deblock_edge || (CF == 2 && dir == 1)) {
-                        if (t & MI355_MB_INTRA) bs = 3;
-                        else if (s.nnz[b] | s.nnz[bn]) bs = 2;
-                        else if (edge & mask_edge) bs = 0;
-                        else if (mask_par0) { const int b0 = dir == 0 ? 5 + edge + 1 : (edge + 1) * 5 + 1; bs = wide_check_mv(s, b0, b0 - (dir ? 5 : 1), list_count, ylim); }
-                        else bs = wide_check_mv(s, b, bn, list_count, ylim);
-                    }
-                }
-                s.bs[dir][edge][i] = (uint8_t)bs;
+                /* edge 0 here: not the mixed left edge and not the twice-filtered top edge (below) */
+                const bool edge0_on = dir == 0 ? (left_ok && !left_mixed) : (top_k >= 0 && !top_double);
+                const uint32_t tm = s.m[dir == 0 ? 2 + pos : (top_k < 0 ? pos : top_k)].mb_type;
+                s.bs[dir][l >> 2][l & 3] = (uint8_t)wide_strength<CF>(s, m, dir, l, edge0_on, tm, (!((t | tm) & 0x80u) || dir == 0) ? 4 : 3,
+                                                                      dir == 1 && ((t ^ tm) & 0x80u) != 0, ylim, two_lists);
             }
             if (l < 8) {
                 /* the left edge between pairs of different coding, :748-770: strength i pairs this macroblock's block row i >> 1 with a block of one of the
@@ -1507,8 +1452,7 @@ k_wide_deblock_mbaff(const mi355_h264_frame *frames, int nframes, int d, int max
                     const int j = cur_field ? l >> 2 : l & 1;                                     /* which macroblock of the left pair */
                     const int lrow = cur_field ? (l & 3) : 2 * pos + (l >> 2);                    /* ... and which of its block rows (column 3) */
                     const mi355_h264_mb &mn = s.m[2 + j];
-                    if ((t | mn.mb_type) & MI355_MB_INTRA) bs = 4;
-                    else bs = 1 + (int)((((m.nnz_mask >> blk_index(0, l >> 1)) | (mn.nnz_mask >> blk_index(3, lrow))) & 1) != 0);
+                    bs = wide_strength_coded(t, mn.mb_type, (((m.nnz_mask >> blk_index(0, l >> 1)) | (mn.nnz_mask >> blk_index(3, lrow))) & 1) != 0, 4);
                 }
                 s.bs8[l] = (uint8_t)bs;
                 /* the top edge of a frame macroblock under a field pair, :497-540: [field j of the pair above][column / 4] */
@@ -1516,8 +1460,7 @@ k_wide_deblock_mbaff(const mi355_h264_frame *frames, int nframes, int d, int max
                 if (top_double) {
                     const int j = l >> 2, col = l & 3;
                     const mi355_h264_mb &mn = s.m[4 + j];
-                    if ((t | mn.mb_type) & MI355_MB_INTRA) bd2 = 3;
-                    else bd2 = 1 + (int)((((m.nnz_mask >> blk_index(col, 0)) | (mn.nnz_mask >> blk_index(col, 3))) & 1) != 0);
+                    bd2 = wide_strength_coded(t, mn.mb_type, (((m.nnz_mask >> blk_index(col, 0)) | (mn.nnz_mask >> blk_index(col, 3))) & 1) != 0, 3);
                 }
                 s.bsd[l >> 2][l & 3] = (uint8_t)bd2;
             }
