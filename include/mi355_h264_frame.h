@@ -313,6 +313,14 @@ int mi355_h264_recon_inter_dev(const mi355_h264_frame *d_frames, int nframes, in
  * kernel instance that carries the tiled form of the macroblock code alone (fewer registers spilled, half the code); a picture of another layout
  * in such a launch is left untouched.  Any other mask = mi355_h264_recon_inter_dev. */
 int mi355_h264_recon_inter_layouts_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int layouts, void *stream);
+/* The run length of the tiled batch's reconstruction (MI355_LAYOUTS_TILED above): a wave walks `run` consecutive macroblocks of a row, `runs_row` runs to a
+ * row of the max_mb_width x max_mb_height grid, of equal length but for the last.  forced = 0: the rule the entry point above follows (longer runs for larger
+ * batches, 4 .. 15); forced > 0: that length, bounded by the row (what MI355_RECON_RUN = 4 .. 15 in the environment does).  Plain host arithmetic, no device.
+ * Returns 0, or -1: bad arguments, or a run of more than 16 macroblocks (a run reports its macroblocks in the two halves of one 32-bit word). */
+int mi355_h264_recon_run_plan(int nframes, int max_mb_width, int max_mb_height, int forced, int *run, int *runs_row);
+/* mi355_h264_recon_inter_layouts_dev(.., MI355_LAYOUTS_TILED, ..) with the run length named (run > 0, as `forced` above), whatever the rule would pick
+ * (tests; measurement).  Returns 0; -1 where the plan above does; -2, -3, -4 as the others. */
+int mi355_h264_recon_inter_run_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int run, void *stream);
 /* The same pass for descriptors whose `coef` arrays live in device-visible host memory (mi355_host_alloc): an inter
  * macroblock fetches its coefficient block only when its record's cbp says it has coefficients (a second, dependent round
  * of loads for those; none for the others) — over PCIe the skipped blocks are what counts.  Same results. */

@@ -305,7 +305,7 @@ k_recon_intra_all(const mi355_h264_frame *__restrict__ frames, int nframes, int 
 /* ------------------------------------------------------------------------- */
 /* host entry points                                                            */
 /* ------------------------------------------------------------------------- */
-static int recon_inter_launch(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, bool sparse, void *stream, int layouts = MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED)
+static int recon_inter_launch(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, bool sparse, void *stream, int layouts = MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED, int tiled_run = 0)
 {
     if (!mi355::bind() || !d_frames || nframes <= 0) return -1;
     /* div_magic is exact below 2^24 work items: larger batches go out as several launches */
@@ -321,7 +321,7 @@ static int recon_inter_launch(const mi355_h264_frame *d_frames, int nframes, int
             hipLaunchKernelGGL(k_recon_inter_sparse, dim3((unsigned)(8 * per_xcd)), dim3(64), 0, (hipStream_t)stream,
                                d_frames + f0, max_mb_width, max_mb_height, iw, ih, nblocks, per_xcd);
         else if (layouts == MI355_LAYOUTS_TILED) {
-            if (!mi355::recon_inter_tiled_launch(d_frames + f0, nf, max_mb_width, max_mb_height, (hipStream_t)stream)) return -4;
+            if (!mi355::recon_inter_tiled_launch(d_frames + f0, nf, max_mb_width, max_mb_height, (hipStream_t)stream, tiled_run)) return -4;
         }
         else
             hipLaunchKernelGGL(k_recon_inter, dim3((unsigned)(8 * per_xcd)), dim3(64), 0, (hipStream_t)stream,
@@ -337,6 +337,12 @@ extern "C" int mi355_h264_recon_inter_layouts_dev(const mi355_h264_frame *d_fram
 {
     if (!(layouts & (MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED))) return -1;
     return recon_inter_launch(d_frames, nframes, max_mb_width, max_mb_height, false, stream, layouts);
+}
+extern "C" int mi355_h264_recon_inter_run_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int run, void *stream)
+{
+    int r, runs_row;
+    if (run <= 0 || !mi355::recon_run_plan(nframes, max_mb_width, max_mb_height, run, &r, &runs_row)) return -1;
+    return recon_inter_launch(d_frames, nframes, max_mb_width, max_mb_height, false, stream, MI355_LAYOUTS_TILED, run);
 }
 extern "C" int mi355_h264_recon_inter_sparse_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, void *stream)
 {

@@ -63,7 +63,8 @@ __device__ __forceinline__ void st8(uint8_t *p, uint2 v, bool al)
 }
 
 /* h264_frame_tiled.hip: launches k_recon_inter_tiled and k_recon_inter_rest (the tiled-only form of the inter reconstruction); false: no scratch words */
-bool recon_inter_tiled_launch(const mi355_h264_frame *d_frames, int nframes, int max_w, int max_h, hipStream_t stream);
+bool recon_run_plan(int nframes, int max_w, int max_h, int forced, int *run, int *runs_row);
+bool recon_inter_tiled_launch(const mi355_h264_frame *d_frames, int nframes, int max_w, int max_h, hipStream_t stream, int forced_run = 0);
 /* h264_frame_rest.hip: k_recon_inter_rest over the words (one per run) k_recon_inter_tiled wrote */
 void recon_inter_rest_launch(const mi355_h264_frame *d_frames, int max_w, int max_h, int run, int runs_row, unsigned long long inv_runs, unsigned long long inv_h, int nruns,
                              const uint32_t *rest, hipStream_t stream);

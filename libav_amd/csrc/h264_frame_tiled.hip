@@ -25,18 +25,35 @@ k_recon_inter_tiled(const mi355_h264_frame *__restrict__ frames, int max_w, int 
 }  // namespace
 
 namespace mi355 {
-/* nframes pictures of a max_w x max_h grid.  The run length: long runs spread the per-wave set-up (lane constants, the run's description) over more
- * macroblocks, short ones keep a small batch's waves many enough to fill the device (256 CUs x 32 waves) */
-bool recon_inter_tiled_launch(const mi355_h264_frame *d_frames, int nframes, int max_w, int max_h, hipStream_t stream)
+/* The run length of a launch over nframes pictures of a max_w x max_h grid, and the runs to a row: the rule recon_inter_tiled_launch follows and
+ * mi355_h264_recon_run_plan reports.  Long runs spread the per-wave set-up (lane constants, the run's description) over more macroblocks, short ones
+ * keep a small batch's waves many enough to fill the device (256 CUs x 32 waves).  forced > 0 names the length instead (MI355_RECON_RUN,
+ * mi355_h264_recon_inter_run_dev); either way it is bounded by the row and the runs of a row are made equal.
+ * false: bad arguments, or a run that would hold a macroblock at i >= 16 — the run's word in `rest` has bit i and bit 16 + i for macroblock i */
+bool recon_run_plan(int nframes, int max_w, int max_h, int forced, int *run_out, int *runs_row_out)
 {
-    static const int forced = std::getenv("MI355_RECON_RUN") ? std::atoi(std::getenv("MI355_RECON_RUN")) : 0;
+    if (nframes <= 0 || max_w <= 0 || max_h <= 0 || forced < 0) return false;
     /* some forty rounds of the device's 8192 wave slots keep the last round's idle slots a few per cent of the launch; beyond that, longer runs */
     const long long mbs = (long long)nframes * max_w * max_h;
-    int run = forced > 0 ? forced : (int)(mbs / (40ll * 8192));
-    run = run < 4 ? 4 : (run > 15 ? 15 : run);
+    int run = (int)(mbs / (40ll * 8192));
+    run = forced > 0 ? forced : (run < 4 ? 4 : (run > 15 ? 15 : run));
     if (run > max_w) run = max_w;
     const int runs_row = (max_w + run - 1) / run;
     run = (max_w + runs_row - 1) / runs_row;                      /* a row's runs of equal length */
+    if (run > 16) return false;
+    *run_out = run;
+    *runs_row_out = runs_row;
+    return true;
+}
+
+/* nframes pictures of a max_w x max_h grid; forced_run > 0: that run length instead of the rule's (and of MI355_RECON_RUN's) */
+bool recon_inter_tiled_launch(const mi355_h264_frame *d_frames, int nframes, int max_w, int max_h, hipStream_t stream, int forced_run)
+{
+    /* the developer switch: 4 .. 15, as the rule's own lengths */
+    static const int env = std::getenv("MI355_RECON_RUN") ? std::atoi(std::getenv("MI355_RECON_RUN")) : 0;
+    static const int forced = env > 0 ? (env < 4 ? 4 : (env > 15 ? 15 : env)) : 0;
+    int run, runs_row;
+    if (!recon_run_plan(nframes, max_w, max_h, forced_run > 0 ? forced_run : forced, &run, &runs_row)) return false;
     const unsigned long long one = 1ull << 40;
     const long long total = (long long)nframes * max_h * runs_row;
     const int nwaves = (int)total, per_xcd = (nwaves + 7) / 8;
@@ -49,3 +66,9 @@ bool recon_inter_tiled_launch(const mi355_h264_frame *d_frames, int nframes, int
     return true;
 }
 }  // namespace mi355
+
+extern "C" int mi355_h264_recon_run_plan(int nframes, int max_mb_width, int max_mb_height, int forced, int *run, int *runs_row)
+{
+    if (!run || !runs_row) return -1;
+    return mi355::recon_run_plan(nframes, max_mb_width, max_mb_height, forced, run, runs_row) ? 0 : -1;
+}

@@ -596,7 +596,7 @@ __device__ __forceinline__ void fq_two(MbLds &s, const FqLane &k, const ResidLan
     MI355_WAVE_SYNC();
 }
 
-/* ---- the run: `run` (<= 32) consecutive macroblocks of ONE row of the launch's max_w x max_h grid per wave; runs_row = ceil(max_w / run) runs to a row.
+/* ---- the run: `run` (<= 16: bit i and bit 16 + i of the run's word in `rest` stand for its macroblock i; mi355::recon_run_plan refuses more) consecutive macroblocks of ONE row of the launch's max_w x max_h grid per wave; runs_row = ceil(max_w / run) runs to a row.
  * Wave w works on run w % runs_row of row w / runs_row of the launch (row = picture * max_h + mb_y). ---- */
 __device__ __forceinline__ void recon_inter_run(MbLds &s, const mi355_h264_frame *__restrict__ frames, int max_w, int max_h, int run, int runs_row,
                                                 unsigned long long inv_runs, unsigned long long inv_h, int nwaves, int per_xcd, uint32_t *__restrict__ rest)
