@@ -308,6 +308,11 @@ int mi355_h264_recon_intra_levels_dev(const mi355_h264_frame *d_frames, int nfra
  * the stream) instead of all pictures waiting for a level's slowest wave at a launch boundary.  The records must hold what mi355_h264_intra_schedule() saw
  * (mb_type) and the list its order.  MI355_INTRA_SINGLE=0 in the environment: the launch per level of mi355_h264_recon_intra_levels_dev. */
 int mi355_h264_recon_intra_all_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int max_intra_level, const int32_t *level_widths, void *stream);
+/* Which form the entry point above takes for a batch: *single = 1, the one launch, with *per_picture workgroups a picture (the sum of level_widths, bounded by the
+ * grid; 0: nothing is launched), or *single = 0, the launch per level of mi355_h264_recon_intra_levels_dev.  The rule: the single launch from 16 levels on.
+ * pinned < 0: as the entry point decides in this process (MI355_INTRA_SINGLE, read once, pins a form); pinned 0 / 1: as if that form were pinned.
+ * Plain host arithmetic, no device.  Returns 0, or -1 (arguments). */
+int mi355_h264_recon_intra_plan(int max_mb_width, int max_mb_height, int max_intra_level, const int32_t *level_widths, int pinned, int *single, long long *per_picture);
 int mi355_h264_recon_inter_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, void *stream);
 /* The same for a caller that knows which surface layouts occur in the batch (MI355_LAYOUTS_*, below): a batch that is tiled throughout runs the
  * kernel instance that carries the tiled form of the macroblock code alone (fewer registers spilled, half the code); a picture of another layout

@@ -359,17 +359,41 @@ extern "C" int mi355_h264_recon_intra_dev(const mi355_h264_frame *d_frames, int 
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+/* The launch form of the intra pass, decided in one place: false = a launch per level (mi355_h264_recon_intra_levels_dev), true = the single launch (k_recon_intra_all)
+ * with *per_picture workgroups a picture — the sum of the level widths (maxima over the batch: a picture has at most that many intra macroblocks), bounded by the grid;
+ * 0 = nothing to launch.  pinned 0 / 1 names a form, anything else leaves it to the rule: at least INTRA_SINGLE_LEVELS levels. */
+static bool recon_intra_plan(int max_mb_width, int max_mb_height, int max_intra_level, const int32_t *level_widths, int pinned, long long *per_picture)
+{
+    *per_picture = 0;
+    if (pinned == 0 || (pinned != 1 && max_intra_level < INTRA_SINGLE_LEVELS)) return false;
+    long long sum = 0;
+    for (int level = 1; level <= max_intra_level; level++) sum += level_widths[level - 1] > 0 ? level_widths[level - 1] : 0;
+    const long long nmb = (long long)max_mb_width * max_mb_height;
+    *per_picture = sum > nmb ? nmb : sum;
+    return true;
+}
+/* MI355_INTRA_SINGLE = 0 / 1 in the environment pins the form; read once */
+static int intra_single_pin()
+{
+    static const int single = std::getenv("MI355_INTRA_SINGLE") ? std::atoi(std::getenv("MI355_INTRA_SINGLE")) : -1;
+    return single;
+}
+extern "C" int mi355_h264_recon_intra_plan(int max_mb_width, int max_mb_height, int max_intra_level, const int32_t *level_widths, int pinned, int *single, long long *per_picture)
+{
+    if (max_mb_width <= 0 || max_mb_height <= 0 || max_intra_level < 0 || (max_intra_level > 0 && !level_widths) || !single || !per_picture) return -1;
+    *single = recon_intra_plan(max_mb_width, max_mb_height, max_intra_level, level_widths, pinned < 0 ? intra_single_pin() : pinned, per_picture) ? 1 : 0;
+    return 0;
+}
+
 /* the intra pass of a batch whose grid the caller knows (max_mb_width x max_mb_height macroblocks per picture at most): ONE launch, k_recon_intra_all */
 extern "C" int mi355_h264_recon_intra_all_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int max_intra_level, const int32_t *level_widths, void *stream)
 {
     if (!mi355::bind() || !d_frames || nframes <= 0 || max_mb_width <= 0 || max_mb_height <= 0 || (max_intra_level > 0 && !level_widths)) return -1;
-    static const int single = std::getenv("MI355_INTRA_SINGLE") ? std::atoi(std::getenv("MI355_INTRA_SINGLE")) : -1;     /* 0 / 1 pins the form */
-    if (single == 0 || (single != 1 && max_intra_level < INTRA_SINGLE_LEVELS)) return mi355_h264_recon_intra_levels_dev(d_frames, nframes, max_intra_level, level_widths, stream);
-    long long per_picture = 0;                           /* a picture has at most the sum of the level widths intra macroblocks (the widths are maxima over the batch) */
-    for (int level = 1; level <= max_intra_level; level++) per_picture += level_widths[level - 1] > 0 ? level_widths[level - 1] : 0;
+    long long per_picture = 0;
+    if (!recon_intra_plan(max_mb_width, max_mb_height, max_intra_level, level_widths, intra_single_pin(), &per_picture))
+        return mi355_h264_recon_intra_levels_dev(d_frames, nframes, max_intra_level, level_widths, stream);
     if (per_picture <= 0) return 0;
     const long long nmb = (long long)max_mb_width * max_mb_height;
-    if (per_picture > nmb) per_picture = nmb;
     if ((long long)nframes * per_picture > 0x7FFFFFFFLL || (long long)nframes * nmb > 0x7FFFFFFFLL) return -3;
     const size_t bytes = ((size_t)nframes * (size_t)nmb + 3) & ~(size_t)3;
     uint32_t *flags = mi355::sync_words((hipStream_t)stream, bytes / 4);

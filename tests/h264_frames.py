@@ -628,6 +628,15 @@ def host_frames(fs, recon, dst, px=1, mb=None, coef=None, refs=None):
     return arr, keep
 
 
+def native_depth(fs, bit_depth, idc):
+    """A set built AT a depth above 8 bits (fs.native = (bit_depth, chroma_format_idc)): fs.refs are uint16 planes of that depth (4:2:2: chroma planes of the luma's
+    height) and fs.pcm_samples[f, m] holds an I_PCM macroblock's samples one per coefficient slot (Y, Cb, Cr: 384, or 512 at 4:2:2) — uploaded and handed to the
+    checker as they are, so the samples reach the depth's own maximum; records and the other coefficients are widened as for every set.  Such a set has one format only."""
+    nat = getattr(fs, "native", None)
+    assert nat is None or nat == (bit_depth, idc), (nat, bit_depth, idc)
+    return nat is not None
+
+
 def widen_samples(a, sh):
     """an 8-bit plane as DeviceFrames(bit_depth=8 + sh) uploads it: shifted up, the low bits filled from the sample's position"""
     lo = (np.arange(a.shape[1], dtype=np.uint16)[None, :] * 3 + np.arange(a.shape[0], dtype=np.uint16)[:, None] * 5) & ((1 << sh) - 1)
@@ -661,6 +670,7 @@ def widen_records(fs, sh, idc=1):
     mb = fs.mb.copy()
     mb["qp"] += 6 * sh
     mb["qpc"] += 6 * sh
+    native = native_depth(fs, 8 + sh, idc)
     off = getattr(fs, "chroma_offset", None)
     if sh and off is not None and off.any():
         # a chroma_qp_index_offset: above 8 bits qp + offset clips at -QpBdOffsetC, not at 0 (Table 8-15 is the identity below 30), so where
@@ -673,10 +683,12 @@ def widen_records(fs, sh, idc=1):
     pcm = (fs.mb["mb_type"] & 4) != 0
     if idc == 1:
         coef = fs.coef.astype(np.int32) << sh
-        coef[pcm] = fs.coef[pcm].view(np.uint8)[:, :384].astype(np.int32) << sh
+        coef[pcm] = fs.pcm_samples[pcm] if native else fs.coef[pcm].view(np.uint8)[:, :384].astype(np.int32) << sh
         return mb, np.ascontiguousarray(coef)
     coef = coefs_422(fs.coef.astype(np.int32)) << sh
-    if pcm.any():
+    if pcm.any() and native:
+        coef[pcm] = fs.pcm_samples[pcm]
+    elif pcm.any():
         b = fs.coef[pcm].view(np.uint8)[:, :384].astype(np.int32)
         coef[pcm] = np.concatenate([b[:, :256], b[:, 256:320], b[:, 320:384], b[:, 320:384], b[:, 256:320][:, ::-1]], axis=1) << sh
     dc_cb, dc_cr = (coef[..., 256:384:16] != 0).any(axis=-1), (coef[..., 384:512:16] != 0).any(axis=-1)
@@ -710,7 +722,10 @@ def run_oracle_hbd(oracle, fs, bit_depth, deblock=True, idc=1):
     assert lib.oracle_h264frame_hbd_bind_cf(*fns, bit_depth, idc) == 0
     mb, coef = widen_records(fs, sh, idc)
     c422 = chroma_422 if idc == 2 else (lambda a: a)
-    refs = [[tuple(widen_samples(pl if i == 0 else c422(pl), sh) for i, pl in enumerate(fs.refs[f][s_])) for s_ in range(fs.nrefs)] for f in range(fs.F)]
+    if native_depth(fs, bit_depth, idc):
+        refs = [[tuple(np.ascontiguousarray(pl, np.uint16) for pl in fs.refs[f][s_]) for s_ in range(fs.nrefs)] for f in range(fs.F)]
+    else:
+        refs = [[tuple(widen_samples(pl if i == 0 else c422(pl), sh) for i, pl in enumerate(fs.refs[f][s_])) for s_ in range(fs.nrefs)] for f in range(fs.F)]
     hc = fs.H if idc == 2 else fs.H // 2
     recon = [np.zeros((fs.F, fs.H, fs.W), np.uint16), np.zeros((fs.F, hc, fs.W // 2), np.uint16), np.zeros((fs.F, hc, fs.W // 2), np.uint16)]
     dst = [np.zeros_like(a) for a in recon]
@@ -810,7 +825,9 @@ class DeviceFrames:
                     refs_host[f, s_, :ysz].reshape(fs.mb_h, ys)[:, :fs.mb_w * 256] = ty.reshape(fs.mb_h, -1)
                     refs_host[f, s_, ysz:].reshape(fs.mb_h, cs)[:, :fs.mb_w * 128] = tc.reshape(fs.mb_h, -1)
                     continue
-                if px == 2:
+                if px == 2 and native_depth(fs, bit_depth, idc):
+                    y, cb, cr = (np.ascontiguousarray(a, np.uint16).view(np.uint8).reshape(a.shape[0], -1) for a in (y, cb, cr))
+                elif px == 2:
                     def wide(a):
                         return widen_samples(a, sh).view(np.uint8).reshape(a.shape[0], -1)
                     if idc == 2:
@@ -982,6 +999,36 @@ class DeviceFrames:
         assert rc == 0, rc
         if sync:
             assert lib.mi355_sync(None) == 0
+
+    def intra_plan(self, pinned=-1):
+        """mi355_h264_recon_intra_plan for this batch -> (single, workgroups per picture)"""
+        fs, fn = self.fs, self.lib.mi355_h264_recon_intra_plan
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lw = (C.c_int32 * max(1, fs.max_intra_level))(*fs.level_widths[:fs.max_intra_level])
+        single, per = C.c_int(-1), C.c_longlong(-1)
+        assert fn(fs.mb_w, fs.mb_h, fs.max_intra_level, lw, pinned, C.byref(single), C.byref(per)) == 0
+        return single.value, per.value
+
+    def decode_intra_form(self, single):
+        """the three passes of the first kernel set with the intra pass's launch form named: the inter pass and the loop filter of the batch's layout, between them
+        mi355_h264_recon_intra_levels_dev (a launch per level) or mi355_h264_recon_intra_all_dev — which must then take the single launch (mi355_h264_recon_intra_plan)"""
+        fs, lib = self.fs, self.lib
+        lw = (C.c_int32 * max(1, fs.max_intra_level))(*fs.level_widths[:fs.max_intra_level])
+        mask = 2 if self.tiled else 1
+        if single:
+            plan = self.intra_plan()
+            assert plan[0] == 1 and plan[1] > 0, "the batch does not take the single launch: plan %s, %d levels" % (plan, fs.max_intra_level)
+            intra = ("mi355_h264_recon_intra_all_dev", (fs.mb_w, fs.mb_h, fs.max_intra_level, lw))
+        else:
+            intra = ("mi355_h264_recon_intra_levels_dev", (fs.max_intra_level, lw))
+        for name, args in (("mi355_h264_recon_inter_layouts_dev", (fs.mb_w, fs.mb_h, mask)), intra, ("mi355_h264_deblock_layouts_dev", (fs.mb_w, fs.mb_h, mask))):
+            fn = getattr(lib, name)
+            fn.restype = C.c_int
+            fn.argtypes = [C.c_void_p, C.c_int] + [C.c_int if isinstance(a, int) else C.c_void_p for a in args] + [C.c_void_p]
+            assert fn(self.d_desc, self.F, *args, None) == 0, name
+        lib.mi355_sync.restype = C.c_int
+        assert lib.mi355_sync(None) == 0
 
     def decode_sparse(self, poison=True):
         """the three passes with mi355_h264_recon_inter_sparse_dev: inter macroblocks whose cbp is zero do not fetch their
