@@ -88,6 +88,7 @@ template <int OFF> static inline void fq_dma4(const uint8_t *src, MbLds &s, int 
 static inline void fq_wait_vm0() {}
 static inline void fq_wait_vm2() {}
 static inline int fq_med3_0(int x, int hi) { return x < 0 ? 0 : (x > hi ? hi : x); }
+static inline bool fq_lane_in(uint64_t lanes) { return ((lanes >> (threadIdx.x & 63)) & 1) != 0; }
 typedef const uint32_t *fq_kptr;
 static inline fq_kptr fq_konst(const void *p) { return reinterpret_cast<const uint32_t *>(p); }
 struct fq_ptr2 { uint32_t w[4]; uint32_t operator[](int i) const { return w[i]; } };
@@ -122,6 +123,10 @@ template <int OFF> __device__ __forceinline__ void fq_dma4(const uint8_t *src, M
 __device__ __forceinline__ void fq_wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void fq_wait_vm2() { asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
 __device__ __forceinline__ int fq_med3_0(int x, int hi) { int r; asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(x), "s"(hi)); return r; }      /* clamp to 0 .. hi (a wave constant) */
+/* this lane's bit of a wave-uniform lane set: the set goes into EXEC as it is (s_and_saveexec), no vector instruction.  Around a request (which the compiler
+ * takes for a store: it writes LDS) `if (fq_lane_in(set))` compiles to s_and_saveexec_b64, s_cbranch_execz over the block, the request and what address
+ * arithmetic the compiler sank in with it, s_or_b64 exec: a scalar branch the source does not show.  It is taken only by an empty set (see fq_need). */
+__device__ __forceinline__ bool fq_lane_in(uint64_t lanes) { return __builtin_amdgcn_inverse_ballot_w64(lanes); }
 /* a wave-uniform address read through the scalar cache: the record's words arrive in scalar registers, no LDS read, no v_readfirstlane */
 typedef const __attribute__((address_space(4))) uint32_t *fq_kptr;
 __device__ __forceinline__ fq_kptr fq_konst(const void *p) { return (fq_kptr)(unsigned long long)p; }
@@ -341,10 +346,48 @@ __device__ __forceinline__ void fq_idct(MbLds &s, const FqLane &k, const ResidLa
 }
 
 /* ---- the windows ---- */
+/* What of the 21 rows x 3 tile columns of a luma window the prediction at a position reads (fq_luma_pred, case by case), as the set of lanes whose piece
+ * (lane 3 r + t: row r, tile column t) is requested.  With o = (ix - 4) & 15 the window's first column is picture column ix - 4 - o:
+ *   columns  a horizontal filter (mx & 3: hband, the filtered transposition, and the 2-D cases' b beside an unfiltered one) multiplies columns o + 2 .. o + 22
+ *            by its taps; without one (cases 0, 4, 8, 12: gsamples(., 0) and the identity transposition at dx = 0) columns o + 4 .. o + 19 reach a sample.
+ *            What a product operand or an aligned dword read covers beyond that meets a zero tap or is shifted out.
+ *   rows     a vertical filter (my & 3: every transposition) reads rows 0 .. 20; without one (cases 0 .. 3: gsamples(0, .), hband(2)) rows 2 .. 17.
+ * A case that needs the wide columns for b on rows 2 .. 18 only and the narrow ones above and below (5, 7, 13, 15) gets the wide ones on every row: the
+ * tile set is one per macroblock.  Tile column 1 holds columns 16 .. 31, and o + 4 <= 19, o + 19 >= 19: it is in every set, so a request never goes out
+ * with no lane (the turn's wait counts it): the branch over an empty set that the compiler puts around a request (fq_lane_in) is never taken, the request
+ * is issued every turn and vmcnt(2) stays exact.  Lane 63 is in no set (it used to fetch piece 62 again, into bytes 1008 .. 1023 of the window): those
+ * sixteen bytes are now never written and hold what the LDS held at launch.  The operand reads of rows 16 .. 20 may cover them up to byte 1012 (the
+ * static_assert at FQ_WSTEP); there they meet zero taps in integer products only — any byte value times zero — so no stored sample sees them.
+ * Scalar code on word a (bits 0-4 o + 2, bits 7-10 the position). */
+constexpr uint64_t FQ_ROWS_ALL = 0x1249249249249249ull;                               /* bit 3 r, r = 0 .. 20: tile column 0 of every window row */
+constexpr uint64_t FQ_ROWS_MID = FQ_ROWS_ALL & ((1ull << 54) - 1) & ~((1ull << 6) - 1);  /* ... of rows 2 .. 17 */
+constexpr uint64_t fq_need(uint32_t a)
+{
+    const uint32_t o2 = a & 31u;
+    const bool hf = ((a >> 7) & 3u) != 0, vf = ((a >> 9) & 3u) != 0;
+    const uint32_t first = hf ? o2 : o2 + 2, last = hf ? o2 + 20 : o2 + 17;
+    const uint64_t rows = vf ? FQ_ROWS_ALL : FQ_ROWS_MID;
+    return (first < 16 ? rows : 0ull) | (rows << 1) | (last >= 32 ? rows << 2 : 0ull);
+}
+constexpr bool fq_need_table_ok()
+{
+    for (uint32_t pos = 0; pos < 16; pos++)
+        for (uint32_t o = 0; o < 16; o++) {
+            const uint64_t n = fq_need((o + 2) | (pos << 7));
+            const bool vf = (pos >> 2) != 0;
+            if ((n >> 63) != 0) return false;                                           /* lane 63 has no piece of its own */
+            for (int r = 0; r < 21; r++) {
+                const uint32_t t = (uint32_t)(n >> (3 * r)) & 7u;
+                if (r >= 2 && r <= 17 ? !(t & 2u) : t != (vf ? (uint32_t)(n >> 6) & 7u : 0u)) return false;     /* tile column 1 in every set; one tile set on all rows requested */
+            }
+        }
+    return true;
+}
+static_assert(fq_need_table_ok(), "every luma window request has lanes: tile column 1 of rows 2 .. 17 is in every set");
 /* issue both fetches of a macroblock (first luma row y0 = iy - 2, first luma tile column t0, first chroma row cy, first chroma column c0 = cx & ~3) into window
  * set `woff`: rows clamped to the picture here, columns fetched from the clamped tile and replicated later (fq_windows_patch).  mc_dir_part's addressing
  * (h264_mb.c:204-318) */
-__device__ __forceinline__ void fq_windows_issue(MbLds &s, const FqLane &k, const mi355_h264_frame *desc, const FrameHot &fr, int slot, int y0, int t0, int cy, int c0, int woff)
+__device__ __forceinline__ void fq_windows_issue(MbLds &s, const FqLane &k, const mi355_h264_frame *desc, const FrameHot &fr, int slot, int y0, int t0, int cy, int c0, int woff, uint64_t need)
 {
     fq_kptr rp = fq_konst(desc->ref[slot]);
     const uint8_t *ry = mi355_global(reinterpret_cast<const uint8_t *>((unsigned long long)rp[0] | ((unsigned long long)rp[1] << 32)));
@@ -353,7 +396,8 @@ __device__ __forceinline__ void fq_windows_issue(MbLds &s, const FqLane &k, cons
     {
         const int y = fq_med3_0(y0 + k.fr, hpix - 1);
         const int tx = fq_med3_0(t0 + (k.fp256 >> 8), mbw - 1);
-        fq_dma16<FQ_WY>(ry + (uint32_t)(__mul24(y >> 4, fr.ref_stride[0]) + tx * 256 + (y & 15) * 16), s, woff);
+        /* the lanes of fq_need only: a clamped row or tile column lands in the place of the row / column it stands for, so the set is the unclamped one */
+        if (fq_lane_in(need)) fq_dma16<FQ_WY>(ry + (uint32_t)(__mul24(y >> 4, fr.ref_stride[0]) + tx * 256 + (y & 15) * 16), s, woff);
     }
     {
         const int y = fq_med3_0(cy + k.crow, hc - 1);
@@ -364,8 +408,10 @@ __device__ __forceinline__ void fq_windows_issue(MbLds &s, const FqLane &k, cons
     }
 }
 /* the same for windows that lie inside the picture (FQA_INSIDE: nine macroblocks of ten in a 1080p picture with vectors of +-16 samples): no clamps, the
- * window's first tile in the scalar base, twelve vector instructions for the two addresses instead of twenty-five */
-__device__ __forceinline__ void fq_windows_issue_inside(MbLds &s, const FqLane &k, const mi355_h264_frame *desc, const FrameHot &fr, int slot, int y0, int t0, int cy, int c0, int woff)
+ * window's first tile in the scalar base, twelve vector instructions for the two addresses instead of twenty-five.  The luma request goes out for the lanes
+ * of `need` (fq_need) alone: whole tile columns and, where the rows left out lie in another half of their tile, whole 128-byte lines drop out of it.  It stays
+ * ONE load instruction with lanes in it — the turn's wait counts it.  What a lane left out would have fetched keeps whatever an earlier macroblock left there. */
+__device__ __forceinline__ void fq_windows_issue_inside(MbLds &s, const FqLane &k, const mi355_h264_frame *desc, const FrameHot &fr, int slot, int y0, int t0, int cy, int c0, int woff, uint64_t need)
 {
     /* both plane pointers in ONE scalar load (as two loads the second took the first's registers and waited behind the luma request) */
     const fq_ptr2 rp = *fq_konst2(desc->ref[slot]);
@@ -373,7 +419,7 @@ __device__ __forceinline__ void fq_windows_issue_inside(MbLds &s, const FqLane &
     const uint8_t *rc = mi355_global(reinterpret_cast<const uint8_t *>((unsigned long long)rp[2] | ((unsigned long long)rp[3] << 32)));
     {
         const uint32_t y = (uint32_t)(y0 + k.fr);
-        fq_dma16<FQ_WY>(ry + (uint32_t)(t0 * 256) + (uint32_t)(__umul24(y >> 4, (uint32_t)fr.ref_stride[0]) + (((y & 15u) << 4) + (uint32_t)k.fp256)), s, woff);
+        if (fq_lane_in(need)) fq_dma16<FQ_WY>(ry + (uint32_t)(t0 * 256) + (uint32_t)(__umul24(y >> 4, (uint32_t)fr.ref_stride[0]) + (((y & 15u) << 4) + (uint32_t)k.fp256)), s, woff);
     }
     {
         const uint32_t y = (uint32_t)(cy + k.crow);
@@ -381,12 +427,13 @@ __device__ __forceinline__ void fq_windows_issue_inside(MbLds &s, const FqLane &
         fq_dma4<FQ_WC>(rc + (uint32_t)((c0 >> 3) * 128) + (uint32_t)(__umul24(y >> 3, (uint32_t)fr.ref_stride[1]) + (((y & 7u) << 3) + x)), s, woff);
     }
 }
-/* columns left / right of the picture: the edge column's sample over the whole piece.  Each lane mends the piece it fetched. */
-__device__ __forceinline__ void fq_windows_patch(MbLds &s, const FqLane &k, bool patch_y, bool patch_c, int t0, int c0, int woff, int mbw)
+/* columns left / right of the picture: the edge column's sample over the whole piece.  Each lane mends the piece it fetched, and only that: a luma piece
+ * left out of the request (need: fq_need of the same word) is neither read nor written. */
+__device__ __forceinline__ void fq_windows_patch(MbLds &s, const FqLane &k, bool patch_y, bool patch_c, int t0, int c0, int woff, int mbw, uint64_t need)
 {
     uint8_t *const base = reinterpret_cast<uint8_t *>(&s) + woff;
     const int lane = lane_id();
-    if (patch_y && lane < 63) {
+    if (patch_y && fq_lane_in(need)) {
         const int t = t0 + (k.fp256 >> 8);
         if (t < 0 || t >= mbw) {
             uint8_t *p = base + FQ_WY + 16 * lane;
@@ -562,8 +609,9 @@ __device__ __forceinline__ void fq_two(MbLds &s, const FqLane &k, const ResidLan
     const FqGeo g1 = fq_geometry(mv[n1], mb_x, mb_y, (int8_t)((w14 >> q1) & 0xFFu), (w12 >> q1) & 0xFFu, pic.hot.mb_width, pic.hot.mb_height);
     const int set0 = woff, set1 = woff ^ FQ_WSTEP;
     auto issue = [&](const FqGeo &g, int set) {
-        if (g.a & FQA_INSIDE) fq_windows_issue_inside(s, k, pic.desc, pic.hot, (int)((g.a >> 17) & 31u), (int16_t)(g.d & 0xFFFFu), (int16_t)(g.e & 0xFFFFu), (int)g.d >> 16, (int)g.e >> 16, set);
-        else fq_windows_issue(s, k, pic.desc, pic.hot, (int)((g.a >> 17) & 31u), (int16_t)(g.d & 0xFFFFu), (int16_t)(g.e & 0xFFFFu), (int)g.d >> 16, (int)g.e >> 16, set);
+        const uint64_t need = fq_need(g.a);            /* the partition's own position: its vector is applied to the whole macroblock */
+        if (g.a & FQA_INSIDE) fq_windows_issue_inside(s, k, pic.desc, pic.hot, (int)((g.a >> 17) & 31u), (int16_t)(g.d & 0xFFFFu), (int16_t)(g.e & 0xFFFFu), (int)g.d >> 16, (int)g.e >> 16, set, need);
+        else fq_windows_issue(s, k, pic.desc, pic.hot, (int)((g.a >> 17) & 31u), (int16_t)(g.d & 0xFFFFu), (int16_t)(g.e & 0xFFFFu), (int)g.d >> 16, (int)g.e >> 16, set, need);
     };
     issue(g0, set0);
     issue(g1, set1);
@@ -572,8 +620,8 @@ __device__ __forceinline__ void fq_two(MbLds &s, const FqLane &k, const ResidLan
     MI355_WAVE_SYNC();
     if (resid) fq_idct(s, k, rl, nnz, has_chroma, pic.mb + mb_xy);
     if ((g0.a | g1.a) & (FQA_PATCH_Y | FQA_PATCH_C)) {
-        fq_windows_patch(s, k, (g0.a & FQA_PATCH_Y) != 0, (g0.a & FQA_PATCH_C) != 0, (int16_t)(g0.e & 0xFFFFu), (int)g0.e >> 16, set0, pic.hot.mb_width);
-        fq_windows_patch(s, k, (g1.a & FQA_PATCH_Y) != 0, (g1.a & FQA_PATCH_C) != 0, (int16_t)(g1.e & 0xFFFFu), (int)g1.e >> 16, set1, pic.hot.mb_width);
+        fq_windows_patch(s, k, (g0.a & FQA_PATCH_Y) != 0, (g0.a & FQA_PATCH_C) != 0, (int16_t)(g0.e & 0xFFFFu), (int)g0.e >> 16, set0, pic.hot.mb_width, fq_need(g0.a));
+        fq_windows_patch(s, k, (g1.a & FQA_PATCH_Y) != 0, (g1.a & FQA_PATCH_C) != 0, (int16_t)(g1.e & 0xFFFFu), (int)g1.e >> 16, set1, pic.hot.mb_width, fq_need(g1.a));
     }
     MI355_WAVE_SYNC();
     const int lane = lane_id();
@@ -644,8 +692,9 @@ __device__ __forceinline__ void recon_inter_run(MbLds &s, const mi355_h264_frame
             if (a & FQA_FAST) {
                 auto issue = [&](int m, uint32_t am, int set) {
                     const uint32_t d = fq_lane_word(rd, m), e = fq_lane_word(re, m);
-                    if (am & FQA_INSIDE) fq_windows_issue_inside(s, k, pic.desc, pic.hot, (int)((am >> 17) & 31u), (int16_t)(d & 0xFFFFu), (int16_t)(e & 0xFFFFu), (int)d >> 16, (int)e >> 16, set);
-                    else fq_windows_issue(s, k, pic.desc, pic.hot, (int)((am >> 17) & 31u), (int16_t)(d & 0xFFFFu), (int16_t)(e & 0xFFFFu), (int)d >> 16, (int)e >> 16, set);
+                    const uint64_t need = fq_need(am);
+                    if (am & FQA_INSIDE) fq_windows_issue_inside(s, k, pic.desc, pic.hot, (int)((am >> 17) & 31u), (int16_t)(d & 0xFFFFu), (int16_t)(e & 0xFFFFu), (int)d >> 16, (int)e >> 16, set, need);
+                    else fq_windows_issue(s, k, pic.desc, pic.hot, (int)((am >> 17) & 31u), (int16_t)(d & 0xFFFFu), (int16_t)(e & 0xFFFFu), (int)d >> 16, (int)e >> 16, set, need);
                 };
                 FQ_MARK("issue");
                 if (!pre_w) issue(i, a, woff);
@@ -665,7 +714,7 @@ __device__ __forceinline__ void recon_inter_run(MbLds &s, const mi355_h264_frame
                 if (next_c) fq_coef_dma(s, k, pic.coef, mb_xy0 + i + 1);
                 if (a & (FQA_PATCH_Y | FQA_PATCH_C)) {
                     const uint32_t e = fq_lane_word(re, i);
-                    fq_windows_patch(s, k, (a & FQA_PATCH_Y) != 0, (a & FQA_PATCH_C) != 0, (int16_t)(e & 0xFFFFu), (int)e >> 16, woff, pic.hot.mb_width);
+                    fq_windows_patch(s, k, (a & FQA_PATCH_Y) != 0, (a & FQA_PATCH_C) != 0, (int16_t)(e & 0xFFFFu), (int)e >> 16, woff, pic.hot.mb_width, fq_need(a));
                     MI355_WAVE_SYNC();
                 }
                 FQ_MARK("luma");
