@@ -114,6 +114,36 @@ __global__ void __launch_bounds__(64) k_hevc_pred_batch(const mi355_hevc_pred_jo
     }
 }
 
+/* ---- records read once, a dword per lane: the fields are scalars from there (v_readlane).  A record is not known to be read-only to the compiler (the kernels
+ * store through other pointers), so read field by field every use of a field is a vector load and a wait in front of whatever needed it — 20-40 dependent round
+ * trips per wave of k_hevc_sao_ctbs before its first sample was requested (profiles/r06_experiments.md) */
+template <class T> __device__ __forceinline__ int rec_fetch(const T *r, int lane)
+{
+    static_assert(sizeof(T) % 4 == 0 && sizeof(T) / 4 <= 64, "a record is read by dword index, one wave's worth at most");
+    constexpr int N = (int)(sizeof(T) / 4);
+    return (int)mi355_global_v(reinterpret_cast<const uint32_t *>(r))[lane < N ? lane : N - 1];
+}
+__device__ __forceinline__ uint32_t rec_dw(int rec, int dw) { return (uint32_t)lane_value(rec, dw); }
+template <class T> __device__ __forceinline__ T *rec_ptr(int rec, int dw)      /* a pointer from dwords dw, dw + 1 */
+{
+    return reinterpret_cast<T *>((uintptr_t)rec_dw(rec, dw) | ((uintptr_t)rec_dw(rec, dw + 1) << 32));
+}
+__device__ __forceinline__ mi355_hevc_lf_picture lf_picture_of(int rec)
+{
+    constexpr int N = (int)(sizeof(mi355_hevc_lf_picture) / 4);
+    mi355_hevc_lf_picture p;
+    uint32_t wds[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) wds[k] = rec_dw(rec, k);
+    __builtin_memcpy(&p, wds, sizeof(p));
+    return p;
+}
+/* the workgroups of a launch go to the eight XCDs in turn: XCD k takes the k-th eighth of the blocks, i.e. neighbouring blocks share an L2 */
+__device__ __forceinline__ int xcd_ordered(int block, int nblocks)
+{
+    return (nblocks & 7) ? block : (block & 7) * (nblocks >> 3) + (block >> 3);
+}
+
 /* ---- deblocking: eight jobs per wavefront --------------------------------------------------------------- */
 __global__ void __launch_bounds__(64) k_hevc_deblock_batch(const mi355_hevc_lf_job *jobs, int n, int bd)
 {
@@ -175,6 +205,56 @@ __device__ __forceinline__ int hevc_tc_calc(int qp, int bs, int tc_offset)
 {
     return k_hevc_tctable[clip3(qp + 2 * (bs - 1) + (tc_offset >> 1 << 1), 0, 53)];
 }
+/* The two strengths of the segment whose first q-side sample is (x, y) (luma coordinates; DIR 0: a vertical edge, 1: a horizontal one), 0 where the picture has no
+ * such edge.  Luma: the 8x8 grid, halves of 4; it filters where a strength is not 0.  Chroma: the 16-luma-sample grid, halves of 8 luma samples; it filters where a
+ * strength is 2.  The reference's pairs of horizontal chroma segments start at x = 8 (mod 16), i.e. at -8 (hevc_filter.c:469-484): a half outside the picture has bS 0. */
+template <int DIR>
+__device__ __forceinline__ void lf_luma_strengths(const mi355_hevc_lf_picture &p, int x, int y, int &bs0, int &bs1)
+{
+    bs0 = bs1 = 0;
+    if (!(x >= 0 && y >= 0 && x < p.width && y < p.height && (DIR ? y >= 8 : x >= 8))) return;
+    if (DIR) { bs0 = mi355_global_v(p.horizontal_bs)[(x + y * p.bs_width) >> 2]; bs1 = mi355_global_v(p.horizontal_bs)[(x + 4 + y * p.bs_width) >> 2]; }
+    else { bs0 = mi355_global_v(p.vertical_bs)[(x >> 3) + (y >> 2) * p.bs_width]; bs1 = mi355_global_v(p.vertical_bs)[(x >> 3) + ((y + 4) >> 2) * p.bs_width]; }
+}
+template <int DIR>
+__device__ __forceinline__ void lf_chroma_strengths(const mi355_hevc_lf_picture &p, int x, int y, int &bs0, int &bs1)
+{
+    bs0 = bs1 = 0;
+    if (!(y >= 0 && x < p.width && y < p.height && (DIR ? y >= 16 : x >= 16))) return;
+    if (DIR) {
+        bs0 = x < 0 ? 0 : mi355_global_v(p.horizontal_bs)[(x + y * p.bs_width) >> 2];
+        bs1 = x + 8 >= p.width ? 0 : mi355_global_v(p.horizontal_bs)[(x + 8 + y * p.bs_width) >> 2];
+    } else {
+        bs0 = mi355_global_v(p.vertical_bs)[(x >> 3) + (y >> 2) * p.bs_width];
+        bs1 = mi355_global_v(p.vertical_bs)[(x >> 3) + ((y + 8) >> 2) * p.bs_width];
+    }
+}
+/* What the filter of that segment needs (plane 0: luma, 1 / 2: Cb / Cr): the QP average across the edge (get_qPy), beta / tc through the tables with the offsets of
+ * the CTB that contains the edge sample, the pcm / bypass marks (get_pcm) as bits: 0, 1 the p side of half 0, 1; 2, 3 the q side.  A luma segment has one QP; a
+ * chroma half has its own, and nothing of a half whose strength is not 2 is read (it may lie outside the picture). */
+struct LfSegParams { int beta, tc0, tc1; uint32_t nob; };
+template <int DIR>
+__device__ __forceinline__ LfSegParams lf_segment_params(const mi355_hevc_lf_picture &p, int plane, int x, int y, int bs0, int bs1)
+{
+    const LfPic P{ p };
+    const int half = plane ? 8 : 4, x1 = DIR ? x + half : x, y1 = DIR ? y : y + half;      /* half 1's first q-side sample */
+    const int dx = DIR ? 0 : 1, dy = DIR ? 1 : 0;                                          /* the p side lies at (-dx, -dy) */
+    auto qp = [&](int xh, int yh) { return (P.qpy(xh - dx, yh - dy) + P.qpy(xh, yh) + 1) >> 1; };
+    LfSegParams s = { 0, 0, 0, 0u };
+    if (plane == 0) {
+        const mi355_hevc_db_params d = P.db(x, y);
+        const int q = qp(x, y);
+        s.beta = k_hevc_betatable[clip3(q + d.beta_offset, 0, 51)];
+        s.tc0 = bs0 ? hevc_tc_calc(q, bs0, d.tc_offset) : 0;
+        s.tc1 = bs1 ? hevc_tc_calc(q, bs1, d.tc_offset) : 0;
+    } else {
+        /* (the halves of a vertical segment lie in one CTB: xh = x for both) */
+        if (bs0 == 2) s.tc0 = P.chroma_tc(qp(x, y), plane, P.db(x, y).tc_offset);
+        if (bs1 == 2) s.tc1 = P.chroma_tc(qp(x1, y1), plane, P.db(x1, y).tc_offset);
+    }
+    if (p.pcmf) s.nob = (P.pcm(x - dx, y - dy) ? 1u : 0u) | (P.pcm(x1 - dx, y1 - dy) ? 2u : 0u) | (P.pcm(x, y) ? 4u : 0u) | (P.pcm(x1, y1) ? 8u : 0u);
+    return s;
+}
 
 /* A wave looks at 64 consecutive segments of the grid (one per lane), keeps those that have something to filter (bS != 0; chroma: bS 2)
  * and filters them eight at a time, eight lanes per segment: on a picture of 32x32 blocks a quarter of the 8x8 grid's edges carry a
@@ -185,54 +265,13 @@ __global__ void __launch_bounds__(64) k_hevc_deblock_pictures(const mi355_hevc_l
                                                               int chroma_rows, int luma_waves, int waves_per_pic, int bd)
 {
     const int lane = lane_id(), slot = lane >> 3;
-#ifndef MI355_LF_NO_XCD_ORDER
-    /* the workgroups of an XCD (they go to the eight in turn) take consecutive waves' worth of segments: XCD k the k-th eighth of the launch */
-    const int nb = (int)gridDim.x, bidx = (nb & 7) ? (int)blockIdx.x : ((int)blockIdx.x & 7) * (nb >> 3) + ((int)blockIdx.x >> 3);
-#else
-    const int bidx = (int)blockIdx.x;
-#endif
+    const int bidx = xcd_ordered((int)blockIdx.x, (int)gridDim.x);
     const int pic = bidx / waves_per_pic, w = bidx - pic * waves_per_pic;
-    /* the picture's record once, a dword per lane, its fields as scalars from there (v_readlane): read field by field through `pics` every use of a field is a
-     * vector load and a wait in front of the load that needed it (the strengths' pointer, then the strength) */
     static_assert(sizeof(mi355_hevc_lf_picture) == 136, "the record is read by dword index");
-    mi355_hevc_lf_picture p;
-    {
-        const int rec = (int)mi355_global_v(reinterpret_cast<const uint32_t *>(pics + pic))[lane < 34 ? lane : 33];
-        uint32_t wds[34];
-#pragma unroll
-        for (int k = 0; k < 34; k++) wds[k] = (uint32_t)lane_value(rec, k);
-        __builtin_memcpy(&p, wds, sizeof(p));
-    }
-    const LfPic P{ p };
-    const int ps = bd > 8, W = p.width, H = p.height;
+    const mi355_hevc_lf_picture p = lf_picture_of(rec_fetch(pics + pic, lane));
+    const int ps = bd > 8;
     const bool luma = w < luma_waves;
     const int per_plane = chroma_cols * chroma_rows;
-    /* strengths of segment `seg` (luma: the 8x8 grid; chroma: plane c on the 16-luma-sample grid; horizontal chroma edges: the reference's
-     * pairs start at x = 8 (mod 16), i.e. at -8 (:469-484), a half outside the picture has bS 0) -> does it filter anything */
-    auto luma_seg = [&](int seg, int &x, int &y, int &bs0, int &bs1) {
-        const int gy = seg / luma_cols, gx = seg - gy * luma_cols;            /* (not mi355_div20: that is exact for seg * luma_cols < 2^20 only) */
-        x = 8 * gx; y = 8 * gy;
-        bs0 = bs1 = 0;
-        if (!(gy < luma_rows && x < W && y < H && (DIR ? y >= 8 : x >= 8))) return false;
-        if (DIR) { bs0 = mi355_global_v(p.horizontal_bs)[(x + y * p.bs_width) >> 2]; bs1 = mi355_global_v(p.horizontal_bs)[(x + 4 + y * p.bs_width) >> 2]; }
-        else { bs0 = mi355_global_v(p.vertical_bs)[(x >> 3) + (y >> 2) * p.bs_width]; bs1 = mi355_global_v(p.vertical_bs)[(x >> 3) + ((y + 4) >> 2) * p.bs_width]; }
-        return (bs0 | bs1) != 0;
-    };
-    auto chroma_seg = [&](int seg, int &c, int &x, int &y, int &bs0, int &bs1) {
-        c = seg >= per_plane ? 2 : 1;
-        const int s2 = seg - (c - 1) * per_plane, gy = s2 / chroma_cols, gx = s2 - gy * chroma_cols;
-        x = DIR ? 16 * gx - 8 : 16 * gx; y = 16 * gy;
-        bs0 = bs1 = 0;
-        if (!(seg < 2 * per_plane && y < H && (DIR ? (y >= 16 && x < W) : (x >= 16 && x < W)))) return false;
-        if (DIR) {
-            bs0 = x < 0 ? 0 : mi355_global_v(p.horizontal_bs)[(x + y * p.bs_width) >> 2];
-            bs1 = x + 8 >= W ? 0 : mi355_global_v(p.horizontal_bs)[(x + 8 + y * p.bs_width) >> 2];
-        } else {
-            bs0 = mi355_global_v(p.vertical_bs)[(x >> 3) + (y >> 2) * p.bs_width];
-            bs1 = mi355_global_v(p.vertical_bs)[(x >> 3) + ((y + 8) >> 2) * p.bs_width];
-        }
-        return bs0 == 2 || bs1 == 2;
-    };
     /* ---- the wave's 64 candidates: each lane works out ITS segment's parameters (QP average, beta / tc through the tables, pcm marks) — every live lane at once, one
      * chain of round trips per wave — and lists them in LDS in lane order; the groups of eight lanes then only fetch samples (before: each group derived its
      * segment's parameters itself in front of its samples' loads, a chain per round of eight segments) */
@@ -241,33 +280,25 @@ __global__ void __launch_bounds__(64) k_hevc_deblock_pictures(const mi355_hevc_l
     uint2 par = make_uint2(0u, 0u);
     bool cand;
     {
-        int c = 0, x, y, bs0, bs1;
-        cand = luma ? luma_seg(seg_base + lane, x, y, bs0, bs1) : chroma_seg(seg_base + lane, c, x, y, bs0, bs1);
+        /* segment `seg` of the wave's grid: luma the 8x8 grid, chroma plane c on the 16-luma-sample grid */
+        const int seg = seg_base + lane;
+        int c = 0, x, y, bs0 = 0, bs1 = 0;
+        if (luma) {
+            const int gy = seg / luma_cols, gx = seg - gy * luma_cols;            /* (not mi355_div20: that is exact for seg * luma_cols < 2^20 only) */
+            x = 8 * gx; y = 8 * gy;
+            if (gy < luma_rows) lf_luma_strengths<DIR>(p, x, y, bs0, bs1);
+            cand = (bs0 | bs1) != 0;
+        } else {
+            c = seg >= per_plane ? 2 : 1;
+            const int s2 = seg - (c - 1) * per_plane, gy = s2 / chroma_cols, gx = s2 - gy * chroma_cols;
+            x = DIR ? 16 * gx - 8 : 16 * gx; y = 16 * gy;
+            if (seg < 2 * per_plane) lf_chroma_strengths<DIR>(p, x, y, bs0, bs1);
+            cand = bs0 == 2 || bs1 == 2;
+        }
         if (cand) {
-            int beta = 0, tc0 = 0, tc1 = 0;
-            uint32_t nob = 0;
-            if (luma) {
-                const mi355_hevc_db_params d = P.db(x, y);
-                const int qp = (P.qpy(DIR ? x : x - 1, DIR ? y - 1 : y) + P.qpy(x, y) + 1) >> 1;
-                beta = k_hevc_betatable[clip3(qp + d.beta_offset, 0, 51)];
-                tc0 = bs0 ? hevc_tc_calc(qp, bs0, d.tc_offset) : 0;
-                tc1 = bs1 ? hevc_tc_calc(qp, bs1, d.tc_offset) : 0;
-                if (p.pcmf) {
-                    if (DIR) nob = (P.pcm(x, y - 1) ? 1u : 0u) | (P.pcm(x + 4, y - 1) ? 2u : 0u) | (P.pcm(x, y) ? 4u : 0u) | (P.pcm(x + 4, y) ? 8u : 0u);
-                    else nob = (P.pcm(x - 1, y) ? 1u : 0u) | (P.pcm(x - 1, y + 4) ? 2u : 0u) | (P.pcm(x, y) ? 4u : 0u) | (P.pcm(x, y + 4) ? 8u : 0u);
-                }
-            } else if (DIR) {
-                if (bs0 == 2) tc0 = P.chroma_tc((P.qpy(x, y - 1) + P.qpy(x, y) + 1) >> 1, c, P.db(x, y).tc_offset);
-                if (bs1 == 2) tc1 = P.chroma_tc((P.qpy(x + 8, y - 1) + P.qpy(x + 8, y) + 1) >> 1, c, P.db(x + 8, y).tc_offset);
-                if (p.pcmf) nob = (P.pcm(x, y - 1) ? 1u : 0u) | (P.pcm(x + 8, y - 1) ? 2u : 0u) | (P.pcm(x, y) ? 4u : 0u) | (P.pcm(x + 8, y) ? 8u : 0u);
-            } else {
-                const int tco = P.db(x, y).tc_offset;
-                if (bs0 == 2) tc0 = P.chroma_tc((P.qpy(x - 1, y) + P.qpy(x, y) + 1) >> 1, c, tco);
-                if (bs1 == 2) tc1 = P.chroma_tc((P.qpy(x - 1, y + 8) + P.qpy(x, y + 8) + 1) >> 1, c, tco);
-                if (p.pcmf) nob = (P.pcm(x - 1, y) ? 1u : 0u) | (P.pcm(x - 1, y + 8) ? 2u : 0u) | (P.pcm(x, y) ? 4u : 0u) | (P.pcm(x, y + 8) ? 8u : 0u);
-            }
+            const LfSegParams s = lf_segment_params<DIR>(p, c, x, y, bs0, bs1);
             /* [0] = (x + 8) | y << 14 | plane << 28, [1] = beta | tc[0] << 8 | tc[1] << 16 | pcm marks << 24 */
-            par = make_uint2((uint32_t)(x + 8) | ((uint32_t)y << 14) | ((uint32_t)c << 28), (uint32_t)beta | ((uint32_t)tc0 << 8) | ((uint32_t)tc1 << 16) | (nob << 24));
+            par = make_uint2((uint32_t)(x + 8) | ((uint32_t)y << 14) | ((uint32_t)c << 28), (uint32_t)s.beta | ((uint32_t)s.tc0 << 8) | ((uint32_t)s.tc1 << 16) | (s.nob << 24));
         }
     }
     const unsigned long long live = __ballot(cand);
@@ -420,28 +451,6 @@ __device__ __forceinline__ SaoRaw sao_raw(const uint8_t *p, bool wide)
     else { const mi355_sao_u32x2a1 q = *reinterpret_cast<const mi355_sao_u32x2a1 *>(p); r.q[0] = q[0]; r.q[1] = q[1]; r.q[2] = r.q[3] = 0; }
     return r;
 }
-__device__ __forceinline__ void sao_unpack(const SaoRaw &r, bool wide, int v[8])
-{
-    if (wide) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) { v[2 * k] = (int)(r.q[k] & 0xFFFFu); v[2 * k + 1] = (int)(r.q[k] >> 16); }
-    } else {
-#pragma unroll
-        for (int k = 0; k < 8; k++) v[k] = (int)((r.q[k >> 2] >> (8 * (k & 3))) & 0xFFu);
-    }
-}
-__device__ __forceinline__ void sao_ld8(const uint8_t *p, bool wide, int v[8])
-{
-    if (wide) {
-        const mi355_sao_u32x4a2 q = *reinterpret_cast<const mi355_sao_u32x4a2 *>(p);
-#pragma unroll
-        for (int k = 0; k < 4; k++) { v[2 * k] = (int)(q[k] & 0xFFFFu); v[2 * k + 1] = (int)(q[k] >> 16); }
-    } else {
-        const mi355_sao_u32x2a1 q = *reinterpret_cast<const mi355_sao_u32x2a1 *>(p);
-#pragma unroll
-        for (int k = 0; k < 8; k++) v[k] = (int)((q[k >> 2] >> (8 * (k & 3))) & 0xFFu);
-    }
-}
 /* ---- two 16-bit samples per register for SAO (v_pk_*_u16 / _i16; plain meaning in the emulator) ---- */
 #ifdef MI355_HIP_EMU_H
 static inline uint32_t sao_pk_sign(uint32_t c, uint32_t a)       /* per half: sign(c - a) as an int16 */
@@ -496,11 +505,58 @@ __device__ __forceinline__ void sao_shift_right(uint32_t v[4])
     v[0] = mi355_alignbyte(v[1], v[0], 2); v[1] = mi355_alignbyte(v[2], v[1], 2); v[2] = mi355_alignbyte(v[3], v[2], 2); v[3] = v[3] >> 16;
 }
 
+/* The arithmetic of a whole-region pass on packed pairs — sao_band_filter / sao_edge_filter (hevcdsp_template.c:270-718) — for samples from wherever the caller
+ * holds them.  The offsets are bytes (offset + 128: |offset| < 128) in two registers, at the places the selectors name, looked up with v_perm_b32.
+ * edge: selector = (sign(c - a) + sign(c - b)) & 7 -> 0: 0, 1: 1, 2: 2, 7: -1, 6: -2; edge_idx[] = { 1, 2, 0, 3, 4 } (:310); neighbour a lies at (dx0, dy0), b
+ * opposite.  band: selector = min((c >> shift) - band_position & 31, 4) -> offsets 1..4, 4: none.  The selectors work on ONE register pair, the loop over the four
+ * stays with the caller (handed over as arrays, k_hevc_sao_ctbs needs five to nine registers more). */
+template <bool EDGE> struct SaoTables {
+    static constexpr int BIAS = 128;
+    uint32_t t_lo, t_hi, bias2, max2, bp2;
+    int shift, dx0, dy0;
+    __device__ __forceinline__ SaoTables(const int32_t *offset_val, int eo, int band_position, int bd)
+    {
+        if (EDGE) {
+            t_lo = (uint32_t)(offset_val[0] + BIAS) | ((uint32_t)(offset_val[3] + BIAS) << 8) | ((uint32_t)(offset_val[4] + BIAS) << 16) | ((uint32_t)BIAS << 24);
+            t_hi = (uint32_t)BIAS | ((uint32_t)BIAS << 8) | ((uint32_t)(offset_val[1] + BIAS) << 16) | ((uint32_t)(offset_val[2] + BIAS) << 24);
+        } else {
+            t_lo = (uint32_t)(offset_val[1] + BIAS) | ((uint32_t)(offset_val[2] + BIAS) << 8) | ((uint32_t)(offset_val[3] + BIAS) << 16) | ((uint32_t)(offset_val[4] + BIAS) << 24);
+            t_hi = (uint32_t)BIAS * 0x01010101u;
+        }
+        bias2 = (uint32_t)BIAS * 0x00010001u; max2 = (uint32_t)((1 << bd) - 1) * 0x00010001u; bp2 = (uint32_t)band_position * 0x00010001u;
+        shift = bd - 5;
+        dx0 = eo == 0 ? -1 : (eo == 1 ? 0 : (eo == 2 ? -1 : 1)); dy0 = eo == 0 ? 0 : -1;
+    }
+    __device__ __forceinline__ uint32_t band(uint32_t c) const { return sao_pk_min_u(pk_sub(sao_pk_shr_u(c, shift), bp2) & 0x001F001Fu, 0x00040004u); }
+    __device__ __forceinline__ uint32_t edge(uint32_t c, uint32_t a, uint32_t b) const { return pk_add(sao_pk_sign(c, a), sao_pk_sign(c, b)); }
+    /* samples without one of their neighbours (the picture ends there) — the piece's first, its last, all eight (the neighbours' row is missing): selector 0 =
+     * offset_val[0], as the reference's border columns and rows (:388-430) */
+    __device__ __forceinline__ void no_neighbour(uint32_t sel[4], bool first, bool last, bool all) const
+    {
+        const uint32_t row = all ? 0xFFFFFFFFu : 0u;
+        sel[0] &= ~(row | (first ? 0x0000FFFFu : 0u));
+        sel[1] &= ~row;
+        sel[2] &= ~row;
+        sel[3] &= ~(row | (last ? 0xFFFF0000u : 0u));
+    }
+    /* clip(c + offset[selector]) of eight samples, stored as one whole piece: the low bytes of four selectors -> four offset bytes -> two pairs */
+    template <bool WIDE> __device__ __forceinline__ void store(uint8_t *d, const uint32_t c[4], const uint32_t sel[4]) const
+    {
+        const uint32_t s01 = byte_perm(sel[1], sel[0], 0x06040200u) & 0x07070707u, s23 = byte_perm(sel[3], sel[2], 0x06040200u) & 0x07070707u;
+        const uint32_t f01 = byte_perm(t_hi, t_lo, s01), f23 = byte_perm(t_hi, t_lo, s23);
+        const uint32_t off[4] = { mi355_widen_lo(f01), mi355_widen_hi(f01), mi355_widen_lo(f23), mi355_widen_hi(f23) };
+        uint32_t v[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] = sao_pk_min_u(sao_pk_subs_u(pk_add(c[k], off[k]), bias2), max2);
+        if (WIDE) *reinterpret_cast<mi355_sao_u32x4a2 *>(d) = mi355_sao_u32x4a2{ v[0], v[1], v[2], v[3] };
+        else *reinterpret_cast<mi355_sao_u32x2a1 *>(d) = mi355_sao_u32x2a1{ byte_perm(v[1], v[0], 0x06040200u), byte_perm(v[3], v[2], 0x06040200u) };
+    }
+};
+
 /* The whole region of an owner CTB in one pass when its pieces differ in nothing that matters: the band filter always (it knows no borders), the
  * edge filter when no piece touches an unfilterable slice / tile edge (nothing is restored) — sao_band_filter / sao_edge_filter
- * (hevcdsp_template.c:270-718) on packed pairs: eight samples per thread and step (a whole 16-byte / 8-byte piece of a row), the loads of a thread's steps
- * issued together, the offsets looked up with v_perm_b32 in a table of bytes held in two registers (offset + 128: |offset| < 128), rows written in whole
- * aligned pieces.  BORDERS: the region touches a picture border (`bo`: bit 0 left, 1 top, 2 right, 3 bottom).  A sample whose neighbour lies outside the
+ * with SaoTables' arithmetic: eight samples per thread and step (a whole 16-byte / 8-byte piece of a row), the loads of a thread's steps issued together, rows
+ * written in whole aligned pieces.  BORDERS: the region touches a picture border (`bo`: bit 0 left, 1 top, 2 right, 3 bottom).  A sample whose neighbour lies outside the
  * picture gets offset_val[0] (the reference's init_x / init_y / width-- / height-- columns and rows, :388-430), and no load leaves the
  * rows and columns the picture has: a neighbour piece that would start left of column 0 / end right of the last column is fetched in place and shifted
  * in registers, a neighbour row above row 0 / below the last row is the row itself (its samples are kept anyway). */
@@ -508,21 +564,9 @@ template <bool WIDE, bool EDGE, bool BORDERS>
 __device__ __forceinline__ void sao_region_fast(uint8_t *dst, const uint8_t *src, int stride, int W, int H, int eo, int band_position,
                                                 const int32_t *offset_val, int bd, int bo, int tid, int nthreads)
 {
-    constexpr int BIAS = 128;
     constexpr bool wide = WIDE, edge = EDGE;     /* compile-time: a load under a run-time choice of its width is a branch, the load and a wait for it */
-    const int px = wide ? 2 : 1, per = W >> 3, inv = mi355_inv20(per), shift = bd - 5;
-    const int dx0 = eo == 0 ? -1 : (eo == 1 ? 0 : (eo == 2 ? -1 : 1)), dy0 = eo == 0 ? 0 : -1;
-    /* the offsets as bytes at the places the selectors name.  edge: selector = (sign(c - a) + sign(c - b)) & 7 -> 0: 0, 1: 1, 2: 2, 7: -1, 6: -2;
-     * edge_idx[] = { 1, 2, 0, 3, 4 } (:310).  band: selector = min((c >> shift) - band_position & 31, 4) -> offsets 1..4, 4: none */
-    uint32_t t_lo, t_hi;
-    if (edge) {
-        t_lo = (uint32_t)(offset_val[0] + BIAS) | ((uint32_t)(offset_val[3] + BIAS) << 8) | ((uint32_t)(offset_val[4] + BIAS) << 16) | ((uint32_t)BIAS << 24);
-        t_hi = (uint32_t)BIAS | ((uint32_t)BIAS << 8) | ((uint32_t)(offset_val[1] + BIAS) << 16) | ((uint32_t)(offset_val[2] + BIAS) << 24);
-    } else {
-        t_lo = (uint32_t)(offset_val[1] + BIAS) | ((uint32_t)(offset_val[2] + BIAS) << 8) | ((uint32_t)(offset_val[3] + BIAS) << 16) | ((uint32_t)(offset_val[4] + BIAS) << 24);
-        t_hi = (uint32_t)BIAS * 0x01010101u;
-    }
-    const uint32_t bias2 = (uint32_t)BIAS * 0x00010001u, max2 = (uint32_t)((1 << bd) - 1) * 0x00010001u, bp2 = (uint32_t)band_position * 0x00010001u;
+    const SaoTables<EDGE> T(offset_val, eo, band_position, bd);
+    const int px = wide ? 2 : 1, per = W >> 3, inv = mi355_inv20(per), dx0 = T.dx0, dy0 = T.dy0;
     /* A step = the eight samples of one piece.  The loads of the next two steps are in flight while a step is worked on and stored (source and
      * destination may be one picture as far as the compiler knows: written in this order, no load waits behind a store): a wave keeps 2-3 KB of
      * requests open all the time instead of waiting out a memory round trip per step — what a wave moves per microsecond it occupies its slot is what
@@ -548,24 +592,17 @@ __device__ __forceinline__ void sao_region_fast(uint8_t *dst, const uint8_t *src
                 s.b = sao_raw(src + s.o + rowb - (fb ? 0 : dx0 * px), wide);
             } else {
                 const ptrdiff_t da = (ptrdiff_t)dx0 * px + (ptrdiff_t)dy0 * stride;
-#ifdef MI355_EXP_SAO_NONEIGH
-                (void)da;
-#elif defined(MI355_EXP_SAO_ALIGNED)
-                const ptrdiff_t dal = (ptrdiff_t)dy0 * stride;
-                s.a = sao_raw(src + s.o + dal, wide); s.b = sao_raw(src + s.o - dal, wide);
-#else
                 s.a = sao_raw(src + s.o + da, wide); s.b = sao_raw(src + s.o - da, wide);
-#endif
             }
         }
         return s;
     };
     auto work = [&](const Step &s) {
-        uint32_t c[4], sel[4], v[4];
+        uint32_t c[4], sel[4];
         sao_pairs(s.c, wide, c);
         if (!edge) {
 #pragma unroll
-            for (int k = 0; k < 4; k++) sel[k] = sao_pk_min_u(pk_sub(sao_pk_shr_u(c[k], shift), bp2) & 0x001F001Fu, 0x00040004u);
+            for (int k = 0; k < 4; k++) sel[k] = T.band(c[k]);
         } else {
             uint32_t a[4], b[4];
             sao_pairs(s.a, wide, a);
@@ -575,24 +612,10 @@ __device__ __forceinline__ void sao_region_fast(uint8_t *dst, const uint8_t *src
                 if (s.fix & 16) { if (dx0 < 0) sao_shift_right(b); else sao_shift_left(b); }
             }
 #pragma unroll
-            for (int k = 0; k < 4; k++) sel[k] = pk_add(sao_pk_sign(c[k], a[k]), sao_pk_sign(c[k], b[k]));
-            if (BORDERS) {
-                /* a sample without one of its neighbours: selector 0 = offset_val[0], as the reference's border columns and rows (:388-430) */
-                const uint32_t row = (s.fix & 4) ? 0xFFFFFFFFu : 0u;
-                sel[0] &= ~(row | ((s.fix & 1) ? 0x0000FFFFu : 0u));
-                sel[1] &= ~row;
-                sel[2] &= ~row;
-                sel[3] &= ~(row | ((s.fix & 2) ? 0xFFFF0000u : 0u));
-            }
+            for (int k = 0; k < 4; k++) sel[k] = T.edge(c[k], a[k], b[k]);
+            if (BORDERS) T.no_neighbour(sel, (s.fix & 1) != 0, (s.fix & 2) != 0, (s.fix & 4) != 0);
         }
-        /* the low bytes of four selectors -> four offset bytes -> two pairs */
-        const uint32_t s01 = byte_perm(sel[1], sel[0], 0x06040200u) & 0x07070707u, s23 = byte_perm(sel[3], sel[2], 0x06040200u) & 0x07070707u;
-        const uint32_t f01 = byte_perm(t_hi, t_lo, s01), f23 = byte_perm(t_hi, t_lo, s23);
-        const uint32_t off[4] = { mi355_widen_lo(f01), mi355_widen_hi(f01), mi355_widen_lo(f23), mi355_widen_hi(f23) };
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] = sao_pk_min_u(sao_pk_subs_u(pk_add(c[k], off[k]), bias2), max2);       /* clip(c + offset) */
-        if (wide) *reinterpret_cast<mi355_sao_u32x4a2 *>(dst + s.o) = mi355_sao_u32x4a2{ v[0], v[1], v[2], v[3] };
-        else *reinterpret_cast<mi355_sao_u32x2a1 *>(dst + s.o) = mi355_sao_u32x2a1{ byte_perm(v[1], v[0], 0x06040200u), byte_perm(v[3], v[2], 0x06040200u) };
+        T.template store<WIDE>(dst + s.o, c, sel);
     };
     if (tid >= n) return;
     /* three sets of registers taking turns (a set handed on by copying would have to wait for its loads first) */
@@ -604,65 +627,73 @@ __device__ __forceinline__ void sao_region_fast(uint8_t *dst, const uint8_t *src
     }
 }
 constexpr int SAO_CTB_THREADS = 64;
-/* The job record (168 bytes = 42 dwords) is fetched ONCE, a dword per lane, and its fields are read out of that register as scalars (v_readlane): the
- * record is not known to be read-only to the compiler (the kernel stores through other pointers), so field-by-field reads are vector loads, each waited
- * for before the branch that depends on it — 20-40 dependent memory round trips per wave before the first sample was requested, which is what this kernel's
- * time consisted of (profiles/r06_experiments.md). */
-static_assert(sizeof(mi355_hevc_sao_ctb_job) == 168 && sizeof(mi355_hevc_sao_piece) == 36 && offsetof(mi355_hevc_sao_ctb_job, piece) == 24, "k_hevc_sao_ctbs reads the record by dword index");
+/* The job record (168 bytes = 42 dwords) from its lane-held copy (rec_fetch).  Piece k: dwords 6 + 9 k ..: offset_val[5]; cls | type << 8 | eo_class << 16 |
+ * band_position << 24; vert | horiz << 8 | diag << 16 | borders << 24; dx | dy << 16; width | height << 16.  Piece 0 is the owner's own call when its class is 0 and it
+ * lies at the job's origin: its size is the region's then, its parameters are every piece's. */
+static_assert(sizeof(mi355_hevc_sao_ctb_job) == 168 && sizeof(mi355_hevc_sao_piece) == 36 && offsetof(mi355_hevc_sao_ctb_job, piece) == 24, "the record is read by dword index");
+struct SaoCtbRec {
+    uint8_t *dst;
+    const uint8_t *src;
+    int stride, chroma, np;
+    int cls, type, eo, band_position, borders, W, H;      /* piece 0's; borders: which picture borders the REGION touches */
+    uint32_t dxy;                                         /* piece 0's dx | dy << 16 */
+    uint32_t flags, types;                                /* over all pieces: an edge that is restored; a type that is not piece 0's */
+    int32_t ov[5];                                        /* piece 0's offsets */
+    bool small;                                           /* ... all within a signed byte */
+};
+__device__ __forceinline__ SaoCtbRec sao_ctb_rec(int rec)
+{
+    SaoCtbRec r;
+    r.dst = mi355_global(rec_ptr<uint8_t>(rec, 0));
+    r.src = mi355_global(rec_ptr<const uint8_t>(rec, 2));
+    r.stride = (int)rec_dw(rec, 4); r.chroma = (rec_dw(rec, 5) & 0xFF) != 0; r.np = (int)((rec_dw(rec, 5) >> 8) & 0xFF);
+    const uint32_t p0a = rec_dw(rec, 6 + 5), p0b = rec_dw(rec, 6 + 6), p0d = rec_dw(rec, 6 + 8);
+    r.cls = (int)(p0a & 0xFF); r.type = (int)((p0a >> 8) & 0xFF); r.eo = (int)((p0a >> 16) & 0xFF); r.band_position = (int)(p0a >> 24);
+    r.borders = (int)(p0b >> 24); r.dxy = rec_dw(rec, 6 + 7);
+    r.W = (int)(int16_t)(p0d & 0xFFFF); r.H = (int)(int16_t)(p0d >> 16);
+    r.flags = p0b & 0x00FFFFFFu; r.types = 0;
+#pragma unroll
+    for (int k = 1; k < 4; k++)
+        if (r.np > k) { r.flags |= rec_dw(rec, 6 + 9 * k + 6) & 0x00FFFFFFu; r.types |= ((rec_dw(rec, 6 + 9 * k + 5) >> 8) & 0xFF) ^ (uint32_t)r.type; }
+    r.small = true;
+#pragma unroll
+    for (int e = 0; e < 5; e++) { r.ov[e] = (int32_t)rec_dw(rec, 6 + e); r.small = r.small && r.ov[e] > -128 && r.ov[e] < 128; }
+    return r;
+}
 /* A wave per job; SAO_CTB_JOBS consecutive jobs share a workgroup, i.e. a CU and its XCD's L2, at the same time: a caller's jobs of one component run along a row of
  * blocks, so a chroma block's 64-byte half of a line is asked for next to its neighbour's other half (fetched once, written back once), and the luma rows of four
  * neighbours are 512 contiguous bytes. */
-#ifndef MI355_SAO_CTB_JOBS
-#define MI355_SAO_CTB_JOBS 4
-#endif
-constexpr int SAO_CTB_JOBS = MI355_SAO_CTB_JOBS;
+constexpr int SAO_CTB_JOBS = 4;
 template <bool WIDE>
 __global__ void __launch_bounds__(SAO_CTB_THREADS * SAO_CTB_JOBS) k_hevc_sao_ctbs(const mi355_hevc_sao_ctb_job *jobs, int n, int bd)
 {
-    /* ... and the workgroups of an XCD (they go to the eight in turn) take consecutive groups: XCD k the k-th eighth of the list */
-    const int ngroups = (int)gridDim.x, grp = (ngroups & 7) ? (int)blockIdx.x : ((int)blockIdx.x & 7) * (ngroups >> 3) + ((int)blockIdx.x >> 3);
+    /* ... and the workgroups of an XCD take consecutive groups */
+    const int grp = xcd_ordered((int)blockIdx.x, (int)gridDim.x);
     const int job = grp * SAO_CTB_JOBS + uniform((int)(threadIdx.x >> 6));
     if (job >= n) return;
     const mi355_hevc_sao_ctb_job &j = jobs[job];
     const int tid = (int)threadIdx.x & 63;
-    const int rec = (int)mi355_global_v(reinterpret_cast<const uint32_t *>(&j))[tid < 42 ? tid : 41];
-#define SAO_REC(dw) ((uint32_t)lane_value(rec, (dw)))
-    uint8_t *dst0 = mi355_global(reinterpret_cast<uint8_t *>((uintptr_t)SAO_REC(0) | ((uintptr_t)SAO_REC(1) << 32)));
-    const uint8_t *src0 = mi355_global(reinterpret_cast<const uint8_t *>((uintptr_t)SAO_REC(2) | ((uintptr_t)SAO_REC(3) << 32)));
-    const int stride = (int)SAO_REC(4), chroma = (SAO_REC(5) & 0xFF) != 0, np = (int)((SAO_REC(5) >> 8) & 0xFF);
+    const SaoCtbRec r = sao_ctb_rec(rec_fetch(&j, tid));
+    uint8_t *const dst0 = r.dst;
+    const uint8_t *const src0 = r.src;
+    const int stride = r.stride, chroma = r.chroma, np = r.np;
     const int cw = (8 >> chroma) + 2, ch = (4 >> chroma) + 2, px = bd > 8 ? 2 : 1;
     __shared__ int tbl_all[SAO_CTB_JOBS][32];          /* the piece-by-piece path's table: a wave's own */
     int *const tbl = tbl_all[uniform((int)(threadIdx.x >> 6))];
     const int st = stride / px;
-    /* piece k: dwords 6 + 9 k ..: offset_val[5]; cls | type << 8 | eo_class << 16 | band_position << 24; vert | horiz << 8 | diag << 16 | borders << 24;
-     * dx | dy << 16; width | height << 16 */
-    const uint32_t p0a = SAO_REC(6 + 5), p0b = SAO_REC(6 + 6), p0c = SAO_REC(6 + 7), p0d = SAO_REC(6 + 8);
-    /* piece 0 is the owner's own call (class 0): its size is the region's, its parameters are every piece's */
-    if (np >= 1 && (p0a & 0xFF) == 0 && p0c == 0) {
-        const int type = (int)((p0a >> 8) & 0xFF), W = (int)(int16_t)(p0d & 0xFFFF), H = (int)(int16_t)(p0d >> 16);
-        /* every piece of the owner's type, none with a restored edge */
-        uint32_t flags = p0b & 0x00FFFFFFu, types = 0;
-        if (np > 1) { flags |= SAO_REC(15 + 6) & 0x00FFFFFFu; types |= ((SAO_REC(15 + 5) >> 8) & 0xFF) ^ (uint32_t)type; }
-        if (np > 2) { flags |= SAO_REC(24 + 6) & 0x00FFFFFFu; types |= ((SAO_REC(24 + 5) >> 8) & 0xFF) ^ (uint32_t)type; }
-        if (np > 3) { flags |= SAO_REC(33 + 6) & 0x00FFFFFFu; types |= ((SAO_REC(33 + 5) >> 8) & 0xFF) ^ (uint32_t)type; }
-        const bool unrestored = flags == 0, same = types == 0;
-        if (same && type == 0) { sao_copy_region(dst0, src0, stride, 0, 0, W, H, px, tid, SAO_CTB_THREADS); return; }
-        const int32_t ov[5] = { (int32_t)SAO_REC(6), (int32_t)SAO_REC(7), (int32_t)SAO_REC(8), (int32_t)SAO_REC(9), (int32_t)SAO_REC(10) };
-        bool small = true;
-        for (int e = 0; e < 5; e++) small = small && ov[e] > -128 && ov[e] < 128;
-        if (same && small && (W & 7) == 0 && (type == 1 || (type == 2 && unrestored))) {
-            /* which picture borders the REGION touches: the owner's own left / top; right / bottom when no other CTB's call covers a strip of it */
-            const int bo = type == 2 ? (int)(p0b >> 24) : 0, eo = (int)((p0a >> 16) & 0xFF), bp = (int)(p0a >> 24);
-            if (type == 1) sao_region_fast<WIDE, false, false>(dst0, src0, stride, W, H, eo, bp, ov, bd, 0, tid, SAO_CTB_THREADS);
-            else if (bo) sao_region_fast<WIDE, true, true>(dst0, src0, stride, W, H, eo, bp, ov, bd, bo, tid, SAO_CTB_THREADS);
-            else sao_region_fast<WIDE, true, false>(dst0, src0, stride, W, H, eo, bp, ov, bd, 0, tid, SAO_CTB_THREADS);
+    /* the whole region in one pass: piece 0 the owner's own call, every piece of its type; filtered: offsets within a byte, whole pieces of eight, no restored edge.
+     * Everything else goes piece by piece below. */
+    if (np >= 1 && r.cls == 0 && r.dxy == 0 && r.types == 0) {
+        const int type = r.type, W = r.W, H = r.H;
+        if (type == 0) { sao_copy_region(dst0, src0, stride, 0, 0, W, H, px, tid, SAO_CTB_THREADS); return; }
+        if (r.small && (W & 7) == 0 && (type == 1 || (type == 2 && r.flags == 0))) {
+            const int bo = type == 2 ? r.borders : 0;
+            if (type == 1) sao_region_fast<WIDE, false, false>(dst0, src0, stride, W, H, r.eo, r.band_position, r.ov, bd, 0, tid, SAO_CTB_THREADS);
+            else if (bo) sao_region_fast<WIDE, true, true>(dst0, src0, stride, W, H, r.eo, r.band_position, r.ov, bd, bo, tid, SAO_CTB_THREADS);
+            else sao_region_fast<WIDE, true, false>(dst0, src0, stride, W, H, r.eo, r.band_position, r.ov, bd, 0, tid, SAO_CTB_THREADS);
             return;
         }
     }
-#undef SAO_REC
-#ifdef MI355_EXP_SAO_NOSLOW
-    return;
-#endif
     /* piece by piece, as the reference makes its calls (hevc_sao_wave is a wave's function) */
     for (int k = 0; k < np && k < 4; k++) {
         const mi355_hevc_sao_piece &q = j.piece[k];
@@ -693,12 +724,11 @@ static_assert(sizeof(mi355_edge_emu_job) == 48 && offsetof(mi355_edge_emu_job, b
 __global__ void __launch_bounds__(64) k_edge_emu_batch(const mi355_edge_emu_job *jobs, int n, int bd)
 {
     if ((int)blockIdx.x >= n) return;
-    /* the record once, a dword per lane (field by field it is a chain of vector loads: see k_hevc_sao_ctbs) */
-    const int rec = (int)mi355_global_v(reinterpret_cast<const uint32_t *>(jobs + blockIdx.x))[lane_id() < 12 ? lane_id() : 11];
-    uint8_t *dst = mi355_global(reinterpret_cast<uint8_t *>((uintptr_t)(uint32_t)lane_value(rec, 0) | ((uintptr_t)(uint32_t)lane_value(rec, 1) << 32)));
-    const uint8_t *src = reinterpret_cast<const uint8_t *>((uintptr_t)(uint32_t)lane_value(rec, 2) | ((uintptr_t)(uint32_t)lane_value(rec, 3) << 32));
-    const int ds = lane_value(rec, 4), ss = lane_value(rec, 5), bw = lane_value(rec, 6), bh = lane_value(rec, 7);
-    const int sx = lane_value(rec, 8), sy = lane_value(rec, 9), w = lane_value(rec, 10), h = lane_value(rec, 11), px = bd > 8 ? 2 : 1;
+    const int rec = rec_fetch(jobs + blockIdx.x, lane_id());
+    uint8_t *dst = mi355_global(rec_ptr<uint8_t>(rec, 0));
+    const uint8_t *src = rec_ptr<const uint8_t>(rec, 2);
+    const int ds = (int)rec_dw(rec, 4), ss = (int)rec_dw(rec, 5), bw = (int)rec_dw(rec, 6), bh = (int)rec_dw(rec, 7);
+    const int sx = (int)rec_dw(rec, 8), sy = (int)rec_dw(rec, 9), w = (int)rec_dw(rec, 10), h = (int)rec_dw(rec, 11), px = bd > 8 ? 2 : 1;
     /* `src` is the window's first sample (possibly outside the plane): the plane's sample (0, 0) lies sy rows and sx samples before it */
     const uint8_t *plane = mi355_global(src) - (ptrdiff_t)sy * ss - (ptrdiff_t)sx * px;
     if (bw <= 0 || bh <= 0 || w <= 0 || h <= 0) return;
@@ -1052,23 +1082,6 @@ template <bool WIDE> struct __attribute__((aligned(16))) FtTile {
     uint8_t y[FT_Y * FT_Y * (WIDE ? 2 : 1)];
     uint8_t c[2][FT_C * FT_C * (WIDE ? 2 : 1)];
 };
-/* one line of an edge in the tile: the eight samples across it one by one (LDS), the decisions and the arithmetic of hevc_lf_luma_wave */
-__device__ __forceinline__ void ft_lf_luma(uint8_t *pix, int xs, int ys, int beta, const int *tc_, const uint8_t *no_p_, const uint8_t *no_q_, int bd, bool on)
-{
-    const int l = lane_id() & 7;
-    int p[4], q[4], np[3], nq[3];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        p[k] = on ? ldpx(pix, -(k + 1) * xs + l * ys, bd) : 0;
-        q[k] = on ? ldpx(pix, k * xs + l * ys, bd) : 0;
-    }
-    if (!hevc_lf_luma_core(p, q, beta, tc_, no_p_, no_q_, bd, on, np, nq)) return;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        if (np[k] != p[k]) stpx(pix, -(k + 1) * xs + l * ys, np[k], bd);
-        if (nq[k] != q[k]) stpx(pix, k * xs + l * ys, nq[k], bd);
-    }
-}
 /* candidates of a pass: the luma edge segments (8 samples along the edge: two halves of 4 with a strength each) that touch rows / columns -4 .. size + 3 of the
  * block, then those of the two chroma planes (8 chroma samples: two halves of 4 = 8 luma samples each; ring -2 .. size / 2 + 1).  Candidate `cand` of pass DIR ->
  * everything the filter needs, as two dwords: [0] = tile x | tile y << 8 | plane << 16 | no_p / no_q bits << 24 (the segment's first q-side sample; tile sample
@@ -1078,69 +1091,32 @@ __device__ __forceinline__ void ft_lf_luma(uint8_t *pix, int xs, int ys, int bet
 template <int DIR>
 __device__ __forceinline__ uint2 ft_params(const mi355_hevc_lf_picture &p, int x0, int y0, int S, int cand)
 {
-    const LfPic P{ p };
-    const int W = p.width, H = p.height;
     const int nUl = (S >> 3) + 2, nl = ((S >> 3) + 1) * nUl;
     const int nUc = DIR ? (S >> 4) + 1 : (S >> 4) + 2, nc = ((S >> 4) + 1) * nUc;
-    const uint8_t *vbs = mi355_global_v(p.vertical_bs), *hbs = mi355_global_v(p.horizontal_bs);
     int plane = 0, x = 0, y = 0, bs0 = 0, bs1 = 0;
     bool live = false;
     if (cand < nl) {
         const int e = mi355_div20(cand, mi355_inv20(nUl)), u = cand - e * nUl;
         if (DIR == 0) { x = x0 + 8 * e; y = y0 - 8 + 8 * u; } else { y = y0 + 8 * e; x = x0 - 8 + 8 * u; }
-        if (x >= 0 && y >= 0 && x < W && y < H && (DIR ? y >= 8 : x >= 8)) {
-            if (DIR) { bs0 = hbs[(x + y * p.bs_width) >> 2]; bs1 = hbs[(x + 4 + y * p.bs_width) >> 2]; }
-            else { bs0 = vbs[(x >> 3) + (y >> 2) * p.bs_width]; bs1 = vbs[(x >> 3) + ((y + 4) >> 2) * p.bs_width]; }
-            if (u == 0) bs0 = 0;                       /* the halves beyond the four rows / columns around the block: not this block's business, not in the tile */
-            if (u == nUl - 1) bs1 = 0;
-            live = (bs0 | bs1) != 0;
-        }
+        lf_luma_strengths<DIR>(p, x, y, bs0, bs1);
+        if (u == 0) bs0 = 0;                       /* the halves beyond the four rows / columns around the block: not this block's business, not in the tile */
+        if (u == nUl - 1) bs1 = 0;
+        live = (bs0 | bs1) != 0;
     } else if (cand - nl < 2 * nc) {
         const int c1 = cand - nl, pl = mi355_div20(c1, mi355_inv20(nc)), c2 = c1 - pl * nc, e = mi355_div20(c2, mi355_inv20(nUc)), u = c2 - e * nUc;
         plane = 1 + pl;
-        if (DIR == 0) {
-            x = x0 + 16 * e; y = y0 - 16 + 16 * u;
-            if (x >= 16 && x < W && y >= 0 && y < H) {
-                bs0 = vbs[(x >> 3) + (y >> 2) * p.bs_width]; bs1 = vbs[(x >> 3) + ((y + 8) >> 2) * p.bs_width];
-                if (u == 0) bs0 = 0;
-                if (u == nUc - 1) bs1 = 0;
-            }
-        } else {
-            /* the reference's pairs of horizontal chroma segments start at x = 8 (mod 16), i.e. at -8 (hevc_filter.c:469-484); a half outside the picture has bS 0 */
-            y = y0 + 16 * e; x = x0 - 8 + 16 * u;
-            if (y >= 16 && y < H && x < W) {
-                bs0 = x < 0 ? 0 : hbs[(x + y * p.bs_width) >> 2];
-                bs1 = x + 8 >= W ? 0 : hbs[(x + 8 + y * p.bs_width) >> 2];
-            }
+        if (DIR == 0) { x = x0 + 16 * e; y = y0 - 16 + 16 * u; } else { y = y0 + 16 * e; x = x0 - 8 + 16 * u; }
+        lf_chroma_strengths<DIR>(p, x, y, bs0, bs1);
+        if (DIR == 0) {                            /* a horizontal segment's pairs start 8 luma samples before the block: the outer halves of the first and the last one are the ring */
+            if (u == 0) bs0 = 0;
+            if (u == nUc - 1) bs1 = 0;
         }
         live = bs0 == 2 || bs1 == 2;
     }
     if (!live) return make_uint2(0u, 0u);
-    int beta = 0, tc[2] = { 0, 0 }, no_p[2] = { 0, 0 }, no_q[2] = { 0, 0 };
-    if (plane == 0) {
-        const mi355_hevc_db_params d = P.db(x, y);
-        const int qp = (P.qpy(DIR ? x : x - 1, DIR ? y - 1 : y) + P.qpy(x, y) + 1) >> 1;
-        beta = k_hevc_betatable[clip3(qp + d.beta_offset, 0, 51)];
-        tc[0] = bs0 ? hevc_tc_calc(qp, bs0, d.tc_offset) : 0;
-        tc[1] = bs1 ? hevc_tc_calc(qp, bs1, d.tc_offset) : 0;
-        if (p.pcmf) {
-            if (DIR) { no_p[0] = P.pcm(x, y - 1); no_p[1] = P.pcm(x + 4, y - 1); no_q[0] = P.pcm(x, y); no_q[1] = P.pcm(x + 4, y); }
-            else { no_p[0] = P.pcm(x - 1, y); no_p[1] = P.pcm(x - 1, y + 4); no_q[0] = P.pcm(x, y); no_q[1] = P.pcm(x, y + 4); }
-        }
-    } else if (DIR) {
-        if (bs0 == 2) tc[0] = P.chroma_tc((P.qpy(x, y - 1) + P.qpy(x, y) + 1) >> 1, plane, P.db(x, y).tc_offset);
-        if (bs1 == 2) tc[1] = P.chroma_tc((P.qpy(x + 8, y - 1) + P.qpy(x + 8, y) + 1) >> 1, plane, P.db(x + 8, y).tc_offset);
-        if (p.pcmf) { no_p[0] = P.pcm(x, y - 1); no_p[1] = P.pcm(x + 8, y - 1); no_q[0] = P.pcm(x, y); no_q[1] = P.pcm(x + 8, y); }
-    } else {
-        const int tco = P.db(x, y).tc_offset;
-        if (bs0 == 2) tc[0] = P.chroma_tc((P.qpy(x - 1, y) + P.qpy(x, y) + 1) >> 1, plane, tco);
-        if (bs1 == 2) tc[1] = P.chroma_tc((P.qpy(x - 1, y + 8) + P.qpy(x, y + 8) + 1) >> 1, plane, tco);
-        if (p.pcmf) { no_p[0] = P.pcm(x - 1, y); no_p[1] = P.pcm(x - 1, y + 8); no_q[0] = P.pcm(x, y); no_q[1] = P.pcm(x, y + 8); }
-    }
+    const LfSegParams s = lf_segment_params<DIR>(p, plane, x, y, bs0, bs1);
     const int tx = plane == 0 ? x - x0 + 8 : (x >> 1) - (x0 >> 1) + 8, ty = plane == 0 ? y - y0 + 8 : (y >> 1) - (y0 >> 1) + 8;
-    /* the pcm / bypass marks as the filters test them: != 0 */
-    const uint32_t nob = (no_p[0] ? 1u : 0u) | (no_p[1] ? 2u : 0u) | (no_q[0] ? 4u : 0u) | (no_q[1] ? 8u : 0u);
-    return make_uint2((uint32_t)tx | ((uint32_t)ty << 8) | ((uint32_t)plane << 16) | (nob << 24), (uint32_t)beta | ((uint32_t)tc[0] << 8) | ((uint32_t)tc[1] << 16) | (1u << 24));
+    return make_uint2((uint32_t)tx | ((uint32_t)ty << 8) | ((uint32_t)plane << 16) | (s.nob << 24), (uint32_t)s.beta | ((uint32_t)s.tc0 << 8) | ((uint32_t)s.tc1 << 16) | (1u << 24));
 }
 /* a pass over the tile: a wave lists the live ones among its candidates (every fourth: a share of the luma and of the chroma segments each) and works through them
  * eight at a time, eight lanes per segment; nothing but LDS is touched */
@@ -1164,7 +1140,7 @@ __device__ __forceinline__ void ft_deblock_pass(FtTile<WIDE> &t, const uint2 *pa
         const bool luma = plane == 0;
         const int pitch = luma ? FT_Y : FT_C;
         uint8_t *pix = (luma ? t.y : (plane == 1 ? t.c[0] : t.c[1])) + ((ty * pitch + tx) << ps);
-        ft_lf_luma(pix, DIR ? pitch : 1, DIR ? 1 : pitch, beta, tc, no_p, no_q, bd, on && luma);
+        hevc_lf_luma_wave<false>(pix, DIR ? pitch : 1, DIR ? 1 : pitch, beta, tc, no_p, no_q, bd, true, on && luma);      /* sample by sample: the tile's lines are not the picture's */
         hevc_lf_chroma_wave(pix, DIR ? pitch : 1, DIR ? 1 : pitch, tc, no_p, no_q, bd, true, on && !luma);
     }
 }
@@ -1175,18 +1151,9 @@ template <bool WIDE, bool EDGE, bool BORDERS>
 __device__ __forceinline__ void ft_sao_region(const uint8_t *tile, int tp, uint8_t *dst, int stride, int W, int H, int eo, int band_position, const int32_t *offset_val,
                                               int bd, int bo, int first, int nthreads)
 {
-    constexpr int BIAS = 128, PX = WIDE ? 2 : 1;
-    const int per = W >> 3, inv = mi355_inv20(per), shift = bd - 5;
-    const int dx0 = eo == 0 ? -1 : (eo == 1 ? 0 : (eo == 2 ? -1 : 1)), dy0 = eo == 0 ? 0 : -1;
-    uint32_t t_lo, t_hi;
-    if (EDGE) {
-        t_lo = (uint32_t)(offset_val[0] + BIAS) | ((uint32_t)(offset_val[3] + BIAS) << 8) | ((uint32_t)(offset_val[4] + BIAS) << 16) | ((uint32_t)BIAS << 24);
-        t_hi = (uint32_t)BIAS | ((uint32_t)BIAS << 8) | ((uint32_t)(offset_val[1] + BIAS) << 16) | ((uint32_t)(offset_val[2] + BIAS) << 24);
-    } else {
-        t_lo = (uint32_t)(offset_val[1] + BIAS) | ((uint32_t)(offset_val[2] + BIAS) << 8) | ((uint32_t)(offset_val[3] + BIAS) << 16) | ((uint32_t)(offset_val[4] + BIAS) << 24);
-        t_hi = (uint32_t)BIAS * 0x01010101u;
-    }
-    const uint32_t bias2 = (uint32_t)BIAS * 0x00010001u, max2 = (uint32_t)((1 << bd) - 1) * 0x00010001u, bp2 = (uint32_t)band_position * 0x00010001u;
+    constexpr int PX = WIDE ? 2 : 1;
+    const SaoTables<EDGE> T(offset_val, eo, band_position, bd);
+    const int per = W >> 3, inv = mi355_inv20(per), dx0 = T.dx0, dy0 = T.dy0;
     /* eight samples at (x + dx, y + dy), dx in -1 .. 1, as pairs: the aligned piece, and for dx != 0 the dword before / behind it shifted in */
     auto fetch = [&](int x, int y, int dx, uint32_t v[4]) {
         const uint8_t *q = tile + y * tp + x * PX;
@@ -1213,35 +1180,23 @@ __device__ __forceinline__ void ft_sao_region(const uint8_t *tile, int tp, uint8
     const int n = per * H;
     for (int i = first; i < n; i += nthreads) {
         const int y = mi355_div20(i, inv), x = 8 * (i - y * per);
-        uint32_t c[4], sel[4], v[4];
+        uint32_t c[4], sel[4];
         fetch(x, y, 0, c);
         if (!EDGE) {
 #pragma unroll
-            for (int k = 0; k < 4; k++) sel[k] = sao_pk_min_u(pk_sub(sao_pk_shr_u(c[k], shift), bp2) & 0x001F001Fu, 0x00040004u);
+            for (int k = 0; k < 4; k++) sel[k] = T.band(c[k]);
         } else {
             uint32_t a[4], b[4];
             fetch(x, y + dy0, dx0, a);
             fetch(x, y - dy0, -dx0, b);
 #pragma unroll
-            for (int k = 0; k < 4; k++) sel[k] = pk_add(sao_pk_sign(c[k], a[k]), sao_pk_sign(c[k], b[k]));
+            for (int k = 0; k < 4; k++) sel[k] = T.edge(c[k], a[k], b[k]);
             if (BORDERS) {
-                /* a sample without one of its neighbours (the picture ends there): selector 0 = offset_val[0] (hevcdsp_template.c:388-430) */
                 const bool xl = (bo & 1) && x == 0, xr = (bo & 4) && x + 8 == W, yt = (bo & 2) && y == 0, yb = (bo & 8) && y == H - 1;
-                const uint32_t row = dy0 && (yt || yb) ? 0xFFFFFFFFu : 0u;
-                sel[0] &= ~(row | (dx0 && xl ? 0x0000FFFFu : 0u));
-                sel[1] &= ~row;
-                sel[2] &= ~row;
-                sel[3] &= ~(row | (dx0 && xr ? 0xFFFF0000u : 0u));
+                T.no_neighbour(sel, dx0 && xl, dx0 && xr, dy0 && (yt || yb));
             }
         }
-        const uint32_t s01 = byte_perm(sel[1], sel[0], 0x06040200u) & 0x07070707u, s23 = byte_perm(sel[3], sel[2], 0x06040200u) & 0x07070707u;
-        const uint32_t f01 = byte_perm(t_hi, t_lo, s01), f23 = byte_perm(t_hi, t_lo, s23);
-        const uint32_t off[4] = { mi355_widen_lo(f01), mi355_widen_hi(f01), mi355_widen_lo(f23), mi355_widen_hi(f23) };
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] = sao_pk_min_u(sao_pk_subs_u(pk_add(c[k], off[k]), bias2), max2);
-        uint8_t *d = dst + (ptrdiff_t)y * stride + x * PX;
-        if (WIDE) *reinterpret_cast<mi355_sao_u32x4a2 *>(d) = mi355_sao_u32x4a2{ v[0], v[1], v[2], v[3] };
-        else *reinterpret_cast<mi355_sao_u32x2a1 *>(d) = mi355_sao_u32x2a1{ byte_perm(v[1], v[0], 0x06040200u), byte_perm(v[3], v[2], 0x06040200u) };
+        T.template store<WIDE>(dst + (ptrdiff_t)y * stride + x * PX, c, sel);
     }
 }
 /* the region leaves as it is (SAO off for the block's component) */
@@ -1272,20 +1227,12 @@ __global__ void __launch_bounds__(FT_THREADS) k_hevc_filter_ctbs(const mi355_hev
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
     const int S = 1 << log2_ctb;
     /* the block's record (5 dwords), then — a dword per lane each — the picture's and the three SAO jobs' */
-    const int brec = (int)mi355_global_v(reinterpret_cast<const uint32_t *>(ctbs + blockIdx.x))[lane < 5 ? lane : 4];
-    const int pic = lane_value(brec, 0), x0 = lane_value(brec, 1) & 0xFFFF, y0 = (int)((uint32_t)lane_value(brec, 1) >> 16);
-    const int prec = (int)mi355_global_v(reinterpret_cast<const uint32_t *>(pics + pic))[lane < 34 ? lane : 33];
+    const int brec = rec_fetch(ctbs + blockIdx.x, lane);
+    const int pic = (int)rec_dw(brec, 0), x0 = (int)(rec_dw(brec, 1) & 0xFFFF), y0 = (int)(rec_dw(brec, 1) >> 16);
+    const int prec = rec_fetch(pics + pic, lane);
     /* the SAO job of the component this wave takes in the last phase: luma for every wave's first two rounds; the chroma planes: waves 0, 1 Cb, waves 2, 3 Cr */
-    const mi355_hevc_sao_ctb_job *job_y = sao + (uint32_t)lane_value(brec, 2), *job_c = sao + (uint32_t)lane_value(brec, wave < 2 ? 3 : 4);
-    const int srec_y = (int)mi355_global_v(reinterpret_cast<const uint32_t *>(job_y))[lane < 42 ? lane : 41];
-    const int srec_c = (int)mi355_global_v(reinterpret_cast<const uint32_t *>(job_c))[lane < 42 ? lane : 41];
-    mi355_hevc_lf_picture p;
-    {
-        uint32_t wds[34];
-#pragma unroll
-        for (int k = 0; k < 34; k++) wds[k] = (uint32_t)lane_value(prec, k);
-        __builtin_memcpy(&p, wds, sizeof(p));
-    }
+    const int srec_y = rec_fetch(sao + rec_dw(brec, 2), lane), srec_c = rec_fetch(sao + rec_dw(brec, wave < 2 ? 3 : 4), lane);
+    const mi355_hevc_lf_picture p = lf_picture_of(prec);
     const int W = p.width, H = p.height;
     /* ---- the tile: luma rows / columns -8 .. S + 7 in pieces of eight samples (rows -4 .. S + 3 are used), chroma -8 .. S / 2 + 7 (rows -2 .. S / 2 + 1) */
     {
@@ -1349,36 +1296,26 @@ __global__ void __launch_bounds__(FT_THREADS) k_hevc_filter_ctbs(const mi355_hev
 #pragma unroll 1
     for (int round = 0; round < 2; round++) {
         const bool chroma = round == 1;
-        const int rec = chroma ? srec_c : srec_y;
-#define SAO_REC(dw) ((uint32_t)lane_value(rec, (dw)))
-        uint8_t *dst0 = mi355_global(reinterpret_cast<uint8_t *>((uintptr_t)SAO_REC(0) | ((uintptr_t)SAO_REC(1) << 32)));
-        const int stride = (int)SAO_REC(4), np = (int)((SAO_REC(5) >> 8) & 0xFF);
-        const uint32_t p0a = SAO_REC(6 + 5), p0b = SAO_REC(6 + 6), p0c = SAO_REC(6 + 7), p0d = SAO_REC(6 + 8);
-        const int type = (int)((p0a >> 8) & 0xFF), RW = (int)(int16_t)(p0d & 0xFFFF), RH = (int)(int16_t)(p0d >> 16);
-        uint32_t flags = p0b & 0x00FFFFFFu, types = 0;
-        if (np > 1) { flags |= SAO_REC(15 + 6) & 0x00FFFFFFu; types |= ((SAO_REC(15 + 5) >> 8) & 0xFF) ^ (uint32_t)type; }
-        if (np > 2) { flags |= SAO_REC(24 + 6) & 0x00FFFFFFu; types |= ((SAO_REC(24 + 5) >> 8) & 0xFF) ^ (uint32_t)type; }
-        if (np > 3) { flags |= SAO_REC(33 + 6) & 0x00FFFFFFu; types |= ((SAO_REC(33 + 5) >> 8) & 0xFF) ^ (uint32_t)type; }
-        const int32_t ov[5] = { (int32_t)SAO_REC(6), (int32_t)SAO_REC(7), (int32_t)SAO_REC(8), (int32_t)SAO_REC(9), (int32_t)SAO_REC(10) };
-        bool fits = np >= 1 && (p0a & 0xFF) == 0 && p0c == 0 && types == 0 && (RW & 3) == 0;
-        for (int e = 0; e < 5; e++) fits = fits && ov[e] > -128 && ov[e] < 128;
-        if (type == 2) fits = fits && flags == 0 && (RW & 7) == 0;
+        const SaoCtbRec r = sao_ctb_rec(chroma ? srec_c : srec_y);
+        const int type = r.type, RW = r.W, RH = r.H;
+        /* the forms this entry point takes (include/mi355_hevc_batch.h): the whole region in one pass — piece 0 the owner's own call, every piece of its type, offsets
+         * within a byte (of a copy job too), whole pieces of four samples copied or of eight filtered, no restored edge */
+        bool fits = r.np >= 1 && r.cls == 0 && r.dxy == 0 && r.types == 0 && (RW & 3) == 0 && r.small;
+        if (type == 2) fits = fits && r.flags == 0 && (RW & 7) == 0;
         if (type == 1) fits = fits && (RW & 7) == 0;
         /* the region in the tile, this thread's first step and the step count's stride */
         const uint8_t *region = chroma ? tile.c[wave < 2 ? 0 : 1] + (8 * FT_C + 8) * PX : tile.y + (8 * FT_Y + 8) * PX;
         const int tp = (chroma ? FT_C : FT_Y) * PX, first = chroma ? (tid & 127) : tid, nth = chroma ? 128 : FT_THREADS;
         if (!fits) {
-            /* a job outside the whole-region forms (pieces of different kinds, an edge that is restored, offsets beyond a byte): this entry point does not take it —
-             * the block's component is left unwritten and the device says so (include/mi355_hevc_batch.h) */
+            /* any other job: the block's component is left unwritten and the device says so */
             if (error_word && lane == 0) atomicOr(error_word, (uint32_t)MI355_ERR_FILTER_CTB_FORM);
             continue;
         }
-        const int eo = (int)((p0a >> 16) & 0xFF), bp = (int)(p0a >> 24), bo = type == 2 ? (int)(p0b >> 24) : 0;
-        if (type == 0) ft_copy_region<WIDE>(region, tp, dst0, stride, RW, RH, first, nth);
-        else if (type == 1) ft_sao_region<WIDE, false, false>(region, tp, dst0, stride, RW, RH, eo, bp, ov, bd, 0, first, nth);
-        else if (bo) ft_sao_region<WIDE, true, true>(region, tp, dst0, stride, RW, RH, eo, bp, ov, bd, bo, first, nth);
-        else ft_sao_region<WIDE, true, false>(region, tp, dst0, stride, RW, RH, eo, bp, ov, bd, 0, first, nth);
-#undef SAO_REC
+        const int bo = type == 2 ? r.borders : 0;
+        if (type == 0) ft_copy_region<WIDE>(region, tp, r.dst, r.stride, RW, RH, first, nth);
+        else if (type == 1) ft_sao_region<WIDE, false, false>(region, tp, r.dst, r.stride, RW, RH, r.eo, r.band_position, r.ov, bd, 0, first, nth);
+        else if (bo) ft_sao_region<WIDE, true, true>(region, tp, r.dst, r.stride, RW, RH, r.eo, r.band_position, r.ov, bd, bo, first, nth);
+        else ft_sao_region<WIDE, true, false>(region, tp, r.dst, r.stride, RW, RH, r.eo, r.band_position, r.ov, bd, 0, first, nth);
     }
 }
 

@@ -616,7 +616,9 @@ __device__ __forceinline__ bool hevc_lf_luma_core(const int p[4], const int q[4]
     return true;
 }
 /* `groups`: false = lanes 0..7 filter one edge (the other lanes idle); true = every group of eight lanes
- * filters its own edge (per-lane arguments) */
+ * filters its own edge (per-lane arguments).  WHOLE_LINES false: the samples one by one whatever the direction
+ * (for a caller whose lines do not allow the whole-line access below: samples in LDS) */
+template <bool WHOLE_LINES = true>
 __device__ inline void hevc_lf_luma_wave(uint8_t *pix, int xs, int ys, int beta, const int *tc_, const uint8_t *no_p_,
                                          const uint8_t *no_q_, int bd, bool groups = false, bool enabled = true)
 {
@@ -624,7 +626,7 @@ __device__ inline void hevc_lf_luma_wave(uint8_t *pix, int xs, int ys, int beta,
     const bool act = enabled && (groups || lane < 8);
     /* across a vertical edge (xs == 1) the eight samples of a line are contiguous: one 16-byte (8-byte for 8-bit samples)
      * access each way instead of eight loads and up to six stores */
-    const bool row_wise = xs == 1;
+    const bool row_wise = WHOLE_LINES && xs == 1;
     int p[4], q[4];
     if (act && row_wise) {
         if (bd > 8) {
