@@ -34,6 +34,12 @@
  *                          MI355_SWS_LINES=1 the inner loops (hyScale / hcScale of a deeper source: mi355_sws_hscale16to15).  Declined: what
  *                          taken() / planar_format() decline, contexts with an input converter, big-endian sources and the plane copies
  *                          (no filter banks: planarCopyWrapper).  mi355_sws_describe / _planar keep their answers (yuv420p only).
+ *   NV12 / NV21            destinations of the generic scaler take the same two forms under the same conditions as the three-plane ones
+ *                          (MI355_SWS_DST_NV12 / _NV21; the inner-loop form also forwards c->yuv2nv12cX to mi355_sws_yuv2nv12cX).
+ *                          mi355_sws_describe_src() also recognises the unscaled packer (yuv420p -> nv12 / nv21 at equal size,
+ *                          planarToNv12Wrapper: unscaled_special = 1 with the format) for callers of the C ABI; the whole-picture binding
+ *                          cannot take it — ff_get_unscaled_swscale sets c->swscale outside the two wrapped selectors — so such a
+ *                          context runs the reference's function.
  * The device is MI355_DEVICE (default 0), as for the decoder bridges.
  */
 #include <pthread.h>
@@ -102,6 +108,8 @@ static int planar_format(const SwsContext *c)
     case AV_PIX_FMT_YUV420P: return MI355_SWS_DST_YUV420P;
     case AV_PIX_FMT_YUV422P: return MI355_SWS_DST_YUV422P;
     case AV_PIX_FMT_YUV444P: return MI355_SWS_DST_YUV444P;
+    case AV_PIX_FMT_NV12:    return MI355_SWS_DST_NV12;
+    case AV_PIX_FMT_NV21:    return MI355_SWS_DST_NV21;
     default: return 0;
     }
 }
@@ -142,11 +150,14 @@ static int source_of(const SwsContext *c, mi355_sws_src *s)
     memcpy(s->dither, ff_dither_8x8_128, sizeof(s->dither));      /* the rows should_dither selects (swscale.c:553-556) */
     return 0;
 }
-/* 0: rgb24, MI355_SWS_DST_*: planar, -1: a context this path leaves to the reference.  special: the context's swscale is yuv2rgb_c_24_rgb */
+/* 0: rgb24, MI355_SWS_DST_*: planar or semi-planar, -1: a context this path leaves to the reference.  special: the context's swscale is
+ * yuv2rgb_c_24_rgb or, with an NV12 / NV21 destination, planarToNv12Wrapper */
 static int src_format(const SwsContext *c, mi355_sws_src *s, int special)
 {
     if (source_of(c, s) != 0 || (c->flags & SWS_FULL_CHR_H_INT)) return -1;       /* (every destination below is 8 bits) */
     if (c->lumToYV12 || c->chrToYV12 || c->readLumPlanar || c->readChrPlanar || c->alpToYV12 || c->readAlpPlanar) return -1;      /* an input converter */
+    if (special && (c->dstFormat == AV_PIX_FMT_NV12 || c->dstFormat == AV_PIX_FMT_NV21))          /* the packer: planarToNv12Wrapper */
+        return c->srcFormat == AV_PIX_FMT_YUV420P ? (c->dstFormat == AV_PIX_FMT_NV12 ? MI355_SWS_DST_NV12 : MI355_SWS_DST_NV21) : -1;
     if (special) return c->dstFormat == AV_PIX_FMT_RGB24 && s->depth == 8 && s->hsub == 1 ? 0 : -1;
     /* the generic scaler: no fast bilinear, no range conversion, no chroma line drop, and its four banks (an unscaled converter or a
      * plane copy has none, utils.c:1043-1048) */
@@ -157,6 +168,8 @@ static int src_format(const SwsContext *c, mi355_sws_src *s, int special)
     case AV_PIX_FMT_YUV420P: return MI355_SWS_DST_YUV420P;
     case AV_PIX_FMT_YUV422P: return MI355_SWS_DST_YUV422P;
     case AV_PIX_FMT_YUV444P: return MI355_SWS_DST_YUV444P;
+    case AV_PIX_FMT_NV12:    return MI355_SWS_DST_NV12;
+    case AV_PIX_FMT_NV21:    return MI355_SWS_DST_NV21;
     default: return -1;
     }
 }
@@ -183,7 +196,11 @@ static int describe_src(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *
 int mi355_sws_describe_src(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *dst_format)
 {
     int special = 0;
-    if (!c->vLumFilter) {
+    if (!c->vLumFilter && (c->dstFormat == AV_PIX_FMT_NV12 || c->dstFormat == AV_PIX_FMT_NV21)) {
+        /* swscale_unscaled.c:1040-1044: whatever the flags */
+        if (c->srcFormat != AV_PIX_FMT_YUV420P || c->srcW != c->dstW || c->srcH != c->dstH) return -1;
+        special = 1;
+    } else if (!c->vLumFilter) {
         if (c->dstFormat != AV_PIX_FMT_RGB24 || (c->flags & SWS_ACCURATE_RND) || (c->dstH & 1) || c->srcW != c->dstW || c->srcH != c->dstH ||
             (c->srcFormat != AV_PIX_FMT_YUV420P && c->srcFormat != AV_PIX_FMT_YUV422P)) return -1;
         special = 1;                                             /* swscale_unscaled.c:1051-1055 */
@@ -245,6 +262,13 @@ static void t1_plane1(const int16_t *src, uint8_t *dest, int dstW, const uint8_t
     mi355_sws_yuv2plane1_8(src, dest, dstW, dither, offset);
 }
 
+/* yuv2nv12cX_c (output.c:267-301): the semi-planar output's chroma loop, with the two context fields it reads */
+static void t1_nv12cX(SwsContext *c, const int16_t *chrFilter, int chrFilterSize, const int16_t **chrUSrc, const int16_t **chrVSrc, uint8_t *dest, int chrDstW)
+{
+    n_calls++;
+    mi355_sws_yuv2nv12cX(chrFilter, chrFilterSize, chrUSrc, chrVSrc, dest, chrDstW, c->chrDither8, c->dstFormat == AV_PIX_FMT_NV21);
+}
+
 void ff_sws_init_mi355x(SwsContext *c)
 {
     mi355_sws_src s;
@@ -254,6 +278,7 @@ void ff_sws_init_mi355x(SwsContext *c)
         c->hyScale = c->hcScale = s.depth > 8 ? t1_hscale16 : t1_hscale;
         c->yuv2planeX = t1_planeX;
         c->yuv2plane1 = t1_plane1;
+        if (c->yuv2nv12cX) c->yuv2nv12cX = t1_nv12cX;
         return;
     }
     /* rgb24: yuv420p as before (taken(): also contexts with range conversion, which swscale() applies between the loops); the other sources
@@ -352,7 +377,8 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
     /* a planar context: all three destination planes; range conversion set since the context was bound (sws_setColorspaceDetails) is
      * the reference's for that picture */
     mi355_sws_src s_now;
-    const int planar_ok = b && b->planar && dstStride[1] > 0 && dstStride[2] > 0 &&
+    const int semi = b && (b->planar == MI355_SWS_DST_NV12 || b->planar == MI355_SWS_DST_NV21);      /* two planes: dstStride[2] is not looked at */
+    const int planar_ok = b && b->planar && dstStride[1] > 0 && (semi || dstStride[2] > 0) &&
                           (b->other ? src_format(c, &s_now, 0) : planar_format(c)) == b->planar;
     /* an rgb24 context of another source: range conversion set since it was bound is the reference's for that picture, as above */
     const int other_ok = !b || !b->other || b->planar || src_format(c, &s_now, b->special) == 0;

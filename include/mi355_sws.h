@@ -1,7 +1,8 @@
 /*
  * mi355_sws.h — C ABI of the libswscale part of the hot path:
  * horizontal 8->15 bit FIR, vertical FIR to planar 8 bit or through the yuv->rgb LUTs to RGB24,
- * and the unscaled yuv420p -> rgb24 converter; whole pictures to RGB24 or to planar yuv420p / yuv422p / yuv444p.
+ * and the unscaled yuv420p -> rgb24 converter; whole pictures to RGB24, to planar yuv420p / yuv422p / yuv444p or to semi-planar
+ * NV12 / NV21 (yuv2nv12cX, and the unscaled yuv420p -> NV12 / NV21 packer).
  *
  * The reference keeps these behind function pointers of the (private) SwsContext
  * (libswscale/swscale_internal.h:253-540): hyScale/hcScale :526-531, yuv2plane1/yuv2planeX/
@@ -81,7 +82,8 @@ enum {
     MI355_SWS_K_GENERIC_C = 5,    /* ... 48 / 24 */
     MI355_SWS_K_PLANAR_A = 6,     /* a planar destination (mi355_sws_create_planar): the tile kernel holding 28 luma / 16 chroma source lines */
     MI355_SWS_K_PLANAR_B = 7,     /* ... 40 / 24 */
-    MI355_SWS_K_PLANAR_C = 8      /* ... 48 / 48 */
+    MI355_SWS_K_PLANAR_C = 8,     /* ... 48 / 48 */
+    MI355_SWS_K_NV12_PACK = 9     /* the unscaled yuv420p -> NV12 / NV21 packer (k_sws_nv12_pack); scaled NV12 / NV21 contexts report PLANAR_A / B / C */
 };
 typedef struct mi355_sws_plan_info {
     int kernel;                   /* MI355_SWS_K_* */
@@ -115,6 +117,24 @@ int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *ctx, const mi355_sws_planar
 int mi355_sws_scale_planar(mi355_sws_ctx *ctx, const uint8_t *const src[3], const int src_stride[3],
                            uint8_t *const dst[3], const int dst_stride[3]);
 
+/* ---- semi-planar destinations: NV12 / NV21, 8 bit (yuv2nv12cX_c output.c:267-301; planarToNv12Wrapper swscale_unscaled.c:138-156) ----
+ * Both creators above and below take these two values as dst_format (4 .. 15 stay refused).  The descriptor is the reference's for that
+ * context: chrDstW = AV_CEIL_RSHIFT(dstW, 1), vChr.n = chrDstH = AV_CEIL_RSHIFT(dstH, 1) (anything else is refused with a message), the LUTs
+ * are not used.  Frames stay mi355_sws_planar_frame through mi355_sws_scale_planar_frames_dev / mi355_sws_scale_planar: dst[0] is luma,
+ * dst[1] the interleaved plane — 2 * chrDstW bytes (U V U V ..., NV21: V U V U ...) on each of chrDstH rows; dst[2] and dst_stride[2] are
+ * never read and may be NULL / 0.
+ * The unscaled packer: desc->unscaled_special = 1 with one of these destinations — 8-bit 4:2:0 source, srcW == dstW, srcH == dstH, no banks
+ * (any other combination: NULL and a message).  Like the reference it copies srcW x srcH luma bytes and interleaves srcW / 2 pairs on
+ * srcH / 2 rows, both ROUNDED DOWN: the last pair of an odd width's chroma rows and the last chroma row of an odd height stay untouched. */
+enum { MI355_SWS_DST_NV12 = 16, MI355_SWS_DST_NV21 = 17 };
+/* the destination side of a context (read only) */
+typedef struct mi355_sws_dest_info {
+    int format;                   /* 0 rgb24, else MI355_SWS_DST_* */
+    int planes;                   /* 1 rgb24, 2 NV12 / NV21, 3 planar */
+    int chr_bytes, chr_rows;      /* bytes per row and rows the context writes to each chroma plane (0 / 0 for rgb24; the packer: 2 * (srcW / 2), srcH / 2) */
+} mi355_sws_dest_info;
+int mi355_sws_destination(const mi355_sws_ctx *ctx, mi355_sws_dest_info *info);   /* 0, -1 bad argument */
+
 /* ---- other sources: planar yuv 4:2:0 / 4:2:2 / 4:4:4 at 8, 9 or 10 bits (yuv420p ... yuv444p10le) -----------------------------------------
  * The descriptor is the one above as the reference's init built it for that source (chrSrcW / chrSrcH and the four banks follow the
  * subsampling, utils.c:1035-1040).  A source deeper than 8 bits takes hScale16To15_c (swscale.c:110-130) in place of hScale8To15_c, and an
@@ -131,7 +151,7 @@ typedef struct mi355_sws_src {
 } mi355_sws_src;
 /* dst_format 0: rgb24 (a context for mi355_sws_scale / mi355_sws_scale_frames_dev), else MI355_SWS_DST_* (for the planar entry points).
  * NULL (and a message) for banks the device tiles cannot hold and for combinations outside the list above; the unscaled special converter
- * (desc->unscaled_special) takes 8-bit 4:2:0 and 4:2:2 only.  depth 8, shifts 1,1 builds the context of mi355_sws_create /
+ * (desc->unscaled_special) takes 8-bit 4:2:0 and 4:2:2 only to rgb24, and 8-bit 4:2:0 only to NV12 / NV21 (the packer).  depth 8, shifts 1,1 builds the context of mi355_sws_create /
  * mi355_sws_create_planar. */
 mi355_sws_ctx *mi355_sws_create_src(const mi355_sws_desc *desc, const mi355_sws_src *src, int dst_format);
 /* the source side of a context (read only) */
@@ -155,6 +175,9 @@ void mi355_sws_hscale16to15(int16_t *dst, int dstW, const uint8_t *src, const in
 void mi355_sws_yuv2planeX_8(const int16_t *filter, int filterSize, const int16_t **src, uint8_t *dest, int dstW,
                             const uint8_t *dither, int offset);
 void mi355_sws_yuv2plane1_8(const int16_t *src, uint8_t *dest, int dstW, const uint8_t *dither, int offset);
+/* yuv2nv12cX_c output.c:267-301 with the two context fields it reads spelled out: c->chrDither8 and (c->dstFormat == AV_PIX_FMT_NV21) */
+void mi355_sws_yuv2nv12cX(const int16_t *chrFilter, int chrFilterSize, const int16_t **chrUSrc, const int16_t **chrVSrc, uint8_t *dest, int chrDstW,
+                          const uint8_t *chrDither, int swap_uv);
 /* yuv2rgb24_X_c / _2_c / _1_c  output.c:937-1110 with target AV_PIX_FMT_RGB24, no alpha */
 void mi355_sws_yuv2rgb24_X(const mi355_sws_luts *luts, const int16_t *lumFilter, const int16_t **lumSrc, int lumFilterSize,
                            const int16_t *chrFilter, const int16_t **chrUSrc, const int16_t **chrVSrc, int chrFilterSize,

@@ -1,9 +1,9 @@
 /*
  * sws.hip — the libswscale part of the path: planar yuv 4:2:0 / 4:2:2 / 4:4:4 sources at 8, 9 or 10 bits (16-bit
- * little-endian samples above 8: hScale16To15_c swscale.c:110-130 in place of hScale8To15_c) -> rgb24 and -> 8-bit yuv420p / yuv422p / yuv444p
- * (dithered from a deeper source, swscale.c:553-556).  This file: the context, the plan (which kernel a context gets) and the entry points of
- * include/mi355_sws.h.  The device side is sws_dev.h: k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1 and the k_sws_line_* kernels of
- * the Tier-1 entry points.
+ * little-endian samples above 8: hScale16To15_c swscale.c:110-130 in place of hScale8To15_c) -> rgb24, -> 8-bit yuv420p / yuv422p / yuv444p
+ * and -> NV12 / NV21 (dithered from a deeper source, swscale.c:553-556), and the unscaled 8-bit yuv420p -> NV12 / NV21 packer.  This file:
+ * the context, the plan (which kernel a context gets) and the entry points of include/mi355_sws.h.  The device side is sws_dev.h:
+ * k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1, k_sws_nv12_pack and the k_sws_line_* kernels of the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
  */
 #include "mi355_rt.h"
@@ -149,11 +149,12 @@ static mi355_sws_ctx *ctx_upload(mi355_sws_ctx *c)
 }
 
 /* what the create entry points share: the source check, the destination family (rgb24, or planar: dst_format MI355_SWS_DST_*), the bank
- * validation with its diagnostics.  The unscaled special converter (rgb24 only) has no banks. */
+ * validation with its diagnostics.  The unscaled special converter (rgb24) and the unscaled packer (NV12 / NV21) have no banks. */
 static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src *src, bool planar, int dst_format, const char *who)
 {
-    if (planar && (!desc || dst_format < MI355_SWS_DST_YUV420P || dst_format > MI355_SWS_DST_YUV444P)) {
-        std::fprintf(stderr, "mi355dsp: %s: destination format %d is not yuv420p / yuv422p / yuv444p\n", who, dst_format);
+    const bool semi = dst_format == MI355_SWS_DST_NV12 || dst_format == MI355_SWS_DST_NV21;
+    if (planar && (!desc || ((dst_format < MI355_SWS_DST_YUV420P || dst_format > MI355_SWS_DST_YUV444P) && !semi))) {
+        std::fprintf(stderr, "mi355dsp: %s: destination format %d is not yuv420p / yuv422p / yuv444p / nv12 / nv21\n", who, dst_format);
         return nullptr;
     }
     mi355_sws_ctx *c = ctx_new(desc);
@@ -168,8 +169,24 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
     if (planar) {
         h.planar = dst_format;
         h.hshift = dst_format == MI355_SWS_DST_YUV444P ? 0 : 1;
-        h.vshift = dst_format == MI355_SWS_DST_YUV420P ? 1 : 0;
+        h.vshift = dst_format == MI355_SWS_DST_YUV420P || semi ? 1 : 0;
         h.chrDstH = (h.dstH + (1 << h.vshift) - 1) >> h.vshift;               /* AV_CEIL_RSHIFT, utils.c:1040 */
+        if (semi && h.special) {
+            /* the unscaled packer (planarToNv12Wrapper): 8-bit 4:2:0 at equal size, no banks */
+            if (h.depth != 8 || !h.src_hsub || !h.src_vsub || h.srcW != h.dstW || h.srcH != h.dstH || h.chrDstW != (h.dstW + 1) >> 1) {
+                std::fprintf(stderr, "mi355dsp: %s: the unscaled nv12 / nv21 packer takes 8-bit 4:2:0 at equal size only (%d bit, shifts %d/%d, %dx%d -> %dx%d, chrDstW %d)\n",
+                             who, h.depth, h.src_hsub, h.src_vsub, h.srcW, h.srcH, h.dstW, h.dstH, h.chrDstW);
+                delete c;
+                return nullptr;
+            }
+            return ctx_upload(c);
+        }
+        if (semi && (h.chrDstW != (h.dstW + 1) >> 1 || desc->vChr.n != h.chrDstH)) {
+            std::fprintf(stderr, "mi355dsp: %s: chrDstW %d / vChr.n %d are not those of a 4:2:0 destination of %dx%d (%d / %d)\n", who, h.chrDstW, desc->vChr.n,
+                         h.dstW, h.dstH, (h.dstW + 1) >> 1, h.chrDstH);
+            delete c;
+            return nullptr;
+        }
         ok = !h.special && desc->hLum.coef && desc->hLum.pos && desc->hChr.coef && desc->hChr.pos && desc->vLum.coef && desc->vLum.pos &&
              desc->vChr.coef && desc->vChr.pos && h.chrDstW == (h.dstW + (1 << h.hshift) - 1) >> h.hshift;
     } else if (h.special) return ctx_upload(c);
@@ -224,6 +241,7 @@ static int sws_kernel(const SwsDev &h)
         return 2;
     };
     static_assert(MI355_SWS_K_GENERIC_C == MI355_SWS_K_GENERIC_A + 2 && MI355_SWS_K_PLANAR_C == MI355_SWS_K_PLANAR_A + 2, "A / B / C follow each other");
+    if (h.planar && h.special) return MI355_SWS_K_NV12_PACK;
     if (h.planar) return MI355_SWS_K_PLANAR_A + instance(PLANAR_SHAPES);
     if (h.special) return MI355_SWS_K_C24;
     /* a context that does not scale: straight from the source bytes (k_sws_ident1; MI355_SWS_NO_IDENT1=1, developer switch: through the tile all the same) */
@@ -249,7 +267,22 @@ extern "C" int mi355_sws_source(const mi355_sws_ctx *c, mi355_sws_source_info *p
 {
     if (!c || !p) return -1;
     p->depth = c->h.depth; p->hsub = c->h.src_hsub; p->vsub = c->h.src_vsub;
-    p->hstaged = sws_kernel(c->h) >= MI355_SWS_K_GENERIC_A && c->h.hstage && c->hfit;
+    const int k = sws_kernel(c->h);
+    p->hstaged = k >= MI355_SWS_K_GENERIC_A && k <= MI355_SWS_K_PLANAR_C && c->h.hstage && c->hfit;
+    return 0;
+}
+
+static bool semi_planar(const SwsDev &h) { return h.planar == MI355_SWS_DST_NV12 || h.planar == MI355_SWS_DST_NV21; }
+
+extern "C" int mi355_sws_destination(const mi355_sws_ctx *c, mi355_sws_dest_info *p)
+{
+    if (!c || !p) return -1;
+    const SwsDev &h = c->h;
+    p->format = h.planar;
+    p->planes = !h.planar ? 1 : (semi_planar(h) ? 2 : 3);
+    /* the packer rounds both extents down (planarToNv12Wrapper) */
+    p->chr_bytes = !h.planar ? 0 : (semi_planar(h) ? 2 * (h.special ? h.srcW >> 1 : h.chrDstW) : h.chrDstW);
+    p->chr_rows = !h.planar ? 0 : (h.special ? h.srcH >> 1 : h.chrDstH);
     return 0;
 }
 
@@ -278,6 +311,18 @@ template <typename ST> static void launch_planar(int i, int hshift, dim3 grid, h
     if (i == 0) launch_planar<0, ST>(hshift, grid, s, d, frames);
     else if (i == 1) launch_planar<1, ST>(hshift, grid, s, d, frames);
     else launch_planar<2, ST>(hshift, grid, s, d, frames);
+}
+/* ... of a semi-planar destination (NV12 / NV21: 4:2:0, the SEMI instances of k_sws_planar) */
+template <int I, typename ST> static void launch_semi(dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+{
+    constexpr SwsShape S = PLANAR_SHAPES[I];
+    hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, ST, true>), grid, dim3(NT), 0, s, d, frames);
+}
+template <typename ST> static void launch_semi(int i, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+{
+    if (i == 0) launch_semi<0, ST>(grid, s, d, frames);
+    else if (i == 1) launch_semi<1, ST>(grid, s, d, frames);
+    else launch_semi<2, ST>(grid, s, d, frames);
 }
 /* workgroups per CU of the instances (8-bit, then 16-bit: their staging lines are STAGE_BYTES16) */
 constexpr int generic_waves(int i, int stage) { return sws_waves(sws_lds_bytes(GENERIC_SHAPES[i].lcap, GENERIC_SHAPES[i].ccap, stage)); }
@@ -318,9 +363,18 @@ extern "C" int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *c, const mi355_s
     hipStream_t s = static_cast<hipStream_t>(stream);
     const SwsDev &h = c->h;
     DeviceScope on(c->device);
+    const int k = sws_kernel(h);
+    if (k == MI355_SWS_K_NV12_PACK) {
+        hipLaunchKernelGGL(k_sws_nv12_pack, dim3((h.srcW + PACK_COLS - 1) / PACK_COLS, (h.srcH + PACK_ROWS - 1) / PACK_ROWS, nframes), dim3(NT), 0, s,
+                           h.srcW, h.srcH, h.planar == MI355_SWS_DST_NV21 ? 1 : 0, d_frames);
+        return hipGetLastError() == hipSuccess ? 0 : -2;
+    }
     const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
-    const int i = sws_kernel(h) - MI355_SWS_K_PLANAR_A;
-    if (h.depth > 8) launch_planar<uint16_t>(i, h.hshift, grid, s, c->d, d_frames);
+    const int i = k - MI355_SWS_K_PLANAR_A;
+    if (semi_planar(h)) {
+        if (h.depth > 8) launch_semi<uint16_t>(i, grid, s, c->d, d_frames);
+        else launch_semi<uint8_t>(i, grid, s, c->d, d_frames);
+    } else if (h.depth > 8) launch_planar<uint16_t>(i, h.hshift, grid, s, c->d, d_frames);
     else launch_planar<uint8_t>(i, h.hshift, grid, s, c->d, d_frames);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -361,7 +415,7 @@ static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int
         ok = ok && hipMalloc(&nf, planar ? sizeof(mi355_sws_planar_frame) : sizeof(mi355_sws_frame)) == hipSuccess;
         if (ok && planar) {
             mi355_sws_planar_frame f;
-            for (int p = 0; p < 3; p++) { f.src[p] = ns[p]; f.src_stride[p] = pw[p]; f.dst[p] = nd + doff[p]; f.dst_stride[p] = dp[p]; }
+            for (int p = 0; p < 3; p++) { f.src[p] = ns[p]; f.src_stride[p] = pw[p]; f.dst[p] = p < ndst ? nd + doff[p] : nullptr; f.dst_stride[p] = dp[p]; }
             ok = hipMemcpy(nf, &f, sizeof(f), hipMemcpyHostToDevice) == hipSuccess;
         } else if (ok) {
             mi355_sws_frame f;
@@ -388,7 +442,7 @@ static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int
         return -2;
     }
     for (int p = 0; p < ndst; p++)
-        if (hipMemcpy2DAsync(dst[p], dst_stride[p], c->d_dst + doff[p], dp[p], back[p], oh[p], hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+        if (back[p] > 0 && oh[p] > 0 && hipMemcpy2DAsync(dst[p], dst_stride[p], c->d_dst + doff[p], dp[p], back[p], oh[p], hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
             (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4;
         }
     if (hipStreamSynchronize(c->stream) != hipSuccess) return -4;
@@ -409,6 +463,12 @@ extern "C" int mi355_sws_scale_planar(mi355_sws_ctx *c, const uint8_t *const src
 {
     if (!c || !src || !src_stride || !dst || !dst_stride || !c->h.planar) return -1;
     const SwsDev &h = c->h;
+    if (semi_planar(h)) {
+        /* two planes, the second one 2 * chrDstW bytes of pairs; the packer writes (and so hands back) the rounded-down extents only */
+        const int ow[2] = { h.dstW, 2 * (h.special ? h.srcW >> 1 : h.chrDstW) }, oh[2] = { h.dstH, h.special ? h.srcH >> 1 : h.chrDstH };
+        const int r = scale_staged(c, src, src_stride, 2, dst, dst_stride, ow, oh, ow);
+        return r ? r : h.dstH;
+    }
     const int ow[3] = { h.dstW, h.chrDstW, h.chrDstW }, oh[3] = { h.dstH, h.chrDstH, h.chrDstH };
     const int r = scale_staged(c, src, src_stride, 3, dst, dst_stride, ow, oh, ow);
     return r ? r : h.dstH;
@@ -476,6 +536,23 @@ extern "C" void mi355_sws_yuv2planeX_8(const int16_t *filter, int filterSize, co
 extern "C" void mi355_sws_yuv2plane1_8(const int16_t *src, uint8_t *dest, int dstW, const uint8_t *dither, int offset)
 {
     plane_line(nullptr, 0, &src, dest, dstW, dither, offset);
+}
+
+extern "C" void mi355_sws_yuv2nv12cX(const int16_t *chrFilter, int chrFilterSize, const int16_t **chrUSrc, const int16_t **chrVSrc, uint8_t *dest, int chrDstW,
+                                     const uint8_t *chrDither, int swap_uv)
+{
+    Arena &a = arena();
+    const int n = chrFilterSize, pitch = (chrDstW + 7) & ~7;
+    a.reserve((size_t)2 * n * pitch * 2 + (size_t)n * 2 + (size_t)2 * chrDstW + 192);
+    const size_t o_u = pack_rows(a, chrUSrc, n, chrDstW, pitch), o_v = pack_rows(a, chrVSrc, n, chrDstW, pitch);
+    const size_t o_f = a.take((size_t)n * 2 + 2), o_di = a.take(8), o_d = a.take((size_t)2 * chrDstW);
+    std::memcpy(a.h<int16_t>(o_f), chrFilter, (size_t)n * 2);
+    std::memcpy(a.h<uint8_t>(o_di), chrDither, 8);
+    a.upload();
+    launch_line(k_sws_line_nv12, a, a.d<const int16_t>(o_f), n, a.d<const int16_t>(o_u), a.d<const int16_t>(o_v), pitch, a.d<uint8_t>(o_d), chrDstW,
+                a.d<const uint8_t>(o_di), swap_uv);
+    a.download();
+    std::memcpy(dest, a.h<uint8_t>(o_d), (size_t)2 * chrDstW);
 }
 
 static void rgb_line(const mi355_sws_luts *luts, int mode, const int16_t *lumF, const int16_t **l, int ls, const int16_t *chrF,

@@ -7,7 +7,9 @@
  *                   (yuv2rgb24_{1,2,X}_c output.c:937-1110) from LDS, RGB rows staged in LDS and
  *                   written as dwords.  No int16 intermediate ever goes to HBM.
  *   k_sws_planar    the same loop's planar branch (swscale.c:618-645, yuv2planeX_8_c / yuv2plane1_8_c output.c:242-266): the
- *                   horizontal pass into LDS as above, the vertical pass from LDS straight to the three destination planes.
+ *                   horizontal pass into LDS as above, the vertical pass from LDS straight to the three destination planes — or, for
+ *                   NV12 / NV21 (yuv2nv12cX_c :267-301), to the luma plane and one plane of interleaved chroma pairs.
+ *   k_sws_nv12_pack the unscaled packer planarToNv12Wrapper (swscale_unscaled.c:138-156) for 8-bit yuv420p -> NV12 / NV21.
  *   k_sws_c24       the unscaled converter yuv2rgb_c_24_rgb (yuv2rgb.c:335-363) for 8-bit yuv420p and yuv422p.
  *   k_sws_ident1    the generic scaler on an 8-bit context that does not scale, from the source bytes.
  * The tile kernels are instantiated per sample type: the uint16_t instances differ in the horizontal pass (its staging lines are twice
@@ -209,12 +211,17 @@ static inline uint32_t sws_pair(uint32_t w, int k) { return ((w >> (16 * k)) & 0
 static inline int sws_dot2(uint32_t a, uint32_t b, int c) { return c + (int16_t)(a & 0xFFFF) * (int16_t)(b & 0xFFFF) + (int16_t)(a >> 16) * (int16_t)(b >> 16); }
 static inline uint32_t sws_lo2(uint32_t a, uint32_t b) { return (a & 0xFFFFu) | (b << 16); }            /* (a.lo, b.lo) */
 static inline uint32_t sws_hi2(uint32_t a, uint32_t b) { return (a >> 16) | (b & 0xFFFF0000u); }        /* (a.hi, b.hi) */
+static inline uint32_t sws_zip_lo(uint32_t a, uint32_t b) { return (a & 0xFFu) | ((b & 0xFFu) << 8) | ((a & 0xFF00u) << 8) | ((b & 0xFF00u) << 16); }   /* a0 b0 a1 b1 */
+static inline uint32_t sws_zip_hi(uint32_t a, uint32_t b) { return sws_zip_lo(a >> 16, b >> 16); }                                               /* a2 b2 a3 b3 */
 #else
 __device__ __forceinline__ uint32_t sws_alignbyte(uint32_t hi, uint32_t lo, uint32_t s) { return __builtin_amdgcn_alignbyte(hi, lo, s); }
 /* bytes 2k, 2k + 1 of w as two 16-bit values */
 __device__ __forceinline__ uint32_t sws_pair(uint32_t w, int k) { return __builtin_amdgcn_perm(0u, w, k ? 0x0C030C02u : 0x0C010C00u); }
 __device__ __forceinline__ uint32_t sws_lo2(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }      /* (a.lo, b.lo) */
 __device__ __forceinline__ uint32_t sws_hi2(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }      /* (a.hi, b.hi) */
+/* the bytes of two dwords interleaved: a0 b0 a1 b1 / a2 b2 a3 b3 */
+__device__ __forceinline__ uint32_t sws_zip_lo(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05010400u); }
+__device__ __forceinline__ uint32_t sws_zip_hi(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07030602u); }
 typedef short sws_short2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int sws_dot2(uint32_t a, uint32_t b, int c)
 {
@@ -873,6 +880,100 @@ __device__ __forceinline__ void planar_pass(const int16_t *s, int lo, int maxl, 
     else planar_rows<0, GPP, NP, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, dith);
 }
 
+/* ---- semi-planar destinations: NV12 / NV21 (yuv2nv12cX_c, output.c:267-301) ------------------------------------------------------
+ * The chroma rows of a 4:2:0 destination as ONE plane of U V (NV21: V U) byte pairs.  Always the X form, also for a one-tap bank:
+ * ((dither << 12) + sum s_j * f_j) >> 19 with the coefficient — (s + d) >> 7 only while it is 4096.  U takes dither column i & 7, V
+ * column (i + 3) & 7 of row chrDstY & 7 (64 everywhere for an 8-bit source).
+ * A thread takes group g (eight samples) of U AND group g of V of one row: one ds_read_b128 each per tap, the row's taps for both.  An LDS
+ * line is U | V, 2 x 64 samples = 256 bytes = all 64 banks once, so every line starts on bank 0; eight lanes cover a row's U groups (banks
+ * 0..31) and its V groups lie 32 banks on.  A 16-lane group of ds_read_b128 is lanes {0-3, 12-15, 20-27} and its like: four quarter rows of
+ * four different rows, two of them on the same 16 banks if every lane read U — so the lanes of odd rows read V where the even rows read U and
+ * the other way round (the quarter rows of a lane group are two even and two odd rows on different halves: every bank once).  The two planes
+ * share their taps, so a lane just accumulates "first read" and "second read" and sorts them out when it packs.
+ * NTAP: 2 / 4 / 8 taps in registers (taps past fs carry a zero coefficient; one tap is the two-tap form), 0: fs taps read as it goes. */
+template <int NTAP, bool DITH>
+__device__ __forceinline__ void semiplanar_rows(const int16_t *s, int lo, int maxl, const int16_t *vC, const int32_t *vP, int fs, int row0, int nrows,
+                                                int gx0, int width, uint8_t *d0, int st, int tid, const uint8_t (*dith)[8], bool swap_uv)
+{
+    constexpr int CW = TW / 2, GPP = CW / 8;           /* samples of a plane's tile row, its groups */
+    for (int t = tid; t < nrows * GPP; t += NT) {
+        const int r = t / GPP, g = t % GPP, gx = gx0 + 8 * g, y = row0 + r;
+        if (gx >= width) continue;
+        const int first = imax(1 - fs, vP[y]);
+        const bool flip = (r & 1) != 0;                /* this lane reads V first */
+        const int16_t *colA = s + 8 * g + (flip ? CW : 0), *colB = s + 8 * g + (flip ? 0 : CW);
+        auto off = [&](int j) { return (size_t)(clampi(first + j, 0, maxl) - lo) * (2 * CW); };
+        int a[8], b[8];
+        if (DITH) {
+            const sws_u32x2 w = *reinterpret_cast<const sws_u32x2 *>(dith[y & 7]);
+            const uint64_t qu = ((uint64_t)w[1] << 32) | w[0], qv = (qu >> 24) | (qu << 40);      /* V: three columns on */
+            const uint64_t qa = flip ? qv : qu, qb = flip ? qu : qv;
+#pragma unroll
+            for (int k = 0; k < 8; k++) { a[k] = (int)((qa >> (8 * k)) & 0xFF) << 12; b[k] = (int)((qb >> (8 * k)) & 0xFF) << 12; }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++) a[k] = b[k] = 64 << 12;
+        }
+        if constexpr (NTAP == 0) {
+            for (int j = 0; j < fs; j++) {
+                const int f = vC[(size_t)y * fs + j];
+                const size_t o = off(j);
+                const sws_u32x4 la = *reinterpret_cast<const sws_u32x4 *>(colA + o), lb = *reinterpret_cast<const sws_u32x4 *>(colB + o);
+#pragma unroll
+                for (int k = 0; k < 8; k++) { a[k] += lane16(la, k) * f; b[k] += lane16(lb, k) * f; }
+            }
+        } else {
+            int lf[NTAP];
+#pragma unroll
+            for (int j = 0; j < NTAP; j++) lf[j] = vC[(size_t)y * fs + (j < fs ? j : 0)];   /* unconditional: in flight together */
+#pragma unroll
+            for (int j = 0; j < NTAP; j += 2) {
+                const size_t o0 = off(j < fs ? j : 0), o1 = off(j + 1 < fs ? j + 1 : 0);
+                const sws_u32x4 a0 = *reinterpret_cast<const sws_u32x4 *>(colA + o0), a1 = *reinterpret_cast<const sws_u32x4 *>(colA + o1);
+                const sws_u32x4 b0 = *reinterpret_cast<const sws_u32x4 *>(colB + o0), b1 = *reinterpret_cast<const sws_u32x4 *>(colB + o1);
+                const uint32_t cp = (j < fs ? (uint32_t)lf[j] & 0xFFFFu : 0u) | (j + 1 < fs ? (uint32_t)lf[j + 1] << 16 : 0u);
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    a[2 * q] = sws_dot2(sws_lo2(a0[q], a1[q]), cp, a[2 * q]);
+                    a[2 * q + 1] = sws_dot2(sws_hi2(a0[q], a1[q]), cp, a[2 * q + 1]);
+                    b[2 * q] = sws_dot2(sws_lo2(b0[q], b1[q]), cp, b[2 * q]);
+                    b[2 * q + 1] = sws_dot2(sws_hi2(b0[q], b1[q]), cp, b[2 * q + 1]);
+                }
+            }
+        }
+        /* the clipped bytes pass sws_opaque before they are packed, as in planar_rows (v_ashr_pk_u8_i32) */
+        uint32_t wa[2] = { 0, 0 }, wb[2] = { 0, 0 };
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            wa[k >> 2] |= sws_opaque((uint32_t)clip_u8(a[k] >> 19)) << (8 * (k & 3));
+            wb[k >> 2] |= sws_opaque((uint32_t)clip_u8(b[k] >> 19)) << (8 * (k & 3));
+        }
+        /* the plane whose byte comes first: U (NV21: V) — the first read on even rows, the second on odd ones */
+        const bool a_first = flip == swap_uv;
+        const uint32_t p0 = a_first ? wa[0] : wb[0], p1 = a_first ? wa[1] : wb[1], q0 = a_first ? wb[0] : wa[0], q1 = a_first ? wb[1] : wa[1];
+        const sws_u32x4 o = { sws_zip_lo(p0, q0), sws_zip_hi(p0, q0), sws_zip_lo(p1, q1), sws_zip_hi(p1, q1) };
+        uint8_t *d = d0 + (size_t)r * st + 2 * gx;
+        if (gx + 8 <= width && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
+            *reinterpret_cast<sws_u32x4 *>(d) = o;
+        } else if (gx + 8 <= width && (reinterpret_cast<uintptr_t>(d) & 7) == 0) {
+            reinterpret_cast<sws_u32x2 *>(d)[0] = sws_u32x2{ o[0], o[1] };
+            reinterpret_cast<sws_u32x2 *>(d)[1] = sws_u32x2{ o[2], o[3] };
+        } else {                                       /* the plane's right edge, or a row that is not 8-byte aligned */
+            const int n = 2 * imin(8, width - gx);
+            for (int k = 0; k < n; k++) d[k] = (uint8_t)(o[k >> 2] >> (8 * (k & 3)));
+        }
+    }
+}
+template <bool DITH>
+__device__ __forceinline__ void semiplanar_pass(const int16_t *s, int lo, int maxl, const int16_t *vC, const int32_t *vP, int fs, int row0, int nrows,
+                                                int gx0, int width, uint8_t *d0, int st, int tid, const uint8_t (*dith)[8], bool swap_uv)
+{
+    if (fs <= 2) semiplanar_rows<2, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st, tid, dith, swap_uv);
+    else if (fs <= 4) semiplanar_rows<4, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st, tid, dith, swap_uv);
+    else if (fs <= 8) semiplanar_rows<8, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st, tid, dith, swap_uv);
+    else semiplanar_rows<0, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st, tid, dith, swap_uv);
+}
+
 /* LDS of a planar workgroup: the luma lines, the chroma lines (U | V side by side, CW samples each) and the staging lines; no LUT, no output rows */
 __host__ __device__ constexpr int sws_planar_lds_bytes(int lum_lines, int chr_lines, int cw, int stage = STAGE_BYTES)
 {
@@ -886,8 +987,10 @@ __host__ __device__ constexpr int sws_planar_waves(int lum_lines, int chr_lines,
 /* One workgroup per output tile of TW luma columns x th luma rows (blockIdx.z: the picture of the batch).  The tile's chroma is CW = TW >> hshift
  * columns and the chroma rows cy with cy << vshift inside the tile's rows (swscale.c:618-645: a chroma row is written with the luma row
  * cy << vshift, chrSkipMask).  Horizontal pass of the source lines the tile needs into LDS (hscale_tile, as k_sws_generic), then the
- * vertical pass from LDS straight to the three planes.  LCAP / CCAP: a row of PLANAR_SHAPES. */
-template <int LCAP, int CCAP, int CW, typename ST = uint8_t>
+ * vertical pass from LDS straight to the three planes.  LCAP / CCAP: a row of PLANAR_SHAPES.
+ * SEMI: an NV12 / NV21 destination (4:2:0, CW = TW / 2) — the chroma rows go to ONE plane of byte pairs, fr.dst[1] (semiplanar_rows);
+ * fr.dst[2] is not used.  The three-plane instances are the SEMI false ones, unchanged. */
+template <int LCAP, int CCAP, int CW, typename ST = uint8_t, bool SEMI = false>
 #ifndef MI355_HIP_EMU_H
 __attribute__((amdgpu_waves_per_eu(sws_planar_waves(LCAP, CCAP, CW, stage_bytes<ST>()), sws_planar_waves(LCAP, CCAP, CW, stage_bytes<ST>()))))
 #endif
@@ -920,9 +1023,81 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
     const uint8_t (*dith)[8] = DITH ? mi355_global(cp)->dither : nullptr;
     planar_pass<TW / 8, 1, DITH>(&s_lum[0][0], llo, c.srcH - 1, c.vLumC, c.vLumP, ls, y0, y1 - y0 + 1, x0, c.dstW,
                                  fr.dst[0] + (size_t)y0 * fr.dst_stride[0], fr.dst_stride[0], nullptr, 0, tid, dith);
+    if constexpr (SEMI) {
+        static_assert(CW == TW / 2, "a semi-planar destination is 4:2:0");
+        if (cy0 <= cy1)
+            semiplanar_pass<DITH>(&s_chr[0][0], clo, c.chrSrcH - 1, c.vChrC, c.vChrP, cs, cy0, cy1 - cy0 + 1, x0 >> 1, c.chrDstW,
+                                  fr.dst[1] + (size_t)cy0 * fr.dst_stride[1], fr.dst_stride[1], tid, dith, c.planar == MI355_SWS_DST_NV21);
+        return;
+    }
     if (cy0 <= cy1)
         planar_pass<CW / 8, 2, DITH>(&s_chr[0][0], clo, c.chrSrcH - 1, c.vChrC, c.vChrP, cs, cy0, cy1 - cy0 + 1, x0 >> hs, c.chrDstW,
                                      fr.dst[1] + (size_t)cy0 * fr.dst_stride[1], fr.dst_stride[1], fr.dst[2] + (size_t)cy0 * fr.dst_stride[2], fr.dst_stride[2], tid, dith);
+}
+
+/* ---- the unscaled packer: 8-bit yuv420p -> NV12 / NV21 at equal size (planarToNv12Wrapper, swscale_unscaled.c:138-156) -------------
+ * srcW x srcH luma bytes copied (copyPlane), srcW / 2 pairs on srcH / 2 rows interleaved (interleaveBytes_c, rgb2rgb_template.c:693-709) —
+ * both divisions round down: the last pair of an odd width's chroma rows and the last chroma row of an odd height are neither read nor
+ * written.  One grid over tiles of PACK_COLS x PACK_ROWS luma samples (blockIdx.z: the picture), luma copy and interleave in the same
+ * launch: a thread moves 16 luma bytes of four rows and eight pairs of two chroma rows, every load requested before the first store.
+ * 16-byte luma pieces where the two luma planes' pointers and strides are multiples of 16, and 8 + 8 -> 16 byte chroma pieces where the
+ * source chroma planes are on 8-byte and the pair plane on 16-byte multiples; otherwise sample by sample. */
+constexpr int PACK_COLS = 1024, PACK_ROWS = 16;
+__global__ void __launch_bounds__(NT) k_sws_nv12_pack(int srcW, int srcH, int swap_uv, const mi355_sws_planar_frame *frames)
+{
+    mi355_sws_planar_frame fr = frames[blockIdx.z];
+    for (int k = 0; k < 3; k++) fr.src[k] = mi355_global(fr.src[k]);
+    fr.dst[0] = mi355_global(fr.dst[0]); fr.dst[1] = mi355_global(fr.dst[1]);
+    const int tid = threadIdx.x, lane = tid & 63, rg = tid >> 6;
+    const int x = blockIdx.x * PACK_COLS + 16 * lane, y0 = blockIdx.y * PACK_ROWS;
+    const int cw = srcW >> 1, ch = srcH >> 1, cx = x >> 1, cy0 = y0 >> 1;                     /* pairs, chroma rows: rounded down */
+    const uint8_t *first = swap_uv ? fr.src[2] : fr.src[1], *second = swap_uv ? fr.src[1] : fr.src[2];
+    const int st_first = swap_uv ? fr.src_stride[2] : fr.src_stride[1], st_second = swap_uv ? fr.src_stride[1] : fr.src_stride[2];
+    const bool lwide = x + 16 <= srcW &&
+                       ((reinterpret_cast<uintptr_t>(fr.src[0]) | (uintptr_t)fr.src_stride[0] | reinterpret_cast<uintptr_t>(fr.dst[0]) | (uintptr_t)fr.dst_stride[0]) & 15) == 0;
+    const bool cwide = cx + 8 <= cw && ((reinterpret_cast<uintptr_t>(fr.dst[1]) | (uintptr_t)fr.dst_stride[1]) & 15) == 0 &&
+                       ((reinterpret_cast<uintptr_t>(first) | (uintptr_t)st_first | reinterpret_cast<uintptr_t>(second) | (uintptr_t)st_second) & 7) == 0;
+    constexpr int LR = PACK_ROWS / (NT / 64), CR = PACK_ROWS / 2 / (NT / 64);                 /* luma / chroma rows of a thread */
+    sws_u32x4 l[LR] = {};
+    sws_u32x2 p[CR] = {}, q[CR] = {};
+#pragma unroll
+    for (int k = 0; k < LR; k++) {
+        const int y = y0 + rg + k * (NT / 64);
+        if (lwide && y < srcH) l[k] = *reinterpret_cast<const sws_u32x4 *>(fr.src[0] + (size_t)y * fr.src_stride[0] + x);
+    }
+#pragma unroll
+    for (int k = 0; k < CR; k++) {
+        const int cy = cy0 + rg + k * (NT / 64);
+        if (cwide && cy < ch) {
+            p[k] = *reinterpret_cast<const sws_u32x2 *>(first + (size_t)cy * st_first + cx);
+            q[k] = *reinterpret_cast<const sws_u32x2 *>(second + (size_t)cy * st_second + cx);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < LR; k++) {
+        const int y = y0 + rg + k * (NT / 64);
+        if (y >= srcH || x >= srcW) continue;
+        uint8_t *d = fr.dst[0] + (size_t)y * fr.dst_stride[0] + x;
+        if (lwide) *reinterpret_cast<sws_u32x4 *>(d) = l[k];
+        else {
+            const uint8_t *sp = fr.src[0] + (size_t)y * fr.src_stride[0] + x;
+            const int n = imin(16, srcW - x);
+            for (int i = 0; i < n; i++) d[i] = sp[i];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < CR; k++) {
+        const int cy = cy0 + rg + k * (NT / 64);
+        if (cy >= ch || cx >= cw) continue;
+        uint8_t *d = fr.dst[1] + (size_t)cy * fr.dst_stride[1] + 2 * cx;
+        if (cwide) {
+            *reinterpret_cast<sws_u32x4 *>(d) = sws_u32x4{ sws_zip_lo(p[k][0], q[k][0]), sws_zip_hi(p[k][0], q[k][0]), sws_zip_lo(p[k][1], q[k][1]), sws_zip_hi(p[k][1], q[k][1]) };
+        } else {
+            const uint8_t *s1 = first + (size_t)cy * st_first + cx, *s2 = second + (size_t)cy * st_second + cx;
+            const int n = imin(8, cw - cx);
+            for (int i = 0; i < n; i++) { d[2 * i] = s1[i]; d[2 * i + 1] = s2[i]; }
+        }
+    }
 }
 
 constexpr int C24_ROWS = 16, C24_COLS = 512, IDENT_ROWS = 16;      /* rows of a tile of k_sws_c24 / of k_sws_ident1 */
@@ -1129,6 +1304,17 @@ __global__ void __launch_bounds__(NT) k_sws_line_plane(const int16_t *filter, in
         int val = dither[(i + offset) & 7] << 12;
         for (int j = 0; j < fs; j++) val += rows[(size_t)j * pitch + i] * filter[j];
         dest[i] = (uint8_t)clip_u8(val >> 19);
+    }
+}
+/* yuv2nv12cX_c output.c:267-301: fs >= 1 rows of U and of V at `pitch` elements, the pairs in U V (swap_uv: V U) order */
+__global__ void __launch_bounds__(NT) k_sws_line_nv12(const int16_t *filter, int fs, const int16_t *urows, const int16_t *vrows, int pitch, uint8_t *dest,
+                                                      int chrDstW, const uint8_t *dither, int swap_uv)
+{
+    for (int i = threadIdx.x; i < chrDstW; i += NT) {
+        int u = dither[i & 7] << 12, v = dither[(i + 3) & 7] << 12;
+        for (int j = 0; j < fs; j++) { u += urows[(size_t)j * pitch + i] * filter[j]; v += vrows[(size_t)j * pitch + i] * filter[j]; }
+        dest[2 * i + (swap_uv ? 1 : 0)] = (uint8_t)clip_u8(u >> 19);
+        dest[2 * i + (swap_uv ? 0 : 1)] = (uint8_t)clip_u8(v >> 19);
     }
 }
 struct PackedRows {

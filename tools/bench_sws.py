@@ -25,6 +25,12 @@ def main():
     ap.add_argument("--sources", action="store_true",
                     help="the deeper / wider sources (mi355_sws_create_src) beside the 8-bit yuv420p point of the same shape, alternating: 2160p -> 1080p "
                          "rgb24 from yuv420p10le, 1080p unscaled generic rgb24 from yuv420p10le and from yuv422p; --frames pictures per launch")
+    ap.add_argument("--nv12", action="store_true",
+                    help="NV12 destinations beside the yuv420p destination of the same shape (2160p -> 1080p from 8 bits, 1080p equal size from 10 "
+                         "bits), the unscaled packer beside k_sws_c24, and with --other-lib the three existing points; 32 and 512 pictures per "
+                         "launch, 3 warm-up + --steps launches a round, alternating, median of 3 rounds")
+    ap.add_argument("--other-lib", default=None,
+                    help="--nv12: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
     ap.add_argument("--rounds", type=int, default=5, help="--planar / --sources: alternating rounds (the median is reported)")
     a = ap.parse_args()
     prov = providers.mi355()
@@ -35,6 +41,8 @@ def main():
         return planar(a, lib)
     if a.sources:
         return sources(a, lib)
+    if a.nv12:
+        return nv12(a, lib)
     orc = S.oracle_backend(providers.oracle())
     for name in a.configs.split(","):
         ctx = S.load_context(name)
@@ -209,6 +217,152 @@ def sources(a, lib):
                 out["kernel"], out["hstaged"] = b.plan["kernel"], b.plan["hstaged"]
             print(json.dumps(out), flush=True)
             b.close()
+
+
+class PlaneBatch:
+    """`frames` pictures for one context of the planar entry points resident in HBM: each its own source planes (the given pictures uploaded,
+    the rest device-side copies) and its own two or three tightly pitched destination planes of `sizes` (bytes per row, rows)"""
+
+    def __init__(self, lib, handle, pics, sizes, frames):
+        import sws_planar as P
+        self.lib, self.bufs, self.n, self.handle = lib, [], frames, handle
+        assert handle
+        lib.mi355_malloc.restype = C.c_void_p
+        lib.mi355_malloc.argtypes = [C.c_size_t]
+        lib.mi355_free.argtypes = [C.c_void_p]
+        for f in ("mi355_memcpy_h2d", "mi355_memcpy_d2d"):
+            getattr(lib, f).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        arr = (P.PlanarFrame * frames)()
+        self.src_bytes = 0
+        for p in range(3):
+            psz = pics[0][p].nbytes
+            self.src_bytes += psz
+            base = self.alloc(frames * psz + 64)
+            for g, pic in enumerate(pics):
+                lib.mi355_memcpy_h2d(base + g * psz, pic[p].ctypes.data, psz)
+            done = len(pics)
+            while done < frames:
+                k = min(done, frames - done)
+                lib.mi355_memcpy_d2d(base + done * psz, base, k * psz)
+                done += k
+            for f in range(frames):
+                arr[f].src[p], arr[f].src_stride[p] = base + f * psz, pics[0][p].strides[0]
+        self.dst_bytes = sum(w * h for w, h in sizes)
+        dst = self.alloc(frames * self.dst_bytes + 64)
+        for f in range(frames):
+            o = dst + f * self.dst_bytes
+            for p, (w, h) in enumerate(sizes):
+                arr[f].dst[p], arr[f].dst_stride[p] = o, w
+                o += w * h
+        self.d_frames = self.alloc(C.sizeof(arr))
+        lib.mi355_memcpy_h2d(self.d_frames, C.addressof(arr), C.sizeof(arr))
+        lib.mi355_sws_scale_planar_frames_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+
+    def alloc(self, n):
+        p = self.lib.mi355_malloc(n)
+        assert p
+        self.bufs.append(p)
+        return p
+
+    def run(self):
+        self.lib.mi355_sws_scale_planar_frames_dev(C.c_void_p(self.handle), C.c_void_p(self.d_frames), self.n, None)
+
+    def close(self):
+        self.lib.mi355_sws_destroy(C.c_void_p(self.handle))
+        for p in self.bufs:
+            self.lib.mi355_free(p)
+
+
+def nv12(a, lib):
+    """NV12 destinations beside the three-plane yuv420p destination of the same shape, the packer beside k_sws_c24, every context from the
+    committed tables (tests/golden).  One process, the batches of a point alternating: 3 warm-up + --steps launches a round, median of 3
+    rounds, at 32 and 512 pictures per launch.  Algorithmic bytes: the source planes read once + the destination planes written once.
+    --other-lib: the contexts a second build of the library takes (not the NV12 ones of a build without them) run on it in the same
+    alternation, and so do the three points of the default mode."""
+    import statistics
+    import numpy as np
+    import sws_nv12 as N
+    import sws_planar as P
+    import sws_sources as X
+    libs = {"this": lib}
+    if a.other_lib:
+        other = C.CDLL(os.path.abspath(a.other_lib))
+        other.mi355_init.restype = C.c_int
+        assert other.mi355_init(C.c_int(0)) == 0
+        other.mi355_event_create.restype = C.c_void_p
+        other.mi355_event_elapsed_ms.restype = C.c_float
+        libs["other"] = other
+    rounds = 3
+
+    def contiguous(pic):
+        return [np.ascontiguousarray(pl) for pl in pic]
+
+    def report(point, frames, batches, nbytes, t, extra):
+        for k in batches:
+            ms = statistics.median(t[k])
+            us = ms * 1e3 / frames
+            out = {"workload": point + ":" + k, "frames_per_launch": frames, "ms_per_launch": ms, "us_per_picture": us,
+                   "algorithmic_bytes_per_frame": nbytes[k], "achieved_GBps": nbytes[k] / us * 1e-3, "frac_of_8TBps": nbytes[k] / us * 1e-3 / 8000.0,
+                   "ms_rounds": [round(x, 4) for x in t[k]]}
+            out.update(extra.get(k, {}))
+            print(json.dumps(out), flush=True)
+
+    def alternate(batches):
+        t = {k: [] for k in batches}
+        for _ in range(rounds):
+            for k, (l, b) in batches.items():
+                t[k].append(time_ms(l, b.run, a.steps))
+        return t
+
+    for frames in (32, 512):
+        # 2160p -> 1080p bicubic from 8-bit yuv420p: nv12 beside yuv420p
+        e = N.stored_entry("big_uhd420d8_to_hd_nv12")
+        pctx = P.stored_context("big_uhd_to_hd")
+        pics = [contiguous(P.picture("big_uhd_to_hd", seed=s)) for s in (1, 2)]
+        batches, extra = {}, {}
+        for tag, l in libs.items():
+            batches["yuv420p@" + tag] = (l, PlaneBatch(l, P.create(l, pctx, "420"), pics, P.plane_sizes(pctx, "420"), frames))
+        batches["nv12@this"] = (lib, PlaneBatch(lib, N.create(lib, e), pics, e.out_sizes(), frames))
+        extra["nv12@this"] = {"kernel": N.plan_of(lib, batches["nv12@this"][1].handle)["kernel"]}
+        nbytes = {k: b.src_bytes + b.dst_bytes for k, (l, b) in batches.items()}
+        report("uhd_to_hd_from_yuv420p", frames, batches, nbytes, alternate(batches), extra)
+        for l, b in batches.values():
+            b.close()
+        # 1080p equal size from 10 bits: yuv420p10le -> nv12 beside yuv422p10le -> yuv420p (yuv420p10le -> yuv420p is a plane copy)
+        e = N.stored_entry("big_hd420d10_to_nv12")
+        pe = X.stored_entry("big_hd422d10_to_420")
+        batches, extra = {}, {}
+        ppics = [contiguous(X.picture("big_hd422d10_to_420", seed=s)) for s in (1, 2)]
+        for tag, l in libs.items():
+            batches["yuv422p10le_to_yuv420p@" + tag] = (l, PlaneBatch(l, X.create(l, pe), ppics, pe.out_sizes(), frames))
+        npics = [contiguous(N.picture("big_hd420d10_to_nv12", seed=s)) for s in (1, 2)]
+        batches["yuv420p10le_to_nv12@this"] = (lib, PlaneBatch(lib, N.create(lib, e), npics, e.out_sizes(), frames))
+        extra["yuv420p10le_to_nv12@this"] = {"kernel": N.plan_of(lib, batches["yuv420p10le_to_nv12@this"][1].handle)["kernel"]}
+        nbytes = {k: b.src_bytes + b.dst_bytes for k, (l, b) in batches.items()}
+        report("hd_same_from_10bit", frames, batches, nbytes, alternate(batches), extra)
+        for l, b in batches.values():
+            b.close()
+        # the packer beside k_sws_c24 (the nearest copy-shaped kernel)
+        e = N.stored_entry("big_hd420d8_pack")
+        kpics = [contiguous(N.picture("big_hd420d8_pack", seed=s)) for s in (1, 2)]
+        sctx = S.load_context("hd_special")
+        batches = {"nv12_pack@this": (lib, PlaneBatch(lib, N.create(lib, e), kpics, e.out_sizes(), frames)),
+                   "c24@this": (lib, S.DeviceBatch(lib, sctx, [S.picture("hd_special", seed=s) for s in (1, 2)], frames))}
+        d = sctx.desc
+        nbytes = {"nv12_pack@this": 2 * (1920 * 1080 * 3 // 2), "c24@this": d.srcW * d.srcH + 2 * d.chrSrcW * d.chrSrcH + d.dstW * d.dstH * 3}
+        report("hd_unscaled", frames, batches, nbytes, alternate(batches), {})
+        for l, b in batches.values():
+            b.close()
+    if "other" in libs:
+        for name in a.configs.split(","):
+            ctx = S.load_context(name)
+            d = ctx.desc
+            pics = [S.picture(name, seed=s) for s in (1, 2)]
+            batches = {tag: (l, S.DeviceBatch(l, ctx, pics, a.frames)) for tag, l in (("other", libs["other"]), ("this", lib))}
+            nb = d.srcW * d.srcH + 2 * d.chrSrcW * d.chrSrcH + d.dstW * d.dstH * 3
+            report(name, a.frames, batches, {k: nb for k in batches}, alternate(batches), {})
+            for l, b in batches.values():
+                b.close()
 
 
 if __name__ == "__main__":
