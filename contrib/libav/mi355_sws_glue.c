@@ -40,6 +40,14 @@
  *                          planarToNv12Wrapper: unscaled_special = 1 with the format) for callers of the C ABI; the whole-picture binding
  *                          cannot take it — ff_get_unscaled_swscale sets c->swscale outside the two wrapped selectors — so such a
  *                          context runs the reference's function.
+ *   NV12 / NV21 sources    (the reference runs nv12ToUV_c / nv21ToUV_c, c->chrToYV12, on each chroma line and then the ordinary hcScale) take
+ *                          the same two forms to every destination above through mi355_sws_describe_fmt() / mi355_sws_create_src_layout():
+ *                          whole pictures hand over TWO source planes (srcStride[2] is not looked at); with MI355_SWS_LINES=1 c->chrToYV12
+ *                          stays the reference's function — a one-line de-interleave on the host leaves the device nothing to do — and the
+ *                          inner loops behind it are forwarded as for the other sources.  mi355_sws_describe_fmt() also recognises the
+ *                          unscaled splitter (nv12 / nv21 -> yuv420p at equal size, nv12ToPlanarWrapper) for callers of the C ABI; like the
+ *                          packer it is set outside the two wrapped selectors.  mi355_sws_describe / _planar / _src keep their answers:
+ *                          they decline these sources.
  * The device is MI355_DEVICE (default 0), as for the decoder bridges.
  */
 #include <pthread.h>
@@ -152,6 +160,8 @@ static int source_of(const SwsContext *c, mi355_sws_src *s)
 }
 /* 0: rgb24, MI355_SWS_DST_*: planar or semi-planar, -1: a context this path leaves to the reference.  special: the context's swscale is
  * yuv2rgb_c_24_rgb or, with an NV12 / NV21 destination, planarToNv12Wrapper */
+/* the destination of a context that runs the generic scaler, -1 for one this path leaves to the reference */
+static int generic_dst(const SwsContext *c);
 static int src_format(const SwsContext *c, mi355_sws_src *s, int special)
 {
     if (source_of(c, s) != 0 || (c->flags & SWS_FULL_CHR_H_INT)) return -1;       /* (every destination below is 8 bits) */
@@ -159,6 +169,10 @@ static int src_format(const SwsContext *c, mi355_sws_src *s, int special)
     if (special && (c->dstFormat == AV_PIX_FMT_NV12 || c->dstFormat == AV_PIX_FMT_NV21))          /* the packer: planarToNv12Wrapper */
         return c->srcFormat == AV_PIX_FMT_YUV420P ? (c->dstFormat == AV_PIX_FMT_NV12 ? MI355_SWS_DST_NV12 : MI355_SWS_DST_NV21) : -1;
     if (special) return c->dstFormat == AV_PIX_FMT_RGB24 && s->depth == 8 && s->hsub == 1 ? 0 : -1;
+    return generic_dst(c);
+}
+static int generic_dst(const SwsContext *c)
+{
     /* the generic scaler: no fast bilinear, no range conversion, no chroma line drop, and its four banks (an unscaled converter or a
      * plane copy has none, utils.c:1043-1048) */
     if (c->hyscale_fast || c->hcscale_fast || c->lumConvertRange || c->chrConvertRange || c->vChrDrop) return -1;
@@ -206,6 +220,54 @@ int mi355_sws_describe_src(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_sr
         special = 1;                                             /* swscale_unscaled.c:1051-1055 */
     }
     return describe_src(c, d, s, dst_format, special);
+}
+
+/* ---- NV12 / NV21 sources beside the planar ones ------------------------------------------------------------------------------------------
+ * src_format() with the source's layout (MI355_SWS_SRC_*): an NV12 / NV21 source is the one context whose input converter this path takes —
+ * c->chrToYV12 alone (nv12ToUV_c / nv21ToUV_c, input.c:475-497) — as an 8-bit 4:2:0 source of the layout.  special: nv12ToPlanarWrapper */
+static int fmt_format(const SwsContext *c, mi355_sws_src *s, int special, int *layout)
+{
+    *layout = c->srcFormat == AV_PIX_FMT_NV12 ? MI355_SWS_SRC_NV12 : (c->srcFormat == AV_PIX_FMT_NV21 ? MI355_SWS_SRC_NV21 : MI355_SWS_SRC_PLANAR);
+    if (!*layout) return src_format(c, s, special);
+    memset(s, 0, sizeof(*s));
+    s->depth = 8; s->hsub = 1; s->vsub = 1;
+    memcpy(s->dither, ff_dither_8x8_128, sizeof(s->dither));
+    if (c->chrSrcHSubSample != 1 || c->chrSrcVSubSample != 1 || (c->flags & SWS_FULL_CHR_H_INT)) return -1;
+    if (c->lumToYV12 || c->readLumPlanar || c->readChrPlanar || c->alpToYV12 || c->readAlpPlanar) return -1;      /* no other input converter */
+    /* (the unscaled path leaves sws_init_context before srcBpc is set and the input converters are chosen: the splitter's context has neither) */
+    if (special) return c->dstFormat == AV_PIX_FMT_YUV420P ? MI355_SWS_DST_YUV420P : -1;
+    if (c->srcBpc != 8 || !c->chrToYV12) return -1;
+    return generic_dst(c);
+}
+/* what mi355_sws_create_src_layout takes for a live context (0), -1 for a context this path declines: mi355_sws_describe_src plus the two
+ * NV sources.  An NV context without the vertical banks is the splitter when it goes to yuv420p at equal size (swscale_unscaled.c:1045-1049,
+ * whatever the flags); any other without them (nv12 -> nv12: a plane copy) is declined. */
+int mi355_sws_describe_fmt(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *src_layout, int *dst_format)
+{
+    int special = 0;
+    if (c->srcFormat != AV_PIX_FMT_NV12 && c->srcFormat != AV_PIX_FMT_NV21) {
+        *src_layout = MI355_SWS_SRC_PLANAR;
+        return mi355_sws_describe_src(c, d, s, dst_format);
+    }
+    if (!c->vLumFilter) {
+        if (c->dstFormat != AV_PIX_FMT_YUV420P || c->srcW != c->dstW || c->srcH != c->dstH) return -1;
+        special = 1;
+    }
+    const int fmt = fmt_format(c, s, special, src_layout);
+    if (fmt < 0) return -1;
+    memset(d, 0, sizeof(*d));
+    d->srcW = c->srcW; d->srcH = c->srcH; d->dstW = c->dstW; d->dstH = c->dstH;
+    d->chrSrcW = c->chrSrcW; d->chrSrcH = c->chrSrcH; d->chrDstW = c->chrDstW;
+    d->unscaled_special = special;
+    if (!special) {
+        d->hLum = (mi355_sws_filter){ c->hLumFilter, c->hLumFilterPos, c->hLumFilterSize, c->dstW };
+        d->hChr = (mi355_sws_filter){ c->hChrFilter, c->hChrFilterPos, c->hChrFilterSize, c->chrDstW };
+        d->vLum = (mi355_sws_filter){ c->vLumFilter, c->vLumFilterPos, c->vLumFilterSize, c->dstH };
+        d->vChr = (mi355_sws_filter){ c->vChrFilter, c->vChrFilterPos, c->vChrFilterSize, fmt ? c->chrDstH : c->dstH };
+    }
+    if (!fmt) luts_of(c, &d->luts);
+    *dst_format = fmt;
+    return 0;
 }
 
 #ifndef MI355_SWS_DESCRIBE_ONLY
@@ -272,7 +334,8 @@ static void t1_nv12cX(SwsContext *c, const int16_t *chrFilter, int chrFilterSize
 void ff_sws_init_mi355x(SwsContext *c)
 {
     mi355_sws_src s;
-    const int fmt = src_format(c, &s, 0);
+    int layout;
+    const int fmt = fmt_format(c, &s, 0, &layout);      /* (an NV12 / NV21 source: c->chrToYV12 stays the reference's) */
     if (fmt > 0) {
         if (!device_ready() || !c->hyScale || !c->hcScale || !c->yuv2planeX || !c->yuv2plane1) return;
         c->hyScale = c->hcScale = s.depth > 8 ? t1_hscale16 : t1_hscale;
@@ -301,7 +364,8 @@ typedef struct Bound {
     SwsFunc real;                 /* what the reference chose */
     int special;                  /* ... through ff_yuv2rgb_get_func_ptr */
     int planar;                   /* MI355_SWS_DST_* of a planar context (mi355_sws_scale_planar), 0 for rgb24 */
-    int other;                    /* a source other than 8-bit yuv420p: described by mi355_sws_describe_src, built by mi355_sws_create_src */
+    int other;                    /* a source other than 8-bit yuv420p: described by mi355_sws_describe_fmt, built by mi355_sws_create_src_layout */
+    int layout;                   /* ... its MI355_SWS_SRC_* (NV12 / NV21: two source planes) */
     mi355_sws_ctx *dev;
     int failed;                   /* the device side does not take this context: the reference's function from now on */
     int busy;                     /* calls of mi355_sws_scale in flight on `dev` (under bound_mu): the device context is destroyed only at 0 */
@@ -348,10 +412,10 @@ static Bound *bound_find(SwsContext *c, int create)
 /* a selector runs for this context: sws_init_context() of a new context — possibly at the address of one that was freed */
 static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
 {
-    int planar = special ? 0 : planar_format(c), other = 0;
+    int planar = special ? 0 : planar_format(c), other = 0, layout = MI355_SWS_SRC_PLANAR;
     if (!(taken(c) || planar)) {
         mi355_sws_src s;
-        const int fmt = src_format(c, &s, special);
+        const int fmt = fmt_format(c, &s, special, &layout);
         if (fmt < 0) return real;
         other = 1; planar = fmt;
     }
@@ -360,7 +424,7 @@ static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
     Bound *b = bound_find(c, 1);
     if (b) {
         slot_release(b);
-        b->c = c; b->real = real; b->special = special; b->planar = planar; b->other = other; b->stamp = ++n_stamp;
+        b->c = c; b->real = real; b->special = special; b->planar = planar; b->other = other; b->layout = layout; b->stamp = ++n_stamp;
     }
     pthread_mutex_unlock(&bound_mu);
     return b ? mi355_swsfunc_entry : real;
@@ -377,20 +441,25 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
     /* a planar context: all three destination planes; range conversion set since the context was bound (sws_setColorspaceDetails) is
      * the reference's for that picture */
     mi355_sws_src s_now;
+    int l_now;
     const int semi = b && (b->planar == MI355_SWS_DST_NV12 || b->planar == MI355_SWS_DST_NV21);      /* two planes: dstStride[2] is not looked at */
     const int planar_ok = b && b->planar && dstStride[1] > 0 && (semi || dstStride[2] > 0) &&
-                          (b->other ? src_format(c, &s_now, 0) : planar_format(c)) == b->planar;
+                          (b->other ? fmt_format(c, &s_now, 0, &l_now) : planar_format(c)) == b->planar;
     /* an rgb24 context of another source: range conversion set since it was bound is the reference's for that picture, as above */
-    const int other_ok = !b || !b->other || b->planar || src_format(c, &s_now, b->special) == 0;
+    const int other_ok = !b || !b->other || b->planar || fmt_format(c, &s_now, b->special, &l_now) == 0;
+    /* an NV12 / NV21 source has two planes: srcStride[2] is not looked at */
     if (b && !b->failed && srcSliceY == 0 && srcSliceH == c->srcH &&
-        srcStride[0] > 0 && srcStride[1] > 0 && srcStride[2] > 0 && dstStride[0] > 0 && (!b->planar || planar_ok) && other_ok) {
+        srcStride[0] > 0 && srcStride[1] > 0 && (b->layout || srcStride[2] > 0) && dstStride[0] > 0 && (!b->planar || planar_ok) && other_ok) {
         if (b->dev && !b->busy && !b->planar && (memcmp(b->y_table, c->yuvTable, 1024) || b->gv0 != c->table_gV[0])) { mi355_sws_destroy(b->dev); b->dev = NULL; }
         if (!b->dev) {
             mi355_sws_desc d;
             int fmt;
             if (b->other) {
                 mi355_sws_src s;
-                if (device_ready() && describe_src(c, &d, &s, &fmt, b->special) == 0 && fmt == b->planar) b->dev = mi355_sws_create_src(&d, &s, fmt);
+                int layout;
+                if (device_ready() && (b->layout ? mi355_sws_describe_fmt(c, &d, &s, &layout, &fmt) == 0 && layout == b->layout
+                                                 : describe_src(c, &d, &s, &fmt, b->special) == 0) && fmt == b->planar)
+                    b->dev = mi355_sws_create_src_layout(&d, &s, b->layout, fmt);
             } else if (b->planar) {
                 if (device_ready() && mi355_sws_describe_planar(c, &d, &fmt) == 0) b->dev = mi355_sws_create_planar(&d, fmt);
             } else if (device_ready() && describe(c, &d, b->special) == 0) b->dev = mi355_sws_create(&d);

@@ -2,7 +2,8 @@
  * mi355_sws.h — C ABI of the libswscale part of the hot path:
  * horizontal 8->15 bit FIR, vertical FIR to planar 8 bit or through the yuv->rgb LUTs to RGB24,
  * and the unscaled yuv420p -> rgb24 converter; whole pictures to RGB24, to planar yuv420p / yuv422p / yuv444p or to semi-planar
- * NV12 / NV21 (yuv2nv12cX, and the unscaled yuv420p -> NV12 / NV21 packer).
+ * NV12 / NV21 (yuv2nv12cX, and the unscaled yuv420p -> NV12 / NV21 packer); from planar sources or from NV12 / NV21 (the reference's
+ * nv12ToUV_c / nv21ToUV_c in front of hcScale, and the unscaled NV12 / NV21 -> yuv420p splitter).
  *
  * The reference keeps these behind function pointers of the (private) SwsContext
  * (libswscale/swscale_internal.h:253-540): hyScale/hcScale :526-531, yuv2plane1/yuv2planeX/
@@ -83,7 +84,8 @@ enum {
     MI355_SWS_K_PLANAR_A = 6,     /* a planar destination (mi355_sws_create_planar): the tile kernel holding 28 luma / 16 chroma source lines */
     MI355_SWS_K_PLANAR_B = 7,     /* ... 40 / 24 */
     MI355_SWS_K_PLANAR_C = 8,     /* ... 48 / 48 */
-    MI355_SWS_K_NV12_PACK = 9     /* the unscaled yuv420p -> NV12 / NV21 packer (k_sws_nv12_pack); scaled NV12 / NV21 contexts report PLANAR_A / B / C */
+    MI355_SWS_K_NV12_PACK = 9,    /* the unscaled yuv420p -> NV12 / NV21 packer (k_sws_nv12_pack); scaled NV12 / NV21 contexts report PLANAR_A / B / C */
+    MI355_SWS_K_NV12_SPLIT = 10   /* the unscaled NV12 / NV21 -> yuv420p splitter (k_sws_nv12_split); scaled NV12 / NV21 SOURCES report the values above */
 };
 typedef struct mi355_sws_plan_info {
     int kernel;                   /* MI355_SWS_K_* */
@@ -131,7 +133,8 @@ enum { MI355_SWS_DST_NV12 = 16, MI355_SWS_DST_NV21 = 17 };
 typedef struct mi355_sws_dest_info {
     int format;                   /* 0 rgb24, else MI355_SWS_DST_* */
     int planes;                   /* 1 rgb24, 2 NV12 / NV21, 3 planar */
-    int chr_bytes, chr_rows;      /* bytes per row and rows the context writes to each chroma plane (0 / 0 for rgb24; the packer: 2 * (srcW / 2), srcH / 2) */
+    int chr_bytes, chr_rows;      /* bytes per row and rows the context writes to each chroma plane (0 / 0 for rgb24; the packer: 2 * (srcW / 2), srcH / 2;
+                                   * the splitter: srcW / 2, srcH / 2) */
 } mi355_sws_dest_info;
 int mi355_sws_destination(const mi355_sws_ctx *ctx, mi355_sws_dest_info *info);   /* 0, -1 bad argument */
 
@@ -162,6 +165,24 @@ typedef struct mi355_sws_source_info {
                                    * (planes on 4-byte multiples; the others, and the other contexts, read sample by sample) */
 } mi355_sws_source_info;
 int mi355_sws_source(const mi355_sws_ctx *ctx, mi355_sws_source_info *info);   /* 0, -1 bad argument */
+
+/* ---- semi-planar sources: NV12 / NV21, 8 bit (nv12ToUV_c / nv21ToUV_c input.c:475-497 in front of hcScale; nv12ToPlanarWrapper
+ * swscale_unscaled.c:158-177) ----
+ * layout 0: exactly mi355_sws_create_src.  1 / 2: an 8-bit 4:2:0 source whose second plane holds chrSrcW byte pairs (U V .., NV21: V U ..)
+ * on chrSrcH rows; src->depth must be 8 and the shifts 1,1 (anything else: NULL and a message).  The descriptor is the reference's for that
+ * context — its banks are those of the yuv420p context of the same sizes and flags.  dst_format takes every value mi355_sws_create_src takes.
+ * Frames stay mi355_sws_frame / mi355_sws_planar_frame through the four scale entry points: src[1] is the pair plane, 2 * chrSrcW bytes a row;
+ * src[2] and src_stride[2] are never read and may be NULL / 0.  The alignment paragraph above mi355_sws_frame holds for the pair plane in
+ * bytes: pointer and stride on 16-byte multiples — aligned 16-byte pieces, readable over the whole stride; on 4-byte multiples — dwords;
+ * anything else is read sample-exactly (a pair may start on an odd address).
+ * The unscaled splitter: desc->unscaled_special = 1 with layout 1 / 2 and dst_format MI355_SWS_DST_YUV420P — srcW == dstW, srcH == dstH, no banks
+ * (every other special combination with such a layout, rgb24 included: NULL and a message; the reference has no special converter from these
+ * sources to rgb24, it runs its generic scaler).  Like the reference it copies srcW x srcH luma bytes and de-interleaves srcW / 2 pairs on
+ * srcH / 2 rows, both ROUNDED DOWN: the last byte of an odd width's chroma rows and the last chroma row of an odd height stay untouched
+ * (mi355_sws_destination reports chr_bytes = srcW / 2, chr_rows = srcH / 2). */
+enum { MI355_SWS_SRC_PLANAR = 0, MI355_SWS_SRC_NV12 = 1, MI355_SWS_SRC_NV21 = 2 };
+mi355_sws_ctx *mi355_sws_create_src_layout(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format);
+int mi355_sws_source_layout(const mi355_sws_ctx *ctx);   /* MI355_SWS_SRC_*, -1 bad argument */
 
 /* ---- the individual inner loops (Tier 1, host pointers), argument lists of the reference's
  * function-pointer types minus the SwsContext ------------------------------------------------ */

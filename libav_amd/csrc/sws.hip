@@ -1,9 +1,10 @@
 /*
  * sws.hip — the libswscale part of the path: planar yuv 4:2:0 / 4:2:2 / 4:4:4 sources at 8, 9 or 10 bits (16-bit
- * little-endian samples above 8: hScale16To15_c swscale.c:110-130 in place of hScale8To15_c) -> rgb24, -> 8-bit yuv420p / yuv422p / yuv444p
- * and -> NV12 / NV21 (dithered from a deeper source, swscale.c:553-556), and the unscaled 8-bit yuv420p -> NV12 / NV21 packer.  This file:
+ * little-endian samples above 8: hScale16To15_c swscale.c:110-130 in place of hScale8To15_c) and 8-bit NV12 / NV21 sources -> rgb24,
+ * -> 8-bit yuv420p / yuv422p / yuv444p and -> NV12 / NV21 (dithered from a deeper source, swscale.c:553-556), the unscaled 8-bit
+ * yuv420p -> NV12 / NV21 packer and the unscaled NV12 / NV21 -> yuv420p splitter.  This file:
  * the context, the plan (which kernel a context gets) and the entry points of include/mi355_sws.h.  The device side is sws_dev.h:
- * k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1, k_sws_nv12_pack and the k_sws_line_* kernels of the Tier-1 entry points.
+ * k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1, k_sws_nv12_pack, k_sws_nv12_split and the k_sws_line_* kernels of the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
  */
 #include "mi355_rt.h"
@@ -96,7 +97,7 @@ static mi355_sws_ctx *ctx_new(const mi355_sws_desc *desc)
     h.hLumP = h.hChrP = h.vLumP = h.vChrP = nullptr;
     h.planar = h.hshift = h.vshift = 0;
     h.chrDstH = h.dstH;
-    h.depth = 8; h.src_hsub = h.src_vsub = 1; h.pad_ = 0;
+    h.depth = 8; h.src_hsub = h.src_vsub = 1; h.src_layout = MI355_SWS_SRC_PLANAR;
     std::memset(h.dither, 64, sizeof(h.dither));
     return c;
 }
@@ -128,7 +129,16 @@ static void ctx_hfit(mi355_sws_ctx *c, const mi355_sws_desc *desc)
         }
         return false;
     };
-    c->hfit = fits(desc->hLum, h.hident_l, TW) || fits(desc->hChr, h.hident_c, cw);
+    /* a plane of pairs: the span of a chroma tile in bytes against the luma staging line (hscale_tile_nv) */
+    auto fits_nv = [&](const mi355_sws_filter &f, int ident, int cols) {
+        if (ident || !f.pos) return false;
+        for (int g = 0; g < f.n; g += cols) {
+            const int last = (g + cols < f.n ? g + cols : f.n) - 1, s0 = 2 * f.pos[g], s1 = 2 * (f.pos[last] + f.size);
+            if (span_fits(span_dwords(s0 & ~15, s1), s0, s1, stage_pitch(TW, 1))) return true;
+        }
+        return false;
+    };
+    c->hfit = fits(desc->hLum, h.hident_l, TW) || (h.src_layout ? fits_nv(desc->hChr, h.hident_c, cw) : fits(desc->hChr, h.hident_c, cw));
 }
 static void upload_banks(mi355_sws_ctx *c, const mi355_sws_desc *desc)
 {
@@ -150,7 +160,7 @@ static mi355_sws_ctx *ctx_upload(mi355_sws_ctx *c)
 
 /* what the create entry points share: the source check, the destination family (rgb24, or planar: dst_format MI355_SWS_DST_*), the bank
  * validation with its diagnostics.  The unscaled special converter (rgb24) and the unscaled packer (NV12 / NV21) have no banks. */
-static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src *src, bool planar, int dst_format, const char *who)
+static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src *src, bool planar, int dst_format, const char *who, int layout = MI355_SWS_SRC_PLANAR)
 {
     const bool semi = dst_format == MI355_SWS_DST_NV12 || dst_format == MI355_SWS_DST_NV21;
     if (planar && (!desc || ((dst_format < MI355_SWS_DST_YUV420P || dst_format > MI355_SWS_DST_YUV444P) && !semi))) {
@@ -164,6 +174,26 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
                      h.chrSrcW, h.chrSrcH, h.srcW, h.srcH);
         delete c;
         return nullptr;
+    }
+    if (layout) {
+        /* NV12 / NV21: 8-bit 4:2:0; the only special context is the splitter (nv12ToPlanarWrapper: to yuv420p at equal size, no banks) */
+        if (h.depth != 8 || !h.src_hsub || !h.src_vsub) {
+            std::fprintf(stderr, "mi355dsp: %s: an nv12 / nv21 source is 8-bit 4:2:0 (%d bit, shifts %d/%d)\n", who, h.depth, h.src_hsub, h.src_vsub);
+            delete c;
+            return nullptr;
+        }
+        h.src_layout = layout;
+        if (h.special) {
+            if (dst_format != MI355_SWS_DST_YUV420P || h.srcW != h.dstW || h.srcH != h.dstH || h.chrDstW != (h.dstW + 1) >> 1) {
+                std::fprintf(stderr, "mi355dsp: %s: the only unscaled special converter of an nv12 / nv21 source is the splitter to yuv420p at equal size "
+                             "(destination %d, %dx%d -> %dx%d, chrDstW %d)\n", who, dst_format, h.srcW, h.srcH, h.dstW, h.dstH, h.chrDstW);
+                delete c;
+                return nullptr;
+            }
+            h.planar = dst_format; h.hshift = h.vshift = 1;
+            h.chrDstH = (h.dstH + 1) >> 1;
+            return ctx_upload(c);
+        }
     }
     bool ok = true;                                   /* what only a planar destination asks for */
     if (planar) {
@@ -217,6 +247,17 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src(const mi355_sws_desc *desc, const
     if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src: no descriptor\n"); return nullptr; }
     return ctx_create(desc, src, dst_format != 0, dst_format, "mi355_sws_create_src");
 }
+extern "C" mi355_sws_ctx *mi355_sws_create_src_layout(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format)
+{
+    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout without mi355_init(); no CPU fallback\n"); std::abort(); }
+    if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout: no descriptor\n"); return nullptr; }
+    if (src_layout < MI355_SWS_SRC_PLANAR || src_layout > MI355_SWS_SRC_NV21) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout: source layout %d is not planar / nv12 / nv21\n", src_layout);
+        return nullptr;
+    }
+    return ctx_create(desc, src, dst_format != 0, dst_format, "mi355_sws_create_src_layout", src_layout);
+}
+extern "C" int mi355_sws_source_layout(const mi355_sws_ctx *c) { return c ? c->h.src_layout : -1; }
 
 extern "C" void mi355_sws_destroy(mi355_sws_ctx *c)
 {
@@ -241,7 +282,7 @@ static int sws_kernel(const SwsDev &h)
         return 2;
     };
     static_assert(MI355_SWS_K_GENERIC_C == MI355_SWS_K_GENERIC_A + 2 && MI355_SWS_K_PLANAR_C == MI355_SWS_K_PLANAR_A + 2, "A / B / C follow each other");
-    if (h.planar && h.special) return MI355_SWS_K_NV12_PACK;
+    if (h.planar && h.special) return h.src_layout ? MI355_SWS_K_NV12_SPLIT : MI355_SWS_K_NV12_PACK;
     if (h.planar) return MI355_SWS_K_PLANAR_A + instance(PLANAR_SHAPES);
     if (h.special) return MI355_SWS_K_C24;
     /* a context that does not scale: straight from the source bytes (k_sws_ident1; MI355_SWS_NO_IDENT1=1, developer switch: through the tile all the same) */
@@ -281,7 +322,8 @@ extern "C" int mi355_sws_destination(const mi355_sws_ctx *c, mi355_sws_dest_info
     p->format = h.planar;
     p->planes = !h.planar ? 1 : (semi_planar(h) ? 2 : 3);
     /* the packer rounds both extents down (planarToNv12Wrapper) */
-    p->chr_bytes = !h.planar ? 0 : (semi_planar(h) ? 2 * (h.special ? h.srcW >> 1 : h.chrDstW) : h.chrDstW);
+    /* ... and so does the splitter (nv12ToPlanarWrapper) */
+    p->chr_bytes = !h.planar ? 0 : (semi_planar(h) ? 2 * (h.special ? h.srcW >> 1 : h.chrDstW) : (h.special ? h.srcW >> 1 : h.chrDstW));
     p->chr_rows = !h.planar ? 0 : (h.special ? h.srcH >> 1 : h.chrDstH);
     return 0;
 }
@@ -324,7 +366,35 @@ template <typename ST> static void launch_semi(int i, dim3 grid, hipStream_t s, 
     else if (i == 1) launch_semi<1, ST>(grid, s, d, frames);
     else launch_semi<2, ST>(grid, s, d, frames);
 }
-/* workgroups per CU of the instances (8-bit, then 16-bit: their staging lines are STAGE_BYTES16) */
+/* ... of an NV12 / NV21 source (8 bit): the NV instances — the LDS, and so the waves per SIMD, of the three-plane ones */
+template <int I> static void launch_generic_nv(dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
+{
+    constexpr SwsShape S = GENERIC_SHAPES[I];
+    hipLaunchKernelGGL((k_sws_generic<S.lcap, S.ccap, sws_waves(sws_lds_bytes(S.lcap, S.ccap, STAGE_BYTES)), uint8_t, true>), grid, dim3(NT), 0, s, d, frames);
+}
+static void launch_generic_nv(int i, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
+{
+    if (i == 0) launch_generic_nv<0>(grid, s, d, frames);
+    else if (i == 1) launch_generic_nv<1>(grid, s, d, frames);
+    else launch_generic_nv<2>(grid, s, d, frames);
+}
+/* form 0: three planes at CW = TW / 2, 1: at CW = TW, 2: a semi-planar destination */
+template <int I> static void launch_planar_nv(int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+{
+    constexpr SwsShape S = PLANAR_SHAPES[I];
+    if (form == 0) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, uint8_t, false, true>), grid, dim3(NT), 0, s, d, frames);
+    else if (form == 1) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW, uint8_t, false, true>), grid, dim3(NT), 0, s, d, frames);
+    else hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, uint8_t, true, true>), grid, dim3(NT), 0, s, d, frames);
+}
+static void launch_planar_nv(int i, int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+{
+    if (i == 0) launch_planar_nv<0>(form, grid, s, d, frames);
+    else if (i == 1) launch_planar_nv<1>(form, grid, s, d, frames);
+    else launch_planar_nv<2>(form, grid, s, d, frames);
+}
+/* workgroups per CU of the instances (8-bit, then 16-bit: their staging lines are STAGE_BYTES16); the NV instances stage the pair plane in the
+ * 8-bit instances' staging lines (StageGeom<TW>) and hold the same tiles: the 8-bit rows below are theirs too */
+static_assert(StageGeom<TW>::PITCH * StageGeom<TW>::LINES * 4 == STAGE_BYTES, "the pair plane's rounds fill the 8-bit staging storage");
 constexpr int generic_waves(int i, int stage) { return sws_waves(sws_lds_bytes(GENERIC_SHAPES[i].lcap, GENERIC_SHAPES[i].ccap, stage)); }
 constexpr int planar_waves(int i, int cw, int stage) { return sws_planar_waves(PLANAR_SHAPES[i].lcap, PLANAR_SHAPES[i].ccap, cw, stage); }
 static_assert(generic_waves(0, STAGE_BYTES) == 8 && generic_waves(1, STAGE_BYTES) == 7 && generic_waves(2, STAGE_BYTES) == 6, "workgroups per CU of the instances");
@@ -347,11 +417,15 @@ extern "C" int mi355_sws_scale_frames_dev(mi355_sws_ctx *c, const mi355_sws_fram
         else hipLaunchKernelGGL(k_sws_c24<1>, grid, dim3(NT), 0, s, &c->d->luts, h.dstW, h.srcH, 0, d_frames);      /* yuv422p: every other chroma line */
     } else if (k == MI355_SWS_K_IDENT1_1 || k == MI355_SWS_K_IDENT1_X) {
         const dim3 grid((h.dstW + C24_COLS - 1) / C24_COLS, (h.dstH + IDENT_ROWS - 1) / IDENT_ROWS, nframes);
-        if (k == MI355_SWS_K_IDENT1_1) hipLaunchKernelGGL(k_sws_ident1<false>, grid, dim3(NT), 0, s, c->d, d_frames);
+        if (h.src_layout) {
+            if (k == MI355_SWS_K_IDENT1_1) hipLaunchKernelGGL((k_sws_ident1<false, true>), grid, dim3(NT), 0, s, c->d, d_frames);
+            else hipLaunchKernelGGL((k_sws_ident1<true, true>), grid, dim3(NT), 0, s, c->d, d_frames);
+        } else if (k == MI355_SWS_K_IDENT1_1) hipLaunchKernelGGL(k_sws_ident1<false>, grid, dim3(NT), 0, s, c->d, d_frames);
         else hipLaunchKernelGGL(k_sws_ident1<true>, grid, dim3(NT), 0, s, c->d, d_frames);
     } else {
         const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
-        if (h.depth > 8) launch_generic<uint16_t>(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
+        if (h.src_layout) launch_generic_nv(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
+        else if (h.depth > 8) launch_generic<uint16_t>(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
         else launch_generic<uint8_t>(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
     }
     return hipGetLastError() == hipSuccess ? 0 : -2;
@@ -369,9 +443,15 @@ extern "C" int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *c, const mi355_s
                            h.srcW, h.srcH, h.planar == MI355_SWS_DST_NV21 ? 1 : 0, d_frames);
         return hipGetLastError() == hipSuccess ? 0 : -2;
     }
+    if (k == MI355_SWS_K_NV12_SPLIT) {
+        hipLaunchKernelGGL(k_sws_nv12_split, dim3((h.srcW + PACK_COLS - 1) / PACK_COLS, (h.srcH + PACK_ROWS - 1) / PACK_ROWS, nframes), dim3(NT), 0, s,
+                           h.srcW, h.srcH, h.src_layout == MI355_SWS_SRC_NV21 ? 1 : 0, d_frames);
+        return hipGetLastError() == hipSuccess ? 0 : -2;
+    }
     const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
     const int i = k - MI355_SWS_K_PLANAR_A;
-    if (semi_planar(h)) {
+    if (h.src_layout) launch_planar_nv(i, semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
+    else if (semi_planar(h)) {
         if (h.depth > 8) launch_semi<uint16_t>(i, grid, s, c->d, d_frames);
         else launch_semi<uint8_t>(i, grid, s, c->d, d_frames);
     } else if (h.depth > 8) launch_planar<uint16_t>(i, h.hshift, grid, s, c->d, d_frames);
@@ -397,8 +477,10 @@ static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int
     const SwsDev &h = c->h;
     const bool planar = h.planar != 0;
     const int B = h.depth > 8 ? 2 : 1;                                  /* bytes per source sample */
-    const int w[3] = { h.srcW * B, h.chrSrcW * B, h.chrSrcW * B }, ph[3] = { h.srcH, h.chrSrcH, h.chrSrcH };
-    for (int p = 0; p < 3; p++) if (!src[p] || src_stride[p] < w[p]) return -1;
+    /* an NV12 / NV21 source: two planes, the second one 2 * chrSrcW bytes of pairs; src[2] is not touched */
+    const int nsrc = h.src_layout ? 2 : 3;
+    const int w[3] = { h.srcW * B, h.src_layout ? 2 * h.chrSrcW : h.chrSrcW * B, h.src_layout ? 0 : h.chrSrcW * B }, ph[3] = { h.srcH, h.chrSrcH, h.chrSrcH };
+    for (int p = 0; p < nsrc; p++) if (!src[p] || src_stride[p] < w[p]) return -1;
     for (int p = 0; p < ndst; p++) if (!dst[p] || dst_stride[p] < back[p]) return -1;
     DeviceScope on(c->device);
     const int pw[3] = { (w[0] + 15) & ~15, (w[1] + 15) & ~15, (w[2] + 15) & ~15 };
@@ -409,7 +491,7 @@ static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int
         uint8_t *ns[3] = { nullptr, nullptr, nullptr }, *nd = nullptr;
         void *nf = nullptr;
         bool ok = true;
-        for (int p = 0; p < 3 && ok; p++) ok = hipMalloc(reinterpret_cast<void **>(&ns[p]), (size_t)pw[p] * ph[p] + 64) == hipSuccess;
+        for (int p = 0; p < nsrc && ok; p++) ok = hipMalloc(reinterpret_cast<void **>(&ns[p]), (size_t)pw[p] * ph[p] + 64) == hipSuccess;
         /* a packed destination has one row of slack, the planar planes 64 bytes */
         ok = ok && hipMalloc(reinterpret_cast<void **>(&nd), planar ? doff[ndst] + 64 : (size_t)dp[0] * (oh[0] + 1)) == hipSuccess;
         ok = ok && hipMalloc(&nf, planar ? sizeof(mi355_sws_planar_frame) : sizeof(mi355_sws_frame)) == hipSuccess;
@@ -435,7 +517,7 @@ static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int
         if (planar) c->d_pframe = static_cast<mi355_sws_planar_frame *>(nf);
         else c->d_frame = static_cast<mi355_sws_frame *>(nf);
     }
-    for (int p = 0; p < 3; p++)
+    for (int p = 0; p < nsrc; p++)
         if (!plane_h2d(c->d_src[p], pw[p], src[p], src_stride[p], w[p], ph[p], c->stream)) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4; }
     if ((planar ? mi355_sws_scale_planar_frames_dev(c, c->d_pframe, 1, c->stream) : mi355_sws_scale_frames_dev(c, c->d_frame, 1, c->stream)) != 0) {
         (void)hipStreamSynchronize(c->stream);
@@ -469,7 +551,9 @@ extern "C" int mi355_sws_scale_planar(mi355_sws_ctx *c, const uint8_t *const src
         const int r = scale_staged(c, src, src_stride, 2, dst, dst_stride, ow, oh, ow);
         return r ? r : h.dstH;
     }
-    const int ow[3] = { h.dstW, h.chrDstW, h.chrDstW }, oh[3] = { h.dstH, h.chrDstH, h.chrDstH };
+    /* the splitter writes (and so hands back) the rounded-down extents only */
+    const int cwb = h.special ? h.srcW >> 1 : h.chrDstW, chr = h.special ? h.srcH >> 1 : h.chrDstH;
+    const int ow[3] = { h.dstW, cwb, cwb }, oh[3] = { h.dstH, chr, chr };
     const int r = scale_staged(c, src, src_stride, 3, dst, dst_stride, ow, oh, ow);
     return r ? r : h.dstH;
 }

@@ -10,10 +10,12 @@
  *                   horizontal pass into LDS as above, the vertical pass from LDS straight to the three destination planes — or, for
  *                   NV12 / NV21 (yuv2nv12cX_c :267-301), to the luma plane and one plane of interleaved chroma pairs.
  *   k_sws_nv12_pack the unscaled packer planarToNv12Wrapper (swscale_unscaled.c:138-156) for 8-bit yuv420p -> NV12 / NV21.
+ *   k_sws_nv12_split the unscaled splitter nv12ToPlanarWrapper (swscale_unscaled.c:158-177) for 8-bit NV12 / NV21 -> yuv420p.
  *   k_sws_c24       the unscaled converter yuv2rgb_c_24_rgb (yuv2rgb.c:335-363) for 8-bit yuv420p and yuv422p.
  *   k_sws_ident1    the generic scaler on an 8-bit context that does not scale, from the source bytes.
  * The tile kernels are instantiated per sample type: the uint16_t instances differ in the horizontal pass (its staging lines are twice
- * as long, so is their LDS) and, for planar destinations, in the dither rows.
+ * as long, so is their LDS) and, for planar destinations, in the dither rows.  The NV instances of the tile kernels and of k_sws_ident1 read
+ * an NV12 / NV21 source: both chroma planes from one pass over its plane of byte pairs (hscale_tile_nv).
  *   k_sws_line_*    the individual inner loops for the Tier-1 entry points.
  * Execution model: 256-thread workgroups (4 waves) sharing one LDS tile; integer only, no MFMA.
  */
@@ -54,8 +56,9 @@ struct SwsDev {
     /* planar destinations (mi355_sws_create_planar): the MI355_SWS_DST_* format, its chroma subsampling and chroma rows (0 / 0 / 0 / dstH for rgb24) */
     int planar, hshift, vshift, chrDstH;
     /* the source side (mi355_sws_create_src): bits per sample (8: bytes; 9 / 10: uint16_t little endian), its chroma shifts, and the 8x8
-     * dither rows a planar destination takes from a source deeper than 8 bits (swscale.c:553-556) */
-    int depth, src_hsub, src_vsub, pad_;
+     * dither rows a planar destination takes from a source deeper than 8 bits (swscale.c:553-556); src_layout: MI355_SWS_SRC_* — 1 / 2: the
+     * second source plane holds chrSrcW byte pairs (NV12: U V, NV21: V U) and there is no third */
+    int depth, src_hsub, src_vsub, src_layout;
     __attribute__((aligned(8))) uint8_t dither[8][8];
 };
 
@@ -213,6 +216,10 @@ static inline uint32_t sws_lo2(uint32_t a, uint32_t b) { return (a & 0xFFFFu) | 
 static inline uint32_t sws_hi2(uint32_t a, uint32_t b) { return (a >> 16) | (b & 0xFFFF0000u); }        /* (a.hi, b.hi) */
 static inline uint32_t sws_zip_lo(uint32_t a, uint32_t b) { return (a & 0xFFu) | ((b & 0xFFu) << 8) | ((a & 0xFF00u) << 8) | ((b & 0xFF00u) << 16); }   /* a0 b0 a1 b1 */
 static inline uint32_t sws_zip_hi(uint32_t a, uint32_t b) { return sws_zip_lo(a >> 16, b >> 16); }                                               /* a2 b2 a3 b3 */
+static inline uint32_t sws_even2(uint32_t w) { return (w & 0xFFu) | (w & 0xFF0000u); }                  /* bytes 0, 2 as two 16-bit values */
+static inline uint32_t sws_odd2(uint32_t w) { return ((w >> 8) & 0xFFu) | ((w >> 8) & 0xFF0000u); }     /* bytes 1, 3 */
+static inline uint32_t sws_even4(uint32_t lo, uint32_t hi) { return (lo & 0xFFu) | ((lo >> 8) & 0xFF00u) | ((hi & 0xFFu) << 16) | ((hi << 8) & 0xFF000000u); }   /* bytes 0 2 4 6 of the eight */
+static inline uint32_t sws_odd4(uint32_t lo, uint32_t hi) { return sws_even4(lo >> 8, hi >> 8); }                                                        /* bytes 1 3 5 7 */
 #else
 __device__ __forceinline__ uint32_t sws_alignbyte(uint32_t hi, uint32_t lo, uint32_t s) { return __builtin_amdgcn_alignbyte(hi, lo, s); }
 /* bytes 2k, 2k + 1 of w as two 16-bit values */
@@ -222,6 +229,12 @@ __device__ __forceinline__ uint32_t sws_hi2(uint32_t a, uint32_t b) { return __b
 /* the bytes of two dwords interleaved: a0 b0 a1 b1 / a2 b2 a3 b3 */
 __device__ __forceinline__ uint32_t sws_zip_lo(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05010400u); }
 __device__ __forceinline__ uint32_t sws_zip_hi(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07030602u); }
+/* the de-interleave of byte pairs (an NV12 / NV21 source plane): bytes 0, 2 / 1, 3 of a dword as two 16-bit values (what v_dot2_i32_i16 takes),
+ * and bytes 0 2 4 6 / 1 3 5 7 of two dwords as one */
+__device__ __forceinline__ uint32_t sws_even2(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x0C020C00u); }
+__device__ __forceinline__ uint32_t sws_odd2(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x0C030C01u); }
+__device__ __forceinline__ uint32_t sws_even4(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x06040200u); }
+__device__ __forceinline__ uint32_t sws_odd4(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x07050301u); }
 typedef short sws_short2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int sws_dot2(uint32_t a, uint32_t b, int c)
 {
@@ -483,6 +496,191 @@ __device__ __forceinline__ void hscale_tile(int16_t (*out)[OP], const uint8_t *s
     }
 }
 
+/* ---- an NV12 / NV21 source: both chroma planes of a tile in ONE pass over the plane of byte pairs ------------------------------------
+ * The reference de-interleaves each chroma line into two temporary lines (nv12ToUV_c / nv21ToUV_c, input.c:475-497: dstU[i] = src[2 * i],
+ * dstV[i] = src[2 * i + 1]) and runs hcScale on each: column x reads its taps at bytes 2 * (pos + j) for the first plane of a pair and
+ * 2 * (pos + j) + 1 for the second, with the same coefficients.  out_a takes the first bytes of the pairs, out_b the second ones (the
+ * caller passes U, V for NV12 and V, U for NV21).  A function of its own beside hscale_tile, not a parameter of it: the three-plane
+ * instances keep their instruction streams.
+ * A tile's span is 2 * (pos[last] + fs - pos[gx0]) bytes — (64 * 2 + 8) * 2 + the 15 of an aligned start for a 2:1 reduction with 8 taps: 72
+ * dwords, the LUMA staging geometry (SRC_DW, SG lines a round) as it is, one round where the two planes take one each of the half geometry.
+ * 2 * pos is even, so after the funnel shift by 0 or 2 a staged dword holds A0 B0 A1 B1: one permute each gives the (A0, A1) and (B0, B1)
+ * 16-bit pairs of the dot product.  NPAIR tap pairs (taps rounded up to 2 / 4 / 8, those past fs carry a zero coefficient; the bytes exist:
+ * the two dwords of slack), 0: fs taps read as it goes. */
+template <int COLS, int NPAIR, int OP>
+__device__ __forceinline__ void hscale_lines_nv(const uint8_t *row0, int16_t *oa, int16_t *ob, const uint32_t *cp, int left, const int16_t *f = nullptr, int fs = 0)
+{
+    constexpr int per = NT / COLS, LINES = StageGeom<TW>::LINES, PITCH = StageGeom<TW>::PITCH, N = LINES / per;
+    static_assert(COLS >= 64, "a wave's threads share their first line: `left` is the same on all of them");
+    if constexpr (NPAIR == 0) {
+        for (int k = 0; k < N && k * per <= left; k++) {
+            const uint8_t *row = row0 + k * per * (PITCH * 4);
+            int a = 0, b = 0;
+            for (int j = 0; j < fs; j++) { a += (int)row[2 * j] * f[j]; b += (int)row[2 * j + 1] * f[j]; }
+            a >>= 7; b >>= 7;
+            oa[k * per * OP] = (int16_t)(a < 32767 ? a : 32767);
+            ob[k * per * OP] = (int16_t)(b < 32767 ? b : 32767);
+        }
+    } else {
+        const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(row0) & 3);       /* 0 or 2 */
+        const uint32_t *w0 = reinterpret_cast<const uint32_t *>(row0 - sh);
+        /* four lines at a time: their LDS reads go out together, then the arithmetic of the group (as hscale_lines8; the reads of a group are
+         * unconditional: the staged lines exist) */
+        constexpr int G = 4;
+        static_assert(N % G == 0, "whole groups of lines");
+#pragma unroll
+        for (int g = 0; g < N; g += G) {
+            if (g * per > left) break;
+            uint32_t d[G][NPAIR + 1];
+#pragma unroll
+            for (int q = 0; q < G; q++) {
+                const uint32_t *w = w0 + (g + q) * per * PITCH;
+#pragma unroll
+                for (int k = 0; k <= NPAIR; k++) d[q][k] = w[k];
+            }
+#pragma unroll
+            for (int q = 0; q < G; q++) {
+                if ((g + q) * per > left) break;                 /* of the wave, like the one between groups */
+                int a = 0, b = 0;
+#pragma unroll
+                for (int k = 0; k < NPAIR; k++) {
+                    const uint32_t m = sws_alignbyte(d[q][k + 1], d[q][k], sh);
+                    a = sws_dot2(sws_even2(m), cp[k], a);
+                    b = sws_dot2(sws_odd2(m), cp[k], b);
+                }
+                a >>= 7; b >>= 7;
+                oa[(g + q) * per * OP] = (int16_t)(a < 32767 ? a : 32767);
+                ob[(g + q) * per * OP] = (int16_t)(b < 32767 ? b : 32767);
+            }
+        }
+    }
+}
+/* srcW: pairs of a line (chrSrcW); stride in bytes.  Identity, staged and direct forms as hscale_tile's (a plane off 4-byte multiples — a pair
+ * may start on an odd address — a span wider than the staged line and non-monotonic banks: direct, two bytes a step) */
+template <int COLS, int OP>
+__device__ __forceinline__ void hscale_tile_nv(int16_t (*out_a)[OP], int16_t (*out_b)[OP], const uint8_t *src, int stride, int srcW, const int32_t *posT,
+                                               const int16_t *coefT, int fs, int gx0, int ncols, int lo, int hi,
+                                               uint32_t *stage_mem, int tid, bool may_stage, bool identity)
+{
+    constexpr int PITCH = StageGeom<TW>::PITCH, LINES = StageGeom<TW>::LINES;
+    uint32_t (*stage)[PITCH] = reinterpret_cast<uint32_t (*)[PITCH]>(stage_mem);
+    if (identity) {
+        /* src << 7 of both bytes of a pair.  Eight columns per thread: one 16-byte load of pairs (aligned planes, inside the line), two 16-byte
+         * LDS writes */
+        constexpr int TPL = COLS / 8;                  /* threads per line */
+        const int xg = 8 * (tid % TPL), gxi = gx0 + xg;
+        const bool al16 = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride | (uintptr_t)(2 * gx0)) & 15) == 0;
+        for (int l = lo + tid / TPL; l <= hi; l += NT / TPL) {
+            const uint8_t *p = src + (size_t)l * stride + 2 * gxi;
+            sws_u32x4 w = { 0u, 0u, 0u, 0u };
+            if (al16 && gxi + 8 <= srcW && gxi + 8 <= ncols) w = *reinterpret_cast<const sws_u32x4 *>(p);
+            else {
+                for (int k = 0; k < 8; k++)
+                    if (gxi + k < ncols && gxi + k < srcW) w[k >> 1] |= ((uint32_t)p[2 * k] | ((uint32_t)p[2 * k + 1] << 8)) << (16 * (k & 1));
+            }
+            sws_u32x4 a, b;
+            for (int k = 0; k < 4; k++) { a[k] = sws_even2(w[k]) << 7; b[k] = sws_odd2(w[k]) << 7; }
+            if (gxi < ncols) {
+                *reinterpret_cast<sws_u32x4 *>(&out_a[l - lo][xg]) = a;
+                *reinterpret_cast<sws_u32x4 *>(&out_b[l - lo][xg]) = b;
+            }
+        }
+        return;
+    }
+    const int x = tid & (COLS - 1), gx = gx0 + x, per = NT / COLS;
+    const bool col_ok = gx < ncols;
+    /* no load below sits under a lane condition: columns past the picture read the last column's entries and do not use them */
+    const int gxc = col_ok ? gx : ncols - 1;
+    const int pos = posT[gxc];
+    const int16_t *f = coefT + (size_t)gxc * fs;
+    const int last = imin(gx0 + COLS, ncols) - 1;
+    const bool al16 = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 15) == 0;
+    const int s0 = 2 * posT[gx0], s1 = 2 * (posT[last] + fs), a0 = al16 ? (s0 & ~15) : (s0 & ~3), nd = (s1 - a0 + 3) >> 2;     /* bytes */
+    uint32_t cp[4];
+    if (fs == 8) {
+        const uint4 w = *reinterpret_cast<const uint4 *>(f);
+        cp[0] = w.x; cp[1] = w.y; cp[2] = w.z; cp[3] = w.w;
+    } else {
+        int t[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) t[j] = f[j < fs ? j : 0];
+#pragma unroll
+        for (int j = 0; j < 4; j++) cp[j] = (2 * j < fs ? (uint32_t)t[2 * j] & 0xFFFFu : 0u) | (2 * j + 1 < fs ? (uint32_t)t[2 * j + 1] << 16 : 0u);
+    }
+    const bool staged = may_stage && span_fits(nd, s0, s1, PITCH) && ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 3) == 0;
+    if (!staged) {
+        if (col_ok) {
+            for (int l = lo + tid / COLS; l <= hi; l += per) {
+                const uint8_t *s = src + (size_t)l * stride + 2 * pos;
+                int a = 0, b = 0;
+                for (int j = 0; j < fs; j++) { a += (int)s[2 * j] * f[j]; b += (int)s[2 * j + 1] * f[j]; }
+                a >>= 7; b >>= 7;
+                out_a[l - lo][x] = (int16_t)(a < 32767 ? a : 32767);
+                out_b[l - lo][x] = (int16_t)(b < 32767 ? b : 32767);
+            }
+        }
+        return;
+    }
+    static_assert(LINES * PITCH * PITCH < (1 << 19), "mi355_div20 range");
+    const int np = al16 ? (nd + 3) >> 2 : nd, inv = mi355_inv20(np);
+    /* 16-byte pieces travel through registers, one round ahead, as in hscale_tile */
+    constexpr int PF = (LINES * ((PITCH + 3) / 4) + NT - 1) / NT;
+    uint4 pre[PF];
+    int p_row[PF], p_col[PF];
+    uint32_t *p_lds[PF];
+#pragma unroll
+    for (int j = 0; j < PF; j++) {
+        const int idx = imin(tid + j * NT, LINES * np - 1), r = mi355_div20(idx, inv), d = idx - r * np, off = a0 + 16 * d;
+        p_row[j] = r;
+        p_col[j] = imin(off, (2 * srcW - 1) & ~15);
+        p_lds[j] = &stage[r][4 * d];
+    }
+    auto fetch16 = [&](int base) {
+#pragma unroll
+        for (int j = 0; j < PF; j++) {
+            if (j * NT >= LINES * np) break;
+            /* the aligned 16 bytes lie inside the line's stride (both multiples of 16, column < 2 * srcW <= stride): always readable */
+            const uint4 w = *reinterpret_cast<const uint4 *>(src + (size_t)imin(base + p_row[j], hi) * stride + p_col[j]);
+            pre[j] = w;
+        }
+    };
+    if (al16) fetch16(lo);
+    for (int base = lo; base <= hi; base += LINES) {
+        if (al16) {
+#pragma unroll
+            for (int j = 0; j < PF; j++) {
+                if (j * NT >= LINES * np) break;
+                *reinterpret_cast<uint4 *>(p_lds[j]) = pre[j];
+            }
+        } else
+        for (int idx = tid; idx < LINES * np; idx += NT) {
+            const int r = mi355_div20(idx, inv), d = idx - r * np, line = base + r;
+            if (line > hi) continue;
+            const uint8_t *p = src + (size_t)line * stride + a0 + 4 * d;
+            uint32_t w;
+            if (a0 + 4 * d + 4 <= 2 * srcW) w = *reinterpret_cast<const uint32_t *>(p);
+            else {
+                w = 0;
+                for (int b = 0; b < 4; b++) if (a0 + 4 * d + b < 2 * srcW) w |= (uint32_t)p[b] << (8 * b);
+            }
+            stage[r][d] = w;
+        }
+        __syncthreads();
+        if (al16 && base + LINES <= hi) fetch16(base + LINES);
+        const int r0 = tid / COLS;
+        const uint8_t *row0 = reinterpret_cast<const uint8_t *>(stage[r0]) + (2 * pos - a0);
+        int16_t *oa = &out_a[base + r0 - lo][x], *ob = &out_b[base + r0 - lo][x];
+        const int left = uniform(hi - base - r0);
+        if (col_ok) {
+            if (fs <= 2) hscale_lines_nv<COLS, 1, OP>(row0, oa, ob, cp, left);
+            else if (fs <= 4) hscale_lines_nv<COLS, 2, OP>(row0, oa, ob, cp, left);
+            else if (fs <= 8) hscale_lines_nv<COLS, 4, OP>(row0, oa, ob, cp, left);
+            else hscale_lines_nv<COLS, 0, OP>(row0, oa, ob, cp, left, f, fs);
+        }
+        __syncthreads();
+    }
+}
+
 /* Vertical pass + LUT for the output rows of a tile with the row's filter taps and source-line indices in
  * registers: NL / NC = luma / chroma tap counts rounded up to 1, 2, 4 or 8 (taps past the real size carry a
  * zero coefficient and a valid line index).  A thread owns one output row and every 16th pair of it. */
@@ -720,7 +918,9 @@ __device__ __forceinline__ void vertical_narrow(const SwsDev *cp, const LutLds *
 
 /* LCAP / CCAP: a row of GENERIC_SHAPES; WAVES: sws_waves() of the instance's LDS */
 /* ST: the source's sample type; the uint16_t instances (9 / 10 bit sources) differ in the horizontal pass and its staging lines only */
-template <int LCAP, int CCAP, int WAVES, typename ST = uint8_t>
+/* NV: an NV12 / NV21 source (8 bit) — both chroma tiles from ONE pass over fr.src[1], the plane of pairs (hscale_tile_nv); fr.src[2] is not read.
+ * The same LDS, so the same workgroups per CU.  The three-plane instances are the NV false ones, unchanged. */
+template <int LCAP, int CCAP, int WAVES, typename ST = uint8_t, bool NV = false>
 #ifndef MI355_HIP_EMU_H
 __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
 #endif
@@ -749,8 +949,15 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
      * zero-initialised tail of the reference's line buffer, utils.c:1241-1262), then the chroma planes */
     uint32_t *s_stage = reinterpret_cast<uint32_t *>(s_io);
     hscale_tile<TW, TW, ST>(s_lum, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi, s_stage, tid, true, c.hstage != 0, c.hident_l != 0, c.depth);
+    if constexpr (NV) {
+        static_assert(sizeof(ST) == 1, "NV12 / NV21 sources are 8 bit");
+        const bool vu = c.src_layout == MI355_SWS_SRC_NV21;         /* the first byte of a pair is V */
+        hscale_tile_nv<TW / 2, TW / 2>(vu ? s_cv : s_cu, vu ? s_cu : s_cv, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi,
+                                       s_stage, tid, c.hstage != 0, c.hident_c != 0);
+    } else {
     hscale_tile<TW / 2, TW / 2, ST>(s_cu, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, c.depth);
     hscale_tile<TW / 2, TW / 2, ST>(s_cv, fr.src[2], fr.src_stride[2], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, c.depth);
+    }
     __syncthreads();
     /* vertical pass + LUT */
     const int mode = packed_mode(ls, cs);
@@ -989,8 +1196,9 @@ __host__ __device__ constexpr int sws_planar_waves(int lum_lines, int chr_lines,
  * cy << vshift, chrSkipMask).  Horizontal pass of the source lines the tile needs into LDS (hscale_tile, as k_sws_generic), then the
  * vertical pass from LDS straight to the three planes.  LCAP / CCAP: a row of PLANAR_SHAPES.
  * SEMI: an NV12 / NV21 destination (4:2:0, CW = TW / 2) — the chroma rows go to ONE plane of byte pairs, fr.dst[1] (semiplanar_rows);
- * fr.dst[2] is not used.  The three-plane instances are the SEMI false ones, unchanged. */
-template <int LCAP, int CCAP, int CW, typename ST = uint8_t, bool SEMI = false>
+ * fr.dst[2] is not used.  The three-plane instances are the SEMI false ones, unchanged.
+ * NV: an NV12 / NV21 source, as k_sws_generic's — U | V of an LDS line from one pass over fr.src[1]. */
+template <int LCAP, int CCAP, int CW, typename ST = uint8_t, bool SEMI = false, bool NV = false>
 #ifndef MI355_HIP_EMU_H
 __attribute__((amdgpu_waves_per_eu(sws_planar_waves(LCAP, CCAP, CW, stage_bytes<ST>()), sws_planar_waves(LCAP, CCAP, CW, stage_bytes<ST>()))))
 #endif
@@ -1014,10 +1222,18 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
     if (cy0 <= cy1) {
         clo = clampi(imax(1 - cs, c.vChrP[cy0]), 0, c.chrSrcH - 1);
         const int chi = clampi(imax(1 - cs, c.vChrP[cy1]) + cs - 1, 0, c.chrSrcH - 1);
+        if constexpr (NV) {
+            static_assert(sizeof(ST) == 1, "NV12 / NV21 sources are 8 bit");
+            int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
+            const bool vu = c.src_layout == MI355_SWS_SRC_NV21;
+            hscale_tile_nv<CW, 2 * CW>(vu ? s_v : s_u, vu ? s_u : s_v, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> hs, c.chrDstW, clo, chi,
+                                       s_stage, tid, c.hstage != 0, c.hident_c != 0);
+        } else {
         hscale_tile<CW, 2 * CW, ST>(s_chr, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false,
                                     c.hstage != 0, c.hident_c != 0, c.depth);
         hscale_tile<CW, 2 * CW, ST>(reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]), fr.src[2], fr.src_stride[2], c.chrSrcW, c.hChrP, c.hChrC, c.hcs,
                                     x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, c.depth);
+        }
     }
     __syncthreads();
     const uint8_t (*dith)[8] = DITH ? mi355_global(cp)->dither : nullptr;
@@ -1096,6 +1312,66 @@ __global__ void __launch_bounds__(NT) k_sws_nv12_pack(int srcW, int srcH, int sw
             const uint8_t *s1 = first + (size_t)cy * st_first + cx, *s2 = second + (size_t)cy * st_second + cx;
             const int n = imin(8, cw - cx);
             for (int i = 0; i < n; i++) { d[2 * i] = s1[i]; d[2 * i + 1] = s2[i]; }
+        }
+    }
+}
+
+/* ---- the unscaled splitter: 8-bit NV12 / NV21 -> yuv420p at equal size (nv12ToPlanarWrapper, swscale_unscaled.c:158-177) -------------
+ * The packer's mirror: srcW x srcH luma bytes copied, srcW / 2 pairs on srcH / 2 rows de-interleaved (deinterleaveBytes), both rounded
+ * down — the last byte of an odd width's chroma rows and the last chroma row of an odd height are neither read nor written.  The same
+ * tile and launch shape, every load requested before the first store.  A 16-byte piece of pairs becomes two 8-byte stores where the pair
+ * plane is on 16-byte and both destination chroma planes on 8-byte multiples; otherwise sample by sample.  swap_uv (NV21): the first byte
+ * of a pair goes to dst[2]. */
+__global__ void __launch_bounds__(NT) k_sws_nv12_split(int srcW, int srcH, int swap_uv, const mi355_sws_planar_frame *frames)
+{
+    mi355_sws_planar_frame fr = frames[blockIdx.z];
+    fr.src[0] = mi355_global(fr.src[0]); fr.src[1] = mi355_global(fr.src[1]);
+    for (int k = 0; k < 3; k++) fr.dst[k] = mi355_global(fr.dst[k]);
+    const int tid = threadIdx.x, lane = tid & 63, rg = tid >> 6;
+    const int x = blockIdx.x * PACK_COLS + 16 * lane, y0 = blockIdx.y * PACK_ROWS;
+    const int cw = srcW >> 1, ch = srcH >> 1, cx = x >> 1, cy0 = y0 >> 1;                     /* pairs, chroma rows: rounded down */
+    uint8_t *first = swap_uv ? fr.dst[2] : fr.dst[1], *second = swap_uv ? fr.dst[1] : fr.dst[2];
+    const int st_first = swap_uv ? fr.dst_stride[2] : fr.dst_stride[1], st_second = swap_uv ? fr.dst_stride[1] : fr.dst_stride[2];
+    const bool lwide = x + 16 <= srcW &&
+                       ((reinterpret_cast<uintptr_t>(fr.src[0]) | (uintptr_t)fr.src_stride[0] | reinterpret_cast<uintptr_t>(fr.dst[0]) | (uintptr_t)fr.dst_stride[0]) & 15) == 0;
+    const bool cwide = cx + 8 <= cw && ((reinterpret_cast<uintptr_t>(fr.src[1]) | (uintptr_t)fr.src_stride[1]) & 15) == 0 &&
+                       ((reinterpret_cast<uintptr_t>(first) | (uintptr_t)st_first | reinterpret_cast<uintptr_t>(second) | (uintptr_t)st_second) & 7) == 0;
+    constexpr int LR = PACK_ROWS / (NT / 64), CR = PACK_ROWS / 2 / (NT / 64);                 /* luma / chroma rows of a thread */
+    sws_u32x4 l[LR] = {}, p[CR] = {};
+#pragma unroll
+    for (int k = 0; k < LR; k++) {
+        const int y = y0 + rg + k * (NT / 64);
+        if (lwide && y < srcH) l[k] = *reinterpret_cast<const sws_u32x4 *>(fr.src[0] + (size_t)y * fr.src_stride[0] + x);
+    }
+#pragma unroll
+    for (int k = 0; k < CR; k++) {
+        const int cy = cy0 + rg + k * (NT / 64);
+        if (cwide && cy < ch) p[k] = *reinterpret_cast<const sws_u32x4 *>(fr.src[1] + (size_t)cy * fr.src_stride[1] + 2 * cx);
+    }
+#pragma unroll
+    for (int k = 0; k < LR; k++) {
+        const int y = y0 + rg + k * (NT / 64);
+        if (y >= srcH || x >= srcW) continue;
+        uint8_t *d = fr.dst[0] + (size_t)y * fr.dst_stride[0] + x;
+        if (lwide) *reinterpret_cast<sws_u32x4 *>(d) = l[k];
+        else {
+            const uint8_t *sp = fr.src[0] + (size_t)y * fr.src_stride[0] + x;
+            const int n = imin(16, srcW - x);
+            for (int i = 0; i < n; i++) d[i] = sp[i];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < CR; k++) {
+        const int cy = cy0 + rg + k * (NT / 64);
+        if (cy >= ch || cx >= cw) continue;
+        uint8_t *d1 = first + (size_t)cy * st_first + cx, *d2 = second + (size_t)cy * st_second + cx;
+        if (cwide) {
+            *reinterpret_cast<sws_u32x2 *>(d1) = sws_u32x2{ sws_even4(p[k][0], p[k][1]), sws_even4(p[k][2], p[k][3]) };
+            *reinterpret_cast<sws_u32x2 *>(d2) = sws_u32x2{ sws_odd4(p[k][0], p[k][1]), sws_odd4(p[k][2], p[k][3]) };
+        } else {
+            const uint8_t *sp = fr.src[1] + (size_t)cy * fr.src_stride[1] + 2 * cx;
+            const int n = imin(8, cw - cx);
+            for (int i = 0; i < n; i++) { d1[i] = sp[2 * i]; d2[i] = sp[2 * i + 1]; }
         }
     }
 }
@@ -1187,7 +1463,9 @@ __global__ void __launch_bounds__(NT) k_sws_c24(const mi355_sws_luts *luts, int 
  *     a pair's four values clipped only if one of them has bit 8 set.
  * 512 x 16 sample tiles, a thread eight samples of a line per step; the rows' table entries, then all the samples of a thread are requested before the LUT copy (two round
  * trips per workgroup instead of the tile's staging rounds and barriers).  Only for even dstW (the phantom partner of an odd width's last sample stays with k_sws_generic). */
-template <bool X>
+/* NV: an NV12 / NV21 source — per tap line one 8-byte load of four pairs from fr.src[1] in place of the two 4-byte loads, U and V out of it with
+ * one permute each; the wide form asks the pair plane for 8-byte multiples; fr.src[2] is not read */
+template <bool X, bool NV = false>
 __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355_sws_frame *frames)
 {
     __shared__ LutLds s_lut;
@@ -1203,9 +1481,11 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
     const int x = blockIdx.x * C24_COLS + (tid & 63) * 8;   /* first of the thread's eight samples */
     const int npairs = dstW >> 1;
     const bool mine = (x >> 1) < npairs;
-    const bool wide = mine && (x >> 1) + 4 <= npairs &&
-                      ((reinterpret_cast<uintptr_t>(fr.src[0]) | (uintptr_t)fr.src_stride[0] | reinterpret_cast<uintptr_t>(fr.dst) | (uintptr_t)fr.dst_stride) & 7) == 0 &&
-                      ((reinterpret_cast<uintptr_t>(fr.src[1]) | (uintptr_t)fr.src_stride[1] | reinterpret_cast<uintptr_t>(fr.src[2]) | (uintptr_t)fr.src_stride[2]) & 3) == 0;
+    bool wide = mine && (x >> 1) + 4 <= npairs &&
+                ((reinterpret_cast<uintptr_t>(fr.src[0]) | (uintptr_t)fr.src_stride[0] | reinterpret_cast<uintptr_t>(fr.dst) | (uintptr_t)fr.dst_stride) & 7) == 0;
+    if constexpr (NV) wide = wide && ((reinterpret_cast<uintptr_t>(fr.src[1]) | (uintptr_t)fr.src_stride[1]) & 7) == 0;
+    else wide = wide && ((reinterpret_cast<uintptr_t>(fr.src[1]) | (uintptr_t)fr.src_stride[1] | reinterpret_cast<uintptr_t>(fr.src[2]) | (uintptr_t)fr.src_stride[2]) & 3) == 0;
+    const int vu = NV && cp->src_layout == MI355_SWS_SRC_NV21;      /* the first byte of a pair is V */
     constexpr int NR = IDENT_ROWS / (NT / 64);
     /* the rows' lines and taps: every load unconditional (rows past the picture repeat its last row and are not written; a tap past the filter reads tap 0 and becomes zero) */
     int li[NR], lf[NR], c0[NR], cf[NR][NC];
@@ -1218,6 +1498,7 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
     }
     sws_u32x2 ya[NR];
     uint32_t u[NR][NC], v[NR][NC];
+    sws_u32x2 uv[NR][NC];                            /* NV: a tap line's four pairs as they lie */
     int ci[NR][NC];
 #pragma unroll
     for (int q = 0; q < NR; q++) {
@@ -1230,6 +1511,11 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
             cf[q][j] = j < cs ? cf[q][j] : 0;
             ci[q][j] = clampi(cfirst + (j < cs ? j : 0), 0, chrSrcH - 1);
             u[q][j] = v[q][j] = 0;
+            if constexpr (NV) {
+                /* the pairs are taken apart behind the barrier, so that no load is waited for before the last one is requested */
+                uv[q][j] = sws_u32x2{ 0u, 0u };
+                if (wide) uv[q][j] = *reinterpret_cast<const sws_u32x2 *>(fr.src[1] + (size_t)ci[q][j] * fr.src_stride[1] + x);
+            } else
             if (wide) {
                 u[q][j] = *reinterpret_cast<const uint32_t *>(fr.src[1] + (size_t)ci[q][j] * fr.src_stride[1] + (x >> 1));
                 v[q][j] = *reinterpret_cast<const uint32_t *>(fr.src[2] + (size_t)ci[q][j] * fr.src_stride[2] + (x >> 1));
@@ -1263,6 +1549,13 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
         };
         if (wide) {
             int Y[8], r[4], g[4], b[4];
+            if constexpr (NV) {
+#pragma unroll
+                for (int j = 0; j < NC; j++) {
+                    const uint32_t e = sws_even4(uv[q][j][0], uv[q][j][1]), o = sws_odd4(uv[q][j][0], uv[q][j][1]);
+                    u[q][j] = vu ? o : e; v[q][j] = vu ? e : o;
+                }
+            }
 #pragma unroll
             for (int p = 0; p < 4; p++) {
                 int us[NC], vs[NC], U, V;
@@ -1279,8 +1572,13 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
                 int us[NC], vs[NC], Y1, Y2, U, V;
 #pragma unroll
                 for (int j = 0; j < NC; j++) {
+                    if constexpr (NV) {
+                        const uint8_t *pp = fr.src[1] + (size_t)ci[q][j] * fr.src_stride[1] + x + 2 * p;
+                        us[j] = pp[vu]; vs[j] = pp[1 - vu];
+                    } else {
                     us[j] = fr.src[1][(size_t)ci[q][j] * fr.src_stride[1] + (x >> 1) + p];
                     vs[j] = fr.src[2][(size_t)ci[q][j] * fr.src_stride[2] + (x >> 1) + p];
+                    }
                 }
                 pair(py[2 * p], py[2 * p + 1], us, vs, Y1, Y2, U, V);
                 write_pair(s_lut, d + 6 * p, Y1, Y2, U, V);

@@ -29,8 +29,13 @@ def main():
                     help="NV12 destinations beside the yuv420p destination of the same shape (2160p -> 1080p from 8 bits, 1080p equal size from 10 "
                          "bits), the unscaled packer beside k_sws_c24, and with --other-lib the three existing points; 32 and 512 pictures per "
                          "launch, 3 warm-up + --steps launches a round, alternating, median of 3 rounds")
+    ap.add_argument("--nvsrc", action="store_true",
+                    help="NV12 sources (mi355_sws_create_src_layout) beside the yuv420p twin of the same shape on --other-lib (the parent commit's "
+                         "build; this build without it): 2160p -> 1080p rgb24, 1080p -> rgb24 at equal size (ident1_x), 2160p -> 1080p nv12, the "
+                         "unscaled splitter beside the packer at 1080p, one twin a second time in another allocation (A/A), and with --other-lib "
+                         "the three existing points; 32 and 512 pictures per launch, 3 warm-up + --steps launches a round, alternating, median of 3 rounds")
     ap.add_argument("--other-lib", default=None,
-                    help="--nv12: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
+                    help="--nv12 / --nvsrc: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
     ap.add_argument("--rounds", type=int, default=5, help="--planar / --sources: alternating rounds (the median is reported)")
     a = ap.parse_args()
     prov = providers.mi355()
@@ -43,6 +48,8 @@ def main():
         return sources(a, lib)
     if a.nv12:
         return nv12(a, lib)
+    if a.nvsrc:
+        return nvsrc(a, lib)
     orc = S.oracle_backend(providers.oracle())
     for name in a.configs.split(","):
         ctx = S.load_context(name)
@@ -123,7 +130,7 @@ class SourceBatch:
     """`frames` pictures of one entry of tests/sws_sources.py resident in HBM, each with its own source planes (the first two uploaded, the
     rest device-side copies) and its own rgb24 destination"""
 
-    def __init__(self, lib, X, e, pics, frames):
+    def __init__(self, lib, X, e, pics, frames, create=None):
         self.lib, self.bufs, self.n = lib, [], frames
         lib.mi355_malloc.restype = C.c_void_p
         lib.mi355_malloc.argtypes = [C.c_size_t]
@@ -133,7 +140,7 @@ class SourceBatch:
         d = e.ctx.desc
         arr = (S.SwsFrame * frames)()
         self.src_bytes = 0
-        for p in range(3):
+        for p in range(len(pics[0])):                 # (two planes for an NV12 / NV21 source)
             psz = pics[0][p].nbytes
             self.src_bytes += psz
             base = self.alloc(frames * psz + 64)
@@ -152,7 +159,7 @@ class SourceBatch:
             arr[f].dst, arr[f].dst_stride = dst + f * self.dst_bytes, d.dstW * 3
         self.d_frames = self.alloc(C.sizeof(arr))
         lib.mi355_memcpy_h2d(self.d_frames, C.addressof(arr), C.sizeof(arr))
-        self.handle = X.create(lib, e)
+        self.handle = (create or X.create)(lib, e)
         assert self.handle
         lib.mi355_sws_scale_frames_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
 
@@ -234,7 +241,7 @@ class PlaneBatch:
             getattr(lib, f).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         arr = (P.PlanarFrame * frames)()
         self.src_bytes = 0
-        for p in range(3):
+        for p in range(len(pics[0])):                 # (two planes for an NV12 / NV21 source)
             psz = pics[0][p].nbytes
             self.src_bytes += psz
             base = self.alloc(frames * psz + 64)
@@ -361,6 +368,95 @@ def nv12(a, lib):
             batches = {tag: (l, S.DeviceBatch(l, ctx, pics, a.frames)) for tag, l in (("other", libs["other"]), ("this", lib))}
             nb = d.srcW * d.srcH + 2 * d.chrSrcW * d.chrSrcH + d.dstW * d.dstH * 3
             report(name, a.frames, batches, {k: nb for k in batches}, alternate(batches), {})
+            for l, b in batches.values():
+                b.close()
+
+
+def nvsrc(a, lib):
+    """NV12 sources beside their yuv420p twins (the same sizes, destination and flags: the same banks).  The contexts come from the reference's
+    libswscale at run time (oracle/_ref/libswsref.so: mi355_sws_describe_fmt / mi355_sws_describe_src) — no full-size context is committed.
+    The twin runs on --other-lib (the parent commit's build) where one is given; `twin#2` is the twin's context a second time with its own
+    buffers: identical code in two allocations, the session's A/A spread.  The splitter's twin is the packer.  One process, the batches of a
+    point alternating: 3 warm-up + --steps launches a round, median of 3 rounds, at 32 and 512 pictures per launch.  Algorithmic bytes: the
+    source planes read once + the destination planes written once."""
+    import statistics
+    import numpy as np
+    import sws_nv12 as N
+    import sws_nvsrc as V
+    import sws_planar as P
+    import sws_sources as X
+    libs = {"this": lib}
+    if a.other_lib:
+        other = C.CDLL(os.path.abspath(a.other_lib))
+        other.mi355_init.restype = C.c_int
+        assert other.mi355_init(C.c_int(0)) == 0
+        other.mi355_event_create.restype = C.c_void_p
+        other.mi355_event_elapsed_ms.restype = C.c_float
+        libs["other"] = other
+    twin_tag, twin_lib = ("parent", libs["other"]) if a.other_lib else ("this", lib)
+    ref = V.Ref(P.bind(V.REF_LIB))
+    rounds = 3
+    # (point, srcW, srcH, dstW, dstH, destination)
+    points = [("uhd_to_hd_rgb24", 3840, 2160, 1920, 1080, "rgb"), ("hd_same_rgb24", 1920, 1080, 1920, 1080, "rgb"),
+              ("uhd_to_hd_nv12", 3840, 2160, 1920, 1080, "nv12"), ("hd_split", 1920, 1080, 1920, 1080, "420")]
+
+    def batch(l, e, pics, frames, create):
+        if e.fmt == 0:
+            return SourceBatch(l, X, e, pics, frames, create=create)
+        return PlaneBatch(l, create(l, e), pics, e.out_sizes(), frames)
+
+    for frames in (32, 512):
+        for point, sw, sh, dw, dh, dst in points:
+            flags = ref.lib.ref_sws_flags_word(1, 1, 1)
+            c = ref.open_formats(sw, sh, b"nv12", dw, dh, V.AV_DST[dst], flags)
+            e = ref.describe(c)
+            ref.free(c)
+            # the twin: yuv420p in; the splitter's is the packer (yuv420p -> nv12 at equal size)
+            tdst = "nv12" if point == "hd_split" else dst
+            c = ref.open_formats(sw, sh, b"yuv420p", dw, dh, V.AV_DST[tdst], flags)
+            t = ref.describe_src(c)
+            ref.free(c)
+            assert e is not None and t is not None, point
+            t = N.Entry.of(t)
+            V.SHAPES["_bench"] = (sw, sh, dw, dh, "nv12", dst, 1, 1, 1)
+            X.SHAPES["_bench"] = (sw, sh, dw, dh, "420", 8, "rgb", 1, 1, 1)
+            npics = [[np.ascontiguousarray(pl) for pl in V.picture("_bench", seed=s)] for s in (1, 2)]
+            tpics = [[np.ascontiguousarray(pl) for pl in X.picture("_bench", seed=s)] for s in (1, 2)]
+            batches = {"nv12_source@this": (lib, batch(lib, e, npics, frames, V.create)),
+                       "twin@" + twin_tag: (twin_lib, batch(twin_lib, t, tpics, frames, X.create)),
+                       "twin#2@" + twin_tag: (twin_lib, batch(twin_lib, t, tpics, frames, X.create))}
+            plan = V.plan_of(lib, batches["nv12_source@this"][1].handle)
+            extra = {"nv12_source@this": {"kernel": plan["kernel"], "hstaged": plan["hstaged"]}}
+            nbytes = {k: b.src_bytes + b.dst_bytes for k, (l, b) in batches.items()}
+            times = {k: [] for k in batches}
+            for _ in range(rounds):
+                for k, (l, b) in batches.items():
+                    times[k].append(time_ms(l, b.run, a.steps))
+            for k in batches:
+                ms = statistics.median(times[k])
+                us = ms * 1e3 / frames
+                out = {"workload": point + ":" + k, "frames_per_launch": frames, "ms_per_launch": ms, "us_per_picture": us,
+                       "algorithmic_bytes_per_frame": nbytes[k], "achieved_GBps": nbytes[k] / us * 1e-3, "frac_of_8TBps": nbytes[k] / us * 1e-3 / 8000.0,
+                       "ms_rounds": [round(x, 4) for x in times[k]]}
+                out.update(extra.get(k, {}))
+                print(json.dumps(out), flush=True)
+            for l, b in batches.values():
+                b.close()
+    if "other" in libs:
+        for name in a.configs.split(","):
+            ctx = S.load_context(name)
+            d = ctx.desc
+            pics = [S.picture(name, seed=s) for s in (1, 2)]
+            batches = {tag: (l, S.DeviceBatch(l, ctx, pics, a.frames)) for tag, l in (("parent", libs["other"]), ("this", lib))}
+            nb = d.srcW * d.srcH + 2 * d.chrSrcW * d.chrSrcH + d.dstW * d.dstH * 3
+            times = {k: [] for k in batches}
+            for _ in range(rounds):
+                for k, (l, b) in batches.items():
+                    times[k].append(time_ms(l, b.run, a.steps))
+            for k in batches:
+                ms = statistics.median(times[k])
+                print(json.dumps({"workload": name + ":" + k, "frames_per_launch": a.frames, "ms_per_launch": ms, "algorithmic_bytes_per_frame": nb,
+                                  "ms_rounds": [round(x, 4) for x in times[k]]}), flush=True)
             for l, b in batches.values():
                 b.close()
 
