@@ -48,6 +48,11 @@
  *                          unscaled splitter (nv12 / nv21 -> yuv420p at equal size, nv12ToPlanarWrapper) for callers of the C ABI; like the
  *                          packer it is set outside the two wrapped selectors.  mi355_sws_describe / _planar / _src keep their answers:
  *                          they decline these sources.
+ *   packed RGB sources     rgb24 / bgr24 (the reference runs c->lumToYV12 and c->chrToYV12 — rgb24ToY_c, rgb24ToUV_c or rgb24ToUV_half_c and their
+ *                          bgr24 forms — on each line and then the ordinary hyScale / hcScale) take the same two forms to every destination
+ *                          above through mi355_sws_describe_fmt() / mi355_sws_create_src_layout(): whole pictures hand over ONE source plane;
+ *                          with MI355_SWS_LINES=1 the two converters are forwarded too (mi355_sws_rgb24ToY / mi355_sws_rgb24ToUV).  The
+ *                          unscaled converters of these sources (bgr24ToYv12Wrapper, rgbToRgbWrapper, the copy) stay the reference's.
  * The device is MI355_DEVICE (default 0), as for the decoder bridges.
  */
 #include <pthread.h>
@@ -227,9 +232,20 @@ int mi355_sws_describe_src(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_sr
  * c->chrToYV12 alone (nv12ToUV_c / nv21ToUV_c, input.c:475-497) — as an 8-bit 4:2:0 source of the layout.  special: nv12ToPlanarWrapper */
 static int fmt_format(const SwsContext *c, mi355_sws_src *s, int special, int *layout)
 {
-    *layout = c->srcFormat == AV_PIX_FMT_NV12 ? MI355_SWS_SRC_NV12 : (c->srcFormat == AV_PIX_FMT_NV21 ? MI355_SWS_SRC_NV21 : MI355_SWS_SRC_PLANAR);
+    *layout = c->srcFormat == AV_PIX_FMT_NV12 ? MI355_SWS_SRC_NV12 : (c->srcFormat == AV_PIX_FMT_NV21 ? MI355_SWS_SRC_NV21 :
+              (c->srcFormat == AV_PIX_FMT_RGB24 ? MI355_SWS_SRC_RGB24 : (c->srcFormat == AV_PIX_FMT_BGR24 ? MI355_SWS_SRC_BGR24 : MI355_SWS_SRC_PLANAR)));
     if (!*layout) return src_format(c, s, special);
     memset(s, 0, sizeof(*s));
+    if (*layout == MI355_SWS_SRC_RGB24 || *layout == MI355_SWS_SRC_BGR24) {
+        /* packed RGB: BOTH input converters (rgb24ToY_c / rgb24ToUV_c or rgb24ToUV_half_c and their bgr24 forms, input.c:539-623) and no other;
+         * which chroma converter runs is the context's chrSrcHSubSample (utils.c:1023-1038), handed over as it is.  No special converter of
+         * these sources is taken (bgr24ToYv12Wrapper, rgbToRgbWrapper, the copy) */
+        s->depth = 8; s->hsub = c->chrSrcHSubSample; s->vsub = 0;
+        memcpy(s->dither, ff_dither_8x8_128, sizeof(s->dither));
+        if (special || c->chrSrcVSubSample != 0 || (c->chrSrcHSubSample & ~1) || (c->flags & SWS_FULL_CHR_H_INT)) return -1;
+        if (!c->lumToYV12 || !c->chrToYV12 || c->readLumPlanar || c->readChrPlanar || c->alpToYV12 || c->readAlpPlanar || c->srcBpc != 8) return -1;
+        return generic_dst(c);
+    }
     s->depth = 8; s->hsub = 1; s->vsub = 1;
     memcpy(s->dither, ff_dither_8x8_128, sizeof(s->dither));
     if (c->chrSrcHSubSample != 1 || c->chrSrcVSubSample != 1 || (c->flags & SWS_FULL_CHR_H_INT)) return -1;
@@ -245,10 +261,12 @@ static int fmt_format(const SwsContext *c, mi355_sws_src *s, int special, int *l
 int mi355_sws_describe_fmt(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *src_layout, int *dst_format)
 {
     int special = 0;
-    if (c->srcFormat != AV_PIX_FMT_NV12 && c->srcFormat != AV_PIX_FMT_NV21) {
+    const int rgb = c->srcFormat == AV_PIX_FMT_RGB24 || c->srcFormat == AV_PIX_FMT_BGR24;
+    if (c->srcFormat != AV_PIX_FMT_NV12 && c->srcFormat != AV_PIX_FMT_NV21 && !rgb) {
         *src_layout = MI355_SWS_SRC_PLANAR;
         return mi355_sws_describe_src(c, d, s, dst_format);
     }
+    if (rgb && !c->vLumFilter) return -1;                        /* an unscaled converter or a copy: the reference's */
     if (!c->vLumFilter) {
         if (c->dstFormat != AV_PIX_FMT_YUV420P || c->srcW != c->dstW || c->srcH != c->dstH) return -1;
         special = 1;
@@ -331,6 +349,25 @@ static void t1_nv12cX(SwsContext *c, const int16_t *chrFilter, int chrFilterSize
     mi355_sws_yuv2nv12cX(chrFilter, chrFilterSize, chrUSrc, chrVSrc, dest, chrDstW, c->chrDither8, c->dstFormat == AV_PIX_FMT_NV21);
 }
 
+/* the input converters of a packed rgb24 / bgr24 source (c->lumToYV12 / c->chrToYV12): their argument lists carry no context, so one shim per
+ * byte order and chroma converter */
+static void t1_rgb24ToY(uint8_t *dst, const uint8_t *src, int width, uint32_t *pal) { (void)pal; n_calls++; mi355_sws_rgb24ToY(dst, src, width, 0); }
+static void t1_bgr24ToY(uint8_t *dst, const uint8_t *src, int width, uint32_t *pal) { (void)pal; n_calls++; mi355_sws_rgb24ToY(dst, src, width, 1); }
+#define T1_TOUV(name, bgr, half) \
+static void name(uint8_t *dstU, uint8_t *dstV, const uint8_t *src1, const uint8_t *src2, int width, uint32_t *pal) \
+{ (void)src2; (void)pal; n_calls++; mi355_sws_rgb24ToUV(dstU, dstV, src1, width, bgr, half); }
+T1_TOUV(t1_rgb24ToUV, 0, 0)
+T1_TOUV(t1_rgb24ToUV_half, 0, 1)
+T1_TOUV(t1_bgr24ToUV, 1, 0)
+T1_TOUV(t1_bgr24ToUV_half, 1, 1)
+static void rgb_converters(SwsContext *c, int layout)
+{
+    const int bgr = layout == MI355_SWS_SRC_BGR24;
+    if (layout != MI355_SWS_SRC_RGB24 && !bgr) return;
+    c->lumToYV12 = bgr ? t1_bgr24ToY : t1_rgb24ToY;
+    c->chrToYV12 = c->chrSrcHSubSample ? (bgr ? t1_bgr24ToUV_half : t1_rgb24ToUV_half) : (bgr ? t1_bgr24ToUV : t1_rgb24ToUV);
+}
+
 void ff_sws_init_mi355x(SwsContext *c)
 {
     mi355_sws_src s;
@@ -338,6 +375,7 @@ void ff_sws_init_mi355x(SwsContext *c)
     const int fmt = fmt_format(c, &s, 0, &layout);      /* (an NV12 / NV21 source: c->chrToYV12 stays the reference's) */
     if (fmt > 0) {
         if (!device_ready() || !c->hyScale || !c->hcScale || !c->yuv2planeX || !c->yuv2plane1) return;
+        rgb_converters(c, layout);
         c->hyScale = c->hcScale = s.depth > 8 ? t1_hscale16 : t1_hscale;
         c->yuv2planeX = t1_planeX;
         c->yuv2plane1 = t1_plane1;
@@ -352,6 +390,7 @@ void ff_sws_init_mi355x(SwsContext *c)
      * uses another template) */
     if (!c->hyScale || !c->hcScale || !c->yuv2packedX || !c->yuv2packed2 || !c->yuv2packed1) return;
     c->hyScale = c->hcScale = s.depth > 8 ? t1_hscale16 : t1_hscale;
+    if (fmt == 0) rgb_converters(c, layout);
     c->yuv2packedX = t1_packedX;
     c->yuv2packed2 = t1_packed2;
     c->yuv2packed1 = t1_packed1;
@@ -447,9 +486,10 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
                           (b->other ? fmt_format(c, &s_now, 0, &l_now) : planar_format(c)) == b->planar;
     /* an rgb24 context of another source: range conversion set since it was bound is the reference's for that picture, as above */
     const int other_ok = !b || !b->other || b->planar || fmt_format(c, &s_now, b->special, &l_now) == 0;
-    /* an NV12 / NV21 source has two planes: srcStride[2] is not looked at */
+    /* an NV12 / NV21 source has two planes: srcStride[2] is not looked at; a packed rgb24 / bgr24 source has one */
+    const int one_plane = b && (b->layout == MI355_SWS_SRC_RGB24 || b->layout == MI355_SWS_SRC_BGR24);
     if (b && !b->failed && srcSliceY == 0 && srcSliceH == c->srcH &&
-        srcStride[0] > 0 && srcStride[1] > 0 && (b->layout || srcStride[2] > 0) && dstStride[0] > 0 && (!b->planar || planar_ok) && other_ok) {
+        srcStride[0] > 0 && (one_plane || srcStride[1] > 0) && (b->layout || srcStride[2] > 0) && dstStride[0] > 0 && (!b->planar || planar_ok) && other_ok) {
         if (b->dev && !b->busy && !b->planar && (memcmp(b->y_table, c->yuvTable, 1024) || b->gv0 != c->table_gV[0])) { mi355_sws_destroy(b->dev); b->dev = NULL; }
         if (!b->dev) {
             mi355_sws_desc d;

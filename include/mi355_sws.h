@@ -3,7 +3,8 @@
  * horizontal 8->15 bit FIR, vertical FIR to planar 8 bit or through the yuv->rgb LUTs to RGB24,
  * and the unscaled yuv420p -> rgb24 converter; whole pictures to RGB24, to planar yuv420p / yuv422p / yuv444p or to semi-planar
  * NV12 / NV21 (yuv2nv12cX, and the unscaled yuv420p -> NV12 / NV21 packer); from planar sources or from NV12 / NV21 (the reference's
- * nv12ToUV_c / nv21ToUV_c in front of hcScale, and the unscaled NV12 / NV21 -> yuv420p splitter).
+ * nv12ToUV_c / nv21ToUV_c in front of hcScale, and the unscaled NV12 / NV21 -> yuv420p splitter) or from packed rgb24 / bgr24 (the
+ * reference's rgb24ToY_c / rgb24ToUV_c / rgb24ToUV_half_c and their bgr24 forms in front of hyScale / hcScale).
  *
  * The reference keeps these behind function pointers of the (private) SwsContext
  * (libswscale/swscale_internal.h:253-540): hyScale/hcScale :526-531, yuv2plane1/yuv2planeX/
@@ -184,6 +185,24 @@ enum { MI355_SWS_SRC_PLANAR = 0, MI355_SWS_SRC_NV12 = 1, MI355_SWS_SRC_NV21 = 2 
 mi355_sws_ctx *mi355_sws_create_src_layout(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format);
 int mi355_sws_source_layout(const mi355_sws_ctx *ctx);   /* MI355_SWS_SRC_*, -1 bad argument */
 
+/* ---- packed sources: rgb24 / bgr24 (rgb24ToY_c / bgr24ToY_c and the ...ToUV_c / ...ToUV_half_c pairs, input.c:539-623, in front of
+ * hyScale / hcScale) ----
+ * layout 4 / 5 of mi355_sws_create_src_layout (3 stays refused): ONE source plane of srcW pixels, three bytes each (R G B, bgr24: B G R), which
+ * the reference converts line by line into 8-bit Y, U and V lines with fixed BT.601 constants and then scales like an 8-bit planar source.  The
+ * source record says which chroma converter the reference chose (utils.c:1023-1038, carried as it is, not second-guessed): src->hsub 1 — the
+ * halving one (each chroma sample from the sum of two neighbouring pixels, chrSrcW = AV_CEIL_RSHIFT(srcW, 1)), src->hsub 0 — the full one
+ * (chrSrcW = srcW); src->depth must be 8, src->vsub 0 and desc->chrSrcH == desc->srcH (anything else: NULL and a message).  dst_format takes
+ * every value mi355_sws_create_src takes.  These sources have no special converter here: desc->unscaled_special = 1 is refused with a message
+ * (bgr24ToYv12Wrapper, rgbToRgbWrapper and the plain copy stay with the reference), and so is a context that scales neither way to rgb24
+ * (the reference never builds one).  mi355_sws_plan reports GENERIC_A .. C / PLANAR_A .. C as for the planar source of the same banks.
+ * Frames stay mi355_sws_frame / mi355_sws_planar_frame through the four scale entry points: src[0] is the packed plane, 3 * srcW bytes a row;
+ * src[1], src[2] and their strides are never read and may be NULL / 0.  A packed plane whose pointer and stride are multiples of 4 is fetched in
+ * dwords that lie whole inside the bytes of the line named here; any other plane is read byte by byte.  No byte past them is read:
+ * a line is read over 3 * srcW bytes — and, with hsub == 1 and an ODD srcW, over 3 * (srcW + 1) bytes, as the reference reads it (its last
+ * chroma sample takes pixel srcW, whatever lies there: the next line's first pixel, padding, or the bytes behind the picture).  The caller keeps
+ * those three bytes readable on the last line too.  The Tier-1 host entry points return -1 when src_stride[0] < 3 * srcW. */
+enum { MI355_SWS_SRC_RGB24 = 4, MI355_SWS_SRC_BGR24 = 5 };
+
 /* ---- the individual inner loops (Tier 1, host pointers), argument lists of the reference's
  * function-pointer types minus the SwsContext ------------------------------------------------ */
 /* hScale8To15_c swscale.c:133-147 (c->hyScale / c->hcScale) */
@@ -192,6 +211,11 @@ void mi355_sws_hscale8to15(int16_t *dst, int dstW, const uint8_t *src, const int
 /* hScale16To15_c swscale.c:110-130: uint16_t samples below 1 << depth (9 ... 15), the shift behind the sum is depth - 1 */
 void mi355_sws_hscale16to15(int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter,
                             const int32_t *filterPos, int filterSize, int depth);
+/* rgb24ToY_c / bgr24ToY_c input.c:539-593 (c->lumToYV12): `width` samples from 3 * width bytes; bgr: the pixels are B G R */
+void mi355_sws_rgb24ToY(uint8_t *dst, const uint8_t *src, int width, int bgr);
+/* rgb24ToUV_c / bgr24ToUV_c and their _half forms input.c:552-623 (c->chrToYV12): `width` OUTPUT samples of each plane; half 0 reads
+ * 3 * width bytes, half 1 (each sample from the sum of two neighbouring pixels) 6 * width */
+void mi355_sws_rgb24ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int width, int bgr, int half);
 /* yuv2planeX_8_c output.c:242-255, yuv2plane1_8_c :257-266 */
 void mi355_sws_yuv2planeX_8(const int16_t *filter, int filterSize, const int16_t **src, uint8_t *dest, int dstW,
                             const uint8_t *dither, int offset);

@@ -1,6 +1,6 @@
 /*
  * sws.hip — the libswscale part of the path: planar yuv 4:2:0 / 4:2:2 / 4:4:4 sources at 8, 9 or 10 bits (16-bit
- * little-endian samples above 8: hScale16To15_c swscale.c:110-130 in place of hScale8To15_c) and 8-bit NV12 / NV21 sources -> rgb24,
+ * little-endian samples above 8: hScale16To15_c swscale.c:110-130 in place of hScale8To15_c), 8-bit NV12 / NV21 and packed rgb24 / bgr24 sources -> rgb24,
  * -> 8-bit yuv420p / yuv422p / yuv444p and -> NV12 / NV21 (dithered from a deeper source, swscale.c:553-556), the unscaled 8-bit
  * yuv420p -> NV12 / NV21 packer and the unscaled NV12 / NV21 -> yuv420p splitter.  This file:
  * the context, the plan (which kernel a context gets) and the entry points of include/mi355_sws.h.  The device side is sws_dev.h:
@@ -115,6 +115,12 @@ static bool ctx_source(mi355_sws_ctx *c, const mi355_sws_src *src)
     if (src->depth > 8) std::memcpy(h.dither, src->dither, sizeof(h.dither));
     return true;
 }
+static bool packed_rgb(const SwsDev &h) { return h.src_layout == MI355_SWS_SRC_RGB24 || h.src_layout == MI355_SWS_SRC_BGR24; }
+/* a context that does not scale, to rgb24: what k_sws_ident1 takes */
+static bool ident1_shape(const SwsDev &h)
+{
+    return h.depth == 8 && h.hident_l && h.hident_c && h.vls == 1 && h.vcs <= 4 && !(h.dstW & 1) && h.srcW >= h.dstW && 2 * h.chrSrcW >= h.dstW;
+}
 /* the tile kernels stage a plane's source spans when the context allows it (hstage), the plane's filter is not the identity and a tile's span
  * fits the staged line (hscale_tile; planes and strides that are multiples of 16: the longest aligned start) */
 static void ctx_hfit(mi355_sws_ctx *c, const mi355_sws_desc *desc)
@@ -138,6 +144,17 @@ static void ctx_hfit(mi355_sws_ctx *c, const mi355_sws_desc *desc)
         }
         return false;
     };
+    /* a packed RGB plane: the span in converted samples from a multiple of four, both planes (hscale_tile_rgb) */
+    auto fits_rgb = [&](const mi355_sws_filter &f, int ident, int cols) {
+        if (ident || !f.pos) return false;
+        for (int g = 0; g < f.n; g += cols) {
+            const int last = (g + cols < f.n ? g + cols : f.n) - 1, s0 = f.pos[g], s1 = f.pos[last] + f.size;
+            if (span_fits(span_dwords(s0 & ~3, s1), s0, s1, stage_pitch(cols, 1))) return true;
+        }
+        return false;
+    };
+    if (packed_rgb(h)) c->hfit = fits_rgb(desc->hLum, h.hident_l, TW) || fits_rgb(desc->hChr, h.hident_c, cw);
+    else
     c->hfit = fits(desc->hLum, h.hident_l, TW) || (h.src_layout ? fits_nv(desc->hChr, h.hident_c, cw) : fits(desc->hChr, h.hident_c, cw));
 }
 static void upload_banks(mi355_sws_ctx *c, const mi355_sws_desc *desc)
@@ -175,6 +192,21 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
         delete c;
         return nullptr;
     }
+    if (layout == MI355_SWS_SRC_RGB24 || layout == MI355_SWS_SRC_BGR24) {
+        /* packed RGB: 8 bit, chroma on every line, the full or the halving converter (ctx_source has checked chrSrcW / chrSrcH against the shifts);
+         * no special converter */
+        if (h.depth != 8 || h.src_vsub) {
+            std::fprintf(stderr, "mi355dsp: %s: an rgb24 / bgr24 source is 8 bit with chroma on every line (%d bit, shifts %d/%d)\n", who, h.depth, h.src_hsub, h.src_vsub);
+            delete c;
+            return nullptr;
+        }
+        h.src_layout = layout;
+        if (h.special) {
+            std::fprintf(stderr, "mi355dsp: %s: no unscaled special converter takes an rgb24 / bgr24 source here\n", who);
+            delete c;
+            return nullptr;
+        }
+    } else
     if (layout) {
         /* NV12 / NV21: 8-bit 4:2:0; the only special context is the splitter (nv12ToPlanarWrapper: to yuv420p at equal size, no banks) */
         if (h.depth != 8 || !h.src_hsub || !h.src_vsub) {
@@ -228,6 +260,12 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
         return nullptr;
     }
     h.lum_lines = lines[0]; h.chr_lines = lines[1];
+    if (packed_rgb(h) && !planar && ident1_shape(h)) {
+        /* rgb in, rgb out, nothing scaled: the reference never runs its scaler on that (a copy, or rgbToRgbWrapper) */
+        std::fprintf(stderr, "mi355dsp: %s: an rgb24 / bgr24 source to rgb24 without scaling is not a context of the scaler\n", who);
+        delete c;
+        return nullptr;
+    }
     upload_banks(c, desc);
     return ctx_upload(c);
 }
@@ -251,8 +289,8 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src_layout(const mi355_sws_desc *desc
 {
     if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout without mi355_init(); no CPU fallback\n"); std::abort(); }
     if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout: no descriptor\n"); return nullptr; }
-    if (src_layout < MI355_SWS_SRC_PLANAR || src_layout > MI355_SWS_SRC_NV21) {
-        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout: source layout %d is not planar / nv12 / nv21\n", src_layout);
+    if (src_layout < MI355_SWS_SRC_PLANAR || src_layout > MI355_SWS_SRC_BGR24 || src_layout == 3) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24\n", src_layout);
         return nullptr;
     }
     return ctx_create(desc, src, dst_format != 0, dst_format, "mi355_sws_create_src_layout", src_layout);
@@ -287,7 +325,7 @@ static int sws_kernel(const SwsDev &h)
     if (h.special) return MI355_SWS_K_C24;
     /* a context that does not scale: straight from the source bytes (k_sws_ident1; MI355_SWS_NO_IDENT1=1, developer switch: through the tile all the same) */
     static const bool no_ident1 = std::getenv("MI355_SWS_NO_IDENT1") != nullptr;
-    if (!no_ident1 && h.depth == 8 && h.hident_l && h.hident_c && h.vls == 1 && h.vcs <= 4 && !(h.dstW & 1) && h.srcW >= h.dstW && 2 * h.chrSrcW >= h.dstW)
+    if (!no_ident1 && ident1_shape(h) && !packed_rgb(h))
         return h.vcs <= 2 ? MI355_SWS_K_IDENT1_1 : MI355_SWS_K_IDENT1_X;      /* packed_mode() 1 / the X template */
     return MI355_SWS_K_GENERIC_A + instance(GENERIC_SHAPES);
 }
@@ -392,6 +430,32 @@ static void launch_planar_nv(int i, int form, dim3 grid, hipStream_t s, const Sw
     else if (i == 1) launch_planar_nv<1>(form, grid, s, d, frames);
     else launch_planar_nv<2>(form, grid, s, d, frames);
 }
+/* ... of a packed rgb24 / bgr24 source (8 bit): the RGB instances — the converted samples are staged in the 8-bit instances' staging lines, the same
+ * LDS and waves per SIMD again */
+template <int I> static void launch_generic_rgb(dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
+{
+    constexpr SwsShape S = GENERIC_SHAPES[I];
+    hipLaunchKernelGGL((k_sws_generic<S.lcap, S.ccap, sws_waves(sws_lds_bytes(S.lcap, S.ccap, STAGE_BYTES)), uint8_t, false, true>), grid, dim3(NT), 0, s, d, frames);
+}
+static void launch_generic_rgb(int i, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
+{
+    if (i == 0) launch_generic_rgb<0>(grid, s, d, frames);
+    else if (i == 1) launch_generic_rgb<1>(grid, s, d, frames);
+    else launch_generic_rgb<2>(grid, s, d, frames);
+}
+template <int I> static void launch_planar_rgb(int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+{
+    constexpr SwsShape S = PLANAR_SHAPES[I];
+    if (form == 0) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, uint8_t, false, false, true>), grid, dim3(NT), 0, s, d, frames);
+    else if (form == 1) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW, uint8_t, false, false, true>), grid, dim3(NT), 0, s, d, frames);
+    else hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, uint8_t, true, false, true>), grid, dim3(NT), 0, s, d, frames);
+}
+static void launch_planar_rgb(int i, int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+{
+    if (i == 0) launch_planar_rgb<0>(form, grid, s, d, frames);
+    else if (i == 1) launch_planar_rgb<1>(form, grid, s, d, frames);
+    else launch_planar_rgb<2>(form, grid, s, d, frames);
+}
 /* workgroups per CU of the instances (8-bit, then 16-bit: their staging lines are STAGE_BYTES16); the NV instances stage the pair plane in the
  * 8-bit instances' staging lines (StageGeom<TW>) and hold the same tiles: the 8-bit rows below are theirs too */
 static_assert(StageGeom<TW>::PITCH * StageGeom<TW>::LINES * 4 == STAGE_BYTES, "the pair plane's rounds fill the 8-bit staging storage");
@@ -424,7 +488,8 @@ extern "C" int mi355_sws_scale_frames_dev(mi355_sws_ctx *c, const mi355_sws_fram
         else hipLaunchKernelGGL(k_sws_ident1<true>, grid, dim3(NT), 0, s, c->d, d_frames);
     } else {
         const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
-        if (h.src_layout) launch_generic_nv(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
+        if (packed_rgb(h)) launch_generic_rgb(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
+        else if (h.src_layout) launch_generic_nv(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
         else if (h.depth > 8) launch_generic<uint16_t>(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
         else launch_generic<uint8_t>(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
     }
@@ -450,7 +515,8 @@ extern "C" int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *c, const mi355_s
     }
     const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
     const int i = k - MI355_SWS_K_PLANAR_A;
-    if (h.src_layout) launch_planar_nv(i, semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
+    if (packed_rgb(h)) launch_planar_rgb(i, semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
+    else if (h.src_layout) launch_planar_nv(i, semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
     else if (semi_planar(h)) {
         if (h.depth > 8) launch_semi<uint16_t>(i, grid, s, c->d, d_frames);
         else launch_semi<uint8_t>(i, grid, s, c->d, d_frames);
@@ -478,12 +544,16 @@ static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int
     const bool planar = h.planar != 0;
     const int B = h.depth > 8 ? 2 : 1;                                  /* bytes per source sample */
     /* an NV12 / NV21 source: two planes, the second one 2 * chrSrcW bytes of pairs; src[2] is not touched */
-    const int nsrc = h.src_layout ? 2 : 3;
-    const int w[3] = { h.srcW * B, h.src_layout ? 2 * h.chrSrcW : h.chrSrcW * B, h.src_layout ? 0 : h.chrSrcW * B }, ph[3] = { h.srcH, h.chrSrcH, h.chrSrcH };
+    /* a packed rgb24 / bgr24 source: one plane of 3 * srcW bytes a row; the halving converter of an odd width also reads pixel srcW, the three
+     * bytes behind each row as they lie in the caller's picture (a second copy: they may belong to the next row) */
+    const bool rgb = packed_rgb(h);
+    const int nsrc = rgb ? 1 : (h.src_layout ? 2 : 3), tail = rgb && h.src_hsub && (h.srcW & 1) ? 3 : 0;
+    const int w[3] = { rgb ? 3 * h.srcW : h.srcW * B, rgb ? 0 : (h.src_layout ? 2 * h.chrSrcW : h.chrSrcW * B), h.src_layout ? 0 : h.chrSrcW * B },
+              ph[3] = { h.srcH, h.chrSrcH, h.chrSrcH };
     for (int p = 0; p < nsrc; p++) if (!src[p] || src_stride[p] < w[p]) return -1;
     for (int p = 0; p < ndst; p++) if (!dst[p] || dst_stride[p] < back[p]) return -1;
     DeviceScope on(c->device);
-    const int pw[3] = { (w[0] + 15) & ~15, (w[1] + 15) & ~15, (w[2] + 15) & ~15 };
+    const int pw[3] = { (w[0] + tail + 15) & ~15, (w[1] + 15) & ~15, (w[2] + 15) & ~15 };
     int dp[3] = {};
     size_t doff[4] = {};
     for (int p = 0; p < ndst; p++) { dp[p] = (ow[p] + 15) & ~15; doff[p + 1] = doff[p] + (size_t)dp[p] * oh[p]; }
@@ -519,6 +589,7 @@ static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int
     }
     for (int p = 0; p < nsrc; p++)
         if (!plane_h2d(c->d_src[p], pw[p], src[p], src_stride[p], w[p], ph[p], c->stream)) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4; }
+    if (tail && !plane_h2d(c->d_src[0] + w[0], pw[0], src[0] + w[0], src_stride[0], tail, ph[0], c->stream)) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4; }
     if ((planar ? mi355_sws_scale_planar_frames_dev(c, c->d_pframe, 1, c->stream) : mi355_sws_scale_frames_dev(c, c->d_frame, 1, c->stream)) != 0) {
         (void)hipStreamSynchronize(c->stream);
         return -2;
@@ -591,6 +662,35 @@ extern "C" void mi355_sws_hscale8to15(int16_t *dst, int dstW, const uint8_t *src
 extern "C" void mi355_sws_hscale16to15(int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize, int depth)
 {
     hscale_line<uint16_t>(dst, dstW, src, filter, filterPos, filterSize, depth - 1);
+}
+
+/* rgb24ToY_c / bgr24ToY_c and the ...ToUV_c / ...ToUV_half_c pairs (input.c:539-623) of one line */
+extern "C" void mi355_sws_rgb24ToY(uint8_t *dst, const uint8_t *src, int width, int bgr)
+{
+    if (width <= 0) return;
+    Arena &a = arena();
+    const size_t nsrc = (size_t)3 * width;
+    a.reserve(nsrc + (size_t)width + 64);
+    const size_t o_src = a.take(nsrc), o_d = a.take((size_t)width);
+    std::memcpy(a.h<uint8_t>(o_src), src, nsrc);
+    a.upload();
+    launch_line(k_sws_line_rgb24_y, a, a.d<uint8_t>(o_d), a.d<const uint8_t>(o_src), width, bgr);
+    a.download();
+    std::memcpy(dst, a.h<uint8_t>(o_d), (size_t)width);
+}
+extern "C" void mi355_sws_rgb24ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int width, int bgr, int half)
+{
+    if (width <= 0) return;
+    Arena &a = arena();
+    const size_t nsrc = (size_t)(half ? 6 : 3) * width;
+    a.reserve(nsrc + (size_t)2 * width + 96);
+    const size_t o_src = a.take(nsrc), o_u = a.take((size_t)width), o_v = a.take((size_t)width);
+    std::memcpy(a.h<uint8_t>(o_src), src, nsrc);
+    a.upload();
+    launch_line(k_sws_line_rgb24_uv, a, a.d<uint8_t>(o_u), a.d<uint8_t>(o_v), a.d<const uint8_t>(o_src), width, bgr, half);
+    a.download();
+    std::memcpy(dstU, a.h<uint8_t>(o_u), (size_t)width);
+    std::memcpy(dstV, a.h<uint8_t>(o_v), (size_t)width);
 }
 
 static size_t pack_rows(Arena &a, const int16_t **rows, int n, int elems, int pitch)

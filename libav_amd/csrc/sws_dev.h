@@ -15,7 +15,8 @@
  *   k_sws_ident1    the generic scaler on an 8-bit context that does not scale, from the source bytes.
  * The tile kernels are instantiated per sample type: the uint16_t instances differ in the horizontal pass (its staging lines are twice
  * as long, so is their LDS) and, for planar destinations, in the dither rows.  The NV instances of the tile kernels and of k_sws_ident1 read
- * an NV12 / NV21 source: both chroma planes from one pass over its plane of byte pairs (hscale_tile_nv).
+ * an NV12 / NV21 source: both chroma planes from one pass over its plane of byte pairs (hscale_tile_nv).  The RGB instances of the tile kernels
+ * read a packed rgb24 / bgr24 source: the reference's input converters in front of the 8-bit horizontal pass (hscale_tile_rgb).
  *   k_sws_line_*    the individual inner loops for the Tier-1 entry points.
  * Execution model: 256-thread workgroups (4 waves) sharing one LDS tile; integer only, no MFMA.
  */
@@ -681,6 +682,229 @@ __device__ __forceinline__ void hscale_tile_nv(int16_t (*out_a)[OP], int16_t (*o
     }
 }
 
+/* ---- a packed rgb24 / bgr24 source: the input converters in front of the 8-bit horizontal pass --------------------------------------------
+ * The reference converts each source line into 8-bit lines of its formatConvBuffer (rgb24ToY_c / bgr24ToY_c, the ...ToUV_c and ...ToUV_half_c
+ * pairs, input.c:539-623, fixed BT.601 constants :38-47) and runs hyScale / hcScale on those bytes (swscale.c:252-334).  Here a staging round
+ * makes those bytes in the staged LDS lines (StageGeom as it is: the staged line holds what formatConvBuffer holds), and hscale_lines8 /
+ * hscale_lines consume them unchanged; the identity form is converted sample << 7, the direct form converts the samples a column needs as it goes.
+ * Luma (NP 1) and both chroma planes (NP 2: U and V from ONE pass over the pixels, each taking half of the staged lines of a round) read the
+ * same plane.  A pixel is three bytes c0 c1 c2 (rgb24: R G B, bgr24: B G R): sample = (K0 c0 + K1 c1 + K2 c2 + rnd) >> sh, the halving chroma
+ * converter over the sums of two neighbouring pixels with one more bit of rounding and shift.  The byte order only swaps which constant meets
+ * c0 and c2.  Results lie in 16 .. 240 by the constants' sums: no clip, as the reference has none. */
+constexpr int RGB_SH = 15;
+constexpr int RGB_RY = (int)(0.299 * 219 / 255 * (1 << RGB_SH) + 0.5), RGB_GY = (int)(0.587 * 219 / 255 * (1 << RGB_SH) + 0.5), RGB_BY = (int)(0.114 * 219 / 255 * (1 << RGB_SH) + 0.5);
+constexpr int RGB_RU = -(int)(0.169 * 224 / 255 * (1 << RGB_SH) + 0.5), RGB_GU = -(int)(0.331 * 224 / 255 * (1 << RGB_SH) + 0.5), RGB_BU = (int)(0.500 * 224 / 255 * (1 << RGB_SH) + 0.5);
+constexpr int RGB_RV = (int)(0.500 * 224 / 255 * (1 << RGB_SH) + 0.5), RGB_GV = -(int)(0.419 * 224 / 255 * (1 << RGB_SH) + 0.5), RGB_BV = -(int)(0.081 * 224 / 255 * (1 << RGB_SH) + 0.5);
+static_assert(RGB_GY < 32768 && RGB_BU < 32768, "the constants are 16-bit lanes of the dot product");
+/* the constants of one call: plane a (Y, or U) and plane b (V) as the (K0, K1) pair of the dot product and K2; luma leaves b zero */
+struct RgbK {
+    uint32_t a01, b01;
+    int a2, b2, rnd, sh;
+};
+__device__ __forceinline__ uint32_t rgb_k2(int lo, int hi) { return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16); }
+__device__ __forceinline__ RgbK rgb_consts(bool chroma, bool half, bool bgr)
+{
+    RgbK k;
+    if (!chroma) {
+        k.a01 = rgb_k2(bgr ? RGB_BY : RGB_RY, RGB_GY); k.a2 = bgr ? RGB_RY : RGB_BY;
+        k.b01 = 0; k.b2 = 0;
+        k.rnd = 33 << (RGB_SH - 1); k.sh = RGB_SH;
+    } else {
+        k.a01 = rgb_k2(bgr ? RGB_BU : RGB_RU, RGB_GU); k.a2 = bgr ? RGB_RU : RGB_BU;
+        k.b01 = rgb_k2(bgr ? RGB_BV : RGB_RV, RGB_GV); k.b2 = bgr ? RGB_RV : RGB_BV;
+        k.rnd = half ? 257 << RGB_SH : 257 << (RGB_SH - 1); k.sh = half ? RGB_SH + 1 : RGB_SH;
+    }
+    return k;
+}
+/* any four bytes of two dwords (v_perm_b32: selector bytes 0-3 pick from lo, 4-7 from hi, 0x0C gives zero) */
+#ifdef MI355_HIP_EMU_H
+static inline uint32_t sws_perm(uint32_t hi, uint32_t lo, uint32_t sel)
+{
+    const uint64_t w = ((uint64_t)hi << 32) | lo;
+    uint32_t r = 0;
+    for (int k = 0; k < 4; k++) {
+        const uint32_t s = (sel >> (8 * k)) & 0xFFu;
+        if (s < 8) r |= (uint32_t)((w >> (8 * s)) & 0xFFu) << (8 * k);
+    }
+    return r;
+}
+#else
+__device__ __forceinline__ uint32_t sws_perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
+#endif
+/* four pixels are three dwords: each pixel's (c0, c1) as the two 16-bit lanes of the dot product and its c2 */
+__device__ __forceinline__ void rgb_unpack4(const uint32_t *w, uint32_t *p01, uint32_t *c2)
+{
+    p01[0] = sws_perm(0u, w[0], 0x0C010C00u);   c2[0] = (w[0] >> 16) & 0xFFu;
+    p01[1] = sws_perm(w[1], w[0], 0x0C040C03u); c2[1] = (w[1] >> 8) & 0xFFu;
+    p01[2] = sws_perm(0u, w[1], 0x0C030C02u);   c2[2] = w[2] & 0xFFu;
+    p01[3] = sws_perm(0u, w[2], 0x0C020C01u);   c2[3] = w[2] >> 24;
+}
+/* N dwords at byte `boff` of a line of which `limit` bytes may be read: dword loads where the plane allows it and the piece lies inside,
+ * else byte by byte (bytes at and past the limit read as zero: no tap with a non-zero coefficient meets a sample made of them) */
+template <int N>
+__device__ __forceinline__ void rgb_load(const uint8_t *line, int boff, int limit, bool al4, uint32_t *w)
+{
+    if (al4 && boff + 4 * N <= limit) {
+#pragma unroll
+        for (int k = 0; k < N; k++) w[k] = reinterpret_cast<const uint32_t *>(line + boff)[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+            w[k] = 0;
+            for (int b = 0; b < 4; b++) if (boff + 4 * k + b < limit) w[k] |= (uint32_t)line[boff + 4 * k + b] << (8 * b);
+        }
+    }
+}
+/* converted samples s .. s + 3 of a line (s a multiple of four) as one dword per plane: 12 source bytes, 24 under halving.  The bytes pass
+ * sws_opaque before they are packed, as in planar_rows */
+template <int NP>
+__device__ __forceinline__ void rgb_unit(const uint8_t *line, int s, bool half, bool al4, int limit, const RgbK &k, uint32_t &oa, uint32_t &ob)
+{
+    uint32_t p[4], c[4];
+    if (half) {
+        uint32_t w[6], pa[4], ca[4], pb[4], cb[4];
+        rgb_load<6>(line, 6 * s, limit, al4, w);
+        rgb_unpack4(w, pa, ca); rgb_unpack4(w + 3, pb, cb);
+        /* the sums of two pixels stay inside the 16-bit lanes */
+        p[0] = pa[0] + pa[1]; p[1] = pa[2] + pa[3]; p[2] = pb[0] + pb[1]; p[3] = pb[2] + pb[3];
+        c[0] = ca[0] + ca[1]; c[1] = ca[2] + ca[3]; c[2] = cb[0] + cb[1]; c[3] = cb[2] + cb[3];
+    } else {
+        uint32_t w[3];
+        rgb_load<3>(line, 3 * s, limit, al4, w);
+        rgb_unpack4(w, p, c);
+    }
+    oa = ob = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        oa |= sws_opaque((uint32_t)(sws_dot2(p[q], k.a01, (int)c[q] * k.a2 + k.rnd) >> k.sh)) << (8 * q);
+        if (NP > 1) ob |= sws_opaque((uint32_t)(sws_dot2(p[q], k.b01, (int)c[q] * k.b2 + k.rnd) >> k.sh)) << (8 * q);
+    }
+}
+/* one converted sample from its bytes (the direct form and the Tier-1 line kernels): px the sample's first pixel */
+__device__ __forceinline__ void rgb_sample(const uint8_t *px, bool half, const RgbK &k, int &a, int &b)
+{
+    int c0 = px[0], c1 = px[1], c2 = px[2];
+    if (half) { c0 += px[3]; c1 += px[4]; c2 += px[5]; }
+    a = (c0 * (int16_t)(k.a01 & 0xFFFF) + c1 * (int16_t)(k.a01 >> 16) + c2 * k.a2 + k.rnd) >> k.sh;
+    b = (c0 * (int16_t)(k.b01 & 0xFFFF) + c1 * (int16_t)(k.b01 >> 16) + c2 * k.b2 + k.rnd) >> k.sh;
+}
+/* bytes -> int16 << 7, two per dword (the identity form) */
+__device__ __forceinline__ sws_u32x4 bytes_shl7(uint32_t b0, uint32_t b1)
+{
+    sws_u32x4 o;
+    o[0] = ((b0 & 0xFFu) << 7) | ((b0 & 0xFF00u) << 15);
+    o[1] = ((b0 >> 9) & 0x7F80u) | ((b0 >> 1) & 0x7F800000u);
+    o[2] = ((b1 & 0xFFu) << 7) | ((b1 & 0xFF00u) << 15);
+    o[3] = ((b1 >> 9) & 0x7F80u) | ((b1 >> 1) & 0x7F800000u);
+    return o;
+}
+/* srcW: pixels of a line; nsamp: converted samples of a line (srcW, or chrSrcW); stride in bytes.  half: the halving converter — with an odd
+ * srcW its last sample reads pixel srcW, three bytes past the line's width, as the reference does.  NP 1: luma into out_a; NP 2: U into out_a,
+ * V into out_b.  Planes on 4-byte multiples are fetched in dwords (12 / 24 bytes a unit of four samples, whole inside the bytes the reference
+ * reads), any other byte by byte — the staged form takes either, so a plane's alignment never sends a tile to the direct form.  Identity,
+ * staged and direct forms as hscale_tile's (direct: spans wider than a staged line and non-monotonic banks). */
+template <int COLS, int OP, int NP>
+__device__ __forceinline__ void hscale_tile_rgb(int16_t (*out_a)[OP], int16_t (*out_b)[OP], const uint8_t *src, int stride, int srcW, int nsamp, bool half, bool bgr,
+                                                const int32_t *posT, const int16_t *coefT, int fs, int gx0, int ncols, int lo, int hi,
+                                                uint32_t *stage_mem, int tid, bool zero_tail, bool may_stage, bool identity)
+{
+    constexpr int PITCH = StageGeom<COLS>::PITCH, LR = StageGeom<COLS>::LINES / NP;      /* staged lines of a plane per round */
+    static_assert(StageGeom<COLS>::LINES % NP == 0 && LR >= NT / COLS, "every thread's first line is staged");
+    const RgbK K = rgb_consts(NP > 1, half, bgr);
+    const bool al4 = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 3) == 0;
+    const int limit = 3 * (half ? (srcW + 1) & ~1 : srcW);                               /* bytes of a line the reference reads */
+    if (identity) {
+        /* converted sample << 7.  Eight columns per thread: two units, one 16-byte LDS write per plane */
+        constexpr int TPL = COLS / 8;                  /* threads per line */
+        const int xg = 8 * (tid % TPL), gxi = gx0 + xg;
+        uint32_t keep[2] = { 0, 0 };                   /* the bytes of columns inside the plane */
+        for (int q = 0; q < 8; q++) if (gxi + q < ncols && gxi + q < nsamp) keep[q >> 2] |= 0xFFu << (8 * (q & 3));
+        for (int l = lo + tid / TPL; l <= hi; l += NT / TPL) {
+            const uint8_t *line = src + (size_t)l * stride;
+            uint32_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;
+            if (keep[0]) rgb_unit<NP>(line, gxi, half, al4, limit, K, a0, b0);
+            if (keep[1]) rgb_unit<NP>(line, gxi + 4, half, al4, limit, K, a1, b1);
+            if (zero_tail || gxi < ncols) {
+                *reinterpret_cast<sws_u32x4 *>(&out_a[l - lo][xg]) = bytes_shl7(a0 & keep[0], a1 & keep[1]);
+                if (NP > 1) *reinterpret_cast<sws_u32x4 *>(&out_b[l - lo][xg]) = bytes_shl7(b0 & keep[0], b1 & keep[1]);
+            }
+        }
+        return;
+    }
+    const int x = tid & (COLS - 1), gx = gx0 + x, per = NT / COLS;
+    const bool col_ok = gx < ncols;
+    /* columns past the picture read the last column's entries and do not use them */
+    const int gxc = col_ok ? gx : ncols - 1;
+    const int pos = posT[gxc];
+    const int16_t *f = coefT + (size_t)gxc * fs;
+    const int last = imin(gx0 + COLS, ncols) - 1;
+    /* the tile's span in converted samples, from a multiple of four: whole units */
+    const int s0 = posT[gx0], s1 = posT[last] + fs, a0 = s0 & ~3, nd = span_dwords(a0, s1);
+    uint32_t cp[4];
+    if (fs == 8) {
+        const uint4 w = *reinterpret_cast<const uint4 *>(f);
+        cp[0] = w.x; cp[1] = w.y; cp[2] = w.z; cp[3] = w.w;
+    } else {
+        int t[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) t[j] = f[j < fs ? j : 0];
+#pragma unroll
+        for (int j = 0; j < 4; j++) cp[j] = (2 * j < fs ? (uint32_t)t[2 * j] & 0xFFFFu : 0u) | (2 * j + 1 < fs ? (uint32_t)t[2 * j + 1] << 16 : 0u);
+    }
+    if (!(may_stage && span_fits(nd, s0, s1, PITCH))) {
+        if (col_ok) {
+            const int step = half ? 6 : 3;
+            for (int l = lo + tid / COLS; l <= hi; l += per) {
+                const uint8_t *s = src + (size_t)l * stride + (size_t)step * pos;
+                int a = 0, b = 0;
+                for (int j = 0; j < fs; j++) {
+                    int ya, yb;
+                    rgb_sample(s + step * j, half, K, ya, yb);
+                    a += ya * f[j]; b += yb * f[j];
+                }
+                a >>= 7; b >>= 7;
+                out_a[l - lo][x] = (int16_t)(a < 32767 ? a : 32767);
+                if (NP > 1) out_b[l - lo][x] = (int16_t)(b < 32767 ? b : 32767);
+            }
+        } else if (zero_tail) {
+            for (int l = lo + tid / COLS; l <= hi; l += per) out_a[l - lo][x] = 0;
+        }
+        return;
+    }
+    static_assert(StageGeom<COLS>::LINES * PITCH * PITCH < (1 << 19), "mi355_div20 range");
+    const int inv = mi355_inv20(nd);
+    uint32_t (*stage)[LR][PITCH] = reinterpret_cast<uint32_t (*)[LR][PITCH]>(stage_mem);      /* [plane][line][dword] */
+    for (int base = lo; base <= hi; base += LR) {
+        for (int idx = tid; idx < LR * nd; idx += NT) {
+            const int r = mi355_div20(idx, inv), d = idx - r * nd, line = base + r;
+            if (line > hi) continue;
+            uint32_t oa, ob;
+            rgb_unit<NP>(src + (size_t)line * stride, a0 + 4 * d, half, al4, limit, K, oa, ob);
+            stage[0][r][d] = oa;
+            if (NP > 1) stage[1][r][d] = ob;
+        }
+        __syncthreads();
+        /* the thread's column over the staged lines of each plane, as hscale_tile; a plane's round is LR lines */
+        const int r0 = tid / COLS;
+        const int left = uniform(imin(hi - base, LR - 1) - r0);
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+            const uint8_t *row0 = reinterpret_cast<const uint8_t *>(stage[p][r0]) + (pos - a0);
+            int16_t *out0 = p ? &out_b[base + r0 - lo][x] : &out_a[base + r0 - lo][x];
+            if (col_ok) {
+                if (fs == 1) hscale_lines<COLS, 1, OP>(row0, out0, cp, left);
+                else if (fs <= 2) hscale_lines<COLS, 2, OP>(row0, out0, cp, left);
+                else if (fs <= 4) hscale_lines<COLS, 4, OP>(row0, out0, cp, left);
+                else if (fs <= 8) hscale_lines8<COLS, OP>(row0, out0, cp, left);
+                else hscale_lines<COLS, 0, OP>(row0, out0, cp, left, 7, f, fs);
+            } else if (zero_tail) {
+                for (int k = 0; k < LR / per && k * per <= left; k++) out0[k * per * OP] = 0;
+            }
+        }
+        __syncthreads();
+    }
+}
+
 /* Vertical pass + LUT for the output rows of a tile with the row's filter taps and source-line indices in
  * registers: NL / NC = luma / chroma tap counts rounded up to 1, 2, 4 or 8 (taps past the real size carry a
  * zero coefficient and a valid line index).  A thread owns one output row and every 16th pair of it. */
@@ -919,8 +1143,10 @@ __device__ __forceinline__ void vertical_narrow(const SwsDev *cp, const LutLds *
 /* LCAP / CCAP: a row of GENERIC_SHAPES; WAVES: sws_waves() of the instance's LDS */
 /* ST: the source's sample type; the uint16_t instances (9 / 10 bit sources) differ in the horizontal pass and its staging lines only */
 /* NV: an NV12 / NV21 source (8 bit) — both chroma tiles from ONE pass over fr.src[1], the plane of pairs (hscale_tile_nv); fr.src[2] is not read.
- * The same LDS, so the same workgroups per CU.  The three-plane instances are the NV false ones, unchanged. */
-template <int LCAP, int CCAP, int WAVES, typename ST = uint8_t, bool NV = false>
+ * The same LDS, so the same workgroups per CU.  The three-plane instances are the NV false ones, unchanged.
+ * RGB: a packed rgb24 / bgr24 source (8 bit) — luma and both chroma tiles from fr.src[0] through the input converters (hscale_tile_rgb);
+ * fr.src[1] and fr.src[2] are not read.  The same LDS again. */
+template <int LCAP, int CCAP, int WAVES, typename ST = uint8_t, bool NV = false, bool RGB = false>
 #ifndef MI355_HIP_EMU_H
 __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
 #endif
@@ -948,6 +1174,14 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
     /* horizontal pass: luma (the phantom partner of the last sample of an odd-width picture reads the
      * zero-initialised tail of the reference's line buffer, utils.c:1241-1262), then the chroma planes */
     uint32_t *s_stage = reinterpret_cast<uint32_t *>(s_io);
+    if constexpr (RGB) {
+        static_assert(sizeof(ST) == 1 && !NV, "packed RGB sources are 8 bit");
+        const bool bgr = c.src_layout == MI355_SWS_SRC_BGR24, half = c.src_hsub != 0;
+        hscale_tile_rgb<TW, TW, 1>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.srcW, false, bgr, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi,
+                                   s_stage, tid, true, c.hstage != 0, c.hident_l != 0);
+        hscale_tile_rgb<TW / 2, TW / 2, 2>(s_cu, s_cv, fr.src[0], fr.src_stride[0], c.srcW, c.chrSrcW, half, bgr, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi,
+                                           s_stage, tid, false, c.hstage != 0, c.hident_c != 0);
+    } else {
     hscale_tile<TW, TW, ST>(s_lum, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi, s_stage, tid, true, c.hstage != 0, c.hident_l != 0, c.depth);
     if constexpr (NV) {
         static_assert(sizeof(ST) == 1, "NV12 / NV21 sources are 8 bit");
@@ -957,6 +1191,7 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
     } else {
     hscale_tile<TW / 2, TW / 2, ST>(s_cu, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, c.depth);
     hscale_tile<TW / 2, TW / 2, ST>(s_cv, fr.src[2], fr.src_stride[2], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, c.depth);
+    }
     }
     __syncthreads();
     /* vertical pass + LUT */
@@ -1197,8 +1432,9 @@ __host__ __device__ constexpr int sws_planar_waves(int lum_lines, int chr_lines,
  * vertical pass from LDS straight to the three planes.  LCAP / CCAP: a row of PLANAR_SHAPES.
  * SEMI: an NV12 / NV21 destination (4:2:0, CW = TW / 2) — the chroma rows go to ONE plane of byte pairs, fr.dst[1] (semiplanar_rows);
  * fr.dst[2] is not used.  The three-plane instances are the SEMI false ones, unchanged.
- * NV: an NV12 / NV21 source, as k_sws_generic's — U | V of an LDS line from one pass over fr.src[1]. */
-template <int LCAP, int CCAP, int CW, typename ST = uint8_t, bool SEMI = false, bool NV = false>
+ * NV: an NV12 / NV21 source, as k_sws_generic's — U | V of an LDS line from one pass over fr.src[1].
+ * RGB: a packed rgb24 / bgr24 source, as k_sws_generic's — luma and U | V from fr.src[0]. */
+template <int LCAP, int CCAP, int CW, typename ST = uint8_t, bool SEMI = false, bool NV = false, bool RGB = false>
 #ifndef MI355_HIP_EMU_H
 __attribute__((amdgpu_waves_per_eu(sws_planar_waves(LCAP, CCAP, CW, stage_bytes<ST>()), sws_planar_waves(LCAP, CCAP, CW, stage_bytes<ST>()))))
 #endif
@@ -1217,11 +1453,21 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
     const int ls = c.vls, cs = c.vcs;
     /* source lines the tile needs (swscale.c:459-468 for the first tap, :571-616 for the clamping) */
     const int llo = clampi(imax(1 - ls, c.vLumP[y0]), 0, c.srcH - 1), lhi = clampi(imax(1 - ls, c.vLumP[y1]) + ls - 1, 0, c.srcH - 1);
+    if constexpr (RGB) {
+        static_assert(sizeof(ST) == 1 && !NV, "packed RGB sources are 8 bit");
+        hscale_tile_rgb<TW, TW, 1>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.srcW, false, c.src_layout == MI355_SWS_SRC_BGR24, c.hLumP, c.hLumC, c.hls, x0, c.dstW,
+                                   llo, lhi, s_stage, tid, false, c.hstage != 0, c.hident_l != 0);
+    } else
     hscale_tile<TW, TW, ST>(s_lum, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi, s_stage, tid, false, c.hstage != 0, c.hident_l != 0, c.depth);
     int clo = 0;
     if (cy0 <= cy1) {
         clo = clampi(imax(1 - cs, c.vChrP[cy0]), 0, c.chrSrcH - 1);
         const int chi = clampi(imax(1 - cs, c.vChrP[cy1]) + cs - 1, 0, c.chrSrcH - 1);
+        if constexpr (RGB) {
+            int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
+            hscale_tile_rgb<CW, 2 * CW, 2>(s_u, s_v, fr.src[0], fr.src_stride[0], c.srcW, c.chrSrcW, c.src_hsub != 0, c.src_layout == MI355_SWS_SRC_BGR24, c.hChrP, c.hChrC, c.hcs,
+                                           x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0);
+        } else
         if constexpr (NV) {
             static_assert(sizeof(ST) == 1, "NV12 / NV21 sources are 8 bit");
             int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
@@ -1592,6 +1838,25 @@ template <typename ST = uint8_t>
 __global__ void __launch_bounds__(NT) k_sws_line_hscale(int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *pos, int fs, int sh)
 {
     for (int i = threadIdx.x; i < dstW; i += NT) dst[i] = (int16_t)hscale_one<ST>(src, filter + (size_t)i * fs, pos[i], fs, sh);
+}
+/* rgb24ToY_c / bgr24ToY_c and the ...ToUV_c / ...ToUV_half_c pairs (input.c:539-623) of one line: one sample per thread and step */
+__global__ void __launch_bounds__(NT) k_sws_line_rgb24_y(uint8_t *dst, const uint8_t *src, int width, int bgr)
+{
+    const RgbK K = rgb_consts(false, false, bgr != 0);
+    for (int i = threadIdx.x; i < width; i += NT) {
+        int a, b;
+        rgb_sample(src + 3 * (size_t)i, false, K, a, b);
+        dst[i] = (uint8_t)a;
+    }
+}
+__global__ void __launch_bounds__(NT) k_sws_line_rgb24_uv(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int width, int bgr, int half)
+{
+    const RgbK K = rgb_consts(true, half != 0, bgr != 0);
+    for (int i = threadIdx.x; i < width; i += NT) {
+        int a, b;
+        rgb_sample(src + (half ? 6 : 3) * (size_t)i, half != 0, K, a, b);
+        dstU[i] = (uint8_t)a; dstV[i] = (uint8_t)b;
+    }
 }
 /* yuv2planeX_8_c output.c:242-255 (fs >= 1 rows at `pitch` elements) / yuv2plane1_8_c :257-266 (fs == 0) */
 __global__ void __launch_bounds__(NT) k_sws_line_plane(const int16_t *filter, int fs, const int16_t *rows, int pitch, uint8_t *dest, int dstW,

@@ -34,8 +34,13 @@ def main():
                          "build; this build without it): 2160p -> 1080p rgb24, 1080p -> rgb24 at equal size (ident1_x), 2160p -> 1080p nv12, the "
                          "unscaled splitter beside the packer at 1080p, one twin a second time in another allocation (A/A), and with --other-lib "
                          "the three existing points; 32 and 512 pictures per launch, 3 warm-up + --steps launches a round, alternating, median of 3 rounds")
+    ap.add_argument("--rgbsrc", action="store_true",
+                    help="packed rgb24 sources (mi355_sws_create_src_layout) beside the 8-bit yuv444p twin — the same three bytes a pixel in, the same "
+                         "destination out — on --other-lib (the parent commit's build; this build without it): 2160p -> 1080p yuv420p, nv12 and rgb24, "
+                         "1080p -> yuv420p at equal size, each twin a second time in another allocation (A/A), and with --other-lib the three "
+                         "existing points; 32 and 512 pictures per launch, 3 warm-up + --steps launches a round, alternating, median of 3 rounds")
     ap.add_argument("--other-lib", default=None,
-                    help="--nv12 / --nvsrc: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
+                    help="--nv12 / --nvsrc / --rgbsrc: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
     ap.add_argument("--rounds", type=int, default=5, help="--planar / --sources: alternating rounds (the median is reported)")
     a = ap.parse_args()
     prov = providers.mi355()
@@ -50,6 +55,8 @@ def main():
         return nv12(a, lib)
     if a.nvsrc:
         return nvsrc(a, lib)
+    if a.rgbsrc:
+        return rgbsrc(a, lib)
     orc = S.oracle_backend(providers.oracle())
     for name in a.configs.split(","):
         ctx = S.load_context(name)
@@ -427,6 +434,94 @@ def nvsrc(a, lib):
                        "twin#2@" + twin_tag: (twin_lib, batch(twin_lib, t, tpics, frames, X.create))}
             plan = V.plan_of(lib, batches["nv12_source@this"][1].handle)
             extra = {"nv12_source@this": {"kernel": plan["kernel"], "hstaged": plan["hstaged"]}}
+            nbytes = {k: b.src_bytes + b.dst_bytes for k, (l, b) in batches.items()}
+            times = {k: [] for k in batches}
+            for _ in range(rounds):
+                for k, (l, b) in batches.items():
+                    times[k].append(time_ms(l, b.run, a.steps))
+            for k in batches:
+                ms = statistics.median(times[k])
+                us = ms * 1e3 / frames
+                out = {"workload": point + ":" + k, "frames_per_launch": frames, "ms_per_launch": ms, "us_per_picture": us,
+                       "algorithmic_bytes_per_frame": nbytes[k], "achieved_GBps": nbytes[k] / us * 1e-3, "frac_of_8TBps": nbytes[k] / us * 1e-3 / 8000.0,
+                       "ms_rounds": [round(x, 4) for x in times[k]]}
+                out.update(extra.get(k, {}))
+                print(json.dumps(out), flush=True)
+            for l, b in batches.values():
+                b.close()
+    if "other" in libs:
+        for name in a.configs.split(","):
+            ctx = S.load_context(name)
+            d = ctx.desc
+            pics = [S.picture(name, seed=s) for s in (1, 2)]
+            batches = {tag: (l, S.DeviceBatch(l, ctx, pics, a.frames)) for tag, l in (("parent", libs["other"]), ("this", lib))}
+            nb = d.srcW * d.srcH + 2 * d.chrSrcW * d.chrSrcH + d.dstW * d.dstH * 3
+            times = {k: [] for k in batches}
+            for _ in range(rounds):
+                for k, (l, b) in batches.items():
+                    times[k].append(time_ms(l, b.run, a.steps))
+            for k in batches:
+                ms = statistics.median(times[k])
+                print(json.dumps({"workload": name + ":" + k, "frames_per_launch": a.frames, "ms_per_launch": ms, "algorithmic_bytes_per_frame": nb,
+                                  "ms_rounds": [round(x, 4) for x in times[k]]}), flush=True)
+            for l, b in batches.values():
+                b.close()
+
+
+def rgbsrc(a, lib):
+    """Packed rgb24 sources beside their traffic twins: the 8-bit yuv444p source of the same sizes, destination and flags reads the same three
+    bytes a pixel and writes the same output.  The contexts come from the reference's libswscale at run time (oracle/_ref/libswsref.so:
+    mi355_sws_describe_fmt / mi355_sws_describe_src) — no full-size context is committed.  The twin runs on --other-lib (the parent commit's
+    build) where one is given; `twin#2` is the twin's context a second time with its own buffers: identical code in two allocations, the
+    session's A/A spread.  One process, the batches of a point alternating: 3 warm-up + --steps launches a round, median of 3 rounds, at 32
+    and 512 pictures per launch.  Algorithmic bytes: the source planes read once + the destination planes written once."""
+    import statistics
+    import numpy as np
+    import sws_nv12 as N
+    import sws_planar as P
+    import sws_rgbsrc as R
+    import sws_sources as X
+    libs = {"this": lib}
+    if a.other_lib:
+        other = C.CDLL(os.path.abspath(a.other_lib))
+        other.mi355_init.restype = C.c_int
+        assert other.mi355_init(C.c_int(0)) == 0
+        other.mi355_event_create.restype = C.c_void_p
+        other.mi355_event_elapsed_ms.restype = C.c_float
+        libs["other"] = other
+    twin_tag, twin_lib = ("parent", libs["other"]) if a.other_lib else ("this", lib)
+    ref = R.Ref(P.bind(R.REF_LIB))
+    rounds = 3
+    # (point, srcW, srcH, dstW, dstH, destination)
+    points = [("uhd_to_hd_yuv420p", 3840, 2160, 1920, 1080, "420"), ("uhd_to_hd_nv12", 3840, 2160, 1920, 1080, "nv12"),
+              ("hd_same_yuv420p", 1920, 1080, 1920, 1080, "420"), ("uhd_to_hd_rgb24", 3840, 2160, 1920, 1080, "rgb")]
+
+    def batch(l, e, pics, frames, create):
+        if e.fmt == 0:
+            return SourceBatch(l, X, e, pics, frames, create=create)
+        return PlaneBatch(l, create(l, e), pics, e.out_sizes(), frames)
+
+    for frames in (32, 512):
+        for point, sw, sh, dw, dh, dst in points:
+            flags = ref.lib.ref_sws_flags_word(1, 1, 1)
+            c = ref.open_formats(sw, sh, b"rgb24", dw, dh, R.AV_DST[dst], flags)
+            e = ref.describe(c)
+            ref.free(c)
+            c = ref.open_formats(sw, sh, b"yuv444p", dw, dh, R.AV_DST[dst], flags)
+            t = ref.describe_src(c)
+            ref.free(c)
+            assert e is not None and t is not None, point
+            t = N.Entry.of(t)
+            R.SHAPES["_bench"] = (sw, sh, dw, dh, "rgb24", dst, 1, 1, 1, 0)
+            X.SHAPES["_bench"] = (sw, sh, dw, dh, "444", 8, "rgb", 1, 1, 1)
+            # (the packed pictures keep their spare line: the kernels never read it at an even width)
+            rpics = [R.picture("_bench", seed=s) for s in (1, 2)]
+            tpics = [[np.ascontiguousarray(pl) for pl in X.picture("_bench", seed=s)] for s in (1, 2)]
+            batches = {"rgb24_source@this": (lib, batch(lib, e, rpics, frames, R.create)),
+                       "twin@" + twin_tag: (twin_lib, batch(twin_lib, t, tpics, frames, X.create)),
+                       "twin#2@" + twin_tag: (twin_lib, batch(twin_lib, t, tpics, frames, X.create))}
+            plan = R.plan_of(lib, batches["rgb24_source@this"][1].handle)
+            extra = {"rgb24_source@this": {"kernel": plan["kernel"], "hstaged": plan["hstaged"], "hsub": plan["hsub"]}}
             nbytes = {k: b.src_bytes + b.dst_bytes for k, (l, b) in batches.items()}
             times = {k: [] for k in batches}
             for _ in range(rounds):
