@@ -53,6 +53,12 @@
  *                          above through mi355_sws_describe_fmt() / mi355_sws_create_src_layout(): whole pictures hand over ONE source plane;
  *                          with MI355_SWS_LINES=1 the two converters are forwarded too (mi355_sws_rgb24ToY / mi355_sws_rgb24ToUV).  The
  *                          unscaled converters of these sources (bgr24ToYv12Wrapper, rgbToRgbWrapper, the copy) stay the reference's.
+ *   range conversion       contexts of the generic scaler whose source and destination differ in range, to a YUV destination (yuvj420p <-> yuv420p
+ *                          and their kin: c->lumConvertRange / c->chrConvertRange between the horizontal and the vertical pass) take the same
+ *                          two forms from every source above through mi355_sws_describe_range() / mi355_sws_create_src_layout_range().  The
+ *                          direction is read from the converters the context holds (range_probe), at bind time and again on every call: a
+ *                          mismatch is the reference's function for that picture.  With MI355_SWS_LINES=1 the two converters are forwarded
+ *                          too (mi355_sws_lumConvertRange / mi355_sws_chrConvertRange).  The four describers above keep declining these.
  * The device is MI355_DEVICE (default 0), as for the decoder bridges.
  */
 #include <pthread.h>
@@ -166,21 +172,23 @@ static int source_of(const SwsContext *c, mi355_sws_src *s)
 /* 0: rgb24, MI355_SWS_DST_*: planar or semi-planar, -1: a context this path leaves to the reference.  special: the context's swscale is
  * yuv2rgb_c_24_rgb or, with an NV12 / NV21 destination, planarToNv12Wrapper */
 /* the destination of a context that runs the generic scaler, -1 for one this path leaves to the reference */
-static int generic_dst(const SwsContext *c);
-static int src_format(const SwsContext *c, mi355_sws_src *s, int special)
+/* ranged: the context may hold lumConvertRange / chrConvertRange (mi355_sws_describe_range); the existing describers ask with 0 */
+static int generic_dst_r(const SwsContext *c, int ranged);
+static int src_format_r(const SwsContext *c, mi355_sws_src *s, int special, int ranged)
 {
     if (source_of(c, s) != 0 || (c->flags & SWS_FULL_CHR_H_INT)) return -1;       /* (every destination below is 8 bits) */
     if (c->lumToYV12 || c->chrToYV12 || c->readLumPlanar || c->readChrPlanar || c->alpToYV12 || c->readAlpPlanar) return -1;      /* an input converter */
     if (special && (c->dstFormat == AV_PIX_FMT_NV12 || c->dstFormat == AV_PIX_FMT_NV21))          /* the packer: planarToNv12Wrapper */
         return c->srcFormat == AV_PIX_FMT_YUV420P ? (c->dstFormat == AV_PIX_FMT_NV12 ? MI355_SWS_DST_NV12 : MI355_SWS_DST_NV21) : -1;
     if (special) return c->dstFormat == AV_PIX_FMT_RGB24 && s->depth == 8 && s->hsub == 1 ? 0 : -1;
-    return generic_dst(c);
+    return generic_dst_r(c, ranged);
 }
-static int generic_dst(const SwsContext *c)
+static int src_format(const SwsContext *c, mi355_sws_src *s, int special) { return src_format_r(c, s, special, 0); }
+static int generic_dst_r(const SwsContext *c, int ranged)
 {
-    /* the generic scaler: no fast bilinear, no range conversion, no chroma line drop, and its four banks (an unscaled converter or a
-     * plane copy has none, utils.c:1043-1048) */
-    if (c->hyscale_fast || c->hcscale_fast || c->lumConvertRange || c->chrConvertRange || c->vChrDrop) return -1;
+    /* the generic scaler: no fast bilinear, no range conversion (unless asked for), no chroma line drop, and its four banks (an unscaled
+     * converter or a plane copy has none, utils.c:1043-1048) */
+    if (c->hyscale_fast || c->hcscale_fast || (!ranged && (c->lumConvertRange || c->chrConvertRange)) || c->vChrDrop) return -1;
     if (!c->vLumFilter || !c->vChrFilter || !c->hLumFilter || !c->hChrFilter) return -1;
     switch (c->dstFormat) {
     case AV_PIX_FMT_RGB24:   return 0;
@@ -192,9 +200,9 @@ static int generic_dst(const SwsContext *c)
     default: return -1;
     }
 }
-static int describe_src(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *dst_format, int special)
+static int describe_src_r(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *dst_format, int special, int ranged)
 {
-    const int fmt = src_format(c, s, special);
+    const int fmt = src_format_r(c, s, special, ranged);
     if (fmt < 0) return -1;
     memset(d, 0, sizeof(*d));
     d->srcW = c->srcW; d->srcH = c->srcH; d->dstW = c->dstW; d->dstH = c->dstH;
@@ -210,6 +218,7 @@ static int describe_src(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *
     *dst_format = fmt;
     return 0;
 }
+static int describe_src(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *dst_format, int special) { return describe_src_r(c, d, s, dst_format, special, 0); }
 /* what mi355_sws_create_src takes for a live context (0), -1 for a context this path declines.  A context without the vertical banks whose
  * swscale is the reference's yuv2rgb_c_24_rgb is the unscaled special converter; any other without them (a plane copy) is declined. */
 int mi355_sws_describe_src(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *dst_format)
@@ -230,11 +239,11 @@ int mi355_sws_describe_src(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_sr
 /* ---- NV12 / NV21 sources beside the planar ones ------------------------------------------------------------------------------------------
  * src_format() with the source's layout (MI355_SWS_SRC_*): an NV12 / NV21 source is the one context whose input converter this path takes —
  * c->chrToYV12 alone (nv12ToUV_c / nv21ToUV_c, input.c:475-497) — as an 8-bit 4:2:0 source of the layout.  special: nv12ToPlanarWrapper */
-static int fmt_format(const SwsContext *c, mi355_sws_src *s, int special, int *layout)
+static int fmt_format_r(const SwsContext *c, mi355_sws_src *s, int special, int *layout, int ranged)
 {
     *layout = c->srcFormat == AV_PIX_FMT_NV12 ? MI355_SWS_SRC_NV12 : (c->srcFormat == AV_PIX_FMT_NV21 ? MI355_SWS_SRC_NV21 :
               (c->srcFormat == AV_PIX_FMT_RGB24 ? MI355_SWS_SRC_RGB24 : (c->srcFormat == AV_PIX_FMT_BGR24 ? MI355_SWS_SRC_BGR24 : MI355_SWS_SRC_PLANAR)));
-    if (!*layout) return src_format(c, s, special);
+    if (!*layout) return src_format_r(c, s, special, ranged);
     memset(s, 0, sizeof(*s));
     if (*layout == MI355_SWS_SRC_RGB24 || *layout == MI355_SWS_SRC_BGR24) {
         /* packed RGB: BOTH input converters (rgb24ToY_c / rgb24ToUV_c or rgb24ToUV_half_c and their bgr24 forms, input.c:539-623) and no other;
@@ -244,7 +253,7 @@ static int fmt_format(const SwsContext *c, mi355_sws_src *s, int special, int *l
         memcpy(s->dither, ff_dither_8x8_128, sizeof(s->dither));
         if (special || c->chrSrcVSubSample != 0 || (c->chrSrcHSubSample & ~1) || (c->flags & SWS_FULL_CHR_H_INT)) return -1;
         if (!c->lumToYV12 || !c->chrToYV12 || c->readLumPlanar || c->readChrPlanar || c->alpToYV12 || c->readAlpPlanar || c->srcBpc != 8) return -1;
-        return generic_dst(c);
+        return generic_dst_r(c, ranged);
     }
     s->depth = 8; s->hsub = 1; s->vsub = 1;
     memcpy(s->dither, ff_dither_8x8_128, sizeof(s->dither));
@@ -253,25 +262,26 @@ static int fmt_format(const SwsContext *c, mi355_sws_src *s, int special, int *l
     /* (the unscaled path leaves sws_init_context before srcBpc is set and the input converters are chosen: the splitter's context has neither) */
     if (special) return c->dstFormat == AV_PIX_FMT_YUV420P ? MI355_SWS_DST_YUV420P : -1;
     if (c->srcBpc != 8 || !c->chrToYV12) return -1;
-    return generic_dst(c);
+    return generic_dst_r(c, ranged);
 }
+static int fmt_format(const SwsContext *c, mi355_sws_src *s, int special, int *layout) { return fmt_format_r(c, s, special, layout, 0); }
 /* what mi355_sws_create_src_layout takes for a live context (0), -1 for a context this path declines: mi355_sws_describe_src plus the two
  * NV sources.  An NV context without the vertical banks is the splitter when it goes to yuv420p at equal size (swscale_unscaled.c:1045-1049,
  * whatever the flags); any other without them (nv12 -> nv12: a plane copy) is declined. */
-int mi355_sws_describe_fmt(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *src_layout, int *dst_format)
+static int describe_fmt_r(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *src_layout, int *dst_format, int ranged)
 {
     int special = 0;
     const int rgb = c->srcFormat == AV_PIX_FMT_RGB24 || c->srcFormat == AV_PIX_FMT_BGR24;
     if (c->srcFormat != AV_PIX_FMT_NV12 && c->srcFormat != AV_PIX_FMT_NV21 && !rgb) {
         *src_layout = MI355_SWS_SRC_PLANAR;
-        return mi355_sws_describe_src(c, d, s, dst_format);
+        return ranged ? describe_src_r(c, d, s, dst_format, 0, 1) : mi355_sws_describe_src(c, d, s, dst_format);
     }
     if (rgb && !c->vLumFilter) return -1;                        /* an unscaled converter or a copy: the reference's */
     if (!c->vLumFilter) {
         if (c->dstFormat != AV_PIX_FMT_YUV420P || c->srcW != c->dstW || c->srcH != c->dstH) return -1;
         special = 1;
     }
-    const int fmt = fmt_format(c, s, special, src_layout);
+    const int fmt = fmt_format_r(c, s, special, src_layout, ranged);
     if (fmt < 0) return -1;
     memset(d, 0, sizeof(*d));
     d->srcW = c->srcW; d->srcH = c->srcH; d->dstW = c->dstW; d->dstH = c->dstH;
@@ -286,6 +296,41 @@ int mi355_sws_describe_fmt(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_sr
     if (!fmt) luts_of(c, &d->luts);
     *dst_format = fmt;
     return 0;
+}
+int mi355_sws_describe_fmt(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *src_layout, int *dst_format)
+{
+    return describe_fmt_r(c, d, s, src_layout, dst_format, 0);
+}
+
+/* ---- range conversion: contexts whose only obstacle above is lumConvertRange / chrConvertRange ---------------------------------------------
+ * The MI355_SWS_RANGE_* of the converters the context HOLDS (sws_setColorspaceDetails rewrites c->srcRange after init without touching the
+ * pointers; the functions are static in the reference): one sample of 0 through each — luma 2048 / chroma 1992 from-JPEG, -2384 / -2269
+ * to-JPEG.  0: neither converter; -1: one of the two only, two directions, other functions, or a destination other than 8 bits — NOTHING is
+ * called then: behind the same pointer types a destination of 16 bits holds the ...Jpeg16_c forms (swscale.c:200-236, :757-764), which read and
+ * write an int32_t per sample, four bytes where the probe has two; every destination of this path is 8 bits, so such a context is not ours
+ * whatever its converters are */
+static int range_probe(const SwsContext *c)
+{
+    int16_t y = 0, u = 0, v = 0;
+    if (!c->lumConvertRange && !c->chrConvertRange) return MI355_SWS_RANGE_NONE;
+    if (!c->lumConvertRange || !c->chrConvertRange || c->dstBpc != 8) return -1;
+    c->lumConvertRange(&y, 1);
+    c->chrConvertRange(&u, &v, 1);
+    if (y == 2048 && u == 1992 && v == 1992) return MI355_SWS_RANGE_FROM_JPEG;
+    if (y == -2384 && u == -2269 && v == -2269) return MI355_SWS_RANGE_TO_JPEG;
+    return -1;
+}
+/* what mi355_sws_create_src_layout_range takes for a live context (0), -1 for a context this path declines: mi355_sws_describe_fmt (range 0)
+ * plus the contexts of the generic scaler with a YUV destination that convert the range */
+int mi355_sws_describe_range(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *src_layout, int *dst_format, int *range)
+{
+    const int r = range_probe(c);
+    if (r < 0) return -1;
+    *range = r;
+    if (!r) return mi355_sws_describe_fmt(c, d, s, src_layout, dst_format);
+    /* the reference sets the converters for YUV destinations of its generic scaler only (swscale.c:748, utils.c:1044) */
+    if (!c->vLumFilter || isAnyRGB(c->dstFormat)) return -1;
+    return describe_fmt_r(c, d, s, src_layout, dst_format, 1) == 0 && *dst_format > 0 ? 0 : -1;
 }
 
 #ifndef MI355_SWS_DESCRIBE_ONLY
@@ -368,14 +413,26 @@ static void rgb_converters(SwsContext *c, int layout)
     c->chrToYV12 = c->chrSrcHSubSample ? (bgr ? t1_bgr24ToUV_half : t1_rgb24ToUV_half) : (bgr ? t1_bgr24ToUV : t1_rgb24ToUV);
 }
 
+/* lumConvertRange / chrConvertRange: no context in their argument lists either, one shim per direction */
+static void t1_lumFromJpeg(int16_t *dst, int width) { n_calls++; mi355_sws_lumConvertRange(dst, width, 0); }
+static void t1_lumToJpeg(int16_t *dst, int width) { n_calls++; mi355_sws_lumConvertRange(dst, width, 1); }
+static void t1_chrFromJpeg(int16_t *dstU, int16_t *dstV, int width) { n_calls++; mi355_sws_chrConvertRange(dstU, dstV, width, 0); }
+static void t1_chrToJpeg(int16_t *dstU, int16_t *dstV, int width) { n_calls++; mi355_sws_chrConvertRange(dstU, dstV, width, 1); }
+
 void ff_sws_init_mi355x(SwsContext *c)
 {
     mi355_sws_src s;
     int layout;
-    const int fmt = fmt_format(c, &s, 0, &layout);      /* (an NV12 / NV21 source: c->chrToYV12 stays the reference's) */
+    const int range = range_probe(c);
+    /* (an NV12 / NV21 source: c->chrToYV12 stays the reference's) */
+    const int fmt = range > 0 ? fmt_format_r(c, &s, 0, &layout, 1) : fmt_format(c, &s, 0, &layout);
     if (fmt > 0) {
         if (!device_ready() || !c->hyScale || !c->hcScale || !c->yuv2planeX || !c->yuv2plane1) return;
         rgb_converters(c, layout);
+        if (range > 0) {
+            c->lumConvertRange = range == MI355_SWS_RANGE_TO_JPEG ? t1_lumToJpeg : t1_lumFromJpeg;
+            c->chrConvertRange = range == MI355_SWS_RANGE_TO_JPEG ? t1_chrToJpeg : t1_chrFromJpeg;
+        }
         c->hyScale = c->hcScale = s.depth > 8 ? t1_hscale16 : t1_hscale;
         c->yuv2planeX = t1_planeX;
         c->yuv2plane1 = t1_plane1;
@@ -405,6 +462,7 @@ typedef struct Bound {
     int planar;                   /* MI355_SWS_DST_* of a planar context (mi355_sws_scale_planar), 0 for rgb24 */
     int other;                    /* a source other than 8-bit yuv420p: described by mi355_sws_describe_fmt, built by mi355_sws_create_src_layout */
     int layout;                   /* ... its MI355_SWS_SRC_* (NV12 / NV21: two source planes) */
+    int range;                    /* ... the MI355_SWS_RANGE_* its converters gave when it was bound (mi355_sws_describe_range / mi355_sws_create_src_layout_range) */
     mi355_sws_ctx *dev;
     int failed;                   /* the device side does not take this context: the reference's function from now on */
     int busy;                     /* calls of mi355_sws_scale in flight on `dev` (under bound_mu): the device context is destroyed only at 0 */
@@ -451,10 +509,15 @@ static Bound *bound_find(SwsContext *c, int create)
 /* a selector runs for this context: sws_init_context() of a new context — possibly at the address of one that was freed */
 static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
 {
-    int planar = special ? 0 : planar_format(c), other = 0, layout = MI355_SWS_SRC_PLANAR;
+    int planar = special ? 0 : planar_format(c), other = 0, layout = MI355_SWS_SRC_PLANAR, range = MI355_SWS_RANGE_NONE;
     if (!(taken(c) || planar)) {
         mi355_sws_src s;
-        const int fmt = fmt_format(c, &s, special, &layout);
+        int fmt = fmt_format(c, &s, special, &layout);
+        if (fmt < 0 && !special && (range = range_probe(c)) > 0) {
+            /* the generic scaler with lumConvertRange / chrConvertRange between its passes, to a YUV destination */
+            fmt = fmt_format_r(c, &s, 0, &layout, 1);
+            if (fmt == 0) fmt = -1;
+        } else range = MI355_SWS_RANGE_NONE;
         if (fmt < 0) return real;
         other = 1; planar = fmt;
     }
@@ -463,7 +526,7 @@ static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
     Bound *b = bound_find(c, 1);
     if (b) {
         slot_release(b);
-        b->c = c; b->real = real; b->special = special; b->planar = planar; b->other = other; b->layout = layout; b->stamp = ++n_stamp;
+        b->c = c; b->real = real; b->special = special; b->planar = planar; b->other = other; b->layout = layout; b->range = range; b->stamp = ++n_stamp;
     }
     pthread_mutex_unlock(&bound_mu);
     return b ? mi355_swsfunc_entry : real;
@@ -482,8 +545,11 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
     mi355_sws_src s_now;
     int l_now;
     const int semi = b && (b->planar == MI355_SWS_DST_NV12 || b->planar == MI355_SWS_DST_NV21);      /* two planes: dstStride[2] is not looked at */
+    /* a context bound with range conversion: the converters it holds NOW give the direction it was bound with (range_probe), else the
+     * reference's function for that picture too */
     const int planar_ok = b && b->planar && dstStride[1] > 0 && (semi || dstStride[2] > 0) &&
-                          (b->other ? fmt_format(c, &s_now, 0, &l_now) : planar_format(c)) == b->planar;
+                          (b->other ? fmt_format_r(c, &s_now, 0, &l_now, b->range != 0) : planar_format(c)) == b->planar &&
+                          (!b->range || range_probe(c) == b->range);
     /* an rgb24 context of another source: range conversion set since it was bound is the reference's for that picture, as above */
     const int other_ok = !b || !b->other || b->planar || fmt_format(c, &s_now, b->special, &l_now) == 0;
     /* an NV12 / NV21 source has two planes: srcStride[2] is not looked at; a packed rgb24 / bgr24 source has one */
@@ -496,10 +562,11 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
             int fmt;
             if (b->other) {
                 mi355_sws_src s;
-                int layout;
-                if (device_ready() && (b->layout ? mi355_sws_describe_fmt(c, &d, &s, &layout, &fmt) == 0 && layout == b->layout
+                int layout, range = MI355_SWS_RANGE_NONE;
+                if (device_ready() && (b->range ? mi355_sws_describe_range(c, &d, &s, &layout, &fmt, &range) == 0 && layout == b->layout && range == b->range :
+                                       b->layout ? mi355_sws_describe_fmt(c, &d, &s, &layout, &fmt) == 0 && layout == b->layout
                                                  : describe_src(c, &d, &s, &fmt, b->special) == 0) && fmt == b->planar)
-                    b->dev = mi355_sws_create_src_layout(&d, &s, b->layout, fmt);
+                    b->dev = mi355_sws_create_src_layout_range(&d, &s, b->layout, fmt, range);
             } else if (b->planar) {
                 if (device_ready() && mi355_sws_describe_planar(c, &d, &fmt) == 0) b->dev = mi355_sws_create_planar(&d, fmt);
             } else if (device_ready() && describe(c, &d, b->special) == 0) b->dev = mi355_sws_create(&d);

@@ -203,6 +203,23 @@ int mi355_sws_source_layout(const mi355_sws_ctx *ctx);   /* MI355_SWS_SRC_*, -1 
  * those three bytes readable on the last line too.  The Tier-1 host entry points return -1 when src_stride[0] < 3 * srcW. */
 enum { MI355_SWS_SRC_RGB24 = 4, MI355_SWS_SRC_BGR24 = 5 };
 
+/* ---- range conversion: contexts whose source and destination differ in range, to a YUV destination (yuvj420p <-> yuv420p and their kin:
+ * c->srcRange != c->dstRange && !isAnyRGB(c->dstFormat), lumConvertRange / chrConvertRange swscale.c:168-198, :748-766) ----
+ * The reference applies the two converters to every horizontally scaled int16 line, between hyScale / hcScale and the vertical pass
+ * (swscale.c:284-285, :334-335); so does a context created here, on the lines of its LDS tile.  Such a context has the banks of its same-range
+ * twin (and is refused exactly where the twin is), and runs the generic scaler at equal size too (utils.c:1044 keeps it off the unscaled
+ * converters).  The 8-bit destination forms, 32-bit arithmetic, the result stored back as int16 (truncated, as the reference's store):
+ *   FROM_JPEG (full -> limited)  luma (v * 14071 + 33561947) >> 14                  chroma (v * 1799 + 4081085) >> 11
+ *   TO_JPEG   (limited -> full)  luma (min(v, 30189) * 19077 - 39057361) >> 14      chroma (min(v, 30775) * 4663 - 9289992) >> 12
+ * range 0: exactly mi355_sws_create_src_layout (same plan, same kernel, same bytes).  1 / 2: every src_layout (0, 1, 2, 4, 5), depth and
+ * subsampling that creator takes, to every YUV dst_format (MI355_SWS_DST_YUV420P / 422P / 444P / NV12 / NV21).  NULL and a message for a range
+ * outside 0..2, for a range with dst_format 0 (an rgb24 destination takes the range into its LUTs: create it without one) and for a range with
+ * desc->unscaled_special (the reference never builds either).  Frames go through mi355_sws_scale_planar_frames_dev / mi355_sws_scale_planar;
+ * mi355_sws_plan reports PLANAR_A / B / C as for the same banks without a range. */
+enum { MI355_SWS_RANGE_NONE = 0, MI355_SWS_RANGE_FROM_JPEG = 1, MI355_SWS_RANGE_TO_JPEG = 2 };
+mi355_sws_ctx *mi355_sws_create_src_layout_range(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format, int range);
+int mi355_sws_range(const mi355_sws_ctx *ctx);   /* MI355_SWS_RANGE_*, -1 bad argument */
+
 /* ---- the individual inner loops (Tier 1, host pointers), argument lists of the reference's
  * function-pointer types minus the SwsContext ------------------------------------------------ */
 /* hScale8To15_c swscale.c:133-147 (c->hyScale / c->hcScale) */
@@ -216,6 +233,10 @@ void mi355_sws_rgb24ToY(uint8_t *dst, const uint8_t *src, int width, int bgr);
 /* rgb24ToUV_c / bgr24ToUV_c and their _half forms input.c:552-623 (c->chrToYV12): `width` OUTPUT samples of each plane; half 0 reads
  * 3 * width bytes, half 1 (each sample from the sum of two neighbouring pixels) 6 * width */
 void mi355_sws_rgb24ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int width, int bgr, int half);
+/* lumRangeFromJpeg_c / lumRangeToJpeg_c and chrRangeFromJpeg_c / chrRangeToJpeg_c swscale.c:168-198 (c->lumConvertRange / c->chrConvertRange):
+ * `width` int16 samples converted in place, any int16 value (a result outside int16 is stored truncated, as the reference stores it) */
+void mi355_sws_lumConvertRange(int16_t *dst, int width, int to_jpeg);
+void mi355_sws_chrConvertRange(int16_t *dstU, int16_t *dstV, int width, int to_jpeg);
 /* yuv2planeX_8_c output.c:242-255, yuv2plane1_8_c :257-266 */
 void mi355_sws_yuv2planeX_8(const int16_t *filter, int filterSize, const int16_t **src, uint8_t *dest, int dstW,
                             const uint8_t *dither, int offset);

@@ -2,7 +2,8 @@
  * sws.hip — the libswscale part of the path: planar yuv 4:2:0 / 4:2:2 / 4:4:4 sources at 8, 9 or 10 bits (16-bit
  * little-endian samples above 8: hScale16To15_c swscale.c:110-130 in place of hScale8To15_c), 8-bit NV12 / NV21 and packed rgb24 / bgr24 sources -> rgb24,
  * -> 8-bit yuv420p / yuv422p / yuv444p and -> NV12 / NV21 (dithered from a deeper source, swscale.c:553-556), the unscaled 8-bit
- * yuv420p -> NV12 / NV21 packer and the unscaled NV12 / NV21 -> yuv420p splitter.  This file:
+ * yuv420p -> NV12 / NV21 packer and the unscaled NV12 / NV21 -> yuv420p splitter; to the YUV destinations also with range conversion between the two
+ * passes (yuvj420p <-> yuv420p and their kin: lumConvertRange / chrConvertRange swscale.c:168-198).  This file:
  * the context, the plan (which kernel a context gets) and the entry points of include/mi355_sws.h.  The device side is sws_dev.h:
  * k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1, k_sws_nv12_pack, k_sws_nv12_split and the k_sws_line_* kernels of the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
@@ -175,9 +176,17 @@ static mi355_sws_ctx *ctx_upload(mi355_sws_ctx *c)
     return c;
 }
 
+/* the four maps of lumConvertRange / chrConvertRange for an 8-bit destination (swscale.c:168-198): full -> limited has no cap of its own — 32767,
+ * what an int16 holds, so the kernel's min is the same instruction both ways */
+static SwsRangeMap range_map(int range, bool chroma)
+{
+    if (range == MI355_SWS_RANGE_TO_JPEG) return chroma ? SwsRangeMap{ 30775, 4663, -9289992, 12 } : SwsRangeMap{ 30189, 19077, -39057361, 14 };
+    return chroma ? SwsRangeMap{ 32767, 1799, 4081085, 11 } : SwsRangeMap{ 32767, 14071, 33561947, 14 };
+}
 /* what the create entry points share: the source check, the destination family (rgb24, or planar: dst_format MI355_SWS_DST_*), the bank
  * validation with its diagnostics.  The unscaled special converter (rgb24) and the unscaled packer (NV12 / NV21) have no banks. */
-static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src *src, bool planar, int dst_format, const char *who, int layout = MI355_SWS_SRC_PLANAR)
+static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src *src, bool planar, int dst_format, const char *who, int layout = MI355_SWS_SRC_PLANAR,
+                                 int range = MI355_SWS_RANGE_NONE)
 {
     const bool semi = dst_format == MI355_SWS_DST_NV12 || dst_format == MI355_SWS_DST_NV21;
     if (planar && (!desc || ((dst_format < MI355_SWS_DST_YUV420P || dst_format > MI355_SWS_DST_YUV444P) && !semi))) {
@@ -186,6 +195,8 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
     }
     mi355_sws_ctx *c = ctx_new(desc);
     SwsDev &h = c->h;
+    h.range = range;
+    h.rng_l = range_map(range, false); h.rng_c = range_map(range, true);      /* (read by the RANGE instances only) */
     if (src && !ctx_source(c, src)) {
         std::fprintf(stderr, "mi355dsp: %s: source %d bit, chroma shifts %d/%d (chroma %dx%d of %dx%d) is outside this backend\n", who, src->depth, src->hsub, src->vsub,
                      h.chrSrcW, h.chrSrcH, h.srcW, h.srcH);
@@ -296,6 +307,31 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src_layout(const mi355_sws_desc *desc
     return ctx_create(desc, src, dst_format != 0, dst_format, "mi355_sws_create_src_layout", src_layout);
 }
 extern "C" int mi355_sws_source_layout(const mi355_sws_ctx *c) { return c ? c->h.src_layout : -1; }
+extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format, int range)
+{
+    if (range == MI355_SWS_RANGE_NONE) return mi355_sws_create_src_layout(desc, src, src_layout, dst_format);
+    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range without mi355_init(); no CPU fallback\n"); std::abort(); }
+    if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: no descriptor\n"); return nullptr; }
+    if (range != MI355_SWS_RANGE_FROM_JPEG && range != MI355_SWS_RANGE_TO_JPEG) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: range %d is not none / from-jpeg / to-jpeg\n", range);
+        return nullptr;
+    }
+    if (src_layout < MI355_SWS_SRC_PLANAR || src_layout > MI355_SWS_SRC_BGR24 || src_layout == 3) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24\n", src_layout);
+        return nullptr;
+    }
+    /* the reference converts the range of YUV destinations only (an RGB one takes it into its LUTs), and never in an unscaled special converter */
+    if (dst_format == 0) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: an rgb24 destination has its range in the LUTs, not in a conversion step\n");
+        return nullptr;
+    }
+    if (desc->unscaled_special) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: no unscaled special converter converts the range\n");
+        return nullptr;
+    }
+    return ctx_create(desc, src, true, dst_format, "mi355_sws_create_src_layout_range", src_layout, range);
+}
+extern "C" int mi355_sws_range(const mi355_sws_ctx *c) { return c ? c->h.range : -1; }
 
 extern "C" void mi355_sws_destroy(mi355_sws_ctx *c)
 {
@@ -456,6 +492,28 @@ static void launch_planar_rgb(int i, int form, dim3 grid, hipStream_t s, const S
     else if (i == 1) launch_planar_rgb<1>(form, grid, s, d, frames);
     else launch_planar_rgb<2>(form, grid, s, d, frames);
 }
+/* ... of a context that converts the range: the RANGE instance of each planar instance above — the same LDS (the step works in place) and waves
+ * per SIMD.  src: 0 8-bit planes, 1 16-bit planes, 2 NV12 / NV21, 3 rgb24 / bgr24; form as above */
+template <int I, typename ST, bool NV, bool RGB> static void launch_planar_range(int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+{
+    constexpr SwsShape S = PLANAR_SHAPES[I];
+    if (form == 0) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, ST, false, NV, RGB, true>), grid, dim3(NT), 0, s, d, frames);
+    else if (form == 1) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW, ST, false, NV, RGB, true>), grid, dim3(NT), 0, s, d, frames);
+    else hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, ST, true, NV, RGB, true>), grid, dim3(NT), 0, s, d, frames);
+}
+template <int I> static void launch_planar_range(int src, int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+{
+    if (src == 0) launch_planar_range<I, uint8_t, false, false>(form, grid, s, d, frames);
+    else if (src == 1) launch_planar_range<I, uint16_t, false, false>(form, grid, s, d, frames);
+    else if (src == 2) launch_planar_range<I, uint8_t, true, false>(form, grid, s, d, frames);
+    else launch_planar_range<I, uint8_t, false, true>(form, grid, s, d, frames);
+}
+static void launch_planar_range(int i, int src, int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+{
+    if (i == 0) launch_planar_range<0>(src, form, grid, s, d, frames);
+    else if (i == 1) launch_planar_range<1>(src, form, grid, s, d, frames);
+    else launch_planar_range<2>(src, form, grid, s, d, frames);
+}
 /* workgroups per CU of the instances (8-bit, then 16-bit: their staging lines are STAGE_BYTES16); the NV instances stage the pair plane in the
  * 8-bit instances' staging lines (StageGeom<TW>) and hold the same tiles: the 8-bit rows below are theirs too */
 static_assert(StageGeom<TW>::PITCH * StageGeom<TW>::LINES * 4 == STAGE_BYTES, "the pair plane's rounds fill the 8-bit staging storage");
@@ -515,7 +573,8 @@ extern "C" int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *c, const mi355_s
     }
     const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
     const int i = k - MI355_SWS_K_PLANAR_A;
-    if (packed_rgb(h)) launch_planar_rgb(i, semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
+    if (h.range) launch_planar_range(i, packed_rgb(h) ? 3 : (h.src_layout ? 2 : (h.depth > 8 ? 1 : 0)), semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
+    else if (packed_rgb(h)) launch_planar_rgb(i, semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
     else if (h.src_layout) launch_planar_nv(i, semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
     else if (semi_planar(h)) {
         if (h.depth > 8) launch_semi<uint16_t>(i, grid, s, c->d, d_frames);
@@ -691,6 +750,30 @@ extern "C" void mi355_sws_rgb24ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t 
     a.download();
     std::memcpy(dstU, a.h<uint8_t>(o_u), (size_t)width);
     std::memcpy(dstV, a.h<uint8_t>(o_v), (size_t)width);
+}
+
+/* lumRangeFromJpeg_c / lumRangeToJpeg_c and chrRangeFromJpeg_c / chrRangeToJpeg_c (swscale.c:168-198) of one line, in place */
+static void range_line(int16_t *const lines[], int n, int width, const SwsRangeMap &m)
+{
+    if (width <= 0) return;
+    Arena &a = arena();
+    const size_t bytes = ((size_t)width * 2 + 15) & ~(size_t)15;
+    a.reserve(n * bytes + 64);
+    const size_t o = a.take(n * bytes);
+    for (int k = 0; k < n; k++) std::memcpy(a.h<uint8_t>(o) + k * bytes, lines[k], (size_t)width * 2);
+    a.upload();
+    for (int k = 0; k < n; k++) launch_line(k_sws_line_range, a, reinterpret_cast<int16_t *>(a.d<uint8_t>(o) + k * bytes), width, m);
+    a.download();
+    for (int k = 0; k < n; k++) std::memcpy(lines[k], a.h<uint8_t>(o) + k * bytes, (size_t)width * 2);
+}
+extern "C" void mi355_sws_lumConvertRange(int16_t *dst, int width, int to_jpeg)
+{
+    range_line(&dst, 1, width, range_map(to_jpeg ? MI355_SWS_RANGE_TO_JPEG : MI355_SWS_RANGE_FROM_JPEG, false));
+}
+extern "C" void mi355_sws_chrConvertRange(int16_t *dstU, int16_t *dstV, int width, int to_jpeg)
+{
+    int16_t *const lines[2] = { dstU, dstV };
+    range_line(lines, 2, width, range_map(to_jpeg ? MI355_SWS_RANGE_TO_JPEG : MI355_SWS_RANGE_FROM_JPEG, true));
 }
 
 static size_t pack_rows(Arena &a, const int16_t **rows, int n, int elems, int pitch)

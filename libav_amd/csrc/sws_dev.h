@@ -16,7 +16,8 @@
  * The tile kernels are instantiated per sample type: the uint16_t instances differ in the horizontal pass (its staging lines are twice
  * as long, so is their LDS) and, for planar destinations, in the dither rows.  The NV instances of the tile kernels and of k_sws_ident1 read
  * an NV12 / NV21 source: both chroma planes from one pass over its plane of byte pairs (hscale_tile_nv).  The RGB instances of the tile kernels
- * read a packed rgb24 / bgr24 source: the reference's input converters in front of the 8-bit horizontal pass (hscale_tile_rgb).
+ * read a packed rgb24 / bgr24 source: the reference's input converters in front of the 8-bit horizontal pass (hscale_tile_rgb).  The RANGE
+ * instances of k_sws_planar convert the range of the int16 lines between the two passes (lumConvertRange / chrConvertRange: range_lines).
  *   k_sws_line_*    the individual inner loops for the Tier-1 entry points.
  * Execution model: 256-thread workgroups (4 waves) sharing one LDS tile; integer only, no MFMA.
  */
@@ -43,6 +44,7 @@ struct SwsShape { int lcap, ccap; };
 constexpr SwsShape GENERIC_SHAPES[3] = { { 28, 16 }, { 40, 20 }, { MAXL, MAXC } };
 constexpr SwsShape PLANAR_SHAPES[3] = { { 28, 16 }, { 40, 24 }, { MAXL, MAXCP } };
 
+struct SwsRangeMap { int cap, mul, add, shift; };
 struct SwsDev {
     int srcW, srcH, dstW, dstH, chrSrcW, chrSrcH, chrDstW, special;
     int hls, hcs, vls, vcs;                 /* filter sizes */
@@ -61,6 +63,10 @@ struct SwsDev {
      * second source plane holds chrSrcW byte pairs (NV12: U V, NV21: V U) and there is no third */
     int depth, src_hsub, src_vsub, src_layout;
     __attribute__((aligned(8))) uint8_t dither[8][8];
+    /* range conversion between the horizontal and the vertical pass (mi355_sws_create_src_layout_range): MI355_SWS_RANGE_*, and the affine map
+     * of each plane kind — (min(v, cap) * mul + add) >> shift, lumConvertRange / chrConvertRange of an 8-bit destination (swscale.c:168-198) */
+    int range;
+    SwsRangeMap rng_l, rng_c;
 };
 
 /* the context record with its bank pointers in the global address space (mi355_rt.h): what the tile kernels open with */
@@ -1426,6 +1432,29 @@ __host__ __device__ constexpr int sws_planar_waves(int lum_lines, int chr_lines,
     return sws_waves(sws_planar_lds_bytes(lum_lines, chr_lines, cw, stage));
 }
 
+/* lumConvertRange / chrConvertRange (lumRangeFromJpeg_c, lumRangeToJpeg_c, chrRangeFromJpeg_c, chrRangeToJpeg_c, swscale.c:168-198) of two int16
+ * samples of a dword: 32-bit arithmetic, the result stored back as int16 (truncated, as the reference's store).  |v| < 2^15 and the four
+ * multipliers are below 2^15: the product is a 24-bit multiply-add */
+__device__ __forceinline__ int range_one(int v, const SwsRangeMap &m)
+{
+    return (__mul24(imin(v, m.cap), m.mul) + m.add) >> m.shift;
+}
+__device__ __forceinline__ uint32_t range_pair(uint32_t w, const SwsRangeMap &m)
+{
+    const int a = range_one((int16_t)w, m), b = range_one((int)w >> 16, m);
+    return ((uint32_t)a & 0xFFFFu) | ((uint32_t)b << 16);
+}
+/* ... of `nvec` 16-byte pieces of LDS lines, in place: a pass of its own over the tile's lines between two workgroup barriers */
+__device__ __forceinline__ void range_lines(int16_t *lines, int nvec, const SwsRangeMap &m, int tid)
+{
+    sws_u32x4 *q = reinterpret_cast<sws_u32x4 *>(lines);
+    for (int i = tid; i < nvec; i += NT) {
+        sws_u32x4 w = q[i];
+        for (int k = 0; k < 4; k++) w[k] = range_pair(w[k], m);
+        q[i] = w;
+    }
+}
+
 /* One workgroup per output tile of TW luma columns x th luma rows (blockIdx.z: the picture of the batch).  The tile's chroma is CW = TW >> hshift
  * columns and the chroma rows cy with cy << vshift inside the tile's rows (swscale.c:618-645: a chroma row is written with the luma row
  * cy << vshift, chrSkipMask).  Horizontal pass of the source lines the tile needs into LDS (hscale_tile, as k_sws_generic), then the
@@ -1433,8 +1462,10 @@ __host__ __device__ constexpr int sws_planar_waves(int lum_lines, int chr_lines,
  * SEMI: an NV12 / NV21 destination (4:2:0, CW = TW / 2) — the chroma rows go to ONE plane of byte pairs, fr.dst[1] (semiplanar_rows);
  * fr.dst[2] is not used.  The three-plane instances are the SEMI false ones, unchanged.
  * NV: an NV12 / NV21 source, as k_sws_generic's — U | V of an LDS line from one pass over fr.src[1].
- * RGB: a packed rgb24 / bgr24 source, as k_sws_generic's — luma and U | V from fr.src[0]. */
-template <int LCAP, int CCAP, int CW, typename ST = uint8_t, bool SEMI = false, bool NV = false, bool RGB = false>
+ * RGB: a packed rgb24 / bgr24 source, as k_sws_generic's — luma and U | V from fr.src[0].
+ * RANGE: a context whose source and destination differ in range — the int16 samples the horizontal pass left in s_lum / s_chr go through
+ * c.rng_l / c.rng_c before the vertical pass reads them (range_lines: the direction is the constants, the same for the whole grid). */
+template <int LCAP, int CCAP, int CW, typename ST = uint8_t, bool SEMI = false, bool NV = false, bool RGB = false, bool RANGE = false>
 #ifndef MI355_HIP_EMU_H
 __attribute__((amdgpu_waves_per_eu(sws_planar_waves(LCAP, CCAP, CW, stage_bytes<ST>()), sws_planar_waves(LCAP, CCAP, CW, stage_bytes<ST>()))))
 #endif
@@ -1459,10 +1490,11 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
                                    llo, lhi, s_stage, tid, false, c.hstage != 0, c.hident_l != 0);
     } else
     hscale_tile<TW, TW, ST>(s_lum, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi, s_stage, tid, false, c.hstage != 0, c.hident_l != 0, c.depth);
-    int clo = 0;
+    int clo = 0, nchr = 0;
     if (cy0 <= cy1) {
         clo = clampi(imax(1 - cs, c.vChrP[cy0]), 0, c.chrSrcH - 1);
         const int chi = clampi(imax(1 - cs, c.vChrP[cy1]) + cs - 1, 0, c.chrSrcH - 1);
+        nchr = chi - clo + 1;
         if constexpr (RGB) {
             int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
             hscale_tile_rgb<CW, 2 * CW, 2>(s_u, s_v, fr.src[0], fr.src_stride[0], c.srcW, c.chrSrcW, c.src_hsub != 0, c.src_layout == MI355_SWS_SRC_BGR24, c.hChrP, c.hChrC, c.hcs,
@@ -1482,6 +1514,13 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
         }
     }
     __syncthreads();
+    if constexpr (RANGE) {
+        /* whole lines of the tile, the columns past the picture with them (nothing stores what the vertical pass makes of those); the lines are
+         * contiguous: TW / 8 and 2 * CW / 8 pieces each */
+        range_lines(&s_lum[0][0], (lhi - llo + 1) * (TW / 8), c.rng_l, tid);
+        range_lines(&s_chr[0][0], nchr * (2 * CW / 8), c.rng_c, tid);
+        __syncthreads();
+    }
     const uint8_t (*dith)[8] = DITH ? mi355_global(cp)->dither : nullptr;
     planar_pass<TW / 8, 1, DITH>(&s_lum[0][0], llo, c.srcH - 1, c.vLumC, c.vLumP, ls, y0, y1 - y0 + 1, x0, c.dstW,
                                  fr.dst[0] + (size_t)y0 * fr.dst_stride[0], fr.dst_stride[0], nullptr, 0, tid, dith);
@@ -1857,6 +1896,11 @@ __global__ void __launch_bounds__(NT) k_sws_line_rgb24_uv(uint8_t *dstU, uint8_t
         rgb_sample(src + (half ? 6 : 3) * (size_t)i, half != 0, K, a, b);
         dstU[i] = (uint8_t)a; dstV[i] = (uint8_t)b;
     }
+}
+/* lumConvertRange / chrConvertRange of one line, in place */
+__global__ void __launch_bounds__(NT) k_sws_line_range(int16_t *line, int width, SwsRangeMap m)
+{
+    for (int i = threadIdx.x; i < width; i += NT) line[i] = (int16_t)range_one(line[i], m);
 }
 /* yuv2planeX_8_c output.c:242-255 (fs >= 1 rows at `pitch` elements) / yuv2plane1_8_c :257-266 (fs == 0) */
 __global__ void __launch_bounds__(NT) k_sws_line_plane(const int16_t *filter, int fs, const int16_t *rows, int pitch, uint8_t *dest, int dstW,

@@ -39,8 +39,14 @@ def main():
                          "destination out — on --other-lib (the parent commit's build; this build without it): 2160p -> 1080p yuv420p, nv12 and rgb24, "
                          "1080p -> yuv420p at equal size, each twin a second time in another allocation (A/A), and with --other-lib the three "
                          "existing points; 32 and 512 pictures per launch, 3 warm-up + --steps launches a round, alternating, median of 3 rounds")
+    ap.add_argument("--range", action="store_true",
+                    help="range conversion (mi355_sws_create_src_layout_range) beside THE SAME descriptor created with range 0 on the same build — identical "
+                         "banks and traffic: 1080p yuvj420p -> yuv420p and yuv420p -> yuvj420p at equal size, 2160p yuvj420p -> 1080p yuv420p and nv12, "
+                         "1080p rgb24 -> yuvj420p; the partner a second time in another allocation (A/A), with --other-lib also on that build, and the "
+                         "reference's single-thread sws_scale(); 32 and 512 pictures per launch, 3 warm-up + --steps launches a round, alternating, "
+                         "median of 3 rounds")
     ap.add_argument("--other-lib", default=None,
-                    help="--nv12 / --nvsrc / --rgbsrc: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
+                    help="--nv12 / --nvsrc / --rgbsrc / --range: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
     ap.add_argument("--rounds", type=int, default=5, help="--planar / --sources: alternating rounds (the median is reported)")
     a = ap.parse_args()
     prov = providers.mi355()
@@ -57,6 +63,8 @@ def main():
         return nvsrc(a, lib)
     if a.rgbsrc:
         return rgbsrc(a, lib)
+    if a.range:
+        return range_points(a, lib)
     orc = S.oracle_backend(providers.oracle())
     for name in a.configs.split(","):
         ctx = S.load_context(name)
@@ -552,6 +560,71 @@ def rgbsrc(a, lib):
                 ms = statistics.median(times[k])
                 print(json.dumps({"workload": name + ":" + k, "frames_per_launch": a.frames, "ms_per_launch": ms, "algorithmic_bytes_per_frame": nb,
                                   "ms_rounds": [round(x, 4) for x in times[k]]}), flush=True)
+            for l, b in batches.values():
+                b.close()
+
+
+def range_points(a, lib):
+    """Range conversion beside its partner: the same descriptor created with range 0 on the same build has identical banks and traffic and lacks
+    only the step between the two passes.  The contexts come from the reference's libswscale at run time (oracle/_ref/libswsref.so:
+    mi355_sws_describe_range) — no full-size context is committed.  `range0#2` is the partner a second time with its own buffers: the session's
+    A/A spread; with --other-lib the partner also runs on that build (the parent commit's, through mi355_sws_create_src_layout).  Beside each
+    point the reference's own single-thread sws_scale() of one picture.  One process, the batches of a point alternating: 3 warm-up + --steps
+    launches a round, median of 3 rounds, at 32 and 512 pictures per launch.  Algorithmic bytes: sources read once + destinations written once."""
+    import statistics
+    import sws_nvsrc as V
+    import sws_planar as P
+    import sws_range as G
+    other = None
+    if a.other_lib:
+        other = C.CDLL(os.path.abspath(a.other_lib))
+        other.mi355_init.restype = C.c_int
+        assert other.mi355_init(C.c_int(0)) == 0
+        other.mi355_event_create.restype = C.c_void_p
+        other.mi355_event_elapsed_ms.restype = C.c_float
+    ref = G.Ref(P.bind(G.REF_LIB))
+    rounds = 3
+    # (point, srcW, srcH, dstW, dstH, source, its range, destination, its range)
+    points = [("hd_same_yuvj420p_to_yuv420p", 1920, 1080, 1920, 1080, "yuv420p", 1, "yuv420p", 0),
+              ("hd_same_yuv420p_to_yuvj420p", 1920, 1080, 1920, 1080, "yuv420p", 0, "yuv420p", 1),
+              ("uhd_to_hd_yuvj420p_to_yuv420p", 3840, 2160, 1920, 1080, "yuv420p", 1, "yuv420p", 0),
+              ("uhd_to_hd_yuvj420p_to_nv12", 3840, 2160, 1920, 1080, "yuv420p", 1, "nv12", 0),
+              ("hd_same_rgb24_to_yuvj420p", 1920, 1080, 1920, 1080, "rgb24", 0, "yuv420p", 1)]
+    cpu = {}
+    for frames in (32, 512):
+        for point, sw, sh, dw, dh, src, sr, dst, dr in points:
+            row = (sw, sh, dw, dh, src, sr, dst, dr, 1, 1, 1)          # a row of tests/sws_range.py's table, not entered into it
+            c = ref.open(row)
+            e = ref.describe_range(c)
+            assert e is not None and e.range == G.direction(row), point
+            pics = [G.picture(row, "noise", seed=s) for s in (1, 2)]
+            if point not in cpu:
+                ref.scale_ctx(c, pics[0], e.out_sizes(), pad=0)
+                t = time.time()
+                for pic in pics:
+                    ref.scale_ctx(c, pic, e.out_sizes(), pad=0)
+                cpu[point] = len(pics) / (time.time() - t)
+            ref.free(c)
+            partner = e.edited(range=0)
+            batches = {"ranged@this": (lib, PlaneBatch(lib, G.create(lib, e), pics, e.out_sizes(), frames)),
+                       "range0@this": (lib, PlaneBatch(lib, G.create(lib, partner), pics, e.out_sizes(), frames)),
+                       "range0#2@this": (lib, PlaneBatch(lib, G.create(lib, partner), pics, e.out_sizes(), frames))}
+            if other:
+                batches["range0@parent"] = (other, PlaneBatch(other, V.create(other, partner), pics, e.out_sizes(), frames))
+            plan = G.plan_of(lib, batches["ranged@this"][1].handle)
+            times = {k: [] for k in batches}
+            for _ in range(rounds):
+                for k, (l, b) in batches.items():
+                    times[k].append(time_ms(l, b.run, a.steps))
+            base = statistics.median(times["range0@this"])
+            for k, (l, b) in batches.items():
+                ms = statistics.median(times[k])
+                us = ms * 1e3 / frames
+                nb = b.src_bytes + b.dst_bytes
+                print(json.dumps({"workload": point + ":" + k, "frames_per_launch": frames, "ms_per_launch": ms, "us_per_picture": us, "frames_per_s": 1e6 / us,
+                                  "algorithmic_bytes_per_frame": nb, "achieved_GBps": nb / us * 1e-3, "frac_of_8TBps": nb / us * 1e-3 / 8000.0,
+                                  "vs_range0": ms / base - 1.0, "kernel": plan["kernel"], "hstaged": plan["hstaged"], "range": plan["range"] if k == "ranged@this" else 0,
+                                  "reference_sws_scale_frames_per_s_1core": cpu[point], "ms_rounds": [round(x, 4) for x in times[k]]}), flush=True)
             for l, b in batches.values():
                 b.close()
 
