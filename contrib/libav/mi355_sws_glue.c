@@ -59,6 +59,13 @@
  *                          direction is read from the converters the context holds (range_probe), at bind time and again on every call: a
  *                          mismatch is the reference's function for that picture.  With MI355_SWS_LINES=1 the two converters are forwarded
  *                          too (mi355_sws_lumConvertRange / mi355_sws_chrConvertRange).  The four describers above keep declining these.
+ *   9- / 10-bit destinations  yuv420p9le / yuv422p9le / yuv444p9le and their 10le forms, from every source above, where the reference runs its generic
+ *                          scaler (15-bit intermediates, yuv2planeX_10 / yuv2plane1_10 without dither) take the same two forms through
+ *                          mi355_sws_describe_depth() / mi355_sws_create_src_layout_range_depth(); the depth is remembered beside layout and
+ *                          range and read again on every call.  With MI355_SWS_LINES=1 c->yuv2planeX / c->yuv2plane1 go to
+ *                          mi355_sws_yuv2planeX_nbps / mi355_sws_yuv2plane1_nbps.  Declined: big-endian, 12 / 14 / 16-bit, P010 and gray
+ *                          destinations, the plane copies (equal size with equal subsampling: planarCopyWrapper, no banks) and a deep
+ *                          destination with range converters.  The five describers above keep declining a destination deeper than 8 bits.
  * The device is MI355_DEVICE (default 0), as for the decoder bridges.
  */
 #include <pthread.h>
@@ -172,8 +179,25 @@ static int source_of(const SwsContext *c, mi355_sws_src *s)
 /* 0: rgb24, MI355_SWS_DST_*: planar or semi-planar, -1: a context this path leaves to the reference.  special: the context's swscale is
  * yuv2rgb_c_24_rgb or, with an NV12 / NV21 destination, planarToNv12Wrapper */
 /* the destination of a context that runs the generic scaler, -1 for one this path leaves to the reference */
-/* ranged: the context may hold lumConvertRange / chrConvertRange (mi355_sws_describe_range); the existing describers ask with 0 */
+/* ranged: the context may hold lumConvertRange / chrConvertRange (mi355_sws_describe_range); the existing describers ask with 0.
+ * ranged == MI355_ASK_DEEP (mi355_sws_describe_depth alone): the destination is one of the six 9- / 10-bit planar formats instead of the 8-bit
+ * ones, and there is no range */
+#define MI355_ASK_DEEP 2
 static int generic_dst_r(const SwsContext *c, int ranged);
+/* the MI355_SWS_DST_* and the depth of a 9- / 10-bit little-endian planar destination, 0 for any other format (big endian, 12 / 14 / 16 bits,
+ * P010, gray: not ours) */
+static int deep_dst(const SwsContext *c, int *depth)
+{
+    switch (c->dstFormat) {
+    case AV_PIX_FMT_YUV420P9LE:  *depth = 9;  return MI355_SWS_DST_YUV420P;
+    case AV_PIX_FMT_YUV422P9LE:  *depth = 9;  return MI355_SWS_DST_YUV422P;
+    case AV_PIX_FMT_YUV444P9LE:  *depth = 9;  return MI355_SWS_DST_YUV444P;
+    case AV_PIX_FMT_YUV420P10LE: *depth = 10; return MI355_SWS_DST_YUV420P;
+    case AV_PIX_FMT_YUV422P10LE: *depth = 10; return MI355_SWS_DST_YUV422P;
+    case AV_PIX_FMT_YUV444P10LE: *depth = 10; return MI355_SWS_DST_YUV444P;
+    default: return 0;
+    }
+}
 static int src_format_r(const SwsContext *c, mi355_sws_src *s, int special, int ranged)
 {
     if (source_of(c, s) != 0 || (c->flags & SWS_FULL_CHR_H_INT)) return -1;       /* (every destination below is 8 bits) */
@@ -188,8 +212,14 @@ static int generic_dst_r(const SwsContext *c, int ranged)
 {
     /* the generic scaler: no fast bilinear, no range conversion (unless asked for), no chroma line drop, and its four banks (an unscaled
      * converter or a plane copy has none, utils.c:1043-1048) */
-    if (c->hyscale_fast || c->hcscale_fast || (!ranged && (c->lumConvertRange || c->chrConvertRange)) || c->vChrDrop) return -1;
+    const int deep = ranged == MI355_ASK_DEEP;
+    if (c->hyscale_fast || c->hcscale_fast || ((!ranged || deep) && (c->lumConvertRange || c->chrConvertRange)) || c->vChrDrop) return -1;
     if (!c->vLumFilter || !c->vChrFilter || !c->hLumFilter || !c->hChrFilter) return -1;
+    if (deep) {
+        int bits;
+        const int fmt = deep_dst(c, &bits);
+        return fmt ? fmt : -1;
+    }
     switch (c->dstFormat) {
     case AV_PIX_FMT_RGB24:   return 0;
     case AV_PIX_FMT_YUV420P: return MI355_SWS_DST_YUV420P;
@@ -274,7 +304,7 @@ static int describe_fmt_r(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src
     const int rgb = c->srcFormat == AV_PIX_FMT_RGB24 || c->srcFormat == AV_PIX_FMT_BGR24;
     if (c->srcFormat != AV_PIX_FMT_NV12 && c->srcFormat != AV_PIX_FMT_NV21 && !rgb) {
         *src_layout = MI355_SWS_SRC_PLANAR;
-        return ranged ? describe_src_r(c, d, s, dst_format, 0, 1) : mi355_sws_describe_src(c, d, s, dst_format);
+        return ranged ? describe_src_r(c, d, s, dst_format, 0, ranged) : mi355_sws_describe_src(c, d, s, dst_format);
     }
     if (rgb && !c->vLumFilter) return -1;                        /* an unscaled converter or a copy: the reference's */
     if (!c->vLumFilter) {
@@ -333,6 +363,27 @@ int mi355_sws_describe_range(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_
     return describe_fmt_r(c, d, s, src_layout, dst_format, 1) == 0 && *dst_format > 0 ? 0 : -1;
 }
 
+/* ---- destinations of 9 or 10 bits: yuv420p9le ... yuv444p10le ------------------------------------------------------------------------------
+ * what mi355_sws_create_src_layout_range_depth takes for a live context (0), -1 for a context this path declines: mi355_sws_describe_range
+ * (depth 8) plus the contexts of the generic scaler to one of the six formats of deep_dst().  Such a context keeps the 15-bit intermediates
+ * (dstBpc <= 15, swscale.c:733-752) and differs from its 8-bit twin in c->yuv2planeX / c->yuv2plane1 alone.  Declined: what generic_dst_r()
+ * declines (fast bilinear, a chroma line drop, no banks — at equal size with equal subsampling the reference copies planes,
+ * planarCopyWrapper), SWS_FULL_CHR_H_INT, a source the other describers do not take, and a deep destination WITH range converters (the
+ * device has no such instance) */
+int mi355_sws_describe_depth(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *src_layout, int *dst_format, int *range, int *dst_depth)
+{
+    int bits = 8;
+    if (!deep_dst(c, &bits)) {
+        *dst_depth = 8;
+        return mi355_sws_describe_range(c, d, s, src_layout, dst_format, range);
+    }
+    if (!c->vLumFilter || c->dstBpc != bits) return -1;
+    if (describe_fmt_r(c, d, s, src_layout, dst_format, MI355_ASK_DEEP) != 0 || *dst_format <= 0) return -1;
+    *range = MI355_SWS_RANGE_NONE;
+    *dst_depth = bits;
+    return 0;
+}
+
 #ifndef MI355_SWS_DESCRIBE_ONLY
 static void t1_hscale16(SwsContext *c, int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
 {
@@ -387,6 +438,16 @@ static void t1_plane1(const int16_t *src, uint8_t *dest, int dstW, const uint8_t
     mi355_sws_yuv2plane1_8(src, dest, dstW, dither, offset);
 }
 
+/* yuv2planeX_9LE_c / _10LE_c and yuv2plane1_9LE_c / _10LE_c (output.c:183-236): no context in their argument lists, one shim per depth; the
+ * dither and the offset are ignored, as the reference ignores them */
+#define T1_NBPS(bits) \
+static void t1_planeX_ ## bits(const int16_t *filter, int filterSize, const int16_t **src, uint8_t *dest, int dstW, const uint8_t *dither, int offset) \
+{ (void)dither; (void)offset; n_calls++; mi355_sws_yuv2planeX_nbps(filter, filterSize, src, (uint16_t *)dest, dstW, bits); } \
+static void t1_plane1_ ## bits(const int16_t *src, uint8_t *dest, int dstW, const uint8_t *dither, int offset) \
+{ (void)dither; (void)offset; n_calls++; mi355_sws_yuv2plane1_nbps(src, (uint16_t *)dest, dstW, bits); }
+T1_NBPS(9)
+T1_NBPS(10)
+
 /* yuv2nv12cX_c (output.c:267-301): the semi-planar output's chroma loop, with the two context fields it reads */
 static void t1_nv12cX(SwsContext *c, const int16_t *chrFilter, int chrFilterSize, const int16_t **chrUSrc, const int16_t **chrVSrc, uint8_t *dest, int chrDstW)
 {
@@ -439,6 +500,16 @@ void ff_sws_init_mi355x(SwsContext *c)
         if (c->yuv2nv12cX) c->yuv2nv12cX = t1_nv12cX;
         return;
     }
+    /* a 9- / 10-bit planar destination: the horizontal loops as above (the intermediates stay 15 bits), the two output loops of its depth */
+    int bits = 8;
+    if (fmt < 0 && !range && deep_dst(c, &bits) && fmt_format_r(c, &s, 0, &layout, MI355_ASK_DEEP) > 0 && c->dstBpc == bits) {
+        if (!device_ready() || !c->hyScale || !c->hcScale || !c->yuv2planeX || !c->yuv2plane1) return;
+        rgb_converters(c, layout);
+        c->hyScale = c->hcScale = s.depth > 8 ? t1_hscale16 : t1_hscale;
+        c->yuv2planeX = bits == 9 ? t1_planeX_9 : t1_planeX_10;
+        c->yuv2plane1 = bits == 9 ? t1_plane1_9 : t1_plane1_10;
+        return;
+    }
     /* rgb24: yuv420p as before (taken(): also contexts with range conversion, which swscale() applies between the loops); the other sources
      * where src_format() takes them */
     if (!(taken(c) || fmt == 0) || c->hyscale_fast) return;
@@ -463,6 +534,7 @@ typedef struct Bound {
     int other;                    /* a source other than 8-bit yuv420p: described by mi355_sws_describe_fmt, built by mi355_sws_create_src_layout */
     int layout;                   /* ... its MI355_SWS_SRC_* (NV12 / NV21: two source planes) */
     int range;                    /* ... the MI355_SWS_RANGE_* its converters gave when it was bound (mi355_sws_describe_range / mi355_sws_create_src_layout_range) */
+    int depth;                    /* ... the bits of its planar destination: 8, or 9 / 10 (mi355_sws_describe_depth / mi355_sws_create_src_layout_range_depth) */
     mi355_sws_ctx *dev;
     int failed;                   /* the device side does not take this context: the reference's function from now on */
     int busy;                     /* calls of mi355_sws_scale in flight on `dev` (under bound_mu): the device context is destroyed only at 0 */
@@ -509,13 +581,17 @@ static Bound *bound_find(SwsContext *c, int create)
 /* a selector runs for this context: sws_init_context() of a new context — possibly at the address of one that was freed */
 static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
 {
-    int planar = special ? 0 : planar_format(c), other = 0, layout = MI355_SWS_SRC_PLANAR, range = MI355_SWS_RANGE_NONE;
+    int planar = special ? 0 : planar_format(c), other = 0, layout = MI355_SWS_SRC_PLANAR, range = MI355_SWS_RANGE_NONE, depth = 8;
     if (!(taken(c) || planar)) {
         mi355_sws_src s;
         int fmt = fmt_format(c, &s, special, &layout);
         if (fmt < 0 && !special && (range = range_probe(c)) > 0) {
             /* the generic scaler with lumConvertRange / chrConvertRange between its passes, to a YUV destination */
             fmt = fmt_format_r(c, &s, 0, &layout, 1);
+            if (fmt == 0) fmt = -1;
+        } else if (fmt < 0 && !special && range == MI355_SWS_RANGE_NONE && deep_dst(c, &depth)) {
+            /* the generic scaler to a 9- / 10-bit planar destination, no range */
+            fmt = c->dstBpc == depth ? fmt_format_r(c, &s, 0, &layout, MI355_ASK_DEEP) : -1;
             if (fmt == 0) fmt = -1;
         } else range = MI355_SWS_RANGE_NONE;
         if (fmt < 0) return real;
@@ -526,7 +602,8 @@ static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
     Bound *b = bound_find(c, 1);
     if (b) {
         slot_release(b);
-        b->c = c; b->real = real; b->special = special; b->planar = planar; b->other = other; b->layout = layout; b->range = range; b->stamp = ++n_stamp;
+        b->c = c; b->real = real; b->special = special; b->planar = planar; b->other = other; b->layout = layout; b->range = range; b->depth = depth;
+        b->stamp = ++n_stamp;
     }
     pthread_mutex_unlock(&bound_mu);
     return b ? mi355_swsfunc_entry : real;
@@ -543,13 +620,14 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
     /* a planar context: all three destination planes; range conversion set since the context was bound (sws_setColorspaceDetails) is
      * the reference's for that picture */
     mi355_sws_src s_now;
-    int l_now;
+    int l_now, d_now = 8;
     const int semi = b && (b->planar == MI355_SWS_DST_NV12 || b->planar == MI355_SWS_DST_NV21);      /* two planes: dstStride[2] is not looked at */
     /* a context bound with range conversion: the converters it holds NOW give the direction it was bound with (range_probe), else the
      * reference's function for that picture too */
     const int planar_ok = b && b->planar && dstStride[1] > 0 && (semi || dstStride[2] > 0) &&
-                          (b->other ? fmt_format_r(c, &s_now, 0, &l_now, b->range != 0) : planar_format(c)) == b->planar &&
-                          (!b->range || range_probe(c) == b->range);
+                          (b->other ? fmt_format_r(c, &s_now, 0, &l_now, b->depth > 8 ? MI355_ASK_DEEP : b->range != 0) : planar_format(c)) == b->planar &&
+                          (!b->range || range_probe(c) == b->range) &&
+                          (b->depth <= 8 || (deep_dst(c, &d_now) == b->planar && d_now == b->depth));   /* (with converters set since: the reference's) */
     /* an rgb24 context of another source: range conversion set since it was bound is the reference's for that picture, as above */
     const int other_ok = !b || !b->other || b->planar || fmt_format(c, &s_now, b->special, &l_now) == 0;
     /* an NV12 / NV21 source has two planes: srcStride[2] is not looked at; a packed rgb24 / bgr24 source has one */
@@ -562,11 +640,12 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
             int fmt;
             if (b->other) {
                 mi355_sws_src s;
-                int layout, range = MI355_SWS_RANGE_NONE;
-                if (device_ready() && (b->range ? mi355_sws_describe_range(c, &d, &s, &layout, &fmt, &range) == 0 && layout == b->layout && range == b->range :
+                int layout, range = MI355_SWS_RANGE_NONE, depth = 8;
+                if (device_ready() && (b->depth > 8 ? mi355_sws_describe_depth(c, &d, &s, &layout, &fmt, &range, &depth) == 0 && layout == b->layout && depth == b->depth :
+                                       b->range ? mi355_sws_describe_range(c, &d, &s, &layout, &fmt, &range) == 0 && layout == b->layout && range == b->range :
                                        b->layout ? mi355_sws_describe_fmt(c, &d, &s, &layout, &fmt) == 0 && layout == b->layout
                                                  : describe_src(c, &d, &s, &fmt, b->special) == 0) && fmt == b->planar)
-                    b->dev = mi355_sws_create_src_layout_range(&d, &s, b->layout, fmt, range);
+                    b->dev = mi355_sws_create_src_layout_range_depth(&d, &s, b->layout, fmt, range, depth);
             } else if (b->planar) {
                 if (device_ready() && mi355_sws_describe_planar(c, &d, &fmt) == 0) b->dev = mi355_sws_create_planar(&d, fmt);
             } else if (device_ready() && describe(c, &d, b->special) == 0) b->dev = mi355_sws_create(&d);

@@ -4,7 +4,8 @@
  * and the unscaled yuv420p -> rgb24 converter; whole pictures to RGB24, to planar yuv420p / yuv422p / yuv444p or to semi-planar
  * NV12 / NV21 (yuv2nv12cX, and the unscaled yuv420p -> NV12 / NV21 packer); from planar sources or from NV12 / NV21 (the reference's
  * nv12ToUV_c / nv21ToUV_c in front of hcScale, and the unscaled NV12 / NV21 -> yuv420p splitter) or from packed rgb24 / bgr24 (the
- * reference's rgb24ToY_c / rgb24ToUV_c / rgb24ToUV_half_c and their bgr24 forms in front of hyScale / hcScale).
+ * reference's rgb24ToY_c / rgb24ToUV_c / rgb24ToUV_half_c and their bgr24 forms in front of hyScale / hcScale); the three planar
+ * destinations also at 9 or 10 bits (yuv420p9le ... yuv444p10le: yuv2planeX_10 / yuv2plane1_10).
  *
  * The reference keeps these behind function pointers of the (private) SwsContext
  * (libswscale/swscale_internal.h:253-540): hyScale/hcScale :526-531, yuv2plane1/yuv2planeX/
@@ -220,6 +221,28 @@ enum { MI355_SWS_RANGE_NONE = 0, MI355_SWS_RANGE_FROM_JPEG = 1, MI355_SWS_RANGE_
 mi355_sws_ctx *mi355_sws_create_src_layout_range(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format, int range);
 int mi355_sws_range(const mi355_sws_ctx *ctx);   /* MI355_SWS_RANGE_*, -1 bad argument */
 
+/* ---- planar destinations of 9 or 10 bits: yuv420p9le / yuv422p9le / yuv444p9le / yuv420p10le / yuv422p10le / yuv444p10le
+ * (yuv2plane1_10_c_template / yuv2planeX_10_c_template, output.c:183-213) ----
+ * For a destination of 15 bits or fewer the reference keeps its 15-bit int16 intermediates (swscale.c:733-752), so such a context has the plan, the
+ * banks and the refusals of its 8-bit twin; only the vertical store differs.  32-bit arithmetic, no dither (also from a 9- or 10-bit source):
+ *   one vertical tap (the coefficient is unused)   clip((s + (1 << (14 - bits))) >> (15 - bits))
+ *   otherwise                                      clip(((1 << (26 - bits)) + sum s_j * f_j) >> (27 - bits))
+ * with clip to 0 .. (1 << bits) - 1.
+ * dst_depth 8: exactly mi355_sws_create_src_layout_range (same plan, same kernel, same bytes).  9 / 10: every src_layout (0, 1, 2, 4, 5), depth and
+ * subsampling that creator takes, to dst_format MI355_SWS_DST_YUV420P / 422P / 444P only — the format names the subsampling, the depth travels
+ * beside it; range must be 0 and desc->unscaled_special 0 (at equal size with equal subsampling the reference copies planes, planarCopyWrapper:
+ * not a context of the scaler).  The descriptor is the reference's for that context: chrDstW, vChr.n = chrDstH as for the 8-bit planar
+ * destination.  NULL and a message for any other depth, for a depth with dst_format 0 / NV12 / NV21, with a range or with a special converter,
+ * and for everything the 8-bit twin is refused for.
+ * Frames stay mi355_sws_planar_frame through mi355_sws_scale_planar_frames_dev / mi355_sws_scale_planar: dst[k] and dst_stride[k] stay byte
+ * pointers and byte strides, both EVEN; a row holds uint16_t samples, little endian, below 1 << dst_depth; only the first dstW / chrDstW samples
+ * of a row are written.  A row whose address is a multiple of 16 is stored in 16-byte pieces, any other sample by sample.  The Tier-1 host entry
+ * returns -1 for an odd stride or a stride below 2 * width.  mi355_sws_destination reports format 1 / 2 / 3, three planes and
+ * chr_bytes = 2 * chrDstW; mi355_sws_plan PLANAR_A / B / C as for the twin; mi355_sws_range 0. */
+mi355_sws_ctx *mi355_sws_create_src_layout_range_depth(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format, int range,
+                                                       int dst_depth);
+int mi355_sws_dest_depth(const mi355_sws_ctx *ctx);   /* 8 / 9 / 10, -1 bad argument */
+
 /* ---- the individual inner loops (Tier 1, host pointers), argument lists of the reference's
  * function-pointer types minus the SwsContext ------------------------------------------------ */
 /* hScale8To15_c swscale.c:133-147 (c->hyScale / c->hcScale) */
@@ -241,6 +264,10 @@ void mi355_sws_chrConvertRange(int16_t *dstU, int16_t *dstV, int width, int to_j
 void mi355_sws_yuv2planeX_8(const int16_t *filter, int filterSize, const int16_t **src, uint8_t *dest, int dstW,
                             const uint8_t *dither, int offset);
 void mi355_sws_yuv2plane1_8(const int16_t *src, uint8_t *dest, int dstW, const uint8_t *dither, int offset);
+/* yuv2planeX_9LE_c / _10LE_c and yuv2plane1_9LE_c / _10LE_c output.c:183-236: the reference's arguments minus the dither, which it ignores, plus
+ * `bits` (9 or 10; anything else does nothing); dstW little-endian uint16_t samples */
+void mi355_sws_yuv2planeX_nbps(const int16_t *filter, int filterSize, const int16_t **src, uint16_t *dest, int dstW, int bits);
+void mi355_sws_yuv2plane1_nbps(const int16_t *src, uint16_t *dest, int dstW, int bits);
 /* yuv2nv12cX_c output.c:267-301 with the two context fields it reads spelled out: c->chrDither8 and (c->dstFormat == AV_PIX_FMT_NV21) */
 void mi355_sws_yuv2nv12cX(const int16_t *chrFilter, int chrFilterSize, const int16_t **chrUSrc, const int16_t **chrVSrc, uint8_t *dest, int chrDstW,
                           const uint8_t *chrDither, int swap_uv);

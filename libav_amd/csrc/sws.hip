@@ -3,7 +3,8 @@
  * little-endian samples above 8: hScale16To15_c swscale.c:110-130 in place of hScale8To15_c), 8-bit NV12 / NV21 and packed rgb24 / bgr24 sources -> rgb24,
  * -> 8-bit yuv420p / yuv422p / yuv444p and -> NV12 / NV21 (dithered from a deeper source, swscale.c:553-556), the unscaled 8-bit
  * yuv420p -> NV12 / NV21 packer and the unscaled NV12 / NV21 -> yuv420p splitter; to the YUV destinations also with range conversion between the two
- * passes (yuvj420p <-> yuv420p and their kin: lumConvertRange / chrConvertRange swscale.c:168-198).  This file:
+ * passes (yuvj420p <-> yuv420p and their kin: lumConvertRange / chrConvertRange swscale.c:168-198), and to the three planar destinations at 9 or
+ * 10 bits (yuv420p9le ... yuv444p10le: yuv2planeX_10 / yuv2plane1_10 output.c:183-213; their tile instances are launched from sws_deep.hip).  This file:
  * the context, the plan (which kernel a context gets) and the entry points of include/mi355_sws.h.  The device side is sws_dev.h:
  * k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1, k_sws_nv12_pack, k_sws_nv12_split and the k_sws_line_* kernels of the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
@@ -100,6 +101,8 @@ static mi355_sws_ctx *ctx_new(const mi355_sws_desc *desc)
     h.chrDstH = h.dstH;
     h.depth = 8; h.src_hsub = h.src_vsub = 1; h.src_layout = MI355_SWS_SRC_PLANAR;
     std::memset(h.dither, 64, sizeof(h.dither));
+    h.dst_bits = 8;
+    h.v1_rnd = h.v1_sh = h.vx_rnd = h.vx_sh = 0;
     return c;
 }
 /* the source side of a context (mi355_sws_create_src); false for a combination outside 8 / 9 / 10 bit 4:2:0 / 4:2:2 / 4:4:4 or a descriptor
@@ -186,7 +189,7 @@ static SwsRangeMap range_map(int range, bool chroma)
 /* what the create entry points share: the source check, the destination family (rgb24, or planar: dst_format MI355_SWS_DST_*), the bank
  * validation with its diagnostics.  The unscaled special converter (rgb24) and the unscaled packer (NV12 / NV21) have no banks. */
 static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src *src, bool planar, int dst_format, const char *who, int layout = MI355_SWS_SRC_PLANAR,
-                                 int range = MI355_SWS_RANGE_NONE)
+                                 int range = MI355_SWS_RANGE_NONE, int dst_depth = 8)
 {
     const bool semi = dst_format == MI355_SWS_DST_NV12 || dst_format == MI355_SWS_DST_NV21;
     if (planar && (!desc || ((dst_format < MI355_SWS_DST_YUV420P || dst_format > MI355_SWS_DST_YUV444P) && !semi))) {
@@ -197,6 +200,12 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
     SwsDev &h = c->h;
     h.range = range;
     h.rng_l = range_map(range, false); h.rng_c = range_map(range, true);      /* (read by the RANGE instances only) */
+    if (dst_depth > 8) {
+        /* yuv2plane1_10 / yuv2planeX_10 (output.c:183-213): rounding term and shift of the two forms (read by the DEEP instances only) */
+        h.dst_bits = dst_depth;
+        h.v1_rnd = 1 << (14 - dst_depth); h.v1_sh = 15 - dst_depth;
+        h.vx_rnd = 1 << (26 - dst_depth); h.vx_sh = 27 - dst_depth;
+    }
     if (src && !ctx_source(c, src)) {
         std::fprintf(stderr, "mi355dsp: %s: source %d bit, chroma shifts %d/%d (chroma %dx%d of %dx%d) is outside this backend\n", who, src->depth, src->hsub, src->vsub,
                      h.chrSrcW, h.chrSrcH, h.srcW, h.srcH);
@@ -332,6 +341,36 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range(const mi355_sws_desc
     return ctx_create(desc, src, true, dst_format, "mi355_sws_create_src_layout_range", src_layout, range);
 }
 extern "C" int mi355_sws_range(const mi355_sws_ctx *c) { return c ? c->h.range : -1; }
+extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range_depth(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format, int range,
+                                                                  int dst_depth)
+{
+    if (dst_depth == 8) return mi355_sws_create_src_layout_range(desc, src, src_layout, dst_format, range);
+    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth without mi355_init(); no CPU fallback\n"); std::abort(); }
+    if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: no descriptor\n"); return nullptr; }
+    if (dst_depth != 9 && dst_depth != 10) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: destination depth %d is not 8 / 9 / 10\n", dst_depth);
+        return nullptr;
+    }
+    if (src_layout < MI355_SWS_SRC_PLANAR || src_layout > MI355_SWS_SRC_BGR24 || src_layout == 3) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24\n", src_layout);
+        return nullptr;
+    }
+    if (dst_format < MI355_SWS_DST_YUV420P || dst_format > MI355_SWS_DST_YUV444P) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: a %d-bit destination is yuv420p / yuv422p / yuv444p (format %d)\n", dst_depth, dst_format);
+        return nullptr;
+    }
+    if (range != MI355_SWS_RANGE_NONE) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: no range conversion (%d) to a %d-bit destination\n", range, dst_depth);
+        return nullptr;
+    }
+    /* a deep destination at equal size with equal subsampling is a plane copy of the reference's (planarCopyWrapper), never its scaler */
+    if (desc->unscaled_special) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: no unscaled special converter writes a %d-bit destination\n", dst_depth);
+        return nullptr;
+    }
+    return ctx_create(desc, src, true, dst_format, "mi355_sws_create_src_layout_range_depth", src_layout, MI355_SWS_RANGE_NONE, dst_depth);
+}
+extern "C" int mi355_sws_dest_depth(const mi355_sws_ctx *c) { return c ? c->h.dst_bits : -1; }
 
 extern "C" void mi355_sws_destroy(mi355_sws_ctx *c)
 {
@@ -399,6 +438,7 @@ extern "C" int mi355_sws_destination(const mi355_sws_ctx *c, mi355_sws_dest_info
     /* ... and so does the splitter (nv12ToPlanarWrapper) */
     p->chr_bytes = !h.planar ? 0 : (semi_planar(h) ? 2 * (h.special ? h.srcW >> 1 : h.chrDstW) : (h.special ? h.srcW >> 1 : h.chrDstW));
     p->chr_rows = !h.planar ? 0 : (h.special ? h.srcH >> 1 : h.chrDstH);
+    if (h.dst_bits > 8) p->chr_bytes = 2 * h.chrDstW;       /* 16-bit samples (mi355_sws_dest_depth) */
     return 0;
 }
 
@@ -573,7 +613,9 @@ extern "C" int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *c, const mi355_s
     }
     const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
     const int i = k - MI355_SWS_K_PLANAR_A;
-    if (h.range) launch_planar_range(i, packed_rgb(h) ? 3 : (h.src_layout ? 2 : (h.depth > 8 ? 1 : 0)), semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
+    /* a 9- / 10-bit destination: the DEEP instances (three planes, no range) */
+    if (h.dst_bits > 8) mi355_sws_launch_planar_deep(i, packed_rgb(h) ? 3 : (h.src_layout ? 2 : (h.depth > 8 ? 1 : 0)), h.hshift ? 0 : 1, grid, s, c->d, d_frames);
+    else if (h.range) launch_planar_range(i, packed_rgb(h) ? 3 : (h.src_layout ? 2 : (h.depth > 8 ? 1 : 0)), semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
     else if (packed_rgb(h)) launch_planar_rgb(i, semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
     else if (h.src_layout) launch_planar_nv(i, semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
     else if (semi_planar(h)) {
@@ -683,6 +725,13 @@ extern "C" int mi355_sws_scale_planar(mi355_sws_ctx *c, const uint8_t *const src
     }
     /* the splitter writes (and so hands back) the rounded-down extents only */
     const int cwb = h.special ? h.srcW >> 1 : h.chrDstW, chr = h.special ? h.srcH >> 1 : h.chrDstH;
+    if (h.dst_bits > 8) {
+        /* 16-bit samples: rows of 2 * width bytes, even strides (scale_staged returns -1 for a stride below a row) */
+        for (int p = 0; p < 3; p++) if (dst_stride[p] & 1) return -1;
+        const int ow16[3] = { 2 * h.dstW, 2 * h.chrDstW, 2 * h.chrDstW }, oh16[3] = { h.dstH, h.chrDstH, h.chrDstH };
+        const int r = scale_staged(c, src, src_stride, 3, dst, dst_stride, ow16, oh16, ow16);
+        return r ? r : h.dstH;
+    }
     const int ow[3] = { h.dstW, cwb, cwb }, oh[3] = { h.dstH, chr, chr };
     const int r = scale_staged(c, src, src_stride, 3, dst, dst_stride, ow, oh, ow);
     return r ? r : h.dstH;
@@ -803,6 +852,29 @@ extern "C" void mi355_sws_yuv2planeX_8(const int16_t *filter, int filterSize, co
 extern "C" void mi355_sws_yuv2plane1_8(const int16_t *src, uint8_t *dest, int dstW, const uint8_t *dither, int offset)
 {
     plane_line(nullptr, 0, &src, dest, dstW, dither, offset);
+}
+/* yuv2planeX_9LE_c / _10LE_c and yuv2plane1_9LE_c / _10LE_c (output.c:183-236) of one line: bits 9 or 10, anything else does nothing */
+static void plane_line16(const int16_t *filter, int fs, const int16_t **rows, uint16_t *dest, int dstW, int bits)
+{
+    if ((bits != 9 && bits != 10) || dstW <= 0) return;
+    Arena &a = arena();
+    const int n = fs ? fs : 1, pitch = (dstW + 7) & ~7;
+    a.reserve((size_t)n * pitch * 2 + (size_t)n * 2 + (size_t)dstW * 2 + 128);
+    const size_t o_r = pack_rows(a, rows, n, dstW, pitch), o_f = a.take((size_t)n * 2), o_d = a.take((size_t)dstW * 2);
+    if (fs) std::memcpy(a.h<int16_t>(o_f), filter, (size_t)fs * 2);
+    a.upload();
+    launch_line(k_sws_line_plane16, a, a.d<const int16_t>(o_f), fs, a.d<const int16_t>(o_r), pitch, a.d<uint16_t>(o_d), dstW, bits);
+    a.download();
+    std::memcpy(dest, a.h<uint16_t>(o_d), (size_t)dstW * 2);
+}
+extern "C" void mi355_sws_yuv2planeX_nbps(const int16_t *filter, int filterSize, const int16_t **src, uint16_t *dest, int dstW, int bits)
+{
+    if (filterSize < 1) return;
+    plane_line16(filter, filterSize, src, dest, dstW, bits);
+}
+extern "C" void mi355_sws_yuv2plane1_nbps(const int16_t *src, uint16_t *dest, int dstW, int bits)
+{
+    plane_line16(nullptr, 0, &src, dest, dstW, bits);
 }
 
 extern "C" void mi355_sws_yuv2nv12cX(const int16_t *chrFilter, int chrFilterSize, const int16_t **chrUSrc, const int16_t **chrVSrc, uint8_t *dest, int chrDstW,

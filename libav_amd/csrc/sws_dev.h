@@ -17,7 +17,8 @@
  * as long, so is their LDS) and, for planar destinations, in the dither rows.  The NV instances of the tile kernels and of k_sws_ident1 read
  * an NV12 / NV21 source: both chroma planes from one pass over its plane of byte pairs (hscale_tile_nv).  The RGB instances of the tile kernels
  * read a packed rgb24 / bgr24 source: the reference's input converters in front of the 8-bit horizontal pass (hscale_tile_rgb).  The RANGE
- * instances of k_sws_planar convert the range of the int16 lines between the two passes (lumConvertRange / chrConvertRange: range_lines).
+ * instances of k_sws_planar convert the range of the int16 lines between the two passes (lumConvertRange / chrConvertRange: range_lines).  The DEEP
+ * instances of k_sws_planar write 9- or 10-bit planes of 16-bit little-endian samples (yuv2plane1_10 / yuv2planeX_10: planar_rows16).
  *   k_sws_line_*    the individual inner loops for the Tier-1 entry points.
  * Execution model: 256-thread workgroups (4 waves) sharing one LDS tile; integer only, no MFMA.
  */
@@ -67,6 +68,10 @@ struct SwsDev {
      * of each plane kind — (min(v, cap) * mul + add) >> shift, lumConvertRange / chrConvertRange of an 8-bit destination (swscale.c:168-198) */
     int range;
     SwsRangeMap rng_l, rng_c;
+    /* a planar destination deeper than 8 bits (mi355_sws_create_src_layout_range_depth): bits per sample (8 / 9 / 10) and, for the DEEP instances,
+     * the rounding term and the shift of the one-tap form and of the X form (yuv2plane1_10 / yuv2planeX_10, output.c:183-213) */
+    int dst_bits;
+    int v1_rnd, v1_sh, vx_rnd, vx_sh;
 };
 
 /* the context record with its bank pointers in the global address space (mi355_rt.h): what the tile kernels open with */
@@ -1328,6 +1333,85 @@ __device__ __forceinline__ void planar_pass(const int16_t *s, int lo, int maxl, 
     else planar_rows<0, GPP, NP, DITH>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, dith);
 }
 
+/* ---- planar destinations of 9 or 10 bits: yuv420p9le ... yuv444p10le -----------------------------------------------------------
+ * yuv2plane1_10_c_template / yuv2planeX_10_c_template (output.c:183-213) on the same int16 lines (a destination of 15 bits or fewer keeps the
+ * 15-bit intermediates, swscale.c:733-752): one tap (s + (1 << (14 - bits))) >> (15 - bits), the others ((1 << (26 - bits)) + sum s_j * f_j)
+ * >> (27 - bits), both clipped to 0 .. (1 << bits) - 1 and stored as uint16_t, little endian.  No dither, whatever the source's depth.
+ * The thread-to-group mapping, the reads and the tap ladder are planar_rows'; rnd / sh: the form's rounding term and shift (uniform, from
+ * SwsDev), top: (1 << bits) - 1.  A group's eight samples are four dwords: one 16-byte store where the address is a multiple of 16 and the
+ * group lies inside the plane, 2-byte stores at the right edge or on a row that is not so aligned (d0 / d1 and the strides are even). */
+template <int NTAP, int GPP, int NP>
+__device__ __forceinline__ void planar_rows16(const int16_t *s, int lo, int maxl, const int16_t *vC, const int32_t *vP, int fs, int row0, int nrows,
+                                              int gx0, int width, uint8_t *d0, int st0, uint8_t *d1, int st1, int tid, int rnd, int sh, int top)
+{
+    constexpr int G = GPP * NP;                        /* groups per LDS line */
+    for (int t = tid; t < nrows * G; t += NT) {
+        const int r = t / G, g = t % G, gx = gx0 + 8 * (g % GPP), y = row0 + r;
+        if (gx >= width) continue;
+        const int first = imax(1 - fs, vP[y]);
+        const int16_t *col = s + 8 * g;
+        auto line = [&](int j) { return *reinterpret_cast<const sws_u32x4 *>(col + (size_t)(clampi(first + j, 0, maxl) - lo) * (G * 8)); };
+        int v[8];
+        if (NTAP == 1) {
+            const sws_u32x4 a = line(0);
+#pragma unroll
+            for (int k = 0; k < 8; k++) v[k] = lane16(a, k) + rnd;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++) v[k] = rnd;
+            if (NTAP == 0) {
+                for (int j = 0; j < fs; j++) {
+                    const int f = vC[(size_t)y * fs + j];
+                    const sws_u32x4 a = line(j);
+#pragma unroll
+                    for (int k = 0; k < 8; k++) v[k] += lane16(a, k) * f;
+                }
+            } else {
+                constexpr int N = NTAP > 1 ? NTAP : 2;
+                int lf[N];
+#pragma unroll
+                for (int j = 0; j < N; j++) lf[j] = vC[(size_t)y * fs + (j < fs ? j : 0)];   /* unconditional: in flight together */
+#pragma unroll
+                for (int j = 0; j < N; j += 2) {
+                    const sws_u32x4 la = line(j < fs ? j : 0), lb = line(j + 1 < fs ? j + 1 : 0);
+                    const uint32_t cp = (j < fs ? (uint32_t)lf[j] & 0xFFFFu : 0u) | (j + 1 < fs ? (uint32_t)lf[j + 1] << 16 : 0u);
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        v[2 * q] = sws_dot2(sws_lo2(la[q], lb[q]), cp, v[2 * q]);
+                        v[2 * q + 1] = sws_dot2(sws_hi2(la[q], lb[q]), cp, v[2 * q + 1]);
+                    }
+                }
+            }
+        }
+        /* the clipped samples pass sws_opaque before they are packed, as in planar_rows: nothing fuses the clip of one sample with the
+         * packing of its neighbour */
+        sws_u32x4 o;
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            o[q] = sws_opaque((uint32_t)clampi(v[2 * q] >> sh, 0, top)) | (sws_opaque((uint32_t)clampi(v[2 * q + 1] >> sh, 0, top)) << 16);
+        const bool second = NP > 1 && g >= GPP;
+        uint8_t *d = (second ? d1 : d0) + (size_t)r * (second ? st1 : st0) + 2 * gx;
+        if (gx + 8 <= width && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
+            *reinterpret_cast<sws_u32x4 *>(d) = o;
+        } else {                                       /* the plane's right edge, or a row that is not 16-byte aligned */
+            const int n = imin(8, width - gx);
+            for (int k = 0; k < n; k++) reinterpret_cast<uint16_t *>(d)[k] = (uint16_t)(o[k >> 1] >> (16 * (k & 1)));
+        }
+    }
+}
+/* the vertical pass of one LDS tile to a 9- / 10-bit plane: the form's constants, its tap count rounded up as planar_pass does */
+template <int GPP, int NP>
+__device__ __forceinline__ void planar_pass16(const SwsDev &c, const int16_t *s, int lo, int maxl, const int16_t *vC, const int32_t *vP, int fs, int row0, int nrows,
+                                              int gx0, int width, uint8_t *d0, int st0, uint8_t *d1, int st1, int tid)
+{
+    const int top = (1 << c.dst_bits) - 1;
+    if (fs == 1) planar_rows16<1, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, c.v1_rnd, c.v1_sh, top);
+    else if (fs <= 2) planar_rows16<2, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, c.vx_rnd, c.vx_sh, top);
+    else if (fs <= 4) planar_rows16<4, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, c.vx_rnd, c.vx_sh, top);
+    else if (fs <= 8) planar_rows16<8, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, c.vx_rnd, c.vx_sh, top);
+    else planar_rows16<0, GPP, NP>(s, lo, maxl, vC, vP, fs, row0, nrows, gx0, width, d0, st0, d1, st1, tid, c.vx_rnd, c.vx_sh, top);
+}
+
 /* ---- semi-planar destinations: NV12 / NV21 (yuv2nv12cX_c, output.c:267-301) ------------------------------------------------------
  * The chroma rows of a 4:2:0 destination as ONE plane of U V (NV21: V U) byte pairs.  Always the X form, also for a one-tap bank:
  * ((dither << 12) + sum s_j * f_j) >> 19 with the coefficient — (s + d) >> 7 only while it is 4096.  U takes dither column i & 7, V
@@ -1464,8 +1548,10 @@ __device__ __forceinline__ void range_lines(int16_t *lines, int nvec, const SwsR
  * NV: an NV12 / NV21 source, as k_sws_generic's — U | V of an LDS line from one pass over fr.src[1].
  * RGB: a packed rgb24 / bgr24 source, as k_sws_generic's — luma and U | V from fr.src[0].
  * RANGE: a context whose source and destination differ in range — the int16 samples the horizontal pass left in s_lum / s_chr go through
- * c.rng_l / c.rng_c before the vertical pass reads them (range_lines: the direction is the constants, the same for the whole grid). */
-template <int LCAP, int CCAP, int CW, typename ST = uint8_t, bool SEMI = false, bool NV = false, bool RGB = false, bool RANGE = false>
+ * c.rng_l / c.rng_c before the vertical pass reads them (range_lines: the direction is the constants, the same for the whole grid).
+ * DEEP: a three-plane destination of c.dst_bits = 9 or 10 bits — everything up to the barrier is the source form's code, the vertical pass is
+ * planar_pass16 (no dither, 16-bit samples; dst pointers and strides stay bytes).  No SEMI and no RANGE instance is DEEP. */
+template <int LCAP, int CCAP, int CW, typename ST = uint8_t, bool SEMI = false, bool NV = false, bool RGB = false, bool RANGE = false, bool DEEP = false>
 #ifndef MI355_HIP_EMU_H
 __attribute__((amdgpu_waves_per_eu(sws_planar_waves(LCAP, CCAP, CW, stage_bytes<ST>()), sws_planar_waves(LCAP, CCAP, CW, stage_bytes<ST>()))))
 #endif
@@ -1521,6 +1607,15 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
         range_lines(&s_chr[0][0], nchr * (2 * CW / 8), c.rng_c, tid);
         __syncthreads();
     }
+    if constexpr (DEEP) {
+        static_assert(!SEMI && !RANGE, "a deep destination is three planes of one range");
+        planar_pass16<TW / 8, 1>(c, &s_lum[0][0], llo, c.srcH - 1, c.vLumC, c.vLumP, ls, y0, y1 - y0 + 1, x0, c.dstW,
+                                 fr.dst[0] + (size_t)y0 * fr.dst_stride[0], fr.dst_stride[0], nullptr, 0, tid);
+        if (cy0 <= cy1)
+            planar_pass16<CW / 8, 2>(c, &s_chr[0][0], clo, c.chrSrcH - 1, c.vChrC, c.vChrP, cs, cy0, cy1 - cy0 + 1, x0 >> hs, c.chrDstW,
+                                     fr.dst[1] + (size_t)cy0 * fr.dst_stride[1], fr.dst_stride[1], fr.dst[2] + (size_t)cy0 * fr.dst_stride[2], fr.dst_stride[2], tid);
+        return;
+    }
     const uint8_t (*dith)[8] = DITH ? mi355_global(cp)->dither : nullptr;
     planar_pass<TW / 8, 1, DITH>(&s_lum[0][0], llo, c.srcH - 1, c.vLumC, c.vLumP, ls, y0, y1 - y0 + 1, x0, c.dstW,
                                  fr.dst[0] + (size_t)y0 * fr.dst_stride[0], fr.dst_stride[0], nullptr, 0, tid, dith);
@@ -1536,6 +1631,9 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
                                      fr.dst[1] + (size_t)cy0 * fr.dst_stride[1], fr.dst_stride[1], fr.dst[2] + (size_t)cy0 * fr.dst_stride[2], fr.dst_stride[2], tid, dith);
 }
 
+/* MI355_SWS_TILE_KERNELS_ONLY (sws_deep.hip): the kernels that are no templates — the packer, the splitter, the line kernels — are sws.hip's
+ * alone; a second file would emit a copy of each */
+#ifndef MI355_SWS_TILE_KERNELS_ONLY
 /* ---- the unscaled packer: 8-bit yuv420p -> NV12 / NV21 at equal size (planarToNv12Wrapper, swscale_unscaled.c:138-156) -------------
  * srcW x srcH luma bytes copied (copyPlane), srcW / 2 pairs on srcH / 2 rows interleaved (interleaveBytes_c, rgb2rgb_template.c:693-709) —
  * both divisions round down: the last pair of an odd width's chroma rows and the last chroma row of an odd height are neither read nor
@@ -1660,6 +1758,7 @@ __global__ void __launch_bounds__(NT) k_sws_nv12_split(int srcW, int srcH, int s
         }
     }
 }
+#endif
 
 constexpr int C24_ROWS = 16, C24_COLS = 512, IDENT_ROWS = 16;      /* rows of a tile of k_sws_c24 / of k_sws_ident1 */
 /* eight samples of one line: Y bytes in (y0, y1), the four pairs' LUT row offsets in r/g/b -> 24 RGB bytes */
@@ -1878,6 +1977,7 @@ __global__ void __launch_bounds__(NT) k_sws_line_hscale(int16_t *dst, int dstW, 
 {
     for (int i = threadIdx.x; i < dstW; i += NT) dst[i] = (int16_t)hscale_one<ST>(src, filter + (size_t)i * fs, pos[i], fs, sh);
 }
+#ifndef MI355_SWS_TILE_KERNELS_ONLY
 /* rgb24ToY_c / bgr24ToY_c and the ...ToUV_c / ...ToUV_half_c pairs (input.c:539-623) of one line: one sample per thread and step */
 __global__ void __launch_bounds__(NT) k_sws_line_rgb24_y(uint8_t *dst, const uint8_t *src, int width, int bgr)
 {
@@ -1913,6 +2013,17 @@ __global__ void __launch_bounds__(NT) k_sws_line_plane(const int16_t *filter, in
         dest[i] = (uint8_t)clip_u8(val >> 19);
     }
 }
+/* yuv2planeX_10_c_template output.c:196-213 (fs >= 1 rows at `pitch` elements) / yuv2plane1_10_c_template :183-194 (fs == 0), little endian */
+__global__ void __launch_bounds__(NT) k_sws_line_plane16(const int16_t *filter, int fs, const int16_t *rows, int pitch, uint16_t *dest, int dstW, int bits)
+{
+    const int top = (1 << bits) - 1;
+    for (int i = threadIdx.x; i < dstW; i += NT) {
+        if (fs == 0) { dest[i] = (uint16_t)clampi((rows[i] + (1 << (14 - bits))) >> (15 - bits), 0, top); continue; }
+        int val = 1 << (26 - bits);
+        for (int j = 0; j < fs; j++) val += rows[(size_t)j * pitch + i] * filter[j];
+        dest[i] = (uint16_t)clampi(val >> (27 - bits), 0, top);
+    }
+}
 /* yuv2nv12cX_c output.c:267-301: fs >= 1 rows of U and of V at `pitch` elements, the pairs in U V (swap_uv: V U) order */
 __global__ void __launch_bounds__(NT) k_sws_line_nv12(const int16_t *filter, int fs, const int16_t *urows, const int16_t *vrows, int pitch, uint8_t *dest,
                                                       int chrDstW, const uint8_t *dither, int swap_uv)
@@ -1941,6 +2052,12 @@ __global__ void __launch_bounds__(NT) k_sws_line_rgb(const mi355_sws_luts *luts,
     PackedRows R{ l, u, v, pitch };
     for (int i = threadIdx.x; i < ((dstW + 1) >> 1); i += NT) rgb_pair(s_lut, dest + (size_t)i * 6, R, i, mode, lumF, ls, chrF, cs, yalpha, uvalpha);
 }
+#endif
 }  // namespace
+
+/* sws_deep.hip: the launch of the DEEP instance of k_sws_planar for a context (d: its SwsDev on the device) — instance i (0 / 1 / 2: A / B / C),
+ * src 0 8-bit planes, 1 16-bit planes, 2 NV12 / NV21, 3 rgb24 / bgr24, full_cw: a 4:4:4 destination (CW = TW).  The DEEP instances are compiled
+ * in a file of their own */
+void mi355_sws_launch_planar_deep(int i, int src, int full_cw, dim3 grid, hipStream_t s, const void *d, const mi355_sws_planar_frame *frames);
 
 #endif

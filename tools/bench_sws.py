@@ -45,6 +45,11 @@ def main():
                          "1080p rgb24 -> yuvj420p; the partner a second time in another allocation (A/A), with --other-lib also on that build, and the "
                          "reference's single-thread sws_scale(); 32 and 512 pictures per launch, 3 warm-up + --steps launches a round, alternating, "
                          "median of 3 rounds")
+    ap.add_argument("--deepdst", action="store_true",
+                    help="10-bit planar destinations (mi355_sws_create_src_layout_range_depth) beside THE SAME descriptor created with depth 8 on the same "
+                         "build — identical banks and source traffic, half the destination bytes: 2160p -> 1080p yuv420p10le and 1080p 4:2:0 -> "
+                         "yuv422p10le at equal size, each from yuv420p10le, yuv420p and nv12; the twin a second time in another allocation (A/A); 32 "
+                         "and 512 pictures per launch, 3 warm-up + --steps launches a round, alternating, median of 3 rounds")
     ap.add_argument("--other-lib", default=None,
                     help="--nv12 / --nvsrc / --rgbsrc / --range: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
     ap.add_argument("--rounds", type=int, default=5, help="--planar / --sources: alternating rounds (the median is reported)")
@@ -65,6 +70,8 @@ def main():
         return rgbsrc(a, lib)
     if a.range:
         return range_points(a, lib)
+    if a.deepdst:
+        return deepdst_points(a, lib)
     orc = S.oracle_backend(providers.oracle())
     for name in a.configs.split(","):
         ctx = S.load_context(name)
@@ -626,6 +633,52 @@ def range_points(a, lib):
                                   "vs_range0": ms / base - 1.0, "kernel": plan["kernel"], "hstaged": plan["hstaged"], "range": plan["range"] if k == "ranged@this" else 0,
                                   "reference_sws_scale_frames_per_s_1core": cpu[point], "ms_rounds": [round(x, 4) for x in times[k]]}), flush=True)
             for l, b in batches.values():
+                b.close()
+
+
+def deepdst_points(a, lib, points=None, frame_counts=(32, 512)):
+    """A 10-bit planar destination beside its twin: the same descriptor created with depth 8 on the same build has identical banks and source
+    traffic and writes half the destination bytes.  The contexts come from the reference's libswscale at run time (oracle/_ref/libswsref.so:
+    mi355_sws_describe_depth) — no full-size context is committed.  `depth8#2` is the twin a second time with its own buffers: the session's
+    A/A spread.  One process, the batches of a point alternating: 3 warm-up + --steps launches a round, median of 3 rounds, at 32 and 512
+    pictures per launch.  Algorithmic bytes: sources read once + destinations written once.  `bound`: the extra destination bytes over the
+    twin's algorithmic bytes — what the deep context may cost if it moves them at the twin's achieved bandwidth (the A/A spread comes on top)."""
+    import statistics
+    import sws_deepdst as D
+    import sws_planar as P
+    ref = D.Ref(P.bind(D.REF_LIB))
+    rounds = 3
+    # (point, srcW, srcH, dstW, dstH, source, destination)
+    points = points or [("uhd_to_hd_%s_to_yuv420p10le" % s, 3840, 2160, 1920, 1080, s, "yuv420p10le") for s in ("yuv420p10le", "yuv420p", "nv12")] + \
+                       [("hd_same_%s_to_yuv422p10le" % s, 1920, 1080, 1920, 1080, s, "yuv422p10le") for s in ("yuv420p10le", "yuv420p", "nv12")]
+    for frames in frame_counts:
+        for point, sw, sh, dw, dh, src, dst in points:
+            row = (sw, sh, dw, dh, src, dst, 1, 1, 1)                  # a row of tests/sws_deepdst.py's table, not entered into it
+            c = ref.open(row)
+            e = ref.describe_depth(c)
+            ref.free(c)
+            assert e is not None and e.dst_depth == D.dst_kind(row)[1], point
+            pics = [D.picture(row, "noise", seed=s) for s in (1, 2)]
+            twin = e.edited(dst_depth=8)
+            batches = {"deep": PlaneBatch(lib, D.create(lib, e), pics, e.out_sizes(), frames),
+                       "depth8": PlaneBatch(lib, D.create(lib, twin), pics, twin.out_sizes(), frames),
+                       "depth8#2": PlaneBatch(lib, D.create(lib, twin), pics, twin.out_sizes(), frames)}
+            plan = D.plan_of(lib, batches["deep"].handle)
+            times = {k: [] for k in batches}
+            for _ in range(rounds):
+                for k, b in batches.items():
+                    times[k].append(time_ms(lib, b.run, a.steps))
+            base = statistics.median(times["depth8"])
+            twin_bytes = batches["depth8"].src_bytes + batches["depth8"].dst_bytes
+            for k, b in batches.items():
+                ms = statistics.median(times[k])
+                us = ms * 1e3 / frames
+                nb = b.src_bytes + b.dst_bytes
+                print(json.dumps({"workload": point + ":" + k, "frames_per_launch": frames, "ms_per_launch": ms, "us_per_picture": us, "frames_per_s": 1e6 / us,
+                                  "algorithmic_bytes_per_frame": nb, "achieved_GBps": nb / us * 1e-3, "frac_of_8TBps": nb / us * 1e-3 / 8000.0,
+                                  "vs_depth8": ms / base - 1.0, "bound": nb / twin_bytes - 1.0, "kernel": plan["kernel"], "hstaged": plan["hstaged"],
+                                  "dst_depth": plan["dst_depth"] if k == "deep" else 8, "ms_rounds": [round(x, 4) for x in times[k]]}), flush=True)
+            for b in batches.values():
                 b.close()
 
 
