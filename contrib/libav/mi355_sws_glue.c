@@ -66,6 +66,13 @@
  *                          mi355_sws_yuv2planeX_nbps / mi355_sws_yuv2plane1_nbps.  Declined: big-endian, 12 / 14 / 16-bit, P010 and gray
  *                          destinations, the plane copies (equal size with equal subsampling: planarCopyWrapper, no banks) and a deep
  *                          destination with range converters.  The five describers above keep declining a destination deeper than 8 bits.
+ *   bgr24 / 32-bit RGB     destinations bgr24, rgba, bgra, argb and abgr, from every source above, where the reference runs its generic scaler or
+ *                          the unscaled special converter (yuv2rgb_c_24_bgr / yuv2rgb_c_32) take the same two forms through
+ *                          mi355_sws_describe_packed() / mi355_sws_create_src_layout_range_depth(); the format is remembered beside the layout and
+ *                          read again on every call, and the tables are compared in the form the device context was built from.  With
+ *                          MI355_SWS_LINES=1 c->yuv2packedX / 2 / 1 go to mi355_sws_yuv2packed_X / _2 / _1.  Declined: SWS_FULL_CHR_H_INT,
+ *                          SWS_FAST_BILINEAR, a source with alpha, 15 / 16-bit and lower RGB, rgb48 / rgba64, planar GBR, rgbToRgbWrapper.  The six
+ *                          describers above keep declining these destinations; this one declines rgb24.
  * The device is MI355_DEVICE (default 0), as for the decoder bridges.
  */
 #include <pthread.h>
@@ -183,7 +190,23 @@ static int source_of(const SwsContext *c, mi355_sws_src *s)
  * ranged == MI355_ASK_DEEP (mi355_sws_describe_depth alone): the destination is one of the six 9- / 10-bit planar formats instead of the 8-bit
  * ones, and there is no range */
 #define MI355_ASK_DEEP 2
+/* ranged == MI355_ASK_PACKED (mi355_sws_describe_packed alone): the destination is bgr24 or one of the four 32-bit orders instead; no range either (an
+ * RGB destination takes it into its tables) */
+#define MI355_ASK_PACKED 3
 static int generic_dst_r(const SwsContext *c, int ranged);
+/* the MI355_SWS_DST_* of a packed destination beside rgb24, 0 for any other format.  The reference's RGB32 / BGR32 / RGB32_1 / BGR32_1 are
+ * host-endian aliases of the four byte-order names: resolved here, once */
+static int packed_dst_of(const SwsContext *c)
+{
+    switch (c->dstFormat) {
+    case AV_PIX_FMT_BGR24: return MI355_SWS_DST_BGR24;
+    case AV_PIX_FMT_RGBA:  return MI355_SWS_DST_RGBA;
+    case AV_PIX_FMT_BGRA:  return MI355_SWS_DST_BGRA;
+    case AV_PIX_FMT_ARGB:  return MI355_SWS_DST_ARGB;
+    case AV_PIX_FMT_ABGR:  return MI355_SWS_DST_ABGR;
+    default: return 0;
+    }
+}
 /* the MI355_SWS_DST_* and the depth of a 9- / 10-bit little-endian planar destination, 0 for any other format (big endian, 12 / 14 / 16 bits,
  * P010, gray: not ours) */
 static int deep_dst(const SwsContext *c, int *depth)
@@ -204,6 +227,8 @@ static int src_format_r(const SwsContext *c, mi355_sws_src *s, int special, int 
     if (c->lumToYV12 || c->chrToYV12 || c->readLumPlanar || c->readChrPlanar || c->alpToYV12 || c->readAlpPlanar) return -1;      /* an input converter */
     if (special && (c->dstFormat == AV_PIX_FMT_NV12 || c->dstFormat == AV_PIX_FMT_NV21))          /* the packer: planarToNv12Wrapper */
         return c->srcFormat == AV_PIX_FMT_YUV420P ? (c->dstFormat == AV_PIX_FMT_NV12 ? MI355_SWS_DST_NV12 : MI355_SWS_DST_NV21) : -1;
+    if (special && ranged == MI355_ASK_PACKED)                    /* yuv2rgb_c_24_bgr / yuv2rgb_c_32: where rgb24 has yuv2rgb_c_24_rgb */
+        return packed_dst_of(c) && s->depth == 8 && s->hsub == 1 ? packed_dst_of(c) : -1;
     if (special) return c->dstFormat == AV_PIX_FMT_RGB24 && s->depth == 8 && s->hsub == 1 ? 0 : -1;
     return generic_dst_r(c, ranged);
 }
@@ -212,9 +237,10 @@ static int generic_dst_r(const SwsContext *c, int ranged)
 {
     /* the generic scaler: no fast bilinear, no range conversion (unless asked for), no chroma line drop, and its four banks (an unscaled
      * converter or a plane copy has none, utils.c:1043-1048) */
-    const int deep = ranged == MI355_ASK_DEEP;
-    if (c->hyscale_fast || c->hcscale_fast || ((!ranged || deep) && (c->lumConvertRange || c->chrConvertRange)) || c->vChrDrop) return -1;
+    const int deep = ranged == MI355_ASK_DEEP, packed = ranged == MI355_ASK_PACKED;
+    if (c->hyscale_fast || c->hcscale_fast || ((!ranged || deep || packed) && (c->lumConvertRange || c->chrConvertRange)) || c->vChrDrop) return -1;
     if (!c->vLumFilter || !c->vChrFilter || !c->hLumFilter || !c->hChrFilter) return -1;
+    if (packed) return packed_dst_of(c) && !isALPHA(c->srcFormat) ? packed_dst_of(c) : -1;
     if (deep) {
         int bits;
         const int fmt = deep_dst(c, &bits);
@@ -384,6 +410,46 @@ int mi355_sws_describe_depth(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_
     return 0;
 }
 
+/* ---- packed destinations beside rgb24: bgr24, rgba, bgra, argb, abgr -----------------------------------------------------------------------
+ * The tables of such a context in the form of mi355_sws_luts.  bgr24 has the 24-bpp tables (yuv2rgb.c:850-863): luts_of().  A 32-bit order has one
+ * uint32_t table of three planes (:864-888): entry i of the r plane holds the clipped value of the 24-bpp table shifted into the r lane (plus 255
+ * in the alpha lane, a source without alpha), the g and b planes the same value in their lanes, 1024 and 2048 ELEMENTS up; fill_table gives the three
+ * pointer rows the same element offsets into their planes, fill_gv_table a byte offset of four bytes an element.  So y_table[i] is the r lane of
+ * entry i and the offset rows are the pointers' element offsets with the plane bases removed */
+static void luts_packed(const SwsContext *c, int fmt, mi355_sws_luts *t)
+{
+    if (fmt == MI355_SWS_DST_BGR24) { luts_of(c, t); return; }
+    const uint32_t *y32 = c->yuvTable;
+    /* rbase of :865-867: base 8 for the two orders with alpha in the low byte of the host's dword, r above b for RGB32 / RGB32_1 */
+    const int base = c->dstFormat == AV_PIX_FMT_RGB32_1 || c->dstFormat == AV_PIX_FMT_BGR32_1 ? 8 : 0;
+    const int rbase = base + (c->dstFormat == AV_PIX_FMT_RGB32 || c->dstFormat == AV_PIX_FMT_RGB32_1 ? 16 : 0);
+    for (int i = 0; i < 1024; i++) t->y_table[i] = (uint8_t)(y32[i] >> rbase);
+    for (int i = 0; i < 256; i++) {
+        t->rV[i] = (const uint32_t *)c->table_rV[i] - y32;
+        t->gU[i] = (const uint32_t *)c->table_gU[i] - y32 - 1024;
+        t->gV[i] = c->table_gV[i] / 4;
+        t->bU[i] = (const uint32_t *)c->table_bU[i] - y32 - 2048;
+    }
+}
+/* what mi355_sws_create_src_layout_range_depth (range 0, depth 8) takes for a live context to one of the five formats (0), -1 for every other
+ * context — rgb24 included: that is mi355_sws_describe_fmt's.  The generic scaler's contexts under the conditions of the rgb24 ones (no
+ * SWS_FULL_CHR_H_INT, no SWS_FAST_BILINEAR, a source without alpha, the four banks); a context without the vertical banks is the unscaled special
+ * converter where ff_yuv2rgb_get_func_ptr gave yuv2rgb_c_24_bgr / yuv2rgb_c_32 (swscale_unscaled.c:1051-1055: 8-bit yuv420p / yuv422p at equal size,
+ * an even height, no SWS_ACCURATE_RND); any other without them (rgbToRgbWrapper, a copy) is declined */
+int mi355_sws_describe_packed(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *src_layout, int *dst_format)
+{
+    const int fmt = packed_dst_of(c);
+    if (!fmt) return -1;
+    if (!c->vLumFilter) {
+        if ((c->flags & SWS_ACCURATE_RND) || (c->dstH & 1) || c->srcW != c->dstW || c->srcH != c->dstH ||
+            (c->srcFormat != AV_PIX_FMT_YUV420P && c->srcFormat != AV_PIX_FMT_YUV422P)) return -1;
+        *src_layout = MI355_SWS_SRC_PLANAR;
+        if (describe_src_r(c, d, s, dst_format, 1, MI355_ASK_PACKED) != 0 || *dst_format != fmt) return -1;
+    } else if (describe_fmt_r(c, d, s, src_layout, dst_format, MI355_ASK_PACKED) != 0 || *dst_format != fmt) return -1;
+    luts_packed(c, fmt, &d->luts);
+    return 0;
+}
+
 #ifndef MI355_SWS_DESCRIBE_ONLY
 static void t1_hscale16(SwsContext *c, int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
 {
@@ -418,6 +484,36 @@ static void t1_packed1(SwsContext *c, const int16_t *lumSrc, const int16_t *chrU
     (void)alpSrc; (void)y; n_calls++;
     luts_of(c, &t);
     mi355_sws_yuv2rgb24_1(&t, lumSrc, chrUSrc, chrVSrc, dest, dstW, uvalpha);
+}
+
+/* yuv2packedX / 2 / 1 of a bgr24 or 32-bit context (yuv2bgr24_X_c ..., yuv2rgbx32_X_c ... and their _2 / _1 forms): the format and the tables are read
+ * from the context at every call, as the rgb24 shims read theirs */
+static void t1_pkX(SwsContext *c, const int16_t *lumFilter, const int16_t **lumSrc, int lumFilterSize, const int16_t *chrFilter,
+                   const int16_t **chrUSrc, const int16_t **chrVSrc, int chrFilterSize, const int16_t **alpSrc, uint8_t *dest, int dstW, int y)
+{
+    mi355_sws_luts t;
+    const int fmt = packed_dst_of(c);
+    (void)alpSrc; (void)y; n_calls++;
+    luts_packed(c, fmt, &t);
+    mi355_sws_yuv2packed_X(&t, fmt, lumFilter, lumSrc, lumFilterSize, chrFilter, chrUSrc, chrVSrc, chrFilterSize, dest, dstW);
+}
+static void t1_pk2(SwsContext *c, const int16_t *lumSrc[2], const int16_t *chrUSrc[2], const int16_t *chrVSrc[2], const int16_t *alpSrc[2],
+                   uint8_t *dest, int dstW, int yalpha, int uvalpha, int y)
+{
+    mi355_sws_luts t;
+    const int fmt = packed_dst_of(c);
+    (void)alpSrc; (void)y; n_calls++;
+    luts_packed(c, fmt, &t);
+    mi355_sws_yuv2packed_2(&t, fmt, lumSrc, chrUSrc, chrVSrc, dest, dstW, yalpha, uvalpha);
+}
+static void t1_pk1(SwsContext *c, const int16_t *lumSrc, const int16_t *chrUSrc[2], const int16_t *chrVSrc[2], const int16_t *alpSrc,
+                   uint8_t *dest, int dstW, int uvalpha, int y)
+{
+    mi355_sws_luts t;
+    const int fmt = packed_dst_of(c);
+    (void)alpSrc; (void)y; n_calls++;
+    luts_packed(c, fmt, &t);
+    mi355_sws_yuv2packed_1(&t, fmt, lumSrc, chrUSrc, chrVSrc, dest, dstW, uvalpha);
 }
 
 static int device_ready(void)
@@ -510,6 +606,16 @@ void ff_sws_init_mi355x(SwsContext *c)
         c->yuv2plane1 = bits == 9 ? t1_plane1_9 : t1_plane1_10;
         return;
     }
+    /* bgr24 / rgba / bgra / argb / abgr: the horizontal loops as above, the three packed loops of the format */
+    if (fmt < 0 && !range && packed_dst_of(c) && fmt_format_r(c, &s, 0, &layout, MI355_ASK_PACKED) > 0) {
+        if (!device_ready() || !c->hyScale || !c->hcScale || !c->yuv2packedX || !c->yuv2packed2 || !c->yuv2packed1) return;
+        rgb_converters(c, layout);
+        c->hyScale = c->hcScale = s.depth > 8 ? t1_hscale16 : t1_hscale;
+        c->yuv2packedX = t1_pkX;
+        c->yuv2packed2 = t1_pk2;
+        c->yuv2packed1 = t1_pk1;
+        return;
+    }
     /* rgb24: yuv420p as before (taken(): also contexts with range conversion, which swscale() applies between the loops); the other sources
      * where src_format() takes them */
     if (!(taken(c) || fmt == 0) || c->hyscale_fast) return;
@@ -535,6 +641,7 @@ typedef struct Bound {
     int layout;                   /* ... its MI355_SWS_SRC_* (NV12 / NV21: two source planes) */
     int range;                    /* ... the MI355_SWS_RANGE_* its converters gave when it was bound (mi355_sws_describe_range / mi355_sws_create_src_layout_range) */
     int depth;                    /* ... the bits of its planar destination: 8, or 9 / 10 (mi355_sws_describe_depth / mi355_sws_create_src_layout_range_depth) */
+    int packed;                   /* ... MI355_SWS_DST_BGR24 ... _ABGR of a packed destination beside rgb24 (mi355_sws_describe_packed), else 0; planar is 0 then */
     mi355_sws_ctx *dev;
     int failed;                   /* the device side does not take this context: the reference's function from now on */
     int busy;                     /* calls of mi355_sws_scale in flight on `dev` (under bound_mu): the device context is destroyed only at 0 */
@@ -581,7 +688,7 @@ static Bound *bound_find(SwsContext *c, int create)
 /* a selector runs for this context: sws_init_context() of a new context — possibly at the address of one that was freed */
 static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
 {
-    int planar = special ? 0 : planar_format(c), other = 0, layout = MI355_SWS_SRC_PLANAR, range = MI355_SWS_RANGE_NONE, depth = 8;
+    int planar = special ? 0 : planar_format(c), other = 0, layout = MI355_SWS_SRC_PLANAR, range = MI355_SWS_RANGE_NONE, depth = 8, packed = 0;
     if (!(taken(c) || planar)) {
         mi355_sws_src s;
         int fmt = fmt_format(c, &s, special, &layout);
@@ -594,6 +701,12 @@ static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
             fmt = c->dstBpc == depth ? fmt_format_r(c, &s, 0, &layout, MI355_ASK_DEEP) : -1;
             if (fmt == 0) fmt = -1;
         } else range = MI355_SWS_RANGE_NONE;
+        if (fmt < 0 && range <= 0 && packed_dst_of(c)) {
+            /* bgr24 or a 32-bit order: the generic scaler, or (special) yuv2rgb_c_24_bgr / yuv2rgb_c_32 */
+            range = MI355_SWS_RANGE_NONE; depth = 8;
+            packed = fmt_format_r(c, &s, special, &layout, MI355_ASK_PACKED);
+            if (packed > 0) fmt = 0; else packed = 0;
+        }
         if (fmt < 0) return real;
         other = 1; planar = fmt;
     }
@@ -603,6 +716,7 @@ static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
     if (b) {
         slot_release(b);
         b->c = c; b->real = real; b->special = special; b->planar = planar; b->other = other; b->layout = layout; b->range = range; b->depth = depth;
+        b->packed = packed;
         b->stamp = ++n_stamp;
     }
     pthread_mutex_unlock(&bound_mu);
@@ -629,15 +743,29 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
                           (!b->range || range_probe(c) == b->range) &&
                           (b->depth <= 8 || (deep_dst(c, &d_now) == b->planar && d_now == b->depth));   /* (with converters set since: the reference's) */
     /* an rgb24 context of another source: range conversion set since it was bound is the reference's for that picture, as above */
-    const int other_ok = !b || !b->other || b->planar || fmt_format(c, &s_now, b->special, &l_now) == 0;
+    const int other_ok = !b || !b->other || b->planar || (b->packed ? fmt_format_r(c, &s_now, b->special, &l_now, MI355_ASK_PACKED) == b->packed
+                                                                     : fmt_format(c, &s_now, b->special, &l_now) == 0);
     /* an NV12 / NV21 source has two planes: srcStride[2] is not looked at; a packed rgb24 / bgr24 source has one */
     const int one_plane = b && (b->layout == MI355_SWS_SRC_RGB24 || b->layout == MI355_SWS_SRC_BGR24);
     if (b && !b->failed && srcSliceY == 0 && srcSliceH == c->srcH &&
         srcStride[0] > 0 && (one_plane || srcStride[1] > 0) && (b->layout || srcStride[2] > 0) && dstStride[0] > 0 && (!b->planar || planar_ok) && other_ok) {
-        if (b->dev && !b->busy && !b->planar && (memcmp(b->y_table, c->yuvTable, 1024) || b->gv0 != c->table_gV[0])) { mi355_sws_destroy(b->dev); b->dev = NULL; }
+        if (b->dev && !b->busy && !b->planar && !b->packed && (memcmp(b->y_table, c->yuvTable, 1024) || b->gv0 != c->table_gV[0])) { mi355_sws_destroy(b->dev); b->dev = NULL; }
+        if (b->dev && !b->busy && b->packed) {
+            /* the tables in the form the device context was built from (a 32-bit order's first 1024 table BYTES are 256 entries below every colour) */
+            mi355_sws_luts now;
+            luts_packed(c, b->packed, &now);
+            if (memcmp(b->y_table, now.y_table, 1024) || b->gv0 != c->table_gV[0]) { mi355_sws_destroy(b->dev); b->dev = NULL; }
+        }
         if (!b->dev) {
             mi355_sws_desc d;
             int fmt;
+            if (b->packed) {
+                mi355_sws_src s;
+                int layout;
+                if (device_ready() && mi355_sws_describe_packed(c, &d, &s, &layout, &fmt) == 0 && layout == b->layout && fmt == b->packed &&
+                    d.unscaled_special == b->special)
+                    b->dev = mi355_sws_create_src_layout_range_depth(&d, &s, layout, fmt, MI355_SWS_RANGE_NONE, 8);
+            } else
             if (b->other) {
                 mi355_sws_src s;
                 int layout, range = MI355_SWS_RANGE_NONE, depth = 8;
@@ -649,7 +777,8 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
             } else if (b->planar) {
                 if (device_ready() && mi355_sws_describe_planar(c, &d, &fmt) == 0) b->dev = mi355_sws_create_planar(&d, fmt);
             } else if (device_ready() && describe(c, &d, b->special) == 0) b->dev = mi355_sws_create(&d);
-            if (b->dev && !b->planar) { memcpy(b->y_table, c->yuvTable, 1024); b->gv0 = c->table_gV[0]; }
+            if (b->dev && b->packed) { memcpy(b->y_table, d.luts.y_table, 1024); b->gv0 = c->table_gV[0]; }
+            else if (b->dev && !b->planar) { memcpy(b->y_table, c->yuvTable, 1024); b->gv0 = c->table_gV[0]; }
             else if (!b->dev) b->failed = 1;
         }
         dev = b->dev;

@@ -5,7 +5,8 @@
  * NV12 / NV21 (yuv2nv12cX, and the unscaled yuv420p -> NV12 / NV21 packer); from planar sources or from NV12 / NV21 (the reference's
  * nv12ToUV_c / nv21ToUV_c in front of hcScale, and the unscaled NV12 / NV21 -> yuv420p splitter) or from packed rgb24 / bgr24 (the
  * reference's rgb24ToY_c / rgb24ToUV_c / rgb24ToUV_half_c and their bgr24 forms in front of hyScale / hcScale); the three planar
- * destinations also at 9 or 10 bits (yuv420p9le ... yuv444p10le: yuv2planeX_10 / yuv2plane1_10).
+ * destinations also at 9 or 10 bits (yuv420p9le ... yuv444p10le: yuv2planeX_10 / yuv2plane1_10); packed destinations also as bgr24 and as
+ * rgba / bgra / argb / abgr (yuv2rgb_write output.c:825-867; yuv2rgb_c_24_bgr / yuv2rgb_c_32), from every source rgb24 is written from.
  *
  * The reference keeps these behind function pointers of the (private) SwsContext
  * (libswscale/swscale_internal.h:253-540): hyScale/hcScale :526-531, yuv2plane1/yuv2planeX/
@@ -58,7 +59,7 @@ typedef struct mi355_sws_ctx mi355_sws_ctx;   /* descriptor + filter banks resid
 typedef struct mi355_sws_frame {
     const uint8_t *src[3];
     int src_stride[3];
-    uint8_t *dst;          /* packed RGB24 */
+    uint8_t *dst;          /* packed RGB24 (or bgr24 / rgba / bgra / argb / abgr: MI355_SWS_DST_BGR24 ... below) */
     int dst_stride;
 } mi355_sws_frame;
 
@@ -134,7 +135,7 @@ enum { MI355_SWS_DST_NV12 = 16, MI355_SWS_DST_NV21 = 17 };
 /* the destination side of a context (read only) */
 typedef struct mi355_sws_dest_info {
     int format;                   /* 0 rgb24, else MI355_SWS_DST_* */
-    int planes;                   /* 1 rgb24, 2 NV12 / NV21, 3 planar */
+    int planes;                   /* 1 rgb24 and the other packed destinations, 2 NV12 / NV21, 3 planar */
     int chr_bytes, chr_rows;      /* bytes per row and rows the context writes to each chroma plane (0 / 0 for rgb24; the packer: 2 * (srcW / 2), srcH / 2;
                                    * the splitter: srcW / 2, srcH / 2) */
 } mi355_sws_dest_info;
@@ -243,6 +244,33 @@ mi355_sws_ctx *mi355_sws_create_src_layout_range_depth(const mi355_sws_desc *des
                                                        int dst_depth);
 int mi355_sws_dest_depth(const mi355_sws_ctx *ctx);   /* 8 / 9 / 10, -1 bad argument */
 
+/* ---- packed destinations beside rgb24: bgr24 and the four 32-bit orders rgba / bgra / argb / abgr (yuv2rgb_write output.c:825-867 behind the three
+ * packed templates yuv2rgb_X / _2 / _1_c_template :937-1110; yuv2rgb_c_24_bgr yuv2rgb.c:366-394 and yuv2rgb_c_32 :237-265) ----
+ * The names give the byte order IN MEMORY (the reference's RGB32 / BGR32 / _1 names are host-endian aliases of these).  mi355_sws_create_src_layout_range_depth
+ * and the creators that forward to it (mi355_sws_create_src, _src_layout, _src_layout_range) take the five values as dst_format with every source the
+ * rgb24 destination takes: src_layout 0, 1, 2, 4, 5, depth 8 / 9 / 10 at 4:2:0 / 4:2:2 / 4:4:4.  The descriptor is the reference's for that context and
+ * has the form of the rgb24 one: chrDstW = AV_CEIL_RSHIFT(dstW, 1), vChr.n = dstH, and the LUTs in the form of mi355_sws_luts — for a 32-bit order
+ * y_table[i] is the colour byte of the reference's uint32_t table entry i (the same clipped value the 24-bpp table holds, yuv2rgb.c:850-888) and the
+ * four offset rows count ELEMENTS of that table with the g / b plane bases (1024 / 2048 elements) removed; the device adds 255 as the alpha byte (a
+ * source without alpha).  Such a context has the banks, the plan (GENERIC_A / B / C, IDENT1_1 / _X, C24) and the refusals of its rgb24 twin: NULL and a
+ * message for banks the device tiles cannot hold, for a packed-RGB source that scales neither way and for desc->unscaled_special from a packed or an
+ * NV source; and, as for rgb24, for a range other than 0, a dst_depth other than 8, and for values of 37 and up (4 .. 15 and 18 .. 31 stay refused).
+ * desc->unscaled_special = 1 with one of the five values is the unscaled special converter to that format: 8-bit 4:2:0 and 4:2:2 sources, exactly where
+ * rgb24 takes k_sws_c24.
+ * Frames stay mi355_sws_frame — ONE packed destination plane — through mi355_sws_scale / mi355_sws_scale_frames_dev; the planar entry points return -1.
+ * A row holds 3 * dstW or 4 * dstW bytes: exactly dstW pixels are written, as for rgb24 (the reference's pair loops also write a partner of an odd
+ * width's last pixel, from a line-buffer sample it never initialised; that pixel is not reproduced and the bytes behind the row stay untouched; the
+ * special converter writes dstW & ~1 pixels, as the reference's).  A 32-bit destination's pointer and stride must be multiples of 4 (a pixel is stored
+ * as a dword): the Tier-1 host entry returns -1 otherwise, and for a stride below the row.  A full tile (128 pixels of the tile kernel, eight of
+ * k_sws_ident1 / k_sws_c24) of a 32-bit row whose pointer and stride are multiples of 16 is stored from registers in 16-byte pieces; of a 24-bit row
+ * on multiples of 8 in 8-byte pieces (the rgb24 rule); every other tile of the tile kernel goes through LDS rows and leaves in 16-byte, 4-byte or
+ * (24-bit only) single-byte pieces as pointer, stride and row length allow, and the other two kernels write it pair by pair.
+ * mi355_sws_destination reports the format, planes = 1 and chr_bytes = chr_rows = 0; mi355_sws_dest_depth 8; mi355_sws_range 0; mi355_sws_plan the
+ * twin's values — there is no MI355_SWS_K_* of these destinations: the twin's value with the destination's format names the kernel.
+ * Not taken (the reference's): 15 / 16-bit and lower RGB (dithered, other tables), rgb48 / rgba64, planar GBR, alpha from a YUVA source,
+ * SWS_FULL_CHR_H_INT, rgbToRgbWrapper, and a range or a 9 / 10-bit depth with these destinations. */
+enum { MI355_SWS_DST_BGR24 = 32, MI355_SWS_DST_RGBA = 33, MI355_SWS_DST_BGRA = 34, MI355_SWS_DST_ARGB = 35, MI355_SWS_DST_ABGR = 36 };
+
 /* ---- the individual inner loops (Tier 1, host pointers), argument lists of the reference's
  * function-pointer types minus the SwsContext ------------------------------------------------ */
 /* hScale8To15_c swscale.c:133-147 (c->hyScale / c->hcScale) */
@@ -282,6 +310,19 @@ void mi355_sws_yuv2rgb24_1(const mi355_sws_luts *luts, const int16_t *buf0, cons
 /* yuv2rgb_c_24_rgb yuv2rgb.c:335-363 (SwsFunc slice interface; returns srcSliceH) */
 int mi355_sws_yuv2rgb_c_24_rgb(const mi355_sws_luts *luts, int dstW, const uint8_t *const src[3], const int srcStride[3],
                                int srcSliceY, int srcSliceH, uint8_t *dst, int dstStride);
+/* the same trio and slice converter for any packed destination: dst_format 0 (rgb24: the bytes of the four entries above) or
+ * MI355_SWS_DST_BGR24 ... _ABGR (yuv2bgr24_X_c ..., yuv2rgba32_X_c ... and their _2 / _1 forms; yuv2rgb_c_24_bgr yuv2rgb.c:366-394, yuv2rgb_c_32
+ * :237-265); any other value does nothing (the slice entry returns -1).  dest holds (dstW + 1) >> 1 pairs — 6 bytes each, 8 for a 32-bit order —
+ * as the reference's loops write them; luts in the form the creators take */
+void mi355_sws_yuv2packed_X(const mi355_sws_luts *luts, int dst_format, const int16_t *lumFilter, const int16_t **lumSrc, int lumFilterSize,
+                            const int16_t *chrFilter, const int16_t **chrUSrc, const int16_t **chrVSrc, int chrFilterSize,
+                            uint8_t *dest, int dstW);
+void mi355_sws_yuv2packed_2(const mi355_sws_luts *luts, int dst_format, const int16_t *buf[2], const int16_t *ubuf[2], const int16_t *vbuf[2],
+                            uint8_t *dest, int dstW, int yalpha, int uvalpha);
+void mi355_sws_yuv2packed_1(const mi355_sws_luts *luts, int dst_format, const int16_t *buf0, const int16_t *ubuf[2], const int16_t *vbuf[2],
+                            uint8_t *dest, int dstW, int uvalpha);
+int mi355_sws_yuv2rgb_c(const mi355_sws_luts *luts, int dst_format, int dstW, const uint8_t *const src[3], const int srcStride[3],
+                        int srcSliceY, int srcSliceH, uint8_t *dst, int dstStride);
 
 #ifdef __cplusplus
 }

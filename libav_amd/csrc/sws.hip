@@ -4,7 +4,8 @@
  * -> 8-bit yuv420p / yuv422p / yuv444p and -> NV12 / NV21 (dithered from a deeper source, swscale.c:553-556), the unscaled 8-bit
  * yuv420p -> NV12 / NV21 packer and the unscaled NV12 / NV21 -> yuv420p splitter; to the YUV destinations also with range conversion between the two
  * passes (yuvj420p <-> yuv420p and their kin: lumConvertRange / chrConvertRange swscale.c:168-198), and to the three planar destinations at 9 or
- * 10 bits (yuv420p9le ... yuv444p10le: yuv2planeX_10 / yuv2plane1_10 output.c:183-213; their tile instances are launched from sws_deep.hip).  This file:
+ * 10 bits (yuv420p9le ... yuv444p10le: yuv2planeX_10 / yuv2plane1_10 output.c:183-213; their tile instances are launched from sws_deep.hip), and
+ * to bgr24 / rgba / bgra / argb / abgr wherever rgb24 is written (yuv2rgb_write output.c:825-867; their instances are launched from sws_packed.hip).  This file:
  * the context, the plan (which kernel a context gets) and the entry points of include/mi355_sws.h.  The device side is sws_dev.h:
  * k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1, k_sws_nv12_pack, k_sws_nv12_split and the k_sws_line_* kernels of the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
@@ -103,6 +104,7 @@ static mi355_sws_ctx *ctx_new(const mi355_sws_desc *desc)
     std::memset(h.dither, 64, sizeof(h.dither));
     h.dst_bits = 8;
     h.v1_rnd = h.v1_sh = h.vx_rnd = h.vx_sh = 0;
+    h.packed = 0; h.dst_sel = 0;
     return c;
 }
 /* the source side of a context (mi355_sws_create_src); false for a combination outside 8 / 9 / 10 bit 4:2:0 / 4:2:2 / 4:4:4 or a descriptor
@@ -119,6 +121,9 @@ static bool ctx_source(mi355_sws_ctx *c, const mi355_sws_src *src)
     if (src->depth > 8) std::memcpy(h.dither, src->dither, sizeof(h.dither));
     return true;
 }
+/* a packed destination other than rgb24: bgr24 or one of the four 32-bit orders */
+static bool packed_dst(int dst_format) { return dst_format >= MI355_SWS_DST_BGR24 && dst_format <= MI355_SWS_DST_ABGR; }
+static int packed_bpp(const SwsDev &h) { return h.packed >= MI355_SWS_DST_RGBA ? 4 : 3; }
 static bool packed_rgb(const SwsDev &h) { return h.src_layout == MI355_SWS_SRC_RGB24 || h.src_layout == MI355_SWS_SRC_BGR24; }
 /* a context that does not scale, to rgb24: what k_sws_ident1 takes */
 static bool ident1_shape(const SwsDev &h)
@@ -198,6 +203,8 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
     }
     mi355_sws_ctx *c = ctx_new(desc);
     SwsDev &h = c->h;
+    /* bgr24 / rgba / bgra / argb / abgr: an rgb24 context in everything but the store (the order's byte selector is read by the 32-bit instances only) */
+    if (!planar && packed_dst(dst_format)) { h.packed = dst_format; h.dst_sel = dst_format >= MI355_SWS_DST_RGBA ? sws_rgb32_sel(dst_format) : 0; }
     h.range = range;
     h.rng_l = range_map(range, false); h.rng_c = range_map(range, true);      /* (read by the RANGE instances only) */
     if (dst_depth > 8) {
@@ -303,7 +310,7 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src(const mi355_sws_desc *desc, const
 {
     if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src without mi355_init(); no CPU fallback\n"); std::abort(); }
     if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src: no descriptor\n"); return nullptr; }
-    return ctx_create(desc, src, dst_format != 0, dst_format, "mi355_sws_create_src");
+    return ctx_create(desc, src, dst_format != 0 && !packed_dst(dst_format), dst_format, "mi355_sws_create_src");
 }
 extern "C" mi355_sws_ctx *mi355_sws_create_src_layout(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format)
 {
@@ -313,7 +320,7 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src_layout(const mi355_sws_desc *desc
         std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24\n", src_layout);
         return nullptr;
     }
-    return ctx_create(desc, src, dst_format != 0, dst_format, "mi355_sws_create_src_layout", src_layout);
+    return ctx_create(desc, src, dst_format != 0 && !packed_dst(dst_format), dst_format, "mi355_sws_create_src_layout", src_layout);
 }
 extern "C" int mi355_sws_source_layout(const mi355_sws_ctx *c) { return c ? c->h.src_layout : -1; }
 extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format, int range)
@@ -330,8 +337,8 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range(const mi355_sws_desc
         return nullptr;
     }
     /* the reference converts the range of YUV destinations only (an RGB one takes it into its LUTs), and never in an unscaled special converter */
-    if (dst_format == 0) {
-        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: an rgb24 destination has its range in the LUTs, not in a conversion step\n");
+    if (dst_format == 0 || packed_dst(dst_format)) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: a packed RGB destination (%d) has its range in the LUTs, not in a conversion step\n", dst_format);
         return nullptr;
     }
     if (desc->unscaled_special) {
@@ -432,7 +439,7 @@ extern "C" int mi355_sws_destination(const mi355_sws_ctx *c, mi355_sws_dest_info
 {
     if (!c || !p) return -1;
     const SwsDev &h = c->h;
-    p->format = h.planar;
+    p->format = h.planar ? h.planar : h.packed;
     p->planes = !h.planar ? 1 : (semi_planar(h) ? 2 : 3);
     /* the packer rounds both extents down (planarToNv12Wrapper) */
     /* ... and so does the splitter (nv12ToPlanarWrapper) */
@@ -573,6 +580,15 @@ extern "C" int mi355_sws_scale_frames_dev(mi355_sws_ctx *c, const mi355_sws_fram
     const SwsDev &h = c->h;
     DeviceScope on(c->device);
     const int k = sws_kernel(h);
+    if (h.packed) {
+        /* bgr24 and the 32-bit orders: the twin's kernel and grid, the DST_BGR24 / DST_RGB32 instance (sws_packed.hip) */
+        const dim3 grid = k == MI355_SWS_K_C24 ? dim3((h.dstW + C24_COLS - 1) / C24_COLS, (h.srcH + C24_ROWS - 1) / C24_ROWS, nframes) :
+                          k == MI355_SWS_K_IDENT1_1 || k == MI355_SWS_K_IDENT1_X ? dim3((h.dstW + C24_COLS - 1) / C24_COLS, (h.dstH + IDENT_ROWS - 1) / IDENT_ROWS, nframes) :
+                          dim3((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
+        const int src = k == MI355_SWS_K_C24 ? (h.src_vsub ? 0 : 1) : (packed_rgb(h) ? 3 : (h.src_layout ? 2 : (h.depth > 8 ? 1 : 0)));
+        mi355_sws_launch_packed(k, src, h.packed, grid, s, c->d, h.dstW, h.srcH, d_frames);
+        return hipGetLastError() == hipSuccess ? 0 : -2;
+    }
     if (k == MI355_SWS_K_C24) {
         const dim3 grid((h.dstW + C24_COLS - 1) / C24_COLS, (h.srcH + C24_ROWS - 1) / C24_ROWS, nframes);
         if (h.src_vsub) hipLaunchKernelGGL(k_sws_c24<0>, grid, dim3(NT), 0, s, &c->d->luts, h.dstW, h.srcH, 0, d_frames);
@@ -707,8 +723,11 @@ extern "C" int mi355_sws_scale(mi355_sws_ctx *c, const uint8_t *const src[3], co
 {
     if (!c || !src || !src_stride || !dst || c->h.planar) return -1;
     const SwsDev &h = c->h;
+    /* a 32-bit destination is stored in dwords */
+    const int bpp = packed_bpp(h);
+    if (bpp == 4 && ((reinterpret_cast<uintptr_t>(dst) | (uintptr_t)dst_stride) & 3)) return -1;
     /* only the samples the converter writes go back */
-    const int ow = h.dstW * 3, back = h.special ? (h.dstW & ~1) * 3 : h.dstW * 3;
+    const int ow = h.dstW * bpp, back = h.special ? (h.dstW & ~1) * bpp : h.dstW * bpp;
     const int r = scale_staged(c, src, src_stride, 1, &dst, &dst_stride, &ow, &h.dstH, &back);
     return r ? r : (h.special ? h.srcH : h.dstH);
 }
@@ -894,23 +913,28 @@ extern "C" void mi355_sws_yuv2nv12cX(const int16_t *chrFilter, int chrFilterSize
     std::memcpy(dest, a.h<uint8_t>(o_d), (size_t)2 * chrDstW);
 }
 
+/* dst_format 0: rgb24 (k_sws_line_rgb); MI355_SWS_DST_BGR24 ... _ABGR: k_sws_line_packed of that form (sws_packed.hip), pairs of 6 or 8 bytes */
 static void rgb_line(const mi355_sws_luts *luts, int mode, const int16_t *lumF, const int16_t **l, int ls, const int16_t *chrF,
-                     const int16_t **u, const int16_t **v, int cs, uint8_t *dest, int dstW, int yalpha, int uvalpha)
+                     const int16_t **u, const int16_t **v, int cs, uint8_t *dest, int dstW, int yalpha, int uvalpha, int dst_format = 0)
 {
     Arena &a = arena();
-    const int npair = (dstW + 1) >> 1, pitch = (2 * npair + 7) & ~7;
-    a.reserve(sizeof(mi355_sws_luts) + (size_t)(ls + 2 * cs + 3) * pitch * 2 + (size_t)(ls + cs) * 2 + (size_t)npair * 6 + 256);
+    const int npair = (dstW + 1) >> 1, pitch = (2 * npair + 7) & ~7, pb = dst_format >= MI355_SWS_DST_RGBA ? 8 : 6;
+    a.reserve(sizeof(mi355_sws_luts) + (size_t)(ls + 2 * cs + 3) * pitch * 2 + (size_t)(ls + cs) * 2 + (size_t)npair * pb + 256);
     const size_t o_t = a.take(sizeof(mi355_sws_luts));
     std::memcpy(a.h<uint8_t>(o_t), luts, sizeof(mi355_sws_luts));
     const size_t o_l = pack_rows(a, l, ls, 2 * npair, pitch), o_u = pack_rows(a, u, cs, npair, pitch), o_v = pack_rows(a, v, cs, npair, pitch);
-    const size_t o_lf = a.take((size_t)ls * 2 + 2), o_cf = a.take((size_t)cs * 2 + 2), o_d = a.take((size_t)npair * 6);
+    const size_t o_lf = a.take((size_t)ls * 2 + 2), o_cf = a.take((size_t)cs * 2 + 2), o_d = a.take((size_t)npair * pb);
     if (lumF) std::memcpy(a.h<int16_t>(o_lf), lumF, (size_t)ls * 2);
     if (chrF) std::memcpy(a.h<int16_t>(o_cf), chrF, (size_t)cs * 2);
     a.upload();
+    if (dst_format)
+        mi355_sws_launch_line_packed(dst_format, a.stream, a.d<const mi355_sws_luts>(o_t), mode, a.d<const int16_t>(o_lf), a.d<const int16_t>(o_l), ls, a.d<const int16_t>(o_cf),
+                                     a.d<const int16_t>(o_u), a.d<const int16_t>(o_v), cs, pitch, a.d<uint8_t>(o_d), dstW, yalpha, uvalpha);
+    else
     launch_line(k_sws_line_rgb, a, a.d<const mi355_sws_luts>(o_t), mode, a.d<const int16_t>(o_lf), a.d<const int16_t>(o_l), ls, a.d<const int16_t>(o_cf),
                 a.d<const int16_t>(o_u), a.d<const int16_t>(o_v), cs, pitch, a.d<uint8_t>(o_d), dstW, yalpha, uvalpha);
     a.download();
-    std::memcpy(dest, a.h<uint8_t>(o_d), (size_t)npair * 6);   /* like the reference: whole pairs, also for odd dstW */
+    std::memcpy(dest, a.h<uint8_t>(o_d), (size_t)npair * pb);   /* like the reference: whole pairs, also for odd dstW */
 }
 extern "C" void mi355_sws_yuv2rgb24_X(const mi355_sws_luts *luts, const int16_t *lumFilter, const int16_t **lumSrc, int lumFilterSize,
                                       const int16_t *chrFilter, const int16_t **chrUSrc, const int16_t **chrVSrc, int chrFilterSize,
@@ -957,6 +981,65 @@ extern "C" int mi355_sws_yuv2rgb_c_24_rgb(const mi355_sws_luts *luts, int dstW, 
     hipLaunchKernelGGL(k_sws_c24<0>, dim3((dstW + C24_COLS - 1) / C24_COLS, (rows + C24_ROWS - 1) / C24_ROWS, 1), dim3(NT), 0, s,
                        reinterpret_cast<const mi355_sws_luts *>(d_l), dstW, rows, 0, d_f);
     MI355_CHECK(hipMemcpy2DAsync(dst + (ptrdiff_t)srcSliceY * dstStride, dstStride, d_dst, dpitch, (dstW & ~1) * 3, rows, hipMemcpyDeviceToHost, s));
+    MI355_CHECK(hipStreamSynchronize(s));
+    for (int p = 0; p < 3; p++) MI355_CHECK(hipFree(const_cast<uint8_t *>(f.src[p])));
+    MI355_CHECK(hipFree(d_dst)); MI355_CHECK(hipFree(d_f)); MI355_CHECK(hipFree(d_l));
+    return srcSliceH;
+}
+
+/* ---- the same entries for any packed destination (dst_format 0: rgb24, the entries above; MI355_SWS_DST_BGR24 ... _ABGR) ---------------- */
+static bool packed_line_format(int dst_format) { return dst_format == 0 || packed_dst(dst_format); }
+extern "C" void mi355_sws_yuv2packed_X(const mi355_sws_luts *luts, int dst_format, const int16_t *lumFilter, const int16_t **lumSrc, int lumFilterSize,
+                                       const int16_t *chrFilter, const int16_t **chrUSrc, const int16_t **chrVSrc, int chrFilterSize,
+                                       uint8_t *dest, int dstW)
+{
+    if (!packed_line_format(dst_format)) return;
+    rgb_line(luts, 0, lumFilter, lumSrc, lumFilterSize, chrFilter, chrUSrc, chrVSrc, chrFilterSize, dest, dstW, 0, 0, dst_format);
+}
+extern "C" void mi355_sws_yuv2packed_2(const mi355_sws_luts *luts, int dst_format, const int16_t *buf[2], const int16_t *ubuf[2], const int16_t *vbuf[2],
+                                       uint8_t *dest, int dstW, int yalpha, int uvalpha)
+{
+    if (!packed_line_format(dst_format)) return;
+    rgb_line(luts, 2, nullptr, buf, 2, nullptr, ubuf, vbuf, 2, dest, dstW, yalpha, uvalpha, dst_format);
+}
+extern "C" void mi355_sws_yuv2packed_1(const mi355_sws_luts *luts, int dst_format, const int16_t *buf0, const int16_t *ubuf[2], const int16_t *vbuf[2],
+                                       uint8_t *dest, int dstW, int uvalpha)
+{
+    if (!packed_line_format(dst_format)) return;
+    const int cs = uvalpha < 2048 ? 1 : 2;                      /* as mi355_sws_yuv2rgb24_1 */
+    rgb_line(luts, 1, nullptr, &buf0, 1, nullptr, ubuf, vbuf, cs, dest, dstW, 0, uvalpha, dst_format);
+}
+
+/* yuv2rgb_c_24_rgb / yuv2rgb_c_24_bgr / yuv2rgb_c_32 (yuv2rgb.c:237-394) on one 4:2:0 slice: mi355_sws_yuv2rgb_c_24_rgb with the destination's format */
+extern "C" int mi355_sws_yuv2rgb_c(const mi355_sws_luts *luts, int dst_format, int dstW, const uint8_t *const src[3], const int srcStride[3],
+                                   int srcSliceY, int srcSliceH, uint8_t *dst, int dstStride)
+{
+    if (dst_format == 0) return mi355_sws_yuv2rgb_c_24_rgb(luts, dstW, src, srcStride, srcSliceY, srcSliceH, dst, dstStride);
+    if (!packed_dst(dst_format)) return -1;
+    if (!ready()) { std::fprintf(stderr, "mi355dsp: mi355_sws_yuv2rgb_c without mi355_init(); no CPU fallback\n"); std::abort(); }
+    const int bpp = dst_format >= MI355_SWS_DST_RGBA ? 4 : 3;
+    if (bpp == 4 && ((reinterpret_cast<uintptr_t>(dst) | (uintptr_t)dstStride) & 3)) return -1;
+    const int rows = srcSliceH, cw = dstW >> 1, crow = (rows + 1) >> 1;   /* even slices, as the reference's callers guarantee */
+    const int pw[3] = { (dstW + 15) & ~15, (cw + 15) & ~15, (cw + 15) & ~15 }, ph[3] = { rows, crow, crow }, w[3] = { dstW & ~1, cw, cw };
+    const int dpitch = (dstW * bpp + 15) & ~15;
+    hipStream_t s = arena().stream;
+    mi355_sws_frame f, *d_f;
+    uint8_t *d_l, *d_dst;
+    for (int p = 0; p < 3; p++) {
+        uint8_t *d;
+        MI355_CHECK(hipMalloc(reinterpret_cast<void **>(&d), (size_t)pw[p] * (ph[p] + 1) + 64));
+        plane_h2d(d, pw[p], src[p], srcStride[p], w[p], ph[p], s);
+        f.src[p] = d; f.src_stride[p] = pw[p];
+    }
+    MI355_CHECK(hipMalloc(reinterpret_cast<void **>(&d_dst), (size_t)dpitch * (rows + 1)));
+    MI355_CHECK(hipMalloc(reinterpret_cast<void **>(&d_f), sizeof(f)));
+    MI355_CHECK(hipMalloc(reinterpret_cast<void **>(&d_l), sizeof(mi355_sws_luts)));
+    f.dst = d_dst; f.dst_stride = dpitch;
+    MI355_CHECK(hipMemcpyAsync(d_f, &f, sizeof(f), hipMemcpyHostToDevice, s));
+    MI355_CHECK(hipMemcpyAsync(d_l, luts, sizeof(mi355_sws_luts), hipMemcpyHostToDevice, s));
+    mi355_sws_launch_c24_slice(dst_format, dim3((dstW + C24_COLS - 1) / C24_COLS, (rows + C24_ROWS - 1) / C24_ROWS, 1), s,
+                               reinterpret_cast<const mi355_sws_luts *>(d_l), dstW, rows, d_f);
+    MI355_CHECK(hipMemcpy2DAsync(dst + (ptrdiff_t)srcSliceY * dstStride, dstStride, d_dst, dpitch, (dstW & ~1) * bpp, rows, hipMemcpyDeviceToHost, s));
     MI355_CHECK(hipStreamSynchronize(s));
     for (int p = 0; p < 3; p++) MI355_CHECK(hipFree(const_cast<uint8_t *>(f.src[p])));
     MI355_CHECK(hipFree(d_dst)); MI355_CHECK(hipFree(d_f)); MI355_CHECK(hipFree(d_l));

@@ -18,7 +18,9 @@
  * an NV12 / NV21 source: both chroma planes from one pass over its plane of byte pairs (hscale_tile_nv).  The RGB instances of the tile kernels
  * read a packed rgb24 / bgr24 source: the reference's input converters in front of the 8-bit horizontal pass (hscale_tile_rgb).  The RANGE
  * instances of k_sws_planar convert the range of the int16 lines between the two passes (lumConvertRange / chrConvertRange: range_lines).  The DEEP
- * instances of k_sws_planar write 9- or 10-bit planes of 16-bit little-endian samples (yuv2plane1_10 / yuv2planeX_10: planar_rows16).
+ * instances of k_sws_planar write 9- or 10-bit planes of 16-bit little-endian samples (yuv2plane1_10 / yuv2planeX_10: planar_rows16).  The DST_BGR24 /
+ * DST_RGB32 instances of k_sws_generic, k_sws_ident1 and k_sws_c24 write bgr24 or one of rgba / bgra / argb / abgr in place of rgb24 (write_pair_d,
+ * store8_d; compiled in sws_packed.hip).
  *   k_sws_line_*    the individual inner loops for the Tier-1 entry points.
  * Execution model: 256-thread workgroups (4 waves) sharing one LDS tile; integer only, no MFMA.
  */
@@ -72,6 +74,10 @@ struct SwsDev {
      * the rounding term and the shift of the one-tap form and of the X form (yuv2plane1_10 / yuv2planeX_10, output.c:183-213) */
     int dst_bits;
     int v1_rnd, v1_sh, vx_rnd, vx_sh;
+    /* a packed destination other than rgb24 (mi355_sws_create_src_layout_range_depth with MI355_SWS_DST_BGR24 ... _ABGR; 0: rgb24 or a planar one)
+     * and, for the four 32-bit orders, the byte selector of the order (sws_rgb32_sel: read by the 32-bit instances only) */
+    int packed;
+    uint32_t dst_sel;
 };
 
 /* the context record with its bank pointers in the global address space (mi355_rt.h): what the tile kernels open with */
@@ -115,13 +121,64 @@ __device__ __forceinline__ void write_pair(const LutLds &t, uint8_t *dest, int Y
     dest[0] = t.y[r + Y1]; dest[1] = t.y[g + Y1]; dest[2] = t.y[b + Y1];
     dest[3] = t.y[r + Y2]; dest[4] = t.y[g + Y2]; dest[5] = t.y[b + Y2];
 }
+/* ---- packed destinations other than rgb24: the DST template forms of the packed kernels (DST_RGB24 is the code above and below, unchanged) ----
+ * DST_BGR24: yuv2rgb_write with r_b / b_r the other way round (output.c:853-866) — the r and the b row offsets change places at compile time, every
+ *   store stays.
+ * DST_RGB32: rgba / bgra / argb / abgr, one dword a pixel: the reference's r[Y] + g[Y] + b[Y] over its uint32_t tables (output.c:831-851,
+ *   yuv2rgb.c:864-888) is the 24-bpp case's clipped byte in three lanes and 255 in the fourth (a source without alpha) — here the three byte reads
+ *   of y_table assembled as r | g << 8 | b << 16 | 255 << 24 and put into the order's bytes by ONE byte permute; its selector is the same on every
+ *   lane (SwsDev::dst_sel, or a kernel argument), so one form serves the four orders. */
+constexpr int DST_RGB24 = 0, DST_BGR24 = 1, DST_RGB32 = 2;
+template <int DST> __host__ __device__ constexpr int dst_bpp() { return DST == DST_RGB32 ? 4 : 3; }
+/* the selector of a 32-bit order (MI355_SWS_DST_RGBA ... _ABGR): byte k of the stored dword is byte (sel >> 8 k) & 3 of r | g << 8 | b << 16 | a << 24 */
+__host__ __device__ constexpr uint32_t sws_rgb32_sel(int dst_format)
+{
+    return dst_format == MI355_SWS_DST_RGBA ? 0x03020100u : (dst_format == MI355_SWS_DST_BGRA ? 0x03000102u :
+           (dst_format == MI355_SWS_DST_ARGB ? 0x02010003u : 0x00010203u));
+}
+#ifdef MI355_HIP_EMU_H
+static inline uint32_t sws_order4(uint32_t w, uint32_t sel)
+{
+    uint32_t o = 0;
+    for (int k = 0; k < 4; k++) o |= ((w >> (8 * ((sel >> (8 * k)) & 3))) & 0xFFu) << (8 * k);
+    return o;
+}
+#else
+__device__ __forceinline__ uint32_t sws_order4(uint32_t w, uint32_t sel) { return __builtin_amdgcn_perm(0u, w, sel); }     /* v_perm_b32 */
+#endif
+template <int DST> __device__ __forceinline__ void lut_rows_d(const LutLds &t, int U, int V, int &r, int &g, int &b)
+{
+    if constexpr (DST == DST_BGR24) lut_rows(t, U, V, b, g, r);
+    else lut_rows(t, U, V, r, g, b);
+}
+/* one pixel of a 32-bit order from its row offsets */
+__device__ __forceinline__ uint32_t rgb32_pixel(const LutLds &t, int r, int g, int b, int Y, uint32_t sel)
+{
+    return sws_order4((uint32_t)t.y[r + Y] | ((uint32_t)t.y[g + Y] << 8) | ((uint32_t)t.y[b + Y] << 16) | 0xFF000000u, sel);
+}
+/* yuv2rgb_write of one pair: six bytes, or two dwords at dest (a multiple of 4) */
+template <int DST> __device__ __forceinline__ void write_pair_d(const LutLds &t, uint8_t *dest, int Y1, int Y2, int U, int V, uint32_t sel)
+{
+    if constexpr (DST == DST_RGB24) write_pair(t, dest, Y1, Y2, U, V);
+    else {
+        int r, g, b;
+        lut_rows_d<DST>(t, U, V, r, g, b);
+        if constexpr (DST == DST_BGR24) {
+            dest[0] = t.y[r + Y1]; dest[1] = t.y[g + Y1]; dest[2] = t.y[b + Y1];
+            dest[3] = t.y[r + Y2]; dest[4] = t.y[g + Y2]; dest[5] = t.y[b + Y2];
+        } else {
+            uint32_t *q = reinterpret_cast<uint32_t *>(dest);
+            q[0] = rgb32_pixel(t, r, g, b, Y1, sel); q[1] = rgb32_pixel(t, r, g, b, Y2, sel);
+        }
+    }
+}
 
 /* one output pair of the three packed templates; rows are addressed through accessors so the same
  * code serves LDS tiles (whole pictures) and packed global rows (Tier-1 line calls).  vertical_rows keeps its own statement of them over
  * the taps it holds in registers: a register-resident accessor here was tried and gave another instruction stream */
-template <typename Rows>
+template <int DST = DST_RGB24, typename Rows>
 __device__ __forceinline__ void rgb_pair(const LutLds &t, uint8_t *dest, const Rows &R, int i, int mode, const int16_t *lumF, int ls,
-                                         const int16_t *chrF, int cs, int yalpha, int uvalpha)
+                                         const int16_t *chrF, int cs, int yalpha, int uvalpha, uint32_t sel = 0)
 {
     int Y1, Y2, U, V;
     if (mode == 1) {          /* yuv2rgb_1_c_template output.c:1043-1110 */
@@ -141,7 +198,7 @@ __device__ __forceinline__ void rgb_pair(const LutLds &t, uint8_t *dest, const R
         Y1 >>= 19; Y2 >>= 19; U >>= 19; V >>= 19;
         if ((Y1 | Y2 | U | V) & 0x100) { Y1 = clip_u8(Y1); Y2 = clip_u8(Y2); U = clip_u8(U); V = clip_u8(V); }
     }
-    write_pair(t, dest, Y1, Y2, U, V);
+    write_pair_d<DST>(t, dest, Y1, Y2, U, V, sel);
 }
 /* eight neighbouring samples of a line (four pairs sharing a chroma sample each): Y values 0..255 in Y[8], the pairs' LUT
  * row offsets in r/g/b -> 24 RGB bytes at d (8-byte aligned), three 8-byte stores */
@@ -164,6 +221,21 @@ __device__ __forceinline__ void rgb24_store8(const LutLds &t, uint8_t *d, const 
     }
     sws_u32x2 *q = reinterpret_cast<sws_u32x2 *>(d);
     q[0] = sws_u32x2{ o[0], o[1] }; q[1] = sws_u32x2{ o[2], o[3] }; q[2] = sws_u32x2{ o[4], o[5] };
+}
+/* the same eight samples as 32-bit pixels: 32 bytes at d (16-byte aligned), two 16-byte stores */
+__device__ __forceinline__ void rgb32_store8(const LutLds &t, uint8_t *d, const int *Y, const int *r, const int *g, const int *b, uint32_t sel)
+{
+    uint32_t o[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) o[k] = rgb32_pixel(t, r[k >> 1], g[k >> 1], b[k >> 1], Y[k], sel);
+    sws_u32x4 *q = reinterpret_cast<sws_u32x4 *>(d);
+    q[0] = sws_u32x4{ o[0], o[1], o[2], o[3] }; q[1] = sws_u32x4{ o[4], o[5], o[6], o[7] };
+}
+/* ... of destination form DST (bgr24: the row offsets came exchanged from lut_rows_d, the packing is rgb24's) */
+template <int DST> __device__ __forceinline__ void store8_d(const LutLds &t, uint8_t *d, const int *Y, const int *r, const int *g, const int *b, uint32_t sel)
+{
+    if constexpr (DST == DST_RGB32) rgb32_store8(t, d, Y, r, g, b, sel);
+    else rgb24_store8(t, d, Y, r, g, b);
 }
 __device__ __forceinline__ int packed_mode(int ls, int cs) { return (ls == 1 && cs <= 2) ? 1 : ((ls == 2 && cs == 2) ? 2 : 0); }  /* swscale.c:658-682 */
 
@@ -218,6 +290,9 @@ template <int COLS, typename ST = uint8_t> struct StageGeom {
 };
 constexpr int OUT_ROWS = STAGE_BYTES / (TW * 3);            /* rows of a narrow tile written per pass (they reuse the staging lines) */
 static_assert(OUT_ROWS >= 8, "the narrow form needs at most two passes over a tile of MAXTH rows");
+/* ... of destination form DST: a 32-bit row is TW * 4 bytes, the staging lines hold nine of them */
+template <int DST> __host__ __device__ constexpr int out_rows() { return STAGE_BYTES / (TW * dst_bpp<DST>()); }
+static_assert(out_rows<DST_RGB24>() == OUT_ROWS && out_rows<DST_BGR24>() == OUT_ROWS && out_rows<DST_RGB32>() == 9, "two passes at most for every form");
 /* byte funnel shift, byte permute and the two-term 16-bit dot product (v_alignbyte_b32, v_perm_b32, v_dot2_i32_i16); plain C
  * under the SIMT emulator */
 #ifdef MI355_HIP_EMU_H
@@ -919,14 +994,18 @@ __device__ __forceinline__ void hscale_tile_rgb(int16_t (*out_a)[OP], int16_t (*
 /* Vertical pass + LUT for the output rows of a tile with the row's filter taps and source-line indices in
  * registers: NL / NC = luma / chroma tap counts rounded up to 1, 2, 4 or 8 (taps past the real size carry a
  * zero coefficient and a valid line index).  A thread owns one output row and every 16th pair of it. */
-template <int NL, int NC, bool WIDE>
+/* DST: the destination form (DST_RGB24 / DST_BGR24 / DST_RGB32) — the row offsets of a pair (lut_rows_d), the bytes of a pixel and the store (store8_d,
+ * write_pair_d); everything up to the LUT is one text for the three */
+template <int NL, int NC, bool WIDE, int DST = DST_RGB24>
 __device__ __forceinline__ void vertical_rows(const SwsDev &c, const LutLds &lut, const int16_t (*s_lum)[TW], const int16_t (*s_cu)[TW / 2],
-                                              const int16_t (*s_cv)[TW / 2], uint8_t (*s_out)[TW * 3], int tid, int y0, int y1, int llo, int clo,
+                                              const int16_t (*s_cv)[TW / 2], uint8_t (*s_out)[TW * dst_bpp<DST>()], int tid, int y0, int y1, int llo, int clo,
                                               int npairs, int mode, uint8_t *wide_dst, int dst_stride, int out_row0)
 {
-    /* out_row0: first tile row of this pass of the narrow form (s_out holds OUT_ROWS rows at a time) */
+    /* out_row0: first tile row of this pass of the narrow form (s_out holds OUT_ROWS rows at a time; nine of a 32-bit destination) */
+    constexpr int BPP = dst_bpp<DST>();
+    const uint32_t sel = DST == DST_RGB32 ? c.dst_sel : 0u;
     const int row = tid >> 4, gy = y0 + row;
-    if (gy > y1 || (!WIDE && (row < out_row0 || row >= out_row0 + OUT_ROWS))) return;
+    if (gy > y1 || (!WIDE && (row < out_row0 || row >= out_row0 + out_rows<DST>()))) return;
     const int ls = c.vls, cs = c.vcs;
     const int lfirst = imax(1 - ls, c.vLumP[gy]), cfirst = imax(1 - cs, c.vChrP[gy]);
     /* the taps: every load unconditional (a tap past the filter reads tap 0 and becomes zero), so that they are in flight together */
@@ -1029,8 +1108,8 @@ __device__ __forceinline__ void vertical_rows(const SwsDev &c, const LutLds &lut
         }
         int r[4], g[4], b[4];
 #pragma unroll
-        for (int p = 0; p < 4; p++) lut_rows(lut, U[p], V[p], r[p], g[p], b[p]);
-        rgb24_store8(lut, wide_dst + (size_t)row * dst_stride + 24 * grp, Y, r, g, b);
+        for (int p = 0; p < 4; p++) lut_rows_d<DST>(lut, U[p], V[p], r[p], g[p], b[p]);
+        store8_d<DST>(lut, wide_dst + (size_t)row * dst_stride + 8 * BPP * grp, Y, r, g, b, sel);
         return;
     }
     /* fixed trip count: the pairs of a thread are 16 apart, so every LDS address is one base plus an immediate */
@@ -1062,7 +1141,7 @@ __device__ __forceinline__ void vertical_rows(const SwsDev &c, const LutLds &lut
             Y1 >>= 19; Y2 >>= 19; U >>= 19; V >>= 19;
             if ((Y1 | Y2 | U | V) & 0x100) { Y1 = clip_u8(Y1); Y2 = clip_u8(Y2); U = clip_u8(U); V = clip_u8(V); }
         }
-        write_pair(lut, &s_out[row - out_row0][i * 6], Y1, Y2, U, V);
+        write_pair_d<DST>(lut, &s_out[row - out_row0][i * 2 * BPP], Y1, Y2, U, V, sel);
     }
 }
 /* LDS of a workgroup, sized per context (sws_plan): the horizontal pass's results for the source lines a tile needs, the tables, and one
@@ -1082,35 +1161,37 @@ __host__ __device__ constexpr int sws_waves(int lds_bytes) { return 160 * 1024 /
 __host__ __device__ constexpr int tap_bucket(int fs) { return fs <= 1 ? 0 : (fs <= 2 ? 1 : (fs <= 4 ? 2 : 3)); }
 /* Tiles that cannot store from registers (the picture's right edge, a destination that is not 8-byte aligned, filters of more than
  * eight taps): the rows go through s_out, OUT_ROWS at a time. */
+template <int DST = DST_RGB24>
 __device__ __forceinline__ void vertical_narrow(const SwsDev *cp, const LutLds *lutp, const int16_t (*s_lum)[TW], const int16_t (*s_cu)[TW / 2],
-                                                          const int16_t (*s_cv)[TW / 2], uint8_t (*s_out)[TW * 3], uint8_t *tile_dst, int dst_stride,
+                                                          const int16_t (*s_cv)[TW / 2], uint8_t (*s_out)[TW * dst_bpp<DST>()], uint8_t *tile_dst, int dst_stride,
                                                           int x0, int y0, int y1, int llo, int clo)
 {
+    constexpr int BPP = dst_bpp<DST>(), OUT_ROWS = out_rows<DST>();
     const SwsDev c = sws_dev(cp);
     const LutLds &s_lut = *lutp;
     const int tid = threadIdx.x, ls = c.vls, cs = c.vcs, mode = packed_mode(ls, cs);
     const int npairs = imin(TW, c.dstW - x0 + 1) >> 1;     /* (dstW + 1) >> 1 pairs in the picture */
-    const int nbytes = imin(TW, c.dstW - x0) * 3, nrows_all = y1 - y0 + 1;
+    const int nbytes = imin(TW, c.dstW - x0) * BPP, nrows_all = y1 - y0 + 1;
     const int bl = tap_bucket(ls), bc = tap_bucket(cs);
     for (int r0 = 0; r0 < nrows_all; r0 += OUT_ROWS) {
         if (ls <= 8 && cs <= 8) {
             switch (bl * 4 + bc) {
-            case 0: vertical_rows<1, 1, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 1: vertical_rows<1, 2, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 2: vertical_rows<1, 4, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 3: vertical_rows<1, 8, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 4: vertical_rows<2, 1, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 5: vertical_rows<2, 2, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 6: vertical_rows<2, 4, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 7: vertical_rows<2, 8, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 8: vertical_rows<4, 1, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 9: vertical_rows<4, 2, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 10: vertical_rows<4, 4, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 11: vertical_rows<4, 8, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 12: vertical_rows<8, 1, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 13: vertical_rows<8, 2, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 14: vertical_rows<8, 4, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            default: vertical_rows<8, 8, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 0: vertical_rows<1, 1, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 1: vertical_rows<1, 2, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 2: vertical_rows<1, 4, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 3: vertical_rows<1, 8, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 4: vertical_rows<2, 1, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 5: vertical_rows<2, 2, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 6: vertical_rows<2, 4, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 7: vertical_rows<2, 8, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 8: vertical_rows<4, 1, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 9: vertical_rows<4, 2, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 10: vertical_rows<4, 4, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 11: vertical_rows<4, 8, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 12: vertical_rows<8, 1, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 13: vertical_rows<8, 2, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 14: vertical_rows<8, 4, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            default: vertical_rows<8, 8, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
             }
         } else
         for (int p = tid; p < OUT_ROWS * (TW / 2); p += NT) {
@@ -1120,7 +1201,7 @@ __device__ __forceinline__ void vertical_narrow(const SwsDev *cp, const LutLds *
             int ya = 0, ua = 0;
             if (mode == 1) ua = cs == 1 ? 0 : c.vChrC[2 * gy + 1];
             else if (mode == 2) { ya = c.vLumC[2 * gy + 1]; ua = c.vChrC[2 * gy + 1]; }
-            rgb_pair(s_lut, &s_out[row - r0][i * 6], R, i, mode, c.vLumC + (size_t)gy * ls, ls, c.vChrC + (size_t)gy * cs, cs, ya, ua);
+            rgb_pair<DST>(s_lut, &s_out[row - r0][i * 2 * BPP], R, i, mode, c.vLumC + (size_t)gy * ls, ls, c.vChrC + (size_t)gy * cs, cs, ya, ua, c.dst_sel);
         }
         __syncthreads();
         /* rows out: only samples below dstW (for odd dstW the reference also writes the phantom partner of
@@ -1129,7 +1210,7 @@ __device__ __forceinline__ void vertical_narrow(const SwsDev *cp, const LutLds *
             uint8_t *d0 = tile_dst + (size_t)r0 * dst_stride;
             const int nrows = imin(OUT_ROWS, nrows_all - r0);
             const unsigned al = (unsigned)(uintptr_t)d0 | (unsigned)dst_stride | (unsigned)nbytes;
-            /* mi355_div20 below: idx < nrows * n with nrows <= 16 and n <= TW * 3 / 4 = 96: idx * n < 2^18 */
+            /* mi355_div20 below: idx < nrows * n with nrows <= 16 and n <= TW * 3 / 4 = 96: idx * n < 2^18 (32 bits: nrows <= 9, n <= TW = 128: the same bound) */
             if ((al & 15) == 0) {                     /* 16 bytes per thread and store */
                 const int n = nbytes >> 4, inv = mi355_inv20(n);
                 for (int idx = tid; idx < nrows * n; idx += NT) {
@@ -1157,7 +1238,9 @@ __device__ __forceinline__ void vertical_narrow(const SwsDev *cp, const LutLds *
  * The same LDS, so the same workgroups per CU.  The three-plane instances are the NV false ones, unchanged.
  * RGB: a packed rgb24 / bgr24 source (8 bit) — luma and both chroma tiles from fr.src[0] through the input converters (hscale_tile_rgb);
  * fr.src[1] and fr.src[2] are not read.  The same LDS again. */
-template <int LCAP, int CCAP, int WAVES, typename ST = uint8_t, bool NV = false, bool RGB = false>
+/* DST: the destination form — DST_RGB24 (the instances above, unchanged), DST_BGR24 or DST_RGB32 (compiled in sws_packed.hip).  The same LDS: the
+ * output rows of the narrow form share the staging lines, nine rows of TW * 4 bytes where rgb24 has twelve of TW * 3. */
+template <int LCAP, int CCAP, int WAVES, typename ST = uint8_t, bool NV = false, bool RGB = false, int DST = DST_RGB24>
 #ifndef MI355_HIP_EMU_H
 __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
 #endif
@@ -1168,7 +1251,8 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
     __shared__ LutLds s_lut;
     /* the staging lines of the horizontal pass; the output rows of tiles that cannot store from registers reuse them after it */
     __shared__ __attribute__((aligned(16))) uint8_t s_io[stage_bytes<ST>()];
-    uint8_t (*s_out)[TW * 3] = reinterpret_cast<uint8_t (*)[TW * 3]>(s_io);
+    constexpr int BPP = dst_bpp<DST>();
+    uint8_t (*s_out)[TW * BPP] = reinterpret_cast<uint8_t (*)[TW * BPP]>(s_io);
     const SwsDev c = sws_dev(cp);
     mi355_sws_frame fr = frames[blockIdx.z];
     for (int k = 0; k < 3; k++) fr.src[k] = mi355_global(fr.src[k]);
@@ -1208,33 +1292,35 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
     /* vertical pass + LUT */
     const int mode = packed_mode(ls, cs);
     const int npairs = imin(TW, c.dstW - x0 + 1) >> 1;     /* (dstW + 1) >> 1 pairs in the picture */
-    /* full tiles with an 8-byte aligned destination leave straight from registers; the others go through s_out, OUT_ROWS rows at a time */
-    uint8_t *const tile_dst = fr.dst + (size_t)y0 * fr.dst_stride + (size_t)x0 * 3;
-    uint8_t *const wide_dst = (ls <= 8 && cs <= 8 && c.dstW - x0 >= TW && ((reinterpret_cast<uintptr_t>(tile_dst) | (uintptr_t)fr.dst_stride) & 7) == 0)
+    /* full tiles with an 8-byte aligned destination leave straight from registers; the others go through s_out, OUT_ROWS rows at a time
+     * (a 32-bit destination: 16-byte aligned, two 16-byte stores a thread) */
+    constexpr uintptr_t WIDE_MASK = DST == DST_RGB32 ? 15 : 7;
+    uint8_t *const tile_dst = fr.dst + (size_t)y0 * fr.dst_stride + (size_t)x0 * BPP;
+    uint8_t *const wide_dst = (ls <= 8 && cs <= 8 && c.dstW - x0 >= TW && ((reinterpret_cast<uintptr_t>(tile_dst) | (uintptr_t)fr.dst_stride) & WIDE_MASK) == 0)
                                   ? tile_dst : nullptr;
     const int bl = tap_bucket(ls), bc = tap_bucket(cs);
     if (wide_dst) {                               /* uniform over the workgroup: every row leaves from registers */
         switch (bl * 4 + bc) {
-        case 0: vertical_rows<1, 1, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 1: vertical_rows<1, 2, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 2: vertical_rows<1, 4, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 3: vertical_rows<1, 8, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 4: vertical_rows<2, 1, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 5: vertical_rows<2, 2, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 6: vertical_rows<2, 4, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 7: vertical_rows<2, 8, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 8: vertical_rows<4, 1, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 9: vertical_rows<4, 2, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 10: vertical_rows<4, 4, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 11: vertical_rows<4, 8, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 12: vertical_rows<8, 1, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 13: vertical_rows<8, 2, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 14: vertical_rows<8, 4, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        default: vertical_rows<8, 8, true>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 0: vertical_rows<1, 1, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 1: vertical_rows<1, 2, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 2: vertical_rows<1, 4, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 3: vertical_rows<1, 8, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 4: vertical_rows<2, 1, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 5: vertical_rows<2, 2, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 6: vertical_rows<2, 4, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 7: vertical_rows<2, 8, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 8: vertical_rows<4, 1, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 9: vertical_rows<4, 2, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 10: vertical_rows<4, 4, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 11: vertical_rows<4, 8, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 12: vertical_rows<8, 1, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 13: vertical_rows<8, 2, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 14: vertical_rows<8, 4, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        default: vertical_rows<8, 8, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
         }
         return;
     }
-    vertical_narrow(cp, &s_lut, s_lum, s_cu, s_cv, s_out, tile_dst, fr.dst_stride, x0, y0, y1, llo, clo);
+    vertical_narrow<DST>(cp, &s_lut, s_lum, s_cu, s_cv, s_out, tile_dst, fr.dst_stride, x0, y0, y1, llo, clo);
 }
 
 /* ---- planar destinations: yuv420p -> yuv420p / yuv422p / yuv444p ----------------------------------------------------------
@@ -1769,15 +1855,38 @@ __device__ __forceinline__ void c24_line(const LutLds &t, uint8_t *d, uint32_t y
     for (int k = 0; k < 8; k++) Y[k] = ((k < 4 ? y0 : y1) >> (8 * (k & 3))) & 0xFF;
     rgb24_store8(t, d, Y, r, g, b);
 }
+template <int DST> __device__ __forceinline__ void c24_line_d(const LutLds &t, uint8_t *d, uint32_t y0, uint32_t y1, const int *r, const int *g, const int *b, uint32_t sel)
+{
+    if constexpr (DST == DST_RGB32) {
+        int Y[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) Y[k] = ((k < 4 ? y0 : y1) >> (8 * (k & 3))) & 0xFF;
+        rgb32_store8(t, d, Y, r, g, b, sel);
+    } else c24_line(t, d, y0, y1, r, g, b);
+}
 /* yuv2rgb_c_24_rgb (yuv2rgb.c:335-363): a block converts a 512 x 16 sample tile; a thread takes eight samples of two
  * lines per step (8-byte luma loads, 4-byte chroma loads, three 8-byte stores per line) — one (U,V) pair serves both
  * lines (LOADCHROMA :67-72, nearest chroma).  Unaligned planes and the right edge go pair by pair. */
 /* CS 1: an 8-bit yuv422p source — the reference doubles the chroma strides and so reads every other chroma line (yuv2rgb.c:133-136): line
  * (y >> 1) << 1 at the frame's own stride */
-template <int CS = 0>
-__global__ void __launch_bounds__(NT) k_sws_c24(const mi355_sws_luts *luts, int dstW, int sliceH, int sliceY, const mi355_sws_frame *frames)
+/* DST: the destination form — DST_BGR24: yuv2rgb_c_24_bgr (yuv2rgb.c:366-394), DST_RGB32: yuv2rgb_c_32 (:237-265), a thread's eight samples of a line
+ * two 16-byte stores.  The kernel has no context record, so the 32-bit form takes the order's byte selector beside the slice's first row: its fourth
+ * argument is a C24Slice (the 24-bit forms keep the int) */
+struct C24Slice { int y; uint32_t sel; };
+template <int DST> struct C24Arg { typedef int type; };
+template <> struct C24Arg<DST_RGB32> { typedef C24Slice type; };
+__host__ __device__ __forceinline__ int c24_slice_y(int a) { return a; }
+__host__ __device__ __forceinline__ int c24_slice_y(const C24Slice &a) { return a.y; }
+__host__ __device__ __forceinline__ uint32_t c24_slice_sel(int) { return 0; }
+__host__ __device__ __forceinline__ uint32_t c24_slice_sel(const C24Slice &a) { return a.sel; }
+template <int CS = 0, int DST = DST_RGB24>
+__global__ void __launch_bounds__(NT) k_sws_c24(const mi355_sws_luts *luts, int dstW, int sliceH, typename C24Arg<DST>::type slice, const mi355_sws_frame *frames)
 {
     __shared__ LutLds s_lut;
+    constexpr int BPP = dst_bpp<DST>();
+    constexpr uintptr_t WIDE_MASK = DST == DST_RGB32 ? 15 : 7;       /* of the destination: 16-byte stores; the 24-bit forms 8-byte ones */
+    const int sliceY = c24_slice_y(slice);
+    const uint32_t sel = c24_slice_sel(slice);
     const int tid = threadIdx.x;
     /* the frame fix-up and the coordinate / mine / wide lines are k_sws_ident1's too: a helper for either was tried and gave another
      * instruction stream of both kernels */
@@ -1789,7 +1898,8 @@ __global__ void __launch_bounds__(NT) k_sws_c24(const mi355_sws_luts *luts, int 
     const bool mine = (x >> 1) < npairs;
     const bool wide = mine && (x >> 1) + 4 <= npairs &&
                       ((reinterpret_cast<uintptr_t>(fr.src[0]) | (uintptr_t)fr.src_stride[0] | reinterpret_cast<uintptr_t>(fr.dst) | (uintptr_t)fr.dst_stride) & 7) == 0 &&
-                      ((reinterpret_cast<uintptr_t>(fr.src[1]) | (uintptr_t)fr.src_stride[1] | reinterpret_cast<uintptr_t>(fr.src[2]) | (uintptr_t)fr.src_stride[2]) & 3) == 0;
+                      ((reinterpret_cast<uintptr_t>(fr.src[1]) | (uintptr_t)fr.src_stride[1] | reinterpret_cast<uintptr_t>(fr.src[2]) | (uintptr_t)fr.src_stride[2]) & 3) == 0 &&
+                      (WIDE_MASK == 7 || ((reinterpret_cast<uintptr_t>(fr.dst) | (uintptr_t)fr.dst_stride) & WIDE_MASK) == 0);
     /* the samples of both of the thread's line pairs are requested before the LUT copy below: the block pays one memory
      * round trip, not three (LUT, first pair, second pair) */
     constexpr int NR = C24_ROWS / 2 / (NT / 64);
@@ -1817,21 +1927,21 @@ __global__ void __launch_bounds__(NT) k_sws_c24(const mi355_sws_luts *luts, int 
         if (y >= sliceH) break;
         const uint8_t *py1 = fr.src[0] + (size_t)y * fr.src_stride[0] + x, *py2 = py1 + fr.src_stride[0];
         const uint8_t *pu = fr.src[1] + (size_t)((y >> 1) << CS) * fr.src_stride[1] + (x >> 1), *pv = fr.src[2] + (size_t)((y >> 1) << CS) * fr.src_stride[2] + (x >> 1);
-        uint8_t *d1 = fr.dst + (size_t)(y + sliceY) * fr.dst_stride + (size_t)x * 3, *d2 = d1 + fr.dst_stride;
+        uint8_t *d1 = fr.dst + (size_t)(y + sliceY) * fr.dst_stride + (size_t)x * BPP, *d2 = d1 + fr.dst_stride;
         if (wide) {
             const sws_u32x2 a = ya[q], c = yc[q];
             int r[4], g[4], b[4];
 #pragma unroll
             for (int p = 0; p < 4; p++) {
                 const int U = (u4[q] >> (8 * p)) & 0xFF, V = (v4[q] >> (8 * p)) & 0xFF;
-                lut_rows(s_lut, U, V, r[p], g[p], b[p]);
+                lut_rows_d<DST>(s_lut, U, V, r[p], g[p], b[p]);
             }
-            c24_line(s_lut, d1, a[0], a[1], r, g, b);
-            c24_line(s_lut, d2, c[0], c[1], r, g, b);
+            c24_line_d<DST>(s_lut, d1, a[0], a[1], r, g, b, sel);
+            c24_line_d<DST>(s_lut, d2, c[0], c[1], r, g, b, sel);
         } else {
             for (int p = 0; p < 4 && (x >> 1) + p < npairs; p++) {
-                write_pair(s_lut, d1 + 6 * p, py1[2 * p], py1[2 * p + 1], pu[p], pv[p]);
-                write_pair(s_lut, d2 + 6 * p, py2[2 * p], py2[2 * p + 1], pu[p], pv[p]);
+                write_pair_d<DST>(s_lut, d1 + 2 * BPP * p, py1[2 * p], py1[2 * p + 1], pu[p], pv[p], sel);
+                write_pair_d<DST>(s_lut, d2 + 2 * BPP * p, py2[2 * p], py2[2 * p + 1], pu[p], pv[p], sel);
             }
         }
     }
@@ -1849,11 +1959,14 @@ __global__ void __launch_bounds__(NT) k_sws_c24(const mi355_sws_luts *luts, int 
  * trips per workgroup instead of the tile's staging rounds and barriers).  Only for even dstW (the phantom partner of an odd width's last sample stays with k_sws_generic). */
 /* NV: an NV12 / NV21 source — per tap line one 8-byte load of four pairs from fr.src[1] in place of the two 4-byte loads, U and V out of it with
  * one permute each; the wide form asks the pair plane for 8-byte multiples; fr.src[2] is not read */
-template <bool X, bool NV = false>
+/* DST: the destination form, as k_sws_generic's (the selector of a 32-bit order from the record; its wide form asks the destination for 16-byte multiples) */
+template <bool X, bool NV = false, int DST = DST_RGB24>
 __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355_sws_frame *frames)
 {
     __shared__ LutLds s_lut;
     constexpr int NC = X ? 4 : 2;
+    constexpr int BPP = dst_bpp<DST>();
+    const uint32_t sel = DST == DST_RGB32 ? cp->dst_sel : 0u;
     const int tid = threadIdx.x;
     const int dstW = cp->dstW, dstH = cp->dstH, cs = cp->vcs, srcH = cp->srcH, chrSrcH = cp->chrSrcH;
     /* only the vertical banks and five sizes of the record: read one by one */
@@ -1867,6 +1980,7 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
     const bool mine = (x >> 1) < npairs;
     bool wide = mine && (x >> 1) + 4 <= npairs &&
                 ((reinterpret_cast<uintptr_t>(fr.src[0]) | (uintptr_t)fr.src_stride[0] | reinterpret_cast<uintptr_t>(fr.dst) | (uintptr_t)fr.dst_stride) & 7) == 0;
+    if constexpr (DST == DST_RGB32) wide = wide && ((reinterpret_cast<uintptr_t>(fr.dst) | (uintptr_t)fr.dst_stride) & 15) == 0;
     if constexpr (NV) wide = wide && ((reinterpret_cast<uintptr_t>(fr.src[1]) | (uintptr_t)fr.src_stride[1]) & 7) == 0;
     else wide = wide && ((reinterpret_cast<uintptr_t>(fr.src[1]) | (uintptr_t)fr.src_stride[1] | reinterpret_cast<uintptr_t>(fr.src[2]) | (uintptr_t)fr.src_stride[2]) & 3) == 0;
     const int vu = NV && cp->src_layout == MI355_SWS_SRC_NV21;      /* the first byte of a pair is V */
@@ -1914,7 +2028,7 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
     for (int q = 0; q < NR; q++) {
         const int gy = blockIdx.y * IDENT_ROWS + (tid >> 6) + q * (NT / 64);
         if (gy >= dstH) break;
-        uint8_t *d = fr.dst + (size_t)gy * fr.dst_stride + (size_t)x * 3;
+        uint8_t *d = fr.dst + (size_t)gy * fr.dst_stride + (size_t)x * BPP;
         const bool mean = !X && cs > 1 && cf[q][1] >= 2048;
         /* one pair of the row from its bytes: two luma samples, the pair's chroma sample of each tap line */
         auto pair = [&](int y1, int y2, const int *us, const int *vs, int &Y1, int &Y2, int &U, int &V) {
@@ -1947,9 +2061,11 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
                 for (int j = 0; j < NC; j++) { us[j] = (u[q][j] >> (8 * p)) & 0xFF; vs[j] = (v[q][j] >> (8 * p)) & 0xFF; }
                 const uint32_t w = ya[q][p >> 1] >> (16 * (p & 1));
                 pair((int)(w & 0xFF), (int)((w >> 8) & 0xFF), us, vs, Y[2 * p], Y[2 * p + 1], U, V);
-                lut_rows(s_lut, U, V, r[p], g[p], b[p]);
+                lut_rows_d<DST>(s_lut, U, V, r[p], g[p], b[p]);
             }
-            rgb24_store8(s_lut, d, Y, r, g, b);
+            /* (through store8_d the rgb24 instances got another instruction stream: the two stores are named here) */
+            if constexpr (DST == DST_RGB32) rgb32_store8(s_lut, d, Y, r, g, b, sel);
+            else rgb24_store8(s_lut, d, Y, r, g, b);
         } else {
             const uint8_t *py = fr.src[0] + (size_t)li[q] * fr.src_stride[0] + x;
             for (int p = 0; p < 4 && (x >> 1) + p < npairs; p++) {
@@ -1965,7 +2081,7 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
                     }
                 }
                 pair(py[2 * p], py[2 * p + 1], us, vs, Y1, Y2, U, V);
-                write_pair(s_lut, d + 6 * p, Y1, Y2, U, V);
+                write_pair_d<DST>(s_lut, d + 2 * BPP * p, Y1, Y2, U, V, sel);
             }
         }
     }
@@ -2035,6 +2151,7 @@ __global__ void __launch_bounds__(NT) k_sws_line_nv12(const int16_t *filter, int
         dest[2 * i + (swap_uv ? 0 : 1)] = (uint8_t)clip_u8(v >> 19);
     }
 }
+#endif
 struct PackedRows {
     const int16_t *l, *u, *v;
     int pitch;
@@ -2042,6 +2159,21 @@ struct PackedRows {
     __device__ __forceinline__ int cu(int j, int x) const { return u[(size_t)j * pitch + x]; }
     __device__ __forceinline__ int cv(int j, int x) const { return v[(size_t)j * pitch + x]; }
 };
+/* yuv2rgb_X_c / _2_c / _1_c (output.c:937-1110) with target bgr24 (DST_BGR24) or one of the four 32-bit orders (DST_RGB32, `sel`: sws_rgb32_sel): the
+ * line kernel below with the destination form of the whole-picture kernels; dest holds (dstW + 1) >> 1 pairs of 2 * dst_bpp<DST>() bytes */
+template <int DST>
+__global__ void __launch_bounds__(NT) k_sws_line_packed(const mi355_sws_luts *luts, int mode, const int16_t *lumF, const int16_t *l, int ls,
+                                                        const int16_t *chrF, const int16_t *u, const int16_t *v, int cs, int pitch, uint8_t *dest,
+                                                        int dstW, int yalpha, int uvalpha, uint32_t sel)
+{
+    __shared__ LutLds s_lut;
+    lut_load(s_lut, luts, threadIdx.x);
+    __syncthreads();
+    PackedRows R{ l, u, v, pitch };
+    for (int i = threadIdx.x; i < ((dstW + 1) >> 1); i += NT)
+        rgb_pair<DST>(s_lut, dest + (size_t)i * 2 * dst_bpp<DST>(), R, i, mode, lumF, ls, chrF, cs, yalpha, uvalpha, sel);
+}
+#ifndef MI355_SWS_TILE_KERNELS_ONLY
 __global__ void __launch_bounds__(NT) k_sws_line_rgb(const mi355_sws_luts *luts, int mode, const int16_t *lumF, const int16_t *l, int ls,
                                                      const int16_t *chrF, const int16_t *u, const int16_t *v, int cs, int pitch, uint8_t *dest,
                                                      int dstW, int yalpha, int uvalpha)
@@ -2059,5 +2191,15 @@ __global__ void __launch_bounds__(NT) k_sws_line_rgb(const mi355_sws_luts *luts,
  * src 0 8-bit planes, 1 16-bit planes, 2 NV12 / NV21, 3 rgb24 / bgr24, full_cw: a 4:4:4 destination (CW = TW).  The DEEP instances are compiled
  * in a file of their own */
 void mi355_sws_launch_planar_deep(int i, int src, int full_cw, dim3 grid, hipStream_t s, const void *d, const mi355_sws_planar_frame *frames);
+
+/* sws_packed.hip: the launches of the DST_BGR24 / DST_RGB32 instances of the packed kernels for a context (d: its SwsDev on the device; dst_format:
+ * MI355_SWS_DST_BGR24 ... _ABGR) — k: MI355_SWS_K_C24 / IDENT1_1 / IDENT1_X / GENERIC_A .. C as sws_kernel() gave it, src as above (c24: 1 — every other
+ * chroma line, an 8-bit yuv422p source; ident1: 2 — NV12 / NV21).  The grids are those of the rgb24 twin.  Compiled in a file of their own. */
+void mi355_sws_launch_packed(int k, int src, int dst_format, dim3 grid, hipStream_t s, const void *d, int dstW, int sliceH, const mi355_sws_frame *frames);
+/* ... and of the line kernel k_sws_line_packed (one workgroup), the arguments of k_sws_line_rgb */
+void mi355_sws_launch_line_packed(int dst_format, hipStream_t s, const mi355_sws_luts *luts, int mode, const int16_t *lumF, const int16_t *l, int ls, const int16_t *chrF,
+                                  const int16_t *u, const int16_t *v, int cs, int pitch, uint8_t *dest, int dstW, int yalpha, int uvalpha);
+/* ... and of k_sws_c24 on one slice with stand-alone tables (mi355_sws_yuv2rgb_c: a 4:2:0 slice) */
+void mi355_sws_launch_c24_slice(int dst_format, dim3 grid, hipStream_t s, const mi355_sws_luts *luts, int dstW, int rows, const mi355_sws_frame *frames);
 
 #endif

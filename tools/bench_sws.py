@@ -50,6 +50,11 @@ def main():
                          "build — identical banks and source traffic, half the destination bytes: 2160p -> 1080p yuv420p10le and 1080p 4:2:0 -> "
                          "yuv422p10le at equal size, each from yuv420p10le, yuv420p and nv12; the twin a second time in another allocation (A/A); 32 "
                          "and 512 pictures per launch, 3 warm-up + --steps launches a round, alternating, median of 3 rounds")
+    ap.add_argument("--packeddst", action="store_true",
+                    help="bgr24 and 32-bit (bgra) destinations beside THE SAME descriptor created as rgb24 on the same build — identical banks, LUTs and "
+                         "source traffic; bgr24 the same destination bytes, bgra a third more: 2160p -> 1080p from yuv420p, nv12 and yuv420p10le, 1080p at "
+                         "equal size through k_sws_ident1 and through the special converter; the twin a second time in another allocation (A/A); 32 and "
+                         "512 pictures per launch, 3 warm-up + --steps launches a round, alternating, median of 3 rounds")
     ap.add_argument("--other-lib", default=None,
                     help="--nv12 / --nvsrc / --rgbsrc / --range: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
     ap.add_argument("--rounds", type=int, default=5, help="--planar / --sources: alternating rounds (the median is reported)")
@@ -72,6 +77,8 @@ def main():
         return range_points(a, lib)
     if a.deepdst:
         return deepdst_points(a, lib)
+    if a.packeddst:
+        return packeddst_points(a, lib)
     orc = S.oracle_backend(providers.oracle())
     for name in a.configs.split(","):
         ctx = S.load_context(name)
@@ -152,7 +159,7 @@ class SourceBatch:
     """`frames` pictures of one entry of tests/sws_sources.py resident in HBM, each with its own source planes (the first two uploaded, the
     rest device-side copies) and its own rgb24 destination"""
 
-    def __init__(self, lib, X, e, pics, frames, create=None):
+    def __init__(self, lib, X, e, pics, frames, create=None, bpp=3):
         self.lib, self.bufs, self.n = lib, [], frames
         lib.mi355_malloc.restype = C.c_void_p
         lib.mi355_malloc.argtypes = [C.c_size_t]
@@ -175,10 +182,10 @@ class SourceBatch:
                 done += k
             for f in range(frames):
                 arr[f].src[p], arr[f].src_stride[p] = base + f * psz, pics[0][p].strides[0]
-        self.dst_bytes = d.dstW * 3 * d.dstH
+        self.dst_bytes = d.dstW * bpp * d.dstH                # (bpp 4: a 32-bit packed destination, tests/sws_packeddst.py)
         dst = self.alloc(frames * self.dst_bytes + 64)
         for f in range(frames):
-            arr[f].dst, arr[f].dst_stride = dst + f * self.dst_bytes, d.dstW * 3
+            arr[f].dst, arr[f].dst_stride = dst + f * self.dst_bytes, d.dstW * bpp
         self.d_frames = self.alloc(C.sizeof(arr))
         lib.mi355_memcpy_h2d(self.d_frames, C.addressof(arr), C.sizeof(arr))
         self.handle = (create or X.create)(lib, e)
@@ -678,6 +685,59 @@ def deepdst_points(a, lib, points=None, frame_counts=(32, 512)):
                                   "algorithmic_bytes_per_frame": nb, "achieved_GBps": nb / us * 1e-3, "frac_of_8TBps": nb / us * 1e-3 / 8000.0,
                                   "vs_depth8": ms / base - 1.0, "bound": nb / twin_bytes - 1.0, "kernel": plan["kernel"], "hstaged": plan["hstaged"],
                                   "dst_depth": plan["dst_depth"] if k == "deep" else 8, "ms_rounds": [round(x, 4) for x in times[k]]}), flush=True)
+            for b in batches.values():
+                b.close()
+
+
+def packeddst_points(a, lib, points=None, frame_counts=(32, 512)):
+    """A bgr24 and a 32-bit (bgra) destination beside their twin: the same descriptor created as rgb24 on the same build has identical banks, LUTs
+    and source traffic; bgr24 writes the same destination bytes, bgra a third more.  The contexts come from the reference's libswscale at run time
+    (oracle/_ref/libswsref.so: mi355_sws_describe_packed) — no full-size context is committed.  `rgb24#2` is the twin a second time with its own
+    buffers: the session's A/A spread.  One process, the batches of a point alternating: 3 warm-up + --steps launches a round, median of 3 rounds,
+    at 32 and 512 pictures per launch.  Algorithmic bytes: sources read once + destinations written once.  `bound`: the extra destination bytes
+    over the twin's algorithmic bytes — what the context may cost if it moves them at the twin's achieved bandwidth (0 for bgr24; the A/A spread
+    comes on top)."""
+    import statistics
+    import sws_nvsrc as V
+    import sws_packeddst as K
+    import sws_planar as P
+    import sws_sources as X
+    ref = K.Ref(P.bind(K.REF_LIB))
+    rounds = 3
+    # (point, srcW, srcH, dstW, dstH, source, accurate_rnd / bitexact: 0 at equal size is the unscaled special converter)
+    points = points or [("uhd_to_hd_%s" % s, 3840, 2160, 1920, 1080, s, 1) for s in ("yuv420p", "nv12", "yuv420p10le")] + \
+                       [("hd_same_yuv420p_ident1", 1920, 1080, 1920, 1080, "yuv420p", 1), ("hd_same_yuv420p_special", 1920, 1080, 1920, 1080, "yuv420p", 0)]
+    for frames in frame_counts:
+        for point, sw, sh, dw, dh, src, acc in points:
+            entries = {}
+            for dst in ("bgr24", "bgra"):
+                row = (sw, sh, dw, dh, src, dst, 1, acc, acc)          # a row of tests/sws_packeddst.py's table, not entered into it
+                c = ref.open(row)
+                entries[dst] = ref.describe_packed(c)
+                ref.free(c)
+                assert entries[dst] is not None and entries[dst].fmt == K.DSTS[dst], point
+            pics = [K.picture(row, "noise", seed=s) for s in (1, 2)]
+            e = entries["bgr24"]
+            twin = V.Entry(e.ctx, e.depth, e.hsub, e.vsub, e.dither, 0, e.layout)     # bgr24 has the rgb24 tables (tests/test_sws_packeddst_emu.py)
+            batches = {"bgr24": SourceBatch(lib, X, entries["bgr24"], pics, frames, create=K.create),
+                       "bgra": SourceBatch(lib, X, entries["bgra"], pics, frames, create=K.create, bpp=4),
+                       "rgb24": SourceBatch(lib, X, twin, pics, frames, create=K.create),
+                       "rgb24#2": SourceBatch(lib, X, twin, pics, frames, create=K.create)}
+            plan = K.plan_of(lib, batches["bgra"].handle)
+            times = {k: [] for k in batches}
+            for _ in range(rounds):
+                for k, b in batches.items():
+                    times[k].append(time_ms(lib, b.run, a.steps))
+            base = statistics.median(times["rgb24"])
+            twin_bytes = batches["rgb24"].src_bytes + batches["rgb24"].dst_bytes
+            for k, b in batches.items():
+                ms = statistics.median(times[k])
+                us = ms * 1e3 / frames
+                nb = b.src_bytes + b.dst_bytes
+                print(json.dumps({"workload": point + ":" + k, "frames_per_launch": frames, "ms_per_launch": ms, "us_per_picture": us, "frames_per_s": 1e6 / us,
+                                  "algorithmic_bytes_per_frame": nb, "achieved_GBps": nb / us * 1e-3, "frac_of_8TBps": nb / us * 1e-3 / 8000.0,
+                                  "vs_rgb24": ms / base - 1.0, "bound": nb / twin_bytes - 1.0, "kernel": plan["kernel"], "hstaged": plan["hstaged"],
+                                  "ms_rounds": [round(x, 4) for x in times[k]]}), flush=True)
             for b in batches.values():
                 b.close()
 
