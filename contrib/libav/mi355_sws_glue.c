@@ -73,6 +73,18 @@
  *                          MI355_SWS_LINES=1 c->yuv2packedX / 2 / 1 go to mi355_sws_yuv2packed_X / _2 / _1.  Declined: SWS_FULL_CHR_H_INT,
  *                          SWS_FAST_BILINEAR, a source with alpha, 15 / 16-bit and lower RGB, rgb48 / rgba64, planar GBR, rgbToRgbWrapper.  The six
  *                          describers above keep declining these destinations; this one declines rgb24.
+ *   32-bit RGB sources     rgba, bgra, argb and abgr (the reference runs rgb32ToY_c / bgr32ToY_c / rgb321ToY_c / bgr321ToY_c, their ...ToUV_c or
+ *                          ...ToUV_half_c forms and — where source AND destination have alpha — rgbaToA_c / abgrToA_c on each line, then the
+ *                          ordinary hyScale / hcScale) take the same two forms to every destination above through ONE describer,
+ *                          mi355_sws_describe_rgb32(), which also reports range, depth and alpha, and mi355_sws_create_src_layout_range_depth() /
+ *                          mi355_sws_create_src_layout_alpha().  The converters the context holds are probed with one pixel (rgb32_probe, as
+ *                          range_probe does: they are static functions), alpToYV12 must be set exactly when the context has an alpha buffer;
+ *                          layout, destination, range, depth and alpha are remembered and described again on every call.  Whole pictures hand
+ *                          over ONE source plane; a plane whose pointer or stride is no multiple of 4 is the reference's for that picture
+ *                          (mi355_sws_scale returns -1).  With MI355_SWS_LINES=1 the three input converters go to mi355_sws_rgb32ToY / _rgb32ToUV /
+ *                          _rgb32ToA and the packed loops of an alpha context to mi355_sws_yuv2packed_X_a / _2_a / _1_a.  Declined: the unscaled
+ *                          converters of these sources (rgbToRgbWrapper, the plain copy: no banks), YUVA on either side, 15 / 16-bit RGB,
+ *                          SWS_FULL_CHR_H_INT, SWS_FAST_BILINEAR.  The seven describers above keep declining these sources.
  * The device is MI355_DEVICE (default 0), as for the decoder bridges.
  */
 #include <pthread.h>
@@ -450,6 +462,88 @@ int mi355_sws_describe_packed(struct SwsContext *c, mi355_sws_desc *d, mi355_sws
     return 0;
 }
 
+/* ---- packed 32-bit sources: rgba, bgra, argb, abgr -----------------------------------------------------------------------------------------
+ * The MI355_SWS_SRC_* of such a source, 0 for any other format (the reference's RGB32 / BGR32 / _1 names are host-endian aliases: resolved here) */
+static int rgb32_layout_of(const SwsContext *c)
+{
+    switch (c->srcFormat) {
+    case AV_PIX_FMT_RGBA: return MI355_SWS_SRC_RGBA;
+    case AV_PIX_FMT_BGRA: return MI355_SWS_SRC_BGRA;
+    case AV_PIX_FMT_ARGB: return MI355_SWS_SRC_ARGB;
+    case AV_PIX_FMT_ABGR: return MI355_SWS_SRC_ABGR;
+    default: return 0;
+    }
+}
+/* the input converters the context HOLDS are the 32-bit ones of `layout` (the functions are static in the reference: one pixel through each, as
+ * range_probe does).  The pixel has its first colour byte at 255, the other two at 0 and alpha at 0x5A; rgb24ToY_c / rgb24ToUV_c give
+ * 16 + (K0 * 255 >> 15) ... for it, and the four orders differ in K0 and in where the colour bytes start */
+static int rgb32_probe(const SwsContext *c, int layout, int alpha)
+{
+    static const int RY = 8414, BY = 3208, RU = -4865, BU = 14392, RV = 14392, BV = -2332;      /* input.c:38-47 at RGB2YUV_SHIFT 15 */
+    const int bgr = layout == MI355_SWS_SRC_BGRA || layout == MI355_SWS_SRC_ABGR, first = layout == MI355_SWS_SRC_ARGB || layout == MI355_SWS_SRC_ABGR;
+    uint32_t px[4] = { 0, 0, 0, 0 };
+    uint8_t *b = (uint8_t *)px, y[4] = { 0 }, u[4] = { 0 }, v[4] = { 0 }, a[4] = { 0 };
+    if (!c->lumToYV12 || !c->chrToYV12 || (c->alpToYV12 != NULL) != (alpha != 0)) return -1;
+    for (int i = 0; i < 2; i++) { b[4 * i + first] = 255; b[4 * i + (first ? 0 : 3)] = 0x5A; }
+    c->lumToYV12(y, b, 1, NULL);
+    c->chrToYV12(u, v, b, b, 1, NULL);                            /* (the halving form reads both pixels: the same value) */
+    if (alpha) c->alpToYV12(a, b, 1, NULL);
+    if (y[0] != (((bgr ? BY : RY) * 255 + (33 << 14)) >> 15) || u[0] != (((bgr ? BU : RU) * 255 + (257 << 14)) >> 15) ||
+        v[0] != (((bgr ? BV : RV) * 255 + (257 << 14)) >> 15)) return -1;
+    return !alpha || a[0] == 0x5A ? 0 : -1;
+}
+/* what mi355_sws_create_src_layout_range_depth takes for a live context FROM one of the four formats (0), -1 for every other context — the seven
+ * describers above keep declining these sources.  The generic scaler's contexts only (the unscaled converters of these sources — rgbToRgbWrapper,
+ * the plain copy, the ...ToYv12 wrappers — have no banks): both input converters the 32-bit ones (rgb32_probe), no other reader; to rgb24, to bgr24
+ * and the four 32-bit orders, to 8-bit planar / semi-planar YUV with or without range converters, to 9- / 10-bit planar YUV.
+ * *alpha: the context carries the source's alpha plane to its 32-bit destination (c->alpPixBuf: both formats have alpha, utils.c:1244) — it then
+ * holds alpToYV12 too, and exactly then; the device writes 255 there, so a caller hands such a context over only for pictures whose alpha is 255
+ * everywhere or keeps it with the reference.  Declined: SWS_FULL_CHR_H_INT, SWS_FAST_BILINEAR, a chroma line drop, YUVA destinations, 15 / 16-bit RGB */
+int mi355_sws_describe_rgb32(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *src_layout, int *dst_format, int *range, int *dst_depth, int *alpha)
+{
+    const int layout = rgb32_layout_of(c);
+    int fmt, bits = 8;
+    if (!layout || !c->vLumFilter || !c->vChrFilter || !c->hLumFilter || !c->hChrFilter) return -1;
+    if (c->hyscale_fast || c->hcscale_fast || c->vChrDrop || (c->flags & SWS_FULL_CHR_H_INT)) return -1;
+    if (c->chrSrcVSubSample != 0 || (c->chrSrcHSubSample & ~1) || c->srcBpc != 8 || c->readLumPlanar || c->readChrPlanar || c->readAlpPlanar) return -1;
+    *alpha = c->alpPixBuf != NULL;
+    if (rgb32_probe(c, layout, *alpha) != 0) return -1;
+    const int r = range_probe(c);
+    if (r < 0) return -1;
+    if (deep_dst(c, &bits)) {
+        if (r || c->dstBpc != bits) return -1;
+        fmt = deep_dst(c, &bits);
+    } else if (packed_dst_of(c) || c->dstFormat == AV_PIX_FMT_RGB24) {
+        if (r) return -1;
+        fmt = packed_dst_of(c);
+    } else {
+        switch (c->dstFormat) {
+        case AV_PIX_FMT_YUV420P: fmt = MI355_SWS_DST_YUV420P; break;
+        case AV_PIX_FMT_YUV422P: fmt = MI355_SWS_DST_YUV422P; break;
+        case AV_PIX_FMT_YUV444P: fmt = MI355_SWS_DST_YUV444P; break;
+        case AV_PIX_FMT_NV12:    fmt = MI355_SWS_DST_NV12; break;
+        case AV_PIX_FMT_NV21:    fmt = MI355_SWS_DST_NV21; break;
+        default: return -1;
+        }
+    }
+    if (*alpha && fmt < MI355_SWS_DST_RGBA) return -1;            /* (the reference allocates alpPixBuf for a destination with alpha only) */
+    const int yuv = fmt >= MI355_SWS_DST_YUV420P && fmt <= MI355_SWS_DST_NV21;
+    memset(s, 0, sizeof(*s));
+    s->depth = 8; s->hsub = c->chrSrcHSubSample; s->vsub = 0;
+    memcpy(s->dither, ff_dither_8x8_128, sizeof(s->dither));
+    memset(d, 0, sizeof(*d));
+    d->srcW = c->srcW; d->srcH = c->srcH; d->dstW = c->dstW; d->dstH = c->dstH;
+    d->chrSrcW = c->chrSrcW; d->chrSrcH = c->chrSrcH; d->chrDstW = c->chrDstW;
+    d->hLum = (mi355_sws_filter){ c->hLumFilter, c->hLumFilterPos, c->hLumFilterSize, c->dstW };
+    d->hChr = (mi355_sws_filter){ c->hChrFilter, c->hChrFilterPos, c->hChrFilterSize, c->chrDstW };
+    d->vLum = (mi355_sws_filter){ c->vLumFilter, c->vLumFilterPos, c->vLumFilterSize, c->dstH };
+    d->vChr = (mi355_sws_filter){ c->vChrFilter, c->vChrFilterPos, c->vChrFilterSize, yuv ? c->chrDstH : c->dstH };
+    if (!fmt) luts_of(c, &d->luts);
+    else if (!yuv) luts_packed(c, fmt, &d->luts);
+    *src_layout = layout; *dst_format = fmt; *range = r; *dst_depth = bits;
+    return 0;
+}
+
 #ifndef MI355_SWS_DESCRIBE_ONLY
 static void t1_hscale16(SwsContext *c, int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
 {
@@ -570,16 +664,97 @@ static void rgb_converters(SwsContext *c, int layout)
     c->chrToYV12 = c->chrSrcHSubSample ? (bgr ? t1_bgr24ToUV_half : t1_rgb24ToUV_half) : (bgr ? t1_bgr24ToUV : t1_rgb24ToUV);
 }
 
+/* ... of a 32-bit source (rgb32ToY_c ... bgr321ToUV_half_c, rgbaToA_c / abgrToA_c): one shim per byte order and converter */
+#define T1_RGB32(order, layout) \
+static void t1_ ## order ## ToY(uint8_t *dst, const uint8_t *src, int width, uint32_t *pal) { (void)pal; n_calls++; mi355_sws_rgb32ToY(dst, src, width, layout); } \
+static void t1_ ## order ## ToA(uint8_t *dst, const uint8_t *src, int width, uint32_t *pal) { (void)pal; n_calls++; mi355_sws_rgb32ToA(dst, src, width, layout); } \
+static void t1_ ## order ## ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src1, const uint8_t *src2, int width, uint32_t *pal) \
+{ (void)src2; (void)pal; n_calls++; mi355_sws_rgb32ToUV(dstU, dstV, src1, width, layout, 0); } \
+static void t1_ ## order ## ToUV_half(uint8_t *dstU, uint8_t *dstV, const uint8_t *src1, const uint8_t *src2, int width, uint32_t *pal) \
+{ (void)src2; (void)pal; n_calls++; mi355_sws_rgb32ToUV(dstU, dstV, src1, width, layout, 1); }
+T1_RGB32(rgba, MI355_SWS_SRC_RGBA)
+T1_RGB32(bgra, MI355_SWS_SRC_BGRA)
+T1_RGB32(argb, MI355_SWS_SRC_ARGB)
+T1_RGB32(abgr, MI355_SWS_SRC_ABGR)
+static void rgb32_converters(SwsContext *c, int layout, int alpha)
+{
+#define T1_SET(order) do { c->lumToYV12 = t1_ ## order ## ToY; c->chrToYV12 = c->chrSrcHSubSample ? t1_ ## order ## ToUV_half : t1_ ## order ## ToUV; \
+                           if (alpha) c->alpToYV12 = t1_ ## order ## ToA; } while (0)
+    if (layout == MI355_SWS_SRC_RGBA) T1_SET(rgba);
+    else if (layout == MI355_SWS_SRC_BGRA) T1_SET(bgra);
+    else if (layout == MI355_SWS_SRC_ARGB) T1_SET(argb);
+    else if (layout == MI355_SWS_SRC_ABGR) T1_SET(abgr);
+#undef T1_SET
+}
+/* yuv2packedX / 2 / 1 of a 32-bit context that carries alpha (the hasAlpha forms: yuv2rgba32_X_c ...) */
+static void t1_pkX_a(SwsContext *c, const int16_t *lumFilter, const int16_t **lumSrc, int lumFilterSize, const int16_t *chrFilter,
+                     const int16_t **chrUSrc, const int16_t **chrVSrc, int chrFilterSize, const int16_t **alpSrc, uint8_t *dest, int dstW, int y)
+{
+    mi355_sws_luts t;
+    const int fmt = packed_dst_of(c);
+    (void)y; n_calls++;
+    luts_packed(c, fmt, &t);
+    mi355_sws_yuv2packed_X_a(&t, fmt, lumFilter, lumSrc, lumFilterSize, chrFilter, chrUSrc, chrVSrc, chrFilterSize, alpSrc, dest, dstW);
+}
+static void t1_pk2_a(SwsContext *c, const int16_t *lumSrc[2], const int16_t *chrUSrc[2], const int16_t *chrVSrc[2], const int16_t *alpSrc[2],
+                     uint8_t *dest, int dstW, int yalpha, int uvalpha, int y)
+{
+    mi355_sws_luts t;
+    const int fmt = packed_dst_of(c);
+    (void)y; n_calls++;
+    luts_packed(c, fmt, &t);
+    mi355_sws_yuv2packed_2_a(&t, fmt, lumSrc, chrUSrc, chrVSrc, alpSrc, dest, dstW, yalpha, uvalpha);
+}
+static void t1_pk1_a(SwsContext *c, const int16_t *lumSrc, const int16_t *chrUSrc[2], const int16_t *chrVSrc[2], const int16_t *alpSrc,
+                     uint8_t *dest, int dstW, int uvalpha, int y)
+{
+    mi355_sws_luts t;
+    const int fmt = packed_dst_of(c);
+    (void)y; n_calls++;
+    luts_packed(c, fmt, &t);
+    mi355_sws_yuv2packed_1_a(&t, fmt, lumSrc, chrUSrc, chrVSrc, alpSrc, dest, dstW, uvalpha);
+}
+
 /* lumConvertRange / chrConvertRange: no context in their argument lists either, one shim per direction */
 static void t1_lumFromJpeg(int16_t *dst, int width) { n_calls++; mi355_sws_lumConvertRange(dst, width, 0); }
 static void t1_lumToJpeg(int16_t *dst, int width) { n_calls++; mi355_sws_lumConvertRange(dst, width, 1); }
 static void t1_chrFromJpeg(int16_t *dstU, int16_t *dstV, int width) { n_calls++; mi355_sws_chrConvertRange(dstU, dstV, width, 0); }
 static void t1_chrToJpeg(int16_t *dstU, int16_t *dstV, int width) { n_calls++; mi355_sws_chrConvertRange(dstU, dstV, width, 1); }
 
+/* the inner loops of a context from a 32-bit source (mi355_sws_describe_rgb32 takes it): the three input converters, the horizontal loops and
+ * the output loops of its destination */
+static int init_rgb32(SwsContext *c)
+{
+    mi355_sws_desc d;
+    mi355_sws_src s;
+    int layout, fmt, range, depth, alpha;
+    if (!rgb32_layout_of(c)) return 0;
+    if (mi355_sws_describe_rgb32(c, &d, &s, &layout, &fmt, &range, &depth, &alpha) != 0 || !device_ready() || !c->hyScale || !c->hcScale) return 1;
+    const int yuv = fmt >= MI355_SWS_DST_YUV420P && fmt <= MI355_SWS_DST_NV21;
+    if (yuv ? (!c->yuv2planeX || !c->yuv2plane1) : (!c->yuv2packedX || !c->yuv2packed2 || !c->yuv2packed1)) return 1;
+    rgb32_converters(c, layout, alpha);
+    c->hyScale = c->hcScale = t1_hscale;
+    if (range > 0) {
+        c->lumConvertRange = range == MI355_SWS_RANGE_TO_JPEG ? t1_lumToJpeg : t1_lumFromJpeg;
+        c->chrConvertRange = range == MI355_SWS_RANGE_TO_JPEG ? t1_chrToJpeg : t1_chrFromJpeg;
+    }
+    if (yuv) {
+        c->yuv2planeX = depth == 9 ? t1_planeX_9 : (depth == 10 ? t1_planeX_10 : t1_planeX);
+        c->yuv2plane1 = depth == 9 ? t1_plane1_9 : (depth == 10 ? t1_plane1_10 : t1_plane1);
+        if (c->yuv2nv12cX) c->yuv2nv12cX = t1_nv12cX;
+    } else if (!fmt) {
+        c->yuv2packedX = t1_packedX; c->yuv2packed2 = t1_packed2; c->yuv2packed1 = t1_packed1;
+    } else {
+        c->yuv2packedX = alpha ? t1_pkX_a : t1_pkX; c->yuv2packed2 = alpha ? t1_pk2_a : t1_pk2; c->yuv2packed1 = alpha ? t1_pk1_a : t1_pk1;
+    }
+    return 1;
+}
+
 void ff_sws_init_mi355x(SwsContext *c)
 {
     mi355_sws_src s;
     int layout;
+    if (init_rgb32(c)) return;
     const int range = range_probe(c);
     /* (an NV12 / NV21 source: c->chrToYV12 stays the reference's) */
     const int fmt = range > 0 ? fmt_format_r(c, &s, 0, &layout, 1) : fmt_format(c, &s, 0, &layout);
@@ -642,6 +817,8 @@ typedef struct Bound {
     int range;                    /* ... the MI355_SWS_RANGE_* its converters gave when it was bound (mi355_sws_describe_range / mi355_sws_create_src_layout_range) */
     int depth;                    /* ... the bits of its planar destination: 8, or 9 / 10 (mi355_sws_describe_depth / mi355_sws_create_src_layout_range_depth) */
     int packed;                   /* ... MI355_SWS_DST_BGR24 ... _ABGR of a packed destination beside rgb24 (mi355_sws_describe_packed), else 0; planar is 0 then */
+    int rgb32;                    /* a 32-bit source (mi355_sws_describe_rgb32: layout, planar / packed, range and depth above are what it gave) ... */
+    int alpha;                    /* ... whose alpha goes to the 32-bit destination (mi355_sws_create_src_layout_alpha) */
     mi355_sws_ctx *dev;
     int failed;                   /* the device side does not take this context: the reference's function from now on */
     int busy;                     /* calls of mi355_sws_scale in flight on `dev` (under bound_mu): the device context is destroyed only at 0 */
@@ -689,6 +866,16 @@ static Bound *bound_find(SwsContext *c, int create)
 static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
 {
     int planar = special ? 0 : planar_format(c), other = 0, layout = MI355_SWS_SRC_PLANAR, range = MI355_SWS_RANGE_NONE, depth = 8, packed = 0;
+    int rgb32 = 0, alpha = 0;
+    if (!special && rgb32_layout_of(c)) {
+        /* a 32-bit source: one describer for every destination it goes to */
+        mi355_sws_desc d;
+        mi355_sws_src s;
+        int fmt;
+        if (mi355_sws_describe_rgb32(c, &d, &s, &layout, &fmt, &range, &depth, &alpha) != 0) return real;
+        rgb32 = other = 1;
+        if (fmt >= MI355_SWS_DST_BGR24) packed = fmt; else planar = fmt;
+    } else
     if (!(taken(c) || planar)) {
         mi355_sws_src s;
         int fmt = fmt_format(c, &s, special, &layout);
@@ -716,7 +903,7 @@ static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
     if (b) {
         slot_release(b);
         b->c = c; b->real = real; b->special = special; b->planar = planar; b->other = other; b->layout = layout; b->range = range; b->depth = depth;
-        b->packed = packed;
+        b->packed = packed; b->rgb32 = rgb32; b->alpha = alpha;
         b->stamp = ++n_stamp;
     }
     pthread_mutex_unlock(&bound_mu);
@@ -738,15 +925,21 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
     const int semi = b && (b->planar == MI355_SWS_DST_NV12 || b->planar == MI355_SWS_DST_NV21);      /* two planes: dstStride[2] is not looked at */
     /* a context bound with range conversion: the converters it holds NOW give the direction it was bound with (range_probe), else the
      * reference's function for that picture too */
-    const int planar_ok = b && b->planar && dstStride[1] > 0 && (semi || dstStride[2] > 0) &&
+    /* a 32-bit source: described again — layout, destination, range, depth and alpha must be what the context was bound with */
+    mi355_sws_desc d32;
+    mi355_sws_src s32;
+    int l32 = 0, f32 = 0, r32 = 0, dp32 = 8, a32 = 0;
+    const int rgb32_ok = b && b->rgb32 && mi355_sws_describe_rgb32(c, &d32, &s32, &l32, &f32, &r32, &dp32, &a32) == 0 && l32 == b->layout &&
+                         f32 == (b->packed ? b->packed : b->planar) && r32 == b->range && dp32 == b->depth && a32 == b->alpha;
+    const int planar_ok = b && b->planar && dstStride[1] > 0 && (semi || dstStride[2] > 0) && (b->rgb32 ? rgb32_ok :
                           (b->other ? fmt_format_r(c, &s_now, 0, &l_now, b->depth > 8 ? MI355_ASK_DEEP : b->range != 0) : planar_format(c)) == b->planar &&
                           (!b->range || range_probe(c) == b->range) &&
-                          (b->depth <= 8 || (deep_dst(c, &d_now) == b->planar && d_now == b->depth));   /* (with converters set since: the reference's) */
+                          (b->depth <= 8 || (deep_dst(c, &d_now) == b->planar && d_now == b->depth)));  /* (with converters set since: the reference's) */
     /* an rgb24 context of another source: range conversion set since it was bound is the reference's for that picture, as above */
-    const int other_ok = !b || !b->other || b->planar || (b->packed ? fmt_format_r(c, &s_now, b->special, &l_now, MI355_ASK_PACKED) == b->packed
-                                                                     : fmt_format(c, &s_now, b->special, &l_now) == 0);
+    const int other_ok = !b || !b->other || (b->rgb32 ? rgb32_ok : (b->planar || (b->packed ? fmt_format_r(c, &s_now, b->special, &l_now, MI355_ASK_PACKED) == b->packed
+                                                                                                  : fmt_format(c, &s_now, b->special, &l_now) == 0)));
     /* an NV12 / NV21 source has two planes: srcStride[2] is not looked at; a packed rgb24 / bgr24 source has one */
-    const int one_plane = b && (b->layout == MI355_SWS_SRC_RGB24 || b->layout == MI355_SWS_SRC_BGR24);
+    const int one_plane = b && (b->layout == MI355_SWS_SRC_RGB24 || b->layout == MI355_SWS_SRC_BGR24 || b->rgb32);
     if (b && !b->failed && srcSliceY == 0 && srcSliceH == c->srcH &&
         srcStride[0] > 0 && (one_plane || srcStride[1] > 0) && (b->layout || srcStride[2] > 0) && dstStride[0] > 0 && (!b->planar || planar_ok) && other_ok) {
         if (b->dev && !b->busy && !b->planar && !b->packed && (memcmp(b->y_table, c->yuvTable, 1024) || b->gv0 != c->table_gV[0])) { mi355_sws_destroy(b->dev); b->dev = NULL; }
@@ -759,6 +952,12 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
         if (!b->dev) {
             mi355_sws_desc d;
             int fmt;
+            if (b->rgb32) {
+                if (device_ready() && rgb32_ok) {
+                    b->dev = a32 ? mi355_sws_create_src_layout_alpha(&d32, &s32, l32, f32, 1) : mi355_sws_create_src_layout_range_depth(&d32, &s32, l32, f32, r32, dp32);
+                    d = d32;
+                }
+            } else
             if (b->packed) {
                 mi355_sws_src s;
                 int layout;

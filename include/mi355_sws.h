@@ -6,7 +6,9 @@
  * nv12ToUV_c / nv21ToUV_c in front of hcScale, and the unscaled NV12 / NV21 -> yuv420p splitter) or from packed rgb24 / bgr24 (the
  * reference's rgb24ToY_c / rgb24ToUV_c / rgb24ToUV_half_c and their bgr24 forms in front of hyScale / hcScale); the three planar
  * destinations also at 9 or 10 bits (yuv420p9le ... yuv444p10le: yuv2planeX_10 / yuv2plane1_10); packed destinations also as bgr24 and as
- * rgba / bgra / argb / abgr (yuv2rgb_write output.c:825-867; yuv2rgb_c_24_bgr / yuv2rgb_c_32), from every source rgb24 is written from.
+ * rgba / bgra / argb / abgr (yuv2rgb_write output.c:825-867; yuv2rgb_c_24_bgr / yuv2rgb_c_32), from every source rgb24 is written from; and from
+ * packed 32-bit rgba / bgra / argb / abgr sources (rgb32ToY_c ... bgr321ToUV_half_c input.c:165-291 in front of hyScale / hcScale) to all of these,
+ * the source's alpha carried to a 32-bit destination where asked for (rgbaToA_c / abgrToA_c and the hasAlpha forms of the packed templates).
  *
  * The reference keeps these behind function pointers of the (private) SwsContext
  * (libswscale/swscale_internal.h:253-540): hyScale/hcScale :526-531, yuv2plane1/yuv2planeX/
@@ -205,6 +207,35 @@ int mi355_sws_source_layout(const mi355_sws_ctx *ctx);   /* MI355_SWS_SRC_*, -1 
  * those three bytes readable on the last line too.  The Tier-1 host entry points return -1 when src_stride[0] < 3 * srcW. */
 enum { MI355_SWS_SRC_RGB24 = 4, MI355_SWS_SRC_BGR24 = 5 };
 
+/* ---- packed 32-bit sources: rgba / bgra / argb / abgr (the reference's rgb32ToY_c / bgr32ToY_c / rgb321ToY_c / bgr321ToY_c and their ...ToUV_c /
+ * ...ToUV_half_c forms: rgb16_32ToY_c_template and its kin behind the four wrappers with S = RGB2YUV_SHIFT + 8, input.c:165-291) ----
+ * layout 8 .. 11 of mi355_sws_create_src_layout and of every creator that forwards to it (3, 6 and 7 stay refused).  The names give the byte order IN
+ * MEMORY, as for the destinations.  The wrappers' constants are the rgb24 ones shifted up by eight and their masks remove the alpha byte before
+ * anything is summed (also in the halving form): the Y, U and V bytes are those of rgb24ToY_c / rgb24ToUV_c / rgb24ToUV_half_c on the pixel's three
+ * colour bytes.  Everything said of the rgb24 / bgr24 sources holds with four bytes a pixel: ONE source plane, 4 * srcW bytes a row; src->depth 8,
+ * src->vsub 0, desc->chrSrcH == desc->srcH, src->hsub 1 / 0 the halving / the full chroma converter as the reference chose it; every dst_format the
+ * rgb24 source takes (0, 32 .. 36, the planar and semi-planar ones, a range to a YUV destination, a 9- / 10-bit planar depth) and its refusals
+ * (desc->unscaled_special, a context that scales neither way to a packed RGB destination, banks the tiles cannot hold); mi355_sws_plan reports
+ * GENERIC_A .. C / PLANAR_A .. C.  To a 32-bit destination these creators write 255 as the alpha byte (the colour bytes never depend on alpha);
+ * mi355_sws_create_src_layout_alpha below carries the source's alpha there, as the reference does.
+ * The plane's pointer and stride must be multiples of 4 — the reference reads a pixel as one aligned dword (AV_RN32A): the Tier-1 host entry points
+ * return -1 otherwise, and for a stride below 4 * srcW.  A plane on 16-byte multiples is fetched in 16-byte pieces, any other in dwords, each whole
+ * inside the bytes named here: a line is read over 4 * srcW bytes — and, with hsub == 1 and an ODD srcW, over 4 * (srcW + 1) bytes, as the reference
+ * reads it.  No byte past that is read; the caller keeps those four bytes readable on the last line too. */
+enum { MI355_SWS_SRC_RGBA = 8, MI355_SWS_SRC_BGRA = 9, MI355_SWS_SRC_ARGB = 10, MI355_SWS_SRC_ABGR = 11 };
+/* ... with the source's alpha carried to a 32-bit destination, as a reference context does whose source AND destination both have alpha: it keeps a
+ * third ring buffer (alpPixBuf, utils.c:1244), reads alpha through rgbaToA_c / abgrToA_c (input.c:305-319), scales it with the LUMA banks
+ * (swscale.c:269-276, :511-513) and writes it through the hasAlpha forms of yuv2rgb_X / _2 / _1_c_template (output.c:937-1110; its tables then hold
+ * 0 in the alpha lane).  So a resized picture's alpha is filtered like its luma — not 255, and not a copy.
+ * alpha 0: exactly mi355_sws_create_src_layout (a 32-bit destination gets 255: a reference without an alpha buffer).  alpha 1: src_layout 8 .. 11 to
+ * dst_format MI355_SWS_DST_RGBA ... _ABGR with desc->unscaled_special 0; NULL and a message for anything else, and for everything the colour-only
+ * context is refused for.  The descriptor, the frames (mi355_sws_frame) and the entry points are the colour-only context's; mi355_sws_plan reports
+ * its values (lum_lines then also counts the lines of the alpha tile).  The alpha tile holds as many lines as the luma tile, in LDS of its own: 7 / 10 /
+ * 12 KB on top of the 19 / 23 / 26 KB of GENERIC_A / B / C — every context the colour-only creator takes still fits a workgroup's LDS, so none is refused
+ * for its alpha; fewer workgroups share a CU (6 / 4 / 4 where the twins have 8 / 7 / 6). */
+mi355_sws_ctx *mi355_sws_create_src_layout_alpha(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format, int alpha);
+int mi355_sws_alpha(const mi355_sws_ctx *ctx);   /* 0 / 1, -1 bad argument */
+
 /* ---- range conversion: contexts whose source and destination differ in range, to a YUV destination (yuvj420p <-> yuv420p and their kin:
  * c->srcRange != c->dstRange && !isAnyRGB(c->dstFormat), lumConvertRange / chrConvertRange swscale.c:168-198, :748-766) ----
  * The reference applies the two converters to every horizontally scaled int16 line, between hyScale / hcScale and the vertical pass
@@ -284,6 +315,12 @@ void mi355_sws_rgb24ToY(uint8_t *dst, const uint8_t *src, int width, int bgr);
 /* rgb24ToUV_c / bgr24ToUV_c and their _half forms input.c:552-623 (c->chrToYV12): `width` OUTPUT samples of each plane; half 0 reads
  * 3 * width bytes, half 1 (each sample from the sum of two neighbouring pixels) 6 * width */
 void mi355_sws_rgb24ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int width, int bgr, int half);
+/* the same three converters of a 32-bit source and its alpha reader (rgb32ToY_c ... bgr321ToUV_half_c input.c:288-291; rgbaToA_c / abgrToA_c
+ * :305-319): layout MI355_SWS_SRC_RGBA ... _ABGR (any other value does nothing); `width` OUTPUT samples from 4 * width bytes, 8 * width with half 1;
+ * src is a multiple of 4 (the reference reads dwords) */
+void mi355_sws_rgb32ToY(uint8_t *dst, const uint8_t *src, int width, int layout);
+void mi355_sws_rgb32ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int width, int layout, int half);
+void mi355_sws_rgb32ToA(uint8_t *dst, const uint8_t *src, int width, int layout);
 /* lumRangeFromJpeg_c / lumRangeToJpeg_c and chrRangeFromJpeg_c / chrRangeToJpeg_c swscale.c:168-198 (c->lumConvertRange / c->chrConvertRange):
  * `width` int16 samples converted in place, any int16 value (a result outside int16 is stored truncated, as the reference stores it) */
 void mi355_sws_lumConvertRange(int16_t *dst, int width, int to_jpeg);
@@ -323,6 +360,16 @@ void mi355_sws_yuv2packed_1(const mi355_sws_luts *luts, int dst_format, const in
                             uint8_t *dest, int dstW, int uvalpha);
 int mi355_sws_yuv2rgb_c(const mi355_sws_luts *luts, int dst_format, int dstW, const uint8_t *const src[3], const int srcStride[3],
                         int srcSliceY, int srcSliceH, uint8_t *dst, int dstStride);
+/* the alpha forms of the trio (yuv2rgba32_X_c ... yuv2rgbx32_1_1_c with hasAlpha, output.c:937-1110): dst_format MI355_SWS_DST_RGBA ... _ABGR only
+ * (any other value, or no alpha line, does nothing); alpSrc / abuf / abuf0 are the alpha lines beside the luma lines — as many, as long, filtered
+ * with the luma taps; luts as the creators take them (the alpha lane is not in them) */
+void mi355_sws_yuv2packed_X_a(const mi355_sws_luts *luts, int dst_format, const int16_t *lumFilter, const int16_t **lumSrc, int lumFilterSize,
+                              const int16_t *chrFilter, const int16_t **chrUSrc, const int16_t **chrVSrc, int chrFilterSize,
+                              const int16_t **alpSrc, uint8_t *dest, int dstW);
+void mi355_sws_yuv2packed_2_a(const mi355_sws_luts *luts, int dst_format, const int16_t *buf[2], const int16_t *ubuf[2], const int16_t *vbuf[2],
+                              const int16_t *abuf[2], uint8_t *dest, int dstW, int yalpha, int uvalpha);
+void mi355_sws_yuv2packed_1_a(const mi355_sws_luts *luts, int dst_format, const int16_t *buf0, const int16_t *ubuf[2], const int16_t *vbuf[2],
+                              const int16_t *abuf0, uint8_t *dest, int dstW, int uvalpha);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,9 @@
  * yuv420p -> NV12 / NV21 packer and the unscaled NV12 / NV21 -> yuv420p splitter; to the YUV destinations also with range conversion between the two
  * passes (yuvj420p <-> yuv420p and their kin: lumConvertRange / chrConvertRange swscale.c:168-198), and to the three planar destinations at 9 or
  * 10 bits (yuv420p9le ... yuv444p10le: yuv2planeX_10 / yuv2plane1_10 output.c:183-213; their tile instances are launched from sws_deep.hip), and
- * to bgr24 / rgba / bgra / argb / abgr wherever rgb24 is written (yuv2rgb_write output.c:825-867; their instances are launched from sws_packed.hip).  This file:
+ * to bgr24 / rgba / bgra / argb / abgr wherever rgb24 is written (yuv2rgb_write output.c:825-867; their instances are launched from sws_packed.hip);
+ * packed 32-bit rgba / bgra / argb / abgr SOURCES to all of these, with the source's alpha carried to a 32-bit destination where the caller asks for it
+ * (mi355_sws_create_src_layout_alpha; their instances, line kernels and line entries are sws_rgb32.hip's).  This file:
  * the context, the plan (which kernel a context gets) and the entry points of include/mi355_sws.h.  The device side is sws_dev.h:
  * k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1, k_sws_nv12_pack, k_sws_nv12_split and the k_sws_line_* kernels of the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
@@ -28,6 +30,7 @@ struct mi355_sws_ctx {
     mi355_sws_planar_frame *d_pframe = nullptr;      /* ... of a planar context (d_dst then holds its three planes) */
     hipStream_t stream = nullptr;
     int device = -1;            /* the device of the thread that created the context: its entry points switch to it */
+    int alpha = 0;              /* a 32-bit source's alpha goes to the 32-bit destination (mi355_sws_create_src_layout_alpha): the ALPHA instances */
     int hfit = 0;               /* a plane with a horizontal filter other than the identity has a tile whose source span fits a staged line (ctx_hfit) */
 };
 
@@ -124,7 +127,12 @@ static bool ctx_source(mi355_sws_ctx *c, const mi355_sws_src *src)
 /* a packed destination other than rgb24: bgr24 or one of the four 32-bit orders */
 static bool packed_dst(int dst_format) { return dst_format >= MI355_SWS_DST_BGR24 && dst_format <= MI355_SWS_DST_ABGR; }
 static int packed_bpp(const SwsDev &h) { return h.packed >= MI355_SWS_DST_RGBA ? 4 : 3; }
-static bool packed_rgb(const SwsDev &h) { return h.src_layout == MI355_SWS_SRC_RGB24 || h.src_layout == MI355_SWS_SRC_BGR24; }
+/* a packed RGB source: rgb24 / bgr24, or one of the four 32-bit orders (rgb32_src: its tile instances are launched from sws_rgb32.hip) */
+static bool rgb32_src(const SwsDev &h) { return sws_rgb32_src(h.src_layout); }
+static bool packed_rgb(const SwsDev &h) { return h.src_layout == MI355_SWS_SRC_RGB24 || h.src_layout == MI355_SWS_SRC_BGR24 || rgb32_src(h); }
+static int src_bpx(const SwsDev &h) { return rgb32_src(h) ? 4 : 3; }
+/* the layouts the creators take: 0, 1, 2, 4, 5 and 8 .. 11 */
+static bool src_layout_taken(int l) { return (l >= MI355_SWS_SRC_PLANAR && l <= MI355_SWS_SRC_BGR24 && l != 3) || sws_rgb32_src(l); }
 /* a context that does not scale, to rgb24: what k_sws_ident1 takes */
 static bool ident1_shape(const SwsDev &h)
 {
@@ -219,17 +227,18 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
         delete c;
         return nullptr;
     }
-    if (layout == MI355_SWS_SRC_RGB24 || layout == MI355_SWS_SRC_BGR24) {
-        /* packed RGB: 8 bit, chroma on every line, the full or the halving converter (ctx_source has checked chrSrcW / chrSrcH against the shifts);
+    const char *const packed_name = sws_rgb32_src(layout) ? "rgba / bgra / argb / abgr" : "rgb24 / bgr24";
+    if (layout == MI355_SWS_SRC_RGB24 || layout == MI355_SWS_SRC_BGR24 || sws_rgb32_src(layout)) {
+        /* packed RGB (three or four bytes a pixel): 8 bit, chroma on every line, the full or the halving converter (ctx_source has checked chrSrcW / chrSrcH against the shifts);
          * no special converter */
         if (h.depth != 8 || h.src_vsub) {
-            std::fprintf(stderr, "mi355dsp: %s: an rgb24 / bgr24 source is 8 bit with chroma on every line (%d bit, shifts %d/%d)\n", who, h.depth, h.src_hsub, h.src_vsub);
+            std::fprintf(stderr, "mi355dsp: %s: an %s source is 8 bit with chroma on every line (%d bit, shifts %d/%d)\n", who, packed_name, h.depth, h.src_hsub, h.src_vsub);
             delete c;
             return nullptr;
         }
         h.src_layout = layout;
         if (h.special) {
-            std::fprintf(stderr, "mi355dsp: %s: no unscaled special converter takes an rgb24 / bgr24 source here\n", who);
+            std::fprintf(stderr, "mi355dsp: %s: no unscaled special converter takes an %s source here\n", who, packed_name);
             delete c;
             return nullptr;
         }
@@ -289,7 +298,7 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
     h.lum_lines = lines[0]; h.chr_lines = lines[1];
     if (packed_rgb(h) && !planar && ident1_shape(h)) {
         /* rgb in, rgb out, nothing scaled: the reference never runs its scaler on that (a copy, or rgbToRgbWrapper) */
-        std::fprintf(stderr, "mi355dsp: %s: an rgb24 / bgr24 source to rgb24 without scaling is not a context of the scaler\n", who);
+        std::fprintf(stderr, "mi355dsp: %s: an %s source to rgb24 without scaling is not a context of the scaler\n", who, packed_name);
         delete c;
         return nullptr;
     }
@@ -316,13 +325,28 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src_layout(const mi355_sws_desc *desc
 {
     if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout without mi355_init(); no CPU fallback\n"); std::abort(); }
     if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout: no descriptor\n"); return nullptr; }
-    if (src_layout < MI355_SWS_SRC_PLANAR || src_layout > MI355_SWS_SRC_BGR24 || src_layout == 3) {
-        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24\n", src_layout);
+    if (!src_layout_taken(src_layout)) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr\n", src_layout);
         return nullptr;
     }
     return ctx_create(desc, src, dst_format != 0 && !packed_dst(dst_format), dst_format, "mi355_sws_create_src_layout", src_layout);
 }
 extern "C" int mi355_sws_source_layout(const mi355_sws_ctx *c) { return c ? c->h.src_layout : -1; }
+extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_alpha(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format, int alpha)
+{
+    if (!alpha) return mi355_sws_create_src_layout(desc, src, src_layout, dst_format);
+    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_alpha without mi355_init(); no CPU fallback\n"); std::abort(); }
+    if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_alpha: no descriptor\n"); return nullptr; }
+    if (alpha != 1 || !sws_rgb32_src(src_layout) || dst_format < MI355_SWS_DST_RGBA || dst_format > MI355_SWS_DST_ABGR || desc->unscaled_special) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_alpha: alpha (%d) is carried from an rgba / bgra / argb / abgr source (layout %d) to an rgba / bgra / "
+                     "argb / abgr destination (format %d) by the scaler only (unscaled_special %d)\n", alpha, src_layout, dst_format, desc->unscaled_special);
+        return nullptr;
+    }
+    mi355_sws_ctx *c = ctx_create(desc, src, false, dst_format, "mi355_sws_create_src_layout_alpha", src_layout);
+    if (c) c->alpha = 1;
+    return c;
+}
+extern "C" int mi355_sws_alpha(const mi355_sws_ctx *c) { return c ? c->alpha : -1; }
 extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format, int range)
 {
     if (range == MI355_SWS_RANGE_NONE) return mi355_sws_create_src_layout(desc, src, src_layout, dst_format);
@@ -332,8 +356,8 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range(const mi355_sws_desc
         std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: range %d is not none / from-jpeg / to-jpeg\n", range);
         return nullptr;
     }
-    if (src_layout < MI355_SWS_SRC_PLANAR || src_layout > MI355_SWS_SRC_BGR24 || src_layout == 3) {
-        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24\n", src_layout);
+    if (!src_layout_taken(src_layout)) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr\n", src_layout);
         return nullptr;
     }
     /* the reference converts the range of YUV destinations only (an RGB one takes it into its LUTs), and never in an unscaled special converter */
@@ -358,8 +382,8 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range_depth(const mi355_sw
         std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: destination depth %d is not 8 / 9 / 10\n", dst_depth);
         return nullptr;
     }
-    if (src_layout < MI355_SWS_SRC_PLANAR || src_layout > MI355_SWS_SRC_BGR24 || src_layout == 3) {
-        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24\n", src_layout);
+    if (!src_layout_taken(src_layout)) {
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr\n", src_layout);
         return nullptr;
     }
     if (dst_format < MI355_SWS_DST_YUV420P || dst_format > MI355_SWS_DST_YUV444P) {
@@ -580,6 +604,11 @@ extern "C" int mi355_sws_scale_frames_dev(mi355_sws_ctx *c, const mi355_sws_fram
     const SwsDev &h = c->h;
     DeviceScope on(c->device);
     const int k = sws_kernel(h);
+    if (rgb32_src(h)) {
+        /* a 32-bit source: always a tile instance (sws_rgb32.hip), to rgb24 and to the five other packed destinations */
+        mi355_sws_launch_generic_rgb32(k - MI355_SWS_K_GENERIC_A, h.packed, c->alpha, dim3((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes), s, c->d, d_frames);
+        return hipGetLastError() == hipSuccess ? 0 : -2;
+    }
     if (h.packed) {
         /* bgr24 and the 32-bit orders: the twin's kernel and grid, the DST_BGR24 / DST_RGB32 instance (sws_packed.hip) */
         const dim3 grid = k == MI355_SWS_K_C24 ? dim3((h.dstW + C24_COLS - 1) / C24_COLS, (h.srcH + C24_ROWS - 1) / C24_ROWS, nframes) :
@@ -629,8 +658,10 @@ extern "C" int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *c, const mi355_s
     }
     const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
     const int i = k - MI355_SWS_K_PLANAR_A;
+    /* a 32-bit source: plain, RANGE and DEEP instances of its own (sws_rgb32.hip) */
+    if (rgb32_src(h)) mi355_sws_launch_planar_rgb32(i, h.dst_bits > 8 ? 2 : (h.range ? 1 : 0), semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
     /* a 9- / 10-bit destination: the DEEP instances (three planes, no range) */
-    if (h.dst_bits > 8) mi355_sws_launch_planar_deep(i, packed_rgb(h) ? 3 : (h.src_layout ? 2 : (h.depth > 8 ? 1 : 0)), h.hshift ? 0 : 1, grid, s, c->d, d_frames);
+    else if (h.dst_bits > 8) mi355_sws_launch_planar_deep(i, packed_rgb(h) ? 3 : (h.src_layout ? 2 : (h.depth > 8 ? 1 : 0)), h.hshift ? 0 : 1, grid, s, c->d, d_frames);
     else if (h.range) launch_planar_range(i, packed_rgb(h) ? 3 : (h.src_layout ? 2 : (h.depth > 8 ? 1 : 0)), semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
     else if (packed_rgb(h)) launch_planar_rgb(i, semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
     else if (h.src_layout) launch_planar_nv(i, semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
@@ -662,10 +693,13 @@ static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int
     const int B = h.depth > 8 ? 2 : 1;                                  /* bytes per source sample */
     /* an NV12 / NV21 source: two planes, the second one 2 * chrSrcW bytes of pairs; src[2] is not touched */
     /* a packed rgb24 / bgr24 source: one plane of 3 * srcW bytes a row; the halving converter of an odd width also reads pixel srcW, the three
-     * bytes behind each row as they lie in the caller's picture (a second copy: they may belong to the next row) */
+     * bytes behind each row as they lie in the caller's picture (a second copy: they may belong to the next row).  A 32-bit source: four bytes a
+     * pixel, pointer and stride on 4-byte multiples (the reference reads dwords) */
     const bool rgb = packed_rgb(h);
-    const int nsrc = rgb ? 1 : (h.src_layout ? 2 : 3), tail = rgb && h.src_hsub && (h.srcW & 1) ? 3 : 0;
-    const int w[3] = { rgb ? 3 * h.srcW : h.srcW * B, rgb ? 0 : (h.src_layout ? 2 * h.chrSrcW : h.chrSrcW * B), h.src_layout ? 0 : h.chrSrcW * B },
+    const int bpx = src_bpx(h);
+    if (rgb32_src(h) && (!src[0] || ((reinterpret_cast<uintptr_t>(src[0]) | (uintptr_t)src_stride[0]) & 3))) return -1;
+    const int nsrc = rgb ? 1 : (h.src_layout ? 2 : 3), tail = rgb && h.src_hsub && (h.srcW & 1) ? bpx : 0;
+    const int w[3] = { rgb ? bpx * h.srcW : h.srcW * B, rgb ? 0 : (h.src_layout ? 2 * h.chrSrcW : h.chrSrcW * B), h.src_layout ? 0 : h.chrSrcW * B },
               ph[3] = { h.srcH, h.chrSrcH, h.chrSrcH };
     for (int p = 0; p < nsrc; p++) if (!src[p] || src_stride[p] < w[p]) return -1;
     for (int p = 0; p < ndst; p++) if (!dst[p] || dst_stride[p] < back[p]) return -1;
@@ -914,19 +948,25 @@ extern "C" void mi355_sws_yuv2nv12cX(const int16_t *chrFilter, int chrFilterSize
 }
 
 /* dst_format 0: rgb24 (k_sws_line_rgb); MI355_SWS_DST_BGR24 ... _ABGR: k_sws_line_packed of that form (sws_packed.hip), pairs of 6 or 8 bytes */
+/* alp: the ls alpha lines of the _a entries (a 32-bit order): k_sws_line_packed_a (sws_rgb32.hip) */
 static void rgb_line(const mi355_sws_luts *luts, int mode, const int16_t *lumF, const int16_t **l, int ls, const int16_t *chrF,
-                     const int16_t **u, const int16_t **v, int cs, uint8_t *dest, int dstW, int yalpha, int uvalpha, int dst_format = 0)
+                     const int16_t **u, const int16_t **v, int cs, uint8_t *dest, int dstW, int yalpha, int uvalpha, int dst_format = 0, const int16_t **alp = nullptr)
 {
     Arena &a = arena();
     const int npair = (dstW + 1) >> 1, pitch = (2 * npair + 7) & ~7, pb = dst_format >= MI355_SWS_DST_RGBA ? 8 : 6;
-    a.reserve(sizeof(mi355_sws_luts) + (size_t)(ls + 2 * cs + 3) * pitch * 2 + (size_t)(ls + cs) * 2 + (size_t)npair * pb + 256);
+    a.reserve(sizeof(mi355_sws_luts) + (size_t)(2 * ls + 2 * cs + 4) * pitch * 2 + (size_t)(ls + cs) * 2 + (size_t)npair * pb + 256);
     const size_t o_t = a.take(sizeof(mi355_sws_luts));
     std::memcpy(a.h<uint8_t>(o_t), luts, sizeof(mi355_sws_luts));
     const size_t o_l = pack_rows(a, l, ls, 2 * npair, pitch), o_u = pack_rows(a, u, cs, npair, pitch), o_v = pack_rows(a, v, cs, npair, pitch);
+    const size_t o_a = alp ? pack_rows(a, alp, ls, 2 * npair, pitch) : 0;
     const size_t o_lf = a.take((size_t)ls * 2 + 2), o_cf = a.take((size_t)cs * 2 + 2), o_d = a.take((size_t)npair * pb);
     if (lumF) std::memcpy(a.h<int16_t>(o_lf), lumF, (size_t)ls * 2);
     if (chrF) std::memcpy(a.h<int16_t>(o_cf), chrF, (size_t)cs * 2);
     a.upload();
+    if (alp)
+        mi355_sws_launch_line_packed_a(dst_format, a.stream, a.d<const mi355_sws_luts>(o_t), mode, a.d<const int16_t>(o_lf), a.d<const int16_t>(o_l), ls, a.d<const int16_t>(o_cf),
+                                       a.d<const int16_t>(o_u), a.d<const int16_t>(o_v), cs, a.d<const int16_t>(o_a), pitch, a.d<uint8_t>(o_d), dstW, yalpha, uvalpha);
+    else
     if (dst_format)
         mi355_sws_launch_line_packed(dst_format, a.stream, a.d<const mi355_sws_luts>(o_t), mode, a.d<const int16_t>(o_lf), a.d<const int16_t>(o_l), ls, a.d<const int16_t>(o_cf),
                                      a.d<const int16_t>(o_u), a.d<const int16_t>(o_v), cs, pitch, a.d<uint8_t>(o_d), dstW, yalpha, uvalpha);
@@ -1008,6 +1048,29 @@ extern "C" void mi355_sws_yuv2packed_1(const mi355_sws_luts *luts, int dst_forma
     if (!packed_line_format(dst_format)) return;
     const int cs = uvalpha < 2048 ? 1 : 2;                      /* as mi355_sws_yuv2rgb24_1 */
     rgb_line(luts, 1, nullptr, &buf0, 1, nullptr, ubuf, vbuf, cs, dest, dstW, 0, uvalpha, dst_format);
+}
+
+/* the alpha forms of the three (yuv2rgba32_X_c ... with hasAlpha, output.c:937-1110): a 32-bit order, the alpha line(s) beside the luma line(s) */
+static bool alpha_line_format(int dst_format) { return dst_format >= MI355_SWS_DST_RGBA && dst_format <= MI355_SWS_DST_ABGR; }
+extern "C" void mi355_sws_yuv2packed_X_a(const mi355_sws_luts *luts, int dst_format, const int16_t *lumFilter, const int16_t **lumSrc, int lumFilterSize,
+                                         const int16_t *chrFilter, const int16_t **chrUSrc, const int16_t **chrVSrc, int chrFilterSize,
+                                         const int16_t **alpSrc, uint8_t *dest, int dstW)
+{
+    if (!alpha_line_format(dst_format) || !alpSrc) return;
+    rgb_line(luts, 0, lumFilter, lumSrc, lumFilterSize, chrFilter, chrUSrc, chrVSrc, chrFilterSize, dest, dstW, 0, 0, dst_format, alpSrc);
+}
+extern "C" void mi355_sws_yuv2packed_2_a(const mi355_sws_luts *luts, int dst_format, const int16_t *buf[2], const int16_t *ubuf[2], const int16_t *vbuf[2],
+                                         const int16_t *abuf[2], uint8_t *dest, int dstW, int yalpha, int uvalpha)
+{
+    if (!alpha_line_format(dst_format) || !abuf) return;
+    rgb_line(luts, 2, nullptr, buf, 2, nullptr, ubuf, vbuf, 2, dest, dstW, yalpha, uvalpha, dst_format, abuf);
+}
+extern "C" void mi355_sws_yuv2packed_1_a(const mi355_sws_luts *luts, int dst_format, const int16_t *buf0, const int16_t *ubuf[2], const int16_t *vbuf[2],
+                                         const int16_t *abuf0, uint8_t *dest, int dstW, int uvalpha)
+{
+    if (!alpha_line_format(dst_format) || !abuf0) return;
+    const int cs = uvalpha < 2048 ? 1 : 2;                      /* as mi355_sws_yuv2rgb24_1 */
+    rgb_line(luts, 1, nullptr, &buf0, 1, nullptr, ubuf, vbuf, cs, dest, dstW, 0, uvalpha, dst_format, &abuf0);
 }
 
 /* yuv2rgb_c_24_rgb / yuv2rgb_c_24_bgr / yuv2rgb_c_32 (yuv2rgb.c:237-394) on one 4:2:0 slice: mi355_sws_yuv2rgb_c_24_rgb with the destination's format */

@@ -20,7 +20,9 @@
  * instances of k_sws_planar convert the range of the int16 lines between the two passes (lumConvertRange / chrConvertRange: range_lines).  The DEEP
  * instances of k_sws_planar write 9- or 10-bit planes of 16-bit little-endian samples (yuv2plane1_10 / yuv2planeX_10: planar_rows16).  The DST_BGR24 /
  * DST_RGB32 instances of k_sws_generic, k_sws_ident1 and k_sws_c24 write bgr24 or one of rgba / bgra / argb / abgr in place of rgb24 (write_pair_d,
- * store8_d; compiled in sws_packed.hip).
+ * store8_d; compiled in sws_packed.hip).  The RGB instances whose sample type is a 32-bit pixel (SwsPx32: rgba / bgra / argb / abgr sources; compiled in
+ * sws_rgb32.hip) run the same converters on a pixel that is one aligned dword; SwsPx32A: the ALPHA form of k_sws_generic, a fourth LDS tile of the
+ * source's alpha through the luma banks into the alpha byte of a 32-bit destination.
  *   k_sws_line_*    the individual inner loops for the Tier-1 entry points.
  * Execution model: 256-thread workgroups (4 waves) sharing one LDS tile; integer only, no MFMA.
  */
@@ -63,7 +65,8 @@ struct SwsDev {
     int planar, hshift, vshift, chrDstH;
     /* the source side (mi355_sws_create_src): bits per sample (8: bytes; 9 / 10: uint16_t little endian), its chroma shifts, and the 8x8
      * dither rows a planar destination takes from a source deeper than 8 bits (swscale.c:553-556); src_layout: MI355_SWS_SRC_* — 1 / 2: the
-     * second source plane holds chrSrcW byte pairs (NV12: U V, NV21: V U) and there is no third */
+     * second source plane holds chrSrcW byte pairs (NV12: U V, NV21: V U) and there is no third; 4 / 5 and 8 .. 11: one packed plane of three / four
+     * bytes a pixel */
     int depth, src_hsub, src_vsub, src_layout;
     __attribute__((aligned(8))) uint8_t dither[8][8];
     /* range conversion between the horizontal and the vertical pass (mi355_sws_create_src_layout_range): MI355_SWS_RANGE_*, and the affine map
@@ -156,6 +159,19 @@ __device__ __forceinline__ uint32_t rgb32_pixel(const LutLds &t, int r, int g, i
 {
     return sws_order4((uint32_t)t.y[r + Y] | ((uint32_t)t.y[g + Y] << 8) | ((uint32_t)t.y[b + Y] << 16) | 0xFF000000u, sel);
 }
+/* ... with the pixel's own alpha (yuv2rgb_write with hasAlpha, output.c:843-847: the reference's tables then hold 0 in the alpha lane and A << 24 — or
+ * << 0 for the two orders with alpha first — is added; here A enters the assembled dword where 255 goes otherwise, and the same permute places it) */
+__device__ __forceinline__ uint32_t rgb32_pixel_a(const LutLds &t, int r, int g, int b, int Y, int A, uint32_t sel)
+{
+    return sws_order4((uint32_t)t.y[r + Y] | ((uint32_t)t.y[g + Y] << 8) | ((uint32_t)t.y[b + Y] << 16) | ((uint32_t)A << 24), sel);
+}
+__device__ __forceinline__ void write_pair_a(const LutLds &t, uint8_t *dest, int Y1, int Y2, int U, int V, int A1, int A2, uint32_t sel)
+{
+    int r, g, b;
+    lut_rows(t, U, V, r, g, b);
+    uint32_t *q = reinterpret_cast<uint32_t *>(dest);
+    q[0] = rgb32_pixel_a(t, r, g, b, Y1, A1, sel); q[1] = rgb32_pixel_a(t, r, g, b, Y2, A2, sel);
+}
 /* yuv2rgb_write of one pair: six bytes, or two dwords at dest (a multiple of 4) */
 template <int DST> __device__ __forceinline__ void write_pair_d(const LutLds &t, uint8_t *dest, int Y1, int Y2, int U, int V, uint32_t sel)
 {
@@ -176,11 +192,27 @@ template <int DST> __device__ __forceinline__ void write_pair_d(const LutLds &t,
 /* one output pair of the three packed templates; rows are addressed through accessors so the same
  * code serves LDS tiles (whole pictures) and packed global rows (Tier-1 line calls).  vertical_rows keeps its own statement of them over
  * the taps it holds in registers: a register-resident accessor here was tried and gave another instruction stream */
-template <int DST = DST_RGB24, typename Rows>
+/* ALPHA (DST_RGB32): the hasAlpha branches of the three templates — A from R.alp() with the LUMA taps, clipped as each template clips it */
+template <int DST = DST_RGB24, bool ALPHA = false, typename Rows>
 __device__ __forceinline__ void rgb_pair(const LutLds &t, uint8_t *dest, const Rows &R, int i, int mode, const int16_t *lumF, int ls,
                                          const int16_t *chrF, int cs, int yalpha, int uvalpha, uint32_t sel = 0)
 {
     int Y1, Y2, U, V;
+    [[maybe_unused]] int A1 = 0, A2 = 0;
+    if constexpr (ALPHA) {
+        static_assert(DST == DST_RGB32, "alpha goes to a 32-bit destination");
+        if (mode == 1) { A1 = clip_u8(R.alp(0, 2 * i) >> 7); A2 = clip_u8(R.alp(0, 2 * i + 1) >> 7); }
+        else if (mode == 2) {
+            const int ya1 = 4096 - yalpha;
+            A1 = clip_u8((R.alp(0, 2 * i) * ya1 + R.alp(1, 2 * i) * yalpha) >> 19);
+            A2 = clip_u8((R.alp(0, 2 * i + 1) * ya1 + R.alp(1, 2 * i + 1) * yalpha) >> 19);
+        } else {
+            A1 = A2 = 1 << 18;
+            for (int j = 0; j < ls; j++) { const int f = lumF[j]; A1 += R.alp(j, 2 * i) * f; A2 += R.alp(j, 2 * i + 1) * f; }
+            A1 >>= 19; A2 >>= 19;
+            if ((A1 | A2) & 0x100) { A1 = clip_u8(A1); A2 = clip_u8(A2); }
+        }
+    }
     if (mode == 1) {          /* yuv2rgb_1_c_template output.c:1043-1110 */
         Y1 = clip_u8(R.lum(0, 2 * i) >> 7); Y2 = clip_u8(R.lum(0, 2 * i + 1) >> 7);
         if (uvalpha < 2048) { U = clip_u8(R.cu(0, i) >> 7); V = clip_u8(R.cv(0, i) >> 7); }
@@ -198,6 +230,8 @@ __device__ __forceinline__ void rgb_pair(const LutLds &t, uint8_t *dest, const R
         Y1 >>= 19; Y2 >>= 19; U >>= 19; V >>= 19;
         if ((Y1 | Y2 | U | V) & 0x100) { Y1 = clip_u8(Y1); Y2 = clip_u8(Y2); U = clip_u8(U); V = clip_u8(V); }
     }
+    if constexpr (ALPHA) write_pair_a(t, dest, Y1, Y2, U, V, A1, A2, sel);
+    else
     write_pair_d<DST>(t, dest, Y1, Y2, U, V, sel);
 }
 /* eight neighbouring samples of a line (four pairs sharing a chroma sample each): Y values 0..255 in Y[8], the pairs' LUT
@@ -231,6 +265,15 @@ __device__ __forceinline__ void rgb32_store8(const LutLds &t, uint8_t *d, const 
     sws_u32x4 *q = reinterpret_cast<sws_u32x4 *>(d);
     q[0] = sws_u32x4{ o[0], o[1], o[2], o[3] }; q[1] = sws_u32x4{ o[4], o[5], o[6], o[7] };
 }
+/* ... each with its own alpha A[k] */
+__device__ __forceinline__ void rgb32_store8_a(const LutLds &t, uint8_t *d, const int *Y, const int *A, const int *r, const int *g, const int *b, uint32_t sel)
+{
+    uint32_t o[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) o[k] = rgb32_pixel_a(t, r[k >> 1], g[k >> 1], b[k >> 1], Y[k], A[k], sel);
+    sws_u32x4 *q = reinterpret_cast<sws_u32x4 *>(d);
+    q[0] = sws_u32x4{ o[0], o[1], o[2], o[3] }; q[1] = sws_u32x4{ o[4], o[5], o[6], o[7] };
+}
 /* ... of destination form DST (bgr24: the row offsets came exchanged from lut_rows_d, the packing is rgb24's) */
 template <int DST> __device__ __forceinline__ void store8_d(const LutLds &t, uint8_t *d, const int *Y, const int *r, const int *g, const int *b, uint32_t sel)
 {
@@ -258,6 +301,8 @@ struct TileRows {
     const int16_t (*cuT)[TW / 2];
     const int16_t (*cvT)[TW / 2];
     int lfirst, llo, lmax, cfirst, clo, cmax;   /* first tap line, first staged line, last picture line */
+    const int16_t (*alpT)[TW] = nullptr;        /* the alpha tile of an ALPHA instance: the luma tile's lines */
+    __device__ __forceinline__ int alp(int j, int x) const { return alpT[clampi(lfirst + j, 0, lmax) - llo][x]; }
     __device__ __forceinline__ int lum(int j, int x) const { return lumT[clampi(lfirst + j, 0, lmax) - llo][x]; }
     __device__ __forceinline__ int cu(int j, int x) const { return cuT[clampi(cfirst + j, 0, cmax) - clo][x]; }
     __device__ __forceinline__ int cv(int j, int x) const { return cvT[clampi(cfirst + j, 0, cmax) - clo][x]; }
@@ -277,7 +322,11 @@ constexpr int SRC_DW_HALF = 40;
  * a chroma tile row (64 * 2 + 8) * 2 + 15.  The same number of lines per round, so a 16-bit instance's staging storage is its own size. */
 constexpr int SRC_DW16 = 140, SRC_DW16_HALF = 76;
 constexpr int STAGE_BYTES16 = (int)sizeof(uint32_t) * SG * SRC_DW16;
-template <typename ST> __host__ __device__ constexpr int stage_bytes() { return sizeof(ST) == 1 ? STAGE_BYTES : STAGE_BYTES16; }
+/* the sample types of a packed 32-bit source (the RGB instances of rgba / bgra / argb / abgr): one pixel — SwsPx32A: its alpha byte is carried to a
+ * 32-bit destination (the ALPHA form of k_sws_generic).  The pixels are converted to 8-bit samples before they are staged: the 8-bit staging lines */
+struct SwsPx32 { uint32_t v; };
+struct SwsPx32A { uint32_t v; };
+template <typename ST> __host__ __device__ constexpr int stage_bytes() { return sizeof(ST) == 2 ? STAGE_BYTES16 : STAGE_BYTES; }
 /* dwords per staged line of `cols` columns of `bytes`-byte samples: a multiple of four (16-byte LDS stores) */
 __host__ __device__ constexpr int stage_pitch(int cols, int bytes) { return bytes == 1 ? (cols == TW ? SRC_DW : SRC_DW_HALF) : (cols == TW ? SRC_DW16 : SRC_DW16_HALF); }
 /* a tile's source span, bytes s0 .. s1 read from the aligned start a0, as dwords; it is staged if it fits the line with two dwords to spare */
@@ -874,6 +923,92 @@ __device__ __forceinline__ void rgb_sample(const uint8_t *px, bool half, const R
     a = (c0 * (int16_t)(k.a01 & 0xFFFF) + c1 * (int16_t)(k.a01 >> 16) + c2 * k.a2 + k.rnd) >> k.sh;
     b = (c0 * (int16_t)(k.b01 & 0xFFFF) + c1 * (int16_t)(k.b01 >> 16) + c2 * k.b2 + k.rnd) >> k.sh;
 }
+/* ---- a packed 32-bit source: rgba / bgra / argb / abgr (rgb16_32ToY_c_template and its ToUV / ToUV_half forms, input.c:165-255, through the four
+ * wrappers with S = RGB2YUV_SHIFT + 8 :288-291) ----
+ * The wrappers' constants are the rgb24 ones shifted up by eight, their rounding term 33u / 257u << (S - 1) likewise, and the masks take the alpha
+ * byte away before anything is summed (the halving form adds the g fields and the r / b fields of two pixels apart, each field a nine-bit sum):
+ * sample = (K0 c0 + K1 c1 + K2 c2 + rnd) >> sh over the three colour bytes, the rgb24 arithmetic with RgbK as it is.  A pixel is ONE aligned dword
+ * (the reference reads AV_RN32A): shifted right by `ash` — 8 where alpha is the first byte in memory (argb / abgr), else 0 — its bytes 0, 1, 2 are
+ * c0 c1 c2; bytes 0, 1 as the two 16-bit lanes of the dot product (sws_pair: alpha is not among them), byte 2 apart.  ash and which constant meets
+ * c0 (bgr: bgra / abgr) are uniform values of the context, one form serves the four orders. */
+__host__ __device__ constexpr bool sws_rgb32_src(int layout) { return layout >= MI355_SWS_SRC_RGBA && layout <= MI355_SWS_SRC_ABGR; }
+__host__ __device__ constexpr bool sws_src_bgr(int layout) { return layout == MI355_SWS_SRC_BGR24 || layout == MI355_SWS_SRC_BGRA || layout == MI355_SWS_SRC_ABGR; }
+__host__ __device__ constexpr uint32_t sws_src_ash(int layout) { return layout == MI355_SWS_SRC_ARGB || layout == MI355_SWS_SRC_ABGR ? 8u : 0u; }
+/* N pixels at byte `boff` (a multiple of 16) of a line of which `limit` bytes may be read: 16-byte loads on a plane of 16-byte multiples, dwords on
+ * one of 4-byte multiples, while the piece lies inside; else byte by byte (bytes at and past the limit read as zero) */
+template <int N>
+__device__ __forceinline__ void rgb32_load(const uint8_t *line, int boff, int limit, bool al4, bool al16, uint32_t *w)
+{
+    static_assert(N % 4 == 0, "whole 16-byte pieces");
+    if (al16 && boff + 4 * N <= limit) {
+#pragma unroll
+        for (int k = 0; k < N; k += 4) {
+            const sws_u32x4 v = *reinterpret_cast<const sws_u32x4 *>(line + boff + 4 * k);
+            w[k] = v[0]; w[k + 1] = v[1]; w[k + 2] = v[2]; w[k + 3] = v[3];
+        }
+    } else rgb_load<N>(line, boff, limit, al4, w);
+}
+/* converted samples s .. s + 3 of a line (s a multiple of four) as one dword per plane: 16 source bytes, 32 under halving; NP as rgb_unit's.
+ * ALPHA: the four pixels' alpha bytes as a third dword (rgbaToA_c / abgrToA_c, input.c:305-319; never under halving: alpha is a luma-sized plane) */
+template <int NP, bool ALPHA = false>
+__device__ __forceinline__ void rgb32_unit(const uint8_t *line, int s, bool half, bool al4, bool al16, int limit, uint32_t ash, const RgbK &k, uint32_t &oa, uint32_t &ob,
+                                           uint32_t *alpha = nullptr)
+{
+    uint32_t p[4], c[4];
+    if (half) {
+        uint32_t w[8];
+        rgb32_load<8>(line, 8 * s, limit, al4, al16, w);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            /* alpha leaves before the sum: the two nine-bit sums of (c0, c1) stay inside the 16-bit lanes */
+            const uint32_t v0 = w[2 * q] >> ash, v1 = w[2 * q + 1] >> ash;
+            p[q] = sws_pair(v0, 0) + sws_pair(v1, 0);
+            c[q] = ((v0 >> 16) & 0xFFu) + ((v1 >> 16) & 0xFFu);
+        }
+    } else {
+        uint32_t w[4];
+        rgb32_load<4>(line, 4 * s, limit, al4, al16, w);
+        if constexpr (ALPHA) {
+            /* the alpha byte: byte 0 where the colours were shifted down, else byte 3 */
+            const uint32_t sel = ash ? 0x0C0C0C00u : 0x0C0C0C03u;
+            *alpha = sws_perm(0u, w[0], sel) | (sws_perm(0u, w[1], sel) << 8) | (sws_perm(0u, w[2], sel) << 16) | (sws_perm(0u, w[3], sel) << 24);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const uint32_t v = w[q] >> ash;
+            p[q] = sws_pair(v, 0);
+            c[q] = (v >> 16) & 0xFFu;
+        }
+    }
+    oa = ob = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        oa |= sws_opaque((uint32_t)(sws_dot2(p[q], k.a01, (int)c[q] * k.a2 + k.rnd) >> k.sh)) << (8 * q);
+        if (NP > 1) ob |= sws_opaque((uint32_t)(sws_dot2(p[q], k.b01, (int)c[q] * k.b2 + k.rnd) >> k.sh)) << (8 * q);
+    }
+}
+/* one converted sample from its bytes (the direct form and the Tier-1 line kernels): px the sample's first pixel, first: 1 where alpha is the
+ * pixel's first byte */
+__device__ __forceinline__ void rgb32_sample(const uint8_t *px, bool half, int first, const RgbK &k, int &a, int &b)
+{
+    int c0 = px[first], c1 = px[first + 1], c2 = px[first + 2];
+    if (half) { c0 += px[first + 4]; c1 += px[first + 5]; c2 += px[first + 6]; }
+    a = (c0 * (int16_t)(k.a01 & 0xFFFF) + c1 * (int16_t)(k.a01 >> 16) + c2 * k.a2 + k.rnd) >> k.sh;
+    b = (c0 * (int16_t)(k.b01 & 0xFFFF) + c1 * (int16_t)(k.b01 >> 16) + c2 * k.b2 + k.rnd) >> k.sh;
+}
+/* the unit and the sample of a pixel of BPX bytes: 3 — the rgb24 forms above, 4 — the 32-bit ones */
+template <int NP, int BPX>
+__device__ __forceinline__ void px_unit(const uint8_t *line, int s, bool half, bool al4, bool al16, int limit, uint32_t ash, const RgbK &k, uint32_t &oa, uint32_t &ob)
+{
+    if constexpr (BPX == 4) rgb32_unit<NP>(line, s, half, al4, al16, limit, ash, k, oa, ob);
+    else rgb_unit<NP>(line, s, half, al4, limit, k, oa, ob);
+}
+template <int BPX>
+__device__ __forceinline__ void px_sample(const uint8_t *px, bool half, uint32_t ash, const RgbK &k, int &a, int &b)
+{
+    if constexpr (BPX == 4) rgb32_sample(px, half, (int)(ash >> 3), k, a, b);
+    else rgb_sample(px, half, k, a, b);
+}
 /* bytes -> int16 << 7, two per dword (the identity form) */
 __device__ __forceinline__ sws_u32x4 bytes_shl7(uint32_t b0, uint32_t b1)
 {
@@ -888,17 +1023,23 @@ __device__ __forceinline__ sws_u32x4 bytes_shl7(uint32_t b0, uint32_t b1)
  * srcW its last sample reads pixel srcW, three bytes past the line's width, as the reference does.  NP 1: luma into out_a; NP 2: U into out_a,
  * V into out_b.  Planes on 4-byte multiples are fetched in dwords (12 / 24 bytes a unit of four samples, whole inside the bytes the reference
  * reads), any other byte by byte — the staged form takes either, so a plane's alignment never sends a tile to the direct form.  Identity,
- * staged and direct forms as hscale_tile's (direct: spans wider than a staged line and non-monotonic banks). */
-template <int COLS, int OP, int NP>
+ * staged and direct forms as hscale_tile's (direct: spans wider than a staged line and non-monotonic banks).
+ * BPX 4: a 32-bit source, a pixel one dword (ash: sws_src_ash of its order) — 16 / 32 bytes a unit, in 16-byte pieces on planes of 16-byte multiples,
+ * dwords on 4-byte multiples (what the contract asks for), byte by byte otherwise; with an odd srcW the halving converter reads the four bytes of
+ * pixel srcW.  ALPHA (BPX 4, luma): out_b takes the alpha plane from the same pixel fetch — the reference's rgbaToA_c / abgrToA_c line through
+ * hyScale with the LUMA bank (swscale.c:269-276); two planes staged, as for chroma. */
+template <int COLS, int OP, int NP, int BPX = 3, bool ALPHA = false>
 __device__ __forceinline__ void hscale_tile_rgb(int16_t (*out_a)[OP], int16_t (*out_b)[OP], const uint8_t *src, int stride, int srcW, int nsamp, bool half, bool bgr,
                                                 const int32_t *posT, const int16_t *coefT, int fs, int gx0, int ncols, int lo, int hi,
-                                                uint32_t *stage_mem, int tid, bool zero_tail, bool may_stage, bool identity)
+                                                uint32_t *stage_mem, int tid, bool zero_tail, bool may_stage, bool identity, uint32_t ash = 0)
 {
+    static_assert(!ALPHA || (BPX == 4 && NP == 2), "the alpha plane rides with the luma of a 32-bit source as a second staged plane");
     constexpr int PITCH = StageGeom<COLS>::PITCH, LR = StageGeom<COLS>::LINES / NP;      /* staged lines of a plane per round */
     static_assert(StageGeom<COLS>::LINES % NP == 0 && LR >= NT / COLS, "every thread's first line is staged");
-    const RgbK K = rgb_consts(NP > 1, half, bgr);
+    const RgbK K = rgb_consts(NP > 1 && !ALPHA, half, bgr);
     const bool al4 = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 3) == 0;
-    const int limit = 3 * (half ? (srcW + 1) & ~1 : srcW);                               /* bytes of a line the reference reads */
+    const bool al16 = BPX == 4 && ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 15) == 0;
+    const int limit = BPX * (half ? (srcW + 1) & ~1 : srcW);                             /* bytes of a line the reference reads */
     if (identity) {
         /* converted sample << 7.  Eight columns per thread: two units, one 16-byte LDS write per plane */
         constexpr int TPL = COLS / 8;                  /* threads per line */
@@ -908,8 +1049,14 @@ __device__ __forceinline__ void hscale_tile_rgb(int16_t (*out_a)[OP], int16_t (*
         for (int l = lo + tid / TPL; l <= hi; l += NT / TPL) {
             const uint8_t *line = src + (size_t)l * stride;
             uint32_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;
-            if (keep[0]) rgb_unit<NP>(line, gxi, half, al4, limit, K, a0, b0);
-            if (keep[1]) rgb_unit<NP>(line, gxi + 4, half, al4, limit, K, a1, b1);
+            if constexpr (ALPHA) {
+                uint32_t none;
+                if (keep[0]) rgb32_unit<1, true>(line, gxi, false, al4, al16, limit, ash, K, a0, none, &b0);
+                if (keep[1]) rgb32_unit<1, true>(line, gxi + 4, false, al4, al16, limit, ash, K, a1, none, &b1);
+            } else {
+            if (keep[0]) px_unit<NP, BPX>(line, gxi, half, al4, al16, limit, ash, K, a0, b0);
+            if (keep[1]) px_unit<NP, BPX>(line, gxi + 4, half, al4, al16, limit, ash, K, a1, b1);
+            }
             if (zero_tail || gxi < ncols) {
                 *reinterpret_cast<sws_u32x4 *>(&out_a[l - lo][xg]) = bytes_shl7(a0 & keep[0], a1 & keep[1]);
                 if (NP > 1) *reinterpret_cast<sws_u32x4 *>(&out_b[l - lo][xg]) = bytes_shl7(b0 & keep[0], b1 & keep[1]);
@@ -939,13 +1086,14 @@ __device__ __forceinline__ void hscale_tile_rgb(int16_t (*out_a)[OP], int16_t (*
     }
     if (!(may_stage && span_fits(nd, s0, s1, PITCH))) {
         if (col_ok) {
-            const int step = half ? 6 : 3;
+            const int step = half ? 2 * BPX : BPX;
             for (int l = lo + tid / COLS; l <= hi; l += per) {
                 const uint8_t *s = src + (size_t)l * stride + (size_t)step * pos;
                 int a = 0, b = 0;
                 for (int j = 0; j < fs; j++) {
                     int ya, yb;
-                    rgb_sample(s + step * j, half, K, ya, yb);
+                    px_sample<BPX>(s + step * j, half, ash, K, ya, yb);
+                    if constexpr (ALPHA) yb = s[step * j + (ash ? 0 : 3)];
                     a += ya * f[j]; b += yb * f[j];
                 }
                 a >>= 7; b >>= 7;
@@ -953,7 +1101,10 @@ __device__ __forceinline__ void hscale_tile_rgb(int16_t (*out_a)[OP], int16_t (*
                 if (NP > 1) out_b[l - lo][x] = (int16_t)(b < 32767 ? b : 32767);
             }
         } else if (zero_tail) {
-            for (int l = lo + tid / COLS; l <= hi; l += per) out_a[l - lo][x] = 0;
+            for (int l = lo + tid / COLS; l <= hi; l += per) {
+                out_a[l - lo][x] = 0;
+                if constexpr (ALPHA) out_b[l - lo][x] = 0;
+            }
         }
         return;
     }
@@ -965,7 +1116,8 @@ __device__ __forceinline__ void hscale_tile_rgb(int16_t (*out_a)[OP], int16_t (*
             const int r = mi355_div20(idx, inv), d = idx - r * nd, line = base + r;
             if (line > hi) continue;
             uint32_t oa, ob;
-            rgb_unit<NP>(src + (size_t)line * stride, a0 + 4 * d, half, al4, limit, K, oa, ob);
+            if constexpr (ALPHA) { uint32_t none; rgb32_unit<1, true>(src + (size_t)line * stride, a0 + 4 * d, false, al4, al16, limit, ash, K, oa, none, &ob); }
+            else px_unit<NP, BPX>(src + (size_t)line * stride, a0 + 4 * d, half, al4, al16, limit, ash, K, oa, ob);
             stage[0][r][d] = oa;
             if (NP > 1) stage[1][r][d] = ob;
         }
@@ -996,11 +1148,14 @@ __device__ __forceinline__ void hscale_tile_rgb(int16_t (*out_a)[OP], int16_t (*
  * zero coefficient and a valid line index).  A thread owns one output row and every 16th pair of it. */
 /* DST: the destination form (DST_RGB24 / DST_BGR24 / DST_RGB32) — the row offsets of a pair (lut_rows_d), the bytes of a pixel and the store (store8_d,
  * write_pair_d); everything up to the LUT is one text for the three */
-template <int NL, int NC, bool WIDE, int DST = DST_RGB24>
+/* ALPHA (DST_RGB32): the row's alpha from s_alp — the luma tile's lines and the LUMA taps, in the form of the row's template (output.c:972-985,
+ * :1030-1035, :1070-1075) — enters each pixel where 255 goes otherwise */
+template <int NL, int NC, bool WIDE, int DST = DST_RGB24, bool ALPHA = false>
 __device__ __forceinline__ void vertical_rows(const SwsDev &c, const LutLds &lut, const int16_t (*s_lum)[TW], const int16_t (*s_cu)[TW / 2],
                                               const int16_t (*s_cv)[TW / 2], uint8_t (*s_out)[TW * dst_bpp<DST>()], int tid, int y0, int y1, int llo, int clo,
-                                              int npairs, int mode, uint8_t *wide_dst, int dst_stride, int out_row0)
+                                              int npairs, int mode, uint8_t *wide_dst, int dst_stride, int out_row0, const int16_t (*s_alp)[TW] = nullptr)
 {
+    static_assert(!ALPHA || DST == DST_RGB32, "alpha goes to a 32-bit destination");
     /* out_row0: first tile row of this pass of the narrow form (s_out holds OUT_ROWS rows at a time; nine of a 32-bit destination) */
     constexpr int BPP = dst_bpp<DST>();
     const uint32_t sel = DST == DST_RGB32 ? c.dst_sel : 0u;
@@ -1109,6 +1264,35 @@ __device__ __forceinline__ void vertical_rows(const SwsDev &c, const LutLds &lut
         int r[4], g[4], b[4];
 #pragma unroll
         for (int p = 0; p < 4; p++) lut_rows_d<DST>(lut, U[p], V[p], r[p], g[p], b[p]);
+        if constexpr (ALPHA) {
+            int A[8];
+            if (mode == 1) {
+                const sws_u32x4 a0 = *reinterpret_cast<const sws_u32x4 *>(&s_alp[li[0]][8 * grp]);
+#pragma unroll
+                for (int k = 0; k < 8; k++) A[k] = clip_u8(lane16(a0, k) >> 7);
+            } else if (mode == 2) {
+                const int ya = lf[NL > 1 ? 1 : 0], ya1 = 4096 - ya;
+                const sws_u32x4 a0 = *reinterpret_cast<const sws_u32x4 *>(&s_alp[li[0]][8 * grp]), a1 = *reinterpret_cast<const sws_u32x4 *>(&s_alp[li[NL > 1 ? 1 : 0]][8 * grp]);
+#pragma unroll
+                for (int k = 0; k < 8; k++) A[k] = clip_u8((lane16(a0, k) * ya1 + lane16(a1, k) * ya) >> 19);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; k++) A[k] = 1 << 18;
+#pragma unroll
+                for (int j = 0; j < NL; j++) {
+                    const sws_u32x4 a = *reinterpret_cast<const sws_u32x4 *>(&s_alp[li[j]][8 * grp]);
+#pragma unroll
+                    for (int k = 0; k < 8; k++) A[k] += lane16(a, k) * lf[j];
+                }
+#pragma unroll
+                for (int p = 0; p < 4; p++) {       /* clipped per pair, only if one of its two values has bit 8 set (output.c:981) */
+                    int &A1 = A[2 * p], &A2 = A[2 * p + 1];
+                    A1 >>= 19; A2 >>= 19;
+                    if ((A1 | A2) & 0x100) { A1 = clip_u8(A1); A2 = clip_u8(A2); }
+                }
+            }
+            rgb32_store8_a(lut, wide_dst + (size_t)row * dst_stride + 8 * BPP * grp, Y, A, r, g, b, sel);
+        } else
         store8_d<DST>(lut, wide_dst + (size_t)row * dst_stride + 8 * BPP * grp, Y, r, g, b, sel);
         return;
     }
@@ -1141,14 +1325,34 @@ __device__ __forceinline__ void vertical_rows(const SwsDev &c, const LutLds &lut
             Y1 >>= 19; Y2 >>= 19; U >>= 19; V >>= 19;
             if ((Y1 | Y2 | U | V) & 0x100) { Y1 = clip_u8(Y1); Y2 = clip_u8(Y2); U = clip_u8(U); V = clip_u8(V); }
         }
+        if constexpr (ALPHA) {
+            int A1, A2;
+            if (mode == 1) { A1 = clip_u8(s_alp[li[0]][2 * i] >> 7); A2 = clip_u8(s_alp[li[0]][2 * i + 1] >> 7); }
+            else if (mode == 2) {
+                const int ya = lf[NL > 1 ? 1 : 0], ya1 = 4096 - ya;
+                A1 = clip_u8((s_alp[li[0]][2 * i] * ya1 + s_alp[li[NL > 1 ? 1 : 0]][2 * i] * ya) >> 19);
+                A2 = clip_u8((s_alp[li[0]][2 * i + 1] * ya1 + s_alp[li[NL > 1 ? 1 : 0]][2 * i + 1] * ya) >> 19);
+            } else {
+                A1 = A2 = 1 << 18;
+#pragma unroll
+                for (int j = 0; j < NL; j++) {
+                    const uint32_t two = *reinterpret_cast<const uint32_t *>(&s_alp[li[j]][2 * i]);
+                    A1 += (int16_t)(two & 0xFFFF) * lf[j]; A2 += (int16_t)(two >> 16) * lf[j];
+                }
+                A1 >>= 19; A2 >>= 19;
+                if ((A1 | A2) & 0x100) { A1 = clip_u8(A1); A2 = clip_u8(A2); }
+            }
+            write_pair_a(lut, &s_out[row - out_row0][i * 2 * BPP], Y1, Y2, U, V, A1, A2, sel);
+        } else
         write_pair_d<DST>(lut, &s_out[row - out_row0][i * 2 * BPP], Y1, Y2, U, V, sel);
     }
 }
 /* LDS of a workgroup, sized per context (sws_plan): the horizontal pass's results for the source lines a tile needs, the tables, and one
  * block shared by the staging lines (horizontal pass) and the output rows of tiles that cannot store from registers (after it). */
-__host__ __device__ constexpr int sws_lds_bytes(int lum_lines, int chr_lines, int stage = STAGE_BYTES)
+/* alpha: with the alpha tile of an ALPHA instance, as many lines as the luma tile */
+__host__ __device__ constexpr int sws_lds_bytes(int lum_lines, int chr_lines, int stage = STAGE_BYTES, bool alpha = false)
 {
-    return lum_lines * TW * 2 + 2 * chr_lines * (TW / 2) * 2 + (int)sizeof(LutLds) + stage;
+    return lum_lines * TW * 2 + 2 * chr_lines * (TW / 2) * 2 + (int)sizeof(LutLds) + stage + (alpha ? lum_lines * TW * 2 : 0);
 }
 /* the waves per SIMD the register allocation of a tile kernel aims at: a CU's 160 KB of LDS hold that many of its workgroups, one wave of
  * each per SIMD */
@@ -1161,10 +1365,10 @@ __host__ __device__ constexpr int sws_waves(int lds_bytes) { return 160 * 1024 /
 __host__ __device__ constexpr int tap_bucket(int fs) { return fs <= 1 ? 0 : (fs <= 2 ? 1 : (fs <= 4 ? 2 : 3)); }
 /* Tiles that cannot store from registers (the picture's right edge, a destination that is not 8-byte aligned, filters of more than
  * eight taps): the rows go through s_out, OUT_ROWS at a time. */
-template <int DST = DST_RGB24>
+template <int DST = DST_RGB24, bool ALPHA = false>
 __device__ __forceinline__ void vertical_narrow(const SwsDev *cp, const LutLds *lutp, const int16_t (*s_lum)[TW], const int16_t (*s_cu)[TW / 2],
                                                           const int16_t (*s_cv)[TW / 2], uint8_t (*s_out)[TW * dst_bpp<DST>()], uint8_t *tile_dst, int dst_stride,
-                                                          int x0, int y0, int y1, int llo, int clo)
+                                                          int x0, int y0, int y1, int llo, int clo, const int16_t (*s_alp)[TW] = nullptr)
 {
     constexpr int BPP = dst_bpp<DST>(), OUT_ROWS = out_rows<DST>();
     const SwsDev c = sws_dev(cp);
@@ -1176,22 +1380,22 @@ __device__ __forceinline__ void vertical_narrow(const SwsDev *cp, const LutLds *
     for (int r0 = 0; r0 < nrows_all; r0 += OUT_ROWS) {
         if (ls <= 8 && cs <= 8) {
             switch (bl * 4 + bc) {
-            case 0: vertical_rows<1, 1, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 1: vertical_rows<1, 2, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 2: vertical_rows<1, 4, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 3: vertical_rows<1, 8, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 4: vertical_rows<2, 1, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 5: vertical_rows<2, 2, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 6: vertical_rows<2, 4, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 7: vertical_rows<2, 8, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 8: vertical_rows<4, 1, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 9: vertical_rows<4, 2, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 10: vertical_rows<4, 4, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 11: vertical_rows<4, 8, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 12: vertical_rows<8, 1, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 13: vertical_rows<8, 2, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            case 14: vertical_rows<8, 4, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
-            default: vertical_rows<8, 8, false, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0); break;
+            case 0: vertical_rows<1, 1, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            case 1: vertical_rows<1, 2, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            case 2: vertical_rows<1, 4, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            case 3: vertical_rows<1, 8, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            case 4: vertical_rows<2, 1, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            case 5: vertical_rows<2, 2, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            case 6: vertical_rows<2, 4, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            case 7: vertical_rows<2, 8, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            case 8: vertical_rows<4, 1, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            case 9: vertical_rows<4, 2, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            case 10: vertical_rows<4, 4, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            case 11: vertical_rows<4, 8, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            case 12: vertical_rows<8, 1, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            case 13: vertical_rows<8, 2, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            case 14: vertical_rows<8, 4, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
+            default: vertical_rows<8, 8, false, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, nullptr, dst_stride, r0, s_alp); break;
             }
         } else
         for (int p = tid; p < OUT_ROWS * (TW / 2); p += NT) {
@@ -1201,6 +1405,10 @@ __device__ __forceinline__ void vertical_narrow(const SwsDev *cp, const LutLds *
             int ya = 0, ua = 0;
             if (mode == 1) ua = cs == 1 ? 0 : c.vChrC[2 * gy + 1];
             else if (mode == 2) { ya = c.vLumC[2 * gy + 1]; ua = c.vChrC[2 * gy + 1]; }
+            if constexpr (ALPHA) {
+                R.alpT = s_alp;
+                rgb_pair<DST, true>(s_lut, &s_out[row - r0][i * 2 * BPP], R, i, mode, c.vLumC + (size_t)gy * ls, ls, c.vChrC + (size_t)gy * cs, cs, ya, ua, c.dst_sel);
+            } else
             rgb_pair<DST>(s_lut, &s_out[row - r0][i * 2 * BPP], R, i, mode, c.vLumC + (size_t)gy * ls, ls, c.vChrC + (size_t)gy * cs, cs, ya, ua, c.dst_sel);
         }
         __syncthreads();
@@ -1253,6 +1461,15 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
     __shared__ __attribute__((aligned(16))) uint8_t s_io[stage_bytes<ST>()];
     constexpr int BPP = dst_bpp<DST>();
     uint8_t (*s_out)[TW * BPP] = reinterpret_cast<uint8_t (*)[TW * BPP]>(s_io);
+    /* ALPHA: a 32-bit source whose alpha goes to a 32-bit destination — a fourth tile of the luma tile's lines (sws_lds_bytes(..., true)) */
+    constexpr bool ALPHA = std::is_same<ST, SwsPx32A>::value;
+    static_assert(!ALPHA || (RGB && DST == DST_RGB32), "alpha is carried from a 32-bit source to a 32-bit destination");
+    [[maybe_unused]] int16_t (*s_alp_w)[TW] = nullptr;
+    if constexpr (ALPHA) {
+        __shared__ __attribute__((aligned(16))) int16_t s_alp_tile[LCAP][TW];
+        s_alp_w = s_alp_tile;
+    }
+    [[maybe_unused]] const int16_t (*const s_alp)[TW] = s_alp_w;
     const SwsDev c = sws_dev(cp);
     mi355_sws_frame fr = frames[blockIdx.z];
     for (int k = 0; k < 3; k++) fr.src[k] = mi355_global(fr.src[k]);
@@ -1269,6 +1486,20 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
     /* horizontal pass: luma (the phantom partner of the last sample of an odd-width picture reads the
      * zero-initialised tail of the reference's line buffer, utils.c:1241-1262), then the chroma planes */
     uint32_t *s_stage = reinterpret_cast<uint32_t *>(s_io);
+    if constexpr (RGB && sizeof(ST) == 4) {
+        /* a 32-bit source: the order's two uniform values from the record */
+        static_assert(!NV, "packed RGB sources have one plane");
+        const bool bgr = sws_src_bgr(c.src_layout), half = c.src_hsub != 0;
+        const uint32_t ash = sws_src_ash(c.src_layout);
+        if constexpr (ALPHA)
+            hscale_tile_rgb<TW, TW, 2, 4, true>(s_lum, s_alp_w, fr.src[0], fr.src_stride[0], c.srcW, c.srcW, false, bgr, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi,
+                                                s_stage, tid, true, c.hstage != 0, c.hident_l != 0, ash);
+        else
+        hscale_tile_rgb<TW, TW, 1, 4>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.srcW, false, bgr, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi,
+                                      s_stage, tid, true, c.hstage != 0, c.hident_l != 0, ash);
+        hscale_tile_rgb<TW / 2, TW / 2, 2, 4>(s_cu, s_cv, fr.src[0], fr.src_stride[0], c.srcW, c.chrSrcW, half, bgr, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi,
+                                              s_stage, tid, false, c.hstage != 0, c.hident_c != 0, ash);
+    } else
     if constexpr (RGB) {
         static_assert(sizeof(ST) == 1 && !NV, "packed RGB sources are 8 bit");
         const bool bgr = c.src_layout == MI355_SWS_SRC_BGR24, half = c.src_hsub != 0;
@@ -1301,26 +1532,26 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
     const int bl = tap_bucket(ls), bc = tap_bucket(cs);
     if (wide_dst) {                               /* uniform over the workgroup: every row leaves from registers */
         switch (bl * 4 + bc) {
-        case 0: vertical_rows<1, 1, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 1: vertical_rows<1, 2, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 2: vertical_rows<1, 4, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 3: vertical_rows<1, 8, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 4: vertical_rows<2, 1, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 5: vertical_rows<2, 2, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 6: vertical_rows<2, 4, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 7: vertical_rows<2, 8, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 8: vertical_rows<4, 1, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 9: vertical_rows<4, 2, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 10: vertical_rows<4, 4, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 11: vertical_rows<4, 8, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 12: vertical_rows<8, 1, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 13: vertical_rows<8, 2, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        case 14: vertical_rows<8, 4, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
-        default: vertical_rows<8, 8, true, DST>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0); break;
+        case 0: vertical_rows<1, 1, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        case 1: vertical_rows<1, 2, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        case 2: vertical_rows<1, 4, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        case 3: vertical_rows<1, 8, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        case 4: vertical_rows<2, 1, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        case 5: vertical_rows<2, 2, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        case 6: vertical_rows<2, 4, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        case 7: vertical_rows<2, 8, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        case 8: vertical_rows<4, 1, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        case 9: vertical_rows<4, 2, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        case 10: vertical_rows<4, 4, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        case 11: vertical_rows<4, 8, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        case 12: vertical_rows<8, 1, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        case 13: vertical_rows<8, 2, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        case 14: vertical_rows<8, 4, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
+        default: vertical_rows<8, 8, true, DST, ALPHA>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, s_alp); break;
         }
         return;
     }
-    vertical_narrow<DST>(cp, &s_lut, s_lum, s_cu, s_cv, s_out, tile_dst, fr.dst_stride, x0, y0, y1, llo, clo);
+    vertical_narrow<DST, ALPHA>(cp, &s_lut, s_lum, s_cu, s_cv, s_out, tile_dst, fr.dst_stride, x0, y0, y1, llo, clo, s_alp);
 }
 
 /* ---- planar destinations: yuv420p -> yuv420p / yuv422p / yuv444p ----------------------------------------------------------
@@ -1656,6 +1887,11 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
     const int ls = c.vls, cs = c.vcs;
     /* source lines the tile needs (swscale.c:459-468 for the first tap, :571-616 for the clamping) */
     const int llo = clampi(imax(1 - ls, c.vLumP[y0]), 0, c.srcH - 1), lhi = clampi(imax(1 - ls, c.vLumP[y1]) + ls - 1, 0, c.srcH - 1);
+    if constexpr (RGB && sizeof(ST) == 4) {
+        static_assert(!NV, "packed RGB sources have one plane");
+        hscale_tile_rgb<TW, TW, 1, 4>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.srcW, false, sws_src_bgr(c.src_layout), c.hLumP, c.hLumC, c.hls, x0, c.dstW,
+                                      llo, lhi, s_stage, tid, false, c.hstage != 0, c.hident_l != 0, sws_src_ash(c.src_layout));
+    } else
     if constexpr (RGB) {
         static_assert(sizeof(ST) == 1 && !NV, "packed RGB sources are 8 bit");
         hscale_tile_rgb<TW, TW, 1>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.srcW, false, c.src_layout == MI355_SWS_SRC_BGR24, c.hLumP, c.hLumC, c.hls, x0, c.dstW,
@@ -1667,6 +1903,11 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
         clo = clampi(imax(1 - cs, c.vChrP[cy0]), 0, c.chrSrcH - 1);
         const int chi = clampi(imax(1 - cs, c.vChrP[cy1]) + cs - 1, 0, c.chrSrcH - 1);
         nchr = chi - clo + 1;
+        if constexpr (RGB && sizeof(ST) == 4) {
+            int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
+            hscale_tile_rgb<CW, 2 * CW, 2, 4>(s_u, s_v, fr.src[0], fr.src_stride[0], c.srcW, c.chrSrcW, c.src_hsub != 0, sws_src_bgr(c.src_layout), c.hChrP, c.hChrC, c.hcs,
+                                              x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, sws_src_ash(c.src_layout));
+        } else
         if constexpr (RGB) {
             int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
             hscale_tile_rgb<CW, 2 * CW, 2>(s_u, s_v, fr.src[0], fr.src_stride[0], c.srcW, c.chrSrcW, c.src_hsub != 0, c.src_layout == MI355_SWS_SRC_BGR24, c.hChrP, c.hChrC, c.hcs,
@@ -2155,6 +2396,8 @@ __global__ void __launch_bounds__(NT) k_sws_line_nv12(const int16_t *filter, int
 struct PackedRows {
     const int16_t *l, *u, *v;
     int pitch;
+    const int16_t *a = nullptr;                 /* the alpha lines of the _a line entries: the luma lines' count and pitch */
+    __device__ __forceinline__ int alp(int j, int x) const { return a[(size_t)j * pitch + x]; }
     __device__ __forceinline__ int lum(int j, int x) const { return l[(size_t)j * pitch + x]; }
     __device__ __forceinline__ int cu(int j, int x) const { return u[(size_t)j * pitch + x]; }
     __device__ __forceinline__ int cv(int j, int x) const { return v[(size_t)j * pitch + x]; }
@@ -2201,5 +2444,14 @@ void mi355_sws_launch_line_packed(int dst_format, hipStream_t s, const mi355_sws
                                   const int16_t *u, const int16_t *v, int cs, int pitch, uint8_t *dest, int dstW, int yalpha, int uvalpha);
 /* ... and of k_sws_c24 on one slice with stand-alone tables (mi355_sws_yuv2rgb_c: a 4:2:0 slice) */
 void mi355_sws_launch_c24_slice(int dst_format, dim3 grid, hipStream_t s, const mi355_sws_luts *luts, int dstW, int rows, const mi355_sws_frame *frames);
+
+/* sws_rgb32.hip: the launches of the tile instances of a 32-bit source (MI355_SWS_SRC_RGBA ... _ABGR) — instance i (0 / 1 / 2: A / B / C) of
+ * k_sws_generic to dst_format 0 / MI355_SWS_DST_BGR24 ... _ABGR (alpha: the ALPHA form, a 32-bit destination), and of k_sws_planar: kind 0 plain, 1 RANGE, 2 DEEP; form 0 three planes at
+ * CW = TW / 2, 1 at CW = TW, 2 a semi-planar destination.  Compiled in a file of their own. */
+void mi355_sws_launch_generic_rgb32(int i, int dst_format, int alpha, dim3 grid, hipStream_t s, const void *d, const mi355_sws_frame *frames);
+void mi355_sws_launch_planar_rgb32(int i, int kind, int form, dim3 grid, hipStream_t s, const void *d, const mi355_sws_planar_frame *frames);
+/* ... and of the line kernel k_sws_line_packed_a (one workgroup): k_sws_line_packed of a 32-bit order with the ls alpha lines `a` at the luma lines' pitch */
+void mi355_sws_launch_line_packed_a(int dst_format, hipStream_t s, const mi355_sws_luts *luts, int mode, const int16_t *lumF, const int16_t *l, int ls, const int16_t *chrF,
+                                    const int16_t *u, const int16_t *v, int cs, const int16_t *a, int pitch, uint8_t *dest, int dstW, int yalpha, int uvalpha);
 
 #endif

@@ -55,8 +55,14 @@ def main():
                          "source traffic; bgr24 the same destination bytes, bgra a third more: 2160p -> 1080p from yuv420p, nv12 and yuv420p10le, 1080p at "
                          "equal size through k_sws_ident1 and through the special converter; the twin a second time in another allocation (A/A); 32 and "
                          "512 pictures per launch, 3 warm-up + --steps launches a round, alternating, median of 3 rounds")
+    ap.add_argument("--rgb32src", action="store_true",
+                    help="32-bit (bgra) sources beside THE SAME descriptor with an rgb24 source on the same build — identical banks and destination, a "
+                         "third more source bytes: 2160p -> 1080p to yuv420p, nv12 and bgra, 1080p -> yuv420p and nv12 at equal size; 2160p -> 1080p bgra -> "
+                         "bgra with alpha beside the same context with alpha 0 (equal bytes); the twin a second time in another allocation (A/A), with "
+                         "--other-lib also on that build (the parent commit's) together with its 2160p -> 1080p yuv420p -> bgra point; 32 and 512 pictures "
+                         "per launch, 3 warm-up + --steps launches a round, alternating, median of 3 rounds")
     ap.add_argument("--other-lib", default=None,
-                    help="--nv12 / --nvsrc / --rgbsrc / --range: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
+                    help="--nv12 / --nvsrc / --rgbsrc / --range / --rgb32src: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
     ap.add_argument("--rounds", type=int, default=5, help="--planar / --sources: alternating rounds (the median is reported)")
     a = ap.parse_args()
     prov = providers.mi355()
@@ -79,6 +85,8 @@ def main():
         return deepdst_points(a, lib)
     if a.packeddst:
         return packeddst_points(a, lib)
+    if a.rgb32src:
+        return rgb32src_points(a, lib)
     orc = S.oracle_backend(providers.oracle())
     for name in a.configs.split(","):
         ctx = S.load_context(name)
@@ -740,6 +748,123 @@ def packeddst_points(a, lib, points=None, frame_counts=(32, 512)):
                                   "ms_rounds": [round(x, 4) for x in times[k]]}), flush=True)
             for b in batches.values():
                 b.close()
+
+
+def rgb32src_points(a, lib, points=None, frame_counts=(32, 512)):
+    """A 32-bit (bgra) source beside its twin: the context of the same sizes, destination and flags from rgb24 on the same build has the same
+    banks and destination traffic and reads three bytes a pixel where this one reads four; and the alpha form (bgra -> bgra with the source's alpha
+    carried) beside the same context with alpha 0, which moves the same bytes.  The contexts come from the reference's libswscale at run time
+    (oracle/_ref/libswsref.so: mi355_sws_describe_rgb32 / _fmt / _packed) — no full-size context is committed.  `twin#2` is the twin a second time
+    with its own buffers: the session's A/A spread.  With --other-lib the twin also runs on that build (the parent commit's), and so does the
+    2160p -> 1080p yuv420p -> bgra point of --packeddst on both builds: what existed before must not have moved.  One process, the batches of a
+    point alternating: 3 warm-up + --steps launches a round, median of 3 rounds, at 32 and 512 pictures per launch.  Algorithmic bytes: sources
+    read once + destinations written once.  `bound`: this context's algorithmic bytes over the twin's — what it may cost if it moves them at the
+    twin's achieved bandwidth.  The last line sums the session up: `aa_session` — the largest A/A spread of its points — and under `miss` every
+    row whose time exceeds its twin's times the byte ratio plus that spread."""
+    import statistics
+    import sws_packeddst as K
+    import sws_planar as P
+    import sws_rgb32src as Q
+    import sws_rgbsrc as R
+    other = None
+    if a.other_lib:
+        other = C.CDLL(os.path.abspath(a.other_lib))
+        other.mi355_init.restype = C.c_int
+        assert other.mi355_init(C.c_int(0)) == 0
+        other.mi355_event_create.restype = C.c_void_p
+        other.mi355_event_elapsed_ms.restype = C.c_float
+    ref = Q.Ref(P.bind(Q.REF_LIB))
+    rounds = 3
+    # (point, srcW, srcH, dstW, dstH, destination of tests/sws_rgb32src.py)
+    points = points or [("uhd_to_hd_yuv420p", 3840, 2160, 1920, 1080, "420"), ("uhd_to_hd_nv12", 3840, 2160, 1920, 1080, "nv12"),
+                        ("uhd_to_hd_bgra", 3840, 2160, 1920, 1080, "bgra"), ("hd_same_yuv420p", 1920, 1080, 1920, 1080, "420"),
+                        ("hd_same_nv12", 1920, 1080, 1920, 1080, "nv12")]
+
+    def batch(l, e, pics, frames, create, **kw):
+        if e.fmt == 0 or e.fmt >= 32:
+            return SourceBatch(l, None, e, pics, frames, create=create, bpp=4 if e.fmt >= 33 else 3, **kw)
+        return PlaneBatch(l, create(l, e), pics, e.out_sizes(), frames)
+
+    rows = []
+
+    def report(point, frames, batches, times, base_key, spread_keys, extra):
+        base = statistics.median(times[base_key])
+        spread = abs(statistics.median(times[spread_keys[1]]) / statistics.median(times[spread_keys[0]]) - 1.0)
+        twin_bytes = batches[base_key][1].src_bytes + batches[base_key][1].dst_bytes
+        for k, (l, b) in batches.items():
+            ms = statistics.median(times[k])
+            us = ms * 1e3 / frames
+            nb = b.src_bytes + b.dst_bytes
+            out = {"workload": point + ":" + k, "frames_per_launch": frames, "ms_per_launch": ms, "us_per_picture": us, "frames_per_s": 1e6 / us,
+                   "algorithmic_bytes_per_frame": nb, "achieved_GBps": nb / us * 1e-3, "frac_of_8TBps": nb / us * 1e-3 / 8000.0,
+                   "vs_twin": ms / base - 1.0, "bound": nb / twin_bytes - 1.0, "aa_spread": spread, "ms_rounds": [round(x, 4) for x in times[k]]}
+            out.update(extra.get(k, {}))
+            rows.append(out)
+            print(json.dumps(out), flush=True)
+
+    for frames in frame_counts:
+        for point, sw, sh, dw, dh, dst in points:
+            row = (sw, sh, dw, dh, "bgra", dst, 1, 1, 1, 0)            # a row of tests/sws_rgb32src.py's table, not entered into it
+            c = ref.open(row)
+            e = ref.describe_rgb32(c)
+            ref.free(c)
+            c = ref.open_twin(row)
+            t = ref.describe_packed(c) if dst in Q.LAYOUTS else ref.describe_fmt(c)
+            ref.free(c)
+            assert e is not None and t is not None, point
+            t = Q.Entry(t.ctx, t.depth, t.hsub, t.vsub, t.dither, t.fmt, t.layout)
+            R.SHAPES["_bench"] = (sw, sh, dw, dh, "rgb24", "rgb", 1, 1, 1, 0)
+            qpics = [Q.picture(row, "noise", seed=s) for s in (1, 2)]
+            tpics = [R.picture("_bench", seed=s) for s in (1, 2)]
+            batches = {"bgra_source": (lib, batch(lib, e, qpics, frames, lambda l, x: Q.create(l, x, alpha=0))),
+                       "twin": (lib, batch(lib, t, tpics, frames, Q.create)), "twin#2": (lib, batch(lib, t, tpics, frames, Q.create))}
+            if other:
+                batches["twin@parent"] = (other, batch(other, t, tpics, frames, Q.create))
+            plan = Q.plan_of(lib, batches["bgra_source"][1].handle)
+            times = {k: [] for k in batches}
+            for _ in range(rounds):
+                for k, (l, b) in batches.items():
+                    times[k].append(time_ms(l, b.run, a.steps))
+            report(point, frames, batches, times, "twin", ("twin", "twin#2"), {"bgra_source": {"kernel": plan["kernel"], "hstaged": plan["hstaged"], "hsub": plan["hsub"]}})
+            for l, b in batches.values():
+                b.close()
+        # the alpha form beside the same context with alpha 0: equal bytes
+        row = (3840, 2160, 1920, 1080, "bgra", "bgra", 1, 1, 1, 0)
+        c = ref.open(row)
+        e = ref.describe_rgb32(c)
+        ref.free(c)
+        assert e is not None and e.alpha == 1
+        qpics = [Q.picture(row, "noise", seed=s) for s in (1, 2)]
+        mk = lambda al: (lib, batch(lib, e, qpics, frames, lambda l, x: Q.create(l, x, alpha=al)))    # noqa: E731
+        batches = {"alpha": mk(1), "alpha0": mk(0), "alpha0#2": mk(0)}
+        times = {k: [] for k in batches}
+        for _ in range(rounds):
+            for k, (l, b) in batches.items():
+                times[k].append(time_ms(l, b.run, a.steps))
+        report("uhd_to_hd_bgra_to_bgra", frames, batches, times, "alpha0", ("alpha0", "alpha0#2"), {})
+        for l, b in batches.values():
+            b.close()
+        if other:
+            # what --packeddst has as its headline, on both builds
+            krow = (3840, 2160, 1920, 1080, "yuv420p", "bgra", 1, 1, 1)
+            kref = K.Ref(P.bind(K.REF_LIB))
+            c = kref.open(krow)
+            ke = kref.describe_packed(c)
+            kref.free(c)
+            kpics = [K.picture(krow, "noise", seed=s) for s in (1, 2)]
+            batches = {"this": (lib, SourceBatch(lib, None, ke, kpics, frames, create=K.create, bpp=4)),
+                       "this#2": (lib, SourceBatch(lib, None, ke, kpics, frames, create=K.create, bpp=4)),
+                       "parent": (other, SourceBatch(other, None, ke, kpics, frames, create=K.create, bpp=4))}
+            times = {k: [] for k in batches}
+            for _ in range(rounds):
+                for k, (l, b) in batches.items():
+                    times[k].append(time_ms(l, b.run, a.steps))
+            report("packeddst_uhd_to_hd_yuv420p_to_bgra", frames, batches, times, "parent", ("this", "this#2"), {})
+            for l, b in batches.values():
+                b.close()
+    aa = max(r["aa_spread"] for r in rows)
+    miss = ["%s@%d %+.1f%% (bound %+.1f%%)" % (r["workload"], r["frames_per_launch"], 100 * r["vs_twin"], 100 * (r["bound"] + aa)) for r in rows if r["vs_twin"] > r["bound"] + aa]
+    print(json.dumps({"summary": "rgb32src", "aa_session": aa, "points": len(rows), "miss": miss}), flush=True)
 
 
 if __name__ == "__main__":
