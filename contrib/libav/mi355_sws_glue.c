@@ -85,6 +85,17 @@
  *                          _rgb32ToA and the packed loops of an alpha context to mi355_sws_yuv2packed_X_a / _2_a / _1_a.  Declined: the unscaled
  *                          converters of these sources (rgbToRgbWrapper, the plain copy: no banks), YUVA on either side, 15 / 16-bit RGB,
  *                          SWS_FULL_CHR_H_INT, SWS_FAST_BILINEAR.  The seven describers above keep declining these sources.
+ *   packed 4:2:2 sources   yuyv422, uyvy422 and yvyu422 (the reference runs the byte picks yuy2ToY_c / uyvyToY_c and yuy2ToUV_c / yvy2ToUV_c /
+ *                          uyvyToUV_c on each line, then the ordinary hyScale / hcScale; at equal size to yuv420p / yuv422p it takes one of
+ *                          its four unscaled converters, yuyvToYuv420Wrapper ... uyvyToYuv422Wrapper) have a describer of their own,
+ *                          mi355_sws_describe_yuy2(), for mi355_sws_create_src_layout_range_depth(): a context without banks whose swscale
+ *                          is one of the four wrappers is described with unscaled_special = 1 (the device's k_sws_yuy2_split) for callers
+ *                          of the C ABI — ff_get_unscaled_swscale sets c->swscale without passing a selector this file wraps, so like the
+ *                          NV splitter it is not bound here.  The generic scaler's contexts are described in full and bound like those of a
+ *                          32-bit source: whole pictures through mi355_swsfunc (described again at every picture; one the creators refuse
+ *                          stays the reference's).  With MI355_SWS_LINES=1 their two input converters go to mi355_sws_yuy2ToY / _yuy2ToUV,
+ *                          the horizontal and output loops as for every other source.
+ *                          The eight describers above keep declining these sources.
  * The device is MI355_DEVICE (default 0), as for the decoder bridges.
  */
 #include <pthread.h>
@@ -544,6 +555,90 @@ int mi355_sws_describe_rgb32(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_
     return 0;
 }
 
+/* ---- packed 4:2:2 sources: yuyv422, uyvy422, yvyu422 ---------------------------------------------------------------------------------------
+ * The MI355_SWS_SRC_* of such a source, 0 for any other format */
+static int yuy2_layout_of(const SwsContext *c)
+{
+    switch (c->srcFormat) {
+    case AV_PIX_FMT_YUYV422: return MI355_SWS_SRC_YUYV422;
+    case AV_PIX_FMT_UYVY422: return MI355_SWS_SRC_UYVY422;
+    case AV_PIX_FMT_YVYU422: return MI355_SWS_SRC_YVYU422;
+    default: return 0;
+    }
+}
+/* the input converters the context HOLDS are the byte picks of `layout` (the functions are static in the reference: one group of four distinct bytes
+ * through each, as rgb32_probe does) */
+static int yuy2_probe(const SwsContext *c, int layout)
+{
+    static const uint8_t b[8] = { 0x11, 0x22, 0x33, 0x44, 0x55, 0x66, 0x77, 0x88 };
+    const int lum = layout == MI355_SWS_SRC_UYVY422, uo = layout == MI355_SWS_SRC_UYVY422 ? 0 : (layout == MI355_SWS_SRC_YVYU422 ? 3 : 1);
+    uint8_t y[4] = { 0 }, u[4] = { 0 }, v[4] = { 0 };
+    if (!c->lumToYV12 || !c->chrToYV12 || c->alpToYV12) return -1;
+    c->lumToYV12(y, b, 1, NULL);
+    c->chrToYV12(u, v, b, b, 1, NULL);
+    return y[0] == b[lum] && u[0] == b[uo] && v[0] == b[uo ^ 2] ? 0 : -1;
+}
+/* what mi355_sws_create_src_layout_range_depth takes for a live context FROM one of the three formats (0), -1 for every other context — the eight
+ * describers above keep declining these sources.  A context without the vertical banks is one of the four unscaled converters (yuyvToYuv420Wrapper,
+ * uyvyToYuv420Wrapper, yuyvToYuv422Wrapper, uyvyToYuv422Wrapper, swscale_unscaled.c:1140-1149: yuyv422 / uyvy422 to yuv420p / yuv422p at equal size and
+ * equal range, whatever the flags): unscaled_special = 1, no banks; any other without them (a copy, the packed-to-packed wrappers, yvyu422) is
+ * declined.  The generic scaler's contexts: both input converters the byte picks of the layout (yuy2_probe), no other reader; to rgb24, bgr24 and the four
+ * 32-bit orders, to 8-bit planar / semi-planar YUV with or without range converters, to 9- / 10-bit planar YUV — described in full, whether or not the
+ * device's creators take them yet.  Declined: SWS_FULL_CHR_H_INT, SWS_FAST_BILINEAR, a chroma line drop, YUVA destinations, 15 / 16-bit RGB */
+int mi355_sws_describe_yuy2(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *src_layout, int *dst_format, int *range, int *dst_depth)
+{
+    const int layout = yuy2_layout_of(c);
+    int fmt, bits = 8, r = MI355_SWS_RANGE_NONE;
+    if (!layout || c->chrSrcHSubSample != 1 || c->chrSrcVSubSample != 0) return -1;
+    const int special = !c->vLumFilter;
+    if (special) {
+        if (layout == MI355_SWS_SRC_YVYU422 || !c->swscale || c->srcW != c->dstW || c->srcH != c->dstH || c->hLumFilter || c->hChrFilter || c->vChrFilter) return -1;
+        if (c->dstFormat != AV_PIX_FMT_YUV420P && c->dstFormat != AV_PIX_FMT_YUV422P) return -1;
+        fmt = c->dstFormat == AV_PIX_FMT_YUV420P ? MI355_SWS_DST_YUV420P : MI355_SWS_DST_YUV422P;
+    } else {
+        if (!c->vChrFilter || !c->hLumFilter || !c->hChrFilter) return -1;
+        if (c->hyscale_fast || c->hcscale_fast || c->vChrDrop || (c->flags & SWS_FULL_CHR_H_INT)) return -1;
+        if (c->srcBpc != 8 || c->readLumPlanar || c->readChrPlanar || c->readAlpPlanar || c->alpPixBuf) return -1;
+        if (yuy2_probe(c, layout) != 0) return -1;
+        r = range_probe(c);
+        if (r < 0) return -1;
+        if (deep_dst(c, &bits)) {
+            if (r || c->dstBpc != bits) return -1;
+            fmt = deep_dst(c, &bits);
+        } else if (packed_dst_of(c) || c->dstFormat == AV_PIX_FMT_RGB24) {
+            if (r) return -1;
+            fmt = packed_dst_of(c);
+        } else {
+            switch (c->dstFormat) {
+            case AV_PIX_FMT_YUV420P: fmt = MI355_SWS_DST_YUV420P; break;
+            case AV_PIX_FMT_YUV422P: fmt = MI355_SWS_DST_YUV422P; break;
+            case AV_PIX_FMT_YUV444P: fmt = MI355_SWS_DST_YUV444P; break;
+            case AV_PIX_FMT_NV12:    fmt = MI355_SWS_DST_NV12; break;
+            case AV_PIX_FMT_NV21:    fmt = MI355_SWS_DST_NV21; break;
+            default: return -1;
+            }
+        }
+    }
+    const int yuv = fmt >= MI355_SWS_DST_YUV420P && fmt <= MI355_SWS_DST_NV21;
+    memset(s, 0, sizeof(*s));
+    s->depth = 8; s->hsub = 1; s->vsub = 0;
+    memcpy(s->dither, ff_dither_8x8_128, sizeof(s->dither));
+    memset(d, 0, sizeof(*d));
+    d->srcW = c->srcW; d->srcH = c->srcH; d->dstW = c->dstW; d->dstH = c->dstH;
+    d->chrSrcW = c->chrSrcW; d->chrSrcH = c->chrSrcH; d->chrDstW = c->chrDstW;
+    d->unscaled_special = special;
+    if (!special) {
+        d->hLum = (mi355_sws_filter){ c->hLumFilter, c->hLumFilterPos, c->hLumFilterSize, c->dstW };
+        d->hChr = (mi355_sws_filter){ c->hChrFilter, c->hChrFilterPos, c->hChrFilterSize, c->chrDstW };
+        d->vLum = (mi355_sws_filter){ c->vLumFilter, c->vLumFilterPos, c->vLumFilterSize, c->dstH };
+        d->vChr = (mi355_sws_filter){ c->vChrFilter, c->vChrFilterPos, c->vChrFilterSize, yuv ? c->chrDstH : c->dstH };
+        if (!fmt) luts_of(c, &d->luts);
+        else if (!yuv) luts_packed(c, fmt, &d->luts);
+    }
+    *src_layout = layout; *dst_format = fmt; *range = r; *dst_depth = bits;
+    return 0;
+}
+
 #ifndef MI355_SWS_DESCRIBE_ONLY
 static void t1_hscale16(SwsContext *c, int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
 {
@@ -750,11 +845,52 @@ static int init_rgb32(SwsContext *c)
     return 1;
 }
 
+/* ... of a packed 4:2:2 source (yuy2ToY_c / uyvyToY_c, yuy2ToUV_c / yvy2ToUV_c / uyvyToUV_c): one shim per byte order and converter */
+#define T1_YUY2(order, layout) \
+static void t1_ ## order ## ToY(uint8_t *dst, const uint8_t *src, int width, uint32_t *pal) { (void)pal; n_calls++; mi355_sws_yuy2ToY(dst, src, width, layout); } \
+static void t1_ ## order ## ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src1, const uint8_t *src2, int width, uint32_t *pal) \
+{ (void)src2; (void)pal; n_calls++; mi355_sws_yuy2ToUV(dstU, dstV, src1, width, layout); }
+T1_YUY2(yuyv, MI355_SWS_SRC_YUYV422)
+T1_YUY2(uyvy, MI355_SWS_SRC_UYVY422)
+T1_YUY2(yvyu, MI355_SWS_SRC_YVYU422)
+/* the inner loops of a context of the generic scaler from a packed 4:2:2 source (mi355_sws_describe_yuy2 takes it): the two input converters, the
+ * horizontal loops and the output loops of its destination.  The four unscaled converters have no inner loops: they stay the reference's here */
+static int init_yuy2(SwsContext *c)
+{
+    mi355_sws_desc d;
+    mi355_sws_src s;
+    int layout, fmt, range, depth;
+    if (!yuy2_layout_of(c)) return 0;
+    /* (returning 1 for a context this describer declines is deliberate: ff_sws_init_mi355x ends there, no older describer takes these sources) */
+    if (mi355_sws_describe_yuy2(c, &d, &s, &layout, &fmt, &range, &depth) != 0 || d.unscaled_special || !device_ready() || !c->hyScale || !c->hcScale) return 1;
+    const int yuv = fmt >= MI355_SWS_DST_YUV420P && fmt <= MI355_SWS_DST_NV21;
+    if (yuv ? (!c->yuv2planeX || !c->yuv2plane1) : (!c->yuv2packedX || !c->yuv2packed2 || !c->yuv2packed1)) return 1;
+    if (layout == MI355_SWS_SRC_YUYV422) { c->lumToYV12 = t1_yuyvToY; c->chrToYV12 = t1_yuyvToUV; }
+    else if (layout == MI355_SWS_SRC_UYVY422) { c->lumToYV12 = t1_uyvyToY; c->chrToYV12 = t1_uyvyToUV; }
+    else { c->lumToYV12 = t1_yvyuToY; c->chrToYV12 = t1_yvyuToUV; }
+    c->hyScale = c->hcScale = t1_hscale;
+    if (range > 0) {
+        c->lumConvertRange = range == MI355_SWS_RANGE_TO_JPEG ? t1_lumToJpeg : t1_lumFromJpeg;
+        c->chrConvertRange = range == MI355_SWS_RANGE_TO_JPEG ? t1_chrToJpeg : t1_chrFromJpeg;
+    }
+    if (yuv) {
+        c->yuv2planeX = depth == 9 ? t1_planeX_9 : (depth == 10 ? t1_planeX_10 : t1_planeX);
+        c->yuv2plane1 = depth == 9 ? t1_plane1_9 : (depth == 10 ? t1_plane1_10 : t1_plane1);
+        if (c->yuv2nv12cX) c->yuv2nv12cX = t1_nv12cX;
+    } else if (!fmt) {
+        c->yuv2packedX = t1_packedX; c->yuv2packed2 = t1_packed2; c->yuv2packed1 = t1_packed1;
+    } else {
+        c->yuv2packedX = t1_pkX; c->yuv2packed2 = t1_pk2; c->yuv2packed1 = t1_pk1;
+    }
+    return 1;
+}
+
 void ff_sws_init_mi355x(SwsContext *c)
 {
     mi355_sws_src s;
     int layout;
     if (init_rgb32(c)) return;
+    if (init_yuy2(c)) return;
     const int range = range_probe(c);
     /* (an NV12 / NV21 source: c->chrToYV12 stays the reference's) */
     const int fmt = range > 0 ? fmt_format_r(c, &s, 0, &layout, 1) : fmt_format(c, &s, 0, &layout);
@@ -817,7 +953,8 @@ typedef struct Bound {
     int range;                    /* ... the MI355_SWS_RANGE_* its converters gave when it was bound (mi355_sws_describe_range / mi355_sws_create_src_layout_range) */
     int depth;                    /* ... the bits of its planar destination: 8, or 9 / 10 (mi355_sws_describe_depth / mi355_sws_create_src_layout_range_depth) */
     int packed;                   /* ... MI355_SWS_DST_BGR24 ... _ABGR of a packed destination beside rgb24 (mi355_sws_describe_packed), else 0; planar is 0 then */
-    int rgb32;                    /* a 32-bit source (mi355_sws_describe_rgb32: layout, planar / packed, range and depth above are what it gave) ... */
+    int rgb32;                    /* 1: a 32-bit source (mi355_sws_describe_rgb32: layout, planar / packed, range and depth above are what it gave) ...;
+                                   * 2: a packed 4:2:2 source in the generic scaler (mi355_sws_describe_yuy2, the same fields; never alpha) */
     int alpha;                    /* ... whose alpha goes to the 32-bit destination (mi355_sws_create_src_layout_alpha) */
     mi355_sws_ctx *dev;
     int failed;                   /* the device side does not take this context: the reference's function from now on */
@@ -876,6 +1013,16 @@ static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
         rgb32 = other = 1;
         if (fmt >= MI355_SWS_DST_BGR24) packed = fmt; else planar = fmt;
     } else
+    if (!special && yuy2_layout_of(c)) {
+        /* a packed 4:2:2 source: one describer as well.  Only the generic scaler's contexts get here (the four unscaled wrappers are set without a
+         * selector: they stay the reference's, like every context the describer declines) */
+        mi355_sws_desc d;
+        mi355_sws_src s;
+        int fmt;
+        if (mi355_sws_describe_yuy2(c, &d, &s, &layout, &fmt, &range, &depth) != 0 || d.unscaled_special) return real;
+        rgb32 = 2; other = 1;
+        if (fmt >= MI355_SWS_DST_BGR24) packed = fmt; else planar = fmt;
+    } else
     if (!(taken(c) || planar)) {
         mi355_sws_src s;
         int fmt = fmt_format(c, &s, special, &layout);
@@ -925,11 +1072,13 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
     const int semi = b && (b->planar == MI355_SWS_DST_NV12 || b->planar == MI355_SWS_DST_NV21);      /* two planes: dstStride[2] is not looked at */
     /* a context bound with range conversion: the converters it holds NOW give the direction it was bound with (range_probe), else the
      * reference's function for that picture too */
-    /* a 32-bit source: described again — layout, destination, range, depth and alpha must be what the context was bound with */
+    /* a 32-bit source: described again — layout, destination, range, depth and alpha must be what the context was bound with; a packed 4:2:2 source
+     * likewise, through its own describer */
     mi355_sws_desc d32;
     mi355_sws_src s32;
     int l32 = 0, f32 = 0, r32 = 0, dp32 = 8, a32 = 0;
-    const int rgb32_ok = b && b->rgb32 && mi355_sws_describe_rgb32(c, &d32, &s32, &l32, &f32, &r32, &dp32, &a32) == 0 && l32 == b->layout &&
+    const int rgb32_ok = b && b->rgb32 && (b->rgb32 == 2 ? mi355_sws_describe_yuy2(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 && !d32.unscaled_special
+                                                         : mi355_sws_describe_rgb32(c, &d32, &s32, &l32, &f32, &r32, &dp32, &a32) == 0) && l32 == b->layout &&
                          f32 == (b->packed ? b->packed : b->planar) && r32 == b->range && dp32 == b->depth && a32 == b->alpha;
     const int planar_ok = b && b->planar && dstStride[1] > 0 && (semi || dstStride[2] > 0) && (b->rgb32 ? rgb32_ok :
                           (b->other ? fmt_format_r(c, &s_now, 0, &l_now, b->depth > 8 ? MI355_ASK_DEEP : b->range != 0) : planar_format(c)) == b->planar &&
@@ -938,7 +1087,7 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
     /* an rgb24 context of another source: range conversion set since it was bound is the reference's for that picture, as above */
     const int other_ok = !b || !b->other || (b->rgb32 ? rgb32_ok : (b->planar || (b->packed ? fmt_format_r(c, &s_now, b->special, &l_now, MI355_ASK_PACKED) == b->packed
                                                                                                   : fmt_format(c, &s_now, b->special, &l_now) == 0)));
-    /* an NV12 / NV21 source has two planes: srcStride[2] is not looked at; a packed rgb24 / bgr24 source has one */
+    /* an NV12 / NV21 source has two planes: srcStride[2] is not looked at; a packed rgb24 / bgr24, 32-bit or 4:2:2 source has one */
     const int one_plane = b && (b->layout == MI355_SWS_SRC_RGB24 || b->layout == MI355_SWS_SRC_BGR24 || b->rgb32);
     if (b && !b->failed && srcSliceY == 0 && srcSliceH == c->srcH &&
         srcStride[0] > 0 && (one_plane || srcStride[1] > 0) && (b->layout || srcStride[2] > 0) && dstStride[0] > 0 && (!b->planar || planar_ok) && other_ok) {

@@ -8,7 +8,10 @@
  * destinations also at 9 or 10 bits (yuv420p9le ... yuv444p10le: yuv2planeX_10 / yuv2plane1_10); packed destinations also as bgr24 and as
  * rgba / bgra / argb / abgr (yuv2rgb_write output.c:825-867; yuv2rgb_c_24_bgr / yuv2rgb_c_32), from every source rgb24 is written from; and from
  * packed 32-bit rgba / bgra / argb / abgr sources (rgb32ToY_c ... bgr321ToUV_half_c input.c:165-291 in front of hyScale / hcScale) to all of these,
- * the source's alpha carried to a 32-bit destination where asked for (rgbaToA_c / abgrToA_c and the hasAlpha forms of the packed templates).
+ * the source's alpha carried to a 32-bit destination where asked for (rgbaToA_c / abgrToA_c and the hasAlpha forms of the packed templates); and
+ * from packed 4:2:2 yuyv422 / uyvy422 / yvyu422 sources (the byte picks yuy2ToY_c ... uyvyToUV_c input.c:369-473 in front of hyScale / hcScale) to all
+ * of these, with the reference's four unscaled converters yuyv422 / uyvy422 -> yuv420p / yuv422p (yuyvToYuv420Wrapper ... uyvyToYuv422Wrapper
+ * swscale_unscaled.c:227-287).
  *
  * The reference keeps these behind function pointers of the (private) SwsContext
  * (libswscale/swscale_internal.h:253-540): hyScale/hcScale :526-531, yuv2plane1/yuv2planeX/
@@ -90,7 +93,8 @@ enum {
     MI355_SWS_K_PLANAR_B = 7,     /* ... 40 / 24 */
     MI355_SWS_K_PLANAR_C = 8,     /* ... 48 / 48 */
     MI355_SWS_K_NV12_PACK = 9,    /* the unscaled yuv420p -> NV12 / NV21 packer (k_sws_nv12_pack); scaled NV12 / NV21 contexts report PLANAR_A / B / C */
-    MI355_SWS_K_NV12_SPLIT = 10   /* the unscaled NV12 / NV21 -> yuv420p splitter (k_sws_nv12_split); scaled NV12 / NV21 SOURCES report the values above */
+    MI355_SWS_K_NV12_SPLIT = 10,  /* the unscaled NV12 / NV21 -> yuv420p splitter (k_sws_nv12_split); scaled NV12 / NV21 SOURCES report the values above */
+    MI355_SWS_K_YUY2_SPLIT = 11   /* the unscaled yuyv422 / uyvy422 -> yuv420p / yuv422p splitter (k_sws_yuy2_split) */
 };
 typedef struct mi355_sws_plan_info {
     int kernel;                   /* MI355_SWS_K_* */
@@ -139,7 +143,7 @@ typedef struct mi355_sws_dest_info {
     int format;                   /* 0 rgb24, else MI355_SWS_DST_* */
     int planes;                   /* 1 rgb24 and the other packed destinations, 2 NV12 / NV21, 3 planar */
     int chr_bytes, chr_rows;      /* bytes per row and rows the context writes to each chroma plane (0 / 0 for rgb24; the packer: 2 * (srcW / 2), srcH / 2;
-                                   * the splitter: srcW / 2, srcH / 2) */
+                                   * the splitter: srcW / 2, srcH / 2; the packed-4:2:2 splitter: (srcW + 1) / 2, and srcH / 2 to yuv420p, srcH to yuv422p) */
 } mi355_sws_dest_info;
 int mi355_sws_destination(const mi355_sws_ctx *ctx, mi355_sws_dest_info *info);   /* 0, -1 bad argument */
 
@@ -236,6 +240,41 @@ enum { MI355_SWS_SRC_RGBA = 8, MI355_SWS_SRC_BGRA = 9, MI355_SWS_SRC_ARGB = 10, 
 mi355_sws_ctx *mi355_sws_create_src_layout_alpha(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format, int alpha);
 int mi355_sws_alpha(const mi355_sws_ctx *ctx);   /* 0 / 1, -1 bad argument */
 
+/* ---- packed 4:2:2 sources: yuyv422 / uyvy422 / yvyu422 (what capture devices deliver; the reference's yuy2ToY_c / yuy2ToUV_c / yvy2ToUV_c /
+ * uyvyToY_c / uyvyToUV_c input.c:369-473, pure byte picks in front of hyScale / hcScale, and its four unscaled converters yuyvToYuv420Wrapper /
+ * uyvyToYuv420Wrapper / yuyvToYuv422Wrapper / uyvyToYuv422Wrapper swscale_unscaled.c:227-287 over yuyvtoyuv420_c ... uyvytoyuv422_c
+ * rgb2rgb_template.c:854-928) ----
+ * layout 16 .. 18 of mi355_sws_create_src_layout and of every creator that forwards to it (3, 6, 7 and 12 .. 15 stay refused).  The names give the
+ * byte order IN MEMORY, per group of four bytes covering pixels 2i and 2i + 1:
+ *   yuyv422  Y0 U Y1 V   luma x at byte 2x,     U i at 4i + 1, V i at 4i + 3
+ *   yvyu422  Y0 V Y1 U   luma x at byte 2x,     U i at 4i + 3, V i at 4i + 1
+ *   uyvy422  U Y0 V Y1   luma x at byte 2x + 1, U i at 4i,     V i at 4i + 2
+ * Nothing is rounded, weighted or clipped in front of the scaler: the picked bytes are the samples of an 8-bit 4:2:2 source.  The source record is
+ * that source's: src->depth 8, src->hsub 1, src->vsub 0, desc->chrSrcW == AV_CEIL_RSHIFT(srcW, 1), desc->chrSrcH == desc->srcH (anything else: NULL
+ * and a message).  The frame is ONE source plane of 2 * srcW bytes a row in src[0]; src[1], src[2] and their strides are never read and may be
+ * NULL / 0.  mi355_sws_create_src_layout_alpha with alpha 1 refuses these layouts (NULL and a message).
+ * The SCALER (desc->unscaled_special 0) takes all three layouts to every dst_format the rgb24 source takes: 0 and 32 .. 36, MI355_SWS_DST_YUV420P /
+ * _YUV422P / _YUV444P at 8, 9 and 10 bits, _NV12 / _NV21, and both ranges (FROM_JPEG and TO_JPEG: unlike an RGB source a YUV source can differ from its
+ * destination either way) to every 8-bit YUV destination.  Twin rule: such a context has the banks, the plan (GENERIC_A .. C, PLANAR_A .. C, IDENT1_1)
+ * and the refusals of the 8-bit yuv422p-source context with the same descriptor — it is refused exactly where that twin's tiles cannot hold the
+ * lines; chroma sits on every source line.  At equal size to a packed RGB destination (the reference has no special converter there and runs its
+ * scaler with one luma and one chroma tap) the plan is MI355_SWS_K_IDENT1_1, straight from the packed bytes (k_sws_ident1_yuy2), never the tile
+ * kernel; with vsub 0 no context reaches MI355_SWS_K_IDENT1_X.
+ * The four unscaled special converters: desc->unscaled_special = 1 with layout 16 / 17 (the reference has no wrapper for
+ * yvyu422: layout 18 is refused) to MI355_SWS_DST_YUV420P or _YUV422P — 8 bit, no range, srcW == dstW, srcH == dstH, chrDstW == AV_CEIL_RSHIFT(dstW, 1),
+ * no banks; every other special combination gets NULL and a message.  Frames go through the planar entry points (mi355_sws_planar_frame).  Luma:
+ * srcW bytes on each of srcH rows.  To yuv422p: AV_CEIL_RSHIFT(srcW, 1) bytes of each chroma plane on each of srcH rows.  To yuv420p: chroma row r is
+ * (a + b) >> 1 of source lines 2r and 2r + 1, truncating as the C template does — AV_CEIL_RSHIFT(srcW, 1) bytes on srcH / 2 rows ROUNDED DOWN: the
+ * last chroma row of an odd height stays untouched and a one-line picture writes no chroma at all (NOT the NV splitter's rule, which rounds the width
+ * down too).  mi355_sws_destination reports those chr_bytes / chr_rows, mi355_sws_plan MI355_SWS_K_YUY2_SPLIT.
+ * Read extent and alignment.  A line is read over 2 * srcW bytes — and, with an ODD srcW, over 2 * (srcW + 1) bytes, as the reference reads it: its
+ * last chroma sample takes the second half of the last group, whatever lies there (the next line's first bytes, padding, or the bytes behind the
+ * picture).  The caller keeps those two bytes readable on the last line too.  No byte past that is read, except on a plane whose pointer and stride
+ * are multiples of 16: it is fetched in aligned 16-byte pieces and must be readable over its whole stride.  A plane on 4-byte multiples is fetched
+ * in dwords that lie whole inside the bytes named here; any other plane is read byte by byte (the reference has no alignment demand on these
+ * formats: a pixel pair may start on an odd address).  The Tier-1 host entry points return -1 for src_stride[0] < 2 * srcW. */
+enum { MI355_SWS_SRC_YUYV422 = 16, MI355_SWS_SRC_UYVY422 = 17, MI355_SWS_SRC_YVYU422 = 18 };
+
 /* ---- range conversion: contexts whose source and destination differ in range, to a YUV destination (yuvj420p <-> yuv420p and their kin:
  * c->srcRange != c->dstRange && !isAnyRGB(c->dstFormat), lumConvertRange / chrConvertRange swscale.c:168-198, :748-766) ----
  * The reference applies the two converters to every horizontally scaled int16 line, between hyScale / hcScale and the vertical pass
@@ -321,6 +360,10 @@ void mi355_sws_rgb24ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int w
 void mi355_sws_rgb32ToY(uint8_t *dst, const uint8_t *src, int width, int layout);
 void mi355_sws_rgb32ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int width, int layout, int half);
 void mi355_sws_rgb32ToA(uint8_t *dst, const uint8_t *src, int width, int layout);
+/* yuy2ToY_c / uyvyToY_c and yuy2ToUV_c / yvy2ToUV_c / uyvyToUV_c input.c:369-473 (c->lumToYV12 / c->chrToYV12 of a packed 4:2:2 source): layout
+ * MI355_SWS_SRC_YUYV422 ... _YVYU422 (any other value does nothing); `width` OUTPUT samples — ToY reads 2 * width bytes, ToUV 4 * width */
+void mi355_sws_yuy2ToY(uint8_t *dst, const uint8_t *src, int width, int layout);
+void mi355_sws_yuy2ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int width, int layout);
 /* lumRangeFromJpeg_c / lumRangeToJpeg_c and chrRangeFromJpeg_c / chrRangeToJpeg_c swscale.c:168-198 (c->lumConvertRange / c->chrConvertRange):
  * `width` int16 samples converted in place, any int16 value (a result outside int16 is stored truncated, as the reference stores it) */
 void mi355_sws_lumConvertRange(int16_t *dst, int width, int to_jpeg);

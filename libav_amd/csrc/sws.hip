@@ -7,7 +7,9 @@
  * 10 bits (yuv420p9le ... yuv444p10le: yuv2planeX_10 / yuv2plane1_10 output.c:183-213; their tile instances are launched from sws_deep.hip), and
  * to bgr24 / rgba / bgra / argb / abgr wherever rgb24 is written (yuv2rgb_write output.c:825-867; their instances are launched from sws_packed.hip);
  * packed 32-bit rgba / bgra / argb / abgr SOURCES to all of these, with the source's alpha carried to a 32-bit destination where the caller asks for it
- * (mi355_sws_create_src_layout_alpha; their instances, line kernels and line entries are sws_rgb32.hip's).  This file:
+ * (mi355_sws_create_src_layout_alpha; their instances, line kernels and line entries are sws_rgb32.hip's); and packed 4:2:2 yuyv422 / uyvy422 / yvyu422
+ * SOURCES to all of these, with the unscaled yuyv422 / uyvy422 -> yuv420p / yuv422p splitter (their tile instances, k_sws_ident1_yuy2, k_sws_yuy2_split
+ * and the line entries mi355_sws_yuy2ToY / _yuy2ToUV are sws_yuy2.hip's).  This file:
  * the context, the plan (which kernel a context gets) and the entry points of include/mi355_sws.h.  The device side is sws_dev.h:
  * k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1, k_sws_nv12_pack, k_sws_nv12_split and the k_sws_line_* kernels of the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
@@ -131,8 +133,12 @@ static int packed_bpp(const SwsDev &h) { return h.packed >= MI355_SWS_DST_RGBA ?
 static bool rgb32_src(const SwsDev &h) { return sws_rgb32_src(h.src_layout); }
 static bool packed_rgb(const SwsDev &h) { return h.src_layout == MI355_SWS_SRC_RGB24 || h.src_layout == MI355_SWS_SRC_BGR24 || rgb32_src(h); }
 static int src_bpx(const SwsDev &h) { return rgb32_src(h) ? 4 : 3; }
-/* the layouts the creators take: 0, 1, 2, 4, 5 and 8 .. 11 */
-static bool src_layout_taken(int l) { return (l >= MI355_SWS_SRC_PLANAR && l <= MI355_SWS_SRC_BGR24 && l != 3) || sws_rgb32_src(l); }
+/* a packed 4:2:2 source: yuyv422 / uyvy422 / yvyu422 (its tile instances, ident1 form, splitter and line entries are sws_yuy2.hip's) */
+static bool yuy2_src(const SwsDev &h) { return sws_yuy2_src(h.src_layout); }
+/* a source of ONE plane whose converted samples are staged (hscale_tile_rgb): packed RGB, or packed 4:2:2 */
+static bool converted_src(const SwsDev &h) { return packed_rgb(h) || yuy2_src(h); }
+/* the layouts the creators take: 0, 1, 2, 4, 5, 8 .. 11 and 16 .. 18 */
+static bool src_layout_taken(int l) { return (l >= MI355_SWS_SRC_PLANAR && l <= MI355_SWS_SRC_BGR24 && l != 3) || sws_rgb32_src(l) || sws_yuy2_src(l); }
 /* a context that does not scale, to rgb24: what k_sws_ident1 takes */
 static bool ident1_shape(const SwsDev &h)
 {
@@ -170,7 +176,7 @@ static void ctx_hfit(mi355_sws_ctx *c, const mi355_sws_desc *desc)
         }
         return false;
     };
-    if (packed_rgb(h)) c->hfit = fits_rgb(desc->hLum, h.hident_l, TW) || fits_rgb(desc->hChr, h.hident_c, cw);
+    if (converted_src(h)) c->hfit = fits_rgb(desc->hLum, h.hident_l, TW) || fits_rgb(desc->hChr, h.hident_c, cw);
     else
     c->hfit = fits(desc->hLum, h.hident_l, TW) || (h.src_layout ? fits_nv(desc->hChr, h.hident_c, cw) : fits(desc->hChr, h.hident_c, cw));
 }
@@ -228,6 +234,30 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
         return nullptr;
     }
     const char *const packed_name = sws_rgb32_src(layout) ? "rgba / bgra / argb / abgr" : "rgb24 / bgr24";
+    if (sws_yuy2_src(layout)) {
+        /* packed 4:2:2 (two bytes a pixel): 8 bit, chroma on every line at half the width (ctx_source has checked chrSrcW / chrSrcH against the shifts) */
+        if (h.depth != 8 || !h.src_hsub || h.src_vsub) {
+            std::fprintf(stderr, "mi355dsp: %s: a yuyv422 / uyvy422 / yvyu422 source is 8-bit 4:2:2 (%d bit, shifts %d/%d)\n", who, h.depth, h.src_hsub, h.src_vsub);
+            delete c;
+            return nullptr;
+        }
+        h.src_layout = layout;
+        /* the four unscaled converters (yuyvToYuv420Wrapper ... uyvyToYuv422Wrapper): none from yvyu422, to 8-bit yuv420p / yuv422p at equal size, no range */
+        if (h.special) {
+        if (layout == MI355_SWS_SRC_YVYU422 || !planar || (dst_format != MI355_SWS_DST_YUV420P && dst_format != MI355_SWS_DST_YUV422P) || range != MI355_SWS_RANGE_NONE ||
+            dst_depth != 8 || h.srcW != h.dstW || h.srcH != h.dstH || h.chrDstW != (h.dstW + 1) >> 1) {
+            std::fprintf(stderr, "mi355dsp: %s: the unscaled special converters of a packed 4:2:2 source are yuyv422 / uyvy422 -> yuv420p / yuv422p at equal size "
+                         "(layout %d, destination %d, %d bit, range %d, %dx%d -> %dx%d, chrDstW %d)\n", who, layout, dst_format, dst_depth, range, h.srcW, h.srcH, h.dstW, h.dstH,
+                         h.chrDstW);
+            delete c;
+            return nullptr;
+        }
+        h.planar = dst_format; h.hshift = 1; h.vshift = dst_format == MI355_SWS_DST_YUV420P ? 1 : 0;
+        h.chrDstH = (h.dstH + (1 << h.vshift) - 1) >> h.vshift;
+        return ctx_upload(c);
+        }
+        /* any other context is the scaler's: the banks, the plan and the refusals of the 8-bit yuv422p source of the same descriptor */
+    } else
     if (layout == MI355_SWS_SRC_RGB24 || layout == MI355_SWS_SRC_BGR24 || sws_rgb32_src(layout)) {
         /* packed RGB (three or four bytes a pixel): 8 bit, chroma on every line, the full or the halving converter (ctx_source has checked chrSrcW / chrSrcH against the shifts);
          * no special converter */
@@ -326,7 +356,7 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src_layout(const mi355_sws_desc *desc
     if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout without mi355_init(); no CPU fallback\n"); std::abort(); }
     if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout: no descriptor\n"); return nullptr; }
     if (!src_layout_taken(src_layout)) {
-        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr\n", src_layout);
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr / yuyv422 / uyvy422 / yvyu422\n", src_layout);
         return nullptr;
     }
     return ctx_create(desc, src, dst_format != 0 && !packed_dst(dst_format), dst_format, "mi355_sws_create_src_layout", src_layout);
@@ -357,7 +387,7 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range(const mi355_sws_desc
         return nullptr;
     }
     if (!src_layout_taken(src_layout)) {
-        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr\n", src_layout);
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr / yuyv422 / uyvy422 / yvyu422\n", src_layout);
         return nullptr;
     }
     /* the reference converts the range of YUV destinations only (an RGB one takes it into its LUTs), and never in an unscaled special converter */
@@ -383,7 +413,7 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range_depth(const mi355_sw
         return nullptr;
     }
     if (!src_layout_taken(src_layout)) {
-        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr\n", src_layout);
+        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr / yuyv422 / uyvy422 / yvyu422\n", src_layout);
         return nullptr;
     }
     if (dst_format < MI355_SWS_DST_YUV420P || dst_format > MI355_SWS_DST_YUV444P) {
@@ -426,12 +456,12 @@ static int sws_kernel(const SwsDev &h)
         return 2;
     };
     static_assert(MI355_SWS_K_GENERIC_C == MI355_SWS_K_GENERIC_A + 2 && MI355_SWS_K_PLANAR_C == MI355_SWS_K_PLANAR_A + 2, "A / B / C follow each other");
-    if (h.planar && h.special) return h.src_layout ? MI355_SWS_K_NV12_SPLIT : MI355_SWS_K_NV12_PACK;
+    if (h.planar && h.special) return yuy2_src(h) ? MI355_SWS_K_YUY2_SPLIT : (h.src_layout ? MI355_SWS_K_NV12_SPLIT : MI355_SWS_K_NV12_PACK);
     if (h.planar) return MI355_SWS_K_PLANAR_A + instance(PLANAR_SHAPES);
     if (h.special) return MI355_SWS_K_C24;
     /* a context that does not scale: straight from the source bytes (k_sws_ident1; MI355_SWS_NO_IDENT1=1, developer switch: through the tile all the same) */
     static const bool no_ident1 = std::getenv("MI355_SWS_NO_IDENT1") != nullptr;
-    if (!no_ident1 && ident1_shape(h) && !packed_rgb(h))
+    if (!no_ident1 && ident1_shape(h) && !packed_rgb(h) && !(yuy2_src(h) && h.vcs > 2))      /* (a packed 4:2:2 source has the _1 form only: chroma on every line) */
         return h.vcs <= 2 ? MI355_SWS_K_IDENT1_1 : MI355_SWS_K_IDENT1_X;      /* packed_mode() 1 / the X template */
     return MI355_SWS_K_GENERIC_A + instance(GENERIC_SHAPES);
 }
@@ -458,6 +488,9 @@ extern "C" int mi355_sws_source(const mi355_sws_ctx *c, mi355_sws_source_info *p
 }
 
 static bool semi_planar(const SwsDev &h) { return h.planar == MI355_SWS_DST_NV12 || h.planar == MI355_SWS_DST_NV21; }
+/* what the packed-4:2:2 splitter writes to each chroma plane: bytes a row, rows */
+static int yuy2_chr_bytes(const SwsDev &h) { return (h.srcW + 1) >> 1; }
+static int yuy2_chr_rows(const SwsDev &h) { return h.planar == MI355_SWS_DST_YUV420P ? h.srcH >> 1 : h.srcH; }
 
 extern "C" int mi355_sws_destination(const mi355_sws_ctx *c, mi355_sws_dest_info *p)
 {
@@ -469,6 +502,8 @@ extern "C" int mi355_sws_destination(const mi355_sws_ctx *c, mi355_sws_dest_info
     /* ... and so does the splitter (nv12ToPlanarWrapper) */
     p->chr_bytes = !h.planar ? 0 : (semi_planar(h) ? 2 * (h.special ? h.srcW >> 1 : h.chrDstW) : (h.special ? h.srcW >> 1 : h.chrDstW));
     p->chr_rows = !h.planar ? 0 : (h.special ? h.srcH >> 1 : h.chrDstH);
+    /* the packed-4:2:2 splitter rounds the width UP and, to yuv420p, the rows down (yuyvtoyuv420_c); to yuv422p every row has chroma */
+    if (h.special && yuy2_src(h)) { p->chr_bytes = yuy2_chr_bytes(h); p->chr_rows = yuy2_chr_rows(h); }
     if (h.dst_bits > 8) p->chr_bytes = 2 * h.chrDstW;       /* 16-bit samples (mi355_sws_dest_depth) */
     return 0;
 }
@@ -609,6 +644,12 @@ extern "C" int mi355_sws_scale_frames_dev(mi355_sws_ctx *c, const mi355_sws_fram
         mi355_sws_launch_generic_rgb32(k - MI355_SWS_K_GENERIC_A, h.packed, c->alpha, dim3((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes), s, c->d, d_frames);
         return hipGetLastError() == hipSuccess ? 0 : -2;
     }
+    if (yuy2_src(h)) {
+        /* a packed 4:2:2 source: the tile instances and the ident1 form of sws_yuy2.hip, to rgb24 and to the five other packed destinations */
+        if (k == MI355_SWS_K_IDENT1_1) mi355_sws_launch_ident1_yuy2(h.packed, dim3((h.dstW + C24_COLS - 1) / C24_COLS, (h.dstH + IDENT_ROWS - 1) / IDENT_ROWS, nframes), s, c->d, d_frames);
+        else mi355_sws_launch_generic_yuy2(k - MI355_SWS_K_GENERIC_A, h.packed, dim3((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes), s, c->d, d_frames);
+        return hipGetLastError() == hipSuccess ? 0 : -2;
+    }
     if (h.packed) {
         /* bgr24 and the 32-bit orders: the twin's kernel and grid, the DST_BGR24 / DST_RGB32 instance (sws_packed.hip) */
         const dim3 grid = k == MI355_SWS_K_C24 ? dim3((h.dstW + C24_COLS - 1) / C24_COLS, (h.srcH + C24_ROWS - 1) / C24_ROWS, nframes) :
@@ -656,10 +697,16 @@ extern "C" int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *c, const mi355_s
                            h.srcW, h.srcH, h.src_layout == MI355_SWS_SRC_NV21 ? 1 : 0, d_frames);
         return hipGetLastError() == hipSuccess ? 0 : -2;
     }
+    if (k == MI355_SWS_K_YUY2_SPLIT) {
+        mi355_sws_launch_yuy2_split(sws_yuy2_luma(h.src_layout), h.planar == MI355_SWS_DST_YUV420P ? 1 : 0, h.srcW, h.srcH, nframes, s, d_frames);
+        return hipGetLastError() == hipSuccess ? 0 : -2;
+    }
     const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
     const int i = k - MI355_SWS_K_PLANAR_A;
     /* a 32-bit source: plain, RANGE and DEEP instances of its own (sws_rgb32.hip) */
     if (rgb32_src(h)) mi355_sws_launch_planar_rgb32(i, h.dst_bits > 8 ? 2 : (h.range ? 1 : 0), semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
+    /* ... and so has a packed 4:2:2 one (sws_yuy2.hip) */
+    else if (yuy2_src(h)) mi355_sws_launch_planar_yuy2(i, h.dst_bits > 8 ? 2 : (h.range ? 1 : 0), semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
     /* a 9- / 10-bit destination: the DEEP instances (three planes, no range) */
     else if (h.dst_bits > 8) mi355_sws_launch_planar_deep(i, packed_rgb(h) ? 3 : (h.src_layout ? 2 : (h.depth > 8 ? 1 : 0)), h.hshift ? 0 : 1, grid, s, c->d, d_frames);
     else if (h.range) launch_planar_range(i, packed_rgb(h) ? 3 : (h.src_layout ? 2 : (h.depth > 8 ? 1 : 0)), semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
@@ -695,8 +742,9 @@ static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int
     /* a packed rgb24 / bgr24 source: one plane of 3 * srcW bytes a row; the halving converter of an odd width also reads pixel srcW, the three
      * bytes behind each row as they lie in the caller's picture (a second copy: they may belong to the next row).  A 32-bit source: four bytes a
      * pixel, pointer and stride on 4-byte multiples (the reference reads dwords) */
-    const bool rgb = packed_rgb(h);
-    const int bpx = src_bpx(h);
+    /* a packed 4:2:2 source: one plane of 2 * srcW bytes a row; an odd width's last chroma sample takes the two bytes behind each row in the same way */
+    const bool rgb = packed_rgb(h) || yuy2_src(h);
+    const int bpx = yuy2_src(h) ? 2 : src_bpx(h);
     if (rgb32_src(h) && (!src[0] || ((reinterpret_cast<uintptr_t>(src[0]) | (uintptr_t)src_stride[0]) & 3))) return -1;
     const int nsrc = rgb ? 1 : (h.src_layout ? 2 : 3), tail = rgb && h.src_hsub && (h.srcW & 1) ? bpx : 0;
     const int w[3] = { rgb ? bpx * h.srcW : h.srcW * B, rgb ? 0 : (h.src_layout ? 2 * h.chrSrcW : h.chrSrcW * B), h.src_layout ? 0 : h.chrSrcW * B },
@@ -777,7 +825,9 @@ extern "C" int mi355_sws_scale_planar(mi355_sws_ctx *c, const uint8_t *const src
         return r ? r : h.dstH;
     }
     /* the splitter writes (and so hands back) the rounded-down extents only */
-    const int cwb = h.special ? h.srcW >> 1 : h.chrDstW, chr = h.special ? h.srcH >> 1 : h.chrDstH;
+    /* ... and the packed-4:2:2 splitter its own: the width rounded up */
+    const bool yuy2 = h.special && yuy2_src(h);
+    const int cwb = yuy2 ? yuy2_chr_bytes(h) : (h.special ? h.srcW >> 1 : h.chrDstW), chr = yuy2 ? yuy2_chr_rows(h) : (h.special ? h.srcH >> 1 : h.chrDstH);
     if (h.dst_bits > 8) {
         /* 16-bit samples: rows of 2 * width bytes, even strides (scale_staged returns -1 for a stride below a row) */
         for (int p = 0; p < 3; p++) if (dst_stride[p] & 1) return -1;

@@ -326,6 +326,7 @@ constexpr int STAGE_BYTES16 = (int)sizeof(uint32_t) * SG * SRC_DW16;
  * 32-bit destination (the ALPHA form of k_sws_generic).  The pixels are converted to 8-bit samples before they are staged: the 8-bit staging lines */
 struct SwsPx32 { uint32_t v; };
 struct SwsPx32A { uint32_t v; };
+struct SwsPxYuy2 { uint8_t v; };          /* a packed 4:2:2 source (the picked bytes are staged in the 8-bit instances' staging lines) */
 template <typename ST> __host__ __device__ constexpr int stage_bytes() { return sizeof(ST) == 2 ? STAGE_BYTES16 : STAGE_BYTES; }
 /* dwords per staged line of `cols` columns of `bytes`-byte samples: a multiple of four (16-byte LDS stores) */
 __host__ __device__ constexpr int stage_pitch(int cols, int bytes) { return bytes == 1 ? (cols == TW ? SRC_DW : SRC_DW_HALF) : (cols == TW ? SRC_DW16 : SRC_DW16_HALF); }
@@ -932,6 +933,11 @@ __device__ __forceinline__ void rgb_sample(const uint8_t *px, bool half, const R
  * c0 c1 c2; bytes 0, 1 as the two 16-bit lanes of the dot product (sws_pair: alpha is not among them), byte 2 apart.  ash and which constant meets
  * c0 (bgr: bgra / abgr) are uniform values of the context, one form serves the four orders. */
 __host__ __device__ constexpr bool sws_rgb32_src(int layout) { return layout >= MI355_SWS_SRC_RGBA && layout <= MI355_SWS_SRC_ABGR; }
+/* a packed 4:2:2 source (yuyv422 / uyvy422 / yvyu422): where the luma, U and V bytes of a group of four lie */
+__host__ __device__ constexpr bool sws_yuy2_src(int layout) { return layout >= MI355_SWS_SRC_YUYV422 && layout <= MI355_SWS_SRC_YVYU422; }
+__host__ __device__ constexpr int sws_yuy2_luma(int layout) { return layout == MI355_SWS_SRC_UYVY422 ? 1 : 0; }
+__host__ __device__ constexpr int sws_yuy2_u(int layout) { return layout == MI355_SWS_SRC_UYVY422 ? 0 : (layout == MI355_SWS_SRC_YVYU422 ? 3 : 1); }
+__host__ __device__ constexpr int sws_yuy2_v(int layout) { return layout == MI355_SWS_SRC_UYVY422 ? 2 : (layout == MI355_SWS_SRC_YVYU422 ? 1 : 3); }
 __host__ __device__ constexpr bool sws_src_bgr(int layout) { return layout == MI355_SWS_SRC_BGR24 || layout == MI355_SWS_SRC_BGRA || layout == MI355_SWS_SRC_ABGR; }
 __host__ __device__ constexpr uint32_t sws_src_ash(int layout) { return layout == MI355_SWS_SRC_ARGB || layout == MI355_SWS_SRC_ABGR ? 8u : 0u; }
 /* N pixels at byte `boff` (a multiple of 16) of a line of which `limit` bytes may be read: 16-byte loads on a plane of 16-byte multiples, dwords on
@@ -996,16 +1002,55 @@ __device__ __forceinline__ void rgb32_sample(const uint8_t *px, bool half, int f
     a = (c0 * (int16_t)(k.a01 & 0xFFFF) + c1 * (int16_t)(k.a01 >> 16) + c2 * k.a2 + k.rnd) >> k.sh;
     b = (c0 * (int16_t)(k.b01 & 0xFFFF) + c1 * (int16_t)(k.b01 >> 16) + c2 * k.b2 + k.rnd) >> k.sh;
 }
-/* the unit and the sample of a pixel of BPX bytes: 3 — the rgb24 forms above, 4 — the 32-bit ones */
+/* ---- packed 4:2:2 sources (yuyv422 / uyvy422 / yvyu422): the input converters are byte picks (yuy2ToY_c, yuy2ToUV_c, yvy2ToUV_c, uyvyToY_c, uyvyToUV_c,
+ * input.c:369-473) — nothing is weighted, rounded or clipped.  Samples s .. s + 3 of a line (s a multiple of four) as one dword per plane.
+ * NP 1: luma, byte sws_yuy2_luma of each pair — 8 source bytes (one 8-byte load inside a 16-byte piece of a plane of 16-byte multiples, dwords on a
+ * plane of 4-byte multiples, else byte by byte).  NP 2: U into oa, V into ob, bytes sws_yuy2_u / _v of each group of four — 16 source bytes (one 16-byte
+ * load, dwords, or bytes).  Bytes at and past the limit read as zero, as rgb_load's. */
+template <int NP>
+__device__ __forceinline__ void yuy2_unit(const uint8_t *line, int s, bool al4, bool al16, int limit, int layout, uint32_t &oa, uint32_t &ob)
+{
+    const bool uy = sws_yuy2_luma(layout) != 0;
+    if constexpr (NP == 1) {
+        uint32_t w[2];
+        const int boff = 2 * s;
+        if (al16 && boff + 8 <= limit) {
+            const sws_u32x2 v = *reinterpret_cast<const sws_u32x2 *>(line + boff);
+            w[0] = v[0]; w[1] = v[1];
+        } else rgb_load<2>(line, boff, limit, al4, w);
+        oa = uy ? sws_odd4(w[0], w[1]) : sws_even4(w[0], w[1]);
+        ob = 0;
+    } else {
+        uint32_t w[4];
+        rgb32_load<4>(line, 4 * s, limit, al4, al16, w);
+        /* the chroma bytes of two groups as they lie (U V U V; V U V U in yvyu422), then every other one */
+        const uint32_t c01 = uy ? sws_even4(w[0], w[1]) : sws_odd4(w[0], w[1]), c23 = uy ? sws_even4(w[2], w[3]) : sws_odd4(w[2], w[3]);
+        const uint32_t e = sws_even4(c01, c23), o = sws_odd4(c01, c23);
+        const bool vu = layout == MI355_SWS_SRC_YVYU422;
+        oa = vu ? o : e; ob = vu ? e : o;
+    }
+}
+/* one sample from its bytes (the direct form): px the sample's pair (luma) or group of four (chroma) */
+__device__ __forceinline__ void yuy2_sample(const uint8_t *px, bool chroma, int layout, int &a, int &b)
+{
+    a = chroma ? px[sws_yuy2_u(layout)] : px[sws_yuy2_luma(layout)];
+    b = chroma ? px[sws_yuy2_v(layout)] : 0;
+}
+/* the unit and the sample of a pixel of BPX bytes: 3 — the rgb24 forms above, 4 — the 32-bit ones, 2 — packed 4:2:2 (ash carries the layout; the
+ * chroma planes are the halving form: a sample every four bytes) */
 template <int NP, int BPX>
 __device__ __forceinline__ void px_unit(const uint8_t *line, int s, bool half, bool al4, bool al16, int limit, uint32_t ash, const RgbK &k, uint32_t &oa, uint32_t &ob)
 {
+    if constexpr (BPX == 2) yuy2_unit<NP>(line, s, al4, al16, limit, (int)ash, oa, ob);
+    else
     if constexpr (BPX == 4) rgb32_unit<NP>(line, s, half, al4, al16, limit, ash, k, oa, ob);
     else rgb_unit<NP>(line, s, half, al4, limit, k, oa, ob);
 }
 template <int BPX>
 __device__ __forceinline__ void px_sample(const uint8_t *px, bool half, uint32_t ash, const RgbK &k, int &a, int &b)
 {
+    if constexpr (BPX == 2) yuy2_sample(px, half, (int)ash, a, b);
+    else
     if constexpr (BPX == 4) rgb32_sample(px, half, (int)(ash >> 3), k, a, b);
     else rgb_sample(px, half, k, a, b);
 }
@@ -1038,7 +1083,7 @@ __device__ __forceinline__ void hscale_tile_rgb(int16_t (*out_a)[OP], int16_t (*
     static_assert(StageGeom<COLS>::LINES % NP == 0 && LR >= NT / COLS, "every thread's first line is staged");
     const RgbK K = rgb_consts(NP > 1 && !ALPHA, half, bgr);
     const bool al4 = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 3) == 0;
-    const bool al16 = BPX == 4 && ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 15) == 0;
+    const bool al16 = BPX != 3 && ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 15) == 0;
     const int limit = BPX * (half ? (srcW + 1) & ~1 : srcW);                             /* bytes of a line the reference reads */
     if (identity) {
         /* converted sample << 7.  Eight columns per thread: two units, one 16-byte LDS write per plane */
@@ -1486,6 +1531,15 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
     /* horizontal pass: luma (the phantom partner of the last sample of an odd-width picture reads the
      * zero-initialised tail of the reference's line buffer, utils.c:1241-1262), then the chroma planes */
     uint32_t *s_stage = reinterpret_cast<uint32_t *>(s_io);
+    if constexpr (std::is_same<ST, SwsPxYuy2>::value) {
+        /* a packed 4:2:2 source: luma from the pairs, both chroma tiles from ONE pass over the groups of four of the same plane */
+        static_assert(RGB && !NV, "packed 4:2:2 sources have one plane");
+        const uint32_t lay = (uint32_t)c.src_layout;
+        hscale_tile_rgb<TW, TW, 1, 2>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.srcW, false, false, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi,
+                                      s_stage, tid, true, c.hstage != 0, c.hident_l != 0, lay);
+        hscale_tile_rgb<TW / 2, TW / 2, 2, 2>(s_cu, s_cv, fr.src[0], fr.src_stride[0], c.srcW, c.chrSrcW, true, false, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi,
+                                              s_stage, tid, false, c.hstage != 0, c.hident_c != 0, lay);
+    } else
     if constexpr (RGB && sizeof(ST) == 4) {
         /* a 32-bit source: the order's two uniform values from the record */
         static_assert(!NV, "packed RGB sources have one plane");
@@ -1887,6 +1941,11 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
     const int ls = c.vls, cs = c.vcs;
     /* source lines the tile needs (swscale.c:459-468 for the first tap, :571-616 for the clamping) */
     const int llo = clampi(imax(1 - ls, c.vLumP[y0]), 0, c.srcH - 1), lhi = clampi(imax(1 - ls, c.vLumP[y1]) + ls - 1, 0, c.srcH - 1);
+    if constexpr (std::is_same<ST, SwsPxYuy2>::value) {
+        static_assert(RGB && !NV, "packed 4:2:2 sources have one plane");
+        hscale_tile_rgb<TW, TW, 1, 2>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.srcW, false, false, c.hLumP, c.hLumC, c.hls, x0, c.dstW,
+                                      llo, lhi, s_stage, tid, false, c.hstage != 0, c.hident_l != 0, (uint32_t)c.src_layout);
+    } else
     if constexpr (RGB && sizeof(ST) == 4) {
         static_assert(!NV, "packed RGB sources have one plane");
         hscale_tile_rgb<TW, TW, 1, 4>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.srcW, false, sws_src_bgr(c.src_layout), c.hLumP, c.hLumC, c.hls, x0, c.dstW,
@@ -1903,6 +1962,11 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
         clo = clampi(imax(1 - cs, c.vChrP[cy0]), 0, c.chrSrcH - 1);
         const int chi = clampi(imax(1 - cs, c.vChrP[cy1]) + cs - 1, 0, c.chrSrcH - 1);
         nchr = chi - clo + 1;
+        if constexpr (std::is_same<ST, SwsPxYuy2>::value) {
+            int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
+            hscale_tile_rgb<CW, 2 * CW, 2, 2>(s_u, s_v, fr.src[0], fr.src_stride[0], c.srcW, c.chrSrcW, true, false, c.hChrP, c.hChrC, c.hcs,
+                                              x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, (uint32_t)c.src_layout);
+        } else
         if constexpr (RGB && sizeof(ST) == 4) {
             int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
             hscale_tile_rgb<CW, 2 * CW, 2, 4>(s_u, s_v, fr.src[0], fr.src_stride[0], c.srcW, c.chrSrcW, c.src_hsub != 0, sws_src_bgr(c.src_layout), c.hChrP, c.hChrC, c.hcs,
@@ -2453,5 +2517,16 @@ void mi355_sws_launch_planar_rgb32(int i, int kind, int form, dim3 grid, hipStre
 /* ... and of the line kernel k_sws_line_packed_a (one workgroup): k_sws_line_packed of a 32-bit order with the ls alpha lines `a` at the luma lines' pitch */
 void mi355_sws_launch_line_packed_a(int dst_format, hipStream_t s, const mi355_sws_luts *luts, int mode, const int16_t *lumF, const int16_t *l, int ls, const int16_t *chrF,
                                     const int16_t *u, const int16_t *v, int cs, const int16_t *a, int pitch, uint8_t *dest, int dstW, int yalpha, int uvalpha);
+
+/* sws_yuy2.hip: the launch of k_sws_yuy2_split, the four unscaled converters of a packed 4:2:2 source (yuyv422 / uyvy422 -> yuv420p / yuv422p) —
+ * luma_off: the byte of a pair that is luma (0 yuyv422, 1 uyvy422), c420: chroma rows averaged in pairs; the grid is the kernel's own.  Compiled in a
+ * file of its own. */
+void mi355_sws_launch_yuy2_split(int luma_off, int c420, int srcW, int srcH, int nframes, hipStream_t s, const mi355_sws_planar_frame *frames);
+/* ... and of the tile instances of these sources — instance i (0 / 1 / 2: A / B / C) of k_sws_generic to dst_format 0 / MI355_SWS_DST_BGR24 ... _ABGR, and of
+ * k_sws_planar: kind 0 plain, 1 RANGE, 2 DEEP; form 0 three planes at CW = TW / 2, 1 at CW = TW, 2 a semi-planar destination — and of k_sws_ident1_yuy2
+ * (k_sws_ident1's grid) */
+void mi355_sws_launch_generic_yuy2(int i, int dst_format, dim3 grid, hipStream_t s, const void *d, const mi355_sws_frame *frames);
+void mi355_sws_launch_planar_yuy2(int i, int kind, int form, dim3 grid, hipStream_t s, const void *d, const mi355_sws_planar_frame *frames);
+void mi355_sws_launch_ident1_yuy2(int dst_format, dim3 grid, hipStream_t s, const void *d, const mi355_sws_frame *frames);
 
 #endif

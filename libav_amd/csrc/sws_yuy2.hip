@@ -1,0 +1,347 @@
+/*
+ * sws_yuy2.hip — packed 4:2:2 SOURCES (yuyv422 / uyvy422 / yvyu422: MI355_SWS_SRC_YUYV422 ... _YVYU422): the instances of the tile kernels (sws_dev.h)
+ * whose horizontal pass picks its samples from the packed bytes — k_sws_generic A / B / C to rgb24, bgr24 and the four 32-bit orders, k_sws_planar
+ * A / B / C at both chroma widths, plain, SEMI, RANGE and DEEP — with their launches, k_sws_ident1_yuy2 (equal size to a packed RGB destination), the
+ * four unscaled special converters the reference has for these sources in one kernel (k_sws_yuy2_split: yuyvToYuv420Wrapper, uyvyToYuv420Wrapper, yuyvToYuv422Wrapper, uyvyToYuv422Wrapper,
+ * swscale_unscaled.c:227-287 over yuyvtoyuv420_c ... uyvytoyuv422_c, rgb2rgb_template.c:854-928), and the two Tier-1 line entries
+ * mi355_sws_yuy2ToY / _yuy2ToUV (yuy2ToY_c, yuy2ToUV_c, yvy2ToUV_c, uyvyToY_c, uyvyToUV_c, input.c:369-473) with their line kernels.  The context,
+ * the plan and the picture entry points are sws.hip's (mi355_sws_create_src_layout with layout 16 .. 18).  A file of its own so that it compiles
+ * beside sws.hip, not behind it.
+ */
+#include "mi355_rt.h"
+#define MI355_SWS_TILE_KERNELS_ONLY
+#include "sws_dev.h"
+#include "../../include/mi355dsp.h"
+
+using namespace mi355;
+
+namespace {
+/* ---- the unscaled splitter: yuyv422 / uyvy422 -> yuv420p / yuv422p at equal size ------------------------------------------------------------
+ * Every byte is a pick: luma is byte luma_off of each pair (srcW bytes on each of srcH rows), U and V bytes 1 - luma_off and 3 - luma_off of each
+ * group of four — (srcW + 1) >> 1 of each on every row (4:2:2), or on srcH / 2 rows ROUNDED DOWN the truncating mean (a + b) >> 1 of source lines
+ * 2r and 2r + 1 (4:2:0: the last chroma row of an odd height is never written, a one-line picture writes none).  The width rounds UP: with an odd
+ * srcW the last chroma sample takes the second half of the last group, the two bytes behind the line's width, as the reference does.
+ * Tiled like k_sws_nv12_split: YUY2_COLS x YUY2_ROWS luma samples a workgroup (blockIdx.z: the picture); a thread takes 32 luma samples — 64 source
+ * bytes — of ONE pair of rows, so the 4:2:0 mean is taken between registers and every plane leaves in 16-byte pieces (luma two, each chroma plane
+ * one), and requests every load before its first store.
+ * The source: four 16-byte pieces where the plane's pointer and stride are multiples of 16 and the pieces lie inside the stride (such a plane is
+ * readable over its whole stride); else the dwords that lie whole inside the bytes the reference reads (4 * ((srcW + 1) >> 1) of a line) — one load
+ * each on a plane of 4-byte multiples, four byte loads each on any other.  The destination: 32 luma bytes / 16 bytes of each chroma plane in 16-byte
+ * pieces where the plane's pointer and stride are multiples of 16 and the pieces lie inside the width; else byte by byte up to the width. */
+constexpr int YUY2_COLS = 2048, YUY2_ROWS = 8, YUY2_PER = 32;     /* luma samples a thread and row */
+static_assert(YUY2_COLS == 64 * YUY2_PER && 2 * (NT / 64) == YUY2_ROWS, "a wave covers a pair of tile rows, the waves cover the tile");
+
+/* the truncating mean of the four bytes of a and b */
+__device__ __forceinline__ uint32_t yuy2_avg4(uint32_t a, uint32_t b) { return (a & b) + (((a ^ b) & 0xFEFEFEFEu) >> 1); }
+
+/* the bytes of one row's 64 source bytes: 32 luma bytes in l[8], 16 U bytes in u[4], 16 V bytes in v[4] */
+__device__ __forceinline__ void yuy2_pick(const uint32_t *w, int luma_off, uint32_t *l, uint32_t *u, uint32_t *v)
+{
+    uint32_t c[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint32_t e = sws_even4(w[2 * j], w[2 * j + 1]), o = sws_odd4(w[2 * j], w[2 * j + 1]);
+        l[j] = luma_off ? o : e;
+        c[j] = luma_off ? e : o;                                   /* U V U V */
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) { u[j] = sws_even4(c[2 * j], c[2 * j + 1]); v[j] = sws_odd4(c[2 * j], c[2 * j + 1]); }
+}
+/* n <= 4 * N bytes of w to d, one at a time */
+template <int N> __device__ __forceinline__ void yuy2_store_bytes(uint8_t *d, const uint32_t *w, int n)
+{
+#pragma unroll
+    for (int i = 0; i < 4 * N; i++) if (i < n) d[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+}
+/* 16 * N bytes of w to d in 16-byte pieces */
+template <int N> __device__ __forceinline__ void yuy2_store_wide(uint8_t *d, const uint32_t *w)
+{
+#pragma unroll
+    for (int i = 0; i < N; i++) reinterpret_cast<sws_u32x4 *>(d)[i] = sws_u32x4{ w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3] };
+}
+
+__global__ void __launch_bounds__(NT) k_sws_yuy2_split(int luma_off, int c420, int srcW, int srcH, const mi355_sws_planar_frame *frames)
+{
+    mi355_sws_planar_frame fr = frames[blockIdx.z];
+    fr.src[0] = mi355_global(fr.src[0]);
+    for (int k = 0; k < 3; k++) fr.dst[k] = mi355_global(fr.dst[k]);
+    const int tid = threadIdx.x, lane = tid & 63, rg = tid >> 6;
+    const int x = blockIdx.x * YUY2_COLS + YUY2_PER * lane, r = blockIdx.y * (YUY2_ROWS / 2) + rg;      /* r: the thread's pair of rows */
+    if (x >= srcW) return;                                         /* (no barrier in this kernel) */
+    const int cw = (srcW + 1) >> 1, ch = c420 ? srcH >> 1 : srcH, cx = x >> 1;      /* chroma: the width rounds up, the 4:2:0 rows down */
+    const int limit = 4 * cw;                                      /* bytes of a line the reference reads */
+    const uintptr_t sal = reinterpret_cast<uintptr_t>(fr.src[0]) | (uintptr_t)fr.src_stride[0];
+    const bool swide = (sal & 15) == 0 && 2 * x + 2 * YUY2_PER <= fr.src_stride[0], sal4 = (sal & 3) == 0;
+    const int nd = imin(16, (limit - 2 * x) >> 2);                 /* dwords of the thread's 64 bytes inside the line */
+    const bool lwide = x + YUY2_PER <= srcW && ((reinterpret_cast<uintptr_t>(fr.dst[0]) | (uintptr_t)fr.dst_stride[0]) & 15) == 0;
+    const bool cwide = cx + YUY2_PER / 2 <= cw && ((reinterpret_cast<uintptr_t>(fr.dst[1]) | (uintptr_t)fr.dst_stride[1] |
+                                                     reinterpret_cast<uintptr_t>(fr.dst[2]) | (uintptr_t)fr.dst_stride[2]) & 15) == 0;
+    uint32_t w[2][16] = {};
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int y = 2 * r + j;
+        if (y >= srcH) continue;                                   /* (uniform over the wave) */
+        const uint8_t *sp = fr.src[0] + (size_t)y * fr.src_stride[0] + 2 * (size_t)x;
+        if (swide) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const sws_u32x4 a = reinterpret_cast<const sws_u32x4 *>(sp)[q];
+#pragma unroll
+                for (int d = 0; d < 4; d++) w[j][4 * q + d] = a[d];
+            }
+        } else if (sal4) {
+#pragma unroll
+            for (int d = 0; d < 16; d++) if (d < nd) w[j][d] = reinterpret_cast<const uint32_t *>(sp)[d];
+        } else {
+#pragma unroll
+            for (int d = 0; d < 16; d++)
+                if (d < nd) w[j][d] = (uint32_t)sp[4 * d] | ((uint32_t)sp[4 * d + 1] << 8) | ((uint32_t)sp[4 * d + 2] << 16) | ((uint32_t)sp[4 * d + 3] << 24);
+        }
+    }
+    uint32_t l[2][8], u[2][4], v[2][4];
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        yuy2_pick(w[j], luma_off, l[j], u[j], v[j]);
+        const int y = 2 * r + j;
+        if (y >= srcH) continue;
+        uint8_t *d = fr.dst[0] + (size_t)y * fr.dst_stride[0] + x;
+        if (lwide) yuy2_store_wide<2>(d, l[j]);
+        else yuy2_store_bytes<8>(d, l[j], imin(YUY2_PER, srcW - x));
+    }
+    if (c420) {
+        /* chroma row r from source lines 2r and 2r + 1, both inside the picture */
+        if (r >= ch) return;
+        uint32_t mu[4], mv[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) { mu[k] = yuy2_avg4(u[0][k], u[1][k]); mv[k] = yuy2_avg4(v[0][k], v[1][k]); }
+        uint8_t *du = fr.dst[1] + (size_t)r * fr.dst_stride[1] + cx, *dv = fr.dst[2] + (size_t)r * fr.dst_stride[2] + cx;
+        if (cwide) {
+            yuy2_store_wide<1>(du, mu);
+            yuy2_store_wide<1>(dv, mv);
+        } else {
+            yuy2_store_bytes<4>(du, mu, imin(YUY2_PER / 2, cw - cx));
+            yuy2_store_bytes<4>(dv, mv, imin(YUY2_PER / 2, cw - cx));
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const int y = 2 * r + j;
+            if (y >= ch) continue;
+            uint8_t *du = fr.dst[1] + (size_t)y * fr.dst_stride[1] + cx, *dv = fr.dst[2] + (size_t)y * fr.dst_stride[2] + cx;
+            if (cwide) {
+                yuy2_store_wide<1>(du, u[j]);
+                yuy2_store_wide<1>(dv, v[j]);
+            } else {
+                yuy2_store_bytes<4>(du, u[j], imin(YUY2_PER / 2, cw - cx));
+                yuy2_store_bytes<4>(dv, v[j], imin(YUY2_PER / 2, cw - cx));
+            }
+        }
+    }
+}
+
+/* ---- Tier-1 line kernels: yuy2ToY_c / uyvyToY_c and yuy2ToUV_c / yvy2ToUV_c / uyvyToUV_c (input.c:369-473) of one line ---------------------- */
+__global__ void __launch_bounds__(NT) k_sws_line_yuy2_y(uint8_t *dst, const uint8_t *src, int width, int off)
+{
+    for (int i = threadIdx.x; i < width; i += NT) dst[i] = src[2 * (size_t)i + off];
+}
+__global__ void __launch_bounds__(NT) k_sws_line_yuy2_uv(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int width, int uoff, int voff)
+{
+    for (int i = threadIdx.x; i < width; i += NT) { dstU[i] = src[4 * (size_t)i + uoff]; dstV[i] = src[4 * (size_t)i + voff]; }
+}
+}  // namespace
+
+namespace {
+/* ---- the scaler from these sources: the tile instances ----------------------------------------------------------------------------------------
+ * k_sws_generic / k_sws_planar with the pick converter in the staging round of hscale_tile_rgb (a 2-byte "pixel" for luma, a 4-byte one for chroma):
+ * the staged line holds the picked bytes, so every instance has the LDS, the waves per SIMD and the workgroups per CU of its 8-bit yuv422p twin. */
+typedef SwsPxYuy2 PxY2;
+static_assert(stage_bytes<PxY2>() == STAGE_BYTES, "the twins' staging lines");
+
+template <int I, int DST> static void launch_generic_y2(dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
+{
+    constexpr SwsShape S = GENERIC_SHAPES[I];
+    hipLaunchKernelGGL((k_sws_generic<S.lcap, S.ccap, sws_waves(sws_lds_bytes(S.lcap, S.ccap, STAGE_BYTES)), PxY2, false, true, DST>), grid, dim3(NT), 0, s, d, frames);
+}
+template <int DST> static void launch_generic_y2(int i, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
+{
+    if (i == 0) launch_generic_y2<0, DST>(grid, s, d, frames);
+    else if (i == 1) launch_generic_y2<1, DST>(grid, s, d, frames);
+    else launch_generic_y2<2, DST>(grid, s, d, frames);
+}
+/* form 0: three planes at CW = TW / 2, 1: at CW = TW, 2: a semi-planar destination; kind 0: plain, 1: RANGE, 2: DEEP (three planes only) */
+template <int I, bool RANGE, bool DEEP> static void launch_planar_y2(int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+{
+    constexpr SwsShape S = PLANAR_SHAPES[I];
+    if (form == 0) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, PxY2, false, false, true, RANGE, DEEP>), grid, dim3(NT), 0, s, d, frames);
+    else if (form == 1) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW, PxY2, false, false, true, RANGE, DEEP>), grid, dim3(NT), 0, s, d, frames);
+    else if constexpr (!DEEP) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, PxY2, true, false, true, RANGE, false>), grid, dim3(NT), 0, s, d, frames);
+}
+template <int I> static void launch_planar_y2(int kind, int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+{
+    if (kind == 0) launch_planar_y2<I, false, false>(form, grid, s, d, frames);
+    else if (kind == 1) launch_planar_y2<I, true, false>(form, grid, s, d, frames);
+    else launch_planar_y2<I, false, true>(form, grid, s, d, frames);
+}
+
+/* ---- equal size to a packed RGB destination: k_sws_ident1's _1 form straight from the packed bytes ---------------------------------------------
+ * The reference has no special converter from these sources to RGB: its scaler runs with identity horizontal filters and ONE vertical luma tap, and
+ * with chroma on every source line the chroma filter has one or two taps — yuv2rgb24_1_c and its kin (output.c:1043-1110): Y = the luma byte, U / V
+ * the first chroma line's byte, or the mean of two lines where the row's second coefficient is >= 2048.  k_sws_ident1's grid, tile and LUT copy; a
+ * thread's eight samples of a row are 16 source bytes that hold luma AND chroma — one 16-byte load on a plane of 16-byte multiples, four dwords on
+ * one of 4-byte multiples; a chroma tap line other than the luma line (uniform over the row's wave) is loaded the same way.  Ragged rows, and planes
+ * on neither multiple, go byte by byte.  A kernel of its own name: another template parameter of k_sws_ident1 would rename its existing instances.
+ * With chroma on every line no context of these sources reaches the X template (more than two chroma taps): sws.hip sends such a one to the tile. */
+template <int DST>
+__global__ void __launch_bounds__(NT) k_sws_ident1_yuy2(const SwsDev *cp, const mi355_sws_frame *frames)
+{
+    __shared__ LutLds s_lut;
+    constexpr int NC = 2;
+    constexpr int BPP = dst_bpp<DST>();
+    const uint32_t sel = DST == DST_RGB32 ? cp->dst_sel : 0u;
+    const int tid = threadIdx.x;
+    const int dstW = cp->dstW, dstH = cp->dstH, cs = cp->vcs, srcH = cp->srcH, chrSrcH = cp->chrSrcH, layout = cp->src_layout;
+    const int32_t *vLumP = mi355_global(cp->vLumP), *vChrP = mi355_global(cp->vChrP);
+    const int16_t *vChrC = mi355_global(cp->vChrC);
+    mi355_sws_frame fr = frames[blockIdx.z];
+    fr.src[0] = mi355_global(fr.src[0]);
+    fr.dst = mi355_global(fr.dst);
+    const int x = blockIdx.x * C24_COLS + (tid & 63) * 8;   /* first of the thread's eight samples */
+    const int npairs = dstW >> 1;
+    const bool mine = (x >> 1) < npairs;
+    const uintptr_t sal = reinterpret_cast<uintptr_t>(fr.src[0]) | (uintptr_t)fr.src_stride[0];
+    const bool al16 = (sal & 15) == 0;
+    constexpr uintptr_t DMASK = DST == DST_RGB32 ? 15 : 7;
+    /* the wide form: four whole pairs (x + 8 <= dstW <= srcW: the 16 bytes lie inside the line's 2 * srcW) */
+    const bool wide = mine && (x >> 1) + 4 <= npairs && (sal & 3) == 0 && ((reinterpret_cast<uintptr_t>(fr.dst) | (uintptr_t)fr.dst_stride) & DMASK) == 0;
+    const bool uy = sws_yuy2_luma(layout) != 0, vu = layout == MI355_SWS_SRC_YVYU422;
+    constexpr int NR = IDENT_ROWS / (NT / 64);
+    int li[NR], ci[NR][NC], cf1[NR];
+    uint32_t wl[NR][4], wc[NR][NC][4];
+    auto load16 = [&](const uint8_t *p, uint32_t *w) {
+        if (al16) {
+            const sws_u32x4 v = *reinterpret_cast<const sws_u32x4 *>(p);
+            w[0] = v[0]; w[1] = v[1]; w[2] = v[2]; w[3] = v[3];
+        } else {
+#pragma unroll
+            for (int d = 0; d < 4; d++) w[d] = reinterpret_cast<const uint32_t *>(p)[d];
+        }
+    };
+#pragma unroll
+    for (int q = 0; q < NR; q++) {
+        /* rows past the picture repeat its last row and are not written; a tap past the filter reads tap 0 */
+        const int gy = imin(blockIdx.y * IDENT_ROWS + (tid >> 6) + q * (NT / 64), dstH - 1);
+        li[q] = clampi(vLumP[gy], 0, srcH - 1);
+        const int cfirst = imax(1 - cs, vChrP[gy]);
+        cf1[q] = cs > 1 ? vChrC[(size_t)gy * cs + 1] : 0;
+#pragma unroll
+        for (int j = 0; j < NC; j++) ci[q][j] = clampi(cfirst + (j < cs ? j : 0), 0, chrSrcH - 1);
+#pragma unroll
+        for (int d = 0; d < 4; d++) wl[q][d] = 0;
+        if (wide) load16(fr.src[0] + (size_t)li[q] * fr.src_stride[0] + 2 * (size_t)x, wl[q]);
+#pragma unroll
+        for (int j = 0; j < NC; j++) {
+#pragma unroll
+            for (int d = 0; d < 4; d++) wc[q][j][d] = wl[q][d];
+            if (wide && ci[q][j] != li[q]) load16(fr.src[0] + (size_t)ci[q][j] * fr.src_stride[0] + 2 * (size_t)x, wc[q][j]);
+        }
+    }
+    MI355_ISSUE_FENCE();
+    lut_load(s_lut, &cp->luts, tid);
+    __syncthreads();
+    if (!mine) return;
+#pragma unroll
+    for (int q = 0; q < NR; q++) {
+        const int gy = blockIdx.y * IDENT_ROWS + (tid >> 6) + q * (NT / 64);
+        if (gy >= dstH) break;
+        uint8_t *d = fr.dst + (size_t)gy * fr.dst_stride + (size_t)x * BPP;
+        const bool mean = cs > 1 && cf1[q] >= 2048;
+        if (wide) {
+            int Y[8], r[4], g[4], b[4];
+            const uint32_t ya[2] = { uy ? sws_odd4(wl[q][0], wl[q][1]) : sws_even4(wl[q][0], wl[q][1]), uy ? sws_odd4(wl[q][2], wl[q][3]) : sws_even4(wl[q][2], wl[q][3]) };
+            uint32_t u[NC], v[NC];
+#pragma unroll
+            for (int j = 0; j < NC; j++) {
+                const uint32_t *w = wc[q][j];
+                const uint32_t c01 = uy ? sws_even4(w[0], w[1]) : sws_odd4(w[0], w[1]), c23 = uy ? sws_even4(w[2], w[3]) : sws_odd4(w[2], w[3]);
+                const uint32_t e = sws_even4(c01, c23), o = sws_odd4(c01, c23);
+                u[j] = vu ? o : e; v[j] = vu ? e : o;
+            }
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                const int u0 = (u[0] >> (8 * p)) & 0xFF, u1 = (u[1] >> (8 * p)) & 0xFF, v0 = (v[0] >> (8 * p)) & 0xFF, v1 = (v[1] >> (8 * p)) & 0xFF;
+                const uint32_t w = ya[p >> 1] >> (16 * (p & 1));
+                Y[2 * p] = (int)(w & 0xFF); Y[2 * p + 1] = (int)((w >> 8) & 0xFF);
+                lut_rows_d<DST>(s_lut, mean ? (u0 + u1) >> 1 : u0, mean ? (v0 + v1) >> 1 : v0, r[p], g[p], b[p]);
+            }
+            if constexpr (DST == DST_RGB32) rgb32_store8(s_lut, d, Y, r, g, b, sel);
+            else rgb24_store8(s_lut, d, Y, r, g, b);
+        } else {
+            const int lo = sws_yuy2_luma(layout), uo = sws_yuy2_u(layout), vo = sws_yuy2_v(layout);
+            const uint8_t *py = fr.src[0] + (size_t)li[q] * fr.src_stride[0] + 2 * (size_t)x;
+            for (int p = 0; p < 4 && (x >> 1) + p < npairs; p++) {
+                const uint8_t *p0 = fr.src[0] + (size_t)ci[q][0] * fr.src_stride[0] + 2 * (size_t)x + 4 * p, *p1 = fr.src[0] + (size_t)ci[q][1] * fr.src_stride[0] + 2 * (size_t)x + 4 * p;
+                const int U = mean ? (p0[uo] + p1[uo]) >> 1 : p0[uo], V = mean ? (p0[vo] + p1[vo]) >> 1 : p0[vo];
+                write_pair_d<DST>(s_lut, d + 2 * BPP * p, py[4 * p + lo], py[4 * p + lo + 2], U, V, sel);
+            }
+        }
+    }
+}
+}  // namespace
+
+void mi355_sws_launch_generic_yuy2(int i, int dst_format, dim3 grid, hipStream_t s, const void *d, const mi355_sws_frame *frames)
+{
+    const SwsDev *dev = static_cast<const SwsDev *>(d);
+    if (dst_format == 0) launch_generic_y2<DST_RGB24>(i, grid, s, dev, frames);
+    else if (dst_format == MI355_SWS_DST_BGR24) launch_generic_y2<DST_BGR24>(i, grid, s, dev, frames);
+    else launch_generic_y2<DST_RGB32>(i, grid, s, dev, frames);
+}
+void mi355_sws_launch_planar_yuy2(int i, int kind, int form, dim3 grid, hipStream_t s, const void *d, const mi355_sws_planar_frame *frames)
+{
+    const SwsDev *dev = static_cast<const SwsDev *>(d);
+    if (i == 0) launch_planar_y2<0>(kind, form, grid, s, dev, frames);
+    else if (i == 1) launch_planar_y2<1>(kind, form, grid, s, dev, frames);
+    else launch_planar_y2<2>(kind, form, grid, s, dev, frames);
+}
+void mi355_sws_launch_ident1_yuy2(int dst_format, dim3 grid, hipStream_t s, const void *d, const mi355_sws_frame *frames)
+{
+    const SwsDev *dev = static_cast<const SwsDev *>(d);
+    if (dst_format == 0) hipLaunchKernelGGL(k_sws_ident1_yuy2<DST_RGB24>, grid, dim3(NT), 0, s, dev, frames);
+    else if (dst_format == MI355_SWS_DST_BGR24) hipLaunchKernelGGL(k_sws_ident1_yuy2<DST_BGR24>, grid, dim3(NT), 0, s, dev, frames);
+    else hipLaunchKernelGGL(k_sws_ident1_yuy2<DST_RGB32>, grid, dim3(NT), 0, s, dev, frames);
+}
+
+void mi355_sws_launch_yuy2_split(int luma_off, int c420, int srcW, int srcH, int nframes, hipStream_t s, const mi355_sws_planar_frame *frames)
+{
+    hipLaunchKernelGGL(k_sws_yuy2_split, dim3((srcW + YUY2_COLS - 1) / YUY2_COLS, (srcH + YUY2_ROWS - 1) / YUY2_ROWS, nframes), dim3(NT), 0, s,
+                       luma_off, c420, srcW, srcH, frames);
+}
+
+/* one line through a line kernel: nsrc source bytes in, nout planes of `width` bytes out */
+extern "C" void mi355_sws_yuy2ToY(uint8_t *dst, const uint8_t *src, int width, int layout)
+{
+    if (width <= 0 || !sws_yuy2_src(layout)) return;
+    Arena &a = arena();
+    const size_t nsrc = (size_t)2 * width;
+    a.reserve(nsrc + (size_t)width + 64);
+    const size_t o_src = a.take(nsrc), o_d = a.take((size_t)width);
+    std::memcpy(a.h<uint8_t>(o_src), src, nsrc);
+    a.upload();
+    hipLaunchKernelGGL(k_sws_line_yuy2_y, dim3(1), dim3(NT), 0, a.stream, a.d<uint8_t>(o_d), a.d<const uint8_t>(o_src), width, sws_yuy2_luma(layout));
+    a.download();
+    std::memcpy(dst, a.h<uint8_t>(o_d), (size_t)width);
+}
+extern "C" void mi355_sws_yuy2ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int width, int layout)
+{
+    if (width <= 0 || !sws_yuy2_src(layout)) return;
+    Arena &a = arena();
+    const size_t nsrc = (size_t)4 * width;
+    a.reserve(nsrc + (size_t)2 * width + 96);
+    const size_t o_src = a.take(nsrc), o_u = a.take((size_t)width), o_v = a.take((size_t)width);
+    std::memcpy(a.h<uint8_t>(o_src), src, nsrc);
+    a.upload();
+    hipLaunchKernelGGL(k_sws_line_yuy2_uv, dim3(1), dim3(NT), 0, a.stream, a.d<uint8_t>(o_u), a.d<uint8_t>(o_v), a.d<const uint8_t>(o_src), width,
+                       sws_yuy2_u(layout), sws_yuy2_v(layout));
+    a.download();
+    std::memcpy(dstU, a.h<uint8_t>(o_u), (size_t)width);
+    std::memcpy(dstV, a.h<uint8_t>(o_v), (size_t)width);
+}

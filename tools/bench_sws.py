@@ -61,9 +61,13 @@ def main():
                          "bgra with alpha beside the same context with alpha 0 (equal bytes); the twin a second time in another allocation (A/A), with "
                          "--other-lib also on that build (the parent commit's) together with its 2160p -> 1080p yuv420p -> bgra point; 32 and 512 pictures "
                          "per launch, 3 warm-up + --steps launches a round, alternating, median of 3 rounds")
+    ap.add_argument("--yuy2src", action="store_true",
+                    help="the unscaled splitter of the packed 4:2:2 sources beside k_sws_nv12_split at the same size on the same build: 1080p uyvy422 -> "
+                         "yuv420p (3.5 bytes a pixel against the twin's 3) and 1080p yuyv422 -> yuv422p (4 against 3); the twin a second time in another "
+                         "allocation (A/A); 32 and 512 pictures per launch, 3 warm-up + --steps launches a round, alternating, median of --rounds rounds")
     ap.add_argument("--other-lib", default=None,
                     help="--nv12 / --nvsrc / --rgbsrc / --range / --rgb32src: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
-    ap.add_argument("--rounds", type=int, default=5, help="--planar / --sources: alternating rounds (the median is reported)")
+    ap.add_argument("--rounds", type=int, default=5, help="--planar / --sources / --yuy2src: alternating rounds (the median is reported)")
     a = ap.parse_args()
     prov = providers.mi355()
     lib = prov.lib
@@ -87,6 +91,8 @@ def main():
         return packeddst_points(a, lib)
     if a.rgb32src:
         return rgb32src_points(a, lib)
+    if a.yuy2src:
+        return yuy2src_points(a, lib)
     orc = S.oracle_backend(providers.oracle())
     for name in a.configs.split(","):
         ctx = S.load_context(name)
@@ -865,6 +871,109 @@ def rgb32src_points(a, lib, points=None, frame_counts=(32, 512)):
     aa = max(r["aa_spread"] for r in rows)
     miss = ["%s@%d %+.1f%% (bound %+.1f%%)" % (r["workload"], r["frames_per_launch"], 100 * r["vs_twin"], 100 * (r["bound"] + aa)) for r in rows if r["vs_twin"] > r["bound"] + aa]
     print(json.dumps({"summary": "rgb32src", "aa_session": aa, "points": len(rows), "miss": miss}), flush=True)
+
+
+def yuy2src_points(a, lib, points=None, frame_counts=(32, 512), scaled=None):
+    """The unscaled splitter of the packed 4:2:2 sources (k_sws_yuy2_split) beside k_sws_nv12_split at the same size — the one kernel of the same
+    kind: a de-interleaving copy without banks or LDS.  It moves 3 bytes a pixel (nv12 -> yuv420p: 1.5 in, 1.5 out); uyvy422 -> yuv420p moves 3.5
+    (2 in, 1.5 out) and yuyv422 -> yuv422p 4 (2 in, 2 out): `bound` is that byte ratio — what the point may cost at the twin's achieved bandwidth.
+    The contexts come from the reference's libswscale at run time (oracle/_ref/libswsref.so: mi355_sws_describe_yuy2 / _fmt) — no full-size
+    context is committed.  `twin#2` is the twin a second time with its own buffers: the session's A/A spread.  One process, the batches of a point
+    alternating: 3 warm-up + --steps launches a round, median of --rounds rounds, at 32 and 512 pictures per launch.  Algorithmic bytes: the source
+    read once + the destination planes written once.  The last line sums the session up: `aa_session` — the largest A/A spread of its points — and
+    under `miss` every row whose time exceeds its twin's times the byte ratio plus that spread.
+    The scaler's points (2160p -> 1080p yuyv422 -> yuv420p, uyvy422 -> nv12, uyvy422 -> bgra, and 1080p yuyv422 -> bgra at equal size: k_sws_ident1_yuy2)
+    run beside their yuv422p twin — the context of the SAME descriptor as an 8-bit planar 4:2:2 source on the de-interleaved planes: equal bytes a pixel
+    (2 in both), so the bound is the twin's time."""
+    import statistics
+    import numpy as np
+    import sws_nvsrc as V
+    import sws_planar as P
+    import sws_yuy2src as Y
+    ref = Y.Ref(P.bind(Y.REF_LIB))
+    vref = V.Ref(ref.lib)
+    # (point, srcW, srcH, source, destination of tests/sws_yuy2src.py)
+    points = points or [("hd_split_uyvy_yuv420p", 1920, 1080, "uyvy", "420"), ("hd_split_yuyv_yuv422p", 1920, 1080, "yuyv", "422")]
+    # (point, srcW, srcH, dstW, dstH, source, destination): the scaler's points and the ident1 point
+    scaled = scaled if scaled is not None else [("uhd_to_hd_yuyv_yuv420p", 3840, 2160, 1920, 1080, "yuyv", "420"), ("uhd_to_hd_uyvy_nv12", 3840, 2160, 1920, 1080, "uyvy", "nv12"),
+              ("uhd_to_hd_uyvy_bgra", 3840, 2160, 1920, 1080, "uyvy", "bgra"), ("hd_same_yuyv_bgra", 1920, 1080, 1920, 1080, "yuyv", "bgra")]
+    rows = []
+    for frames in frame_counts:
+        for point, sw, sh, src, dst in points:
+            row = (sw, sh, sw, sh, src, dst, 1, 1, 1)                   # a row of tests/sws_yuy2src.py's form, not entered into its table
+            c = ref.open(row)
+            e = ref.describe_yuy2(c)
+            ref.free(c)
+            c = vref.open_formats(sw, sh, b"nv12", sw, sh, b"yuv420p", ref.flags(row))
+            t = vref.describe(c)
+            vref.free(c)
+            assert e is not None and e.ctx.desc.unscaled_special and t is not None and t.ctx.desc.unscaled_special, point
+            V.SHAPES["_bench"] = (sw, sh, sw, sh, "nv12", "420", 1, 1, 1)
+            ypics = [[np.ascontiguousarray(Y.picture(row, "noise", seed=s)[0])] for s in (1, 2)]
+            tpics = [[np.ascontiguousarray(pl) for pl in V.picture("_bench", seed=s)] for s in (1, 2)]
+            batches = {src + "422_split": (lib, PlaneBatch(lib, Y.create(lib, e), ypics, e.out_sizes(), frames)),
+                       "twin": (lib, PlaneBatch(lib, V.create(lib, t), tpics, t.out_sizes(), frames)),
+                       "twin#2": (lib, PlaneBatch(lib, V.create(lib, t), tpics, t.out_sizes(), frames))}
+            plan = Y.plan_of(lib, batches[src + "422_split"][1].handle)
+            times = {k: [] for k in batches}
+            for _ in range(a.rounds):
+                for k, (l, b) in batches.items():
+                    times[k].append(time_ms(l, b.run, a.steps))
+            base = statistics.median(times["twin"])
+            spread = abs(statistics.median(times["twin#2"]) / base - 1.0)
+            twin_bytes = batches["twin"][1].src_bytes + batches["twin"][1].dst_bytes
+            for k, (l, b) in batches.items():
+                ms = statistics.median(times[k])
+                us = ms * 1e3 / frames
+                nb = b.src_bytes + b.dst_bytes
+                out = {"workload": point + ":" + k, "frames_per_launch": frames, "ms_per_launch": ms, "us_per_picture": us, "frames_per_s": 1e6 / us,
+                       "algorithmic_bytes_per_frame": nb, "achieved_GBps": nb / us * 1e-3, "frac_of_8TBps": nb / us * 1e-3 / 8000.0,
+                       "vs_twin": ms / base - 1.0, "bound": nb / twin_bytes - 1.0, "aa_spread": spread, "ms_rounds": [round(x, 4) for x in times[k]]}
+                if k not in ("twin", "twin#2"):
+                    out["kernel"] = plan["kernel"]
+                rows.append(out)
+                print(json.dumps(out), flush=True)
+            for l, b in batches.values():
+                b.close()
+        for point, sw, sh, dw, dh, src, dst in scaled:
+            row = (sw, sh, dw, dh, src, dst, 1, 1, 1)
+            c = ref.open(row)
+            e = ref.describe_yuy2(c)
+            ref.free(c)
+            assert e is not None and not e.ctx.desc.unscaled_special, point
+            t = Y.twin_entry(e)
+            ypics = [[np.ascontiguousarray(Y.picture(row, "noise", seed=s)[0])] for s in (1, 2)]
+            tpics = [Y.deinterleave(row, pl) for pl in ypics]
+
+            def batch(x, pics):
+                if x.fmt == 0 or x.fmt >= 32:
+                    return SourceBatch(lib, None, x, pics, frames, create=Y.create, bpp=4 if x.fmt >= 33 else 3)
+                return PlaneBatch(lib, Y.create(lib, x), pics, x.out_sizes(), frames)
+            batches = {src + "422": (lib, batch(e, ypics)), "twin": (lib, batch(t, tpics)), "twin#2": (lib, batch(t, tpics))}
+            plan = Y.plan_of(lib, batches[src + "422"][1].handle)
+            times = {k: [] for k in batches}
+            for _ in range(a.rounds):
+                for k, (l, b) in batches.items():
+                    times[k].append(time_ms(l, b.run, a.steps))
+            base = statistics.median(times["twin"])
+            spread = abs(statistics.median(times["twin#2"]) / base - 1.0)
+            twin_bytes = batches["twin"][1].src_bytes + batches["twin"][1].dst_bytes
+            for k, (l, b) in batches.items():
+                ms = statistics.median(times[k])
+                us = ms * 1e3 / frames
+                nb = b.src_bytes + b.dst_bytes
+                out = {"workload": point + ":" + k, "frames_per_launch": frames, "ms_per_launch": ms, "us_per_picture": us, "frames_per_s": 1e6 / us,
+                       "algorithmic_bytes_per_frame": nb, "achieved_GBps": nb / us * 1e-3, "frac_of_8TBps": nb / us * 1e-3 / 8000.0,
+                       "vs_twin": ms / base - 1.0, "bound": nb / twin_bytes - 1.0, "aa_spread": spread, "ms_rounds": [round(x, 4) for x in times[k]]}
+                if k not in ("twin", "twin#2"):
+                    out.update({"kernel": plan["kernel"], "hstaged": plan["hstaged"]})
+                rows.append(out)
+                print(json.dumps(out), flush=True)
+            for l, b in batches.values():
+                b.close()
+    aa = max(r["aa_spread"] for r in rows)
+    miss = ["%s@%d %+.1f%% (bound %+.1f%%)" % (r["workload"], r["frames_per_launch"], 100 * r["vs_twin"], 100 * (r["bound"] + aa)) for r in rows if r["vs_twin"] > r["bound"] + aa]
+    print(json.dumps({"summary": "yuy2src", "aa_session": aa, "points": len(rows), "miss": miss}), flush=True)
 
 
 if __name__ == "__main__":
