@@ -13,6 +13,10 @@
  * the context, the plan (which kernel a context gets) and the entry points of include/mi355_sws.h.  The device side is sws_dev.h:
  * k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1, k_sws_nv12_pack, k_sws_nv12_split and the k_sws_line_* kernels of the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
+ * Launches: sws_key() names a context's instance once (sws_dev.h: SwsKey), sws_run() hands the key to the file that compiles that instance — here
+ * the plain and RANGE instances of k_sws_planar and the rgb24 destination of k_sws_generic / k_sws_ident1 / k_sws_c24 for the four classic source
+ * classes; sws_deep.hip, sws_packed.hip, sws_rgb32.hip and sws_yuy2.hip hold the rest, one launch function each — and every file maps the key to its
+ * instance through the one dispatcher sws_launch() of sws_dev.h.
  */
 #include "mi355_rt.h"
 #include "sws_dev.h"
@@ -335,38 +339,51 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
     upload_banks(c, desc);
     return ctx_upload(c);
 }
+/* what the creators open with, each under the name `who` of the entry point: a thread bound to its device (no CPU fallback: abort), ... */
+static void creator_bind(const char *who)
+{
+    if (!bind()) { std::fprintf(stderr, "mi355dsp: %s without mi355_init(); no CPU fallback\n", who); std::abort(); }
+}
+/* ... a descriptor and a source side, ... */
+static bool creator_args(const char *who, const mi355_sws_desc *desc, const mi355_sws_src *src)
+{
+    creator_bind(who);
+    if (!desc || !src) { std::fprintf(stderr, "mi355dsp: %s: no descriptor\n", who); return false; }
+    return true;
+}
+/* ... and a source layout of the list (the layered creators check their own argument first, so this is a step of its own) */
+static bool creator_layout(const char *who, int src_layout)
+{
+    if (src_layout_taken(src_layout)) return true;
+    std::fprintf(stderr, "mi355dsp: %s: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr / yuyv422 / uyvy422 / yvyu422\n", who, src_layout);
+    return false;
+}
 extern "C" mi355_sws_ctx *mi355_sws_create(const mi355_sws_desc *desc)
 {
-    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create without mi355_init(); no CPU fallback\n"); std::abort(); }
+    creator_bind("mi355_sws_create");
     return ctx_create(desc, nullptr, false, 0, "mi355_sws_create");
 }
 extern "C" mi355_sws_ctx *mi355_sws_create_planar(const mi355_sws_desc *desc, int dst_format)
 {
-    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_planar without mi355_init(); no CPU fallback\n"); std::abort(); }
+    creator_bind("mi355_sws_create_planar");
     return ctx_create(desc, nullptr, true, dst_format, "mi355_sws_create_planar");
 }
 extern "C" mi355_sws_ctx *mi355_sws_create_src(const mi355_sws_desc *desc, const mi355_sws_src *src, int dst_format)
 {
-    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src without mi355_init(); no CPU fallback\n"); std::abort(); }
-    if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src: no descriptor\n"); return nullptr; }
+    if (!creator_args("mi355_sws_create_src", desc, src)) return nullptr;
     return ctx_create(desc, src, dst_format != 0 && !packed_dst(dst_format), dst_format, "mi355_sws_create_src");
 }
 extern "C" mi355_sws_ctx *mi355_sws_create_src_layout(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format)
 {
-    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout without mi355_init(); no CPU fallback\n"); std::abort(); }
-    if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout: no descriptor\n"); return nullptr; }
-    if (!src_layout_taken(src_layout)) {
-        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr / yuyv422 / uyvy422 / yvyu422\n", src_layout);
-        return nullptr;
-    }
+    if (!creator_args("mi355_sws_create_src_layout", desc, src)) return nullptr;
+    if (!creator_layout("mi355_sws_create_src_layout", src_layout)) return nullptr;
     return ctx_create(desc, src, dst_format != 0 && !packed_dst(dst_format), dst_format, "mi355_sws_create_src_layout", src_layout);
 }
 extern "C" int mi355_sws_source_layout(const mi355_sws_ctx *c) { return c ? c->h.src_layout : -1; }
 extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_alpha(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format, int alpha)
 {
     if (!alpha) return mi355_sws_create_src_layout(desc, src, src_layout, dst_format);
-    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_alpha without mi355_init(); no CPU fallback\n"); std::abort(); }
-    if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_alpha: no descriptor\n"); return nullptr; }
+    if (!creator_args("mi355_sws_create_src_layout_alpha", desc, src)) return nullptr;
     if (alpha != 1 || !sws_rgb32_src(src_layout) || dst_format < MI355_SWS_DST_RGBA || dst_format > MI355_SWS_DST_ABGR || desc->unscaled_special) {
         std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_alpha: alpha (%d) is carried from an rgba / bgra / argb / abgr source (layout %d) to an rgba / bgra / "
                      "argb / abgr destination (format %d) by the scaler only (unscaled_special %d)\n", alpha, src_layout, dst_format, desc->unscaled_special);
@@ -380,16 +397,12 @@ extern "C" int mi355_sws_alpha(const mi355_sws_ctx *c) { return c ? c->alpha : -
 extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format, int range)
 {
     if (range == MI355_SWS_RANGE_NONE) return mi355_sws_create_src_layout(desc, src, src_layout, dst_format);
-    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range without mi355_init(); no CPU fallback\n"); std::abort(); }
-    if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: no descriptor\n"); return nullptr; }
+    if (!creator_args("mi355_sws_create_src_layout_range", desc, src)) return nullptr;
     if (range != MI355_SWS_RANGE_FROM_JPEG && range != MI355_SWS_RANGE_TO_JPEG) {
         std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: range %d is not none / from-jpeg / to-jpeg\n", range);
         return nullptr;
     }
-    if (!src_layout_taken(src_layout)) {
-        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr / yuyv422 / uyvy422 / yvyu422\n", src_layout);
-        return nullptr;
-    }
+    if (!creator_layout("mi355_sws_create_src_layout_range", src_layout)) return nullptr;
     /* the reference converts the range of YUV destinations only (an RGB one takes it into its LUTs), and never in an unscaled special converter */
     if (dst_format == 0 || packed_dst(dst_format)) {
         std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: a packed RGB destination (%d) has its range in the LUTs, not in a conversion step\n", dst_format);
@@ -406,16 +419,12 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range_depth(const mi355_sw
                                                                   int dst_depth)
 {
     if (dst_depth == 8) return mi355_sws_create_src_layout_range(desc, src, src_layout, dst_format, range);
-    if (!bind()) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth without mi355_init(); no CPU fallback\n"); std::abort(); }
-    if (!desc || !src) { std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: no descriptor\n"); return nullptr; }
+    if (!creator_args("mi355_sws_create_src_layout_range_depth", desc, src)) return nullptr;
     if (dst_depth != 9 && dst_depth != 10) {
         std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: destination depth %d is not 8 / 9 / 10\n", dst_depth);
         return nullptr;
     }
-    if (!src_layout_taken(src_layout)) {
-        std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr / yuyv422 / uyvy422 / yvyu422\n", src_layout);
-        return nullptr;
-    }
+    if (!creator_layout("mi355_sws_create_src_layout_range_depth", src_layout)) return nullptr;
     if (dst_format < MI355_SWS_DST_YUV420P || dst_format > MI355_SWS_DST_YUV444P) {
         std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range_depth: a %d-bit destination is yuv420p / yuv422p / yuv444p (format %d)\n", dst_depth, dst_format);
         return nullptr;
@@ -508,118 +517,57 @@ extern "C" int mi355_sws_destination(const mi355_sws_ctx *c, mi355_sws_dest_info
     return 0;
 }
 
-/* the launch of instance I (0 / 1 / 2: A / B / C) of a tile kernel for samples of type ST; the generic kernel's waves per SIMD are what its
- * LDS allows, like the planar kernel's own */
-template <int I, typename ST> static void launch_generic(dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
+/* ---- launches --------------------------------------------------------------------------------------------------------------------------- */
+/* the destination form of the packed kernels for a dst_format (0: rgb24, MI355_SWS_DST_BGR24 ... _ABGR) */
+static int dst_form(int dst_format) { return !dst_format ? DST_RGB24 : (dst_format == MI355_SWS_DST_BGR24 ? DST_BGR24 : DST_RGB32); }
+
+/* the launch key (sws_dev.h: SwsKey) of a context whose kernel is k = sws_kernel(): the one place where the context's fields become the key's codes */
+static SwsKey sws_key(const mi355_sws_ctx *c, int k)
 {
-    constexpr SwsShape S = GENERIC_SHAPES[I];
-    hipLaunchKernelGGL((k_sws_generic<S.lcap, S.ccap, sws_waves(sws_lds_bytes(S.lcap, S.ccap, stage_bytes<ST>())), ST>), grid, dim3(NT), 0, s, d, frames);
+    const SwsDev &h = c->h;
+    SwsKey key{};
+    if (k >= MI355_SWS_K_PLANAR_A && k <= MI355_SWS_K_PLANAR_C) { key.kernel = SWS_KERNEL_PLANAR; key.i = k - MI355_SWS_K_PLANAR_A; }
+    else if (k >= MI355_SWS_K_GENERIC_A && k <= MI355_SWS_K_GENERIC_C) { key.kernel = SWS_KERNEL_GENERIC; key.i = k - MI355_SWS_K_GENERIC_A; }
+    else if (k == MI355_SWS_K_C24) key.kernel = h.src_vsub ? SWS_KERNEL_C24 : SWS_KERNEL_C24_422;
+    else if (k == MI355_SWS_K_IDENT1_1) key.kernel = SWS_KERNEL_IDENT1_1;
+    else if (k == MI355_SWS_K_IDENT1_X) key.kernel = SWS_KERNEL_IDENT1_X;
+    else key.kernel = SWS_KERNEL_YUY2_SPLIT;
+    key.src = rgb32_src(h) ? SWS_SRC_RGB32 : yuy2_src(h) ? SWS_SRC_YUY2 : packed_rgb(h) ? SWS_SRC_RGB24 : h.src_layout ? SWS_SRC_NV : h.depth > 8 ? SWS_SRC_P16 : SWS_SRC_P8;
+    key.form = semi_planar(h) ? SWS_FORM_SEMI : (h.hshift ? SWS_FORM_HALF : SWS_FORM_FULL);
+    key.kind = h.dst_bits > 8 ? SWS_KIND_DEEP : (h.range ? SWS_KIND_RANGE : SWS_KIND_PLAIN);
+    key.dst = dst_form(h.packed);
+    key.alpha = c->alpha != 0;
+    return key;
 }
-template <int I, typename ST> static void launch_planar(int hshift, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+static dim3 key_grid(const SwsKey &key, const SwsDev &h, int nframes)
 {
-    constexpr SwsShape S = PLANAR_SHAPES[I];
-    if (hshift) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, ST>), grid, dim3(NT), 0, s, d, frames);
-    else hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW, ST>), grid, dim3(NT), 0, s, d, frames);
+    switch (key.kernel) {
+    case SWS_KERNEL_GENERIC: case SWS_KERNEL_PLANAR: return sws_tile_grid(h, nframes);
+    case SWS_KERNEL_IDENT1_1: case SWS_KERNEL_IDENT1_X: return sws_ident1_grid(h, nframes);
+    case SWS_KERNEL_C24: case SWS_KERNEL_C24_422: return sws_c24_grid(h.dstW, h.srcH, nframes);
+    default: return dim3(1, 1, nframes);        /* k_sws_yuy2_split: the tile is its file's, the pictures are z */
+    }
 }
-/* the same for run-time instance i (0 / 1 / 2) */
-template <typename ST> static void launch_generic(int i, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
+/* the launch of a key by the file that holds its instance; this file: the plain and RANGE instances of k_sws_planar and the rgb24 destination of the
+ * packed kernels, of the four classic source classes */
+static bool sws_run(const SwsKey &key, const SwsOperands &op)
 {
-    if (i == 0) launch_generic<0, ST>(grid, s, d, frames);
-    else if (i == 1) launch_generic<1, ST>(grid, s, d, frames);
-    else launch_generic<2, ST>(grid, s, d, frames);
+    if (key.src == SWS_SRC_RGB32) return mi355_sws_launch_rgb32(key, op);
+    if (key.src == SWS_SRC_YUY2) return mi355_sws_launch_yuy2(key, op);
+    if (key.kernel == SWS_KERNEL_PLANAR && key.kind == SWS_KIND_DEEP) return mi355_sws_launch_deep(key, op);
+    if (key.kernel != SWS_KERNEL_PLANAR && key.dst != DST_RGB24) return mi355_sws_launch_packed(key, op);
+    return sws_launch<SWS_CLASSIC_SRCS, sws_bit(SWS_KIND_PLAIN) | sws_bit(SWS_KIND_RANGE), sws_bit(DST_RGB24)>(key, op);
 }
-template <typename ST> static void launch_planar(int i, int hshift, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
+/* the context's kernel k on nframes pictures; -2: no file has the key's instance, or the launch failed */
+static int ctx_launch(const mi355_sws_ctx *c, int k, const void *d_frames, int nframes, hipStream_t s)
 {
-    if (i == 0) launch_planar<0, ST>(hshift, grid, s, d, frames);
-    else if (i == 1) launch_planar<1, ST>(hshift, grid, s, d, frames);
-    else launch_planar<2, ST>(hshift, grid, s, d, frames);
+    const SwsDev &h = c->h;
+    const SwsKey key = sws_key(c, k);
+    const SwsOperands op{ key_grid(key, h, nframes), s, &h, c->d, d_frames, &c->d->luts, h.dstW, h.srcH, h.dst_sel, nullptr };
+    if (!sws_run(key, op)) return -2;
+    return hipGetLastError() == hipSuccess ? 0 : -2;
 }
-/* ... of a semi-planar destination (NV12 / NV21: 4:2:0, the SEMI instances of k_sws_planar) */
-template <int I, typename ST> static void launch_semi(dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
-{
-    constexpr SwsShape S = PLANAR_SHAPES[I];
-    hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, ST, true>), grid, dim3(NT), 0, s, d, frames);
-}
-template <typename ST> static void launch_semi(int i, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
-{
-    if (i == 0) launch_semi<0, ST>(grid, s, d, frames);
-    else if (i == 1) launch_semi<1, ST>(grid, s, d, frames);
-    else launch_semi<2, ST>(grid, s, d, frames);
-}
-/* ... of an NV12 / NV21 source (8 bit): the NV instances — the LDS, and so the waves per SIMD, of the three-plane ones */
-template <int I> static void launch_generic_nv(dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
-{
-    constexpr SwsShape S = GENERIC_SHAPES[I];
-    hipLaunchKernelGGL((k_sws_generic<S.lcap, S.ccap, sws_waves(sws_lds_bytes(S.lcap, S.ccap, STAGE_BYTES)), uint8_t, true>), grid, dim3(NT), 0, s, d, frames);
-}
-static void launch_generic_nv(int i, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
-{
-    if (i == 0) launch_generic_nv<0>(grid, s, d, frames);
-    else if (i == 1) launch_generic_nv<1>(grid, s, d, frames);
-    else launch_generic_nv<2>(grid, s, d, frames);
-}
-/* form 0: three planes at CW = TW / 2, 1: at CW = TW, 2: a semi-planar destination */
-template <int I> static void launch_planar_nv(int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
-{
-    constexpr SwsShape S = PLANAR_SHAPES[I];
-    if (form == 0) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, uint8_t, false, true>), grid, dim3(NT), 0, s, d, frames);
-    else if (form == 1) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW, uint8_t, false, true>), grid, dim3(NT), 0, s, d, frames);
-    else hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, uint8_t, true, true>), grid, dim3(NT), 0, s, d, frames);
-}
-static void launch_planar_nv(int i, int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
-{
-    if (i == 0) launch_planar_nv<0>(form, grid, s, d, frames);
-    else if (i == 1) launch_planar_nv<1>(form, grid, s, d, frames);
-    else launch_planar_nv<2>(form, grid, s, d, frames);
-}
-/* ... of a packed rgb24 / bgr24 source (8 bit): the RGB instances — the converted samples are staged in the 8-bit instances' staging lines, the same
- * LDS and waves per SIMD again */
-template <int I> static void launch_generic_rgb(dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
-{
-    constexpr SwsShape S = GENERIC_SHAPES[I];
-    hipLaunchKernelGGL((k_sws_generic<S.lcap, S.ccap, sws_waves(sws_lds_bytes(S.lcap, S.ccap, STAGE_BYTES)), uint8_t, false, true>), grid, dim3(NT), 0, s, d, frames);
-}
-static void launch_generic_rgb(int i, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
-{
-    if (i == 0) launch_generic_rgb<0>(grid, s, d, frames);
-    else if (i == 1) launch_generic_rgb<1>(grid, s, d, frames);
-    else launch_generic_rgb<2>(grid, s, d, frames);
-}
-template <int I> static void launch_planar_rgb(int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
-{
-    constexpr SwsShape S = PLANAR_SHAPES[I];
-    if (form == 0) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, uint8_t, false, false, true>), grid, dim3(NT), 0, s, d, frames);
-    else if (form == 1) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW, uint8_t, false, false, true>), grid, dim3(NT), 0, s, d, frames);
-    else hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, uint8_t, true, false, true>), grid, dim3(NT), 0, s, d, frames);
-}
-static void launch_planar_rgb(int i, int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
-{
-    if (i == 0) launch_planar_rgb<0>(form, grid, s, d, frames);
-    else if (i == 1) launch_planar_rgb<1>(form, grid, s, d, frames);
-    else launch_planar_rgb<2>(form, grid, s, d, frames);
-}
-/* ... of a context that converts the range: the RANGE instance of each planar instance above — the same LDS (the step works in place) and waves
- * per SIMD.  src: 0 8-bit planes, 1 16-bit planes, 2 NV12 / NV21, 3 rgb24 / bgr24; form as above */
-template <int I, typename ST, bool NV, bool RGB> static void launch_planar_range(int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
-{
-    constexpr SwsShape S = PLANAR_SHAPES[I];
-    if (form == 0) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, ST, false, NV, RGB, true>), grid, dim3(NT), 0, s, d, frames);
-    else if (form == 1) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW, ST, false, NV, RGB, true>), grid, dim3(NT), 0, s, d, frames);
-    else hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, ST, true, NV, RGB, true>), grid, dim3(NT), 0, s, d, frames);
-}
-template <int I> static void launch_planar_range(int src, int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
-{
-    if (src == 0) launch_planar_range<I, uint8_t, false, false>(form, grid, s, d, frames);
-    else if (src == 1) launch_planar_range<I, uint16_t, false, false>(form, grid, s, d, frames);
-    else if (src == 2) launch_planar_range<I, uint8_t, true, false>(form, grid, s, d, frames);
-    else launch_planar_range<I, uint8_t, false, true>(form, grid, s, d, frames);
-}
-static void launch_planar_range(int i, int src, int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
-{
-    if (i == 0) launch_planar_range<0>(src, form, grid, s, d, frames);
-    else if (i == 1) launch_planar_range<1>(src, form, grid, s, d, frames);
-    else launch_planar_range<2>(src, form, grid, s, d, frames);
-}
+
 /* workgroups per CU of the instances (8-bit, then 16-bit: their staging lines are STAGE_BYTES16); the NV instances stage the pair plane in the
  * 8-bit instances' staging lines (StageGeom<TW>) and hold the same tiles: the 8-bit rows below are theirs too */
 static_assert(StageGeom<TW>::PITCH * StageGeom<TW>::LINES * 4 == STAGE_BYTES, "the pair plane's rounds fill the 8-bit staging storage");
@@ -635,49 +583,8 @@ static_assert(planar_waves(0, TW / 2, STAGE_BYTES16) == 8 && planar_waves(1, TW 
 extern "C" int mi355_sws_scale_frames_dev(mi355_sws_ctx *c, const mi355_sws_frame *d_frames, int nframes, void *stream)
 {
     if (!c || !d_frames || nframes <= 0 || c->h.planar) return -1;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const SwsDev &h = c->h;
     DeviceScope on(c->device);
-    const int k = sws_kernel(h);
-    if (rgb32_src(h)) {
-        /* a 32-bit source: always a tile instance (sws_rgb32.hip), to rgb24 and to the five other packed destinations */
-        mi355_sws_launch_generic_rgb32(k - MI355_SWS_K_GENERIC_A, h.packed, c->alpha, dim3((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes), s, c->d, d_frames);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
-    }
-    if (yuy2_src(h)) {
-        /* a packed 4:2:2 source: the tile instances and the ident1 form of sws_yuy2.hip, to rgb24 and to the five other packed destinations */
-        if (k == MI355_SWS_K_IDENT1_1) mi355_sws_launch_ident1_yuy2(h.packed, dim3((h.dstW + C24_COLS - 1) / C24_COLS, (h.dstH + IDENT_ROWS - 1) / IDENT_ROWS, nframes), s, c->d, d_frames);
-        else mi355_sws_launch_generic_yuy2(k - MI355_SWS_K_GENERIC_A, h.packed, dim3((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes), s, c->d, d_frames);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
-    }
-    if (h.packed) {
-        /* bgr24 and the 32-bit orders: the twin's kernel and grid, the DST_BGR24 / DST_RGB32 instance (sws_packed.hip) */
-        const dim3 grid = k == MI355_SWS_K_C24 ? dim3((h.dstW + C24_COLS - 1) / C24_COLS, (h.srcH + C24_ROWS - 1) / C24_ROWS, nframes) :
-                          k == MI355_SWS_K_IDENT1_1 || k == MI355_SWS_K_IDENT1_X ? dim3((h.dstW + C24_COLS - 1) / C24_COLS, (h.dstH + IDENT_ROWS - 1) / IDENT_ROWS, nframes) :
-                          dim3((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
-        const int src = k == MI355_SWS_K_C24 ? (h.src_vsub ? 0 : 1) : (packed_rgb(h) ? 3 : (h.src_layout ? 2 : (h.depth > 8 ? 1 : 0)));
-        mi355_sws_launch_packed(k, src, h.packed, grid, s, c->d, h.dstW, h.srcH, d_frames);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
-    }
-    if (k == MI355_SWS_K_C24) {
-        const dim3 grid((h.dstW + C24_COLS - 1) / C24_COLS, (h.srcH + C24_ROWS - 1) / C24_ROWS, nframes);
-        if (h.src_vsub) hipLaunchKernelGGL(k_sws_c24<0>, grid, dim3(NT), 0, s, &c->d->luts, h.dstW, h.srcH, 0, d_frames);
-        else hipLaunchKernelGGL(k_sws_c24<1>, grid, dim3(NT), 0, s, &c->d->luts, h.dstW, h.srcH, 0, d_frames);      /* yuv422p: every other chroma line */
-    } else if (k == MI355_SWS_K_IDENT1_1 || k == MI355_SWS_K_IDENT1_X) {
-        const dim3 grid((h.dstW + C24_COLS - 1) / C24_COLS, (h.dstH + IDENT_ROWS - 1) / IDENT_ROWS, nframes);
-        if (h.src_layout) {
-            if (k == MI355_SWS_K_IDENT1_1) hipLaunchKernelGGL((k_sws_ident1<false, true>), grid, dim3(NT), 0, s, c->d, d_frames);
-            else hipLaunchKernelGGL((k_sws_ident1<true, true>), grid, dim3(NT), 0, s, c->d, d_frames);
-        } else if (k == MI355_SWS_K_IDENT1_1) hipLaunchKernelGGL(k_sws_ident1<false>, grid, dim3(NT), 0, s, c->d, d_frames);
-        else hipLaunchKernelGGL(k_sws_ident1<true>, grid, dim3(NT), 0, s, c->d, d_frames);
-    } else {
-        const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
-        if (packed_rgb(h)) launch_generic_rgb(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
-        else if (h.src_layout) launch_generic_nv(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
-        else if (h.depth > 8) launch_generic<uint16_t>(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
-        else launch_generic<uint8_t>(k - MI355_SWS_K_GENERIC_A, grid, s, c->d, d_frames);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return ctx_launch(c, sws_kernel(c->h), d_frames, nframes, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *c, const mi355_sws_planar_frame *d_frames, int nframes, void *stream)
@@ -687,37 +594,14 @@ extern "C" int mi355_sws_scale_planar_frames_dev(mi355_sws_ctx *c, const mi355_s
     const SwsDev &h = c->h;
     DeviceScope on(c->device);
     const int k = sws_kernel(h);
-    if (k == MI355_SWS_K_NV12_PACK) {
-        hipLaunchKernelGGL(k_sws_nv12_pack, dim3((h.srcW + PACK_COLS - 1) / PACK_COLS, (h.srcH + PACK_ROWS - 1) / PACK_ROWS, nframes), dim3(NT), 0, s,
-                           h.srcW, h.srcH, h.planar == MI355_SWS_DST_NV21 ? 1 : 0, d_frames);
+    if (k == MI355_SWS_K_NV12_PACK || k == MI355_SWS_K_NV12_SPLIT) {
+        /* the unscaled packer and splitter: one kernel each, the NV side's pair order as an argument */
+        const dim3 grid((h.srcW + PACK_COLS - 1) / PACK_COLS, (h.srcH + PACK_ROWS - 1) / PACK_ROWS, nframes);
+        if (k == MI355_SWS_K_NV12_PACK) hipLaunchKernelGGL(k_sws_nv12_pack, grid, dim3(NT), 0, s, h.srcW, h.srcH, h.planar == MI355_SWS_DST_NV21 ? 1 : 0, d_frames);
+        else hipLaunchKernelGGL(k_sws_nv12_split, grid, dim3(NT), 0, s, h.srcW, h.srcH, h.src_layout == MI355_SWS_SRC_NV21 ? 1 : 0, d_frames);
         return hipGetLastError() == hipSuccess ? 0 : -2;
     }
-    if (k == MI355_SWS_K_NV12_SPLIT) {
-        hipLaunchKernelGGL(k_sws_nv12_split, dim3((h.srcW + PACK_COLS - 1) / PACK_COLS, (h.srcH + PACK_ROWS - 1) / PACK_ROWS, nframes), dim3(NT), 0, s,
-                           h.srcW, h.srcH, h.src_layout == MI355_SWS_SRC_NV21 ? 1 : 0, d_frames);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
-    }
-    if (k == MI355_SWS_K_YUY2_SPLIT) {
-        mi355_sws_launch_yuy2_split(sws_yuy2_luma(h.src_layout), h.planar == MI355_SWS_DST_YUV420P ? 1 : 0, h.srcW, h.srcH, nframes, s, d_frames);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
-    }
-    const dim3 grid((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes);
-    const int i = k - MI355_SWS_K_PLANAR_A;
-    /* a 32-bit source: plain, RANGE and DEEP instances of its own (sws_rgb32.hip) */
-    if (rgb32_src(h)) mi355_sws_launch_planar_rgb32(i, h.dst_bits > 8 ? 2 : (h.range ? 1 : 0), semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
-    /* ... and so has a packed 4:2:2 one (sws_yuy2.hip) */
-    else if (yuy2_src(h)) mi355_sws_launch_planar_yuy2(i, h.dst_bits > 8 ? 2 : (h.range ? 1 : 0), semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
-    /* a 9- / 10-bit destination: the DEEP instances (three planes, no range) */
-    else if (h.dst_bits > 8) mi355_sws_launch_planar_deep(i, packed_rgb(h) ? 3 : (h.src_layout ? 2 : (h.depth > 8 ? 1 : 0)), h.hshift ? 0 : 1, grid, s, c->d, d_frames);
-    else if (h.range) launch_planar_range(i, packed_rgb(h) ? 3 : (h.src_layout ? 2 : (h.depth > 8 ? 1 : 0)), semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
-    else if (packed_rgb(h)) launch_planar_rgb(i, semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
-    else if (h.src_layout) launch_planar_nv(i, semi_planar(h) ? 2 : (h.hshift ? 0 : 1), grid, s, c->d, d_frames);
-    else if (semi_planar(h)) {
-        if (h.depth > 8) launch_semi<uint16_t>(i, grid, s, c->d, d_frames);
-        else launch_semi<uint8_t>(i, grid, s, c->d, d_frames);
-    } else if (h.depth > 8) launch_planar<uint16_t>(i, h.hshift, grid, s, c->d, d_frames);
-    else launch_planar<uint8_t>(i, h.hshift, grid, s, c->d, d_frames);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return ctx_launch(c, k, d_frames, nframes, s);
 }
 
 /* copy a host plane into a tightly pitched device plane */
@@ -879,29 +763,13 @@ extern "C" void mi355_sws_hscale16to15(int16_t *dst, int dstW, const uint8_t *sr
 extern "C" void mi355_sws_rgb24ToY(uint8_t *dst, const uint8_t *src, int width, int bgr)
 {
     if (width <= 0) return;
-    Arena &a = arena();
-    const size_t nsrc = (size_t)3 * width;
-    a.reserve(nsrc + (size_t)width + 64);
-    const size_t o_src = a.take(nsrc), o_d = a.take((size_t)width);
-    std::memcpy(a.h<uint8_t>(o_src), src, nsrc);
-    a.upload();
-    launch_line(k_sws_line_rgb24_y, a, a.d<uint8_t>(o_d), a.d<const uint8_t>(o_src), width, bgr);
-    a.download();
-    std::memcpy(dst, a.h<uint8_t>(o_d), (size_t)width);
+    sws_line<1>(k_sws_line_rgb24_y, &dst, src, (size_t)3 * width, width, bgr);
 }
 extern "C" void mi355_sws_rgb24ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int width, int bgr, int half)
 {
     if (width <= 0) return;
-    Arena &a = arena();
-    const size_t nsrc = (size_t)(half ? 6 : 3) * width;
-    a.reserve(nsrc + (size_t)2 * width + 96);
-    const size_t o_src = a.take(nsrc), o_u = a.take((size_t)width), o_v = a.take((size_t)width);
-    std::memcpy(a.h<uint8_t>(o_src), src, nsrc);
-    a.upload();
-    launch_line(k_sws_line_rgb24_uv, a, a.d<uint8_t>(o_u), a.d<uint8_t>(o_v), a.d<const uint8_t>(o_src), width, bgr, half);
-    a.download();
-    std::memcpy(dstU, a.h<uint8_t>(o_u), (size_t)width);
-    std::memcpy(dstV, a.h<uint8_t>(o_v), (size_t)width);
+    uint8_t *const out[2] = { dstU, dstV };
+    sws_line<2>(k_sws_line_rgb24_uv, out, src, (size_t)(half ? 6 : 3) * width, width, bgr, half);
 }
 
 /* lumRangeFromJpeg_c / lumRangeToJpeg_c and chrRangeFromJpeg_c / chrRangeToJpeg_c (swscale.c:168-198) of one line, in place */
@@ -1013,16 +881,18 @@ static void rgb_line(const mi355_sws_luts *luts, int mode, const int16_t *lumF, 
     if (lumF) std::memcpy(a.h<int16_t>(o_lf), lumF, (size_t)ls * 2);
     if (chrF) std::memcpy(a.h<int16_t>(o_cf), chrF, (size_t)cs * 2);
     a.upload();
-    if (alp)
-        mi355_sws_launch_line_packed_a(dst_format, a.stream, a.d<const mi355_sws_luts>(o_t), mode, a.d<const int16_t>(o_lf), a.d<const int16_t>(o_l), ls, a.d<const int16_t>(o_cf),
-                                       a.d<const int16_t>(o_u), a.d<const int16_t>(o_v), cs, a.d<const int16_t>(o_a), pitch, a.d<uint8_t>(o_d), dstW, yalpha, uvalpha);
-    else
-    if (dst_format)
-        mi355_sws_launch_line_packed(dst_format, a.stream, a.d<const mi355_sws_luts>(o_t), mode, a.d<const int16_t>(o_lf), a.d<const int16_t>(o_l), ls, a.d<const int16_t>(o_cf),
-                                     a.d<const int16_t>(o_u), a.d<const int16_t>(o_v), cs, pitch, a.d<uint8_t>(o_d), dstW, yalpha, uvalpha);
-    else
-    launch_line(k_sws_line_rgb, a, a.d<const mi355_sws_luts>(o_t), mode, a.d<const int16_t>(o_lf), a.d<const int16_t>(o_l), ls, a.d<const int16_t>(o_cf),
-                a.d<const int16_t>(o_u), a.d<const int16_t>(o_v), cs, pitch, a.d<uint8_t>(o_d), dstW, yalpha, uvalpha);
+    const SwsLine n{ a.d<const mi355_sws_luts>(o_t), mode, a.d<const int16_t>(o_lf), a.d<const int16_t>(o_l), ls, a.d<const int16_t>(o_cf), a.d<const int16_t>(o_u),
+                     a.d<const int16_t>(o_v), cs, alp ? a.d<const int16_t>(o_a) : nullptr, pitch, a.d<uint8_t>(o_d), dstW, yalpha, uvalpha };
+    if (dst_format) {
+        SwsKey key{};
+        key.kernel = SWS_KERNEL_LINE; key.dst = dst_form(dst_format); key.alpha = alp != nullptr;
+        const SwsOperands op{ dim3(1), a.stream, nullptr, nullptr, nullptr, nullptr, 0, 0, key.dst == DST_RGB32 ? sws_rgb32_sel(dst_format) : 0u, &n };
+        if (!(alp ? mi355_sws_launch_rgb32(key, op) : mi355_sws_launch_packed(key, op))) {
+            std::fprintf(stderr, "mi355dsp: no line kernel for destination format %d%s\n", dst_format, alp ? " with alpha" : "");
+            std::abort();
+        }
+    } else
+    launch_line(k_sws_line_rgb, a, n.luts, n.mode, n.lumF, n.l, n.ls, n.chrF, n.u, n.v, n.cs, n.pitch, n.dest, n.dstW, n.yalpha, n.uvalpha);
     a.download();
     std::memcpy(dest, a.h<uint8_t>(o_d), (size_t)npair * pb);   /* like the reference: whole pairs, also for odd dstW */
 }
@@ -1045,14 +915,19 @@ extern "C" void mi355_sws_yuv2rgb24_1(const mi355_sws_luts *luts, const int16_t 
     rgb_line(luts, 1, nullptr, &buf0, 1, nullptr, ubuf, vbuf, cs, dest, dstW, 0, uvalpha);
 }
 
-extern "C" int mi355_sws_yuv2rgb_c_24_rgb(const mi355_sws_luts *luts, int dstW, const uint8_t *const src[3], const int srcStride[3],
-                                          int srcSliceY, int srcSliceH, uint8_t *dst, int dstStride)
+/* yuv2rgb_c_24_rgb / yuv2rgb_c_24_bgr / yuv2rgb_c_32 (yuv2rgb.c:237-394) on one 4:2:0 slice, to dst_format 0 (rgb24) or MI355_SWS_DST_BGR24 ... _ABGR;
+ * who: the entry point that was called */
+static int c24_slice(const char *who, const mi355_sws_luts *luts, int dst_format, int dstW, const uint8_t *const src[3], const int srcStride[3], int srcSliceY, int srcSliceH,
+                     uint8_t *dst, int dstStride)
 {
-    if (!ready()) { std::fprintf(stderr, "mi355dsp: mi355_sws_yuv2rgb_c_24_rgb without mi355_init(); no CPU fallback\n"); std::abort(); }
+    if (dst_format != 0 && !packed_dst(dst_format)) return -1;
+    if (!ready()) { std::fprintf(stderr, "mi355dsp: %s without mi355_init(); no CPU fallback\n", who); std::abort(); }
+    const int bpp = dst_format >= MI355_SWS_DST_RGBA ? 4 : 3;
+    if (bpp == 4 && ((reinterpret_cast<uintptr_t>(dst) | (uintptr_t)dstStride) & 3)) return -1;      /* a 32-bit destination is stored in dwords */
     /* a slice may be a whole picture: device buffers per call instead of the staging arena */
     const int rows = srcSliceH, cw = dstW >> 1, crow = (rows + 1) >> 1;   /* even slices, as the reference's callers guarantee */
     const int pw[3] = { (dstW + 15) & ~15, (cw + 15) & ~15, (cw + 15) & ~15 }, ph[3] = { rows, crow, crow }, w[3] = { dstW & ~1, cw, cw };
-    const int dpitch = (dstW * 3 + 15) & ~15;
+    const int dpitch = (dstW * bpp + 15) & ~15;
     hipStream_t s = arena().stream;
     mi355_sws_frame f, *d_f;
     uint8_t *d_l, *d_dst;
@@ -1068,13 +943,20 @@ extern "C" int mi355_sws_yuv2rgb_c_24_rgb(const mi355_sws_luts *luts, int dstW, 
     f.dst = d_dst; f.dst_stride = dpitch;
     MI355_CHECK(hipMemcpyAsync(d_f, &f, sizeof(f), hipMemcpyHostToDevice, s));
     MI355_CHECK(hipMemcpyAsync(d_l, luts, sizeof(mi355_sws_luts), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_sws_c24<0>, dim3((dstW + C24_COLS - 1) / C24_COLS, (rows + C24_ROWS - 1) / C24_ROWS, 1), dim3(NT), 0, s,
-                       reinterpret_cast<const mi355_sws_luts *>(d_l), dstW, rows, 0, d_f);
-    MI355_CHECK(hipMemcpy2DAsync(dst + (ptrdiff_t)srcSliceY * dstStride, dstStride, d_dst, dpitch, (dstW & ~1) * 3, rows, hipMemcpyDeviceToHost, s));
+    SwsKey key{};
+    key.kernel = SWS_KERNEL_C24; key.src = SWS_SRC_P8; key.dst = dst_form(dst_format);
+    const bool launched = sws_run(key, SwsOperands{ sws_c24_grid(dstW, rows, 1), s, nullptr, nullptr, d_f, reinterpret_cast<const mi355_sws_luts *>(d_l), dstW, rows,
+                                                    bpp == 4 ? sws_rgb32_sel(dst_format) : 0u, nullptr });
+    MI355_CHECK(hipMemcpy2DAsync(dst + (ptrdiff_t)srcSliceY * dstStride, dstStride, d_dst, dpitch, (dstW & ~1) * bpp, rows, hipMemcpyDeviceToHost, s));
     MI355_CHECK(hipStreamSynchronize(s));
     for (int p = 0; p < 3; p++) MI355_CHECK(hipFree(const_cast<uint8_t *>(f.src[p])));
     MI355_CHECK(hipFree(d_dst)); MI355_CHECK(hipFree(d_f)); MI355_CHECK(hipFree(d_l));
-    return srcSliceH;
+    return launched ? srcSliceH : -2;
+}
+extern "C" int mi355_sws_yuv2rgb_c_24_rgb(const mi355_sws_luts *luts, int dstW, const uint8_t *const src[3], const int srcStride[3],
+                                          int srcSliceY, int srcSliceH, uint8_t *dst, int dstStride)
+{
+    return c24_slice("mi355_sws_yuv2rgb_c_24_rgb", luts, 0, dstW, src, srcStride, srcSliceY, srcSliceH, dst, dstStride);
 }
 
 /* ---- the same entries for any packed destination (dst_format 0: rgb24, the entries above; MI355_SWS_DST_BGR24 ... _ABGR) ---------------- */
@@ -1123,38 +1005,10 @@ extern "C" void mi355_sws_yuv2packed_1_a(const mi355_sws_luts *luts, int dst_for
     rgb_line(luts, 1, nullptr, &buf0, 1, nullptr, ubuf, vbuf, cs, dest, dstW, 0, uvalpha, dst_format, &abuf0);
 }
 
-/* yuv2rgb_c_24_rgb / yuv2rgb_c_24_bgr / yuv2rgb_c_32 (yuv2rgb.c:237-394) on one 4:2:0 slice: mi355_sws_yuv2rgb_c_24_rgb with the destination's format */
+/* ... and the slice entry with the destination's format */
 extern "C" int mi355_sws_yuv2rgb_c(const mi355_sws_luts *luts, int dst_format, int dstW, const uint8_t *const src[3], const int srcStride[3],
                                    int srcSliceY, int srcSliceH, uint8_t *dst, int dstStride)
 {
-    if (dst_format == 0) return mi355_sws_yuv2rgb_c_24_rgb(luts, dstW, src, srcStride, srcSliceY, srcSliceH, dst, dstStride);
-    if (!packed_dst(dst_format)) return -1;
-    if (!ready()) { std::fprintf(stderr, "mi355dsp: mi355_sws_yuv2rgb_c without mi355_init(); no CPU fallback\n"); std::abort(); }
-    const int bpp = dst_format >= MI355_SWS_DST_RGBA ? 4 : 3;
-    if (bpp == 4 && ((reinterpret_cast<uintptr_t>(dst) | (uintptr_t)dstStride) & 3)) return -1;
-    const int rows = srcSliceH, cw = dstW >> 1, crow = (rows + 1) >> 1;   /* even slices, as the reference's callers guarantee */
-    const int pw[3] = { (dstW + 15) & ~15, (cw + 15) & ~15, (cw + 15) & ~15 }, ph[3] = { rows, crow, crow }, w[3] = { dstW & ~1, cw, cw };
-    const int dpitch = (dstW * bpp + 15) & ~15;
-    hipStream_t s = arena().stream;
-    mi355_sws_frame f, *d_f;
-    uint8_t *d_l, *d_dst;
-    for (int p = 0; p < 3; p++) {
-        uint8_t *d;
-        MI355_CHECK(hipMalloc(reinterpret_cast<void **>(&d), (size_t)pw[p] * (ph[p] + 1) + 64));
-        plane_h2d(d, pw[p], src[p], srcStride[p], w[p], ph[p], s);
-        f.src[p] = d; f.src_stride[p] = pw[p];
-    }
-    MI355_CHECK(hipMalloc(reinterpret_cast<void **>(&d_dst), (size_t)dpitch * (rows + 1)));
-    MI355_CHECK(hipMalloc(reinterpret_cast<void **>(&d_f), sizeof(f)));
-    MI355_CHECK(hipMalloc(reinterpret_cast<void **>(&d_l), sizeof(mi355_sws_luts)));
-    f.dst = d_dst; f.dst_stride = dpitch;
-    MI355_CHECK(hipMemcpyAsync(d_f, &f, sizeof(f), hipMemcpyHostToDevice, s));
-    MI355_CHECK(hipMemcpyAsync(d_l, luts, sizeof(mi355_sws_luts), hipMemcpyHostToDevice, s));
-    mi355_sws_launch_c24_slice(dst_format, dim3((dstW + C24_COLS - 1) / C24_COLS, (rows + C24_ROWS - 1) / C24_ROWS, 1), s,
-                               reinterpret_cast<const mi355_sws_luts *>(d_l), dstW, rows, d_f);
-    MI355_CHECK(hipMemcpy2DAsync(dst + (ptrdiff_t)srcSliceY * dstStride, dstStride, d_dst, dpitch, (dstW & ~1) * bpp, rows, hipMemcpyDeviceToHost, s));
-    MI355_CHECK(hipStreamSynchronize(s));
-    for (int p = 0; p < 3; p++) MI355_CHECK(hipFree(const_cast<uint8_t *>(f.src[p])));
-    MI355_CHECK(hipFree(d_dst)); MI355_CHECK(hipFree(d_f)); MI355_CHECK(hipFree(d_l));
-    return srcSliceH;
+    /* (dst_format 0 is mi355_sws_yuv2rgb_c_24_rgb, under its name) */
+    return c24_slice(dst_format ? "mi355_sws_yuv2rgb_c" : "mi355_sws_yuv2rgb_c_24_rgb", luts, dst_format, dstW, src, srcStride, srcSliceY, srcSliceH, dst, dstStride);
 }

@@ -1,6 +1,7 @@
 /*
- * sws_dev.h — the device side of sws.hip (included by it only): the tile geometry and its instance table, the steps of the scaler
- * (horizontal pass into LDS, packed and planar vertical passes) and the kernels:
+ * sws_dev.h — the device side of sws.hip and of the files that compile instances beside it (sws_deep.hip, sws_packed.hip, sws_rgb32.hip,
+ * sws_yuy2.hip): the tile geometry and its instance table, the steps of the scaler (horizontal pass into LDS, packed and planar vertical passes),
+ * at the end the host side of a launch (the launch key SwsKey, the dispatcher sws_launch, the grids, the line helper) and the kernels:
  *   k_sws_generic   the generic scaler of swscale() (libswscale/swscale.c:343-722) for whole pictures,
  *                   fused per output tile: horizontal 8->15 bit FIR of the source lines the tile needs
  *                   (hScale8To15_c :133-147) into LDS, vertical FIR + yuv->rgb LUT
@@ -2494,39 +2495,182 @@ __global__ void __launch_bounds__(NT) k_sws_line_rgb(const mi355_sws_luts *luts,
 #endif
 }  // namespace
 
-/* sws_deep.hip: the launch of the DEEP instance of k_sws_planar for a context (d: its SwsDev on the device) — instance i (0 / 1 / 2: A / B / C),
- * src 0 8-bit planes, 1 16-bit planes, 2 NV12 / NV21, 3 rgb24 / bgr24, full_cw: a 4:4:4 destination (CW = TW).  The DEEP instances are compiled
- * in a file of their own */
-void mi355_sws_launch_planar_deep(int i, int src, int full_cw, dim3 grid, hipStream_t s, const void *d, const mi355_sws_planar_frame *frames);
+/* ---- the launch key --------------------------------------------------------------------------------------------------------------------
+ * Which instance of which kernel a launch runs, named once.  sws.hip fills a key from a context (sws_key) and hands it to the file that owns the
+ * instance; every file maps it to hipLaunchKernelGGL through the one dispatcher below (sws_launch).
+ *   kernel  GENERIC / PLANAR: the tile kernels k_sws_generic / k_sws_planar, instance i; IDENT1_1 / IDENT1_X: k_sws_ident1<false / true> (a packed
+ *           4:2:2 source: k_sws_ident1_yuy2); C24 / C24_422: k_sws_c24<0 / 1> (yuv422p: every other chroma line); LINE: k_sws_line_packed of one line
+ *           (alpha: k_sws_line_packed_a); YUY2_SPLIT: k_sws_yuy2_split
+ *   i       0 / 1 / 2: the A / B / C row of GENERIC_SHAPES / PLANAR_SHAPES, as sws_kernel() chose it
+ *   src     the source class — P8 / P16: three planes of bytes / of 16-bit samples, NV: NV12 / NV21, RGB24: rgb24 / bgr24, RGB32: rgba / bgra /
+ *           argb / abgr, YUY2: yuyv422 / uyvy422 / yvyu422 (the order inside a class is read from the context on the device)
+ *   form    of k_sws_planar — HALF: three planes, chroma tiles of CW = TW / 2, FULL: of CW = TW (a 4:4:4 destination), SEMI: NV12 / NV21
+ *   kind    of k_sws_planar — PLAIN, RANGE (range conversion between the passes), DEEP (9- / 10-bit planes; three planes, no range)
+ *   dst     of the packed kernels — DST_RGB24 / DST_BGR24 / DST_RGB32 (the 32-bit order is the operands' sel)
+ *   alpha   the ALPHA form: a 32-bit source's alpha to a 32-bit destination
+ * A key a file has no instance for (DEEP with SEMI, ALPHA outside RGB32 -> DST_RGB32, another file's source class, kind or destination) is not
+ * launched: the launch functions return false and the entry point -2. */
+enum SwsKernel { SWS_KERNEL_GENERIC, SWS_KERNEL_PLANAR, SWS_KERNEL_IDENT1_1, SWS_KERNEL_IDENT1_X, SWS_KERNEL_C24, SWS_KERNEL_C24_422, SWS_KERNEL_LINE, SWS_KERNEL_YUY2_SPLIT };
+enum SwsSrcClass { SWS_SRC_P8, SWS_SRC_P16, SWS_SRC_NV, SWS_SRC_RGB24, SWS_SRC_RGB32, SWS_SRC_YUY2 };
+enum SwsForm { SWS_FORM_HALF, SWS_FORM_FULL, SWS_FORM_SEMI };
+enum SwsKind { SWS_KIND_PLAIN, SWS_KIND_RANGE, SWS_KIND_DEEP };
+struct SwsKey {
+    SwsKernel kernel;
+    int i;
+    SwsSrcClass src;
+    SwsForm form;
+    SwsKind kind;
+    int dst;
+    bool alpha;
+};
+/* the arguments of k_sws_line_rgb / k_sws_line_packed / k_sws_line_packed_a (a: the alpha lines of the last one) */
+struct SwsLine {
+    const mi355_sws_luts *luts;
+    int mode;
+    const int16_t *lumF, *l;
+    int ls;
+    const int16_t *chrF, *u, *v;
+    int cs;
+    const int16_t *a;
+    int pitch;
+    uint8_t *dest;
+    int dstW, yalpha, uvalpha;
+};
+/* what a launch takes besides its key.  h / d: the context's SwsDev on the host / on the device (none for a slice or a line); frames: the
+ * mi355_sws_frame / mi355_sws_planar_frame records on the device; luts, dstW, rows: the tables, width and slice rows of k_sws_c24; sel: the byte
+ * selector of a 32-bit order where the kernel takes it as an argument (k_sws_c24, the line kernels); line: the operands of SWS_KERNEL_LINE */
+struct SwsOperands {
+    dim3 grid;
+    hipStream_t s;
+    const void *h, *d, *frames;
+    const mi355_sws_luts *luts;
+    int dstW, rows;
+    uint32_t sel;
+    const SwsLine *line;
+};
+/* one launch function a file: false for a key the file has no instance for */
+bool mi355_sws_launch_deep(const SwsKey &key, const SwsOperands &op);       /* sws_deep.hip: the DEEP instances of the four classic source classes */
+bool mi355_sws_launch_packed(const SwsKey &key, const SwsOperands &op);     /* sws_packed.hip: DST_BGR24 / DST_RGB32 of k_sws_generic, k_sws_ident1, k_sws_c24, k_sws_line_packed */
+bool mi355_sws_launch_rgb32(const SwsKey &key, const SwsOperands &op);      /* sws_rgb32.hip: every tile instance of SWS_SRC_RGB32, k_sws_line_packed_a */
+bool mi355_sws_launch_yuy2(const SwsKey &key, const SwsOperands &op);       /* sws_yuy2.hip: every tile instance of SWS_SRC_YUY2, k_sws_ident1_yuy2, k_sws_yuy2_split */
 
-/* sws_packed.hip: the launches of the DST_BGR24 / DST_RGB32 instances of the packed kernels for a context (d: its SwsDev on the device; dst_format:
- * MI355_SWS_DST_BGR24 ... _ABGR) — k: MI355_SWS_K_C24 / IDENT1_1 / IDENT1_X / GENERIC_A .. C as sws_kernel() gave it, src as above (c24: 1 — every other
- * chroma line, an 8-bit yuv422p source; ident1: 2 — NV12 / NV21).  The grids are those of the rgb24 twin.  Compiled in a file of their own. */
-void mi355_sws_launch_packed(int k, int src, int dst_format, dim3 grid, hipStream_t s, const void *d, int dstW, int sliceH, const mi355_sws_frame *frames);
-/* ... and of the line kernel k_sws_line_packed (one workgroup), the arguments of k_sws_line_rgb */
-void mi355_sws_launch_line_packed(int dst_format, hipStream_t s, const mi355_sws_luts *luts, int mode, const int16_t *lumF, const int16_t *l, int ls, const int16_t *chrF,
-                                  const int16_t *u, const int16_t *v, int cs, int pitch, uint8_t *dest, int dstW, int yalpha, int uvalpha);
-/* ... and of k_sws_c24 on one slice with stand-alone tables (mi355_sws_yuv2rgb_c: a 4:2:0 slice) */
-void mi355_sws_launch_c24_slice(int dst_format, dim3 grid, hipStream_t s, const mi355_sws_luts *luts, int dstW, int rows, const mi355_sws_frame *frames);
+namespace {
+/* the three grids of the picture kernels: the tile kernels' (th rows of TW samples), k_sws_ident1's and k_sws_c24's (rows: source rows of the slice) */
+inline dim3 sws_tile_grid(const SwsDev &h, int nframes) { return dim3((h.dstW + TW - 1) / TW, (h.dstH + h.th - 1) / h.th, nframes); }
+inline dim3 sws_ident1_grid(const SwsDev &h, int nframes) { return dim3((h.dstW + C24_COLS - 1) / C24_COLS, (h.dstH + IDENT_ROWS - 1) / IDENT_ROWS, nframes); }
+inline dim3 sws_c24_grid(int dstW, int rows, int nframes) { return dim3((dstW + C24_COLS - 1) / C24_COLS, (rows + C24_ROWS - 1) / C24_ROWS, nframes); }
 
-/* sws_rgb32.hip: the launches of the tile instances of a 32-bit source (MI355_SWS_SRC_RGBA ... _ABGR) — instance i (0 / 1 / 2: A / B / C) of
- * k_sws_generic to dst_format 0 / MI355_SWS_DST_BGR24 ... _ABGR (alpha: the ALPHA form, a 32-bit destination), and of k_sws_planar: kind 0 plain, 1 RANGE, 2 DEEP; form 0 three planes at
- * CW = TW / 2, 1 at CW = TW, 2 a semi-planar destination.  Compiled in a file of their own. */
-void mi355_sws_launch_generic_rgb32(int i, int dst_format, int alpha, dim3 grid, hipStream_t s, const void *d, const mi355_sws_frame *frames);
-void mi355_sws_launch_planar_rgb32(int i, int kind, int form, dim3 grid, hipStream_t s, const void *d, const mi355_sws_planar_frame *frames);
-/* ... and of the line kernel k_sws_line_packed_a (one workgroup): k_sws_line_packed of a 32-bit order with the ls alpha lines `a` at the luma lines' pitch */
-void mi355_sws_launch_line_packed_a(int dst_format, hipStream_t s, const mi355_sws_luts *luts, int mode, const int16_t *lumF, const int16_t *l, int ls, const int16_t *chrF,
-                                    const int16_t *u, const int16_t *v, int cs, const int16_t *a, int pitch, uint8_t *dest, int dstW, int yalpha, int uvalpha);
+/* f(std::integral_constant<E, V>()) for the V of Vs that v equals: a run-time code as a template argument.  false where v is none of them */
+template <typename E, E... Vs, typename F> bool sws_pick(E v, F f)
+{
+    bool done = false;
+    (void)((v == Vs && ((done = f(std::integral_constant<E, Vs>())), true)) || ...);
+    return done;
+}
+template <typename F> bool sws_pick_dst(int dst, F f) { return sws_pick<int, DST_RGB24, DST_BGR24, DST_RGB32>(dst, f); }
+/* instance i as I: the row of GENERIC_SHAPES / PLANAR_SHAPES that sws_launch_generic / sws_launch_planar read */
+template <typename F> bool sws_pick_instance(int i, F f) { return sws_pick<int, 0, 1, 2>(i, f); }
+constexpr unsigned sws_bit(int v) { return 1u << v; }
+constexpr unsigned SWS_CLASSIC_SRCS = sws_bit(SWS_SRC_P8) | sws_bit(SWS_SRC_P16) | sws_bit(SWS_SRC_NV) | sws_bit(SWS_SRC_RGB24);
+constexpr unsigned SWS_ALL_KINDS = sws_bit(SWS_KIND_PLAIN) | sws_bit(SWS_KIND_RANGE) | sws_bit(SWS_KIND_DEEP);
+constexpr unsigned SWS_ALL_DSTS = sws_bit(DST_RGB24) | sws_bit(DST_BGR24) | sws_bit(DST_RGB32);
 
-/* sws_yuy2.hip: the launch of k_sws_yuy2_split, the four unscaled converters of a packed 4:2:2 source (yuyv422 / uyvy422 -> yuv420p / yuv422p) —
- * luma_off: the byte of a pair that is luma (0 yuyv422, 1 uyvy422), c420: chroma rows averaged in pairs; the grid is the kernel's own.  Compiled in a
- * file of its own. */
-void mi355_sws_launch_yuy2_split(int luma_off, int c420, int srcW, int srcH, int nframes, hipStream_t s, const mi355_sws_planar_frame *frames);
-/* ... and of the tile instances of these sources — instance i (0 / 1 / 2: A / B / C) of k_sws_generic to dst_format 0 / MI355_SWS_DST_BGR24 ... _ABGR, and of
- * k_sws_planar: kind 0 plain, 1 RANGE, 2 DEEP; form 0 three planes at CW = TW / 2, 1 at CW = TW, 2 a semi-planar destination — and of k_sws_ident1_yuy2
- * (k_sws_ident1's grid) */
-void mi355_sws_launch_generic_yuy2(int i, int dst_format, dim3 grid, hipStream_t s, const void *d, const mi355_sws_frame *frames);
-void mi355_sws_launch_planar_yuy2(int i, int kind, int form, dim3 grid, hipStream_t s, const void *d, const mi355_sws_planar_frame *frames);
-void mi355_sws_launch_ident1_yuy2(int dst_format, dim3 grid, hipStream_t s, const void *d, const mi355_sws_frame *frames);
+/* what a source class is to the tile kernels: the sample type and the NV / RGB arguments (the ALPHA form: SwsPx32A in place of SwsPx32) */
+template <SwsSrcClass C> struct SwsSrc { typedef uint8_t ST; static constexpr bool NV = false, RGB = false; };
+template <> struct SwsSrc<SWS_SRC_P16> { typedef uint16_t ST; static constexpr bool NV = false, RGB = false; };
+template <> struct SwsSrc<SWS_SRC_NV> { typedef uint8_t ST; static constexpr bool NV = true, RGB = false; };
+template <> struct SwsSrc<SWS_SRC_RGB24> { typedef uint8_t ST; static constexpr bool NV = false, RGB = true; };
+template <> struct SwsSrc<SWS_SRC_RGB32> { typedef SwsPx32 ST; static constexpr bool NV = false, RGB = true; };
+template <> struct SwsSrc<SWS_SRC_YUY2> { typedef SwsPxYuy2 ST; static constexpr bool NV = false, RGB = true; };
+
+/* instance I of k_sws_generic: its waves per SIMD are what its LDS allows (the staging lines of its sample type, the alpha tile of the ALPHA form),
+ * like the planar kernel's own */
+template <int I, SwsSrcClass C, int DST, bool ALPHA> void sws_launch_generic(const SwsOperands &op)
+{
+    typedef typename std::conditional<ALPHA, SwsPx32A, typename SwsSrc<C>::ST>::type ST;
+    constexpr SwsShape S = GENERIC_SHAPES[I];
+    hipLaunchKernelGGL((k_sws_generic<S.lcap, S.ccap, sws_waves(sws_lds_bytes(S.lcap, S.ccap, stage_bytes<ST>(), ALPHA)), ST, SwsSrc<C>::NV, SwsSrc<C>::RGB, DST>), op.grid, dim3(NT), 0,
+                       op.s, static_cast<const SwsDev *>(op.d), static_cast<const mi355_sws_frame *>(op.frames));
+}
+template <int I, SwsSrcClass C, SwsForm F, SwsKind K> void sws_launch_planar(const SwsOperands &op)
+{
+    constexpr SwsShape S = PLANAR_SHAPES[I];
+    hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, F == SWS_FORM_FULL ? TW : TW / 2, typename SwsSrc<C>::ST, F == SWS_FORM_SEMI, SwsSrc<C>::NV, SwsSrc<C>::RGB, K == SWS_KIND_RANGE,
+                                     K == SWS_KIND_DEEP>), op.grid, dim3(NT), 0, op.s, static_cast<const SwsDev *>(op.d), static_cast<const mi355_sws_planar_frame *>(op.frames));
+}
+template <int CS, int DST> void sws_launch_c24(const SwsOperands &op)
+{
+    typename C24Arg<DST>::type slice{};                     /* the slice starts at row 0; a 32-bit form: with the order's selector */
+    if constexpr (DST == DST_RGB32) slice.sel = op.sel;
+    hipLaunchKernelGGL((k_sws_c24<CS, DST>), op.grid, dim3(NT), 0, op.s, op.luts, op.dstW, op.rows, slice, static_cast<const mi355_sws_frame *>(op.frames));
+}
+template <bool X, bool NV, int DST> void sws_launch_ident1(const SwsOperands &op)
+{
+    hipLaunchKernelGGL((k_sws_ident1<X, NV, DST>), op.grid, dim3(NT), 0, op.s, static_cast<const SwsDev *>(op.d), static_cast<const mi355_sws_frame *>(op.frames));
+}
+
+/* THE dispatcher: the picture kernels of sws_dev.h for a key, restricted at compile time to the slice of the instance space the calling file owns —
+ * SRCS: its source classes, KINDS: its kinds of k_sws_planar, DSTS: its destination forms of the packed kernels (masks of sws_bit).  What lies outside
+ * the masks is not instantiated, and a key that asks for it comes back false. */
+template <unsigned SRCS, unsigned KINDS, unsigned DSTS> bool sws_launch(const SwsKey &key, const SwsOperands &op)
+{
+    return sws_pick<SwsSrcClass, SWS_SRC_P8, SWS_SRC_P16, SWS_SRC_NV, SWS_SRC_RGB24, SWS_SRC_RGB32, SWS_SRC_YUY2>(key.src, [&](auto src) {
+        constexpr SwsSrcClass C = decltype(src)::value;
+        if constexpr ((SRCS & sws_bit(C)) == 0) return false;
+        else if (key.kernel == SWS_KERNEL_PLANAR) {
+            return sws_pick<SwsKind, SWS_KIND_PLAIN, SWS_KIND_RANGE, SWS_KIND_DEEP>(key.kind, [&](auto kind) {
+                constexpr SwsKind K = decltype(kind)::value;
+                if constexpr ((KINDS & sws_bit(K)) == 0) return false;
+                else return sws_pick<SwsForm, SWS_FORM_HALF, SWS_FORM_FULL, SWS_FORM_SEMI>(key.form, [&](auto form) {
+                    constexpr SwsForm F = decltype(form)::value;
+                    if constexpr (K == SWS_KIND_DEEP && F == SWS_FORM_SEMI) return false;
+                    else return sws_pick_instance(key.i, [&](auto i) { sws_launch_planar<decltype(i)::value, C, F, K>(op); return true; });
+                });
+            });
+        } else {
+            return sws_pick_dst(key.dst, [&](auto dst) {
+                constexpr int DST = decltype(dst)::value;
+                if constexpr ((DSTS & sws_bit(DST)) == 0) return false;
+                else if (key.kernel == SWS_KERNEL_GENERIC) {
+                    constexpr bool HAS_ALPHA = C == SWS_SRC_RGB32 && DST == DST_RGB32;       /* the one pair that has an ALPHA form */
+                    if (key.alpha && !HAS_ALPHA) return false;
+                    return sws_pick_instance(key.i, [&](auto i) {
+                        if constexpr (HAS_ALPHA) if (key.alpha) { sws_launch_generic<decltype(i)::value, C, DST, true>(op); return true; }
+                        sws_launch_generic<decltype(i)::value, C, DST, false>(op);
+                        return true;
+                    });
+                } else if constexpr (C == SWS_SRC_P8 || C == SWS_SRC_NV) {
+                    /* k_sws_ident1 reads three planes of bytes or an NV source, k_sws_c24 three planes of bytes */
+                    if (key.kernel == SWS_KERNEL_IDENT1_1) { sws_launch_ident1<false, C == SWS_SRC_NV, DST>(op); return true; }
+                    if (key.kernel == SWS_KERNEL_IDENT1_X) { sws_launch_ident1<true, C == SWS_SRC_NV, DST>(op); return true; }
+                    if constexpr (C == SWS_SRC_P8) {
+                        if (key.kernel == SWS_KERNEL_C24) { sws_launch_c24<0, DST>(op); return true; }
+                        if (key.kernel == SWS_KERNEL_C24_422) { sws_launch_c24<1, DST>(op); return true; }
+                    }
+                    return false;
+                } else return false;
+            });
+        }
+    });
+}
+
+/* one line through a Tier-1 line kernel on the staging arena: nsrc source bytes in, NOUT (1 / 2) planes of `width` bytes out; tail: the kernel's
+ * arguments behind (dst..., src, width) */
+template <int NOUT, typename K, typename... A>
+void sws_line(K kernel, uint8_t *const *out, const uint8_t *src, size_t nsrc, int width, A... tail)
+{
+    mi355::Arena &a = mi355::arena();
+    a.reserve(nsrc + (size_t)NOUT * (width + 32) + 64);
+    const size_t o_src = a.take(nsrc);
+    size_t o_d[NOUT];
+    for (int p = 0; p < NOUT; p++) o_d[p] = a.take((size_t)width);
+    std::memcpy(a.h<uint8_t>(o_src), src, nsrc);
+    a.upload();
+    if constexpr (NOUT == 2) hipLaunchKernelGGL(kernel, dim3(1), dim3(NT), 0, a.stream, a.d<uint8_t>(o_d[0]), a.d<uint8_t>(o_d[1]), a.d<const uint8_t>(o_src), width, tail...);
+    else hipLaunchKernelGGL(kernel, dim3(1), dim3(NT), 0, a.stream, a.d<uint8_t>(o_d[0]), a.d<const uint8_t>(o_src), width, tail...);
+    a.download();
+    for (int p = 0; p < NOUT; p++) std::memcpy(out[p], a.h<uint8_t>(o_d[p]), (size_t)width);
+}
+}  // namespace
 
 #endif

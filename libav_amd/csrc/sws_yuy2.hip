@@ -1,7 +1,8 @@
 /*
  * sws_yuy2.hip — packed 4:2:2 SOURCES (yuyv422 / uyvy422 / yvyu422: MI355_SWS_SRC_YUYV422 ... _YVYU422): the instances of the tile kernels (sws_dev.h)
  * whose horizontal pass picks its samples from the packed bytes — k_sws_generic A / B / C to rgb24, bgr24 and the four 32-bit orders, k_sws_planar
- * A / B / C at both chroma widths, plain, SEMI, RANGE and DEEP — with their launches, k_sws_ident1_yuy2 (equal size to a packed RGB destination), the
+ * A / B / C at both chroma widths, plain, SEMI, RANGE and DEEP: every key of source class SWS_SRC_YUY2 (sws_dev.h: SwsKey; the key is sws.hip's) —
+ * with their launch, k_sws_ident1_yuy2 (equal size to a packed RGB destination), the
  * four unscaled special converters the reference has for these sources in one kernel (k_sws_yuy2_split: yuyvToYuv420Wrapper, uyvyToYuv420Wrapper, yuyvToYuv422Wrapper, uyvyToYuv422Wrapper,
  * swscale_unscaled.c:227-287 over yuyvtoyuv420_c ... uyvytoyuv422_c, rgb2rgb_template.c:854-928), and the two Tier-1 line entries
  * mi355_sws_yuy2ToY / _yuy2ToUV (yuy2ToY_c, yuy2ToUV_c, yvy2ToUV_c, uyvyToY_c, uyvyToUV_c, input.c:369-473) with their line kernels.  The context,
@@ -154,34 +155,7 @@ namespace {
 /* ---- the scaler from these sources: the tile instances ----------------------------------------------------------------------------------------
  * k_sws_generic / k_sws_planar with the pick converter in the staging round of hscale_tile_rgb (a 2-byte "pixel" for luma, a 4-byte one for chroma):
  * the staged line holds the picked bytes, so every instance has the LDS, the waves per SIMD and the workgroups per CU of its 8-bit yuv422p twin. */
-typedef SwsPxYuy2 PxY2;
-static_assert(stage_bytes<PxY2>() == STAGE_BYTES, "the twins' staging lines");
-
-template <int I, int DST> static void launch_generic_y2(dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
-{
-    constexpr SwsShape S = GENERIC_SHAPES[I];
-    hipLaunchKernelGGL((k_sws_generic<S.lcap, S.ccap, sws_waves(sws_lds_bytes(S.lcap, S.ccap, STAGE_BYTES)), PxY2, false, true, DST>), grid, dim3(NT), 0, s, d, frames);
-}
-template <int DST> static void launch_generic_y2(int i, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_frame *frames)
-{
-    if (i == 0) launch_generic_y2<0, DST>(grid, s, d, frames);
-    else if (i == 1) launch_generic_y2<1, DST>(grid, s, d, frames);
-    else launch_generic_y2<2, DST>(grid, s, d, frames);
-}
-/* form 0: three planes at CW = TW / 2, 1: at CW = TW, 2: a semi-planar destination; kind 0: plain, 1: RANGE, 2: DEEP (three planes only) */
-template <int I, bool RANGE, bool DEEP> static void launch_planar_y2(int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
-{
-    constexpr SwsShape S = PLANAR_SHAPES[I];
-    if (form == 0) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, PxY2, false, false, true, RANGE, DEEP>), grid, dim3(NT), 0, s, d, frames);
-    else if (form == 1) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW, PxY2, false, false, true, RANGE, DEEP>), grid, dim3(NT), 0, s, d, frames);
-    else if constexpr (!DEEP) hipLaunchKernelGGL((k_sws_planar<S.lcap, S.ccap, TW / 2, PxY2, true, false, true, RANGE, false>), grid, dim3(NT), 0, s, d, frames);
-}
-template <int I> static void launch_planar_y2(int kind, int form, dim3 grid, hipStream_t s, const SwsDev *d, const mi355_sws_planar_frame *frames)
-{
-    if (kind == 0) launch_planar_y2<I, false, false>(form, grid, s, d, frames);
-    else if (kind == 1) launch_planar_y2<I, true, false>(form, grid, s, d, frames);
-    else launch_planar_y2<I, false, true>(form, grid, s, d, frames);
-}
+static_assert(stage_bytes<SwsPxYuy2>() == STAGE_BYTES, "the twins' staging lines");
 
 /* ---- equal size to a packed RGB destination: k_sws_ident1's _1 form straight from the packed bytes ---------------------------------------------
  * The reference has no special converter from these sources to RGB: its scaler runs with identity horizontal filters and ONE vertical luma tap, and
@@ -288,60 +262,33 @@ __global__ void __launch_bounds__(NT) k_sws_ident1_yuy2(const SwsDev *cp, const 
 }
 }  // namespace
 
-void mi355_sws_launch_generic_yuy2(int i, int dst_format, dim3 grid, hipStream_t s, const void *d, const mi355_sws_frame *frames)
+bool mi355_sws_launch_yuy2(const SwsKey &key, const SwsOperands &op)
 {
-    const SwsDev *dev = static_cast<const SwsDev *>(d);
-    if (dst_format == 0) launch_generic_y2<DST_RGB24>(i, grid, s, dev, frames);
-    else if (dst_format == MI355_SWS_DST_BGR24) launch_generic_y2<DST_BGR24>(i, grid, s, dev, frames);
-    else launch_generic_y2<DST_RGB32>(i, grid, s, dev, frames);
-}
-void mi355_sws_launch_planar_yuy2(int i, int kind, int form, dim3 grid, hipStream_t s, const void *d, const mi355_sws_planar_frame *frames)
-{
-    const SwsDev *dev = static_cast<const SwsDev *>(d);
-    if (i == 0) launch_planar_y2<0>(kind, form, grid, s, dev, frames);
-    else if (i == 1) launch_planar_y2<1>(kind, form, grid, s, dev, frames);
-    else launch_planar_y2<2>(kind, form, grid, s, dev, frames);
-}
-void mi355_sws_launch_ident1_yuy2(int dst_format, dim3 grid, hipStream_t s, const void *d, const mi355_sws_frame *frames)
-{
-    const SwsDev *dev = static_cast<const SwsDev *>(d);
-    if (dst_format == 0) hipLaunchKernelGGL(k_sws_ident1_yuy2<DST_RGB24>, grid, dim3(NT), 0, s, dev, frames);
-    else if (dst_format == MI355_SWS_DST_BGR24) hipLaunchKernelGGL(k_sws_ident1_yuy2<DST_BGR24>, grid, dim3(NT), 0, s, dev, frames);
-    else hipLaunchKernelGGL(k_sws_ident1_yuy2<DST_RGB32>, grid, dim3(NT), 0, s, dev, frames);
+    if (key.src != SWS_SRC_YUY2) return false;
+    const SwsDev *dev = static_cast<const SwsDev *>(op.d);
+    if (key.kernel == SWS_KERNEL_YUY2_SPLIT) {
+        /* the kernel's own grid (op.grid.z: the pictures); the byte of a pair that is luma, chroma rows averaged in pairs to yuv420p */
+        const SwsDev &h = *static_cast<const SwsDev *>(op.h);
+        hipLaunchKernelGGL(k_sws_yuy2_split, dim3((h.srcW + YUY2_COLS - 1) / YUY2_COLS, (h.srcH + YUY2_ROWS - 1) / YUY2_ROWS, op.grid.z), dim3(NT), 0, op.s,
+                           sws_yuy2_luma(h.src_layout), h.planar == MI355_SWS_DST_YUV420P ? 1 : 0, h.srcW, h.srcH, static_cast<const mi355_sws_planar_frame *>(op.frames));
+        return true;
+    }
+    if (key.kernel == SWS_KERNEL_IDENT1_1)
+        return sws_pick_dst(key.dst, [&](auto dst) {
+            hipLaunchKernelGGL(k_sws_ident1_yuy2<decltype(dst)::value>, op.grid, dim3(NT), 0, op.s, dev, static_cast<const mi355_sws_frame *>(op.frames));
+            return true;
+        });
+    return sws_launch<sws_bit(SWS_SRC_YUY2), SWS_ALL_KINDS, SWS_ALL_DSTS>(key, op);
 }
 
-void mi355_sws_launch_yuy2_split(int luma_off, int c420, int srcW, int srcH, int nframes, hipStream_t s, const mi355_sws_planar_frame *frames)
-{
-    hipLaunchKernelGGL(k_sws_yuy2_split, dim3((srcW + YUY2_COLS - 1) / YUY2_COLS, (srcH + YUY2_ROWS - 1) / YUY2_ROWS, nframes), dim3(NT), 0, s,
-                       luma_off, c420, srcW, srcH, frames);
-}
-
-/* one line through a line kernel: nsrc source bytes in, nout planes of `width` bytes out */
 extern "C" void mi355_sws_yuy2ToY(uint8_t *dst, const uint8_t *src, int width, int layout)
 {
     if (width <= 0 || !sws_yuy2_src(layout)) return;
-    Arena &a = arena();
-    const size_t nsrc = (size_t)2 * width;
-    a.reserve(nsrc + (size_t)width + 64);
-    const size_t o_src = a.take(nsrc), o_d = a.take((size_t)width);
-    std::memcpy(a.h<uint8_t>(o_src), src, nsrc);
-    a.upload();
-    hipLaunchKernelGGL(k_sws_line_yuy2_y, dim3(1), dim3(NT), 0, a.stream, a.d<uint8_t>(o_d), a.d<const uint8_t>(o_src), width, sws_yuy2_luma(layout));
-    a.download();
-    std::memcpy(dst, a.h<uint8_t>(o_d), (size_t)width);
+    sws_line<1>(k_sws_line_yuy2_y, &dst, src, (size_t)2 * width, width, sws_yuy2_luma(layout));
 }
 extern "C" void mi355_sws_yuy2ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int width, int layout)
 {
     if (width <= 0 || !sws_yuy2_src(layout)) return;
-    Arena &a = arena();
-    const size_t nsrc = (size_t)4 * width;
-    a.reserve(nsrc + (size_t)2 * width + 96);
-    const size_t o_src = a.take(nsrc), o_u = a.take((size_t)width), o_v = a.take((size_t)width);
-    std::memcpy(a.h<uint8_t>(o_src), src, nsrc);
-    a.upload();
-    hipLaunchKernelGGL(k_sws_line_yuy2_uv, dim3(1), dim3(NT), 0, a.stream, a.d<uint8_t>(o_u), a.d<uint8_t>(o_v), a.d<const uint8_t>(o_src), width,
-                       sws_yuy2_u(layout), sws_yuy2_v(layout));
-    a.download();
-    std::memcpy(dstU, a.h<uint8_t>(o_u), (size_t)width);
-    std::memcpy(dstV, a.h<uint8_t>(o_v), (size_t)width);
+    uint8_t *const out[2] = { dstU, dstV };
+    sws_line<2>(k_sws_line_yuy2_uv, out, src, (size_t)4 * width, width, sws_yuy2_u(layout), sws_yuy2_v(layout));
 }

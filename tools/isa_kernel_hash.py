@@ -17,6 +17,8 @@ for name, desc in re.findall(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel",
     ins = [l for l in ins if l and not l.startswith(".")]
     # local labels carry the number of the function in the file (.LBB10_25): a symbol name, not part of the stream
     ins = [re.sub(r"\.L([A-Za-z]+)\d+_", r".L\1_", l) for l in ins]
+    # ... and so does the label of a long branch's s_getpc (.Lpost_getpc8): numbered through the file in the order the kernels are emitted
+    ins = [re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", l) for l in ins]
     r = dict(re.findall(r"\.amdhsa_(next_free_vgpr|next_free_sgpr|group_segment_fixed_size|private_segment_fixed_size) (\d+)", desc))
     # the instance: the demangled name without its namespace, return type and parameter list (the "(" that follows the template arguments)
     full = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "")
