@@ -96,6 +96,18 @@
  *                          stays the reference's).  With MI355_SWS_LINES=1 their two input converters go to mi355_sws_yuy2ToY / _yuy2ToUV,
  *                          the horizontal and output loops as for every other source.
  *                          The eight describers above keep declining these sources.
+ *   packed 4:2:2 destinations  yuyv422, uyvy422 and yvyu422 (c->yuv2packedX / 2 / 1 are yuv2yuyv422_X_c ... yuv2uyvy422_1_c; from 8-bit yuv422p / yuv420p at
+ *                          equal size the reference takes one of its four unscaled packers, yuv422pToYuy2Wrapper ... planarToUyvyWrapper) have the
+ *                          tenth describer, mi355_sws_describe_yuy2dst(), for mi355_sws_create_src_layout_range_depth(): from every source above,
+ *                          with the range read from the converters the context holds.  A context without banks whose source and destination are
+ *                          those of a packer is described with unscaled_special = 1 (the device's k_sws_yuy2_pack) for callers of the C ABI and,
+ *                          set outside the wrapped selectors, never bound.  The generic scaler's contexts are bound like those of a 32-bit source:
+ *                          whole pictures through mi355_swsfunc (described again at every picture; one the creators refuse stays the
+ *                          reference's).  With MI355_SWS_LINES=1 c->yuv2packedX / 2 / 1 go to mi355_sws_yuv2packed_X / _2 / _1 with the format (no
+ *                          tables), the input converters, horizontal loops and range converters as for the source.  Declined:
+ *                          SWS_FAST_BILINEAR scaled contexts, SWS_FULL_CHR_H_INT / _INP where the describers above decline them, alpha / YUVA,
+ *                          other sources, and contexts without banks that are not one of the four packers (the plain copy of a packed 4:2:2
+ *                          source to its own order; to another order the reference runs its scaler, and that context is taken).  The nine describers above keep declining these destinations.
  * The device is MI355_DEVICE (default 0), as for the decoder bridges.
  */
 #include <pthread.h>
@@ -216,7 +228,20 @@ static int source_of(const SwsContext *c, mi355_sws_src *s)
 /* ranged == MI355_ASK_PACKED (mi355_sws_describe_packed alone): the destination is bgr24 or one of the four 32-bit orders instead; no range either (an
  * RGB destination takes it into its tables) */
 #define MI355_ASK_PACKED 3
+/* ranged == MI355_ASK_YUY2DST (mi355_sws_describe_yuy2dst alone): the destination is yuyv422 / uyvy422 / yvyu422 instead, with or without range converters
+ * (a YUV destination) */
+#define MI355_ASK_YUY2DST 4
 static int generic_dst_r(const SwsContext *c, int ranged);
+/* the MI355_SWS_DST_* of a packed 4:2:2 destination, 0 for any other format */
+static int yuy2_dst_of(const SwsContext *c)
+{
+    switch (c->dstFormat) {
+    case AV_PIX_FMT_YUYV422: return MI355_SWS_DST_YUYV422;
+    case AV_PIX_FMT_UYVY422: return MI355_SWS_DST_UYVY422;
+    case AV_PIX_FMT_YVYU422: return MI355_SWS_DST_YVYU422;
+    default: return 0;
+    }
+}
 /* the MI355_SWS_DST_* of a packed destination beside rgb24, 0 for any other format.  The reference's RGB32 / BGR32 / RGB32_1 / BGR32_1 are
  * host-endian aliases of the four byte-order names: resolved here, once */
 static int packed_dst_of(const SwsContext *c)
@@ -264,6 +289,7 @@ static int generic_dst_r(const SwsContext *c, int ranged)
     if (c->hyscale_fast || c->hcscale_fast || ((!ranged || deep || packed) && (c->lumConvertRange || c->chrConvertRange)) || c->vChrDrop) return -1;
     if (!c->vLumFilter || !c->vChrFilter || !c->hLumFilter || !c->hChrFilter) return -1;
     if (packed) return packed_dst_of(c) && !isALPHA(c->srcFormat) ? packed_dst_of(c) : -1;
+    if (ranged == MI355_ASK_YUY2DST) return yuy2_dst_of(c) && !isALPHA(c->srcFormat) ? yuy2_dst_of(c) : -1;
     if (deep) {
         int bits;
         const int fmt = deep_dst(c, &bits);
@@ -639,6 +665,59 @@ int mi355_sws_describe_yuy2(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_s
     return 0;
 }
 
+/* ---- packed 4:2:2 destinations: yuyv422, uyvy422, yvyu422 ----------------------------------------------------------------------------------
+ * what mi355_sws_create_src_layout_range_depth takes for a live context TO one of the three formats (0), -1 for every other context — the nine
+ * describers above keep declining these destinations.  The generic scaler's contexts from every source of the describers above (three planes at 8 / 9 /
+ * 10 bits, NV12 / NV21, rgb24 / bgr24, the four 32-bit orders, the three packed 4:2:2 orders — each under the checks of its own describer), with the
+ * range the context's converters give (range_probe) and depth 8; the descriptor has the rgb24 form (vChr.n = dstH) and no tables.  A context without the
+ * vertical banks is one of the four unscaled packers — 8-bit yuv422p (whatever the flags) or yuv420p (the reference takes it under SWS_POINT /
+ * SWS_FAST_BILINEAR only, swscale_unscaled.c:1123-1139) to yuyv422 / uyvy422 at equal size: unscaled_special = 1, no banks; any other without them (the plain
+ * copy) is declined.  Declined too: SWS_FAST_BILINEAR scaled contexts, SWS_FULL_CHR_H_INT, a chroma line drop, a source
+ * with alpha */
+int mi355_sws_describe_yuy2dst(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *src_layout, int *dst_format, int *range, int *dst_depth)
+{
+    const int fmt = yuy2_dst_of(c);
+    int r = MI355_SWS_RANGE_NONE, layout = MI355_SWS_SRC_PLANAR;
+    if (!fmt || (isALPHA(c->srcFormat) && !rgb32_layout_of(c))) return -1;
+    if (!c->vLumFilter) {
+        if ((c->srcFormat != AV_PIX_FMT_YUV422P && c->srcFormat != AV_PIX_FMT_YUV420P) || fmt == MI355_SWS_DST_YVYU422 || !c->swscale || c->srcW != c->dstW ||
+            c->srcH != c->dstH || c->hLumFilter || c->hChrFilter || c->vChrFilter || c->lumConvertRange || c->chrConvertRange) return -1;
+        if (source_of(c, s) != 0) return -1;
+        memset(d, 0, sizeof(*d));
+        d->srcW = c->srcW; d->srcH = c->srcH; d->dstW = c->dstW; d->dstH = c->dstH;
+        d->chrSrcW = c->chrSrcW; d->chrSrcH = c->chrSrcH; d->chrDstW = c->chrDstW;
+        d->unscaled_special = 1;
+        *src_layout = layout; *dst_format = fmt; *range = r; *dst_depth = 8;
+        return 0;
+    }
+    r = range_probe(c);
+    if (r < 0) return -1;
+    if (rgb32_layout_of(c) || yuy2_layout_of(c)) {
+        /* the checks of mi355_sws_describe_rgb32 / mi355_sws_describe_yuy2 on the source side: no alpha is carried to these destinations */
+        layout = rgb32_layout_of(c) ? rgb32_layout_of(c) : yuy2_layout_of(c);
+        if (!c->vChrFilter || !c->hLumFilter || !c->hChrFilter) return -1;
+        if (c->hyscale_fast || c->hcscale_fast || c->vChrDrop || (c->flags & SWS_FULL_CHR_H_INT)) return -1;
+        if (c->chrSrcVSubSample != 0 || (c->chrSrcHSubSample & ~1) || c->srcBpc != 8 || c->readLumPlanar || c->readChrPlanar || c->readAlpPlanar || c->alpPixBuf) return -1;
+        if (rgb32_layout_of(c) ? rgb32_probe(c, layout, 0) != 0 : (c->chrSrcHSubSample != 1 || yuy2_probe(c, layout) != 0)) return -1;
+        memset(s, 0, sizeof(*s));
+        s->depth = 8; s->hsub = c->chrSrcHSubSample; s->vsub = 0;
+        memcpy(s->dither, ff_dither_8x8_128, sizeof(s->dither));
+        memset(d, 0, sizeof(*d));
+        d->srcW = c->srcW; d->srcH = c->srcH; d->dstW = c->dstW; d->dstH = c->dstH;
+        d->chrSrcW = c->chrSrcW; d->chrSrcH = c->chrSrcH; d->chrDstW = c->chrDstW;
+        d->hLum = (mi355_sws_filter){ c->hLumFilter, c->hLumFilterPos, c->hLumFilterSize, c->dstW };
+        d->hChr = (mi355_sws_filter){ c->hChrFilter, c->hChrFilterPos, c->hChrFilterSize, c->chrDstW };
+        d->vLum = (mi355_sws_filter){ c->vLumFilter, c->vLumFilterPos, c->vLumFilterSize, c->dstH };
+        d->vChr = (mi355_sws_filter){ c->vChrFilter, c->vChrFilterPos, c->vChrFilterSize, c->dstH };
+        *src_layout = layout; *dst_format = fmt; *range = r; *dst_depth = 8;
+        return 0;
+    }
+    if (describe_fmt_r(c, d, s, src_layout, dst_format, MI355_ASK_YUY2DST) != 0 || *dst_format != fmt || d->unscaled_special) return -1;
+    d->vChr.n = c->dstH;
+    *range = r; *dst_depth = 8;
+    return 0;
+}
+
 #ifndef MI355_SWS_DESCRIBE_ONLY
 static void t1_hscale16(SwsContext *c, int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
 {
@@ -885,10 +964,55 @@ static int init_yuy2(SwsContext *c)
     return 1;
 }
 
+/* yuv2packedX / 2 / 1 of a packed 4:2:2 context (yuv2yuyv422_X_c ... yuv2uyvy422_1_c): the format is read from the context at every call; no tables */
+static void t1_y2X(SwsContext *c, const int16_t *lumFilter, const int16_t **lumSrc, int lumFilterSize, const int16_t *chrFilter,
+                   const int16_t **chrUSrc, const int16_t **chrVSrc, int chrFilterSize, const int16_t **alpSrc, uint8_t *dest, int dstW, int y)
+{
+    (void)alpSrc; (void)y; n_calls++;
+    mi355_sws_yuv2packed_X(NULL, yuy2_dst_of(c), lumFilter, lumSrc, lumFilterSize, chrFilter, chrUSrc, chrVSrc, chrFilterSize, dest, dstW);
+}
+static void t1_y22(SwsContext *c, const int16_t *lumSrc[2], const int16_t *chrUSrc[2], const int16_t *chrVSrc[2], const int16_t *alpSrc[2],
+                   uint8_t *dest, int dstW, int yalpha, int uvalpha, int y)
+{
+    (void)alpSrc; (void)y; n_calls++;
+    mi355_sws_yuv2packed_2(NULL, yuy2_dst_of(c), lumSrc, chrUSrc, chrVSrc, dest, dstW, yalpha, uvalpha);
+}
+static void t1_y21(SwsContext *c, const int16_t *lumSrc, const int16_t *chrUSrc[2], const int16_t *chrVSrc[2], const int16_t *alpSrc,
+                   uint8_t *dest, int dstW, int uvalpha, int y)
+{
+    (void)alpSrc; (void)y; n_calls++;
+    mi355_sws_yuv2packed_1(NULL, yuy2_dst_of(c), lumSrc, chrUSrc, chrVSrc, dest, dstW, uvalpha);
+}
+/* the inner loops of a context of the generic scaler to a packed 4:2:2 destination (mi355_sws_describe_yuy2dst takes it): the input converters of its
+ * source, the horizontal loops, the range converters and the three packed loops.  The four unscaled packers have no inner loops */
+static int init_yuy2dst(SwsContext *c)
+{
+    mi355_sws_desc d;
+    mi355_sws_src s;
+    int layout, fmt, range, depth;
+    if (!yuy2_dst_of(c)) return 0;
+    /* (returning 1 for a context this describer declines is deliberate: no other describer takes these destinations) */
+    if (mi355_sws_describe_yuy2dst(c, &d, &s, &layout, &fmt, &range, &depth) != 0 || d.unscaled_special || !device_ready() || !c->hyScale || !c->hcScale) return 1;
+    if (!c->yuv2packedX || !c->yuv2packed2 || !c->yuv2packed1) return 1;
+    rgb_converters(c, layout);
+    rgb32_converters(c, layout, 0);
+    if (layout == MI355_SWS_SRC_YUYV422) { c->lumToYV12 = t1_yuyvToY; c->chrToYV12 = t1_yuyvToUV; }
+    else if (layout == MI355_SWS_SRC_UYVY422) { c->lumToYV12 = t1_uyvyToY; c->chrToYV12 = t1_uyvyToUV; }
+    else if (layout == MI355_SWS_SRC_YVYU422) { c->lumToYV12 = t1_yvyuToY; c->chrToYV12 = t1_yvyuToUV; }
+    c->hyScale = c->hcScale = s.depth > 8 ? t1_hscale16 : t1_hscale;
+    if (range > 0) {
+        c->lumConvertRange = range == MI355_SWS_RANGE_TO_JPEG ? t1_lumToJpeg : t1_lumFromJpeg;
+        c->chrConvertRange = range == MI355_SWS_RANGE_TO_JPEG ? t1_chrToJpeg : t1_chrFromJpeg;
+    }
+    c->yuv2packedX = t1_y2X; c->yuv2packed2 = t1_y22; c->yuv2packed1 = t1_y21;
+    return 1;
+}
+
 void ff_sws_init_mi355x(SwsContext *c)
 {
     mi355_sws_src s;
     int layout;
+    if (init_yuy2dst(c)) return;
     if (init_rgb32(c)) return;
     if (init_yuy2(c)) return;
     const int range = range_probe(c);
@@ -954,7 +1078,8 @@ typedef struct Bound {
     int depth;                    /* ... the bits of its planar destination: 8, or 9 / 10 (mi355_sws_describe_depth / mi355_sws_create_src_layout_range_depth) */
     int packed;                   /* ... MI355_SWS_DST_BGR24 ... _ABGR of a packed destination beside rgb24 (mi355_sws_describe_packed), else 0; planar is 0 then */
     int rgb32;                    /* 1: a 32-bit source (mi355_sws_describe_rgb32: layout, planar / packed, range and depth above are what it gave) ...;
-                                   * 2: a packed 4:2:2 source in the generic scaler (mi355_sws_describe_yuy2, the same fields; never alpha) */
+                                   * 2: a packed 4:2:2 source in the generic scaler (mi355_sws_describe_yuy2, the same fields; never alpha);
+                                   * 3: a packed 4:2:2 DESTINATION from any source (mi355_sws_describe_yuy2dst, the same fields; packed is its format, no tables) */
     int alpha;                    /* ... whose alpha goes to the 32-bit destination (mi355_sws_create_src_layout_alpha) */
     mi355_sws_ctx *dev;
     int failed;                   /* the device side does not take this context: the reference's function from now on */
@@ -1004,6 +1129,15 @@ static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
 {
     int planar = special ? 0 : planar_format(c), other = 0, layout = MI355_SWS_SRC_PLANAR, range = MI355_SWS_RANGE_NONE, depth = 8, packed = 0;
     int rgb32 = 0, alpha = 0;
+    if (!special && yuy2_dst_of(c)) {
+        /* a packed 4:2:2 destination: one describer for every source it comes from.  Only the generic scaler's contexts get here (the four unscaled
+         * packers are set without a selector) */
+        mi355_sws_desc d;
+        mi355_sws_src s;
+        int fmt;
+        if (mi355_sws_describe_yuy2dst(c, &d, &s, &layout, &fmt, &range, &depth) != 0 || d.unscaled_special) return real;
+        rgb32 = 3; other = 1; packed = fmt;
+    } else
     if (!special && rgb32_layout_of(c)) {
         /* a 32-bit source: one describer for every destination it goes to */
         mi355_sws_desc d;
@@ -1077,7 +1211,8 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
     mi355_sws_desc d32;
     mi355_sws_src s32;
     int l32 = 0, f32 = 0, r32 = 0, dp32 = 8, a32 = 0;
-    const int rgb32_ok = b && b->rgb32 && (b->rgb32 == 2 ? mi355_sws_describe_yuy2(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 && !d32.unscaled_special
+    const int rgb32_ok = b && b->rgb32 && (b->rgb32 == 3 ? mi355_sws_describe_yuy2dst(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 && !d32.unscaled_special :
+                                           b->rgb32 == 2 ? mi355_sws_describe_yuy2(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 && !d32.unscaled_special
                                                          : mi355_sws_describe_rgb32(c, &d32, &s32, &l32, &f32, &r32, &dp32, &a32) == 0) && l32 == b->layout &&
                          f32 == (b->packed ? b->packed : b->planar) && r32 == b->range && dp32 == b->depth && a32 == b->alpha;
     const int planar_ok = b && b->planar && dstStride[1] > 0 && (semi || dstStride[2] > 0) && (b->rgb32 ? rgb32_ok :
@@ -1088,11 +1223,12 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
     const int other_ok = !b || !b->other || (b->rgb32 ? rgb32_ok : (b->planar || (b->packed ? fmt_format_r(c, &s_now, b->special, &l_now, MI355_ASK_PACKED) == b->packed
                                                                                                   : fmt_format(c, &s_now, b->special, &l_now) == 0)));
     /* an NV12 / NV21 source has two planes: srcStride[2] is not looked at; a packed rgb24 / bgr24, 32-bit or 4:2:2 source has one */
-    const int one_plane = b && (b->layout == MI355_SWS_SRC_RGB24 || b->layout == MI355_SWS_SRC_BGR24 || b->rgb32);
+    const int one_plane = b && (b->layout == MI355_SWS_SRC_RGB24 || b->layout == MI355_SWS_SRC_BGR24 || b->rgb32 == 1 || b->rgb32 == 2 ||
+                                (b->layout >= MI355_SWS_SRC_RGBA && b->layout <= MI355_SWS_SRC_ABGR) || (b->layout >= MI355_SWS_SRC_YUYV422 && b->layout <= MI355_SWS_SRC_YVYU422));
     if (b && !b->failed && srcSliceY == 0 && srcSliceH == c->srcH &&
         srcStride[0] > 0 && (one_plane || srcStride[1] > 0) && (b->layout || srcStride[2] > 0) && dstStride[0] > 0 && (!b->planar || planar_ok) && other_ok) {
         if (b->dev && !b->busy && !b->planar && !b->packed && (memcmp(b->y_table, c->yuvTable, 1024) || b->gv0 != c->table_gV[0])) { mi355_sws_destroy(b->dev); b->dev = NULL; }
-        if (b->dev && !b->busy && b->packed) {
+        if (b->dev && !b->busy && b->packed && b->rgb32 != 3) {      /* (a packed 4:2:2 destination has no tables) */
             /* the tables in the form the device context was built from (a 32-bit order's first 1024 table BYTES are 256 entries below every colour) */
             mi355_sws_luts now;
             luts_packed(c, b->packed, &now);
@@ -1125,7 +1261,8 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
             } else if (b->planar) {
                 if (device_ready() && mi355_sws_describe_planar(c, &d, &fmt) == 0) b->dev = mi355_sws_create_planar(&d, fmt);
             } else if (device_ready() && describe(c, &d, b->special) == 0) b->dev = mi355_sws_create(&d);
-            if (b->dev && b->packed) { memcpy(b->y_table, d.luts.y_table, 1024); b->gv0 = c->table_gV[0]; }
+            if (b->dev && b->rgb32 == 3) ;
+            else if (b->dev && b->packed) { memcpy(b->y_table, d.luts.y_table, 1024); b->gv0 = c->table_gV[0]; }
             else if (b->dev && !b->planar) { memcpy(b->y_table, c->yuvTable, 1024); b->gv0 = c->table_gV[0]; }
             else if (!b->dev) b->failed = 1;
         }

@@ -11,7 +11,9 @@
  * the source's alpha carried to a 32-bit destination where asked for (rgbaToA_c / abgrToA_c and the hasAlpha forms of the packed templates); and
  * from packed 4:2:2 yuyv422 / uyvy422 / yvyu422 sources (the byte picks yuy2ToY_c ... uyvyToUV_c input.c:369-473 in front of hyScale / hcScale) to all
  * of these, with the reference's four unscaled converters yuyv422 / uyvy422 -> yuv420p / yuv422p (yuyvToYuv420Wrapper ... uyvyToYuv422Wrapper
- * swscale_unscaled.c:227-287).
+ * swscale_unscaled.c:227-287); and TO packed 4:2:2 yuyv422 / uyvy422 / yvyu422 (yuv2422_X / _2 / _1_c_template output.c:451-582), from every source
+ * rgb24 is written from, with range conversion, and the reference's four unscaled packers yuv422p / yuv420p -> yuyv422 / uyvy422
+ * (yuv422pToYuy2Wrapper, yuv422pToUyvyWrapper, planarToYuy2Wrapper, planarToUyvyWrapper swscale_unscaled.c:179-225).
  *
  * The reference keeps these behind function pointers of the (private) SwsContext
  * (libswscale/swscale_internal.h:253-540): hyScale/hcScale :526-531, yuv2plane1/yuv2planeX/
@@ -64,7 +66,7 @@ typedef struct mi355_sws_ctx mi355_sws_ctx;   /* descriptor + filter banks resid
 typedef struct mi355_sws_frame {
     const uint8_t *src[3];
     int src_stride[3];
-    uint8_t *dst;          /* packed RGB24 (or bgr24 / rgba / bgra / argb / abgr: MI355_SWS_DST_BGR24 ... below) */
+    uint8_t *dst;          /* packed RGB24 (or bgr24 / rgba / bgra / argb / abgr: MI355_SWS_DST_BGR24 ... below; or yuyv422 / uyvy422 / yvyu422: MI355_SWS_DST_YUYV422 ...) */
     int dst_stride;
 } mi355_sws_frame;
 
@@ -94,7 +96,8 @@ enum {
     MI355_SWS_K_PLANAR_C = 8,     /* ... 48 / 48 */
     MI355_SWS_K_NV12_PACK = 9,    /* the unscaled yuv420p -> NV12 / NV21 packer (k_sws_nv12_pack); scaled NV12 / NV21 contexts report PLANAR_A / B / C */
     MI355_SWS_K_NV12_SPLIT = 10,  /* the unscaled NV12 / NV21 -> yuv420p splitter (k_sws_nv12_split); scaled NV12 / NV21 SOURCES report the values above */
-    MI355_SWS_K_YUY2_SPLIT = 11   /* the unscaled yuyv422 / uyvy422 -> yuv420p / yuv422p splitter (k_sws_yuy2_split) */
+    MI355_SWS_K_YUY2_SPLIT = 11,  /* the unscaled yuyv422 / uyvy422 -> yuv420p / yuv422p splitter (k_sws_yuy2_split) */
+    MI355_SWS_K_YUY2_PACK = 12    /* the unscaled yuv422p / yuv420p -> yuyv422 / uyvy422 packer (k_sws_yuy2_pack); scaled contexts to these destinations report the values above */
 };
 typedef struct mi355_sws_plan_info {
     int kernel;                   /* MI355_SWS_K_* */
@@ -341,6 +344,52 @@ int mi355_sws_dest_depth(const mi355_sws_ctx *ctx);   /* 8 / 9 / 10, -1 bad argu
  * SWS_FULL_CHR_H_INT, rgbToRgbWrapper, and a range or a 9 / 10-bit depth with these destinations. */
 enum { MI355_SWS_DST_BGR24 = 32, MI355_SWS_DST_RGBA = 33, MI355_SWS_DST_BGRA = 34, MI355_SWS_DST_ARGB = 35, MI355_SWS_DST_ABGR = 36 };
 
+/* ---- packed 4:2:2 destinations: yuyv422 / uyvy422 / yvyu422 (what capture, SDI and display pipelines take back; yuv2422_X / _2 / _1_c_template
+ * output.c:451-582 behind c->yuv2packedX / 2 / 1, and the four unscaled packers yuv422pToYuy2Wrapper / yuv422pToUyvyWrapper / planarToYuy2Wrapper /
+ * planarToUyvyWrapper swscale_unscaled.c:179-225, :1123-1139) ----
+ * The names give the byte order IN MEMORY, per group of four bytes covering pixels 2i and 2i + 1, as for the sources:
+ *   yuyv422  Y1 U Y2 V      yvyu422  Y1 V Y2 U      uyvy422  U Y1 V Y2
+ * mi355_sws_create_src_layout_range_depth and the creators that forward to it take the three values as dst_format with every source the rgb24
+ * destination takes: src_layout 0, 1, 2, 4, 5, 8 .. 11 and 16 .. 18, depth 8 / 9 / 10 at 4:2:0 / 4:2:2 / 4:4:4; mi355_sws_create_src_layout_alpha with
+ * alpha 1 refuses them (NULL and a message).  37 .. 47 and 51 and up stay refused.  The descriptor is the reference's for that context and has the form
+ * of the rgb24 one: chrDstW = AV_CEIL_RSHIFT(dstW, 1), vChr.n = dstH; the LUTs are not read.
+ * Twin rule: such a context has the plan (GENERIC_A / B / C, IDENT1_1 / _X), the instance and the refusals of the rgb24-destination context of the same
+ * descriptor and source — NULL and a message exactly where that twin's tiles cannot hold the lines — with ONE exception: a packed-RGB source at equal
+ * size IS a context of the reference's scaler to these destinations (to rgb24 it is a copy or rgbToRgbWrapper), so the "scales neither way" refusal
+ * does not apply and such a context runs the tile kernel.
+ * Range: these are YUV destinations, so range 1 / 2 is accepted (mi355_sws_create_src_layout_range's formulas on the lines of the LDS tile between the
+ * two passes, over dstW luma and chrDstW chroma samples); such a context has the banks of its same-range twin.  dst_depth must be 8.
+ * The arithmetic, 32 bit, per pair i (luma samples 2i and 2i + 1, chroma sample i); the form is chosen as for the packed RGB destinations
+ * (one luma tap and at most two chroma taps: _1; two and two: _2; otherwise X):
+ *   X    each of Y1, Y2, U, V is ((1 << 18) + sum s_j * f_j) >> 19; if (Y1 | Y2 | U | V) & 0x100 all four are clipped to 0 .. 255, otherwise the four
+ *        values are stored as they are, truncated to a byte (the reference's rule: 600 has bit 9 but not bit 8 and is stored as 88)
+ *   _2   (a * (4096 - alpha) + b * alpha) >> 19, always clipped
+ *   _1   luma >> 7; chroma >> 7 for uvalpha < 2048, else (u0 + u1) >> 8; always clipped
+ * Frames stay mi355_sws_frame — ONE packed destination plane — through mi355_sws_scale / mi355_sws_scale_frames_dev; the planar entry points return -1.
+ * A row holds 4 * ((dstW + 1) >> 1) bytes: all of them are written and no byte behind them.  With an odd dstW the last group's second luma byte is 0
+ * in all three forms, with and without a range (the reference computes it from the sample behind the line of its zero-allocated line buffer, which
+ * neither the horizontal scaler nor the range converter touches).  The destination has no alignment demand: a full tile (128 pixels) of a row whose
+ * pointer and stride are multiples of 16 leaves from registers in 16-byte pieces, eight pixels a thread; every other tile goes through LDS rows and
+ * leaves in 16-byte, 4-byte or single-byte pieces as pointer, stride and row length allow.  The Tier-1 host entry returns -1 for a stride below the row.
+ * mi355_sws_destination reports the format, planes = 1 and chr_bytes = chr_rows = 0; mi355_sws_dest_depth 8; mi355_sws_range the range;
+ * mi355_sws_plan the twin's values.
+ * The four unscaled packers: desc->unscaled_special = 1 with src_layout 0, depth 8, source shifts 1,0 (yuv422pToYuy2Wrapper / yuv422pToUyvyWrapper, any
+ * flags) or 1,1 (planarToYuy2Wrapper / planarToUyvyWrapper: the reference takes them under SWS_POINT / SWS_FAST_BILINEAR only) to
+ * MI355_SWS_DST_YUYV422 or _UYVY422 (the reference has no wrapper to yvyu422) — srcW == dstW, srcH == dstH, no banks, range 0; every other special
+ * combination with these destinations gets NULL and a message.  Byte picks only, chroma of row y from chroma row y >> vsub; mi355_sws_plan reports
+ * MI355_SWS_K_YUY2_PACK.  The reference's loop writes two groups a step — G = 2 * ceil((srcW >> 1) / 2) groups on a row; the device writes
+ * min(G, (srcW + 1) >> 1) groups and never past the row:
+ *   srcW % 4 == 0 or 2   srcW / 2 groups (at remainder 2 the reference's extra group BEHIND the row is not reproduced)
+ *   srcW % 4 == 1        (srcW - 1) / 2 groups: the last pixel stays untouched, as in the reference
+ *   srcW % 4 == 3        (srcW + 1) / 2 groups: the last group's second luma byte is the source byte at x = srcW, as the reference reads it — the
+ *                        caller keeps that one byte readable on the last line too; it is the only read behind a width (the last group's chroma is
+ *                        sample (srcW - 1) / 2, inside the chroma width)
+ * A plane on 16-byte multiples is fetched in aligned 16-byte pieces over its stride, as everywhere else.
+ * A packed 4:2:2 source to ANOTHER packed 4:2:2 order at equal size is a context of the reference's scaler (banks of one tap each: it has no converter
+ * between the orders) and has its twin's plan, MI355_SWS_K_IDENT1_1 straight from the packed bytes; to the SAME order the reference copies.
+ * Not taken (the reference's): 9 / 10 / 16-bit packed YUV (y210 and kin), a YUVA source's alpha, SWS_FAST_BILINEAR scaled contexts and the plain copy. */
+enum { MI355_SWS_DST_YUYV422 = 48, MI355_SWS_DST_UYVY422 = 49, MI355_SWS_DST_YVYU422 = 50 };
+
 /* ---- the individual inner loops (Tier 1, host pointers), argument lists of the reference's
  * function-pointer types minus the SwsContext ------------------------------------------------ */
 /* hScale8To15_c swscale.c:133-147 (c->hyScale / c->hcScale) */
@@ -393,7 +442,9 @@ int mi355_sws_yuv2rgb_c_24_rgb(const mi355_sws_luts *luts, int dstW, const uint8
 /* the same trio and slice converter for any packed destination: dst_format 0 (rgb24: the bytes of the four entries above) or
  * MI355_SWS_DST_BGR24 ... _ABGR (yuv2bgr24_X_c ..., yuv2rgba32_X_c ... and their _2 / _1 forms; yuv2rgb_c_24_bgr yuv2rgb.c:366-394, yuv2rgb_c_32
  * :237-265); any other value does nothing (the slice entry returns -1).  dest holds (dstW + 1) >> 1 pairs — 6 bytes each, 8 for a 32-bit order —
- * as the reference's loops write them; luts in the form the creators take */
+ * as the reference's loops write them; luts in the form the creators take.
+ * MI355_SWS_DST_YUYV422 / _UYVY422 / _YVYU422 (yuv2yuyv422_X_c ..., output.c:451-582): dest receives (dstW + 1) >> 1 groups of 4 bytes, luts is not
+ * read and may be NULL; the slice entry returns -1 for these values */
 void mi355_sws_yuv2packed_X(const mi355_sws_luts *luts, int dst_format, const int16_t *lumFilter, const int16_t **lumSrc, int lumFilterSize,
                             const int16_t *chrFilter, const int16_t **chrUSrc, const int16_t **chrVSrc, int chrFilterSize,
                             uint8_t *dest, int dstW);

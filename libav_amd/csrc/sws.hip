@@ -9,13 +9,15 @@
  * packed 32-bit rgba / bgra / argb / abgr SOURCES to all of these, with the source's alpha carried to a 32-bit destination where the caller asks for it
  * (mi355_sws_create_src_layout_alpha; their instances, line kernels and line entries are sws_rgb32.hip's); and packed 4:2:2 yuyv422 / uyvy422 / yvyu422
  * SOURCES to all of these, with the unscaled yuyv422 / uyvy422 -> yuv420p / yuv422p splitter (their tile instances, k_sws_ident1_yuy2, k_sws_yuy2_split
- * and the line entries mi355_sws_yuy2ToY / _yuy2ToUV are sws_yuy2.hip's).  This file:
+ * and the line entries mi355_sws_yuy2ToY / _yuy2ToUV are sws_yuy2.hip's); and packed 4:2:2 yuyv422 / uyvy422 / yvyu422 DESTINATIONS from every one of these
+ * sources wherever rgb24 is written, also with range conversion, with the unscaled yuv422p / yuv420p -> yuyv422 / uyvy422 packer (yuv2422_X / _2 / _1_c_template
+ * output.c:451-582; their DST_YUY2 instances and k_sws_yuy2_pack are sws_yuy2dst.hip's).  This file:
  * the context, the plan (which kernel a context gets) and the entry points of include/mi355_sws.h.  The device side is sws_dev.h:
  * k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1, k_sws_nv12_pack, k_sws_nv12_split and the k_sws_line_* kernels of the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
  * Launches: sws_key() names a context's instance once (sws_dev.h: SwsKey), sws_run() hands the key to the file that compiles that instance — here
  * the plain and RANGE instances of k_sws_planar and the rgb24 destination of k_sws_generic / k_sws_ident1 / k_sws_c24 for the four classic source
- * classes; sws_deep.hip, sws_packed.hip, sws_rgb32.hip and sws_yuy2.hip hold the rest, one launch function each — and every file maps the key to its
+ * classes; sws_deep.hip, sws_packed.hip, sws_rgb32.hip, sws_yuy2.hip and sws_yuy2dst.hip hold the rest, one launch function each — and every file maps the key to its
  * instance through the one dispatcher sws_launch() of sws_dev.h.
  */
 #include "mi355_rt.h"
@@ -133,6 +135,13 @@ static bool ctx_source(mi355_sws_ctx *c, const mi355_sws_src *src)
 /* a packed destination other than rgb24: bgr24 or one of the four 32-bit orders */
 static bool packed_dst(int dst_format) { return dst_format >= MI355_SWS_DST_BGR24 && dst_format <= MI355_SWS_DST_ABGR; }
 static int packed_bpp(const SwsDev &h) { return h.packed >= MI355_SWS_DST_RGBA ? 4 : 3; }
+/* a packed 4:2:2 destination: yuyv422 / uyvy422 / yvyu422 (a YUV destination in ONE plane: it converts the range, and its instances are sws_yuy2dst.hip's) */
+static bool yuy2_dst(int dst_format) { return sws_yuy2_dst(dst_format); }
+static bool yuy2_dst(const SwsDev &h) { return sws_yuy2_dst(h.packed); }
+/* a destination of ONE packed plane, for the creators: everything but the planar and semi-planar formats */
+static bool one_plane_dst(int dst_format) { return dst_format == 0 || packed_dst(dst_format) || yuy2_dst(dst_format); }
+/* groups of four bytes the unscaled packer writes to a row: the reference's two-at-a-time loop, held inside the row (include/mi355_sws.h) */
+static int yuy2_pack_groups(const SwsDev &h) { const int g = 2 * (((h.srcW >> 1) + 1) >> 1), r = (h.srcW + 1) >> 1; return g < r ? g : r; }
 /* a packed RGB source: rgb24 / bgr24, or one of the four 32-bit orders (rgb32_src: its tile instances are launched from sws_rgb32.hip) */
 static bool rgb32_src(const SwsDev &h) { return sws_rgb32_src(h.src_layout); }
 static bool packed_rgb(const SwsDev &h) { return h.src_layout == MI355_SWS_SRC_RGB24 || h.src_layout == MI355_SWS_SRC_BGR24 || rgb32_src(h); }
@@ -223,6 +232,8 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
     SwsDev &h = c->h;
     /* bgr24 / rgba / bgra / argb / abgr: an rgb24 context in everything but the store (the order's byte selector is read by the 32-bit instances only) */
     if (!planar && packed_dst(dst_format)) { h.packed = dst_format; h.dst_sel = dst_format >= MI355_SWS_DST_RGBA ? sws_rgb32_sel(dst_format) : 0; }
+    /* yuyv422 / uyvy422 / yvyu422: an rgb24 context too in everything but the vertical pass's store (the order's byte selector is read by the DST_YUY2 instances) */
+    if (!planar && yuy2_dst(dst_format)) { h.packed = dst_format; h.dst_sel = sws_yuy2_dst_sel(dst_format); }
     h.range = range;
     h.rng_l = range_map(range, false); h.rng_c = range_map(range, true);      /* (read by the RANGE instances only) */
     if (dst_depth > 8) {
@@ -321,6 +332,17 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
         }
         ok = !h.special && desc->hLum.coef && desc->hLum.pos && desc->hChr.coef && desc->hChr.pos && desc->vLum.coef && desc->vLum.pos &&
              desc->vChr.coef && desc->vChr.pos && h.chrDstW == (h.dstW + (1 << h.hshift) - 1) >> h.hshift;
+    } else if (h.special && yuy2_dst(h)) {
+        /* the four unscaled packers (yuv422pToYuy2Wrapper, yuv422pToUyvyWrapper, planarToYuy2Wrapper, planarToUyvyWrapper): three planes of bytes at 4:2:2 or
+         * 4:2:0 (ctx_source has refused 4:4:4 and deeper samples) to yuyv422 / uyvy422 — none to yvyu422 — at equal size, no range */
+        if (h.src_layout != MI355_SWS_SRC_PLANAR || dst_format == MI355_SWS_DST_YVYU422 || range != MI355_SWS_RANGE_NONE || h.srcW != h.dstW || h.srcH != h.dstH ||
+            h.chrDstW != (h.dstW + 1) >> 1) {
+            std::fprintf(stderr, "mi355dsp: %s: the unscaled packers to a packed 4:2:2 destination are 8-bit yuv422p / yuv420p -> yuyv422 / uyvy422 at equal size "
+                         "(layout %d, destination %d, range %d, %dx%d -> %dx%d, chrDstW %d)\n", who, h.src_layout, dst_format, range, h.srcW, h.srcH, h.dstW, h.dstH, h.chrDstW);
+            delete c;
+            return nullptr;
+        }
+        return ctx_upload(c);
     } else if (h.special) return ctx_upload(c);
     int lines[2] = { 1, 1 };
     if (!ok || desc->hLum.n != h.dstW || desc->hChr.n != h.chrDstW || desc->vLum.n != h.dstH || desc->vChr.n != h.chrDstH ||
@@ -330,7 +352,8 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
         return nullptr;
     }
     h.lum_lines = lines[0]; h.chr_lines = lines[1];
-    if (packed_rgb(h) && !planar && ident1_shape(h)) {
+    /* (to a packed 4:2:2 destination the reference does build that context: it runs the tile kernel) */
+    if (packed_rgb(h) && !planar && !yuy2_dst(h) && ident1_shape(h)) {
         /* rgb in, rgb out, nothing scaled: the reference never runs its scaler on that (a copy, or rgbToRgbWrapper) */
         std::fprintf(stderr, "mi355dsp: %s: an %s source to rgb24 without scaling is not a context of the scaler\n", who, packed_name);
         delete c;
@@ -371,13 +394,13 @@ extern "C" mi355_sws_ctx *mi355_sws_create_planar(const mi355_sws_desc *desc, in
 extern "C" mi355_sws_ctx *mi355_sws_create_src(const mi355_sws_desc *desc, const mi355_sws_src *src, int dst_format)
 {
     if (!creator_args("mi355_sws_create_src", desc, src)) return nullptr;
-    return ctx_create(desc, src, dst_format != 0 && !packed_dst(dst_format), dst_format, "mi355_sws_create_src");
+    return ctx_create(desc, src, !one_plane_dst(dst_format), dst_format, "mi355_sws_create_src");
 }
 extern "C" mi355_sws_ctx *mi355_sws_create_src_layout(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format)
 {
     if (!creator_args("mi355_sws_create_src_layout", desc, src)) return nullptr;
     if (!creator_layout("mi355_sws_create_src_layout", src_layout)) return nullptr;
-    return ctx_create(desc, src, dst_format != 0 && !packed_dst(dst_format), dst_format, "mi355_sws_create_src_layout", src_layout);
+    return ctx_create(desc, src, !one_plane_dst(dst_format), dst_format, "mi355_sws_create_src_layout", src_layout);
 }
 extern "C" int mi355_sws_source_layout(const mi355_sws_ctx *c) { return c ? c->h.src_layout : -1; }
 extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_alpha(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format, int alpha)
@@ -412,7 +435,8 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range(const mi355_sws_desc
         std::fprintf(stderr, "mi355dsp: mi355_sws_create_src_layout_range: no unscaled special converter converts the range\n");
         return nullptr;
     }
-    return ctx_create(desc, src, true, dst_format, "mi355_sws_create_src_layout_range", src_layout, range);
+    /* (a packed 4:2:2 destination is a YUV destination in one plane: the rgb24 form of the context, with the range) */
+    return ctx_create(desc, src, !yuy2_dst(dst_format), dst_format, "mi355_sws_create_src_layout_range", src_layout, range);
 }
 extern "C" int mi355_sws_range(const mi355_sws_ctx *c) { return c ? c->h.range : -1; }
 extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range_depth(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, int dst_format, int range,
@@ -467,10 +491,11 @@ static int sws_kernel(const SwsDev &h)
     static_assert(MI355_SWS_K_GENERIC_C == MI355_SWS_K_GENERIC_A + 2 && MI355_SWS_K_PLANAR_C == MI355_SWS_K_PLANAR_A + 2, "A / B / C follow each other");
     if (h.planar && h.special) return yuy2_src(h) ? MI355_SWS_K_YUY2_SPLIT : (h.src_layout ? MI355_SWS_K_NV12_SPLIT : MI355_SWS_K_NV12_PACK);
     if (h.planar) return MI355_SWS_K_PLANAR_A + instance(PLANAR_SHAPES);
-    if (h.special) return MI355_SWS_K_C24;
+    if (h.special) return yuy2_dst(h) ? MI355_SWS_K_YUY2_PACK : MI355_SWS_K_C24;
     /* a context that does not scale: straight from the source bytes (k_sws_ident1; MI355_SWS_NO_IDENT1=1, developer switch: through the tile all the same) */
     static const bool no_ident1 = std::getenv("MI355_SWS_NO_IDENT1") != nullptr;
-    if (!no_ident1 && ident1_shape(h) && !packed_rgb(h) && !(yuy2_src(h) && h.vcs > 2))      /* (a packed 4:2:2 source has the _1 form only: chroma on every line) */
+    /* (a context that converts the range — to a packed 4:2:2 destination only — goes through the tile: the conversion sits between its two passes) */
+    if (!no_ident1 && ident1_shape(h) && !packed_rgb(h) && !(yuy2_src(h) && h.vcs > 2) && !h.range)      /* (a packed 4:2:2 source has the _1 form only: chroma on every line) */
         return h.vcs <= 2 ? MI355_SWS_K_IDENT1_1 : MI355_SWS_K_IDENT1_X;      /* packed_mode() 1 / the X template */
     return MI355_SWS_K_GENERIC_A + instance(GENERIC_SHAPES);
 }
@@ -519,7 +544,7 @@ extern "C" int mi355_sws_destination(const mi355_sws_ctx *c, mi355_sws_dest_info
 
 /* ---- launches --------------------------------------------------------------------------------------------------------------------------- */
 /* the destination form of the packed kernels for a dst_format (0: rgb24, MI355_SWS_DST_BGR24 ... _ABGR) */
-static int dst_form(int dst_format) { return !dst_format ? DST_RGB24 : (dst_format == MI355_SWS_DST_BGR24 ? DST_BGR24 : DST_RGB32); }
+static int dst_form(int dst_format) { return !dst_format ? DST_RGB24 : (dst_format == MI355_SWS_DST_BGR24 ? DST_BGR24 : (sws_yuy2_dst(dst_format) ? DST_YUY2 : DST_RGB32)); }
 
 /* the launch key (sws_dev.h: SwsKey) of a context whose kernel is k = sws_kernel(): the one place where the context's fields become the key's codes */
 static SwsKey sws_key(const mi355_sws_ctx *c, int k)
@@ -531,6 +556,7 @@ static SwsKey sws_key(const mi355_sws_ctx *c, int k)
     else if (k == MI355_SWS_K_C24) key.kernel = h.src_vsub ? SWS_KERNEL_C24 : SWS_KERNEL_C24_422;
     else if (k == MI355_SWS_K_IDENT1_1) key.kernel = SWS_KERNEL_IDENT1_1;
     else if (k == MI355_SWS_K_IDENT1_X) key.kernel = SWS_KERNEL_IDENT1_X;
+    else if (k == MI355_SWS_K_YUY2_PACK) key.kernel = SWS_KERNEL_YUY2_PACK;
     else key.kernel = SWS_KERNEL_YUY2_SPLIT;
     key.src = rgb32_src(h) ? SWS_SRC_RGB32 : yuy2_src(h) ? SWS_SRC_YUY2 : packed_rgb(h) ? SWS_SRC_RGB24 : h.src_layout ? SWS_SRC_NV : h.depth > 8 ? SWS_SRC_P16 : SWS_SRC_P8;
     key.form = semi_planar(h) ? SWS_FORM_SEMI : (h.hshift ? SWS_FORM_HALF : SWS_FORM_FULL);
@@ -545,13 +571,14 @@ static dim3 key_grid(const SwsKey &key, const SwsDev &h, int nframes)
     case SWS_KERNEL_GENERIC: case SWS_KERNEL_PLANAR: return sws_tile_grid(h, nframes);
     case SWS_KERNEL_IDENT1_1: case SWS_KERNEL_IDENT1_X: return sws_ident1_grid(h, nframes);
     case SWS_KERNEL_C24: case SWS_KERNEL_C24_422: return sws_c24_grid(h.dstW, h.srcH, nframes);
-    default: return dim3(1, 1, nframes);        /* k_sws_yuy2_split: the tile is its file's, the pictures are z */
+    default: return dim3(1, 1, nframes);        /* k_sws_yuy2_split, k_sws_yuy2_pack: the tile is its file's, the pictures are z */
     }
 }
 /* the launch of a key by the file that holds its instance; this file: the plain and RANGE instances of k_sws_planar and the rgb24 destination of the
  * packed kernels, of the four classic source classes */
 static bool sws_run(const SwsKey &key, const SwsOperands &op)
 {
+    if (key.dst == DST_YUY2) return mi355_sws_launch_yuy2dst(key, op);         /* (from every source class) */
     if (key.src == SWS_SRC_RGB32) return mi355_sws_launch_rgb32(key, op);
     if (key.src == SWS_SRC_YUY2) return mi355_sws_launch_yuy2(key, op);
     if (key.kernel == SWS_KERNEL_PLANAR && key.kind == SWS_KIND_DEEP) return mi355_sws_launch_deep(key, op);
@@ -630,7 +657,9 @@ static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int
     const bool rgb = packed_rgb(h) || yuy2_src(h);
     const int bpx = yuy2_src(h) ? 2 : src_bpx(h);
     if (rgb32_src(h) && (!src[0] || ((reinterpret_cast<uintptr_t>(src[0]) | (uintptr_t)src_stride[0]) & 3))) return -1;
-    const int nsrc = rgb ? 1 : (h.src_layout ? 2 : 3), tail = rgb && h.src_hsub && (h.srcW & 1) ? bpx : 0;
+    /* the packer to a packed 4:2:2 destination: with srcW % 4 == 3 its last group takes the luma byte behind each row in the same way */
+    const bool pack3 = h.special && yuy2_dst(h) && (h.srcW & 3) == 3;
+    const int nsrc = rgb ? 1 : (h.src_layout ? 2 : 3), tail = pack3 ? 1 : (rgb && h.src_hsub && (h.srcW & 1) ? bpx : 0);
     const int w[3] = { rgb ? bpx * h.srcW : h.srcW * B, rgb ? 0 : (h.src_layout ? 2 * h.chrSrcW : h.chrSrcW * B), h.src_layout ? 0 : h.chrSrcW * B },
               ph[3] = { h.srcH, h.chrSrcH, h.chrSrcH };
     for (int p = 0; p < nsrc; p++) if (!src[p] || src_stride[p] < w[p]) return -1;
@@ -689,6 +718,12 @@ extern "C" int mi355_sws_scale(mi355_sws_ctx *c, const uint8_t *const src[3], co
 {
     if (!c || !src || !src_stride || !dst || c->h.planar) return -1;
     const SwsDev &h = c->h;
+    if (yuy2_dst(h)) {
+        /* a packed 4:2:2 row: whole groups of four bytes, the phantom partner of an odd width's last sample with them; the packer: its groups */
+        const int ow = 4 * ((h.dstW + 1) >> 1), back = h.special ? 4 * yuy2_pack_groups(h) : ow;
+        const int r = scale_staged(c, src, src_stride, 1, &dst, &dst_stride, &ow, &h.dstH, &back);
+        return r ? r : (h.special ? h.srcH : h.dstH);
+    }
     /* a 32-bit destination is stored in dwords */
     const int bpp = packed_bpp(h);
     if (bpp == 4 && ((reinterpret_cast<uintptr_t>(dst) | (uintptr_t)dst_stride) & 3)) return -1;
@@ -865,16 +900,17 @@ extern "C" void mi355_sws_yuv2nv12cX(const int16_t *chrFilter, int chrFilterSize
     std::memcpy(dest, a.h<uint8_t>(o_d), (size_t)2 * chrDstW);
 }
 
-/* dst_format 0: rgb24 (k_sws_line_rgb); MI355_SWS_DST_BGR24 ... _ABGR: k_sws_line_packed of that form (sws_packed.hip), pairs of 6 or 8 bytes */
+/* dst_format 0: rgb24 (k_sws_line_rgb); MI355_SWS_DST_BGR24 ... _ABGR: k_sws_line_packed of that form (sws_packed.hip), pairs of 6 or 8 bytes;
+ * MI355_SWS_DST_YUYV422 ... _YVYU422: of DST_YUY2 (sws_yuy2dst.hip), groups of 4 bytes, luts not read */
 /* alp: the ls alpha lines of the _a entries (a 32-bit order): k_sws_line_packed_a (sws_rgb32.hip) */
 static void rgb_line(const mi355_sws_luts *luts, int mode, const int16_t *lumF, const int16_t **l, int ls, const int16_t *chrF,
                      const int16_t **u, const int16_t **v, int cs, uint8_t *dest, int dstW, int yalpha, int uvalpha, int dst_format = 0, const int16_t **alp = nullptr)
 {
     Arena &a = arena();
-    const int npair = (dstW + 1) >> 1, pitch = (2 * npair + 7) & ~7, pb = dst_format >= MI355_SWS_DST_RGBA ? 8 : 6;
+    const int npair = (dstW + 1) >> 1, pitch = (2 * npair + 7) & ~7, pb = sws_yuy2_dst(dst_format) ? 4 : (dst_format >= MI355_SWS_DST_RGBA ? 8 : 6);
     a.reserve(sizeof(mi355_sws_luts) + (size_t)(2 * ls + 2 * cs + 4) * pitch * 2 + (size_t)(ls + cs) * 2 + (size_t)npair * pb + 256);
     const size_t o_t = a.take(sizeof(mi355_sws_luts));
-    std::memcpy(a.h<uint8_t>(o_t), luts, sizeof(mi355_sws_luts));
+    if (luts) std::memcpy(a.h<uint8_t>(o_t), luts, sizeof(mi355_sws_luts));      /* (a packed 4:2:2 order reads none) */
     const size_t o_l = pack_rows(a, l, ls, 2 * npair, pitch), o_u = pack_rows(a, u, cs, npair, pitch), o_v = pack_rows(a, v, cs, npair, pitch);
     const size_t o_a = alp ? pack_rows(a, alp, ls, 2 * npair, pitch) : 0;
     const size_t o_lf = a.take((size_t)ls * 2 + 2), o_cf = a.take((size_t)cs * 2 + 2), o_d = a.take((size_t)npair * pb);
@@ -886,8 +922,9 @@ static void rgb_line(const mi355_sws_luts *luts, int mode, const int16_t *lumF, 
     if (dst_format) {
         SwsKey key{};
         key.kernel = SWS_KERNEL_LINE; key.dst = dst_form(dst_format); key.alpha = alp != nullptr;
-        const SwsOperands op{ dim3(1), a.stream, nullptr, nullptr, nullptr, nullptr, 0, 0, key.dst == DST_RGB32 ? sws_rgb32_sel(dst_format) : 0u, &n };
-        if (!(alp ? mi355_sws_launch_rgb32(key, op) : mi355_sws_launch_packed(key, op))) {
+        const SwsOperands op{ dim3(1), a.stream, nullptr, nullptr, nullptr, nullptr, 0, 0,
+                              key.dst == DST_RGB32 ? sws_rgb32_sel(dst_format) : (key.dst == DST_YUY2 ? sws_yuy2_dst_sel(dst_format) : 0u), &n };
+        if (!(alp ? mi355_sws_launch_rgb32(key, op) : (key.dst == DST_YUY2 ? mi355_sws_launch_yuy2dst(key, op) : mi355_sws_launch_packed(key, op)))) {
             std::fprintf(stderr, "mi355dsp: no line kernel for destination format %d%s\n", dst_format, alp ? " with alpha" : "");
             std::abort();
         }
@@ -960,7 +997,7 @@ extern "C" int mi355_sws_yuv2rgb_c_24_rgb(const mi355_sws_luts *luts, int dstW, 
 }
 
 /* ---- the same entries for any packed destination (dst_format 0: rgb24, the entries above; MI355_SWS_DST_BGR24 ... _ABGR) ---------------- */
-static bool packed_line_format(int dst_format) { return dst_format == 0 || packed_dst(dst_format); }
+static bool packed_line_format(int dst_format) { return one_plane_dst(dst_format); }
 extern "C" void mi355_sws_yuv2packed_X(const mi355_sws_luts *luts, int dst_format, const int16_t *lumFilter, const int16_t **lumSrc, int lumFilterSize,
                                        const int16_t *chrFilter, const int16_t **chrUSrc, const int16_t **chrVSrc, int chrFilterSize,
                                        uint8_t *dest, int dstW)

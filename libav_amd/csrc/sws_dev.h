@@ -1,6 +1,6 @@
 /*
  * sws_dev.h — the device side of sws.hip and of the files that compile instances beside it (sws_deep.hip, sws_packed.hip, sws_rgb32.hip,
- * sws_yuy2.hip): the tile geometry and its instance table, the steps of the scaler (horizontal pass into LDS, packed and planar vertical passes),
+ * sws_yuy2.hip, sws_yuy2dst.hip — the last one the DST_YUY2 form of the packed kernels: yuyv422 / uyvy422 / yvyu422 destinations, vertical_yuy2): the tile geometry and its instance table, the steps of the scaler (horizontal pass into LDS, packed and planar vertical passes),
  * at the end the host side of a launch (the launch key SwsKey, the dispatcher sws_launch, the grids, the line helper) and the kernels:
  *   k_sws_generic   the generic scaler of swscale() (libswscale/swscale.c:343-722) for whole pictures,
  *                   fused per output tile: horizontal 8->15 bit FIR of the source lines the tile needs
@@ -132,13 +132,22 @@ __device__ __forceinline__ void write_pair(const LutLds &t, uint8_t *dest, int Y
  *   yuv2rgb.c:864-888) is the 24-bpp case's clipped byte in three lanes and 255 in the fourth (a source without alpha) — here the three byte reads
  *   of y_table assembled as r | g << 8 | b << 16 | 255 << 24 and put into the order's bytes by ONE byte permute; its selector is the same on every
  *   lane (SwsDev::dst_sel, or a kernel argument), so one form serves the four orders. */
-constexpr int DST_RGB24 = 0, DST_BGR24 = 1, DST_RGB32 = 2;
-template <int DST> __host__ __device__ constexpr int dst_bpp() { return DST == DST_RGB32 ? 4 : 3; }
+/* DST_YUY2: yuyv422 / yvyu422 / uyvy422, two bytes a pixel (yuv2422_X / _2 / _1_c_template output.c:451-582: the templates' Y1, Y2, U, V, and no table behind
+ *   them) — a pair is ONE dword Y1 | U << 8 | Y2 << 16 | V << 24, each value truncated to its byte as the reference's stores truncate it, put into the
+ *   order's bytes by the same byte permute (sws_yuy2_dst_sel).  The form has no LUT: neither lut_load nor LutLds (compiled in sws_yuy2dst.hip). */
+constexpr int DST_RGB24 = 0, DST_BGR24 = 1, DST_RGB32 = 2, DST_YUY2 = 3;
+template <int DST> __host__ __device__ constexpr int dst_bpp() { return DST == DST_RGB32 ? 4 : (DST == DST_YUY2 ? 2 : 3); }
 /* the selector of a 32-bit order (MI355_SWS_DST_RGBA ... _ABGR): byte k of the stored dword is byte (sel >> 8 k) & 3 of r | g << 8 | b << 16 | a << 24 */
 __host__ __device__ constexpr uint32_t sws_rgb32_sel(int dst_format)
 {
     return dst_format == MI355_SWS_DST_RGBA ? 0x03020100u : (dst_format == MI355_SWS_DST_BGRA ? 0x03000102u :
            (dst_format == MI355_SWS_DST_ARGB ? 0x02010003u : 0x00010203u));
+}
+/* the selector of a packed 4:2:2 order (MI355_SWS_DST_YUYV422 / _UYVY422 / _YVYU422) over Y1 | U << 8 | Y2 << 16 | V << 24: Y1 U Y2 V, U Y1 V Y2, Y1 V Y2 U */
+__host__ __device__ constexpr bool sws_yuy2_dst(int dst_format) { return dst_format >= MI355_SWS_DST_YUYV422 && dst_format <= MI355_SWS_DST_YVYU422; }
+__host__ __device__ constexpr uint32_t sws_yuy2_dst_sel(int dst_format)
+{
+    return dst_format == MI355_SWS_DST_UYVY422 ? 0x02030001u : (dst_format == MI355_SWS_DST_YVYU422 ? 0x01020300u : 0x03020100u);
 }
 #ifdef MI355_HIP_EMU_H
 static inline uint32_t sws_order4(uint32_t w, uint32_t sel)
@@ -174,8 +183,18 @@ __device__ __forceinline__ void write_pair_a(const LutLds &t, uint8_t *dest, int
     q[0] = rgb32_pixel_a(t, r, g, b, Y1, A1, sel); q[1] = rgb32_pixel_a(t, r, g, b, Y2, A2, sel);
 }
 /* yuv2rgb_write of one pair: six bytes, or two dwords at dest (a multiple of 4) */
+/* one group of a packed 4:2:2 order: the four values as they are, truncated to bytes (output_pixels, output.c:451-467) */
+__device__ __forceinline__ uint32_t yuy2_group(int Y1, int U, int Y2, int V, uint32_t sel)
+{
+    return sws_order4(((uint32_t)Y1 & 0xFFu) | (((uint32_t)U & 0xFFu) << 8) | (((uint32_t)Y2 & 0xFFu) << 16) | ((uint32_t)V << 24), sel);
+}
 template <int DST> __device__ __forceinline__ void write_pair_d(const LutLds &t, uint8_t *dest, int Y1, int Y2, int U, int V, uint32_t sel)
 {
+    if constexpr (DST == DST_YUY2) {
+        /* four bytes at any address (a line entry's dest, a ragged row of k_sws_ident1) */
+        const uint32_t w = yuy2_group(Y1, U, Y2, V, sel);
+        dest[0] = (uint8_t)w; dest[1] = (uint8_t)(w >> 8); dest[2] = (uint8_t)(w >> 16); dest[3] = (uint8_t)(w >> 24);
+    } else
     if constexpr (DST == DST_RGB24) write_pair(t, dest, Y1, Y2, U, V);
     else {
         int r, g, b;
@@ -1396,9 +1415,10 @@ __device__ __forceinline__ void vertical_rows(const SwsDev &c, const LutLds &lut
 /* LDS of a workgroup, sized per context (sws_plan): the horizontal pass's results for the source lines a tile needs, the tables, and one
  * block shared by the staging lines (horizontal pass) and the output rows of tiles that cannot store from registers (after it). */
 /* alpha: with the alpha tile of an ALPHA instance, as many lines as the luma tile */
-__host__ __device__ constexpr int sws_lds_bytes(int lum_lines, int chr_lines, int stage = STAGE_BYTES, bool alpha = false)
+/* lut: with the tables (every form but DST_YUY2) */
+__host__ __device__ constexpr int sws_lds_bytes(int lum_lines, int chr_lines, int stage = STAGE_BYTES, bool alpha = false, bool lut = true)
 {
-    return lum_lines * TW * 2 + 2 * chr_lines * (TW / 2) * 2 + (int)sizeof(LutLds) + stage + (alpha ? lum_lines * TW * 2 : 0);
+    return lum_lines * TW * 2 + 2 * chr_lines * (TW / 2) * 2 + (lut ? (int)sizeof(LutLds) : 0) + stage + (alpha ? lum_lines * TW * 2 : 0);
 }
 /* the waves per SIMD the register allocation of a tile kernel aims at: a CU's 160 KB of LDS hold that many of its workgroups, one wave of
  * each per SIMD */
@@ -1486,6 +1506,128 @@ __device__ __forceinline__ void vertical_narrow(const SwsDev *cp, const LutLds *
     }
 }
 
+/* ---- DST_YUY2: the vertical pass of a packed 4:2:2 destination (yuv2422_1 / _2 / _X_c_template, output.c:469-576) --------------------------------
+ * range conversion of the tile's lines between the two passes (lumConvertRange over dstW, chrConvertRange over chrDstW samples, swscale.c:284-285,
+ * :334-335): only the samples of the picture — the phantom partner of an odd width's last sample stays the 0 the horizontal pass left (the
+ * reference's converters never reach sample dstW of its zero-allocated line) */
+__device__ __forceinline__ int range_one(int v, const SwsRangeMap &m);      /* (below, with the planar kernel's range_lines) */
+__device__ __forceinline__ void yuy2_range_tile(const SwsDev &c, int16_t (*s_lum)[TW], int16_t (*s_cu)[TW / 2], int16_t (*s_cv)[TW / 2], int nlum, int nchr, int x0, int tid)
+{
+    const int wl = imin(TW, c.dstW - x0), wc = imin(TW / 2, c.chrDstW - (x0 >> 1));
+    for (int i = tid; i < nlum * TW; i += NT) {
+        const int l = i / TW, x = i % TW;
+        if (x < wl) s_lum[l][x] = (int16_t)range_one(s_lum[l][x], c.rng_l);
+    }
+    for (int i = tid; i < nchr * (TW / 2); i += NT) {
+        const int l = i / (TW / 2), x = i % (TW / 2);
+        if (x < wc) { s_cu[l][x] = (int16_t)range_one(s_cu[l][x], c.rng_c); s_cv[l][x] = (int16_t)range_one(s_cv[l][x], c.rng_c); }
+    }
+}
+/* A thread owns one output row of the tile and eight neighbouring samples of it — four groups, 16 bytes: one 16-byte LDS read a luma tap line, one
+ * 8-byte read a chroma tap line and plane.  The X form takes two taps at a time (v_dot2_i32_i16 over the same sample of two lines, as
+ * vertical_rows; a tap past the filter has a zero coefficient and the last line's index); the taps are read as the loop goes, so any filter size
+ * runs here.  A full tile of a row whose pointer and stride are multiples of 16 leaves from registers; every other tile goes through s_out (the
+ * staging lines: TW * 2 bytes a row, all MAXTH rows at once) and leaves in 16-byte, 4-byte or single-byte pieces.  The row extent is
+ * 4 * ((dstW + 1) >> 1) bytes: the phantom partner of an odd width's last sample is written — 0, the luma tile's zero tail through any of the three
+ * forms. */
+__device__ __forceinline__ void vertical_yuy2(const SwsDev &c, const int16_t (*s_lum)[TW], const int16_t (*s_cu)[TW / 2], const int16_t (*s_cv)[TW / 2],
+                                              uint8_t (*s_out)[TW * 2], int tid, int x0, int y0, int y1, int llo, int clo, uint8_t *tile_dst, int dst_stride)
+{
+    static_assert(STAGE_BYTES >= MAXTH * TW * 2 && NT / 16 >= MAXTH, "one pass over the rows of a tile");
+    const int ls = c.vls, cs = c.vcs, mode = packed_mode(ls, cs);
+    const int row = tid >> 4, grp = tid & 15, gy = y0 + row;
+    const uint32_t sel = c.dst_sel;
+    const bool wide = c.dstW - x0 >= TW && ((reinterpret_cast<uintptr_t>(tile_dst) | (uintptr_t)dst_stride) & 15) == 0;      /* uniform over the workgroup */
+    if (gy <= y1) {
+        const int lfirst = imax(1 - ls, c.vLumP[gy]), cfirst = imax(1 - cs, c.vChrP[gy]);
+        const int16_t *lumF = c.vLumC + (size_t)gy * ls, *chrF = c.vChrC + (size_t)gy * cs;
+        auto lline = [&](int j) { return *reinterpret_cast<const sws_u32x4 *>(&s_lum[clampi(lfirst + j, 0, c.srcH - 1) - llo][8 * grp]); };
+        auto uline = [&](int j) { return *reinterpret_cast<const sws_u32x2 *>(&s_cu[clampi(cfirst + j, 0, c.chrSrcH - 1) - clo][4 * grp]); };
+        auto vline = [&](int j) { return *reinterpret_cast<const sws_u32x2 *>(&s_cv[clampi(cfirst + j, 0, c.chrSrcH - 1) - clo][4 * grp]); };
+        int Y[8], U[4], V[4];
+        if (mode == 1) {
+            const int uvalpha = cs == 1 ? 0 : chrF[1];
+            const sws_u32x4 l0 = lline(0);
+            const sws_u32x2 u0 = uline(0), v0 = vline(0), u1 = uline(cs - 1), v1 = vline(cs - 1);
+#pragma unroll
+            for (int k = 0; k < 8; k++) Y[k] = clip_u8(lane16(l0, k) >> 7);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                if (uvalpha < 2048) { U[k] = clip_u8(lane16(u0, k) >> 7); V[k] = clip_u8(lane16(v0, k) >> 7); }
+                else { U[k] = clip_u8((lane16(u0, k) + lane16(u1, k)) >> 8); V[k] = clip_u8((lane16(v0, k) + lane16(v1, k)) >> 8); }
+            }
+        } else if (mode == 2) {
+            const int ya = lumF[1], ua = chrF[1], ya1 = 4096 - ya, ua1 = 4096 - ua;
+            const sws_u32x4 l0 = lline(0), l1 = lline(1);
+            const sws_u32x2 u0 = uline(0), v0 = vline(0), u1 = uline(1), v1 = vline(1);
+#pragma unroll
+            for (int k = 0; k < 8; k++) Y[k] = clip_u8((lane16(l0, k) * ya1 + lane16(l1, k) * ya) >> 19);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                U[k] = clip_u8((lane16(u0, k) * ua1 + lane16(u1, k) * ua) >> 19);
+                V[k] = clip_u8((lane16(v0, k) * ua1 + lane16(v1, k) * ua) >> 19);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++) Y[k] = 1 << 18;
+#pragma unroll
+            for (int k = 0; k < 4; k++) U[k] = V[k] = 1 << 18;
+            for (int j = 0; j < ls; j += 2) {
+                const int j1 = j + 1 < ls ? j + 1 : j;
+                const uint32_t cp = ((uint32_t)lumF[j] & 0xFFFFu) | (j + 1 < ls ? (uint32_t)lumF[j1] << 16 : 0u);
+                const sws_u32x4 la = lline(j), lb = lline(j1);
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    Y[2 * q] = sws_dot2(sws_lo2(la[q], lb[q]), cp, Y[2 * q]);
+                    Y[2 * q + 1] = sws_dot2(sws_hi2(la[q], lb[q]), cp, Y[2 * q + 1]);
+                }
+            }
+            for (int j = 0; j < cs; j += 2) {
+                const int j1 = j + 1 < cs ? j + 1 : j;
+                const uint32_t cp = ((uint32_t)chrF[j] & 0xFFFFu) | (j + 1 < cs ? (uint32_t)chrF[j1] << 16 : 0u);
+                const sws_u32x2 ua = uline(j), ub = uline(j1), va = vline(j), vb = vline(j1);
+#pragma unroll
+                for (int q = 0; q < 2; q++) {
+                    U[2 * q] = sws_dot2(sws_lo2(ua[q], ub[q]), cp, U[2 * q]);
+                    U[2 * q + 1] = sws_dot2(sws_hi2(ua[q], ub[q]), cp, U[2 * q + 1]);
+                    V[2 * q] = sws_dot2(sws_lo2(va[q], vb[q]), cp, V[2 * q]);
+                    V[2 * q + 1] = sws_dot2(sws_hi2(va[q], vb[q]), cp, V[2 * q + 1]);
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < 4; p++) {       /* clipped per group, only if one of its four values has bit 8 set (output.c:498); else stored as they are */
+                int &Y1 = Y[2 * p], &Y2 = Y[2 * p + 1], &Up = U[p], &Vp = V[p];
+                Y1 >>= 19; Y2 >>= 19; Up >>= 19; Vp >>= 19;
+                if ((Y1 | Y2 | Up | Vp) & 0x100) { Y1 = clip_u8(Y1); Y2 = clip_u8(Y2); Up = clip_u8(Up); Vp = clip_u8(Vp); }
+            }
+        }
+        const sws_u32x4 o = { yuy2_group(Y[0], U[0], Y[1], V[0], sel), yuy2_group(Y[2], U[1], Y[3], V[1], sel), yuy2_group(Y[4], U[2], Y[5], V[2], sel),
+                              yuy2_group(Y[6], U[3], Y[7], V[3], sel) };
+        if (wide) *reinterpret_cast<sws_u32x4 *>(tile_dst + (size_t)row * dst_stride + 16 * grp) = o;
+        else *reinterpret_cast<sws_u32x4 *>(&s_out[row][16 * grp]) = o;
+    }
+    if (wide) return;
+    __syncthreads();
+    const int nbytes = 4 * (imin(TW, c.dstW - x0 + 1) >> 1), nrows = y1 - y0 + 1;        /* whole groups: (dstW + 1) >> 1 of them in the picture */
+    const unsigned al = (unsigned)(uintptr_t)tile_dst | (unsigned)dst_stride;
+    if ((al & 15) == 0 && (nbytes & 15) == 0) {
+        const int n = nbytes >> 4;
+        for (int idx = tid; idx < nrows * n; idx += NT) {
+            const int r = idx / n, k = idx - r * n;
+            reinterpret_cast<uint4 *>(tile_dst + (size_t)r * dst_stride)[k] = reinterpret_cast<const uint4 *>(s_out[r])[k];
+        }
+    } else if ((al & 3) == 0) {
+        const int n = nbytes >> 2;
+        for (int idx = tid; idx < nrows * n; idx += NT) {
+            const int r = idx / n, k = idx - r * n;
+            reinterpret_cast<uint32_t *>(tile_dst + (size_t)r * dst_stride)[k] = reinterpret_cast<const uint32_t *>(s_out[r])[k];
+        }
+    } else {
+        for (int r = 0; r < nrows; r++)
+            for (int k = tid; k < nbytes; k += NT) tile_dst[(size_t)r * dst_stride + k] = s_out[r][k];
+    }
+}
+
 /* LCAP / CCAP: a row of GENERIC_SHAPES; WAVES: sws_waves() of the instance's LDS */
 /* ST: the source's sample type; the uint16_t instances (9 / 10 bit sources) differ in the horizontal pass and its staging lines only */
 /* NV: an NV12 / NV21 source (8 bit) — both chroma tiles from ONE pass over fr.src[1], the plane of pairs (hscale_tile_nv); fr.src[2] is not read.
@@ -1493,7 +1635,9 @@ __device__ __forceinline__ void vertical_narrow(const SwsDev *cp, const LutLds *
  * RGB: a packed rgb24 / bgr24 source (8 bit) — luma and both chroma tiles from fr.src[0] through the input converters (hscale_tile_rgb);
  * fr.src[1] and fr.src[2] are not read.  The same LDS again. */
 /* DST: the destination form — DST_RGB24 (the instances above, unchanged), DST_BGR24 or DST_RGB32 (compiled in sws_packed.hip).  The same LDS: the
- * output rows of the narrow form share the staging lines, nine rows of TW * 4 bytes where rgb24 has twelve of TW * 3. */
+ * output rows of the narrow form share the staging lines, nine rows of TW * 4 bytes where rgb24 has twelve of TW * 3.
+ * DST_YUY2 (compiled in sws_yuy2dst.hip): yuyv422 / uyvy422 / yvyu422 — the same horizontal pass, then vertical_yuy2; no table in LDS (WAVES follows the
+ * smaller tile), and the range conversion of such a context as a run-time branch of this form alone */
 template <int LCAP, int CCAP, int WAVES, typename ST = uint8_t, bool NV = false, bool RGB = false, int DST = DST_RGB24>
 #ifndef MI355_HIP_EMU_H
 __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
@@ -1528,6 +1672,7 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
     const int cfirst0 = imax(1 - cs, c.vChrP[y0]), cfirst1 = imax(1 - cs, c.vChrP[y1]);
     const int llo = clampi(lfirst0, 0, c.srcH - 1), lhi = clampi(lfirst1 + ls - 1, 0, c.srcH - 1);
     const int clo = clampi(cfirst0, 0, c.chrSrcH - 1), chi = clampi(cfirst1 + cs - 1, 0, c.chrSrcH - 1);
+    if constexpr (DST != DST_YUY2)
     lut_load(s_lut, &cp->luts, tid);
     /* horizontal pass: luma (the phantom partner of the last sample of an odd-width picture reads the
      * zero-initialised tail of the reference's line buffer, utils.c:1241-1262), then the chroma planes */
@@ -1575,6 +1720,16 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
     }
     }
     __syncthreads();
+    if constexpr (DST == DST_YUY2) {
+        /* a packed 4:2:2 destination: no table; a context that converts the range (uniform over the grid) does so on the tile's lines first */
+        static_assert(!ALPHA, "no alpha in a packed 4:2:2 destination");
+        if (c.range) {
+            yuy2_range_tile(c, s_lum, s_cu, s_cv, lhi - llo + 1, chi - clo + 1, x0, tid);
+            __syncthreads();
+        }
+        vertical_yuy2(c, s_lum, s_cu, s_cv, s_out, tid, x0, y0, y1, llo, clo, fr.dst + (size_t)y0 * fr.dst_stride + (size_t)x0 * BPP, fr.dst_stride);
+        return;
+    }
     /* vertical pass + LUT */
     const int mode = packed_mode(ls, cs);
     const int npairs = imin(TW, c.dstW - x0 + 1) >> 1;     /* (dstW + 1) >> 1 pairs in the picture */
@@ -2266,13 +2421,15 @@ __global__ void __launch_bounds__(NT) k_sws_c24(const mi355_sws_luts *luts, int 
 /* NV: an NV12 / NV21 source — per tap line one 8-byte load of four pairs from fr.src[1] in place of the two 4-byte loads, U and V out of it with
  * one permute each; the wide form asks the pair plane for 8-byte multiples; fr.src[2] is not read */
 /* DST: the destination form, as k_sws_generic's (the selector of a 32-bit order from the record; its wide form asks the destination for 16-byte multiples) */
+/* DST_YUY2: a thread's eight samples are four groups, 16 bytes — the pair's Y1, Y2, U, V of either form straight into the group, no table and no barrier;
+ * the wide form asks the destination for 16-byte multiples, ragged rows leave group by group in bytes */
 template <bool X, bool NV = false, int DST = DST_RGB24>
 __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355_sws_frame *frames)
 {
     __shared__ LutLds s_lut;
     constexpr int NC = X ? 4 : 2;
     constexpr int BPP = dst_bpp<DST>();
-    const uint32_t sel = DST == DST_RGB32 ? cp->dst_sel : 0u;
+    const uint32_t sel = DST == DST_RGB32 || DST == DST_YUY2 ? cp->dst_sel : 0u;
     const int tid = threadIdx.x;
     const int dstW = cp->dstW, dstH = cp->dstH, cs = cp->vcs, srcH = cp->srcH, chrSrcH = cp->chrSrcH;
     /* only the vertical banks and five sizes of the record: read one by one */
@@ -2286,7 +2443,7 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
     const bool mine = (x >> 1) < npairs;
     bool wide = mine && (x >> 1) + 4 <= npairs &&
                 ((reinterpret_cast<uintptr_t>(fr.src[0]) | (uintptr_t)fr.src_stride[0] | reinterpret_cast<uintptr_t>(fr.dst) | (uintptr_t)fr.dst_stride) & 7) == 0;
-    if constexpr (DST == DST_RGB32) wide = wide && ((reinterpret_cast<uintptr_t>(fr.dst) | (uintptr_t)fr.dst_stride) & 15) == 0;
+    if constexpr (DST == DST_RGB32 || DST == DST_YUY2) wide = wide && ((reinterpret_cast<uintptr_t>(fr.dst) | (uintptr_t)fr.dst_stride) & 15) == 0;
     if constexpr (NV) wide = wide && ((reinterpret_cast<uintptr_t>(fr.src[1]) | (uintptr_t)fr.src_stride[1]) & 7) == 0;
     else wide = wide && ((reinterpret_cast<uintptr_t>(fr.src[1]) | (uintptr_t)fr.src_stride[1] | reinterpret_cast<uintptr_t>(fr.src[2]) | (uintptr_t)fr.src_stride[2]) & 3) == 0;
     const int vu = NV && cp->src_layout == MI355_SWS_SRC_NV21;      /* the first byte of a pair is V */
@@ -2327,8 +2484,10 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
         }
     }
     MI355_ISSUE_FENCE();
+    if constexpr (DST != DST_YUY2) {
     lut_load(s_lut, &cp->luts, tid);
     __syncthreads();
+    }
     if (!mine) return;
 #pragma unroll
     for (int q = 0; q < NR; q++) {
@@ -2353,6 +2512,7 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
         };
         if (wide) {
             int Y[8], r[4], g[4], b[4];
+            [[maybe_unused]] uint32_t grp4[4];                  /* DST_YUY2: the four groups as they leave */
             if constexpr (NV) {
 #pragma unroll
                 for (int j = 0; j < NC; j++) {
@@ -2367,9 +2527,13 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
                 for (int j = 0; j < NC; j++) { us[j] = (u[q][j] >> (8 * p)) & 0xFF; vs[j] = (v[q][j] >> (8 * p)) & 0xFF; }
                 const uint32_t w = ya[q][p >> 1] >> (16 * (p & 1));
                 pair((int)(w & 0xFF), (int)((w >> 8) & 0xFF), us, vs, Y[2 * p], Y[2 * p + 1], U, V);
+                if constexpr (DST == DST_YUY2) grp4[p] = yuy2_group(Y[2 * p], U, Y[2 * p + 1], V, sel);
+                else
                 lut_rows_d<DST>(s_lut, U, V, r[p], g[p], b[p]);
             }
             /* (through store8_d the rgb24 instances got another instruction stream: the two stores are named here) */
+            if constexpr (DST == DST_YUY2) *reinterpret_cast<sws_u32x4 *>(d) = sws_u32x4{ grp4[0], grp4[1], grp4[2], grp4[3] };
+            else
             if constexpr (DST == DST_RGB32) rgb32_store8(s_lut, d, Y, r, g, b, sel);
             else rgb24_store8(s_lut, d, Y, r, g, b);
         } else {
@@ -2388,6 +2552,118 @@ __global__ void __launch_bounds__(NT) k_sws_ident1(const SwsDev *cp, const mi355
                 }
                 pair(py[2 * p], py[2 * p + 1], us, vs, Y1, Y2, U, V);
                 write_pair_d<DST>(s_lut, d + 2 * BPP * p, Y1, Y2, U, V, sel);
+            }
+        }
+    }
+}
+
+/* ---- equal size to a packed RGB destination: k_sws_ident1's _1 form straight from the packed bytes ---------------------------------------------
+ * The reference has no special converter from these sources to RGB: its scaler runs with identity horizontal filters and ONE vertical luma tap, and
+ * with chroma on every source line the chroma filter has one or two taps — yuv2rgb24_1_c and its kin (output.c:1043-1110): Y = the luma byte, U / V
+ * the first chroma line's byte, or the mean of two lines where the row's second coefficient is >= 2048.  k_sws_ident1's grid, tile and LUT copy; a
+ * thread's eight samples of a row are 16 source bytes that hold luma AND chroma — one 16-byte load on a plane of 16-byte multiples, four dwords on
+ * one of 4-byte multiples; a chroma tap line other than the luma line (uniform over the row's wave) is loaded the same way.  Ragged rows, and planes
+ * on neither multiple, go byte by byte.  A kernel of its own name: another template parameter of k_sws_ident1 would rename its existing instances.
+ * DST_YUY2: as k_sws_ident1's — four groups a thread, no table and no barrier (a re-ordering of the packed bytes, with the chroma mean where the row has it).
+ * With chroma on every line no context of these sources reaches the X template (more than two chroma taps): sws.hip sends such a one to the tile. */
+template <int DST>
+__global__ void __launch_bounds__(NT) k_sws_ident1_yuy2(const SwsDev *cp, const mi355_sws_frame *frames)
+{
+    __shared__ LutLds s_lut;
+    constexpr int NC = 2;
+    constexpr int BPP = dst_bpp<DST>();
+    const uint32_t sel = DST == DST_RGB32 || DST == DST_YUY2 ? cp->dst_sel : 0u;
+    const int tid = threadIdx.x;
+    const int dstW = cp->dstW, dstH = cp->dstH, cs = cp->vcs, srcH = cp->srcH, chrSrcH = cp->chrSrcH, layout = cp->src_layout;
+    const int32_t *vLumP = mi355_global(cp->vLumP), *vChrP = mi355_global(cp->vChrP);
+    const int16_t *vChrC = mi355_global(cp->vChrC);
+    mi355_sws_frame fr = frames[blockIdx.z];
+    fr.src[0] = mi355_global(fr.src[0]);
+    fr.dst = mi355_global(fr.dst);
+    const int x = blockIdx.x * C24_COLS + (tid & 63) * 8;   /* first of the thread's eight samples */
+    const int npairs = dstW >> 1;
+    const bool mine = (x >> 1) < npairs;
+    const uintptr_t sal = reinterpret_cast<uintptr_t>(fr.src[0]) | (uintptr_t)fr.src_stride[0];
+    const bool al16 = (sal & 15) == 0;
+    constexpr uintptr_t DMASK = DST == DST_RGB32 || DST == DST_YUY2 ? 15 : 7;
+    /* the wide form: four whole pairs (x + 8 <= dstW <= srcW: the 16 bytes lie inside the line's 2 * srcW) */
+    const bool wide = mine && (x >> 1) + 4 <= npairs && (sal & 3) == 0 && ((reinterpret_cast<uintptr_t>(fr.dst) | (uintptr_t)fr.dst_stride) & DMASK) == 0;
+    const bool uy = sws_yuy2_luma(layout) != 0, vu = layout == MI355_SWS_SRC_YVYU422;
+    constexpr int NR = IDENT_ROWS / (NT / 64);
+    int li[NR], ci[NR][NC], cf1[NR];
+    uint32_t wl[NR][4], wc[NR][NC][4];
+    auto load16 = [&](const uint8_t *p, uint32_t *w) {
+        if (al16) {
+            const sws_u32x4 v = *reinterpret_cast<const sws_u32x4 *>(p);
+            w[0] = v[0]; w[1] = v[1]; w[2] = v[2]; w[3] = v[3];
+        } else {
+#pragma unroll
+            for (int d = 0; d < 4; d++) w[d] = reinterpret_cast<const uint32_t *>(p)[d];
+        }
+    };
+#pragma unroll
+    for (int q = 0; q < NR; q++) {
+        /* rows past the picture repeat its last row and are not written; a tap past the filter reads tap 0 */
+        const int gy = imin(blockIdx.y * IDENT_ROWS + (tid >> 6) + q * (NT / 64), dstH - 1);
+        li[q] = clampi(vLumP[gy], 0, srcH - 1);
+        const int cfirst = imax(1 - cs, vChrP[gy]);
+        cf1[q] = cs > 1 ? vChrC[(size_t)gy * cs + 1] : 0;
+#pragma unroll
+        for (int j = 0; j < NC; j++) ci[q][j] = clampi(cfirst + (j < cs ? j : 0), 0, chrSrcH - 1);
+#pragma unroll
+        for (int d = 0; d < 4; d++) wl[q][d] = 0;
+        if (wide) load16(fr.src[0] + (size_t)li[q] * fr.src_stride[0] + 2 * (size_t)x, wl[q]);
+#pragma unroll
+        for (int j = 0; j < NC; j++) {
+#pragma unroll
+            for (int d = 0; d < 4; d++) wc[q][j][d] = wl[q][d];
+            if (wide && ci[q][j] != li[q]) load16(fr.src[0] + (size_t)ci[q][j] * fr.src_stride[0] + 2 * (size_t)x, wc[q][j]);
+        }
+    }
+    MI355_ISSUE_FENCE();
+    if constexpr (DST != DST_YUY2) {
+    lut_load(s_lut, &cp->luts, tid);
+    __syncthreads();
+    }
+    if (!mine) return;
+#pragma unroll
+    for (int q = 0; q < NR; q++) {
+        const int gy = blockIdx.y * IDENT_ROWS + (tid >> 6) + q * (NT / 64);
+        if (gy >= dstH) break;
+        uint8_t *d = fr.dst + (size_t)gy * fr.dst_stride + (size_t)x * BPP;
+        const bool mean = cs > 1 && cf1[q] >= 2048;
+        if (wide) {
+            int Y[8], r[4], g[4], b[4];
+            [[maybe_unused]] uint32_t grp4[4];                  /* DST_YUY2: the four groups as they leave */
+            const uint32_t ya[2] = { uy ? sws_odd4(wl[q][0], wl[q][1]) : sws_even4(wl[q][0], wl[q][1]), uy ? sws_odd4(wl[q][2], wl[q][3]) : sws_even4(wl[q][2], wl[q][3]) };
+            uint32_t u[NC], v[NC];
+#pragma unroll
+            for (int j = 0; j < NC; j++) {
+                const uint32_t *w = wc[q][j];
+                const uint32_t c01 = uy ? sws_even4(w[0], w[1]) : sws_odd4(w[0], w[1]), c23 = uy ? sws_even4(w[2], w[3]) : sws_odd4(w[2], w[3]);
+                const uint32_t e = sws_even4(c01, c23), o = sws_odd4(c01, c23);
+                u[j] = vu ? o : e; v[j] = vu ? e : o;
+            }
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                const int u0 = (u[0] >> (8 * p)) & 0xFF, u1 = (u[1] >> (8 * p)) & 0xFF, v0 = (v[0] >> (8 * p)) & 0xFF, v1 = (v[1] >> (8 * p)) & 0xFF;
+                const uint32_t w = ya[p >> 1] >> (16 * (p & 1));
+                Y[2 * p] = (int)(w & 0xFF); Y[2 * p + 1] = (int)((w >> 8) & 0xFF);
+                if constexpr (DST == DST_YUY2) grp4[p] = yuy2_group(Y[2 * p], mean ? (u0 + u1) >> 1 : u0, Y[2 * p + 1], mean ? (v0 + v1) >> 1 : v0, sel);
+                else
+                lut_rows_d<DST>(s_lut, mean ? (u0 + u1) >> 1 : u0, mean ? (v0 + v1) >> 1 : v0, r[p], g[p], b[p]);
+            }
+            if constexpr (DST == DST_YUY2) *reinterpret_cast<sws_u32x4 *>(d) = sws_u32x4{ grp4[0], grp4[1], grp4[2], grp4[3] };
+            else
+            if constexpr (DST == DST_RGB32) rgb32_store8(s_lut, d, Y, r, g, b, sel);
+            else rgb24_store8(s_lut, d, Y, r, g, b);
+        } else {
+            const int lo = sws_yuy2_luma(layout), uo = sws_yuy2_u(layout), vo = sws_yuy2_v(layout);
+            const uint8_t *py = fr.src[0] + (size_t)li[q] * fr.src_stride[0] + 2 * (size_t)x;
+            for (int p = 0; p < 4 && (x >> 1) + p < npairs; p++) {
+                const uint8_t *p0 = fr.src[0] + (size_t)ci[q][0] * fr.src_stride[0] + 2 * (size_t)x + 4 * p, *p1 = fr.src[0] + (size_t)ci[q][1] * fr.src_stride[0] + 2 * (size_t)x + 4 * p;
+                const int U = mean ? (p0[uo] + p1[uo]) >> 1 : p0[uo], V = mean ? (p0[vo] + p1[vo]) >> 1 : p0[vo];
+                write_pair_d<DST>(s_lut, d + 2 * BPP * p, py[4 * p + lo], py[4 * p + lo + 2], U, V, sel);
             }
         }
     }
@@ -2475,8 +2751,10 @@ __global__ void __launch_bounds__(NT) k_sws_line_packed(const mi355_sws_luts *lu
                                                         int dstW, int yalpha, int uvalpha, uint32_t sel)
 {
     __shared__ LutLds s_lut;
+    if constexpr (DST != DST_YUY2) {                /* (a packed 4:2:2 order has no table: luts is not read) */
     lut_load(s_lut, luts, threadIdx.x);
     __syncthreads();
+    }
     PackedRows R{ l, u, v, pitch };
     for (int i = threadIdx.x; i < ((dstW + 1) >> 1); i += NT)
         rgb_pair<DST>(s_lut, dest + (size_t)i * 2 * dst_bpp<DST>(), R, i, mode, lumF, ls, chrF, cs, yalpha, uvalpha, sel);
@@ -2500,17 +2778,18 @@ __global__ void __launch_bounds__(NT) k_sws_line_rgb(const mi355_sws_luts *luts,
  * instance; every file maps it to hipLaunchKernelGGL through the one dispatcher below (sws_launch).
  *   kernel  GENERIC / PLANAR: the tile kernels k_sws_generic / k_sws_planar, instance i; IDENT1_1 / IDENT1_X: k_sws_ident1<false / true> (a packed
  *           4:2:2 source: k_sws_ident1_yuy2); C24 / C24_422: k_sws_c24<0 / 1> (yuv422p: every other chroma line); LINE: k_sws_line_packed of one line
- *           (alpha: k_sws_line_packed_a); YUY2_SPLIT: k_sws_yuy2_split
+ *           (alpha: k_sws_line_packed_a); YUY2_SPLIT: k_sws_yuy2_split; YUY2_PACK: k_sws_yuy2_pack
  *   i       0 / 1 / 2: the A / B / C row of GENERIC_SHAPES / PLANAR_SHAPES, as sws_kernel() chose it
  *   src     the source class — P8 / P16: three planes of bytes / of 16-bit samples, NV: NV12 / NV21, RGB24: rgb24 / bgr24, RGB32: rgba / bgra /
  *           argb / abgr, YUY2: yuyv422 / uyvy422 / yvyu422 (the order inside a class is read from the context on the device)
  *   form    of k_sws_planar — HALF: three planes, chroma tiles of CW = TW / 2, FULL: of CW = TW (a 4:4:4 destination), SEMI: NV12 / NV21
  *   kind    of k_sws_planar — PLAIN, RANGE (range conversion between the passes), DEEP (9- / 10-bit planes; three planes, no range)
- *   dst     of the packed kernels — DST_RGB24 / DST_BGR24 / DST_RGB32 (the 32-bit order is the operands' sel)
+ *   dst     of the packed kernels — DST_RGB24 / DST_BGR24 / DST_RGB32 (the 32-bit order is the operands' sel) / DST_YUY2 (the 4:2:2 order likewise)
  *   alpha   the ALPHA form: a 32-bit source's alpha to a 32-bit destination
  * A key a file has no instance for (DEEP with SEMI, ALPHA outside RGB32 -> DST_RGB32, another file's source class, kind or destination) is not
  * launched: the launch functions return false and the entry point -2. */
-enum SwsKernel { SWS_KERNEL_GENERIC, SWS_KERNEL_PLANAR, SWS_KERNEL_IDENT1_1, SWS_KERNEL_IDENT1_X, SWS_KERNEL_C24, SWS_KERNEL_C24_422, SWS_KERNEL_LINE, SWS_KERNEL_YUY2_SPLIT };
+enum SwsKernel { SWS_KERNEL_GENERIC, SWS_KERNEL_PLANAR, SWS_KERNEL_IDENT1_1, SWS_KERNEL_IDENT1_X, SWS_KERNEL_C24, SWS_KERNEL_C24_422, SWS_KERNEL_LINE, SWS_KERNEL_YUY2_SPLIT,
+                 SWS_KERNEL_YUY2_PACK };
 enum SwsSrcClass { SWS_SRC_P8, SWS_SRC_P16, SWS_SRC_NV, SWS_SRC_RGB24, SWS_SRC_RGB32, SWS_SRC_YUY2 };
 enum SwsForm { SWS_FORM_HALF, SWS_FORM_FULL, SWS_FORM_SEMI };
 enum SwsKind { SWS_KIND_PLAIN, SWS_KIND_RANGE, SWS_KIND_DEEP };
@@ -2553,6 +2832,7 @@ bool mi355_sws_launch_deep(const SwsKey &key, const SwsOperands &op);       /* s
 bool mi355_sws_launch_packed(const SwsKey &key, const SwsOperands &op);     /* sws_packed.hip: DST_BGR24 / DST_RGB32 of k_sws_generic, k_sws_ident1, k_sws_c24, k_sws_line_packed */
 bool mi355_sws_launch_rgb32(const SwsKey &key, const SwsOperands &op);      /* sws_rgb32.hip: every tile instance of SWS_SRC_RGB32, k_sws_line_packed_a */
 bool mi355_sws_launch_yuy2(const SwsKey &key, const SwsOperands &op);       /* sws_yuy2.hip: every tile instance of SWS_SRC_YUY2, k_sws_ident1_yuy2, k_sws_yuy2_split */
+bool mi355_sws_launch_yuy2dst(const SwsKey &key, const SwsOperands &op);    /* sws_yuy2dst.hip: DST_YUY2 of k_sws_generic, k_sws_ident1, k_sws_ident1_yuy2, k_sws_line_packed from every source class; k_sws_yuy2_pack */
 
 namespace {
 /* the three grids of the picture kernels: the tile kernels' (th rows of TW samples), k_sws_ident1's and k_sws_c24's (rows: source rows of the slice) */
@@ -2567,7 +2847,9 @@ template <typename E, E... Vs, typename F> bool sws_pick(E v, F f)
     (void)((v == Vs && ((done = f(std::integral_constant<E, Vs>())), true)) || ...);
     return done;
 }
-template <typename F> bool sws_pick_dst(int dst, F f) { return sws_pick<int, DST_RGB24, DST_BGR24, DST_RGB32>(dst, f); }
+template <typename F> bool sws_pick_dst(int dst, F f) { return sws_pick<int, DST_RGB24, DST_BGR24, DST_RGB32, DST_YUY2>(dst, f); }
+/* ... of the three RGB forms alone (a file that compiles no DST_YUY2 instance of a kernel it picks for) */
+template <typename F> bool sws_pick_dst_rgb(int dst, F f) { return sws_pick<int, DST_RGB24, DST_BGR24, DST_RGB32>(dst, f); }
 /* instance i as I: the row of GENERIC_SHAPES / PLANAR_SHAPES that sws_launch_generic / sws_launch_planar read */
 template <typename F> bool sws_pick_instance(int i, F f) { return sws_pick<int, 0, 1, 2>(i, f); }
 constexpr unsigned sws_bit(int v) { return 1u << v; }
@@ -2589,7 +2871,7 @@ template <int I, SwsSrcClass C, int DST, bool ALPHA> void sws_launch_generic(con
 {
     typedef typename std::conditional<ALPHA, SwsPx32A, typename SwsSrc<C>::ST>::type ST;
     constexpr SwsShape S = GENERIC_SHAPES[I];
-    hipLaunchKernelGGL((k_sws_generic<S.lcap, S.ccap, sws_waves(sws_lds_bytes(S.lcap, S.ccap, stage_bytes<ST>(), ALPHA)), ST, SwsSrc<C>::NV, SwsSrc<C>::RGB, DST>), op.grid, dim3(NT), 0,
+    hipLaunchKernelGGL((k_sws_generic<S.lcap, S.ccap, sws_waves(sws_lds_bytes(S.lcap, S.ccap, stage_bytes<ST>(), ALPHA, DST != DST_YUY2)), ST, SwsSrc<C>::NV, SwsSrc<C>::RGB, DST>), op.grid, dim3(NT), 0,
                        op.s, static_cast<const SwsDev *>(op.d), static_cast<const mi355_sws_frame *>(op.frames));
 }
 template <int I, SwsSrcClass C, SwsForm F, SwsKind K> void sws_launch_planar(const SwsOperands &op)
@@ -2643,7 +2925,7 @@ template <unsigned SRCS, unsigned KINDS, unsigned DSTS> bool sws_launch(const Sw
                     /* k_sws_ident1 reads three planes of bytes or an NV source, k_sws_c24 three planes of bytes */
                     if (key.kernel == SWS_KERNEL_IDENT1_1) { sws_launch_ident1<false, C == SWS_SRC_NV, DST>(op); return true; }
                     if (key.kernel == SWS_KERNEL_IDENT1_X) { sws_launch_ident1<true, C == SWS_SRC_NV, DST>(op); return true; }
-                    if constexpr (C == SWS_SRC_P8) {
+                    if constexpr (C == SWS_SRC_P8 && DST != DST_YUY2) {          /* (no special converter writes a packed 4:2:2 order) */
                         if (key.kernel == SWS_KERNEL_C24) { sws_launch_c24<0, DST>(op); return true; }
                         if (key.kernel == SWS_KERNEL_C24_422) { sws_launch_c24<1, DST>(op); return true; }
                     }

@@ -157,109 +157,7 @@ namespace {
  * the staged line holds the picked bytes, so every instance has the LDS, the waves per SIMD and the workgroups per CU of its 8-bit yuv422p twin. */
 static_assert(stage_bytes<SwsPxYuy2>() == STAGE_BYTES, "the twins' staging lines");
 
-/* ---- equal size to a packed RGB destination: k_sws_ident1's _1 form straight from the packed bytes ---------------------------------------------
- * The reference has no special converter from these sources to RGB: its scaler runs with identity horizontal filters and ONE vertical luma tap, and
- * with chroma on every source line the chroma filter has one or two taps — yuv2rgb24_1_c and its kin (output.c:1043-1110): Y = the luma byte, U / V
- * the first chroma line's byte, or the mean of two lines where the row's second coefficient is >= 2048.  k_sws_ident1's grid, tile and LUT copy; a
- * thread's eight samples of a row are 16 source bytes that hold luma AND chroma — one 16-byte load on a plane of 16-byte multiples, four dwords on
- * one of 4-byte multiples; a chroma tap line other than the luma line (uniform over the row's wave) is loaded the same way.  Ragged rows, and planes
- * on neither multiple, go byte by byte.  A kernel of its own name: another template parameter of k_sws_ident1 would rename its existing instances.
- * With chroma on every line no context of these sources reaches the X template (more than two chroma taps): sws.hip sends such a one to the tile. */
-template <int DST>
-__global__ void __launch_bounds__(NT) k_sws_ident1_yuy2(const SwsDev *cp, const mi355_sws_frame *frames)
-{
-    __shared__ LutLds s_lut;
-    constexpr int NC = 2;
-    constexpr int BPP = dst_bpp<DST>();
-    const uint32_t sel = DST == DST_RGB32 ? cp->dst_sel : 0u;
-    const int tid = threadIdx.x;
-    const int dstW = cp->dstW, dstH = cp->dstH, cs = cp->vcs, srcH = cp->srcH, chrSrcH = cp->chrSrcH, layout = cp->src_layout;
-    const int32_t *vLumP = mi355_global(cp->vLumP), *vChrP = mi355_global(cp->vChrP);
-    const int16_t *vChrC = mi355_global(cp->vChrC);
-    mi355_sws_frame fr = frames[blockIdx.z];
-    fr.src[0] = mi355_global(fr.src[0]);
-    fr.dst = mi355_global(fr.dst);
-    const int x = blockIdx.x * C24_COLS + (tid & 63) * 8;   /* first of the thread's eight samples */
-    const int npairs = dstW >> 1;
-    const bool mine = (x >> 1) < npairs;
-    const uintptr_t sal = reinterpret_cast<uintptr_t>(fr.src[0]) | (uintptr_t)fr.src_stride[0];
-    const bool al16 = (sal & 15) == 0;
-    constexpr uintptr_t DMASK = DST == DST_RGB32 ? 15 : 7;
-    /* the wide form: four whole pairs (x + 8 <= dstW <= srcW: the 16 bytes lie inside the line's 2 * srcW) */
-    const bool wide = mine && (x >> 1) + 4 <= npairs && (sal & 3) == 0 && ((reinterpret_cast<uintptr_t>(fr.dst) | (uintptr_t)fr.dst_stride) & DMASK) == 0;
-    const bool uy = sws_yuy2_luma(layout) != 0, vu = layout == MI355_SWS_SRC_YVYU422;
-    constexpr int NR = IDENT_ROWS / (NT / 64);
-    int li[NR], ci[NR][NC], cf1[NR];
-    uint32_t wl[NR][4], wc[NR][NC][4];
-    auto load16 = [&](const uint8_t *p, uint32_t *w) {
-        if (al16) {
-            const sws_u32x4 v = *reinterpret_cast<const sws_u32x4 *>(p);
-            w[0] = v[0]; w[1] = v[1]; w[2] = v[2]; w[3] = v[3];
-        } else {
-#pragma unroll
-            for (int d = 0; d < 4; d++) w[d] = reinterpret_cast<const uint32_t *>(p)[d];
-        }
-    };
-#pragma unroll
-    for (int q = 0; q < NR; q++) {
-        /* rows past the picture repeat its last row and are not written; a tap past the filter reads tap 0 */
-        const int gy = imin(blockIdx.y * IDENT_ROWS + (tid >> 6) + q * (NT / 64), dstH - 1);
-        li[q] = clampi(vLumP[gy], 0, srcH - 1);
-        const int cfirst = imax(1 - cs, vChrP[gy]);
-        cf1[q] = cs > 1 ? vChrC[(size_t)gy * cs + 1] : 0;
-#pragma unroll
-        for (int j = 0; j < NC; j++) ci[q][j] = clampi(cfirst + (j < cs ? j : 0), 0, chrSrcH - 1);
-#pragma unroll
-        for (int d = 0; d < 4; d++) wl[q][d] = 0;
-        if (wide) load16(fr.src[0] + (size_t)li[q] * fr.src_stride[0] + 2 * (size_t)x, wl[q]);
-#pragma unroll
-        for (int j = 0; j < NC; j++) {
-#pragma unroll
-            for (int d = 0; d < 4; d++) wc[q][j][d] = wl[q][d];
-            if (wide && ci[q][j] != li[q]) load16(fr.src[0] + (size_t)ci[q][j] * fr.src_stride[0] + 2 * (size_t)x, wc[q][j]);
-        }
-    }
-    MI355_ISSUE_FENCE();
-    lut_load(s_lut, &cp->luts, tid);
-    __syncthreads();
-    if (!mine) return;
-#pragma unroll
-    for (int q = 0; q < NR; q++) {
-        const int gy = blockIdx.y * IDENT_ROWS + (tid >> 6) + q * (NT / 64);
-        if (gy >= dstH) break;
-        uint8_t *d = fr.dst + (size_t)gy * fr.dst_stride + (size_t)x * BPP;
-        const bool mean = cs > 1 && cf1[q] >= 2048;
-        if (wide) {
-            int Y[8], r[4], g[4], b[4];
-            const uint32_t ya[2] = { uy ? sws_odd4(wl[q][0], wl[q][1]) : sws_even4(wl[q][0], wl[q][1]), uy ? sws_odd4(wl[q][2], wl[q][3]) : sws_even4(wl[q][2], wl[q][3]) };
-            uint32_t u[NC], v[NC];
-#pragma unroll
-            for (int j = 0; j < NC; j++) {
-                const uint32_t *w = wc[q][j];
-                const uint32_t c01 = uy ? sws_even4(w[0], w[1]) : sws_odd4(w[0], w[1]), c23 = uy ? sws_even4(w[2], w[3]) : sws_odd4(w[2], w[3]);
-                const uint32_t e = sws_even4(c01, c23), o = sws_odd4(c01, c23);
-                u[j] = vu ? o : e; v[j] = vu ? e : o;
-            }
-#pragma unroll
-            for (int p = 0; p < 4; p++) {
-                const int u0 = (u[0] >> (8 * p)) & 0xFF, u1 = (u[1] >> (8 * p)) & 0xFF, v0 = (v[0] >> (8 * p)) & 0xFF, v1 = (v[1] >> (8 * p)) & 0xFF;
-                const uint32_t w = ya[p >> 1] >> (16 * (p & 1));
-                Y[2 * p] = (int)(w & 0xFF); Y[2 * p + 1] = (int)((w >> 8) & 0xFF);
-                lut_rows_d<DST>(s_lut, mean ? (u0 + u1) >> 1 : u0, mean ? (v0 + v1) >> 1 : v0, r[p], g[p], b[p]);
-            }
-            if constexpr (DST == DST_RGB32) rgb32_store8(s_lut, d, Y, r, g, b, sel);
-            else rgb24_store8(s_lut, d, Y, r, g, b);
-        } else {
-            const int lo = sws_yuy2_luma(layout), uo = sws_yuy2_u(layout), vo = sws_yuy2_v(layout);
-            const uint8_t *py = fr.src[0] + (size_t)li[q] * fr.src_stride[0] + 2 * (size_t)x;
-            for (int p = 0; p < 4 && (x >> 1) + p < npairs; p++) {
-                const uint8_t *p0 = fr.src[0] + (size_t)ci[q][0] * fr.src_stride[0] + 2 * (size_t)x + 4 * p, *p1 = fr.src[0] + (size_t)ci[q][1] * fr.src_stride[0] + 2 * (size_t)x + 4 * p;
-                const int U = mean ? (p0[uo] + p1[uo]) >> 1 : p0[uo], V = mean ? (p0[vo] + p1[vo]) >> 1 : p0[vo];
-                write_pair_d<DST>(s_lut, d + 2 * BPP * p, py[4 * p + lo], py[4 * p + lo + 2], U, V, sel);
-            }
-        }
-    }
-}
+/* (k_sws_ident1_yuy2, the equal-size form of these sources, is sws_dev.h's: sws_yuy2dst.hip compiles its packed 4:2:2 destination) */
 }  // namespace
 
 bool mi355_sws_launch_yuy2(const SwsKey &key, const SwsOperands &op)
@@ -274,7 +172,7 @@ bool mi355_sws_launch_yuy2(const SwsKey &key, const SwsOperands &op)
         return true;
     }
     if (key.kernel == SWS_KERNEL_IDENT1_1)
-        return sws_pick_dst(key.dst, [&](auto dst) {
+        return sws_pick_dst_rgb(key.dst, [&](auto dst) {
             hipLaunchKernelGGL(k_sws_ident1_yuy2<decltype(dst)::value>, op.grid, dim3(NT), 0, op.s, dev, static_cast<const mi355_sws_frame *>(op.frames));
             return true;
         });

@@ -65,9 +65,15 @@ def main():
                     help="the unscaled splitter of the packed 4:2:2 sources beside k_sws_nv12_split at the same size on the same build: 1080p uyvy422 -> "
                          "yuv420p (3.5 bytes a pixel against the twin's 3) and 1080p yuyv422 -> yuv422p (4 against 3); the twin a second time in another "
                          "allocation (A/A); 32 and 512 pictures per launch, 3 warm-up + --steps launches a round, alternating, median of --rounds rounds")
+    ap.add_argument("--yuy2dst", action="store_true",
+                    help="packed 4:2:2 destinations beside THE SAME descriptor with an rgb24 destination on the same build — identical banks and source, two "
+                         "bytes a pixel written where rgb24 writes three, no table lookups: 2160p -> 1080p yuv420p -> yuyv422 and nv12 -> uyvy422, 1080p "
+                         "yuv420p -> yuyv422 at equal size (k_sws_ident1); the unscaled packer 1080p yuv422p -> yuyv422 beside k_sws_nv12_pack at the same "
+                         "size (4 bytes a pixel against 3); the twin a second time in another allocation (A/A); 32 and 512 pictures per launch, 3 warm-up + "
+                         "--steps launches a round, alternating, median of --rounds rounds")
     ap.add_argument("--other-lib", default=None,
                     help="--nv12 / --nvsrc / --rgbsrc / --range / --rgb32src: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
-    ap.add_argument("--rounds", type=int, default=5, help="--planar / --sources / --yuy2src: alternating rounds (the median is reported)")
+    ap.add_argument("--rounds", type=int, default=5, help="--planar / --sources / --yuy2src / --yuy2dst: alternating rounds (the median is reported)")
     a = ap.parse_args()
     prov = providers.mi355()
     lib = prov.lib
@@ -93,6 +99,8 @@ def main():
         return rgb32src_points(a, lib)
     if a.yuy2src:
         return yuy2src_points(a, lib)
+    if a.yuy2dst:
+        return yuy2dst_points(a, lib)
     orc = S.oracle_backend(providers.oracle())
     for name in a.configs.split(","):
         ctx = S.load_context(name)
@@ -974,6 +982,93 @@ def yuy2src_points(a, lib, points=None, frame_counts=(32, 512), scaled=None):
     aa = max(r["aa_spread"] for r in rows)
     miss = ["%s@%d %+.1f%% (bound %+.1f%%)" % (r["workload"], r["frames_per_launch"], 100 * r["vs_twin"], 100 * (r["bound"] + aa)) for r in rows if r["vs_twin"] > r["bound"] + aa]
     print(json.dumps({"summary": "yuy2src", "aa_session": aa, "points": len(rows), "miss": miss}), flush=True)
+
+
+def yuy2dst_points(a, lib, points=None, frame_counts=(32, 512), scaled=None):
+    """Packed 4:2:2 destinations.  The scaler's points run beside their rgb24 twin — the context of the SAME descriptor and source to rgb24, on the same
+    pictures: the same horizontal pass and the same vertical sums, two bytes a pixel written where the twin writes three and no table lookups, so
+    `bound` (the ratio of algorithmic bytes) is negative: a point above its twin is a miss.  The unscaled packer (k_sws_yuy2_pack) runs beside
+    k_sws_nv12_pack at the same size — the one kernel of the same kind, an interleaving copy without banks or LDS: yuv420p -> nv12 moves 3 bytes a
+    pixel, yuv422p -> yuyv422 moves 4.  The contexts come from the reference's libswscale at run time (oracle/_ref/libswsref.so:
+    mi355_sws_describe_yuy2dst / _src) — no full-size context is committed.  `twin#2` is the twin a second time with its own buffers: the session's A/A
+    spread.  One process, the batches of a point alternating: 3 warm-up + --steps launches a round, median of --rounds rounds, at 32 and 512 pictures per
+    launch.  Algorithmic bytes: the source read once + the destination written once.  The last line sums the session up: `aa_session` — the largest
+    A/A spread of its points — and under `miss` every row whose time exceeds its twin's times the byte ratio plus that spread."""
+    import statistics
+    import numpy as np
+    import sws_nv12 as N
+    import sws_planar as P
+    import sws_sources as X
+    import sws_yuy2dst as Z
+    ref = Z.Ref(P.bind(Z.REF_LIB))
+    # (point, srcW, srcH, source, destination order): the packer
+    points = points or [("hd_pack_yuv422p_yuyv", 1920, 1080, "yuv422p", "yuyv")]
+    # (point, srcW, srcH, dstW, dstH, source, destination order): the scaler's points and the ident1 point
+    scaled = scaled if scaled is not None else [("uhd_to_hd_yuv420p_yuyv", 3840, 2160, 1920, 1080, "yuv420p", "yuyv"), ("uhd_to_hd_nv12_uyvy", 3840, 2160, 1920, 1080, "nv12", "uyvy"),
+                                                ("hd_same_yuv420p_yuyv", 1920, 1080, 1920, 1080, "yuv420p", "yuyv")]
+    rows = []
+
+    def report(point, frames, batches, plan, times):
+        base = statistics.median(times["twin"])
+        spread = abs(statistics.median(times["twin#2"]) / base - 1.0)
+        twin_bytes = batches["twin"].src_bytes + batches["twin"].dst_bytes
+        for k, b in batches.items():
+            ms = statistics.median(times[k])
+            us = ms * 1e3 / frames
+            nb = b.src_bytes + b.dst_bytes
+            out = {"workload": point + ":" + k, "frames_per_launch": frames, "ms_per_launch": ms, "us_per_picture": us, "frames_per_s": 1e6 / us,
+                   "algorithmic_bytes_per_frame": nb, "achieved_GBps": nb / us * 1e-3, "frac_of_8TBps": nb / us * 1e-3 / 8000.0,
+                   "vs_twin": ms / base - 1.0, "bound": nb / twin_bytes - 1.0, "aa_spread": spread, "ms_rounds": [round(x, 4) for x in times[k]]}
+            if k not in ("twin", "twin#2"):
+                out.update({"kernel": plan["kernel"], "hstaged": plan["hstaged"], "narrow": plan["narrow"]})
+            rows.append(out)
+            print(json.dumps(out), flush=True)
+
+    def measure(batches):
+        times = {k: [] for k in batches}
+        for _ in range(a.rounds):
+            for k, b in batches.items():
+                times[k].append(time_ms(lib, b.run, a.steps))
+        return times
+
+    for frames in frame_counts:
+        for point, sw, sh, src, dst in points:
+            row = (sw, sh, sw, sh, src, 0, dst, 0, 1, 1, 1, 0)               # a row of tests/sws_yuy2dst.py's form, not entered into its table
+            c = ref.open(row)
+            e = ref.describe_yuy2dst(c)
+            ref.free(c)
+            c = ref.open_formats(sw, sh, b"yuv420p", sw, sh, b"nv12", ref.flags(row))
+            t = ref.describe_src(c)
+            ref.free(c)
+            assert e is not None and e.ctx.desc.unscaled_special and t is not None and t.ctx.desc.unscaled_special and t.fmt == 16, point
+            ypics = [[np.ascontiguousarray(pl) for pl in Z.picture(row, "noise", seed=s)] for s in (1, 2)]
+            trow = (sw, sh, sw, sh, "yuv420p", 0, dst, 0, 1, 1, 1, 0)
+            tpics = [[np.ascontiguousarray(pl) for pl in Z.picture(trow, "noise", seed=s)] for s in (1, 2)]
+            tsizes = [(sw, sh), (2 * (sw // 2), sh // 2)]
+            batches = {"pack": SourceBatch(lib, None, e, ypics, frames, create=Z.create, bpp=2),
+                       "twin": PlaneBatch(lib, X.create(lib, t), tpics, tsizes, frames), "twin#2": PlaneBatch(lib, X.create(lib, t), tpics, tsizes, frames)}
+            plan = Z.plan_of(lib, batches["pack"].handle)
+            assert plan["kernel"] == "yuy2_pack" and N.KERNELS[9] == "nv12_pack", plan
+            report(point, frames, batches, plan, measure(batches))
+            for b in batches.values():
+                b.close()
+        for point, sw, sh, dw, dh, src, dst in scaled:
+            row = (sw, sh, dw, dh, src, 0, dst, 0, 1, 1, 1, 0)
+            c = ref.open(row)
+            e = ref.describe_yuy2dst(c)
+            ref.free(c)
+            assert e is not None and not e.ctx.desc.unscaled_special and dw % 2 == 0, point
+            t = Z.twin_entry(e)
+            pics = [[np.ascontiguousarray(pl) for pl in Z.picture(row, "noise", seed=s)] for s in (1, 2)]
+            batches = {dst + "422": SourceBatch(lib, None, e, pics, frames, create=Z.create, bpp=2),
+                       "twin": SourceBatch(lib, None, t, pics, frames, create=Z.create, bpp=3), "twin#2": SourceBatch(lib, None, t, pics, frames, create=Z.create, bpp=3)}
+            plan = Z.plan_of(lib, batches[dst + "422"].handle)
+            report(point, frames, batches, plan, measure(batches))
+            for b in batches.values():
+                b.close()
+    aa = max(r["aa_spread"] for r in rows)
+    miss = ["%s@%d %+.1f%% (bound %+.1f%%)" % (r["workload"], r["frames_per_launch"], 100 * r["vs_twin"], 100 * (r["bound"] + aa)) for r in rows if r["vs_twin"] > r["bound"] + aa]
+    print(json.dumps({"summary": "yuy2dst", "aa_session": aa, "points": len(rows), "miss": miss}), flush=True)
 
 
 if __name__ == "__main__":
