@@ -108,6 +108,14 @@
  *                          SWS_FAST_BILINEAR scaled contexts, SWS_FULL_CHR_H_INT / _INP where the describers above decline them, alpha / YUVA,
  *                          other sources, and contexts without banks that are not one of the four packers (the plain copy of a packed 4:2:2
  *                          source to its own order; to another order the reference runs its scaler, and that context is taken).  The nine describers above keep declining these destinations.
+ *   p010le sources         (the reference runs p010LEToY_c / p010LEToUV_c on each line, word >> 6, then hScale16To15_c with depth 10; it has NO unscaled
+ *                          converter from P010, so every context is the generic scaler's) have the eleventh describer, mi355_sws_describe_p010(), for
+ *                          mi355_sws_create_src_layout_range_depth(): to every destination above, the packed 4:2:2 ones included, with the range read
+ *                          from the converters the context holds.  Bound like a 32-bit source: whole pictures through mi355_swsfunc, TWO source planes
+ *                          (described again at every picture; one the creators refuse stays the reference's).  With MI355_SWS_LINES=1 the two input
+ *                          converters go to mi355_sws_p010ToY / _p010ToUV, the horizontal loops to mi355_sws_hscale16to15.  Declined: p010be,
+ *                          SWS_FULL_CHR_H_INT, a chroma line drop, YUVA destinations (SWS_FAST_BILINEAR leaves a 16-bit source on hScale16To15_c with
+ *                          bilinear banks: taken).  The ten describers above keep declining it.
  * The device is MI355_DEVICE (default 0), as for the decoder bridges.
  */
 #include <pthread.h>
@@ -718,6 +726,70 @@ int mi355_sws_describe_yuy2dst(struct SwsContext *c, mi355_sws_desc *d, mi355_sw
     return 0;
 }
 
+/* ---- P010 sources: p010le -----------------------------------------------------------------------------------------------------------------
+ * the input converters the context HOLDS are word >> 6 of a little-endian word, U from the first and V from the second word of a pair (the functions are
+ * static in the reference: one pair of distinct words through each, as yuy2_probe does; the big-endian forms give other values) */
+static int p010_probe(const SwsContext *c)
+{
+    static const uint8_t b[8] = { 0xC1, 0x12, 0x83, 0x34, 0x45, 0x56, 0x07, 0x78 };      /* 0x12C1 0x3483 0x5645 0x7807 */
+    uint16_t y[2] = { 0 }, u[2] = { 0 }, v[2] = { 0 };
+    if (!c->lumToYV12 || !c->chrToYV12 || c->alpToYV12) return -1;
+    c->lumToYV12((uint8_t *)y, b, 1, NULL);
+    c->chrToYV12((uint8_t *)u, (uint8_t *)v, b, b, 1, NULL);
+    return y[0] == (0x12C1 >> 6) && u[0] == (0x12C1 >> 6) && v[0] == (0x3483 >> 6) ? 0 : -1;
+}
+/* what mi355_sws_create_src_layout_range_depth takes for a live context FROM p010le (0), -1 for every other context — the describers above keep declining
+ * this source.  The reference has no unscaled converter from P010 (swscale_unscaled.c:1162-1167 keeps it off the plane copy too): a context without the
+ * banks is declined.  The generic scaler's contexts: both input converters (p010LEToY_c / p010LEToUV_c, p010_probe), no other reader, srcBpc 10, no
+ * alpha; to rgb24, bgr24, the four 32-bit orders and the three packed 4:2:2 orders (the descriptor's rgb24 form: vChr.n = dstH), to 8-bit planar /
+ * semi-planar YUV, to 9- / 10-bit planar YUV; with the range the context's converters give (range_probe) to the 8-bit YUV destinations, the packed 4:2:2
+ * ones included.  Declined: p010be, SWS_FULL_CHR_H_INT, the fast bilinear horizontal functions (the reference sets them for 8-bit sources only), a chroma
+ * line drop, YUVA destinations, 15 / 16-bit RGB */
+int mi355_sws_describe_p010(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *src_layout, int *dst_format, int *range, int *dst_depth)
+{
+    int fmt, bits = 8, r;
+    if (c->srcFormat != AV_PIX_FMT_P010LE || c->chrSrcHSubSample != 1 || c->chrSrcVSubSample != 1) return -1;
+    if (!c->vLumFilter || !c->vChrFilter || !c->hLumFilter || !c->hChrFilter) return -1;
+    if (c->hyscale_fast || c->hcscale_fast || c->vChrDrop || (c->flags & SWS_FULL_CHR_H_INT)) return -1;
+    if (c->srcBpc != 10 || c->readLumPlanar || c->readChrPlanar || c->readAlpPlanar || c->alpPixBuf) return -1;
+    if (p010_probe(c) != 0) return -1;
+    r = range_probe(c);
+    if (r < 0) return -1;
+    if (deep_dst(c, &bits)) {
+        if (r || c->dstBpc != bits) return -1;
+        fmt = deep_dst(c, &bits);
+    } else if (packed_dst_of(c) || c->dstFormat == AV_PIX_FMT_RGB24) {
+        if (r) return -1;
+        fmt = packed_dst_of(c);
+    } else if (yuy2_dst_of(c)) {
+        fmt = yuy2_dst_of(c);
+    } else {
+        switch (c->dstFormat) {
+        case AV_PIX_FMT_YUV420P: fmt = MI355_SWS_DST_YUV420P; break;
+        case AV_PIX_FMT_YUV422P: fmt = MI355_SWS_DST_YUV422P; break;
+        case AV_PIX_FMT_YUV444P: fmt = MI355_SWS_DST_YUV444P; break;
+        case AV_PIX_FMT_NV12:    fmt = MI355_SWS_DST_NV12; break;
+        case AV_PIX_FMT_NV21:    fmt = MI355_SWS_DST_NV21; break;
+        default: return -1;
+        }
+    }
+    const int yuv = fmt >= MI355_SWS_DST_YUV420P && fmt <= MI355_SWS_DST_NV21;
+    memset(s, 0, sizeof(*s));
+    s->depth = 10; s->hsub = 1; s->vsub = 1;
+    memcpy(s->dither, ff_dither_8x8_128, sizeof(s->dither));      /* the rows should_dither selects (swscale.c:553-556) */
+    memset(d, 0, sizeof(*d));
+    d->srcW = c->srcW; d->srcH = c->srcH; d->dstW = c->dstW; d->dstH = c->dstH;
+    d->chrSrcW = c->chrSrcW; d->chrSrcH = c->chrSrcH; d->chrDstW = c->chrDstW;
+    d->hLum = (mi355_sws_filter){ c->hLumFilter, c->hLumFilterPos, c->hLumFilterSize, c->dstW };
+    d->hChr = (mi355_sws_filter){ c->hChrFilter, c->hChrFilterPos, c->hChrFilterSize, c->chrDstW };
+    d->vLum = (mi355_sws_filter){ c->vLumFilter, c->vLumFilterPos, c->vLumFilterSize, c->dstH };
+    d->vChr = (mi355_sws_filter){ c->vChrFilter, c->vChrFilterPos, c->vChrFilterSize, yuv ? c->chrDstH : c->dstH };
+    if (!fmt) luts_of(c, &d->luts);
+    else if (!yuv && !yuy2_dst_of(c)) luts_packed(c, fmt, &d->luts);
+    *src_layout = MI355_SWS_SRC_P010; *dst_format = fmt; *range = r; *dst_depth = bits;
+    return 0;
+}
+
 #ifndef MI355_SWS_DESCRIBE_ONLY
 static void t1_hscale16(SwsContext *c, int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
 {
@@ -1008,10 +1080,47 @@ static int init_yuy2dst(SwsContext *c)
     return 1;
 }
 
+/* ... of a p010le source (p010LEToY_c / p010LEToUV_c): the output lines are host-order uint16_t */
+static void t1_p010ToY(uint8_t *dst, const uint8_t *src, int width, uint32_t *pal) { (void)pal; n_calls++; mi355_sws_p010ToY((uint16_t *)dst, src, width); }
+static void t1_p010ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src1, const uint8_t *src2, int width, uint32_t *pal)
+{ (void)src2; (void)pal; n_calls++; mi355_sws_p010ToUV((uint16_t *)dstU, (uint16_t *)dstV, src1, width); }
+/* the inner loops of a context from a p010le source (mi355_sws_describe_p010 takes it): the two input converters, the 16-bit horizontal loops (srcBpc 10),
+ * the range converters and the output loops of its destination */
+static int init_p010(SwsContext *c)
+{
+    mi355_sws_desc d;
+    mi355_sws_src s;
+    int layout, fmt, range, depth;
+    if (c->srcFormat != AV_PIX_FMT_P010LE) return 0;
+    /* (returning 1 for a context this describer declines is deliberate: ff_sws_init_mi355x ends there, no other describer takes this source) */
+    if (mi355_sws_describe_p010(c, &d, &s, &layout, &fmt, &range, &depth) != 0 || !device_ready() || !c->hyScale || !c->hcScale) return 1;
+    const int yuv = fmt >= MI355_SWS_DST_YUV420P && fmt <= MI355_SWS_DST_NV21;
+    if (yuv ? (!c->yuv2planeX || !c->yuv2plane1) : (!c->yuv2packedX || !c->yuv2packed2 || !c->yuv2packed1)) return 1;
+    c->lumToYV12 = t1_p010ToY; c->chrToYV12 = t1_p010ToUV;
+    c->hyScale = c->hcScale = t1_hscale16;
+    if (range > 0) {
+        c->lumConvertRange = range == MI355_SWS_RANGE_TO_JPEG ? t1_lumToJpeg : t1_lumFromJpeg;
+        c->chrConvertRange = range == MI355_SWS_RANGE_TO_JPEG ? t1_chrToJpeg : t1_chrFromJpeg;
+    }
+    if (yuv) {
+        c->yuv2planeX = depth == 9 ? t1_planeX_9 : (depth == 10 ? t1_planeX_10 : t1_planeX);
+        c->yuv2plane1 = depth == 9 ? t1_plane1_9 : (depth == 10 ? t1_plane1_10 : t1_plane1);
+        if (c->yuv2nv12cX) c->yuv2nv12cX = t1_nv12cX;
+    } else if (!fmt) {
+        c->yuv2packedX = t1_packedX; c->yuv2packed2 = t1_packed2; c->yuv2packed1 = t1_packed1;
+    } else if (yuy2_dst_of(c)) {
+        c->yuv2packedX = t1_y2X; c->yuv2packed2 = t1_y22; c->yuv2packed1 = t1_y21;
+    } else {
+        c->yuv2packedX = t1_pkX; c->yuv2packed2 = t1_pk2; c->yuv2packed1 = t1_pk1;
+    }
+    return 1;
+}
+
 void ff_sws_init_mi355x(SwsContext *c)
 {
     mi355_sws_src s;
     int layout;
+    if (init_p010(c)) return;
     if (init_yuy2dst(c)) return;
     if (init_rgb32(c)) return;
     if (init_yuy2(c)) return;
@@ -1079,7 +1188,8 @@ typedef struct Bound {
     int packed;                   /* ... MI355_SWS_DST_BGR24 ... _ABGR of a packed destination beside rgb24 (mi355_sws_describe_packed), else 0; planar is 0 then */
     int rgb32;                    /* 1: a 32-bit source (mi355_sws_describe_rgb32: layout, planar / packed, range and depth above are what it gave) ...;
                                    * 2: a packed 4:2:2 source in the generic scaler (mi355_sws_describe_yuy2, the same fields; never alpha);
-                                   * 3: a packed 4:2:2 DESTINATION from any source (mi355_sws_describe_yuy2dst, the same fields; packed is its format, no tables) */
+                                   * 3: a packed 4:2:2 DESTINATION from any source (mi355_sws_describe_yuy2dst, the same fields; packed is its format, no tables);
+                                   * 4: a p010le source to any destination (mi355_sws_describe_p010, the same fields; TWO source planes; never alpha) */
     int alpha;                    /* ... whose alpha goes to the 32-bit destination (mi355_sws_create_src_layout_alpha) */
     mi355_sws_ctx *dev;
     int failed;                   /* the device side does not take this context: the reference's function from now on */
@@ -1129,6 +1239,15 @@ static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
 {
     int planar = special ? 0 : planar_format(c), other = 0, layout = MI355_SWS_SRC_PLANAR, range = MI355_SWS_RANGE_NONE, depth = 8, packed = 0;
     int rgb32 = 0, alpha = 0;
+    if (!special && c->srcFormat == AV_PIX_FMT_P010LE) {
+        /* a p010le source: one describer for every destination it goes to, the packed 4:2:2 ones included (every such context is the generic scaler's) */
+        mi355_sws_desc d;
+        mi355_sws_src s;
+        int fmt;
+        if (mi355_sws_describe_p010(c, &d, &s, &layout, &fmt, &range, &depth) != 0) return real;
+        rgb32 = 4; other = 1;
+        if (fmt >= MI355_SWS_DST_BGR24) packed = fmt; else planar = fmt;
+    } else
     if (!special && yuy2_dst_of(c)) {
         /* a packed 4:2:2 destination: one describer for every source it comes from.  Only the generic scaler's contexts get here (the four unscaled
          * packers are set without a selector) */
@@ -1211,7 +1330,8 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
     mi355_sws_desc d32;
     mi355_sws_src s32;
     int l32 = 0, f32 = 0, r32 = 0, dp32 = 8, a32 = 0;
-    const int rgb32_ok = b && b->rgb32 && (b->rgb32 == 3 ? mi355_sws_describe_yuy2dst(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 && !d32.unscaled_special :
+    const int rgb32_ok = b && b->rgb32 && (b->rgb32 == 4 ? mi355_sws_describe_p010(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 :
+                                           b->rgb32 == 3 ? mi355_sws_describe_yuy2dst(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 && !d32.unscaled_special :
                                            b->rgb32 == 2 ? mi355_sws_describe_yuy2(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 && !d32.unscaled_special
                                                          : mi355_sws_describe_rgb32(c, &d32, &s32, &l32, &f32, &r32, &dp32, &a32) == 0) && l32 == b->layout &&
                          f32 == (b->packed ? b->packed : b->planar) && r32 == b->range && dp32 == b->depth && a32 == b->alpha;
@@ -1228,7 +1348,7 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
     if (b && !b->failed && srcSliceY == 0 && srcSliceH == c->srcH &&
         srcStride[0] > 0 && (one_plane || srcStride[1] > 0) && (b->layout || srcStride[2] > 0) && dstStride[0] > 0 && (!b->planar || planar_ok) && other_ok) {
         if (b->dev && !b->busy && !b->planar && !b->packed && (memcmp(b->y_table, c->yuvTable, 1024) || b->gv0 != c->table_gV[0])) { mi355_sws_destroy(b->dev); b->dev = NULL; }
-        if (b->dev && !b->busy && b->packed && b->rgb32 != 3) {      /* (a packed 4:2:2 destination has no tables) */
+        if (b->dev && !b->busy && b->packed && b->rgb32 != 3 && b->packed < MI355_SWS_DST_YUYV422) {      /* (a packed 4:2:2 destination has no tables) */
             /* the tables in the form the device context was built from (a 32-bit order's first 1024 table BYTES are 256 entries below every colour) */
             mi355_sws_luts now;
             luts_packed(c, b->packed, &now);
@@ -1261,7 +1381,7 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
             } else if (b->planar) {
                 if (device_ready() && mi355_sws_describe_planar(c, &d, &fmt) == 0) b->dev = mi355_sws_create_planar(&d, fmt);
             } else if (device_ready() && describe(c, &d, b->special) == 0) b->dev = mi355_sws_create(&d);
-            if (b->dev && b->rgb32 == 3) ;
+            if (b->dev && (b->rgb32 == 3 || b->packed >= MI355_SWS_DST_YUYV422)) ;
             else if (b->dev && b->packed) { memcpy(b->y_table, d.luts.y_table, 1024); b->gv0 = c->table_gV[0]; }
             else if (b->dev && !b->planar) { memcpy(b->y_table, c->yuvTable, 1024); b->gv0 = c->table_gV[0]; }
             else if (!b->dev) b->failed = 1;

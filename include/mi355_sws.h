@@ -13,7 +13,8 @@
  * of these, with the reference's four unscaled converters yuyv422 / uyvy422 -> yuv420p / yuv422p (yuyvToYuv420Wrapper ... uyvyToYuv422Wrapper
  * swscale_unscaled.c:227-287); and TO packed 4:2:2 yuyv422 / uyvy422 / yvyu422 (yuv2422_X / _2 / _1_c_template output.c:451-582), from every source
  * rgb24 is written from, with range conversion, and the reference's four unscaled packers yuv422p / yuv420p -> yuyv422 / uyvy422
- * (yuv422pToYuy2Wrapper, yuv422pToUyvyWrapper, planarToYuy2Wrapper, planarToUyvyWrapper swscale_unscaled.c:179-225).
+ * (yuv422pToYuy2Wrapper, yuv422pToUyvyWrapper, planarToYuy2Wrapper, planarToUyvyWrapper swscale_unscaled.c:179-225); and from p010le sources
+ * (p010LEToY_c / p010LEToUV_c input.c:499-524 in front of hScale16To15_c, depth 10) to every destination the yuv420p10le source takes.
  *
  * The reference keeps these behind function pointers of the (private) SwsContext
  * (libswscale/swscale_internal.h:253-540): hyScale/hcScale :526-531, yuv2plane1/yuv2planeX/
@@ -278,6 +279,32 @@ int mi355_sws_alpha(const mi355_sws_ctx *ctx);   /* 0 / 1, -1 bad argument */
  * formats: a pixel pair may start on an odd address).  The Tier-1 host entry points return -1 for src_stride[0] < 2 * srcW. */
 enum { MI355_SWS_SRC_YUYV422 = 16, MI355_SWS_SRC_UYVY422 = 17, MI355_SWS_SRC_YVYU422 = 18 };
 
+/* ---- P010 sources: p010le (what hardware decoders and 10-bit HEVC / AV1 pipelines hand over; the reference's p010LEToY_c / p010LEToUV_c
+ * input.c:499-524 in front of hScale16To15_c with depth 10.  A source only in the reference, utils.c:205-206, and without any unscaled converter: it is
+ * even kept off the plane copy, swscale_unscaled.c:1162-1167 — every P010 context, equal size included, is a context of the generic scaler) ----
+ * layout 24 of mi355_sws_create_src_layout and of every creator that forwards to it (3, 6, 7, 12 .. 15, 19 .. 23 and 25 and up stay refused; p010be is
+ * not taken, no big-endian format is).  The source record is that of a 10-bit 4:2:0 source: src->depth 10, src->hsub 1, src->vsub 1,
+ * desc->chrSrcW == AV_CEIL_RSHIFT(srcW, 1), desc->chrSrcH == AV_CEIL_RSHIFT(srcH, 1); src->dither is read for an 8-bit planar / semi-planar destination,
+ * as for any deep source (anything else: NULL and a message).  desc->unscaled_special = 1 is refused with a message: the reference has no wrapper from
+ * P010.  mi355_sws_create_src_layout_alpha with alpha 1 refuses the layout.
+ * Frames stay mi355_sws_frame / mi355_sws_planar_frame through the four scale entry points: src[0] is the luma plane, srcW little-endian uint16_t on
+ * each of srcH rows; src[1] is the pair plane, chrSrcW pairs U V of uint16_t — four bytes a pair — on chrSrcH rows; src[2] and src_stride[2] are never
+ * read and may be NULL / 0.  Pointers and strides are bytes and must be even: the Tier-1 host entry points return -1 otherwise, and for a stride below
+ * 2 * srcW or 4 * chrSrcW.
+ * The sample is word >> 6, exactly as the reference's two converters compute it, and EVERY uint16_t value is inside the contract: the low six bits are
+ * dropped, not required to be zero.  (This differs from the planar 9- / 10-bit sources above, whose samples must lie below 1 << depth.)
+ * Destinations: every dst_format the yuv420p10le source takes — 0 and 32 .. 36, 48 .. 50, MI355_SWS_DST_YUV420P / _YUV422P / _YUV444P at 8, 9 and 10
+ * bits, _NV12 / _NV21, and range 1 / 2 to every 8-bit YUV destination, the packed 4:2:2 ones included.  Twin rule: a P010 context has the banks, the
+ * plan (GENERIC_A .. C / PLANAR_A .. C), the narrow / hstage report and the refusals of the planar context with src_layout 0, depth 10, shifts 1, 1
+ * and the same descriptor; like every deep source it is never IDENT1_* or C24, and it is refused exactly where the twin's tiles cannot hold the lines.
+ * mi355_sws_source_layout returns 24, mi355_sws_source 10 / 1 / 1 and hstaged under the rule stated there (the pair plane is de-interleaved as it is
+ * staged: a chroma tile's span fits where the twin's fits).
+ * Read extent and alignment, in bytes as in the paragraph above mi355_sws_frame: a plane whose pointer and stride are multiples of 16 is fetched in
+ * aligned 16-byte pieces and must be readable over its whole stride; a plane on 4-byte multiples is fetched in dwords that lie whole inside the row;
+ * anything else (2-byte multiples: a pair may start at an address that is 2 mod 4) is read sample by sample.  No byte behind 2 * srcW of a luma row or
+ * 4 * chrSrcW of a pair row is read otherwise; with an odd srcW the last pair is ordinary plane content, not a read behind the width. */
+enum { MI355_SWS_SRC_P010 = 24 };
+
 /* ---- range conversion: contexts whose source and destination differ in range, to a YUV destination (yuvj420p <-> yuv420p and their kin:
  * c->srcRange != c->dstRange && !isAnyRGB(c->dstFormat), lumConvertRange / chrConvertRange swscale.c:168-198, :748-766) ----
  * The reference applies the two converters to every horizontally scaled int16 line, between hyScale / hcScale and the vertical pass
@@ -413,6 +440,11 @@ void mi355_sws_rgb32ToA(uint8_t *dst, const uint8_t *src, int width, int layout)
  * MI355_SWS_SRC_YUYV422 ... _YVYU422 (any other value does nothing); `width` OUTPUT samples — ToY reads 2 * width bytes, ToUV 4 * width */
 void mi355_sws_yuy2ToY(uint8_t *dst, const uint8_t *src, int width, int layout);
 void mi355_sws_yuy2ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int width, int layout);
+/* p010LEToY_c / p010LEToUV_c input.c:499-524 (c->lumToYV12 / c->chrToYV12 of a p010le source): `width` OUTPUT samples, host-order uint16_t, each the
+ * little-endian source word >> 6; ToY reads 2 * width bytes, ToUV 4 * width (U from the first, V from the second word of a pair); host pointers at any
+ * address */
+void mi355_sws_p010ToY(uint16_t *dst, const uint8_t *src, int width);
+void mi355_sws_p010ToUV(uint16_t *dstU, uint16_t *dstV, const uint8_t *src, int width);
 /* lumRangeFromJpeg_c / lumRangeToJpeg_c and chrRangeFromJpeg_c / chrRangeToJpeg_c swscale.c:168-198 (c->lumConvertRange / c->chrConvertRange):
  * `width` int16 samples converted in place, any int16 value (a result outside int16 is stored truncated, as the reference stores it) */
 void mi355_sws_lumConvertRange(int16_t *dst, int width, int to_jpeg);

@@ -11,13 +11,15 @@
  * SOURCES to all of these, with the unscaled yuyv422 / uyvy422 -> yuv420p / yuv422p splitter (their tile instances, k_sws_ident1_yuy2, k_sws_yuy2_split
  * and the line entries mi355_sws_yuy2ToY / _yuy2ToUV are sws_yuy2.hip's); and packed 4:2:2 yuyv422 / uyvy422 / yvyu422 DESTINATIONS from every one of these
  * sources wherever rgb24 is written, also with range conversion, with the unscaled yuv422p / yuv420p -> yuyv422 / uyvy422 packer (yuv2422_X / _2 / _1_c_template
- * output.c:451-582; their DST_YUY2 instances and k_sws_yuy2_pack are sws_yuy2dst.hip's).  This file:
+ * output.c:451-582; their DST_YUY2 instances and k_sws_yuy2_pack are sws_yuy2dst.hip's); and p010le SOURCES (MI355_SWS_SRC_P010: a plane of 16-bit words and a
+ * plane of word pairs, the sample word >> 6 — p010LEToY_c / p010LEToUV_c input.c:499-524) to every destination the yuv420p10le source takes (their tile
+ * instances, line kernels and the line entries mi355_sws_p010ToY / _p010ToUV are sws_p010.hip's).  This file:
  * the context, the plan (which kernel a context gets) and the entry points of include/mi355_sws.h.  The device side is sws_dev.h:
  * k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1, k_sws_nv12_pack, k_sws_nv12_split and the k_sws_line_* kernels of the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
  * Launches: sws_key() names a context's instance once (sws_dev.h: SwsKey), sws_run() hands the key to the file that compiles that instance — here
  * the plain and RANGE instances of k_sws_planar and the rgb24 destination of k_sws_generic / k_sws_ident1 / k_sws_c24 for the four classic source
- * classes; sws_deep.hip, sws_packed.hip, sws_rgb32.hip, sws_yuy2.hip and sws_yuy2dst.hip hold the rest, one launch function each — and every file maps the key to its
+ * classes; sws_deep.hip, sws_packed.hip, sws_rgb32.hip, sws_yuy2.hip, sws_yuy2dst.hip and sws_p010.hip hold the rest, one launch function each — and every file maps the key to its
  * instance through the one dispatcher sws_launch() of sws_dev.h.
  */
 #include "mi355_rt.h"
@@ -150,8 +152,10 @@ static int src_bpx(const SwsDev &h) { return rgb32_src(h) ? 4 : 3; }
 static bool yuy2_src(const SwsDev &h) { return sws_yuy2_src(h.src_layout); }
 /* a source of ONE plane whose converted samples are staged (hscale_tile_rgb): packed RGB, or packed 4:2:2 */
 static bool converted_src(const SwsDev &h) { return packed_rgb(h) || yuy2_src(h); }
-/* the layouts the creators take: 0, 1, 2, 4, 5, 8 .. 11 and 16 .. 18 */
-static bool src_layout_taken(int l) { return (l >= MI355_SWS_SRC_PLANAR && l <= MI355_SWS_SRC_BGR24 && l != 3) || sws_rgb32_src(l) || sws_yuy2_src(l); }
+/* a P010 source: p010le, a plane of 16-bit words and a plane of pairs of them, the sample word >> 6 (its tile instances and line entries are sws_p010.hip's) */
+static bool p010_src(const SwsDev &h) { return h.src_layout == MI355_SWS_SRC_P010; }
+/* the layouts the creators take: 0, 1, 2, 4, 5, 8 .. 11, 16 .. 18 and 24 */
+static bool src_layout_taken(int l) { return (l >= MI355_SWS_SRC_PLANAR && l <= MI355_SWS_SRC_BGR24 && l != 3) || sws_rgb32_src(l) || sws_yuy2_src(l) || l == MI355_SWS_SRC_P010; }
 /* a context that does not scale, to rgb24: what k_sws_ident1 takes */
 static bool ident1_shape(const SwsDev &h)
 {
@@ -191,7 +195,8 @@ static void ctx_hfit(mi355_sws_ctx *c, const mi355_sws_desc *desc)
     };
     if (converted_src(h)) c->hfit = fits_rgb(desc->hLum, h.hident_l, TW) || fits_rgb(desc->hChr, h.hident_c, cw);
     else
-    c->hfit = fits(desc->hLum, h.hident_l, TW) || (h.src_layout ? fits_nv(desc->hChr, h.hident_c, cw) : fits(desc->hChr, h.hident_c, cw));
+    /* (a P010 source: the pair plane is de-interleaved as it is staged — U and V each in a line of the planar 16-bit source's chroma geometry) */
+    c->hfit = fits(desc->hLum, h.hident_l, TW) || (h.src_layout && !p010_src(h) ? fits_nv(desc->hChr, h.hident_c, cw) : fits(desc->hChr, h.hident_c, cw));
 }
 static void upload_banks(mi355_sws_ctx *c, const mi355_sws_desc *desc)
 {
@@ -249,6 +254,22 @@ static mi355_sws_ctx *ctx_create(const mi355_sws_desc *desc, const mi355_sws_src
         return nullptr;
     }
     const char *const packed_name = sws_rgb32_src(layout) ? "rgba / bgra / argb / abgr" : "rgb24 / bgr24";
+    if (layout == MI355_SWS_SRC_P010) {
+        /* p010le: 10-bit 4:2:0 (ctx_source has checked chrSrcW / chrSrcH against the shifts).  The reference has no unscaled converter from it, not even the
+         * plane copy (swscale_unscaled.c:1162-1167): every context is the scaler's, with the banks, the plan and the refusals of the yuv420p10le source of
+         * the same descriptor */
+        if (h.depth != 10 || !h.src_hsub || !h.src_vsub) {
+            std::fprintf(stderr, "mi355dsp: %s: a p010 source is 10-bit 4:2:0 (%d bit, shifts %d/%d)\n", who, h.depth, h.src_hsub, h.src_vsub);
+            delete c;
+            return nullptr;
+        }
+        h.src_layout = layout;
+        if (h.special) {
+            std::fprintf(stderr, "mi355dsp: %s: no unscaled special converter takes a p010 source\n", who);
+            delete c;
+            return nullptr;
+        }
+    } else
     if (sws_yuy2_src(layout)) {
         /* packed 4:2:2 (two bytes a pixel): 8 bit, chroma on every line at half the width (ctx_source has checked chrSrcW / chrSrcH against the shifts) */
         if (h.depth != 8 || !h.src_hsub || h.src_vsub) {
@@ -378,7 +399,7 @@ static bool creator_args(const char *who, const mi355_sws_desc *desc, const mi35
 static bool creator_layout(const char *who, int src_layout)
 {
     if (src_layout_taken(src_layout)) return true;
-    std::fprintf(stderr, "mi355dsp: %s: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr / yuyv422 / uyvy422 / yvyu422\n", who, src_layout);
+    std::fprintf(stderr, "mi355dsp: %s: source layout %d is not planar / nv12 / nv21 / rgb24 / bgr24 / rgba / bgra / argb / abgr / yuyv422 / uyvy422 / yvyu422 / p010\n", who, src_layout);
     return false;
 }
 extern "C" mi355_sws_ctx *mi355_sws_create(const mi355_sws_desc *desc)
@@ -558,7 +579,7 @@ static SwsKey sws_key(const mi355_sws_ctx *c, int k)
     else if (k == MI355_SWS_K_IDENT1_X) key.kernel = SWS_KERNEL_IDENT1_X;
     else if (k == MI355_SWS_K_YUY2_PACK) key.kernel = SWS_KERNEL_YUY2_PACK;
     else key.kernel = SWS_KERNEL_YUY2_SPLIT;
-    key.src = rgb32_src(h) ? SWS_SRC_RGB32 : yuy2_src(h) ? SWS_SRC_YUY2 : packed_rgb(h) ? SWS_SRC_RGB24 : h.src_layout ? SWS_SRC_NV : h.depth > 8 ? SWS_SRC_P16 : SWS_SRC_P8;
+    key.src = p010_src(h) ? SWS_SRC_P010 : rgb32_src(h) ? SWS_SRC_RGB32 : yuy2_src(h) ? SWS_SRC_YUY2 : packed_rgb(h) ? SWS_SRC_RGB24 : h.src_layout ? SWS_SRC_NV : h.depth > 8 ? SWS_SRC_P16 : SWS_SRC_P8;
     key.form = semi_planar(h) ? SWS_FORM_SEMI : (h.hshift ? SWS_FORM_HALF : SWS_FORM_FULL);
     key.kind = h.dst_bits > 8 ? SWS_KIND_DEEP : (h.range ? SWS_KIND_RANGE : SWS_KIND_PLAIN);
     key.dst = dst_form(h.packed);
@@ -578,7 +599,8 @@ static dim3 key_grid(const SwsKey &key, const SwsDev &h, int nframes)
  * packed kernels, of the four classic source classes */
 static bool sws_run(const SwsKey &key, const SwsOperands &op)
 {
-    if (key.dst == DST_YUY2) return mi355_sws_launch_yuy2dst(key, op);         /* (from every source class) */
+    if (key.src == SWS_SRC_P010) return mi355_sws_launch_p010(key, op);        /* (to every destination, the packed 4:2:2 orders included) */
+    if (key.dst == DST_YUY2) return mi355_sws_launch_yuy2dst(key, op);         /* (from every other source class) */
     if (key.src == SWS_SRC_RGB32) return mi355_sws_launch_rgb32(key, op);
     if (key.src == SWS_SRC_YUY2) return mi355_sws_launch_yuy2(key, op);
     if (key.kernel == SWS_KERNEL_PLANAR && key.kind == SWS_KIND_DEEP) return mi355_sws_launch_deep(key, op);
@@ -660,8 +682,11 @@ static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int
     /* the packer to a packed 4:2:2 destination: with srcW % 4 == 3 its last group takes the luma byte behind each row in the same way */
     const bool pack3 = h.special && yuy2_dst(h) && (h.srcW & 3) == 3;
     const int nsrc = rgb ? 1 : (h.src_layout ? 2 : 3), tail = pack3 ? 1 : (rgb && h.src_hsub && (h.srcW & 1) ? bpx : 0);
-    const int w[3] = { rgb ? bpx * h.srcW : h.srcW * B, rgb ? 0 : (h.src_layout ? 2 * h.chrSrcW : h.chrSrcW * B), h.src_layout ? 0 : h.chrSrcW * B },
+    /* a P010 source: two planes of 16-bit words — 2 * srcW bytes of luma and 4 * chrSrcW bytes of pairs a row (B is 2), pointers and strides even */
+    const int w[3] = { rgb ? bpx * h.srcW : h.srcW * B, rgb ? 0 : (h.src_layout ? 2 * h.chrSrcW * B : h.chrSrcW * B), h.src_layout ? 0 : h.chrSrcW * B },
               ph[3] = { h.srcH, h.chrSrcH, h.chrSrcH };
+    if (p010_src(h))
+        for (int p = 0; p < 2; p++) if (!src[p] || ((reinterpret_cast<uintptr_t>(src[p]) | (uintptr_t)src_stride[p]) & 1)) return -1;
     for (int p = 0; p < nsrc; p++) if (!src[p] || src_stride[p] < w[p]) return -1;
     for (int p = 0; p < ndst; p++) if (!dst[p] || dst_stride[p] < back[p]) return -1;
     DeviceScope on(c->device);

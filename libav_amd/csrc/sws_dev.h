@@ -1,6 +1,7 @@
 /*
  * sws_dev.h — the device side of sws.hip and of the files that compile instances beside it (sws_deep.hip, sws_packed.hip, sws_rgb32.hip,
- * sws_yuy2.hip, sws_yuy2dst.hip — the last one the DST_YUY2 form of the packed kernels: yuyv422 / uyvy422 / yvyu422 destinations, vertical_yuy2): the tile geometry and its instance table, the steps of the scaler (horizontal pass into LDS, packed and planar vertical passes),
+ * sws_yuy2.hip, sws_yuy2dst.hip — the last one the DST_YUY2 form of the packed kernels: yuyv422 / uyvy422 / yvyu422 destinations, vertical_yuy2 — and sws_p010.hip: the
+ * SwsPxP010 instances, a p010le source, hscale_tile_p010): the tile geometry and its instance table, the steps of the scaler (horizontal pass into LDS, packed and planar vertical passes),
  * at the end the host side of a launch (the launch key SwsKey, the dispatcher sws_launch, the grids, the line helper) and the kernels:
  *   k_sws_generic   the generic scaler of swscale() (libswscale/swscale.c:343-722) for whole pictures,
  *                   fused per output tile: horizontal 8->15 bit FIR of the source lines the tile needs
@@ -347,6 +348,7 @@ constexpr int STAGE_BYTES16 = (int)sizeof(uint32_t) * SG * SRC_DW16;
 struct SwsPx32 { uint32_t v; };
 struct SwsPx32A { uint32_t v; };
 struct SwsPxYuy2 { uint8_t v; };          /* a packed 4:2:2 source (the picked bytes are staged in the 8-bit instances' staging lines) */
+struct SwsPxP010 { uint16_t v; };         /* a P010 source (the samples, word >> 6, are staged in the 16-bit instances' staging lines) */
 template <typename ST> __host__ __device__ constexpr int stage_bytes() { return sizeof(ST) == 2 ? STAGE_BYTES16 : STAGE_BYTES; }
 /* dwords per staged line of `cols` columns of `bytes`-byte samples: a multiple of four (16-byte LDS stores) */
 __host__ __device__ constexpr int stage_pitch(int cols, int bytes) { return bytes == 1 ? (cols == TW ? SRC_DW : SRC_DW_HALF) : (cols == TW ? SRC_DW16 : SRC_DW16_HALF); }
@@ -1208,6 +1210,163 @@ __device__ __forceinline__ void hscale_tile_rgb(int16_t (*out_a)[OP], int16_t (*
     }
 }
 
+/* ---- a P010 source (p010le): the input converters in front of the 16-bit horizontal pass ----------------------------------------------------
+ * The reference converts each source line into 16-bit lines of its formatConvBuffer (p010LEToY_c / p010LEToUV_c, input.c:499-524: dst[i] =
+ * word >> 6; U from the first, V from the second word of a pair) and runs hScale16To15_c with depth 10 on them (swscale.c:110-130).  Here a staging
+ * round makes those lines in the 16-bit instances' staging storage (StageGeom<COLS, uint16_t> as it is: a staged line holds what formatConvBuffer
+ * holds), and hscale_lines8 / hscale_lines consume them unchanged with hsh = 9.  Every uint16_t value is a sample: the low six bits are dropped.
+ * NP 1: the luma plane, srcW words a line.  NP 2: the plane of pairs, chrSrcW pairs of four bytes a line — de-interleaved as it is staged (sws_lo2 /
+ * sws_hi2 over two dwords), so U and V each lie in a line of the chroma geometry and take half of the staged lines of a round, as the two
+ * planes of a packed source do in hscale_tile_rgb.  A unit is eight samples of a line, 16 bytes of the luma plane and 32 of the pair plane: aligned
+ * 16-byte pieces on a plane of 16-byte multiples, dwords on one of 4-byte multiples, 16-bit loads otherwise (pointers and strides are even), each
+ * while the piece lies whole inside the 2 * srcW / 4 * chrSrcW bytes of the line; words at and past that read as zero (no tap with a non-zero
+ * coefficient meets them: mi355_sws_create stages only banks whose every position + size stays inside the line). */
+__device__ __forceinline__ uint32_t p010_shr6(uint32_t w) { return (w >> 6) & 0x03FF03FFu; }      /* both 16-bit lanes of a dword */
+template <int N>
+__device__ __forceinline__ void p010_load(const uint8_t *line, int boff, int limit, bool al4, bool al16, uint32_t *w)
+{
+    static_assert(N % 4 == 0, "whole 16-byte pieces");
+    if (al16 && boff + 4 * N <= limit) {
+#pragma unroll
+        for (int k = 0; k < N; k += 4) {
+            const sws_u32x4 v = *reinterpret_cast<const sws_u32x4 *>(line + boff + 4 * k);
+            w[k] = v[0]; w[k + 1] = v[1]; w[k + 2] = v[2]; w[k + 3] = v[3];
+        }
+    } else if (al4 && boff + 4 * N <= limit) {
+#pragma unroll
+        for (int k = 0; k < N; k++) w[k] = reinterpret_cast<const uint32_t *>(line + boff)[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++) {
+            w[k] = 0;
+            for (int h = 0; h < 2; h++)
+                if (boff + 4 * k + 2 * h < limit) w[k] |= (uint32_t)*reinterpret_cast<const uint16_t *>(line + boff + 4 * k + 2 * h) << (16 * h);
+        }
+    }
+}
+/* samples s .. s + 7 of a line (s a multiple of eight) as four dwords per plane: NP 1 luma into oa; NP 2 U into oa, V into ob */
+template <int NP>
+__device__ __forceinline__ void p010_unit(const uint8_t *line, int s, bool al4, bool al16, int limit, sws_u32x4 &oa, sws_u32x4 &ob)
+{
+    if constexpr (NP == 1) {
+        uint32_t w[4];
+        p010_load<4>(line, 2 * s, limit, al4, al16, w);
+#pragma unroll
+        for (int k = 0; k < 4; k++) { oa[k] = p010_shr6(w[k]); ob[k] = 0; }
+    } else {
+        uint32_t w[8];
+        p010_load<8>(line, 4 * s, limit, al4, al16, w);
+#pragma unroll
+        for (int k = 0; k < 4; k++) { oa[k] = p010_shr6(sws_lo2(w[2 * k], w[2 * k + 1])); ob[k] = p010_shr6(sws_hi2(w[2 * k], w[2 * k + 1])); }
+    }
+}
+/* nsamp: samples of a line and plane (srcW, or chrSrcW pairs); stride in bytes.  Identity, staged and direct forms as hscale_tile's: the identity
+ * columns are sample << 5 (one tap of 1 << 14 shifted down by depth - 1 = 9), the direct form (spans wider than a staged line, non-monotonic banks)
+ * reads word by word.  A tile's span is staged from a multiple of eight samples — the aligned 16 bytes the planar 16-bit source starts from — so a
+ * span fits here exactly where it fits a staged line of that source; the plane's alignment picks the loads of a unit, never the form. */
+template <int COLS, int OP, int NP>
+__device__ __forceinline__ void hscale_tile_p010(int16_t (*out_a)[OP], int16_t (*out_b)[OP], const uint8_t *src, int stride, int nsamp, const int32_t *posT,
+                                                 const int16_t *coefT, int fs, int gx0, int ncols, int lo, int hi,
+                                                 uint32_t *stage_mem, int tid, bool zero_tail, bool may_stage, bool identity)
+{
+    constexpr int PITCH = StageGeom<COLS, uint16_t>::PITCH, LR = StageGeom<COLS, uint16_t>::LINES / NP;      /* staged lines of a plane per round */
+    static_assert(StageGeom<COLS, uint16_t>::LINES % NP == 0 && LR >= NT / COLS, "every thread's first line is staged");
+    constexpr int HSH = 9, UP = 5;                     /* hScale16To15_c's shift at depth 10, and 14 - HSH */
+    const bool al4 = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 3) == 0;
+    const bool al16 = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 15) == 0;
+    const int limit = 2 * NP * nsamp;                  /* bytes of a line the reference reads */
+    if (identity) {
+        /* eight columns per thread: one unit, one 16-byte LDS write per plane */
+        constexpr int TPL = COLS / 8;                  /* threads per line */
+        const int xg = 8 * (tid % TPL), gxi = gx0 + xg;
+        uint32_t keep[4];                              /* the lanes of columns inside the picture */
+#pragma unroll
+        for (int k = 0; k < 4; k++) keep[k] = (gxi + 2 * k < ncols ? 0xFFFFu : 0u) | (gxi + 2 * k + 1 < ncols ? 0xFFFF0000u : 0u);
+        for (int l = lo + tid / TPL; l <= hi; l += NT / TPL) {
+            sws_u32x4 a = { 0u, 0u, 0u, 0u }, b = { 0u, 0u, 0u, 0u };
+            if (keep[0]) p010_unit<NP>(src + (size_t)l * stride, gxi, al4, al16, limit, a, b);
+#pragma unroll
+            for (int k = 0; k < 4; k++) { a[k] = (a[k] & keep[k]) << UP; b[k] = (b[k] & keep[k]) << UP; }
+            if (zero_tail || gxi < ncols) {
+                *reinterpret_cast<sws_u32x4 *>(&out_a[l - lo][xg]) = a;
+                if (NP > 1) *reinterpret_cast<sws_u32x4 *>(&out_b[l - lo][xg]) = b;
+            }
+        }
+        return;
+    }
+    const int x = tid & (COLS - 1), gx = gx0 + x, per = NT / COLS;
+    const bool col_ok = gx < ncols;
+    /* columns past the picture read the last column's entries and do not use them */
+    const int gxc = col_ok ? gx : ncols - 1;
+    const int pos = posT[gxc];
+    const int16_t *f = coefT + (size_t)gxc * fs;
+    const int last = imin(gx0 + COLS, ncols) - 1;
+    /* the tile's span in samples, from a multiple of eight: whole units; nd: the dwords of its staged line */
+    const int s0 = posT[gx0], s1 = posT[last] + fs, a0 = s0 & ~7, nd = span_dwords(2 * a0, 2 * s1);
+    uint32_t cp[4];
+    if (fs == 8) {
+        const uint4 w = *reinterpret_cast<const uint4 *>(f);
+        cp[0] = w.x; cp[1] = w.y; cp[2] = w.z; cp[3] = w.w;
+    } else {
+        int t[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) t[j] = f[j < fs ? j : 0];
+#pragma unroll
+        for (int j = 0; j < 4; j++) cp[j] = (2 * j < fs ? (uint32_t)t[2 * j] & 0xFFFFu : 0u) | (2 * j + 1 < fs ? (uint32_t)t[2 * j + 1] << 16 : 0u);
+    }
+    if (!(may_stage && span_fits(nd, s0, s1, PITCH))) {
+        if (col_ok) {
+            for (int l = lo + tid / COLS; l <= hi; l += per) {
+                const uint16_t *s = reinterpret_cast<const uint16_t *>(src + (size_t)l * stride) + (size_t)NP * pos;
+                int a = 0, b = 0;
+                for (int j = 0; j < fs; j++) {
+                    a += (int)(s[NP * j] >> 6) * f[j];
+                    if (NP > 1) b += (int)(s[NP * j + 1] >> 6) * f[j];
+                }
+                a >>= HSH; b >>= HSH;
+                out_a[l - lo][x] = (int16_t)(a < 32767 ? a : 32767);
+                if (NP > 1) out_b[l - lo][x] = (int16_t)(b < 32767 ? b : 32767);
+            }
+        } else if (zero_tail) {
+            for (int l = lo + tid / COLS; l <= hi; l += per) out_a[l - lo][x] = 0;
+        }
+        return;
+    }
+    /* units of four staged dwords: 4 * nu <= PITCH (a multiple of four, nd <= PITCH - 2) */
+    static_assert(StageGeom<COLS, uint16_t>::LINES * PITCH * PITCH < (1 << 19), "mi355_div20 range");
+    const int nu = (nd + 3) >> 2, inv = mi355_inv20(nu);
+    uint32_t (*stage)[LR][PITCH] = reinterpret_cast<uint32_t (*)[LR][PITCH]>(stage_mem);      /* [plane][line][dword] */
+    for (int base = lo; base <= hi; base += LR) {
+        for (int idx = tid; idx < LR * nu; idx += NT) {
+            const int r = mi355_div20(idx, inv), u = idx - r * nu, line = base + r;
+            if (line > hi) continue;
+            sws_u32x4 oa, ob;
+            p010_unit<NP>(src + (size_t)line * stride, a0 + 8 * u, al4, al16, limit, oa, ob);
+            *reinterpret_cast<sws_u32x4 *>(&stage[0][r][4 * u]) = oa;
+            if (NP > 1) *reinterpret_cast<sws_u32x4 *>(&stage[1][r][4 * u]) = ob;
+        }
+        __syncthreads();
+        /* the thread's column over the staged lines of each plane, as hscale_tile; a plane's round is LR lines */
+        const int r0 = tid / COLS;
+        const int left = uniform(imin(hi - base, LR - 1) - r0);
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+            const uint8_t *row0 = reinterpret_cast<const uint8_t *>(stage[p][r0]) + 2 * (pos - a0);
+            int16_t *out0 = p ? &out_b[base + r0 - lo][x] : &out_a[base + r0 - lo][x];
+            if (col_ok) {
+                if (fs == 1) hscale_lines<COLS, 1, OP, uint16_t>(row0, out0, cp, left, HSH);
+                else if (fs <= 2) hscale_lines<COLS, 2, OP, uint16_t>(row0, out0, cp, left, HSH);
+                else if (fs <= 4) hscale_lines<COLS, 4, OP, uint16_t>(row0, out0, cp, left, HSH);
+                else if (fs <= 8) hscale_lines8<COLS, OP, uint16_t>(row0, out0, cp, left, HSH);
+                else hscale_lines<COLS, 0, OP, uint16_t>(row0, out0, cp, left, HSH, f, fs);
+            } else if (zero_tail) {
+                for (int k = 0; k < LR / per && k * per <= left; k++) out0[k * per * OP] = 0;
+            }
+        }
+        __syncthreads();
+    }
+}
+
 /* Vertical pass + LUT for the output rows of a tile with the row's filter taps and source-line indices in
  * registers: NL / NC = luma / chroma tap counts rounded up to 1, 2, 4 or 8 (taps past the real size carry a
  * zero coefficient and a valid line index).  A thread owns one output row and every 16th pair of it. */
@@ -1677,6 +1836,14 @@ __global__ void __launch_bounds__(NT) k_sws_generic(const SwsDev *cp, const mi35
     /* horizontal pass: luma (the phantom partner of the last sample of an odd-width picture reads the
      * zero-initialised tail of the reference's line buffer, utils.c:1241-1262), then the chroma planes */
     uint32_t *s_stage = reinterpret_cast<uint32_t *>(s_io);
+    if constexpr (std::is_same<ST, SwsPxP010>::value) {
+        /* a P010 source: luma from fr.src[0], both chroma tiles from ONE pass over fr.src[1], the plane of pairs; fr.src[2] is not read */
+        static_assert(NV && !RGB, "a P010 source is a luma plane and a plane of pairs");
+        hscale_tile_p010<TW, TW, 1>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi,
+                                    s_stage, tid, true, c.hstage != 0, c.hident_l != 0);
+        hscale_tile_p010<TW / 2, TW / 2, 2>(s_cu, s_cv, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> 1, c.chrDstW, clo, chi,
+                                            s_stage, tid, false, c.hstage != 0, c.hident_c != 0);
+    } else
     if constexpr (std::is_same<ST, SwsPxYuy2>::value) {
         /* a packed 4:2:2 source: luma from the pairs, both chroma tiles from ONE pass over the groups of four of the same plane */
         static_assert(RGB && !NV, "packed 4:2:2 sources have one plane");
@@ -2097,6 +2264,11 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
     const int ls = c.vls, cs = c.vcs;
     /* source lines the tile needs (swscale.c:459-468 for the first tap, :571-616 for the clamping) */
     const int llo = clampi(imax(1 - ls, c.vLumP[y0]), 0, c.srcH - 1), lhi = clampi(imax(1 - ls, c.vLumP[y1]) + ls - 1, 0, c.srcH - 1);
+    if constexpr (std::is_same<ST, SwsPxP010>::value) {
+        static_assert(NV && !RGB, "a P010 source is a luma plane and a plane of pairs");
+        hscale_tile_p010<TW, TW, 1>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi, s_stage, tid, false,
+                                    c.hstage != 0, c.hident_l != 0);
+    } else
     if constexpr (std::is_same<ST, SwsPxYuy2>::value) {
         static_assert(RGB && !NV, "packed 4:2:2 sources have one plane");
         hscale_tile_rgb<TW, TW, 1, 2>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.srcW, false, false, c.hLumP, c.hLumC, c.hls, x0, c.dstW,
@@ -2118,6 +2290,11 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
         clo = clampi(imax(1 - cs, c.vChrP[cy0]), 0, c.chrSrcH - 1);
         const int chi = clampi(imax(1 - cs, c.vChrP[cy1]) + cs - 1, 0, c.chrSrcH - 1);
         nchr = chi - clo + 1;
+        if constexpr (std::is_same<ST, SwsPxP010>::value) {
+            int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
+            hscale_tile_p010<CW, 2 * CW, 2>(s_u, s_v, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false,
+                                            c.hstage != 0, c.hident_c != 0);
+        } else
         if constexpr (std::is_same<ST, SwsPxYuy2>::value) {
             int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
             hscale_tile_rgb<CW, 2 * CW, 2, 2>(s_u, s_v, fr.src[0], fr.src_stride[0], c.srcW, c.chrSrcW, true, false, c.hChrP, c.hChrC, c.hcs,
@@ -2781,7 +2958,8 @@ __global__ void __launch_bounds__(NT) k_sws_line_rgb(const mi355_sws_luts *luts,
  *           (alpha: k_sws_line_packed_a); YUY2_SPLIT: k_sws_yuy2_split; YUY2_PACK: k_sws_yuy2_pack
  *   i       0 / 1 / 2: the A / B / C row of GENERIC_SHAPES / PLANAR_SHAPES, as sws_kernel() chose it
  *   src     the source class — P8 / P16: three planes of bytes / of 16-bit samples, NV: NV12 / NV21, RGB24: rgb24 / bgr24, RGB32: rgba / bgra /
- *           argb / abgr, YUY2: yuyv422 / uyvy422 / yvyu422 (the order inside a class is read from the context on the device)
+ *           argb / abgr, YUY2: yuyv422 / uyvy422 / yvyu422 (the order inside a class is read from the context on the device), P010: p010le, a plane of
+ *           16-bit words and a plane of pairs of them
  *   form    of k_sws_planar — HALF: three planes, chroma tiles of CW = TW / 2, FULL: of CW = TW (a 4:4:4 destination), SEMI: NV12 / NV21
  *   kind    of k_sws_planar — PLAIN, RANGE (range conversion between the passes), DEEP (9- / 10-bit planes; three planes, no range)
  *   dst     of the packed kernels — DST_RGB24 / DST_BGR24 / DST_RGB32 (the 32-bit order is the operands' sel) / DST_YUY2 (the 4:2:2 order likewise)
@@ -2790,7 +2968,7 @@ __global__ void __launch_bounds__(NT) k_sws_line_rgb(const mi355_sws_luts *luts,
  * launched: the launch functions return false and the entry point -2. */
 enum SwsKernel { SWS_KERNEL_GENERIC, SWS_KERNEL_PLANAR, SWS_KERNEL_IDENT1_1, SWS_KERNEL_IDENT1_X, SWS_KERNEL_C24, SWS_KERNEL_C24_422, SWS_KERNEL_LINE, SWS_KERNEL_YUY2_SPLIT,
                  SWS_KERNEL_YUY2_PACK };
-enum SwsSrcClass { SWS_SRC_P8, SWS_SRC_P16, SWS_SRC_NV, SWS_SRC_RGB24, SWS_SRC_RGB32, SWS_SRC_YUY2 };
+enum SwsSrcClass { SWS_SRC_P8, SWS_SRC_P16, SWS_SRC_NV, SWS_SRC_RGB24, SWS_SRC_RGB32, SWS_SRC_YUY2, SWS_SRC_P010 };
 enum SwsForm { SWS_FORM_HALF, SWS_FORM_FULL, SWS_FORM_SEMI };
 enum SwsKind { SWS_KIND_PLAIN, SWS_KIND_RANGE, SWS_KIND_DEEP };
 struct SwsKey {
@@ -2832,6 +3010,7 @@ bool mi355_sws_launch_deep(const SwsKey &key, const SwsOperands &op);       /* s
 bool mi355_sws_launch_packed(const SwsKey &key, const SwsOperands &op);     /* sws_packed.hip: DST_BGR24 / DST_RGB32 of k_sws_generic, k_sws_ident1, k_sws_c24, k_sws_line_packed */
 bool mi355_sws_launch_rgb32(const SwsKey &key, const SwsOperands &op);      /* sws_rgb32.hip: every tile instance of SWS_SRC_RGB32, k_sws_line_packed_a */
 bool mi355_sws_launch_yuy2(const SwsKey &key, const SwsOperands &op);       /* sws_yuy2.hip: every tile instance of SWS_SRC_YUY2, k_sws_ident1_yuy2, k_sws_yuy2_split */
+bool mi355_sws_launch_p010(const SwsKey &key, const SwsOperands &op);       /* sws_p010.hip: every tile instance of SWS_SRC_P010, DST_YUY2 included */
 bool mi355_sws_launch_yuy2dst(const SwsKey &key, const SwsOperands &op);    /* sws_yuy2dst.hip: DST_YUY2 of k_sws_generic, k_sws_ident1, k_sws_ident1_yuy2, k_sws_line_packed from every source class; k_sws_yuy2_pack */
 
 namespace {
@@ -2864,6 +3043,7 @@ template <> struct SwsSrc<SWS_SRC_NV> { typedef uint8_t ST; static constexpr boo
 template <> struct SwsSrc<SWS_SRC_RGB24> { typedef uint8_t ST; static constexpr bool NV = false, RGB = true; };
 template <> struct SwsSrc<SWS_SRC_RGB32> { typedef SwsPx32 ST; static constexpr bool NV = false, RGB = true; };
 template <> struct SwsSrc<SWS_SRC_YUY2> { typedef SwsPxYuy2 ST; static constexpr bool NV = false, RGB = true; };
+template <> struct SwsSrc<SWS_SRC_P010> { typedef SwsPxP010 ST; static constexpr bool NV = true, RGB = false; };
 
 /* instance I of k_sws_generic: its waves per SIMD are what its LDS allows (the staging lines of its sample type, the alpha tile of the ALPHA form),
  * like the planar kernel's own */
@@ -2896,7 +3076,7 @@ template <bool X, bool NV, int DST> void sws_launch_ident1(const SwsOperands &op
  * the masks is not instantiated, and a key that asks for it comes back false. */
 template <unsigned SRCS, unsigned KINDS, unsigned DSTS> bool sws_launch(const SwsKey &key, const SwsOperands &op)
 {
-    return sws_pick<SwsSrcClass, SWS_SRC_P8, SWS_SRC_P16, SWS_SRC_NV, SWS_SRC_RGB24, SWS_SRC_RGB32, SWS_SRC_YUY2>(key.src, [&](auto src) {
+    return sws_pick<SwsSrcClass, SWS_SRC_P8, SWS_SRC_P16, SWS_SRC_NV, SWS_SRC_RGB24, SWS_SRC_RGB32, SWS_SRC_YUY2, SWS_SRC_P010>(key.src, [&](auto src) {
         constexpr SwsSrcClass C = decltype(src)::value;
         if constexpr ((SRCS & sws_bit(C)) == 0) return false;
         else if (key.kernel == SWS_KERNEL_PLANAR) {

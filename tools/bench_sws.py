@@ -71,8 +71,14 @@ def main():
                          "yuv420p -> yuyv422 at equal size (k_sws_ident1); the unscaled packer 1080p yuv422p -> yuyv422 beside k_sws_nv12_pack at the same "
                          "size (4 bytes a pixel against 3); the twin a second time in another allocation (A/A); 32 and 512 pictures per launch, 3 warm-up + "
                          "--steps launches a round, alternating, median of --rounds rounds")
+    ap.add_argument("--p010", action="store_true",
+                    help="P010 sources beside THE SAME descriptor as a yuv420p10le source on the word >> 6 planes — identical banks, destination and source "
+                         "bytes: 2160p -> 1080p p010le -> rgb24 and -> yuv420p10le, 1080p p010le -> nv12 at equal size; the twin a second time in another "
+                         "allocation (A/A), with --other-lib also on that build (the parent commit's); and a plain device copy of the source bytes (the "
+                         "twin plus that copy is the cheapest two-step route); 32 and 512 pictures per launch, 3 warm-up + --steps launches a round, "
+                         "alternating, median of --rounds rounds")
     ap.add_argument("--other-lib", default=None,
-                    help="--nv12 / --nvsrc / --rgbsrc / --range / --rgb32src: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
+                    help="--nv12 / --nvsrc / --rgbsrc / --range / --rgb32src / --p010: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
     ap.add_argument("--rounds", type=int, default=5, help="--planar / --sources / --yuy2src / --yuy2dst: alternating rounds (the median is reported)")
     a = ap.parse_args()
     prov = providers.mi355()
@@ -101,6 +107,8 @@ def main():
         return yuy2src_points(a, lib)
     if a.yuy2dst:
         return yuy2dst_points(a, lib)
+    if a.p010:
+        return p010_points(a, lib)
     orc = S.oracle_backend(providers.oracle())
     for name in a.configs.split(","):
         ctx = S.load_context(name)
@@ -1069,6 +1077,93 @@ def yuy2dst_points(a, lib, points=None, frame_counts=(32, 512), scaled=None):
     aa = max(r["aa_spread"] for r in rows)
     miss = ["%s@%d %+.1f%% (bound %+.1f%%)" % (r["workload"], r["frames_per_launch"], 100 * r["vs_twin"], 100 * (r["bound"] + aa)) for r in rows if r["vs_twin"] > r["bound"] + aa]
     print(json.dumps({"summary": "yuy2dst", "aa_session": aa, "points": len(rows), "miss": miss}), flush=True)
+
+
+def p010_points(a, lib, points=None, frame_counts=(32, 512)):
+    """A P010 source beside its planar 10-bit twin: the context of the SAME descriptor as a yuv420p10le source (src_layout 0, depth 10, shifts 1, 1) on
+    the de-interleaved word >> 6 planes reads exactly as many source bytes and writes the same destination; the only added work is a shift and a
+    permute per staged dword, so the expectation is the twin's time within the twin's own A/A spread (`bound` is 0).  The contexts come from the
+    reference's libswscale at run time (oracle/_ref/libswsref.so: mi355_sws_describe_p010) — no full-size context is committed.  `twin#2` is the twin
+    a second time with its own buffers: the session's A/A spread.  With --other-lib the twin also runs on that build (the parent commit's).  `copy`
+    is a plain device-to-device copy of one launch's source bytes: `vs_two_step` of the P010 row is its time over the twin's plus that copy, the
+    cheapest possible two-step route, which the fused path has to beat (below 0).  One process, the batches of a point alternating: 3 warm-up +
+    --steps launches a round, median of --rounds rounds, at 32 and 512 pictures per launch.  Algorithmic bytes: the source planes read once + the
+    destination planes written once.  The last line sums the session up: `aa_session` — the largest A/A spread of its points — and under `miss`
+    every P010 row whose time exceeds its twin's by more than that spread."""
+    import statistics
+    import numpy as np
+    import sws_planar as P
+    import sws_p010 as Z
+    other = None
+    if a.other_lib:
+        other = C.CDLL(os.path.abspath(a.other_lib))
+        other.mi355_init.restype = C.c_int
+        assert other.mi355_init(C.c_int(0)) == 0
+        other.mi355_event_create.restype = C.c_void_p
+        other.mi355_event_elapsed_ms.restype = C.c_float
+    ref = Z.Ref(P.bind(Z.REF_LIB))
+    # (point, srcW, srcH, dstW, dstH, destination of tests/sws_p010.py)
+    points = points or [("uhd_to_hd_rgb24", 3840, 2160, 1920, 1080, "rgb24"), ("uhd_to_hd_yuv420p10le", 3840, 2160, 1920, 1080, "420p10"),
+                        ("hd_same_nv12", 1920, 1080, 1920, 1080, "nv12")]
+    rows = []
+
+    def batch(l, x, pics, frames):
+        if Z.one_plane(x):
+            return SourceBatch(l, None, x, pics, frames, create=Z.create, bpp=4 if x.fmt >= 33 else 3)
+        return PlaneBatch(l, Z.create(l, x), pics, x.out_sizes(), frames)
+
+    for frames in frame_counts:
+        for point, sw, sh, dw, dh, dst in points:
+            row = (sw, sh, dw, dh, 0, dst, 0, 1, 1, 1)                  # a row of tests/sws_p010.py's form, not entered into its table
+            c = ref.open(row)
+            e = ref.describe_p010(c)
+            ref.free(c)
+            assert e is not None, point
+            t = Z.twin_entry(e)
+            ppics = [[np.ascontiguousarray(pl) for pl in Z.picture(row, "noise", seed=s)] for s in (1, 2)]
+            tpics = [Z.planar_twin_planes(row, pic) for pic in ppics]
+            batches = {"p010": (lib, batch(lib, e, ppics, frames)), "twin": (lib, batch(lib, t, tpics, frames)), "twin#2": (lib, batch(lib, t, tpics, frames))}
+            if other:
+                batches["twin@parent"] = (other, batch(other, t, tpics, frames))
+            plan = Z.plan_of(lib, batches["p010"][1].handle)
+            tplan = Z.plan_of(lib, batches["twin"][1].handle)
+            # the plain copy: one launch's source bytes from one allocation to another
+            nsrc = batches["p010"][1].src_bytes * frames
+            lib.mi355_malloc.restype = C.c_void_p
+            ca, cb = lib.mi355_malloc(C.c_size_t(nsrc)), lib.mi355_malloc(C.c_size_t(nsrc))
+            assert ca and cb
+            lib.mi355_memcpy_d2d.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+            times = {k: [] for k in batches}
+            times["copy"] = []
+            for _ in range(a.rounds):
+                for k, (l, b) in batches.items():
+                    times[k].append(time_ms(l, b.run, a.steps))
+                times["copy"].append(time_ms(lib, lambda: lib.mi355_memcpy_d2d(cb, ca, nsrc), a.steps))
+            lib.mi355_free(C.c_void_p(ca)); lib.mi355_free(C.c_void_p(cb))
+            base = statistics.median(times["twin"])
+            copy = statistics.median(times["copy"])
+            spread = max(abs(x / base - 1.0) for k in ("twin#2", "twin@parent") if k in times for x in (statistics.median(times[k]),))
+            twin_bytes = batches["twin"][1].src_bytes + batches["twin"][1].dst_bytes
+            for k, (l, b) in batches.items():
+                ms = statistics.median(times[k])
+                us = ms * 1e3 / frames
+                nb = b.src_bytes + b.dst_bytes
+                out = {"workload": point + ":" + k, "frames_per_launch": frames, "ms_per_launch": ms, "us_per_picture": us, "frames_per_s": 1e6 / us,
+                       "algorithmic_bytes_per_frame": nb, "achieved_GBps": nb / us * 1e-3, "frac_of_8TBps": nb / us * 1e-3 / 8000.0,
+                       "vs_twin": ms / base - 1.0, "bound": nb / twin_bytes - 1.0, "aa_spread": spread, "ms_rounds": [round(x, 4) for x in times[k]],
+                       "ms_min_max": [round(min(times[k]), 4), round(max(times[k]), 4)]}
+                if k == "p010":
+                    out.update({"kernel": plan["kernel"], "twin_kernel": tplan["kernel"], "hstaged": plan["hstaged"], "copy_ms": copy,
+                                "vs_two_step": ms / (base + copy) - 1.0})
+                rows.append(out)
+                print(json.dumps(out), flush=True)
+            for l, b in batches.values():
+                b.close()
+    aa = max(r["aa_spread"] for r in rows)
+    miss = ["%s@%d %+.1f%% (spread %+.1f%%)" % (r["workload"], r["frames_per_launch"], 100 * r["vs_twin"], 100 * r["aa_spread"])
+            for r in rows if r["workload"].endswith(":p010") and r["vs_twin"] > r["aa_spread"]]
+    slow = ["%s@%d %+.1f%% of twin + copy" % (r["workload"], r["frames_per_launch"], 100 * r["vs_two_step"]) for r in rows if r.get("vs_two_step", -1) >= 0]
+    print(json.dumps({"summary": "p010", "aa_session": aa, "points": len(rows), "miss": miss, "not_below_two_step": slow}), flush=True)
 
 
 if __name__ == "__main__":
