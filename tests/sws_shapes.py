@@ -212,7 +212,7 @@ class PlanInfo(C.Structure):
     _fields_ = [("kernel", C.c_int), ("th", C.c_int), ("hstage", C.c_int), ("lum_lines", C.c_int), ("chr_lines", C.c_int), ("narrow", C.c_int)]
 
 
-KERNELS = ("c24", "ident1_1", "ident1_x", "generic_a", "generic_b", "generic_c")
+KERNELS = S.KERNELS[:6]            # what an rgb24 context of this table may report: c24 ... generic_c
 
 
 def create(lib, ctx):
@@ -228,7 +228,7 @@ def plan_of(lib, handle):
     p = PlanInfo()
     lib.mi355_sws_plan.argtypes = [C.c_void_p, C.c_void_p]
     assert lib.mi355_sws_plan(C.c_void_p(handle), C.byref(p)) == 0
-    return {"kernel": KERNELS[p.kernel], "th": p.th, "hstage": p.hstage, "lum_lines": p.lum_lines, "chr_lines": p.chr_lines, "narrow": p.narrow}
+    return {"kernel": S.KERNELS[p.kernel], "th": p.th, "hstage": p.hstage, "lum_lines": p.lum_lines, "chr_lines": p.chr_lines, "narrow": p.narrow}
 
 
 def plan(lib, ctx):

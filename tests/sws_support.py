@@ -35,6 +35,11 @@ class SwsFrame(C.Structure):
     _fields_ = [("src", C.c_void_p * 3), ("src_stride", C.c_int * 3), ("dst", C.c_void_p), ("dst_stride", C.c_int)]
 
 
+# MI355_SWS_K_* of include/mi355_sws.h by value: what mi355_sws_plan reports.  The ONE copy — every table's plan_of() reads it, so a plan of any
+# kernel has a name whichever module asks
+KERNELS = ("c24", "ident1_1", "ident1_x", "generic_a", "generic_b", "generic_c", "planar_a", "planar_b", "planar_c", "nv12_pack", "nv12_split",
+           "yuy2_split", "yuy2_pack")
+
 INTS = ("srcW", "srcH", "dstW", "dstH", "chrSrcW", "chrSrcH", "chrDstW", "unscaled_special")
 BANKS = ("hLum", "hChr", "vLum", "vChr")
 LUTS = ("y_table", "rV", "gU", "gV", "bU")
