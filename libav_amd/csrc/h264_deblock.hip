@@ -145,13 +145,24 @@ __device__ __forceinline__ uint32_t bs_role(const MbInfo &h, const MbInfo &nb, b
 /* Luma edge, one line: p3 p2 p1 p0 | q0 q1 q2 q3.  bS 1..3: h264_loop_filter_luma (h264dsp_template.c:104-150) with the
  * line's conditions folded into the clipping bounds (tc = 0 leaves a sample as it is); bS 4
  * (h264_loop_filter_luma_intra :165-210) only where a lane of the wave has it (MAY_INTRA: macroblock edges only).
- * Returns 0 when no line of the WAVE passes the conditions (nothing changed), else 1, or 2 when the bS 4 filter ran. */
-template <bool MAY_INTRA>
+ * Returns 0 when no line of the WAVE passes the conditions (nothing changed), else 1, or 2 when the bS 4 filter ran.
+ * BALLOT: the wave-level votes are taken on the scalar unit, from the lane masks the comparisons leave there (lanes_all4, h264_dev.h): the
+ * form of the tiled kernels, two vector instructions per vote less; the line-stride kernels keep __any and with it their instruction streams. */
+template <bool MAY_INTRA, bool BALLOT = false>
 __device__ __forceinline__ int luma_line(int p3, int &p2, int &p1, int &p0, int &q0, int &q1, int &q2, int q3,
                                          int bs, int alpha, int beta, int tc0)
 {
-    const bool f = bs != 0 && absdiff8(p0, q0) < alpha && absdiff8(p1, p0) < beta && absdiff8(q1, q0) < beta;
-    if (!__any(f)) return 0;
+    bool f;
+    uint64_t fm = 0;                                         /* BALLOT: the lanes that hold f */
+    if constexpr (BALLOT) {
+        const bool f_bs = bs != 0, f_a = absdiff8(p0, q0) < alpha, f_p = absdiff8(p1, p0) < beta, f_q = absdiff8(q1, q0) < beta;
+        f = f_bs && f_a && f_p && f_q;
+        fm = lanes_all4(f_bs, f_a, f_p, f_q);
+        if (!fm) return 0;
+    } else {
+        f = bs != 0 && absdiff8(p0, q0) < alpha && absdiff8(p1, p0) < beta && absdiff8(q1, q0) < beta;
+        if (!__any(f)) return 0;
+    }
     const bool ap = absdiff8(p2, p0) < beta, aq = absdiff8(q2, q0) < beta;
     const bool fn = f && bs < 4;
     const int avg = (p0 + q0 + 1) >> 1;
@@ -164,7 +175,7 @@ __device__ __forceinline__ int luma_line(int p3, int &p2, int &p1, int &p0, int 
     q0 = clip_u8(Q0 - delta);
     if (MAY_INTRA) {
         const bool fi = f && bs == 4;
-        if (__any(fi)) {
+        if (BALLOT ? (fm & lane_mask(bs == 4)) != 0 : __any(fi) != 0) {
             const bool strong = absdiff8(P0, Q0) < ((alpha >> 2) + 2), sp = strong && ap, sq = strong && aq;
             const int wp0 = (2 * P1 + P0 + Q1 + 2) >> 2, wq0 = (2 * Q1 + Q0 + P1 + 2) >> 2;
             const int s4 = P0 + Q0 + 4;
@@ -183,10 +194,18 @@ __device__ __forceinline__ int luma_line(int p3, int &p2, int &p1, int &p0, int 
 }
 /* Chroma edge, one line: p1 p0 | q0 q1: h264_loop_filter_chroma / _intra (h264dsp_template.c:212-265); `tc1` is the
  * caller's tc0 + 1 (h264_loopfilter.c:126-129).  Returns whether any line of the wave changed. */
+template <bool BALLOT = false>
 __device__ __forceinline__ bool chroma_line(int p1, int &p0, int &q0, int q1, int bs, int alpha, int beta, int tc1)
 {
-    const bool f = bs != 0 && absdiff8(p0, q0) < alpha && absdiff8(p1, p0) < beta && absdiff8(q1, q0) < beta;
-    if (!__any(f)) return false;
+    bool f;
+    if constexpr (BALLOT) {
+        const bool f_bs = bs != 0, f_a = absdiff8(p0, q0) < alpha, f_p = absdiff8(p1, p0) < beta, f_q = absdiff8(q1, q0) < beta;
+        f = f_bs && f_a && f_p && f_q;
+        if (!lanes_all4(f_bs, f_a, f_p, f_q)) return false;
+    } else {
+        f = bs != 0 && absdiff8(p0, q0) < alpha && absdiff8(p1, p0) < beta && absdiff8(q1, q0) < beta;
+        if (!__any(f)) return false;
+    }
     const int tc = f && bs < 4 ? tc1 : 0;
     const int delta = med3i((((q0 - p0) * 4) + (p1 - q1) + 4) >> 3, -tc, tc);
     const bool fi = f && bs == 4;
@@ -196,21 +215,22 @@ __device__ __forceinline__ bool chroma_line(int p1, int &p0, int &q0, int q1, in
     return true;
 }
 /* the same on a row held as dwords: P = samples -4..-1 of the edge, Q = samples 0..3 (memory order) */
-template <bool MAY_INTRA>
+template <bool MAY_INTRA, bool BALLOT>
 __device__ __forceinline__ bool luma_row_edge(uint32_t &P, uint32_t &Q, int bs, int alpha, int beta, int tc0)
 {
     int p3 = P & 0xFF, p2 = (P >> 8) & 0xFF, p1 = (P >> 16) & 0xFF, p0 = P >> 24;
     int q0 = Q & 0xFF, q1 = (Q >> 8) & 0xFF, q2 = (Q >> 16) & 0xFF, q3 = Q >> 24;
-    const int r = luma_line<MAY_INTRA>(p3, p2, p1, p0, q0, q1, q2, q3, bs, alpha, beta, tc0);
+    const int r = luma_line<MAY_INTRA, BALLOT>(p3, p2, p1, p0, q0, q1, q2, q3, bs, alpha, beta, tc0);
     if (!r) return false;
     P = (uint32_t)p3 | ((uint32_t)p2 << 8) | ((uint32_t)p1 << 16) | ((uint32_t)p0 << 24);
     Q = (uint32_t)q0 | ((uint32_t)q1 << 8) | ((uint32_t)q2 << 16) | ((uint32_t)q3 << 24);
     return true;
 }
+template <bool BALLOT>
 __device__ __forceinline__ bool chroma_row_edge(uint32_t &P, uint32_t &Q, int bs, int alpha, int beta, int tc1)
 {
     int p0 = P >> 24, q0 = Q & 0xFF;
-    if (!chroma_line((P >> 16) & 0xFF, p0, q0, (Q >> 8) & 0xFF, bs, alpha, beta, tc1)) return false;
+    if (!chroma_line<BALLOT>((P >> 16) & 0xFF, p0, q0, (Q >> 8) & 0xFF, bs, alpha, beta, tc1)) return false;
     P = (P & 0x00FFFFFFu) | ((uint32_t)p0 << 24);
     Q = (Q & 0xFFFFFF00u) | (uint32_t)q0;
     return true;
@@ -226,6 +246,7 @@ __device__ __forceinline__ int byte_of(uint32_t w, int e) { return (int)((w >> (
  * filterSamplesFlag conditions first and leaves when no line of the wave passes (the reference's own per-line `continue`,
  * h264dsp_template.c:117-121, taken at wave granularity), and only what changed is written back: bit-identical either way.
  * ab_*: alpha | beta << 8, tc*: tc0 per edge (bytes), of the left (l) and the inner (i) edges; c*: chroma */
+template <bool BALLOT = false>
 __device__ __forceinline__ void vertical_edges(uint8_t *rowp, uint8_t *leftp, uint8_t *crowp, uint8_t *cleftp, uint32_t bsw0, uint32_t bsc0,
                                                uint32_t ab_l, uint32_t ab_i, uint32_t tcl0, uint32_t tci0, uint32_t cab_l, uint32_t cab_i, uint32_t ccl0, uint32_t cci0)
 {
@@ -233,14 +254,14 @@ __device__ __forceinline__ void vertical_edges(uint8_t *rowp, uint8_t *leftp, ui
     const uint2 cown = *reinterpret_cast<const uint2 *>(crowp);
     uint32_t wl = *reinterpret_cast<const uint32_t *>(leftp), w0 = own.x, w1 = own.y, w2 = own.z, w3 = own.w;
     uint32_t cl = *reinterpret_cast<const uint32_t *>(cleftp), cw0 = cown.x, cw1 = cown.y;      /* columns -4..-1, 0..3, 4..7 */
-    const bool c0 = luma_row_edge<true>(wl, w0, byte_of(bsw0, 0), ab_alpha(ab_l), ab_beta(ab_l), byte_of(tcl0, 0));
-    const bool c1 = luma_row_edge<false>(w0, w1, byte_of(bsw0, 1), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci0, 1));
-    const bool c2 = luma_row_edge<false>(w1, w2, byte_of(bsw0, 2), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci0, 2));
-    const bool c3 = luma_row_edge<false>(w2, w3, byte_of(bsw0, 3), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci0, 3));
+    const bool c0 = luma_row_edge<true, BALLOT>(wl, w0, byte_of(bsw0, 0), ab_alpha(ab_l), ab_beta(ab_l), byte_of(tcl0, 0));
+    const bool c1 = luma_row_edge<false, BALLOT>(w0, w1, byte_of(bsw0, 1), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci0, 1));
+    const bool c2 = luma_row_edge<false, BALLOT>(w1, w2, byte_of(bsw0, 2), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci0, 2));
+    const bool c3 = luma_row_edge<false, BALLOT>(w2, w3, byte_of(bsw0, 3), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci0, 3));
     if (c0) *reinterpret_cast<uint32_t *>(leftp) = wl;
     if (c0 || c1 || c2 || c3) lds16(rowp, make_uint4(w0, w1, w2, w3));
-    const bool d0 = chroma_row_edge(cl, cw0, byte_of(bsc0, 0), ab_alpha(cab_l), ab_beta(cab_l), byte_of(ccl0, 0));
-    const bool d1 = chroma_row_edge(cw0, cw1, byte_of(bsc0, 2), ab_alpha(cab_i), ab_beta(cab_i), byte_of(cci0, 2));
+    const bool d0 = chroma_row_edge<BALLOT>(cl, cw0, byte_of(bsc0, 0), ab_alpha(cab_l), ab_beta(cab_l), byte_of(ccl0, 0));
+    const bool d1 = chroma_row_edge<BALLOT>(cw0, cw1, byte_of(bsc0, 2), ab_alpha(cab_i), ab_beta(cab_i), byte_of(cci0, 2));
     if (d0) *reinterpret_cast<uint32_t *>(cleftp) = cl;
     if (d0 || d1) *reinterpret_cast<mi355_u32x2 *>(crowp) = mi355_u32x2{ cw0, cw1 };
 }
@@ -655,7 +676,14 @@ k_deblock_bands(const mi355_h264_frame *__restrict__ frames, int band0, int skip
  *    finds stores a whole step old, and the progress counter is published behind it without a drain of its own;
  *  - the boundary-strength roles sit in a 768-byte LDS table, the address arithmetic in a dozen per-lane constants.
  * The kernel runs at the VALU's issue rate (profiles/r04d_pmc_deblock_tiled_f2048.txt: 555 VALU per step, 84 % of the issue slots
- * at four waves per SIMD). */
+ * at four waves per SIMD; 477 per step since round 8 took what a step executed outside the edge arithmetic down: wave-level votes on the scalar
+ * unit, lane constants for the horizontal edges' columns and the parm words, strengths packed by two quad exchanges — profiles/r08_experiments.md). */
+/* the bitwise or over this lane's group of four (two DPP exchanges) */
+__device__ __forceinline__ uint32_t quad_or(uint32_t v)
+{
+    v |= (uint32_t)quad_xor1((int)v);
+    return v | (uint32_t)quad_xor2((int)v);
+}
 struct __attribute__((aligned(128))) Deblock3Lds {
     uint8_t y[4][4][256];
     uint8_t c[4][4][128];
@@ -728,12 +756,19 @@ __device__ __forceinline__ void deblock3_band(Deblock3Lds &s, Deblock3Mail *mail
     uint8_t *const lds = reinterpret_cast<uint8_t *>(&s);
     constexpr uint32_t OY = (uint32_t)offsetof(Deblock3Lds, y), OC = (uint32_t)offsetof(Deblock3Lds, c), OA = (uint32_t)offsetof(Deblock3Lds, above);
     uint32_t k_g2, k_rec, k_topd, k_dy, k_dc, k_gc2, k_da, k_sab, k_sc, k_sd, k_se, k_la, k_lc, k_ld, k_rv, k_cv, k_flags;
-    enum { KF_ROW = 1, KF_TOP = 2, KF_BOTTOM = 4, KF_LO = 8, KF_G0 = 16, KF_ROW0 = 32 };
+    uint32_t k_pl, k_pc, k_hy, k_ha, k_hc, k_hca;
+    /* k_flags: the bits below; bits 8..15: four times the lane whose packed strengths this lane's chroma line takes; bits 16..23: eight times
+     * the edge of this lane's boundary-strength role (the byte of a packed word its strength goes to) */
+    enum { KF_ROW = 1, KF_TOP = 2, KF_BOTTOM = 4, KF_LO = 8, KF_G0 = 16, KF_ROW0 = 32, KF_CSRC_SHIFT = 8, KF_EDGE8_SHIFT = 16 };
+    constexpr uint32_t OP = (uint32_t)offsetof(Deblock3Lds, parm), PB = (uint32_t)sizeof(uint32_t[4][9][2]);
     {
         const int lane = lane_id(), g = lane >> 4, l = lane & 15, ga = (g - 1) & 3;
         const int mb_y = 4 * band + g, mb_yc = mb_y < H ? mb_y : H - 1;
         const bool row_ok = mb_y < H, has_t = row_ok && mb_y > 0, bottom = row_ok && (g == 3 || mb_y == H - 1), lo = l < 8;
         k_flags = (row_ok ? KF_ROW : 0) | (has_t ? KF_TOP : 0) | (bottom ? KF_BOTTOM : 0) | (lo ? KF_LO : 0) | (g == 0 ? KF_G0 : 0) | (mb_yc == 0 ? KF_ROW0 : 0);
+        /* a chroma line (row / column l & 7 of plane l >> 3) lies in luma segment (l & 7) >> 1, whose four lanes all hold its packed strengths */
+        k_flags |= (uint32_t)(4 * ((lane & ~15) | (((l & 7) >> 1) << 2))) << KF_CSRC_SHIFT;
+        k_flags |= (uint32_t)(8 * (l & 3)) << KF_EDGE8_SHIFT;
         k_g2 = (uint32_t)(2 * g);
         k_rec = (uint32_t)(64 * mb_yc * W);
         k_topd = mb_yc > 0 ? 64u * (uint32_t)W : 0u;
@@ -754,6 +789,16 @@ __device__ __forceinline__ void deblock3_band(Deblock3Lds &s, Deblock3Mail *mail
         k_la = lo ? k_rv : (uint32_t)(g ? 256 * ga + 128 + 16 * ((l - 8) ^ ga) : 16 * ((l - 8) ^ 3));       /* (a): row l of the left tile / (b): row l of the tile above */
         k_lc = (uint32_t)(g ? 128 * ga + 16 * ((l >> 1) ^ ga) + 8 * (l & 1) : 128 + 16 * ((l >> 1) ^ 3) + 8 * (l & 1));   /* chroma row of the tile above */
         k_ld = (uint32_t)(256 * g + 16 * ((8 + (l >> 1)) ^ g) + 8 * (l & 1));              /* half (l & 1) of row 8 + (l >> 1) of the own tile */
+        k_pl = OP + (uint32_t)(72 * g);                                                    /* parm[0][g][0]: the luma words of this lane's group */
+        k_pc = k_pl + (uint32_t)(24 + 24 * (l >> 3));                                      /* parm[0][g][3 + 3 * plane]: this lane's chroma plane */
+        /* the horizontal edges' columns.  Row r = 4k + j of group g's tile lies at 64k + 16 * (j ^ g) = 64k + ((16 * g) ^ (16 * j)): the base of
+         * j = 0 carries 16 * g, and since nothing else of an address touches bits 4 and 5 (the ring slots, `above` and the tiles are multiples of
+         * 64, a column is below 16) the bases of j = 1..3 are that one exclusive-or 16 * j.  Without the term of the ring slot, as the rest */
+        k_hy = (uint32_t)(256 * g + 16 * g + l);                                           /* column l of the own tile */
+        k_ha = (uint32_t)(g ? 256 * ga + 128 + 64 + 16 * ga + l : 64 + 16 * 3 + l);        /* rows 12..15 of the tile above (in above[]: swizzled with 3) */
+        k_hc = (uint32_t)(128 * g + 16 * g + 64 * (l >> 3) + (l & 7));                     /* column l & 7 of plane l >> 3 of the own chroma tile */
+        k_hca = (uint32_t)(g ? 128 * ga + 16 * (ga ^ 3) + 64 * (l >> 3) + (l & 7) : 128 + 64 * (l >> 3) + (l & 7));   /* rows 6, 7 of the chroma tile above */
+        static_assert((OY & 63) == 0 && (OC & 63) == 0 && (OA & 63) == 0, "bits 4 and 5 of a column's address are the swizzle's alone");
     }
     auto kf = [&](uint32_t bit) { return (k_flags & bit) != 0; };
     /* records and vectors of group g's macroblock t1 - 2g: into registers */
@@ -830,9 +875,9 @@ __device__ __forceinline__ void deblock3_band(Deblock3Lds &s, Deblock3Mail *mail
      * byte e of bsw0 / bsw1 = the strength of vertical / horizontal edge e of this lane's luma row / column, bsc0 / bsc1 the same for its chroma
      * line; alpha / beta / tc0 of the step into parm[pb] */
     auto strengths = [&](int t, int pb, uint32_t &bsw0, uint32_t &bsw1, uint32_t &bsc0, uint32_t &bsc1) {
-        const int lane = lane_id(), g = lane >> 4, l = lane & 15;
-        const int mb_y = 4 * band + g, mb_x = t - 2 * g;
-        const bool row_ok = mb_y < H, has_t = row_ok && mb_y > 0, valid = row_ok && mb_x >= 0 && mb_x < W;
+        const int l = lane_id() & 15;
+        const int mb_x = t - (int)k_g2;
+        const bool has_t = kf(KF_TOP), valid = kf(KF_ROW) && (uint32_t)mb_x < (uint32_t)W;
         const bool outer = (l & 3) == 0, odd = (l & 1) != 0;
         const MbInfo &h = pre.h, &ht = pre.ht;
         const mi355_u32x4 ra = *reinterpret_cast<const mi355_u32x4 *>(&s.role[l][0]), rb = *reinterpret_cast<const mi355_u32x4 *>(&s.role[l][4]);
@@ -841,10 +886,11 @@ __device__ __forceinline__ void deblock3_band(Deblock3Lds &s, Deblock3Mail *mail
         const bool have_left = filter && mb_x > 0 && (h.flags() & MI355_MBF_LEFT_EDGE), have_top = filter && has_t && (h.flags() & MI355_MBF_TOP_EDGE);
         const uint32_t b0 = bs_role(h, hl, outer, odd, filter && (!outer || have_left), r0, pre.p0, pre.q0, two_lists, mv_far, 4u);
         const uint32_t b1 = bs_role(h, ht, outer, odd, filter && (!outer || have_top), r1, pre.p1, pre.q1, two_lists, mv_far, field ? 3u : 4u);
-        bsw0 = (uint32_t)quad_bcast<0>((int)b0) | ((uint32_t)quad_bcast<1>((int)b0) << 8) | ((uint32_t)quad_bcast<2>((int)b0) << 16) | ((uint32_t)quad_bcast<3>((int)b0) << 24);
-        bsw1 = (uint32_t)quad_bcast<0>((int)b1) | ((uint32_t)quad_bcast<1>((int)b1) << 8) | ((uint32_t)quad_bcast<2>((int)b1) << 16) | ((uint32_t)quad_bcast<3>((int)b1) << 24);
-        const int csrc = (lane & ~15) | (((l & 7) >> 1) << 2);
-        bsc0 = (uint32_t)__shfl((int)bsw0, csrc); bsc1 = (uint32_t)__shfl((int)bsw1, csrc);
+        /* the four strengths of a line: edge e of this lane's segment sits in lane e of its group of four: each into its byte, two exchanges */
+        const uint32_t edge8 = k_flags >> KF_EDGE8_SHIFT;
+        bsw0 = quad_or(b0 << edge8); bsw1 = quad_or(b1 << edge8);
+        const uint32_t csrc4 = (k_flags >> KF_CSRC_SHIFT) & 0xFFu;
+        bsc0 = lane_gather4(bsw0, csrc4); bsc1 = lane_gather4(bsw1, csrc4);
         /* alpha / beta / tc0: lane k < 9 of a group looks up (component k / 3, edge kind k % 3) */
         const int comp = l < 3 ? 0 : (l < 6 ? 1 : 2), kind = l - 3 * comp;
         const int kindc = kind > 2 ? 2 : kind;
@@ -860,42 +906,41 @@ __device__ __forceinline__ void deblock3_band(Deblock3Lds &s, Deblock3Mail *mail
         const int ia = clip3(qp + h.alpha_off(), 0, 51), ib = clip3(qp + h.beta_off(), 0, 51);
         const uint32_t w0 = (uint32_t)s.t_alpha[ia] | ((uint32_t)s.t_beta[ib] << 8);
         const uint32_t w1 = s.t_tc0[ia] + (comp ? 0x01010100u : 0u);
-        if (l < 9) { s.parm[pb][g][l][0] = w0; s.parm[pb][g][l][1] = w1; }
+        if (l < 9) *reinterpret_cast<mi355_u32x2 *>(lds + (k_pl + PB * (uint32_t)pb + 8u * (uint32_t)l)) = mi355_u32x2{ w0, w1 };
         hl = h;
     };
     auto edges_v = [&](int t, int pb, uint32_t bsw0, uint32_t bsc0) {
         /* ---- vertical edges: lane l of a group = luma row l and chroma row (plane l >> 3, row l & 7), from and to the ring ---------------- */
         {
-            const int lane = lane_id(), g = lane >> 4, l = lane & 15;
-            const uint32_t *pl = s.parm[pb][g][0], *pc = s.parm[pb][g][3 + 3 * (l >> 3)];
+            const uint32_t *pl = reinterpret_cast<const uint32_t *>(lds + (k_pl + PB * (uint32_t)pb)), *pc = reinterpret_cast<const uint32_t *>(lds + (k_pc + PB * (uint32_t)pb));
             const uint32_t ab_i = pl[0], tr_i = pl[1], ab_l = pl[2], tr_l = pl[3];
             const uint32_t cab_i = pc[0], ctr_i = pc[1], cab_l = pc[2], ctr_l = pc[3];
             const uint32_t tci0 = byte_perm(0, tr_i, bsw0 & 0x03030303u), tcl0 = byte_perm(0, tr_l, bsw0 & 3u);
             const uint32_t cci0 = byte_perm(0, ctr_i, bsc0 & 0x03030303u), ccl0 = byte_perm(0, ctr_l, bsc0 & 3u);
             uint8_t *rowp = lds + (k_rv + OY + 1024u * (uint32_t)(t & 3)), *leftp = lds + (k_rv + OY + 12u + 1024u * (uint32_t)((t - 1) & 3));
             uint8_t *crowp = lds + (k_cv + OC + 512u * (uint32_t)(t & 3)), *cleftp = lds + (k_cv + OC + 4u + 512u * (uint32_t)((t - 1) & 3));
-            vertical_edges(rowp, leftp, crowp, cleftp, bsw0, bsc0, ab_l, ab_i, tcl0, tci0, cab_l, cab_i, ccl0, cci0);
+            vertical_edges<true>(rowp, leftp, crowp, cleftp, bsw0, bsc0, ab_l, ab_i, tcl0, tci0, cab_l, cab_i, ccl0, cci0);
         }
     };
     auto edges_h = [&](int t, int pb, uint32_t bsw1, uint32_t bsc1) {
         /* ---- horizontal edges: lane l of a group = luma column l and chroma column (plane l >> 3, column l & 7); rows -4..-1 (chroma -2, -1)
          * are rows 12..15 (6, 7) of the tile above — in the ring of the group above, or in above[] — read and patched where they lie -------- */
         {
-            const int lane = lane_id(), g = lane >> 4, l = lane & 15, ga = (g - 1) & 3, cp = l >> 3, cr = l & 7;
-            const uint32_t *pl = s.parm[pb][g][0], *pc = s.parm[pb][g][3 + 3 * cp];
+            const uint32_t *pl = reinterpret_cast<const uint32_t *>(lds + (k_pl + PB * (uint32_t)pb)), *pc = reinterpret_cast<const uint32_t *>(lds + (k_pc + PB * (uint32_t)pb));
             const uint32_t ab_i = pl[0], tr_i = pl[1], ab_t = pl[4], tr_t = pl[5];
             const uint32_t cab_i = pc[0], ctr_i = pc[1], cab_t = pc[4], ctr_t = pc[5];
             const uint32_t tci1 = byte_perm(0, tr_i, bsw1 & 0x03030303u), tct1 = byte_perm(0, tr_t, bsw1 & 3u);
             const uint32_t cci1 = byte_perm(0, ctr_i, bsc1 & 0x03030303u), cct1 = byte_perm(0, ctr_t, bsc1 & 3u);
-            uint8_t *const Y = &s.y[t & 3][g][l], *const C = &s.c[t & 3][g][64 * cp + cr];
-            uint8_t *const A = (g ? &s.y[(t - 2) & 3][ga][128] : &s.above[t & 1][0]) + l;          /* row 8 + m at A[16 * (m ^ ga)] */
-            uint8_t *const CA = (g ? &s.c[(t - 2) & 3][ga][0] : &s.above[t & 1][128]) + 64 * cp + cr;
-            /* row r of the own tile at Y[16 * (r ^ g)]: r = 4k + j -> 64k + 16 * (j ^ g): one base per j (the swizzle is an exclusive or: not an
-             * address offset the instruction could carry), the rest immediate offsets */
-            const int g16 = 16 * g, a16 = 16 * ga;
-            uint8_t *const Y0 = Y + g16, *const Y1 = Y + (g16 ^ 16), *const Y2 = Y + (g16 ^ 32), *const Y3 = Y + (g16 ^ 48);
-            uint8_t *const A0 = A + 64 + a16, *const A1 = A + 64 + (a16 ^ 16), *const A2 = A + 64 + (a16 ^ 32), *const A3 = A + 64 + (a16 ^ 48);
-            uint8_t *const C0 = C + g16, *const C1 = C + (g16 ^ 16), *const C2 = C + (g16 ^ 32), *const CA3 = CA + (a16 ^ 48);
+            /* row r of the own tile at 16 * (r ^ g): r = 4k + j -> 64k + 16 * (j ^ g): one base per j (the swizzle is an exclusive or: not an
+             * address offset the instruction could carry), the rest immediate offsets.  The base of j = 0 is a lane constant plus the ring slot,
+             * the others are it exclusive-or 16 * j (see k_hy).  The tile above: the ring of the group above, two steps back, or above[] */
+            const bool g0 = kf(KF_G0);
+            const uint32_t ua = OA + 256u * (uint32_t)(t & 1);
+            const uint32_t yb = k_hy + (OY + 1024u * (uint32_t)(t & 3)), cb = k_hc + (OC + 512u * (uint32_t)(t & 3));
+            const uint32_t ab = k_ha + (g0 ? ua : OY + 1024u * (uint32_t)((t - 2) & 3)), cab = k_hca + (g0 ? ua : OC + 512u * (uint32_t)((t - 2) & 3));
+            uint8_t *const Y0 = lds + yb, *const Y1 = lds + (yb ^ 16u), *const Y2 = lds + (yb ^ 32u), *const Y3 = lds + (yb ^ 48u);
+            uint8_t *const A0 = lds + ab, *const A1 = lds + (ab ^ 16u), *const A2 = lds + (ab ^ 32u), *const A3 = lds + (ab ^ 48u);
+            uint8_t *const C0 = lds + cb, *const C1 = lds + (cb ^ 16u), *const C2 = lds + (cb ^ 32u), *const CA3 = lds + cab;
 #define YJ(j) ((j) == 0 ? Y0 : ((j) == 1 ? Y1 : ((j) == 2 ? Y2 : Y3)))
 #define AJ(j) ((j) == 0 ? A0 : ((j) == 1 ? A1 : ((j) == 2 ? A2 : A3)))
 #define YR(r) YJ((r) & 3)[64 * ((r) >> 2)]
@@ -906,25 +951,25 @@ __device__ __forceinline__ void deblock3_band(Deblock3Lds &s, Deblock3Mail *mail
             int y4 = YR(0), y5 = YR(1), y6 = YR(2), y7 = YR(3), y8 = YR(4), y9 = YR(5), y10 = YR(6), y11 = YR(7);
             int y12 = YR(8), y13 = YR(9), y14 = YR(10), y15 = YR(11), y16 = YR(12), y17 = YR(13), y18 = YR(14);
             int u0 = CAR(6), u1 = CAR(7), u2 = CR(0), u3 = CR(1), u4 = CR(2), u5 = CR(3), u6 = CR(4), u7 = CR(5);
-            const int e0 = luma_line<true>(y0, y1, y2, y3, y4, y5, y6, y7, byte_of(bsw1, 0), ab_alpha(ab_t), ab_beta(ab_t), byte_of(tct1, 0));
+            const int e0 = luma_line<true, true>(y0, y1, y2, y3, y4, y5, y6, y7, byte_of(bsw1, 0), ab_alpha(ab_t), ab_beta(ab_t), byte_of(tct1, 0));
             if (e0) {
                 if (e0 == 2) { AR(13) = (uint8_t)y1; YR(2) = (uint8_t)y6; }
                 AR(14) = (uint8_t)y2; AR(15) = (uint8_t)y3; YR(0) = (uint8_t)y4; YR(1) = (uint8_t)y5;
             }
-            if (luma_line<false>(y4, y5, y6, y7, y8, y9, y10, y11, byte_of(bsw1, 1), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci1, 1))) {
+            if (luma_line<false, true>(y4, y5, y6, y7, y8, y9, y10, y11, byte_of(bsw1, 1), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci1, 1))) {
                 YR(2) = (uint8_t)y6; YR(3) = (uint8_t)y7; YR(4) = (uint8_t)y8; YR(5) = (uint8_t)y9;
             }
-            if (luma_line<false>(y8, y9, y10, y11, y12, y13, y14, y15, byte_of(bsw1, 2), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci1, 2))) {
+            if (luma_line<false, true>(y8, y9, y10, y11, y12, y13, y14, y15, byte_of(bsw1, 2), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci1, 2))) {
                 YR(6) = (uint8_t)y10; YR(7) = (uint8_t)y11; YR(8) = (uint8_t)y12; YR(9) = (uint8_t)y13;
             }
             int y19 = 0;
-            if (luma_line<false>(y12, y13, y14, y15, y16, y17, y18, y19, byte_of(bsw1, 3), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci1, 3))) {
+            if (luma_line<false, true>(y12, y13, y14, y15, y16, y17, y18, y19, byte_of(bsw1, 3), ab_alpha(ab_i), ab_beta(ab_i), byte_of(tci1, 3))) {
                 YR(10) = (uint8_t)y14; YR(11) = (uint8_t)y15; YR(12) = (uint8_t)y16; YR(13) = (uint8_t)y17;
             }
-            if (chroma_line(u0, u1, u2, u3, byte_of(bsc1, 0), ab_alpha(cab_t), ab_beta(cab_t), byte_of(cct1, 0))) {
+            if (chroma_line<true>(u0, u1, u2, u3, byte_of(bsc1, 0), ab_alpha(cab_t), ab_beta(cab_t), byte_of(cct1, 0))) {
                 CAR(7) = (uint8_t)u1; CR(0) = (uint8_t)u2;
             }
-            if (chroma_line(u4, u5, u6, u7, byte_of(bsc1, 2), ab_alpha(cab_i), ab_beta(cab_i), byte_of(cci1, 2))) {
+            if (chroma_line<true>(u4, u5, u6, u7, byte_of(bsc1, 2), ab_alpha(cab_i), ab_beta(cab_i), byte_of(cci1, 2))) {
                 CR(3) = (uint8_t)u5; CR(4) = (uint8_t)u6;
             }
 #undef YJ

@@ -105,6 +105,22 @@ static inline int lane_value(int v, int l) { return __shfl(v, l); }
 #else
 __device__ __forceinline__ int lane_value(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
 #endif
+/* lane_mask: bit l = lane l holds f.  lanes_all4: the lanes that hold all four conditions — each comparison leaves its lane mask in scalar
+ * registers and the masks meet there; a vote on `a && b && c && d` (__any) first makes a 0 / 1 value per lane of it and compares that again */
+#ifdef MI355_HIP_EMU_H
+static inline uint64_t lane_mask(bool f) { return (uint64_t)__ballot(f); }
+static inline uint64_t lanes_all4(bool a, bool b, bool c, bool d) { return (uint64_t)__ballot(a && b && c && d); }
+#else
+__device__ __forceinline__ uint64_t lane_mask(bool f) { return __builtin_amdgcn_ballot_w64(f); }
+__device__ __forceinline__ uint64_t lanes_all4(bool a, bool b, bool c, bool d) { return lane_mask(a) & lane_mask(b) & lane_mask(c) & lane_mask(d); }
+#endif
+/* the value lane `src4 >> 2` of the wave holds; src4 = 4 * lane, 0 .. 252, a per-lane constant the caller keeps: the
+ * shuffle alone (ds_bpermute_b32), without __shfl's arithmetic on the lane number in front of it */
+#ifdef MI355_HIP_EMU_H
+static inline uint32_t lane_gather4(uint32_t v, uint32_t src4) { return (uint32_t)__shfl((int)v, (int)(src4 >> 2)); }
+#else
+__device__ __forceinline__ uint32_t lane_gather4(uint32_t v, uint32_t src4) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)src4, (int)v); }
+#endif
 
 /* a value every lane of the wave holds identically (read from this wave's LDS record): telling the
  * compiler moves everything derived from it to the scalar unit */

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Developer experiment (GPU box, round 5): pass times of the three passes on a few workloads of the config-2 family with the library that is in
-libav_amd/ right now (the session script swaps build/variants/*.so in).  usage: exp_workloads.py <label> [workload ...]   workloads: base mixed f512 f64 intra512 intra64"""
+libav_amd/ right now (the session script swaps build/variants/*.so in).  usage: exp_workloads.py <label> [workload ...]   workloads: base mixed smooth f512 f64 intra512 intra64"""
 import ctypes as C
 import os
 import sys
@@ -67,6 +67,8 @@ for w in which:
         measure("base", base, 2048)
     elif w == "mixed":
         measure("mixed", HF.synth_frames_fast(4, mbw, mbh, seed=0x2640, lib=lib, partitions="mixed"), 2048)
+    elif w == "smooth":     # bench.py's config2_smooth_f2048: smooth references, small residuals: the loop filter's conditions pass
+        measure("smooth", HF.synth_frames_fast(4, mbw, mbh, seed=0x2264, lib=lib, refs="smooth", coef_b=4), 2048)
     elif w == "f512":
         measure("f512", base, 512)
     elif w == "f64":
