@@ -340,6 +340,20 @@ int mi355_h264_deblock_dev(const mi355_h264_frame *d_frames, int nframes, int ma
  * above cannot look, and launches the loop filter's kernel for each layout — the waves of the kernel whose layout a picture does
  * not have leave at once, ~1 us per 1000 macroblock-row bands): `layouts` = MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED, or one of them. */
 int mi355_h264_deblock_layouts_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int layouts, void *stream);
+/* The same for a caller whose loop filter shares the device with other launches (mi355_h264_pipelines_decode_dev: the other shares'
+ * reconstructions).  k_deblock_tiled then runs as `resident_waves` waves that take the batch's bands (four macroblock rows of a
+ * picture) in turn, instead of a wave per band: a loop-filter wave holds registers and LDS of two reconstruction waves for
+ * hundreds of microseconds.  resident_waves = 0: the rule's count for a launch with others beside it (mi355_h264_deblock_resident
+ * with shares = 2); at or above the number of bands: a wave per band, what the two entry points above launch.  Same pictures
+ * whatever the count.  A count other than 0 names waves of k_deblock_tiled: the tiled pictures then go through that kernel also where
+ * the rule would take k_deblock_tiled2 (few bands); with 0 the kernel forms are those of the entry points above.  The environment variable
+ * MI355_DEBLOCK_RESIDENT = n pins the count the rule gives (a developer switch).  Returns as above; -1 also for a negative count. */
+int mi355_h264_deblock_resident_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int layouts,
+                                    int resident_waves, void *stream);
+/* *resident_waves = what the rule picks for k_deblock_tiled's launch over this batch on a device of `cus` CUs (0 = this device)
+ * when the caller runs `shares` such batches side by side (1: nothing beside it: a wave per band), MI355_DEBLOCK_RESIDENT
+ * included; 0 when the batch has no one-wave tiled launch (mi355_h264_deblock_plan: tiled_waves != 1).  Returns 0, or -1 (arguments). */
+int mi355_h264_deblock_resident(int nframes, int max_mb_width, int max_mb_height, int layouts, int cus, int shares, int *resident_waves);
 
 /* The kernel forms the two entry points above launch for a batch (the developer switches MI355_DEBLOCK_FORM / MI355_DEBLOCK_WAVES included):
  * tiled pictures go through ONE launch of k_deblock_tiled (one wave per band) or, when the batch has fewer than two bands per SIMD,

@@ -1074,24 +1074,43 @@ __device__ __forceinline__ void deblock3_band(Deblock3Lds &s, Deblock3Mail *mail
 
 /* Band-major tickets: all pictures' band 0, then band 1, ...; a wave's only dependence is the ticket nframes before its own, taken by a
  * wave that is running or done.  sync[0]: the ticket counter; sync[16 ...]: one progress word per picture and band.  Pictures that
- * are not tiled are left to k_deblock / k_deblock_bands (their waves take a ticket, look at the descriptor and leave). */
+ * are not tiled are left to k_deblock / k_deblock_bands (their tickets are taken, looked at and skipped).
+ *
+ * Resident waves (round 9): the launch is `resident` workgroups of one wave, at most one per ticket, and a wave takes tickets until
+ * the counter is past nframes * nbands — how many loop-filter waves sit on the device is the launcher's choice, not the number of
+ * bands.  Why no wave waits for ever, whatever `resident` is and in whatever order the hardware starts the workgroups: the counter
+ * hands tickets out in increasing order, and only to waves that are running.  A wave waits on the progress word of a LOWER ticket
+ * alone; that ticket's holder took it while running, so it is running or done.  The lowest unfinished ticket waits for nobody (all
+ * below it are done), so it finishes, and then the next one is the lowest.  A single wave (resident = 1) filters every band in
+ * ticket order and never waits.
+ * Between two bands of a wave: the last step's dma_issue(t + 1) has requested tiles nobody uses, into ring slot nsteps & 3 and
+ * above[]; they have landed, and every store of the band has left the wave, before the next band's tables, parm words and first
+ * dma_issue reuse the same LDS (one s_waitcnt vmcnt(0)).  seen, hl and pre are deblock3_band's locals: fresh per band.
+ * turns = 0: a launch of a wave per ticket, whose waves leave after their band without asking the counter again (round 9 measured the
+ * second request of 34 816 waves on the one counter: the kernel alone 4 % slower). */
 #ifdef MI355_DB3_WAVES
 __attribute__((amdgpu_waves_per_eu(MI355_DB3_WAVES, MI355_DB3_WAVES)))
 #endif
 __global__ void __launch_bounds__(64)
-k_deblock_tiled(const mi355_h264_frame *__restrict__ frames, int nframes, int nbands, uint32_t *sync)
+k_deblock_tiled(const mi355_h264_frame *__restrict__ frames, int nframes, int nbands, uint32_t *sync, int turns)
 {
     __shared__ Deblock3Lds s;
-    uint32_t tk = 0;
-    if (lane_id() == 0) tk = atomicAdd(mi355_global(sync), 1u);
-    tk = (uint32_t)lane_value((int)tk, 0);
-    const int band = (int)(tk / (uint32_t)nframes), pic = (int)(tk - (uint32_t)band * (uint32_t)nframes);
-    if (band >= nbands) return;
-    const mi355_h264_frame &fr = frames[pic];
-    if (4 * band >= uniform(fr.mb_height) || uniform(fr.surface_layout) != MI355_SURFACE_TILED) return;
-    uint32_t *prog = mi355_global(sync) + 16 + (size_t)pic * (size_t)nbands;
-    if (mi355_global(fr.mv[1]) != nullptr) deblock3_band<true, 1>(s, nullptr, fr, band, prog, 0);
-    else deblock3_band<false, 1>(s, nullptr, fr, band, prog, 0);
+    const uint32_t ntickets = (uint32_t)nframes * (uint32_t)nbands;
+    do {
+        uint32_t tk = 0;
+        if (lane_id() == 0) tk = atomicAdd(mi355_global(sync), 1u);
+        tk = (uint32_t)lane_value((int)tk, 0);
+        if (tk >= ntickets) return;
+        const int band = (int)(tk / (uint32_t)nframes), pic = (int)(tk - (uint32_t)band * (uint32_t)nframes);
+        const mi355_h264_frame &fr = frames[pic];
+        if (4 * band >= uniform(fr.mb_height) || uniform(fr.surface_layout) != MI355_SURFACE_TILED) continue;
+        uint32_t *prog = mi355_global(sync) + 16 + (size_t)pic * (size_t)nbands;
+        if (mi355_global(fr.mv[1]) != nullptr) deblock3_band<true, 1>(s, nullptr, fr, band, prog, 0);
+        else deblock3_band<false, 1>(s, nullptr, fr, band, prog, 0);
+        if (!turns) return;
+        agent_drain_stores();
+        MI355_WAVE_SYNC();
+    } while (turns);
 }
 /* the same with two waves per band (few pictures): see deblock3_band */
 __global__ void __launch_bounds__(128)
@@ -1172,7 +1191,7 @@ void mi355::sync_words_release(hipStream_t st)
 /* The forms of the loop filter.  deblock_plan() is the rule mi355_h264_deblock_layouts_dev follows and mi355_h264_deblock_plan reports;
  * deblock_launch() runs a plan (also one that mi355_h264_deblock_form_dev names). */
 namespace {
-/* MI355_DEBLOCK_FORM / MI355_DEBLOCK_WAVES (developer switches), read once per process */
+/* MI355_DEBLOCK_FORM / MI355_DEBLOCK_WAVES / MI355_DEBLOCK_RESIDENT (developer switches), read once per process */
 int deblock_form_pin()
 {
     static const int force = std::getenv("MI355_DEBLOCK_FORM") ? std::atoi(std::getenv("MI355_DEBLOCK_FORM")) : 0;
@@ -1181,6 +1200,11 @@ int deblock_form_pin()
 int deblock_waves_pin()
 {
     static const int pin = std::getenv("MI355_DEBLOCK_WAVES") ? std::atoi(std::getenv("MI355_DEBLOCK_WAVES")) : 0;
+    return pin;
+}
+int deblock_resident_pin()
+{
+    static const int pin = std::getenv("MI355_DEBLOCK_RESIDENT") ? std::atoi(std::getenv("MI355_DEBLOCK_RESIDENT")) : 0;
     return pin;
 }
 int device_cus()
@@ -1231,7 +1255,25 @@ mi355_h264_deblock_plan_info deblock_plan(int nframes, int max_mb_width, int max
     return p;
 }
 
-int deblock_launch(const mi355_h264_frame *d_frames, int nframes, int nbands, const mi355_h264_deblock_plan_info &p, hipStream_t st)
+/* How many waves a launch of k_deblock_tiled gets (each takes bands in turn until none is left), for a device of `simds` SIMDs, a
+ * launch of `tickets` bands and a caller that runs the batch as `shares` shares side by side: never more than a wave per band.
+ * DEBLOCK_RESIDENT_HALVES: the count per launch in half waves per SIMD when other shares' launches run beside it; 0: a wave per band.
+ * profiles/r09_experiments.md has the sweep it comes from (2048 1080p pictures as three shares on 256 CUs; ms per step against 11.44 with
+ * a wave per band: 1/2 wave per SIMD and launch 15.0, 1 11.6, 1 1/2 11.2, 2 11.4, 4 11.6 — too few and the loop filter is the longest chain
+ * of the step, too many and its waves keep the reconstruction's registers and LDS).  Measured with three shares only.
+ * A launch with nothing beside it (shares = 1) is a wave per band: the kernel alone runs at the vector pipe's issue rate with every
+ * slot taken.  MI355_DEBLOCK_RESIDENT (developer switch) pins the count per launch. */
+constexpr int DEBLOCK_RESIDENT_HALVES = 3;
+long long deblock_resident_rule(long long simds, long long tickets, int shares)
+{
+    long long n = tickets;
+    if (shares > 1 && DEBLOCK_RESIDENT_HALVES > 0) n = (simds * DEBLOCK_RESIDENT_HALVES + 1) / 2;
+    if (deblock_resident_pin() > 0) n = deblock_resident_pin();
+    return n < 1 ? 1 : (n < tickets ? n : tickets);
+}
+
+/* resident: the waves of the one-wave tiled launch (0 or at least a wave per band: a wave per band) */
+int deblock_launch(const mi355_h264_frame *d_frames, int nframes, int nbands, const mi355_h264_deblock_plan_info &p, hipStream_t st, long long resident = 0)
 {
     if (p.tiled_waves) {
         if ((long long)nframes * nbands > 0x7FFFFFFFLL) return -3;
@@ -1240,7 +1282,11 @@ int deblock_launch(const mi355_h264_frame *d_frames, int nframes, int nbands, co
         if (!sync) return -4;
         MI355_TRY(hipMemsetAsync(sync, 0, words * sizeof(uint32_t), st), -4);
         if (p.tiled_waves == 2) hipLaunchKernelGGL(k_deblock_tiled2, dim3((unsigned)(nframes * nbands)), dim3(128), 0, st, d_frames, nframes, nbands, sync);
-        else hipLaunchKernelGGL(k_deblock_tiled, dim3((unsigned)(nframes * nbands)), dim3(64), 0, st, d_frames, nframes, nbands, sync);
+        else {
+            const long long tickets = (long long)nframes * nbands;
+            const bool turns = resident > 0 && resident < tickets;
+            hipLaunchKernelGGL(k_deblock_tiled, dim3((unsigned)(turns ? resident : tickets)), dim3(64), 0, st, d_frames, nframes, nbands, sync, turns ? 1 : 0);
+        }
     }
     for (int band = 0; p.linear_bands && band < nbands; band += p.linear_bands) {
         const dim3 grid((unsigned)nframes);
@@ -1274,6 +1320,30 @@ extern "C" int mi355_h264_deblock_layouts_dev(const mi355_h264_frame *d_frames, 
     const int nbands = deblock_args(d_frames, nframes, max_mb_width, max_mb_height, layouts);
     if (!nbands) return -1;
     return deblock_launch(d_frames, nframes, nbands, deblock_plan(nframes, max_mb_width, max_mb_height, layouts, device_cus()), (hipStream_t)stream);
+}
+
+extern "C" int mi355_h264_deblock_resident_dev(const mi355_h264_frame *d_frames, int nframes, int max_mb_width, int max_mb_height, int layouts, int resident_waves, void *stream)
+{
+    const int nbands = deblock_args(d_frames, nframes, max_mb_width, max_mb_height, layouts);
+    if (!nbands || resident_waves < 0) return -1;
+    mi355_h264_deblock_plan_info p = deblock_plan(nframes, max_mb_width, max_mb_height, layouts, device_cus());
+    /* a count names waves of k_deblock_tiled: the tiled pictures go through it also where the rule would take the two-wave form */
+    if (resident_waves && p.tiled_waves == 2) p.tiled_waves = 1;
+    const long long resident = resident_waves ? resident_waves : deblock_resident_rule(4LL * device_cus(), (long long)nframes * nbands, 2);
+    return deblock_launch(d_frames, nframes, nbands, p, (hipStream_t)stream, resident);
+}
+
+extern "C" int mi355_h264_deblock_resident(int nframes, int max_mb_width, int max_mb_height, int layouts, int cus, int shares, int *resident_waves)
+{
+    if (!resident_waves || nframes <= 0 || max_mb_width <= 0 || max_mb_height <= 0 || cus < 0 || shares < 1 || !(layouts & (MI355_LAYOUTS_LINEAR | MI355_LAYOUTS_TILED))) return -1;
+    if (cus == 0) {
+        if (!mi355::bind()) return -1;
+        cus = device_cus();
+    }
+    const long long tickets = (long long)nframes * ((max_mb_height + 3) / 4);
+    if (tickets > 0x7FFFFFFFLL) return -1;
+    *resident_waves = deblock_plan(nframes, max_mb_width, max_mb_height, layouts, cus).tiled_waves == 1 ? (int)deblock_resident_rule(4LL * cus, tickets, shares) : 0;
+    return 0;
 }
 
 extern "C" int mi355_h264_deblock_plan(int nframes, int max_mb_width, int max_mb_height, int layouts, int cus, mi355_h264_deblock_plan_info *plan)

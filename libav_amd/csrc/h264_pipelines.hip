@@ -137,7 +137,11 @@ extern "C" int mi355_h264_pipelines_decode_dev(mi355_h264_pipelines *p, const mi
         rc = mi355_h264_recon_intra_all_dev(d, count, max_mb_width, max_mb_height, max_intra_level, level_widths, st);
         if (rc) return fail(rc);
         if ((rc = stamp(st))) return fail(rc);
-        rc = mi355_h264_deblock_layouts_dev(d, count, max_mb_width, max_mb_height, layouts, st);
+        /* the loop filter runs beside the other shares' reconstructions: as many resident waves as the rule gives a launch among `shares` (0: no one-wave tiled launch) */
+        int resident = 0;
+        if (mi355_h264_deblock_resident(count, max_mb_width, max_mb_height, layouts, 0, p->shares, &resident)) return fail(-1);
+        rc = resident ? mi355_h264_deblock_resident_dev(d, count, max_mb_width, max_mb_height, layouts, resident, st)
+                      : mi355_h264_deblock_layouts_dev(d, count, max_mb_width, max_mb_height, layouts, st);
         if (rc) return fail(rc);
         if ((rc = stamp(st))) return fail(rc);
         PIPE_TRY(hipEventRecord(p->done[(size_t)i], st));
