@@ -116,6 +116,14 @@
  *                          converters go to mi355_sws_p010ToY / _p010ToUV, the horizontal loops to mi355_sws_hscale16to15.  Declined: p010be,
  *                          SWS_FULL_CHR_H_INT, a chroma line drop, YUVA destinations (SWS_FAST_BILINEAR leaves a 16-bit source on hScale16To15_c with
  *                          bilinear banks: taken).  The ten describers above keep declining it.
+ *   SWS_FAST_BILINEAR      contexts of the planar 8-bit sources (c->hyscale_fast / c->hcscale_fast = hyscale_fast_c / hcscale_fast_c in place of hyScale /
+ *                          hcScale: no filter bank, every position and weight from c->lumXInc / c->chrXInc) have the twelfth describer,
+ *                          mi355_sws_describe_fast(), for mi355_sws_create_fast_bilinear(): a context is taken when both functions are the C ones
+ *                          (fast_probe) and one of the describers above takes it without them (the context is only read).  Bound like a 32-bit source —
+ *                          asked before every other describer, since mi355_sws_describe() looks at the formats alone — the two
+ *                          increments kept in the slot.  With MI355_SWS_LINES=1 the two functions go to mi355_sws_hyscale_fast / _hcscale_fast, the
+ *                          other loops as for the same context without them.  Declined: the flag from any other source (the reference's conversion
+ *                          buffer holds an uninitialised sample behind the width there), the x86 build's MMXEXT scaler.
  * The device is MI355_DEVICE (default 0), as for the decoder bridges.
  */
 #include <pthread.h>
@@ -240,6 +248,9 @@ static int source_of(const SwsContext *c, mi355_sws_src *s)
  * (a YUV destination) */
 #define MI355_ASK_YUY2DST 4
 static int generic_dst_r(const SwsContext *c, int ranged);
+/* set by mi355_sws_describe_fast (this thread, for the length of its call): generic_dst_r() then looks past the two fast functions, so that the
+ * describers below answer for a fast-bilinear context what they answer for the same context without them — the context itself is not written to */
+static __thread int describing_fast;
 /* the MI355_SWS_DST_* of a packed 4:2:2 destination, 0 for any other format */
 static int yuy2_dst_of(const SwsContext *c)
 {
@@ -294,7 +305,7 @@ static int generic_dst_r(const SwsContext *c, int ranged)
     /* the generic scaler: no fast bilinear, no range conversion (unless asked for), no chroma line drop, and its four banks (an unscaled
      * converter or a plane copy has none, utils.c:1043-1048) */
     const int deep = ranged == MI355_ASK_DEEP, packed = ranged == MI355_ASK_PACKED;
-    if (c->hyscale_fast || c->hcscale_fast || ((!ranged || deep || packed) && (c->lumConvertRange || c->chrConvertRange)) || c->vChrDrop) return -1;
+    if ((!describing_fast && (c->hyscale_fast || c->hcscale_fast)) || ((!ranged || deep || packed) && (c->lumConvertRange || c->chrConvertRange)) || c->vChrDrop) return -1;
     if (!c->vLumFilter || !c->vChrFilter || !c->hLumFilter || !c->hChrFilter) return -1;
     if (packed) return packed_dst_of(c) && !isALPHA(c->srcFormat) ? packed_dst_of(c) : -1;
     if (ranged == MI355_ASK_YUY2DST) return yuy2_dst_of(c) && !isALPHA(c->srcFormat) ? yuy2_dst_of(c) : -1;
@@ -790,6 +801,51 @@ int mi355_sws_describe_p010(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_s
     return 0;
 }
 
+/* ---- SWS_FAST_BILINEAR contexts of the planar 8-bit sources ------------------------------------------------------------------------------------
+ * the two fast functions the context HOLDS are the C ones, hyscale_fast_c / hcscale_fast_c (static in the reference: three samples through each at an
+ * increment with a fraction, as range_probe does — six samples on the host, nothing on the device; the x86 build's generated code is not called:
+ * canMMXEXTBeUsed is declined before).  A context whose two functions are this file's own shims (ff_sws_init_mi355x set them for a context that passed
+ * this probe) is taken without calling them: no line goes to the device and no call is counted for a question */
+#ifndef MI355_SWS_DESCRIBE_ONLY
+static void t1_hyscale_fast(SwsContext *c, int16_t *dst, int dstWidth, const uint8_t *src, int srcW, int xInc);
+static void t1_hcscale_fast(SwsContext *c, int16_t *dst1, int16_t *dst2, int dstWidth, const uint8_t *src1, const uint8_t *src2, int srcW, int xInc);
+#endif
+static int fast_probe(const SwsContext *c)
+{
+    static const uint8_t b[4] = { 10, 200, 77, 0 };
+    int16_t y[3] = { 0 }, u[3] = { 0 }, v[3] = { 0 };
+    if (!c->hyscale_fast || !c->hcscale_fast || c->canMMXEXTBeUsed) return -1;
+#ifndef MI355_SWS_DESCRIBE_ONLY
+    if (c->hyscale_fast == t1_hyscale_fast && c->hcscale_fast == t1_hcscale_fast) return 0;
+#endif
+    /* (the reference's prototypes take a writable context; the two C functions do not look at it) */
+    c->hyscale_fast((SwsContext *)c, y, 3, b, 3, 40000);       /* xx, a: 0, 0 / 0, 78 / 1, 28 */
+    c->hcscale_fast((SwsContext *)c, u, v, 3, b, b, 3, 40000);
+    return y[0] == 1280 && y[1] == 16100 && y[2] == 22156 && u[0] == 1270 && u[1] == 16090 && u[2] == 21956 && v[0] == 1270 && v[1] == 16090 && v[2] == 21956 ? 0 : -1;
+}
+/* what mi355_sws_create_fast_bilinear takes for a live context (0), -1 for every other context — the eleven describers above keep declining these.  A
+ * context is taken exactly when both fast functions are the C ones (fast_probe) AND one of those describers would take it without the two functions
+ * (describing_fast: asked of generic_dst_r, the one place their chain looks at the two fields; the context is read only) — as a source of layout 0
+ * and 8 bits in the generic scaler.  The descriptor is that describer's (the horizontal banks the reference built all the same travel with it; the
+ * device does not read them); lumXInc / chrXInc are the context's fields as its init left them.  Declined: every source but 8-bit yuv420p / yuv422p /
+ * yuv444p (the reference runs the fast pass of the others on its conversion buffer, whose sample behind the width is uninitialised),
+ * SWS_FULL_CHR_H_INT, YUVA, a chroma line drop, the x86 build's MMXEXT scaler */
+int mi355_sws_describe_fast(const struct SwsContext *cc, mi355_sws_desc *d, mi355_sws_src *s, int *dst_format, int *range, int *dst_depth, int *lumXInc, int *chrXInc)
+{
+    struct SwsContext *c = (struct SwsContext *)cc;          /* (the describers' parameter type; none of them writes to a context) */
+    int layout = -1, rc;
+    if (fast_probe(cc) != 0 || cc->lumXInc <= 0 || cc->chrXInc <= 0) return -1;
+    *range = MI355_SWS_RANGE_NONE; *dst_depth = 8;
+    describing_fast = 1;
+    if (yuy2_dst_of(c)) rc = mi355_sws_describe_yuy2dst(c, d, s, &layout, dst_format, range, dst_depth);
+    else if (packed_dst_of(c)) rc = mi355_sws_describe_packed(c, d, s, &layout, dst_format);
+    else rc = mi355_sws_describe_depth(c, d, s, &layout, dst_format, range, dst_depth);
+    describing_fast = 0;
+    if (rc != 0 || layout != MI355_SWS_SRC_PLANAR || s->depth != 8 || d->unscaled_special) return -1;
+    *lumXInc = cc->lumXInc; *chrXInc = cc->chrXInc;
+    return 0;
+}
+
 #ifndef MI355_SWS_DESCRIBE_ONLY
 static void t1_hscale16(SwsContext *c, int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
 {
@@ -1116,7 +1172,30 @@ static int init_p010(SwsContext *c)
     return 1;
 }
 
+/* ... of a fast-bilinear context (hyscale_fast_c / hcscale_fast_c): the two lines of a chroma pair go through one entry */
+static void t1_hyscale_fast(SwsContext *c, int16_t *dst, int dstWidth, const uint8_t *src, int srcW, int xInc)
+{ (void)c; n_calls++; mi355_sws_hyscale_fast(dst, dstWidth, src, srcW, xInc); }
+static void t1_hcscale_fast(SwsContext *c, int16_t *dst1, int16_t *dst2, int dstWidth, const uint8_t *src1, const uint8_t *src2, int srcW, int xInc)
+{ (void)c; n_calls++; mi355_sws_hcscale_fast(dst1, dst2, dstWidth, src1, src2, srcW, xInc); }
+
+static void init_loops(SwsContext *c);
 void ff_sws_init_mi355x(SwsContext *c)
+{
+    if (c->hyscale_fast || c->hcscale_fast) {
+        /* a fast-bilinear context mi355_sws_describe_fast takes: the other loops as for the same context without the two fast functions (the range
+         * converters, the vertical loops), then the two fast functions themselves; any other context with them stays the reference's */
+        mi355_sws_desc d;
+        mi355_sws_src s;
+        int fmt, range, depth, li, ci;
+        if (mi355_sws_describe_fast(c, &d, &s, &fmt, &range, &depth, &li, &ci) != 0 || !device_ready()) return;
+        c->hyscale_fast = NULL; c->hcscale_fast = NULL;
+        init_loops(c);
+        c->hyscale_fast = t1_hyscale_fast; c->hcscale_fast = t1_hcscale_fast;
+        return;
+    }
+    init_loops(c);
+}
+static void init_loops(SwsContext *c)
 {
     mi355_sws_src s;
     int layout;
@@ -1189,7 +1268,10 @@ typedef struct Bound {
     int rgb32;                    /* 1: a 32-bit source (mi355_sws_describe_rgb32: layout, planar / packed, range and depth above are what it gave) ...;
                                    * 2: a packed 4:2:2 source in the generic scaler (mi355_sws_describe_yuy2, the same fields; never alpha);
                                    * 3: a packed 4:2:2 DESTINATION from any source (mi355_sws_describe_yuy2dst, the same fields; packed is its format, no tables);
-                                   * 4: a p010le source to any destination (mi355_sws_describe_p010, the same fields; TWO source planes; never alpha) */
+                                   * 4: a p010le source to any destination (mi355_sws_describe_p010, the same fields; TWO source planes; never alpha);
+                                   * 5: a fast-bilinear context of a planar 8-bit source (mi355_sws_describe_fast, the same fields and the two increments below;
+                                   *    built by mi355_sws_create_fast_bilinear) */
+    int lumXInc, chrXInc;         /* ... the increments it was bound with */
     int alpha;                    /* ... whose alpha goes to the 32-bit destination (mi355_sws_create_src_layout_alpha) */
     mi355_sws_ctx *dev;
     int failed;                   /* the device side does not take this context: the reference's function from now on */
@@ -1238,7 +1320,18 @@ static Bound *bound_find(SwsContext *c, int create)
 static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
 {
     int planar = special ? 0 : planar_format(c), other = 0, layout = MI355_SWS_SRC_PLANAR, range = MI355_SWS_RANGE_NONE, depth = 8, packed = 0;
-    int rgb32 = 0, alpha = 0;
+    int rgb32 = 0, alpha = 0, lum_inc = 0, chr_inc = 0;
+    if (!special && (c->hyscale_fast || c->hcscale_fast)) {
+        /* a fast-bilinear context: asked FIRST, before every branch below, and built through its own creator.  The ten describers behind those branches
+         * decline such a context anyway, but taken() — mi355_sws_describe's test — looks at the two formats alone and would hand yuv420p -> rgb24 to the
+         * bank-driven kernels; a context the new describer declines stays the reference's */
+        mi355_sws_desc d;
+        mi355_sws_src s;
+        int fmt;
+        if (mi355_sws_describe_fast(c, &d, &s, &fmt, &range, &depth, &lum_inc, &chr_inc) != 0) return real;
+        rgb32 = 5; other = 1; planar = 0;
+        if (fmt >= MI355_SWS_DST_BGR24) packed = fmt; else planar = fmt;
+    } else
     if (!special && c->srcFormat == AV_PIX_FMT_P010LE) {
         /* a p010le source: one describer for every destination it goes to, the packed 4:2:2 ones included (every such context is the generic scaler's) */
         mi355_sws_desc d;
@@ -1303,7 +1396,7 @@ static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
     if (b) {
         slot_release(b);
         b->c = c; b->real = real; b->special = special; b->planar = planar; b->other = other; b->layout = layout; b->range = range; b->depth = depth;
-        b->packed = packed; b->rgb32 = rgb32; b->alpha = alpha;
+        b->packed = packed; b->rgb32 = rgb32; b->alpha = alpha; b->lumXInc = lum_inc; b->chrXInc = chr_inc;
         b->stamp = ++n_stamp;
     }
     pthread_mutex_unlock(&bound_mu);
@@ -1329,8 +1422,9 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
      * likewise, through its own describer */
     mi355_sws_desc d32;
     mi355_sws_src s32;
-    int l32 = 0, f32 = 0, r32 = 0, dp32 = 8, a32 = 0;
-    const int rgb32_ok = b && b->rgb32 && (b->rgb32 == 4 ? mi355_sws_describe_p010(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 :
+    int l32 = 0, f32 = 0, r32 = 0, dp32 = 8, a32 = 0, li32 = 0, ci32 = 0;
+    const int rgb32_ok = b && b->rgb32 && (b->rgb32 == 5 ? mi355_sws_describe_fast(c, &d32, &s32, &f32, &r32, &dp32, &li32, &ci32) == 0 && li32 == b->lumXInc && ci32 == b->chrXInc :
+                                           b->rgb32 == 4 ? mi355_sws_describe_p010(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 :
                                            b->rgb32 == 3 ? mi355_sws_describe_yuy2dst(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 && !d32.unscaled_special :
                                            b->rgb32 == 2 ? mi355_sws_describe_yuy2(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 && !d32.unscaled_special
                                                          : mi355_sws_describe_rgb32(c, &d32, &s32, &l32, &f32, &r32, &dp32, &a32) == 0) && l32 == b->layout &&
@@ -1359,7 +1453,8 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
             int fmt;
             if (b->rgb32) {
                 if (device_ready() && rgb32_ok) {
-                    b->dev = a32 ? mi355_sws_create_src_layout_alpha(&d32, &s32, l32, f32, 1) : mi355_sws_create_src_layout_range_depth(&d32, &s32, l32, f32, r32, dp32);
+                    b->dev = b->rgb32 == 5 ? mi355_sws_create_fast_bilinear(&d32, &s32, f32, r32, dp32, li32, ci32) :
+                             a32 ? mi355_sws_create_src_layout_alpha(&d32, &s32, l32, f32, 1) : mi355_sws_create_src_layout_range_depth(&d32, &s32, l32, f32, r32, dp32);
                     d = d32;
                 }
             } else

@@ -14,7 +14,9 @@
  * swscale_unscaled.c:227-287); and TO packed 4:2:2 yuyv422 / uyvy422 / yvyu422 (yuv2422_X / _2 / _1_c_template output.c:451-582), from every source
  * rgb24 is written from, with range conversion, and the reference's four unscaled packers yuv422p / yuv420p -> yuyv422 / uyvy422
  * (yuv422pToYuy2Wrapper, yuv422pToUyvyWrapper, planarToYuy2Wrapper, planarToUyvyWrapper swscale_unscaled.c:179-225); and from p010le sources
- * (p010LEToY_c / p010LEToUV_c input.c:499-524 in front of hScale16To15_c, depth 10) to every destination the yuv420p10le source takes.
+ * (p010LEToY_c / p010LEToUV_c input.c:499-524 in front of hScale16To15_c, depth 10) to every destination the yuv420p10le source takes; and
+ * SWS_FAST_BILINEAR contexts of the planar 8-bit sources (hyscale_fast_c / hcscale_fast_c swscale.c:238-301 in place of hyScale / hcScale:
+ * mi355_sws_create_fast_bilinear) to every destination those sources take.
  *
  * The reference keeps these behind function pointers of the (private) SwsContext
  * (libswscale/swscale_internal.h:253-540): hyScale/hcScale :526-531, yuv2plane1/yuv2planeX/
@@ -414,8 +416,45 @@ enum { MI355_SWS_DST_BGR24 = 32, MI355_SWS_DST_RGBA = 33, MI355_SWS_DST_BGRA = 3
  * A plane on 16-byte multiples is fetched in aligned 16-byte pieces over its stride, as everywhere else.
  * A packed 4:2:2 source to ANOTHER packed 4:2:2 order at equal size is a context of the reference's scaler (banks of one tap each: it has no converter
  * between the orders) and has its twin's plan, MI355_SWS_K_IDENT1_1 straight from the packed bytes; to the SAME order the reference copies.
- * Not taken (the reference's): 9 / 10 / 16-bit packed YUV (y210 and kin), a YUVA source's alpha, SWS_FAST_BILINEAR scaled contexts and the plain copy. */
+ * Not taken (the reference's): 9 / 10 / 16-bit packed YUV (y210 and kin), a YUVA source's alpha, SWS_FAST_BILINEAR scaled contexts of any source but the
+ * planar 8-bit ones (those: mi355_sws_create_fast_bilinear below) and the plain copy. */
 enum { MI355_SWS_DST_YUYV422 = 48, MI355_SWS_DST_UYVY422 = 49, MI355_SWS_DST_YVYU422 = 50 };
+
+/* ---- SWS_FAST_BILINEAR contexts: the reference's cheap scaler (c->hyscale_fast / c->hcscale_fast = hyscale_fast_c / hcscale_fast_c, swscale.c:238-249,
+ * :288-301, chosen at :733-739 when srcBpc == 8, dstBpc <= 15 and the flag is set) ----
+ * Its horizontal pass reads NO filter bank: output sample i of a plane is
+ *   xpos = i * xInc (unsigned 32 bit);  xx = xpos >> 16;  a = (xpos & 0xFFFF) >> 9          (0 .. 127)
+ *   luma    (src[xx] << 7) + (src[xx + 1] - src[xx]) * a
+ *   chroma   src[xx] * (a ^ 127) + src[xx + 1] * a                                           (the weights sum to 127, not 128)
+ * with xInc = c->lumXInc for luma and c->chrXInc for chroma AS THE REFERENCE'S INIT LEFT THEM (utils.c:968, :1081-1101: a plain-C build has
+ * ((srcW << 16) + (dstW >> 1)) / dstW, other builds alter it by +-20): the binding hands both over unchanged, nothing here recomputes them.  At equal
+ * width (xInc 65536) luma is src << 7 but chroma src * 127: such a context is never MI355_SWS_K_IDENT1_*.  The range converters and the vertical pass
+ * follow on the int16 lines as in every other context; the vertical banks are the reference's ordinary ones.
+ * Source: layout 0 (three planes) with src->depth == 8 at 4:2:0, 4:2:2 or 4:4:4, no alpha — the creator has no layout and no alpha argument, so
+ * mi355_sws_source_layout is 0 and mi355_sws_alpha 0 for every such context.  NV12 / NV21, packed RGB, packed 4:2:2 and P010 sources stay the
+ * reference's: it runs the fast pass on its conversion buffer for those, and the sample behind the width is then uninitialised heap memory that no
+ * device code can reproduce.  Deeper sources never take the fast pass in the reference (srcBpc == 8 only).
+ * Descriptor: the reference's for that context.  vLum / vChr are its vertical banks (vChr.n = dstH for a one-plane destination, chrDstH otherwise, as for
+ * the twin); hLum / hChr are NOT read and may be empty (coef / pos NULL).
+ * Twin rule: the twin is the bank-driven context of mi355_sws_create_src_layout_range_depth(desc, src, 0, dst_format, range, dst_depth).  A
+ * fast-bilinear context takes every dst_format, range and dst_depth the twin takes (0 and 32 .. 36, 48 .. 50, the three planar formats at 8 / 9 / 10 bits,
+ * NV12 / NV21, range 1 / 2 to the 8-bit YUV destinations) and has the twin's plan by lum_lines / chr_lines (MI355_SWS_K_GENERIC_A .. C / _PLANAR_A ..
+ * C), th, narrow report and vertical refusals; hstage is always 1; it is never IDENT1_*, C24 or a packer.  Frames are mi355_sws_frame /
+ * mi355_sws_planar_frame through the four scale entry points, and mi355_sws_destination / _range / _dest_depth / _source report the twin's values
+ * (hstaged: a tile's span fits a staged line).
+ * NULL and a message for: src->depth other than 8; desc->unscaled_special; an increment <= 0; a plane whose last column has
+ * ((n - 1) * xInc) >> 16 > w - 1 (n its output width, w its source width: an extreme upscale, n * n above roughly w << 17, where the reference reads
+ * two or more samples behind the line); (n - 1) * xInc not fitting 32 bits; a dst_format, range or dst_depth the twin refuses; vertical banks the
+ * twin's tiles cannot hold.
+ * Read extent, in bytes as in the paragraph above mi355_sws_frame: the reference has no tail fix-up — a column with xx == w - 1 reads src[w], the byte
+ * BEHIND the line as it lies in the caller's plane (padding, the next line's first byte, or the byte behind the plane), and with a != 0 that byte is
+ * part of the result.  So the caller keeps ONE byte behind srcW of every luma line and behind chrSrcW of every chroma line readable, the last line
+ * included, and the device reads it — never more, and only on a line of a plane whose last column has xx == w - 1.  The Tier-1 host entry points copy
+ * that byte of every line along.  A plane whose pointer and stride are multiples of 16 is fetched in aligned 16-byte pieces over its stride, as
+ * everywhere else; one on 4-byte multiples in dwords that lie whole inside the bytes the reference reads; any other byte by byte. */
+mi355_sws_ctx *mi355_sws_create_fast_bilinear(const mi355_sws_desc *desc, const mi355_sws_src *src, int dst_format, int range, int dst_depth,
+                                              int lumXInc, int chrXInc);
+int mi355_sws_fast_bilinear(const mi355_sws_ctx *ctx, int *lumXInc, int *chrXInc);   /* 1 / 0 (the increments: 0 then), -1 bad argument; either pointer may be NULL */
 
 /* ---- the individual inner loops (Tier 1, host pointers), argument lists of the reference's
  * function-pointer types minus the SwsContext ------------------------------------------------ */
@@ -445,6 +484,11 @@ void mi355_sws_yuy2ToUV(uint8_t *dstU, uint8_t *dstV, const uint8_t *src, int wi
  * address */
 void mi355_sws_p010ToY(uint16_t *dst, const uint8_t *src, int width);
 void mi355_sws_p010ToUV(uint16_t *dstU, uint16_t *dstV, const uint8_t *src, int width);
+/* hyscale_fast_c / hcscale_fast_c swscale.c:238-249, :288-301 (c->hyscale_fast / c->hcscale_fast): `dstWidth` int16 samples of each plane by the two
+ * formulas above mi355_sws_create_fast_bilinear.  Like the reference's loops they read ((dstWidth - 1) * xInc >> 16) + 2 bytes of each source line,
+ * whatever srcW says (srcW is not looked at); nothing is done for dstWidth <= 0, xInc <= 0 or a last position that does not fit 32 bits */
+void mi355_sws_hyscale_fast(int16_t *dst, int dstWidth, const uint8_t *src, int srcW, int xInc);
+void mi355_sws_hcscale_fast(int16_t *dst1, int16_t *dst2, int dstWidth, const uint8_t *src1, const uint8_t *src2, int srcW, int xInc);
 /* lumRangeFromJpeg_c / lumRangeToJpeg_c and chrRangeFromJpeg_c / chrRangeToJpeg_c swscale.c:168-198 (c->lumConvertRange / c->chrConvertRange):
  * `width` int16 samples converted in place, any int16 value (a result outside int16 is stored truncated, as the reference stores it) */
 void mi355_sws_lumConvertRange(int16_t *dst, int width, int to_jpeg);

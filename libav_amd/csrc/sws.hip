@@ -13,14 +13,16 @@
  * sources wherever rgb24 is written, also with range conversion, with the unscaled yuv422p / yuv420p -> yuyv422 / uyvy422 packer (yuv2422_X / _2 / _1_c_template
  * output.c:451-582; their DST_YUY2 instances and k_sws_yuy2_pack are sws_yuy2dst.hip's); and p010le SOURCES (MI355_SWS_SRC_P010: a plane of 16-bit words and a
  * plane of word pairs, the sample word >> 6 — p010LEToY_c / p010LEToUV_c input.c:499-524) to every destination the yuv420p10le source takes (their tile
- * instances, line kernels and the line entries mi355_sws_p010ToY / _p010ToUV are sws_p010.hip's).  This file:
+ * instances, line kernels and the line entries mi355_sws_p010ToY / _p010ToUV are sws_p010.hip's); and SWS_FAST_BILINEAR contexts of the planar 8-bit
+ * sources (mi355_sws_create_fast_bilinear: hyscale_fast_c / hcscale_fast_c swscale.c:238-301 in place of the bank-driven horizontal pass; the tile kernels
+ * k_sws_fbl_generic / k_sws_fbl_planar and the line entries mi355_sws_hyscale_fast / _hcscale_fast are sws_fastbl.hip's).  This file:
  * the context, the plan (which kernel a context gets) and the entry points of include/mi355_sws.h.  The device side is sws_dev.h:
  * k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1, k_sws_nv12_pack, k_sws_nv12_split and the k_sws_line_* kernels of the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
  * Launches: sws_key() names a context's instance once (sws_dev.h: SwsKey), sws_run() hands the key to the file that compiles that instance — here
  * the plain and RANGE instances of k_sws_planar and the rgb24 destination of k_sws_generic / k_sws_ident1 / k_sws_c24 for the four classic source
  * classes; sws_deep.hip, sws_packed.hip, sws_rgb32.hip, sws_yuy2.hip, sws_yuy2dst.hip and sws_p010.hip hold the rest, one launch function each — and every file maps the key to its
- * instance through the one dispatcher sws_launch() of sws_dev.h.
+ * instance through the one dispatcher sws_launch() of sws_dev.h.  A fast-bilinear context has its twin's key and goes to sws_fastbl.hip with it.
  */
 #include "mi355_rt.h"
 #include "sws_dev.h"
@@ -42,6 +44,9 @@ struct mi355_sws_ctx {
     int device = -1;            /* the device of the thread that created the context: its entry points switch to it */
     int alpha = 0;              /* a 32-bit source's alpha goes to the 32-bit destination (mi355_sws_create_src_layout_alpha): the ALPHA instances */
     int hfit = 0;               /* a plane with a horizontal filter other than the identity has a tile whose source span fits a staged line (ctx_hfit) */
+    /* a SWS_FAST_BILINEAR context (mi355_sws_create_fast_bilinear): the horizontal pass reads no bank — the reference's two 16.16 increments, as its init
+     * left them; the tile kernels are sws_fastbl.hip's k_sws_fbl_generic / k_sws_fbl_planar under the twin's key */
+    int fast_bilinear = 0, lumXInc = 0, chrXInc = 0;
 };
 
 template <typename T> static const T *upload_bank(mi355_sws_ctx *c, int slot, const T *host, size_t n)
@@ -487,6 +492,81 @@ extern "C" mi355_sws_ctx *mi355_sws_create_src_layout_range_depth(const mi355_sw
 }
 extern "C" int mi355_sws_dest_depth(const mi355_sws_ctx *c) { return c ? c->h.dst_bits : -1; }
 
+/* ---- SWS_FAST_BILINEAR contexts: the reference's hyscale_fast_c / hcscale_fast_c in place of the bank-driven horizontal pass ---------------------
+ * The context of the planar 8-bit source (layout 0, no alpha: the creator has neither argument) whose horizontal pass is the bank-free one of
+ * sws_dev.h.  Everything else is the twin's — the bank-driven context of the same descriptor, source and destination: it is created as that twin
+ * (ctx_create through the layered creators: the destination, range and depth checks, the vertical banks against the tiles, the plan) with a
+ * one-tap stand-in for the two horizontal banks, which the fast pass never reads, and then marked.  Never IDENT1_* (no bank is an identity),
+ * never C24 or a packer (unscaled_special is refused). */
+extern "C" mi355_sws_ctx *mi355_sws_create_fast_bilinear(const mi355_sws_desc *desc, const mi355_sws_src *src, int dst_format, int range, int dst_depth,
+                                                         int lumXInc, int chrXInc)
+{
+    const char *const who = "mi355_sws_create_fast_bilinear";
+    if (!creator_args(who, desc, src)) return nullptr;
+    if (src->depth != 8) {
+        std::fprintf(stderr, "mi355dsp: %s: the reference runs its fast bilinear pass on 8-bit sources only (%d bit)\n", who, src->depth);
+        return nullptr;
+    }
+    if (desc->unscaled_special) {
+        std::fprintf(stderr, "mi355dsp: %s: an unscaled special converter has no horizontal pass\n", who);
+        return nullptr;
+    }
+    if (lumXInc <= 0 || chrXInc <= 0) {
+        std::fprintf(stderr, "mi355dsp: %s: increments %d / %d are not positive\n", who, lumXInc, chrXInc);
+        return nullptr;
+    }
+    /* the last column of a plane: its position fits the reference's unsigned 32-bit xpos, and it reads no further than sample w (one behind the line) */
+    auto plane_ok = [&](const char *name, int n, int w, int inc) {
+        if (n < 1 || w < 1) { std::fprintf(stderr, "mi355dsp: %s: %s plane of %d -> %d samples\n", who, name, w, n); return false; }
+        const uint64_t last = (uint64_t)(n - 1) * (uint64_t)inc;
+        if (last > 0xFFFFFFFFull) {
+            std::fprintf(stderr, "mi355dsp: %s: %s position (%d - 1) * %d does not fit 32 bits\n", who, name, n, inc);
+            return false;
+        }
+        if ((last >> 16) > (uint64_t)(w - 1)) {
+            std::fprintf(stderr, "mi355dsp: %s: the last %s column reads sample %llu of %d: more than one behind the line\n", who, name, (unsigned long long)(last >> 16) + 1, w);
+            return false;
+        }
+        return true;
+    };
+    if (!plane_ok("luma", desc->dstW, desc->srcW, lumXInc) || !plane_ok("chroma", desc->chrDstW, desc->chrSrcW, chrXInc)) return nullptr;
+    /* the twin, with stand-ins for hLum / hChr (one tap of 0 at position 0: no identity, monotonic, inside the line).  ctx_create uploads them like any
+     * bank: dstW + chrDstW zero taps and positions stay on the device for the life of the context (SwsDev's hLumC / hLumP / hChrC / hChrP point at
+     * them) and no kernel of this context reads them */
+    const int nmax = desc->dstW > desc->chrDstW ? desc->dstW : desc->chrDstW;
+    int16_t *coef = new int16_t[nmax]();
+    int32_t *pos = new int32_t[nmax]();
+    mi355_sws_desc twin = *desc;
+    twin.hLum = mi355_sws_filter{ coef, pos, 1, desc->dstW };
+    twin.hChr = mi355_sws_filter{ coef, pos, 1, desc->chrDstW };
+    mi355_sws_ctx *c = mi355_sws_create_src_layout_range_depth(&twin, src, MI355_SWS_SRC_PLANAR, dst_format, range, dst_depth);
+    delete[] coef;
+    delete[] pos;
+    if (!c) {
+        std::fprintf(stderr, "mi355dsp: %s: the bank-driven context of this descriptor is refused (above)\n", who);
+        return nullptr;
+    }
+    c->fast_bilinear = 1; c->lumXInc = lumXInc; c->chrXInc = chrXInc;
+    /* a tile's span [xx(first), xx(last) + 1] fits a staged line (hscale_tile_fbl) */
+    const SwsDev &h = c->h;
+    auto fits = [](int n, uint32_t inc, int cols) {
+        for (int g = 0; g < n; g += cols) {
+            const int last = (g + cols < n ? g + cols : n) - 1, s0 = (int)(((uint32_t)g * inc) >> 16), s1 = (int)(((uint32_t)last * inc) >> 16) + 2;
+            if (span_fits(span_dwords(s0 & ~15, s1), s0, s1, stage_pitch(cols, 1))) return true;
+        }
+        return false;
+    };
+    c->hfit = fits(h.dstW, (uint32_t)lumXInc, TW) || fits(h.chrDstW, (uint32_t)chrXInc, h.planar ? TW >> h.hshift : TW / 2);
+    return c;
+}
+extern "C" int mi355_sws_fast_bilinear(const mi355_sws_ctx *c, int *lumXInc, int *chrXInc)
+{
+    if (!c) return -1;
+    if (lumXInc) *lumXInc = c->lumXInc;
+    if (chrXInc) *chrXInc = c->chrXInc;
+    return c->fast_bilinear;
+}
+
 extern "C" void mi355_sws_destroy(mi355_sws_ctx *c)
 {
     if (!c) return;
@@ -612,8 +692,9 @@ static int ctx_launch(const mi355_sws_ctx *c, int k, const void *d_frames, int n
 {
     const SwsDev &h = c->h;
     const SwsKey key = sws_key(c, k);
-    const SwsOperands op{ key_grid(key, h, nframes), s, &h, c->d, d_frames, &c->d->luts, h.dstW, h.srcH, h.dst_sel, nullptr };
-    if (!sws_run(key, op)) return -2;
+    const SwsOperands op{ key_grid(key, h, nframes), s, &h, c->d, d_frames, &c->d->luts, h.dstW, h.srcH, h.dst_sel, nullptr, (uint32_t)c->lumXInc, (uint32_t)c->chrXInc };
+    /* a fast-bilinear context: the twin's key names its instance of the bank-free tile kernels */
+    if (!(c->fast_bilinear ? mi355_sws_launch_fastbl(key, op) : sws_run(key, op))) return -2;
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -681,7 +762,8 @@ static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int
     if (rgb32_src(h) && (!src[0] || ((reinterpret_cast<uintptr_t>(src[0]) | (uintptr_t)src_stride[0]) & 3))) return -1;
     /* the packer to a packed 4:2:2 destination: with srcW % 4 == 3 its last group takes the luma byte behind each row in the same way */
     const bool pack3 = h.special && yuy2_dst(h) && (h.srcW & 3) == 3;
-    const int nsrc = rgb ? 1 : (h.src_layout ? 2 : 3), tail = pack3 ? 1 : (rgb && h.src_hsub && (h.srcW & 1) ? bpx : 0);
+    /* a fast-bilinear context: the byte behind srcW / chrSrcW of every line of every plane travels with the picture in the same way (ftail) */
+    const int nsrc = rgb ? 1 : (h.src_layout ? 2 : 3), ftail = c->fast_bilinear ? 1 : 0, tail = pack3 || ftail ? 1 : (rgb && h.src_hsub && (h.srcW & 1) ? bpx : 0);
     /* a P010 source: two planes of 16-bit words — 2 * srcW bytes of luma and 4 * chrSrcW bytes of pairs a row (B is 2), pointers and strides even */
     const int w[3] = { rgb ? bpx * h.srcW : h.srcW * B, rgb ? 0 : (h.src_layout ? 2 * h.chrSrcW * B : h.chrSrcW * B), h.src_layout ? 0 : h.chrSrcW * B },
               ph[3] = { h.srcH, h.chrSrcH, h.chrSrcH };
@@ -690,7 +772,7 @@ static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int
     for (int p = 0; p < nsrc; p++) if (!src[p] || src_stride[p] < w[p]) return -1;
     for (int p = 0; p < ndst; p++) if (!dst[p] || dst_stride[p] < back[p]) return -1;
     DeviceScope on(c->device);
-    const int pw[3] = { (w[0] + tail + 15) & ~15, (w[1] + 15) & ~15, (w[2] + 15) & ~15 };
+    const int pw[3] = { (w[0] + tail + 15) & ~15, (w[1] + ftail + 15) & ~15, (w[2] + ftail + 15) & ~15 };
     int dp[3] = {};
     size_t doff[4] = {};
     for (int p = 0; p < ndst; p++) { dp[p] = (ow[p] + 15) & ~15; doff[p + 1] = doff[p] + (size_t)dp[p] * oh[p]; }
@@ -727,6 +809,8 @@ static int scale_staged(mi355_sws_ctx *c, const uint8_t *const src[3], const int
     for (int p = 0; p < nsrc; p++)
         if (!plane_h2d(c->d_src[p], pw[p], src[p], src_stride[p], w[p], ph[p], c->stream)) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4; }
     if (tail && !plane_h2d(c->d_src[0] + w[0], pw[0], src[0] + w[0], src_stride[0], tail, ph[0], c->stream)) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4; }
+    for (int p = 1; p < 3 && ftail; p++)
+        if (!plane_h2d(c->d_src[p] + w[p], pw[p], src[p] + w[p], src_stride[p], 1, ph[p], c->stream)) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); return -4; }
     if ((planar ? mi355_sws_scale_planar_frames_dev(c, c->d_pframe, 1, c->stream) : mi355_sws_scale_frames_dev(c, c->d_frame, 1, c->stream)) != 0) {
         (void)hipStreamSynchronize(c->stream);
         return -2;

@@ -25,6 +25,9 @@
  * store8_d; compiled in sws_packed.hip).  The RGB instances whose sample type is a 32-bit pixel (SwsPx32: rgba / bgra / argb / abgr sources; compiled in
  * sws_rgb32.hip) run the same converters on a pixel that is one aligned dword; SwsPx32A: the ALPHA form of k_sws_generic, a fourth LDS tile of the
  * source's alpha through the luma banks into the alpha byte of a 32-bit destination.
+ *   k_sws_fbl_generic / k_sws_fbl_planar   the two tile kernels again for SWS_FAST_BILINEAR contexts (compiled in sws_fastbl.hip): the horizontal pass
+ *                   reads no filter bank (hscale_tile_fbl: hyscale_fast_c / hcscale_fast_c swscale.c:238-301), the range step and the vertical pass are
+ *                   the device functions of the two kernels above.  Kernels of their own names: k_sws_generic / k_sws_planar gain no instance.
  *   k_sws_line_*    the individual inner loops for the Tier-1 entry points.
  * Execution model: 256-thread workgroups (4 waves) sharing one LDS tile; integer only, no MFMA.
  */
@@ -2355,6 +2358,202 @@ __global__ void __launch_bounds__(NT) k_sws_planar(const SwsDev *cp, const mi355
                                      fr.dst[1] + (size_t)cy0 * fr.dst_stride[1], fr.dst_stride[1], fr.dst[2] + (size_t)cy0 * fr.dst_stride[2], fr.dst_stride[2], tid, dith);
 }
 
+/* ---- SWS_FAST_BILINEAR contexts: the bank-free horizontal pass and its two tile kernels (compiled in sws_fastbl.hip) ------------------------
+ * The reference's hyscale_fast_c / hcscale_fast_c (swscale.c:238-249, :288-301; selected at :733-739 for 8-bit sources) read no filter bank: output
+ * sample i of a plane sits at xpos = i * xInc (unsigned 32 bit, 16.16), xx = xpos >> 16, a = (xpos & 0xFFFF) >> 9 (0 .. 127), and is
+ *   luma    (src[xx] << 7) + (src[xx + 1] - src[xx]) * a
+ *   chroma   src[xx] * (a ^ 127) + src[xx + 1] * a                    (the weights sum to 127)
+ * with xInc the context's lumXInc / chrXInc as the reference's init left them — kernel arguments here, never recomputed.  There is no tail fix-up:
+ * a column with xx == srcW - 1 reads src[srcW], the byte behind the line in the caller's plane, and with a != 0 that byte is part of the result.  No
+ * result reaches the 32767 clip (255 * 128, 255 * 127).
+ * A tile's span [xx(gx0), xx(last) + 1] is staged as hscale_tile stages a monotonic bank — aligned 16-byte pieces on a plane of 16-byte multiples
+ * (read over the stride), dwords that lie whole inside the span on one of 4-byte multiples — and every thread works out xx and a of its column in
+ * registers.  The byte at x = srcW is read on a tile whose last column has xx == srcW - 1 and on no other: a piece that starts at the stride
+ * (srcW == stride) is that one byte.  Spans wider than a staged line and planes off 4-byte multiples read byte by byte.  mi355_sws_create_fast_bilinear
+ * refuses a plane whose last column has xx > srcW - 1; the min() below keeps such a column inside the same extent all the same.
+ * Unlike hscale_tile the 16-byte pieces do NOT travel through registers one round ahead (its fetch16): a round loads, stores to LDS, waits at its
+ * barrier and computes.  Where this pass is slower than it should be, that is the first thing to try. */
+template <bool CHROMA> __device__ __forceinline__ int fbl_blend(int v0, int v1, int a) { return CHROMA ? v0 * (a ^ 127) + v1 * a : (v0 << 7) + (v1 - v0) * a; }
+template <int COLS, int OP, bool CHROMA>
+__device__ __forceinline__ void hscale_tile_fbl(int16_t (*out)[OP], const uint8_t *src, int stride, int srcW, uint32_t xinc, int gx0, int ncols, int lo, int hi,
+                                                uint32_t *stage_mem, int tid, bool zero_tail)
+{
+    constexpr int PITCH = StageGeom<COLS>::PITCH, LINES = StageGeom<COLS>::LINES, per = NT / COLS;
+    static_assert(LINES % per == 0 && LINES * PITCH * PITCH < (1 << 19), "whole rounds; mi355_div20 range");
+    uint32_t (*stage)[PITCH] = reinterpret_cast<uint32_t (*)[PITCH]>(stage_mem);
+    const int x = tid & (COLS - 1), gx = gx0 + x;
+    const bool col_ok = gx < ncols;
+    /* columns past the picture work on the last column's position and store nothing of it */
+    const uint32_t xpos = (uint32_t)(col_ok ? gx : ncols - 1) * xinc;
+    const int xx = imin((int)(xpos >> 16), srcW - 1), a = (int)((xpos & 0xFFFFu) >> 9);
+    const int last = imin(gx0 + COLS, ncols) - 1;
+    /* the tile's span in bytes: s1 is one past the last byte the reference reads, srcW + 1 at the most */
+    const int s0 = imin((int)(((uint32_t)gx0 * xinc) >> 16), srcW - 1), s1 = imin((int)(((uint32_t)last * xinc) >> 16), srcW - 1) + 2;
+    const uintptr_t al = reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride;
+    const bool al16 = (al & 15) == 0;
+    const int a0 = al16 ? (s0 & ~15) : (s0 & ~3), nd = span_dwords(a0, s1);
+    if (!(span_fits(nd, s0, s1, PITCH) && (al & 3) == 0)) {
+        for (int l = lo + tid / COLS; l <= hi; l += per) {
+            const uint8_t *p = src + (size_t)l * stride + xx;
+            if (col_ok) out[l - lo][x] = (int16_t)fbl_blend<CHROMA>(p[0], p[1], a);
+            else if (zero_tail) out[l - lo][x] = 0;
+        }
+        return;
+    }
+    const int np = al16 ? (nd + 3) >> 2 : nd, inv = mi355_inv20(np);      /* pieces of a staged line */
+    for (int base = lo; base <= hi; base += LINES) {
+        for (int idx = tid; idx < LINES * np; idx += NT) {
+            const int r = mi355_div20(idx, inv), d = idx - r * np, line = base + r;
+            if (line > hi) continue;
+            const uint8_t *row = src + (size_t)line * stride;
+            if (al16) {
+                const int off = a0 + 16 * d;
+                sws_u32x4 w = { 0u, 0u, 0u, 0u };
+                if (off + 16 <= stride) w = *reinterpret_cast<const sws_u32x4 *>(row + off);
+                else {
+                    /* the piece starts at the stride: srcW == stride, and the span's one byte there is x = srcW */
+                    for (int b = 0; b < 16; b++) if (off + b < s1) w[b >> 2] |= (uint32_t)row[off + b] << (8 * (b & 3));
+                }
+                *reinterpret_cast<sws_u32x4 *>(&stage[r][4 * d]) = w;
+            } else {
+                const int off = a0 + 4 * d;
+                uint32_t w = 0;
+                if (off + 4 <= s1) w = *reinterpret_cast<const uint32_t *>(row + off);
+                else {
+                    for (int b = 0; b < 4; b++) if (off + b < s1) w |= (uint32_t)row[off + b] << (8 * b);
+                }
+                stage[r][d] = w;
+            }
+        }
+        __syncthreads();
+        const int r0 = tid / COLS;
+        const uint8_t *p = reinterpret_cast<const uint8_t *>(stage[r0]) + (xx - a0);
+        for (int k = 0; k < LINES / per && base + r0 + k * per <= hi; k++) {
+            const uint8_t *q = p + k * per * (PITCH * 4);
+            if (col_ok) out[base + r0 + k * per - lo][x] = (int16_t)fbl_blend<CHROMA>(q[0], q[1], a);
+            else if (zero_tail) out[base + r0 + k * per - lo][x] = 0;
+        }
+        __syncthreads();
+    }
+}
+
+/* k_sws_generic's tile (LCAP / CCAP / WAVES / DST as there: an 8-bit three-plane source, no alpha) with the bank-free horizontal pass: the same LDS,
+ * the same vertical pass.  lum_inc / chr_inc: the context's lumXInc / chrXInc */
+template <int LCAP, int CCAP, int WAVES, int DST = DST_RGB24>
+#ifndef MI355_HIP_EMU_H
+__attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
+#endif
+__global__ void __launch_bounds__(NT) k_sws_fbl_generic(const SwsDev *cp, uint32_t lum_inc, uint32_t chr_inc, const mi355_sws_frame *frames)
+{
+    __shared__ __attribute__((aligned(16))) int16_t s_lum[LCAP][TW];
+    __shared__ __attribute__((aligned(16))) int16_t s_cu[CCAP][TW / 2], s_cv[CCAP][TW / 2];
+    __shared__ LutLds s_lut;
+    __shared__ __attribute__((aligned(16))) uint8_t s_io[STAGE_BYTES];
+    constexpr int BPP = dst_bpp<DST>();
+    uint8_t (*s_out)[TW * BPP] = reinterpret_cast<uint8_t (*)[TW * BPP]>(s_io);
+    const SwsDev c = sws_dev(cp);
+    mi355_sws_frame fr = frames[blockIdx.z];
+    for (int k = 0; k < 3; k++) fr.src[k] = mi355_global(fr.src[k]);
+    fr.dst = mi355_global(fr.dst);
+    const int tid = threadIdx.x, th = c.th;
+    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * th, y1 = imin(y0 + th, c.dstH) - 1;
+    const int ls = c.vls, cs = c.vcs;
+    const int lfirst0 = imax(1 - ls, c.vLumP[y0]), lfirst1 = imax(1 - ls, c.vLumP[y1]);
+    const int cfirst0 = imax(1 - cs, c.vChrP[y0]), cfirst1 = imax(1 - cs, c.vChrP[y1]);
+    const int llo = clampi(lfirst0, 0, c.srcH - 1), lhi = clampi(lfirst1 + ls - 1, 0, c.srcH - 1);
+    const int clo = clampi(cfirst0, 0, c.chrSrcH - 1), chi = clampi(cfirst1 + cs - 1, 0, c.chrSrcH - 1);
+    if constexpr (DST != DST_YUY2) lut_load(s_lut, &cp->luts, tid);
+    uint32_t *s_stage = reinterpret_cast<uint32_t *>(s_io);
+    hscale_tile_fbl<TW, TW, false>(s_lum, fr.src[0], fr.src_stride[0], c.srcW, lum_inc, x0, c.dstW, llo, lhi, s_stage, tid, true);
+    hscale_tile_fbl<TW / 2, TW / 2, true>(s_cu, fr.src[1], fr.src_stride[1], c.chrSrcW, chr_inc, x0 >> 1, c.chrDstW, clo, chi, s_stage, tid, false);
+    hscale_tile_fbl<TW / 2, TW / 2, true>(s_cv, fr.src[2], fr.src_stride[2], c.chrSrcW, chr_inc, x0 >> 1, c.chrDstW, clo, chi, s_stage, tid, false);
+    __syncthreads();
+    if constexpr (DST == DST_YUY2) {
+        if (c.range) {
+            yuy2_range_tile(c, s_lum, s_cu, s_cv, lhi - llo + 1, chi - clo + 1, x0, tid);
+            __syncthreads();
+        }
+        vertical_yuy2(c, s_lum, s_cu, s_cv, s_out, tid, x0, y0, y1, llo, clo, fr.dst + (size_t)y0 * fr.dst_stride + (size_t)x0 * BPP, fr.dst_stride);
+        return;
+    }
+    /* vertical pass + LUT, as k_sws_generic: full tiles with an aligned destination leave from registers, the others through s_out */
+    const int mode = packed_mode(ls, cs);
+    const int npairs = imin(TW, c.dstW - x0 + 1) >> 1;
+    constexpr uintptr_t WIDE_MASK = DST == DST_RGB32 ? 15 : 7;
+    uint8_t *const tile_dst = fr.dst + (size_t)y0 * fr.dst_stride + (size_t)x0 * BPP;
+    uint8_t *const wide_dst = (ls <= 8 && cs <= 8 && c.dstW - x0 >= TW && ((reinterpret_cast<uintptr_t>(tile_dst) | (uintptr_t)fr.dst_stride) & WIDE_MASK) == 0)
+                                  ? tile_dst : nullptr;
+    if (wide_dst) {
+#define FBL_ROWS(NL, NC) vertical_rows<NL, NC, true, DST, false>(c, s_lut, s_lum, s_cu, s_cv, s_out, tid, y0, y1, llo, clo, npairs, mode, wide_dst, fr.dst_stride, 0, nullptr)
+        switch (tap_bucket(ls) * 4 + tap_bucket(cs)) {
+        case 0: FBL_ROWS(1, 1); break;   case 1: FBL_ROWS(1, 2); break;   case 2: FBL_ROWS(1, 4); break;   case 3: FBL_ROWS(1, 8); break;
+        case 4: FBL_ROWS(2, 1); break;   case 5: FBL_ROWS(2, 2); break;   case 6: FBL_ROWS(2, 4); break;   case 7: FBL_ROWS(2, 8); break;
+        case 8: FBL_ROWS(4, 1); break;   case 9: FBL_ROWS(4, 2); break;   case 10: FBL_ROWS(4, 4); break;  case 11: FBL_ROWS(4, 8); break;
+        case 12: FBL_ROWS(8, 1); break;  case 13: FBL_ROWS(8, 2); break;  case 14: FBL_ROWS(8, 4); break;  default: FBL_ROWS(8, 8); break;
+        }
+#undef FBL_ROWS
+        return;
+    }
+    vertical_narrow<DST, false>(cp, &s_lut, s_lum, s_cu, s_cv, s_out, tile_dst, fr.dst_stride, x0, y0, y1, llo, clo, nullptr);
+}
+
+/* k_sws_planar's tile (LCAP / CCAP / CW / SEMI / RANGE / DEEP as there: an 8-bit three-plane source, no dither) with the bank-free horizontal pass */
+template <int LCAP, int CCAP, int CW, bool SEMI = false, bool RANGE = false, bool DEEP = false>
+#ifndef MI355_HIP_EMU_H
+__attribute__((amdgpu_waves_per_eu(sws_planar_waves(LCAP, CCAP, CW), sws_planar_waves(LCAP, CCAP, CW))))
+#endif
+__global__ void __launch_bounds__(NT) k_sws_fbl_planar(const SwsDev *cp, uint32_t lum_inc, uint32_t chr_inc, const mi355_sws_planar_frame *frames)
+{
+    __shared__ __attribute__((aligned(16))) int16_t s_lum[LCAP][TW];
+    __shared__ __attribute__((aligned(16))) int16_t s_chr[CCAP][2 * CW];
+    __shared__ __attribute__((aligned(16))) uint32_t s_stage[STAGE_BYTES / 4];
+    const SwsDev c = sws_dev(cp);
+    mi355_sws_planar_frame fr = frames[blockIdx.z];
+    for (int k = 0; k < 3; k++) { fr.src[k] = mi355_global(fr.src[k]); fr.dst[k] = mi355_global(fr.dst[k]); }
+    const int tid = threadIdx.x, th = c.th, hs = c.hshift, vs = c.vshift;
+    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * th, y1 = imin(y0 + th, c.dstH) - 1;
+    const int cy0 = (y0 + (1 << vs) - 1) >> vs, cy1 = y1 >> vs;
+    const int ls = c.vls, cs = c.vcs;
+    const int llo = clampi(imax(1 - ls, c.vLumP[y0]), 0, c.srcH - 1), lhi = clampi(imax(1 - ls, c.vLumP[y1]) + ls - 1, 0, c.srcH - 1);
+    hscale_tile_fbl<TW, TW, false>(s_lum, fr.src[0], fr.src_stride[0], c.srcW, lum_inc, x0, c.dstW, llo, lhi, s_stage, tid, false);
+    int clo = 0, nchr = 0;
+    if (cy0 <= cy1) {
+        clo = clampi(imax(1 - cs, c.vChrP[cy0]), 0, c.chrSrcH - 1);
+        const int chi = clampi(imax(1 - cs, c.vChrP[cy1]) + cs - 1, 0, c.chrSrcH - 1);
+        nchr = chi - clo + 1;
+        hscale_tile_fbl<CW, 2 * CW, true>(s_chr, fr.src[1], fr.src_stride[1], c.chrSrcW, chr_inc, x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false);
+        hscale_tile_fbl<CW, 2 * CW, true>(reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]), fr.src[2], fr.src_stride[2], c.chrSrcW, chr_inc, x0 >> hs, c.chrDstW,
+                                          clo, chi, s_stage, tid, false);
+    }
+    __syncthreads();
+    if constexpr (RANGE) {
+        range_lines(&s_lum[0][0], (lhi - llo + 1) * (TW / 8), c.rng_l, tid);
+        range_lines(&s_chr[0][0], nchr * (2 * CW / 8), c.rng_c, tid);
+        __syncthreads();
+    }
+    if constexpr (DEEP) {
+        static_assert(!SEMI && !RANGE, "a deep destination is three planes of one range");
+        planar_pass16<TW / 8, 1>(c, &s_lum[0][0], llo, c.srcH - 1, c.vLumC, c.vLumP, ls, y0, y1 - y0 + 1, x0, c.dstW,
+                                 fr.dst[0] + (size_t)y0 * fr.dst_stride[0], fr.dst_stride[0], nullptr, 0, tid);
+        if (cy0 <= cy1)
+            planar_pass16<CW / 8, 2>(c, &s_chr[0][0], clo, c.chrSrcH - 1, c.vChrC, c.vChrP, cs, cy0, cy1 - cy0 + 1, x0 >> hs, c.chrDstW,
+                                     fr.dst[1] + (size_t)cy0 * fr.dst_stride[1], fr.dst_stride[1], fr.dst[2] + (size_t)cy0 * fr.dst_stride[2], fr.dst_stride[2], tid);
+        return;
+    }
+    planar_pass<TW / 8, 1, false>(&s_lum[0][0], llo, c.srcH - 1, c.vLumC, c.vLumP, ls, y0, y1 - y0 + 1, x0, c.dstW,
+                                  fr.dst[0] + (size_t)y0 * fr.dst_stride[0], fr.dst_stride[0], nullptr, 0, tid, nullptr);
+    if constexpr (SEMI) {
+        static_assert(CW == TW / 2, "a semi-planar destination is 4:2:0");
+        if (cy0 <= cy1)
+            semiplanar_pass<false>(&s_chr[0][0], clo, c.chrSrcH - 1, c.vChrC, c.vChrP, cs, cy0, cy1 - cy0 + 1, x0 >> 1, c.chrDstW,
+                                   fr.dst[1] + (size_t)cy0 * fr.dst_stride[1], fr.dst_stride[1], tid, nullptr, c.planar == MI355_SWS_DST_NV21);
+        return;
+    }
+    if (cy0 <= cy1)
+        planar_pass<CW / 8, 2, false>(&s_chr[0][0], clo, c.chrSrcH - 1, c.vChrC, c.vChrP, cs, cy0, cy1 - cy0 + 1, x0 >> hs, c.chrDstW,
+                                      fr.dst[1] + (size_t)cy0 * fr.dst_stride[1], fr.dst_stride[1], fr.dst[2] + (size_t)cy0 * fr.dst_stride[2], fr.dst_stride[2], tid, nullptr);
+}
+
 /* MI355_SWS_TILE_KERNELS_ONLY (sws_deep.hip): the kernels that are no templates — the packer, the splitter, the line kernels — are sws.hip's
  * alone; a second file would emit a copy of each */
 #ifndef MI355_SWS_TILE_KERNELS_ONLY
@@ -3004,6 +3203,7 @@ struct SwsOperands {
     int dstW, rows;
     uint32_t sel;
     const SwsLine *line;
+    uint32_t lum_inc, chr_inc;     /* a fast-bilinear context's lumXInc / chrXInc (mi355_sws_launch_fastbl alone reads them) */
 };
 /* one launch function a file: false for a key the file has no instance for */
 bool mi355_sws_launch_deep(const SwsKey &key, const SwsOperands &op);       /* sws_deep.hip: the DEEP instances of the four classic source classes */
@@ -3011,6 +3211,7 @@ bool mi355_sws_launch_packed(const SwsKey &key, const SwsOperands &op);     /* s
 bool mi355_sws_launch_rgb32(const SwsKey &key, const SwsOperands &op);      /* sws_rgb32.hip: every tile instance of SWS_SRC_RGB32, k_sws_line_packed_a */
 bool mi355_sws_launch_yuy2(const SwsKey &key, const SwsOperands &op);       /* sws_yuy2.hip: every tile instance of SWS_SRC_YUY2, k_sws_ident1_yuy2, k_sws_yuy2_split */
 bool mi355_sws_launch_p010(const SwsKey &key, const SwsOperands &op);       /* sws_p010.hip: every tile instance of SWS_SRC_P010, DST_YUY2 included */
+bool mi355_sws_launch_fastbl(const SwsKey &key, const SwsOperands &op);     /* sws_fastbl.hip: every instance of k_sws_fbl_generic / k_sws_fbl_planar (a fast-bilinear context's key is its twin's) */
 bool mi355_sws_launch_yuy2dst(const SwsKey &key, const SwsOperands &op);    /* sws_yuy2dst.hip: DST_YUY2 of k_sws_generic, k_sws_ident1, k_sws_ident1_yuy2, k_sws_line_packed from every source class; k_sws_yuy2_pack */
 
 namespace {

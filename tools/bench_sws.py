@@ -77,6 +77,11 @@ def main():
                          "allocation (A/A), with --other-lib also on that build (the parent commit's); and a plain device copy of the source bytes (the "
                          "twin plus that copy is the cheapest two-step route); 32 and 512 pictures per launch, 3 warm-up + --steps launches a round, "
                          "alternating, median of --rounds rounds")
+    ap.add_argument("--fast-bilinear", action="store_true",
+                    help="SWS_FAST_BILINEAR contexts (mi355_sws_create_fast_bilinear) beside (a) the SWS_BILINEAR context of the same geometry on the bank-driven "
+                         "kernels and (b) the same arithmetic restated as two-tap banks for the existing creator: 2160p -> 1080p and 1080p -> 2160p yuv420p to "
+                         "rgb24 and to yuv420p; (a) a second time in another allocation (A/A); 32 and 512 pictures per launch, 3 warm-up + --steps launches a "
+                         "round, alternating, median of --rounds rounds")
     ap.add_argument("--other-lib", default=None,
                     help="--nv12 / --nvsrc / --rgbsrc / --range / --rgb32src / --p010: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
     ap.add_argument("--rounds", type=int, default=5, help="--planar / --sources / --yuy2src / --yuy2dst: alternating rounds (the median is reported)")
@@ -109,6 +114,8 @@ def main():
         return yuy2dst_points(a, lib)
     if a.p010:
         return p010_points(a, lib)
+    if a.fast_bilinear:
+        return fastbl_points(a, lib)
     orc = S.oracle_backend(providers.oracle())
     for name in a.configs.split(","):
         ctx = S.load_context(name)
@@ -1164,6 +1171,71 @@ def p010_points(a, lib, points=None, frame_counts=(32, 512)):
             for r in rows if r["workload"].endswith(":p010") and r["vs_twin"] > r["aa_spread"]]
     slow = ["%s@%d %+.1f%% of twin + copy" % (r["workload"], r["frames_per_launch"], 100 * r["vs_two_step"]) for r in rows if r.get("vs_two_step", -1) >= 0]
     print(json.dumps({"summary": "p010", "aa_session": aa, "points": len(rows), "miss": miss, "not_below_two_step": slow}), flush=True)
+
+
+def fastbl_points(a, lib, points=None, frame_counts=(32, 512)):
+    """A SWS_FAST_BILINEAR context (the bank-free horizontal pass of k_sws_fbl_generic / k_sws_fbl_planar) beside two yardsticks of the same geometry,
+    source bytes and destination: `bilinear` — the reference's SWS_BILINEAR context on the bank-driven kernels (what a caller got on the device before,
+    by asking for the other scaler; its vertical banks differ in size where the picture shrinks), `bilinear#2` the same a second time with its own
+    buffers: the session's A/A spread; `banked` — the fast arithmetic restated as two-tap banks for the existing creator (tests/sws_fastbl.py:
+    Entry.bank_twin), which for an upscale has a tap behind the line and so runs unstaged: the route the new pass replaces.  The contexts come from the
+    reference's libswscale at run time (oracle/_ref/libswsref.so: mi355_sws_describe_fast and the existing describers) — no full-size context is
+    committed.  One process, the batches of a point alternating: 3 warm-up + --steps launches a round, median of --rounds rounds, at 32 and 512
+    pictures per launch.  Algorithmic bytes: the source planes read once + the destination planes written once.  The last line sums the session up:
+    `aa_session` and, under `miss`, every fast row slower than `bilinear` by more than the point's spread."""
+    import statistics
+    import numpy as np
+    import sws_planar as P
+    import sws_fastbl as F
+    ref = F.Ref(P.bind(F.REF_LIB))
+    # (point, srcW, srcH, dstW, dstH, destination of tests/sws_fastbl.py)
+    points = points or [("uhd_to_hd_rgb24", 3840, 2160, 1920, 1080, "rgb24"), ("uhd_to_hd_yuv420p", 3840, 2160, 1920, 1080, "420"),
+                        ("hd_to_uhd_rgb24", 1920, 1080, 3840, 2160, "rgb24"), ("hd_to_uhd_yuv420p", 1920, 1080, 3840, 2160, "420")]
+    rows = []
+
+    def batch(x, pics, frames, create):
+        if x.one_plane():
+            return SourceBatch(lib, None, x, pics, frames, create=create, bpp=3)
+        return PlaneBatch(lib, create(lib, x), pics, x.out_sizes(), frames)
+
+    for frames in frame_counts:
+        for point, sw, sh, dw, dh, dst in points:
+            row = (sw, sh, dw, dh, "420", 0, dst, 0)                    # a row of tests/sws_fastbl.py's form, not entered into its table
+            c = ref.open(row)
+            e = ref.describe_fast(c)
+            ref.free(c)
+            c = ref.open(row, fast=False)
+            t = ref.describe_fmt(c)
+            ref.free(c)
+            assert e is not None and t is not None, point
+            bil = F.Entry(t.ctx, t.hsub, t.vsub, t.fmt, 0, 8, 0, 0)
+            noise = F.frames(row)
+            pics = [[np.ascontiguousarray(pl[:, :w]) for pl, (w, _) in zip(noise[f], F.plane_dims(row))] for f in (1, 2)]      # tightly pitched planes
+            batches = {"fast": batch(e, pics, frames, F.create), "bilinear": batch(bil, pics, frames, F.create_banked),
+                       "bilinear#2": batch(bil, pics, frames, F.create_banked), "banked": batch(e.bank_twin(force=True), pics, frames, F.create_banked)}
+            plans = {k: F.plan_of(lib, b.handle) for k, b in batches.items()}
+            times = {k: [] for k in batches}
+            for _ in range(a.rounds):
+                for k, b in batches.items():
+                    times[k].append(time_ms(lib, b.run, a.steps))
+            base, banked = statistics.median(times["bilinear"]), statistics.median(times["banked"])
+            spread = abs(statistics.median(times["bilinear#2"]) / base - 1.0)
+            for k, b in batches.items():
+                ms = statistics.median(times[k])
+                us = ms * 1e3 / frames
+                nb = b.src_bytes + b.dst_bytes
+                out = {"workload": point + ":" + k, "frames_per_launch": frames, "ms_per_launch": ms, "us_per_picture": us, "frames_per_s": 1e6 / us,
+                       "algorithmic_bytes_per_frame": nb, "achieved_GBps": nb / us * 1e-3, "frac_of_8TBps": nb / us * 1e-3 / 8000.0,
+                       "vs_bilinear": ms / base - 1.0, "vs_banked": ms / banked - 1.0, "aa_spread": spread, "kernel": plans[k]["kernel"],
+                       "hstage": plans[k]["hstage"], "hstaged": plans[k]["hstaged"], "ms_rounds": [round(x, 4) for x in times[k]]}
+                rows.append(out)
+                print(json.dumps(out), flush=True)
+            for b in batches.values():
+                b.close()
+    aa = max(r["aa_spread"] for r in rows)
+    miss = ["%s@%d %+.1f%% (spread %+.1f%%)" % (r["workload"], r["frames_per_launch"], 100 * r["vs_bilinear"], 100 * r["aa_spread"])
+            for r in rows if r["workload"].endswith(":fast") and r["vs_bilinear"] > r["aa_spread"]]
+    print(json.dumps({"summary": "fast_bilinear", "aa_session": aa, "points": len(rows), "miss": miss}), flush=True)
 
 
 if __name__ == "__main__":
