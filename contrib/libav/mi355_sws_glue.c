@@ -124,6 +124,12 @@
  *                          increments kept in the slot.  With MI355_SWS_LINES=1 the two functions go to mi355_sws_hyscale_fast / _hcscale_fast, the
  *                          other loops as for the same context without them.  Declined: the flag from any other source (the reference's conversion
  *                          buffer holds an uninitialised sample behind the width there), the x86 build's MMXEXT scaler.
+ *   gbrp destinations      (AV_PIX_FMT_GBRP: c->yuv2anyX = yuv2gbrp_full_X_c, the arithmetic yuv -> rgb path under the SWS_FULL_CHR_H_INT the reference forces for
+ *                          planar RGB) have the thirteenth describer, mi355_sws_describe_gbrp(), for mi355_sws_create_gbrp(): from every source above, with the
+ *                          six c->yuv2rgb_* coefficients as the context holds them.  Bound like a 32-bit source — asked before every other describer, whole
+ *                          pictures through mi355_sws_scale_planar (dst[0..2] = G, B, R); coefficients changed since (sws_setColorspaceDetails) build the device
+ *                          side anew.  With MI355_SWS_LINES=1 c->yuv2anyX goes to mi355_sws_yuv2gbrp_full_X, the other loops stay the reference's.  Declined:
+ *                          gbrap, deeper gbrp, planar RGB sources, rgbToPlanarRgbWrapper (no banks), SWS_FAST_BILINEAR, a chroma line drop.
  * The device is MI355_DEVICE (default 0), as for the decoder bridges.
  */
 #include <pthread.h>
@@ -846,6 +852,99 @@ int mi355_sws_describe_fast(const struct SwsContext *cc, mi355_sws_desc *d, mi35
     return 0;
 }
 
+/* ---- planar RGB destinations: gbrp -------------------------------------------------------------------------------------------------------------
+ * the output function the context HOLDS is the C one, yuv2gbrp_full_X_c (static in the reference: two pixels through it — one inside the range, one that
+ * clips — with one tap a bank, as range_probe does; nothing runs on the device).  A context whose function is this file's own shim (ff_sws_init_mi355x
+ * set it for a context that passed this probe) is taken without calling it */
+#ifndef MI355_SWS_DESCRIBE_ONLY
+static void t1_gbrpX(SwsContext *c, const int16_t *lumFilter, const int16_t **lumSrc, int lumFilterSize, const int16_t *chrFilter, const int16_t **chrUSrc,
+                     const int16_t **chrVSrc, int chrFilterSize, const int16_t **alpSrc, uint8_t **dest, int dstW, int y);
+#endif
+static void coefs_of(const SwsContext *c, mi355_sws_rgb_coefs *k)
+{
+    k->y_offset = c->yuv2rgb_y_offset; k->y_coeff = c->yuv2rgb_y_coeff;
+    k->v2r = c->yuv2rgb_v2r_coeff; k->v2g = c->yuv2rgb_v2g_coeff; k->u2g = c->yuv2rgb_u2g_coeff; k->u2b = c->yuv2rgb_u2b_coeff;
+}
+/* one byte of the formula above mi355_sws_create_gbrp (include/mi355_sws.h): a sum modulo 2^32, clipped on its bits 30 / 31 */
+static uint8_t gbrp_byte(uint32_t v) { return (uint8_t)(((v & 0xC0000000u) ? ((v >> 31) ? 0u : 0x3FFFFFFFu) : v) >> 22); }
+static int gbrp_probe(const SwsContext *c)
+{
+    static const int16_t f[1] = { 4096 }, l[2] = { 100 << 7, 255 << 7 }, u[2] = { 90 << 7, 255 << 7 }, v[2] = { 200 << 7, 10 << 7 };
+    const int16_t *lp[1] = { l }, *up[1] = { u }, *vp[1] = { v };
+    uint8_t g[2] = { 0 }, b[2] = { 0 }, r[2] = { 0 }, *dest[4] = { g, b, r, NULL };
+    mi355_sws_rgb_coefs k;
+    if (!c->yuv2anyX) return -1;
+#ifndef MI355_SWS_DESCRIBE_ONLY
+    if (c->yuv2anyX == t1_gbrpX) return 0;
+#endif
+    coefs_of(c, &k);
+    /* (the reference's prototype takes a writable context; the C function reads dstFormat and the six coefficients) */
+    c->yuv2anyX((SwsContext *)c, f, lp, 1, f, up, vp, 1, NULL, dest, 2, 0);
+    for (int i = 0; i < 2; i++) {
+        const int Y = ((1 << 9) + l[i] * 4096) >> 10, U = ((1 << 9) - (128 << 19) + u[i] * 4096) >> 10, V = ((1 << 9) - (128 << 19) + v[i] * 4096) >> 10;
+        const uint32_t y = (uint32_t)(Y - k.y_offset) * (uint32_t)k.y_coeff + (1u << 21);
+        if (r[i] != gbrp_byte(y + (uint32_t)V * (uint32_t)k.v2r) || g[i] != gbrp_byte(y + (uint32_t)V * (uint32_t)k.v2g + (uint32_t)U * (uint32_t)k.u2g) ||
+            b[i] != gbrp_byte(y + (uint32_t)U * (uint32_t)k.u2b)) return -1;
+    }
+    return 0;
+}
+/* what mi355_sws_create_gbrp takes for a live context (0), -1 for every other context — the twelve describers above keep declining this destination
+ * (it is none of their formats, and the reference forces SWS_FULL_CHR_H_INT for it, utils.c:986-994).  The generic scaler's contexts to AV_PIX_FMT_GBRP
+ * whose yuv2anyX is the C function (gbrp_probe): chrDstW = dstW, chrDstH = dstH, no range converter, no alpha; from every source of the describers
+ * above, each under the source-side checks of its own describer (three planes at 8 / 9 / 10 bits; NV12 / NV21; rgb24 / bgr24; the four 32-bit orders,
+ * whose alpha is not carried: gbrp has none; the three packed 4:2:2 orders; p010le).  *coefs: c->yuv2rgb_* as they are NOW (sws_setColorspaceDetails
+ * rewrites them after init).  Declined: a context without the banks (rgbToPlanarRgbWrapper from an 8-bit packed RGB source at equal size,
+ * swscale_unscaled.c:1090-1092), gbrap and the deeper gbrp formats, planar RGB sources, SWS_FAST_BILINEAR, a chroma line drop */
+int mi355_sws_describe_gbrp(struct SwsContext *c, mi355_sws_desc *d, mi355_sws_src *s, int *src_layout, mi355_sws_rgb_coefs *coefs)
+{
+    int layout = MI355_SWS_SRC_PLANAR;
+    if (c->dstFormat != AV_PIX_FMT_GBRP || c->dstBpc != 8 || !c->vLumFilter || !c->vChrFilter || !c->hLumFilter || !c->hChrFilter) return -1;
+    if (c->hyscale_fast || c->hcscale_fast || c->vChrDrop || c->lumConvertRange || c->chrConvertRange || c->alpPixBuf) return -1;
+    if (c->chrDstHSubSample || c->chrDstVSubSample || c->chrDstW != c->dstW || c->chrDstH != c->dstH) return -1;
+    if (c->readLumPlanar || c->readChrPlanar || c->readAlpPlanar || c->alpToYV12) return -1;
+    if (rgb32_layout_of(c) || yuy2_layout_of(c)) {
+        /* the checks of mi355_sws_describe_rgb32 / mi355_sws_describe_yuy2 on the source side */
+        layout = rgb32_layout_of(c) ? rgb32_layout_of(c) : yuy2_layout_of(c);
+        if (c->chrSrcVSubSample != 0 || (c->chrSrcHSubSample & ~1) || c->srcBpc != 8) return -1;
+        if (rgb32_layout_of(c) ? rgb32_probe(c, layout, 0) != 0 : (c->chrSrcHSubSample != 1 || yuy2_probe(c, layout) != 0)) return -1;
+        memset(s, 0, sizeof(*s));
+        s->depth = 8; s->hsub = c->chrSrcHSubSample; s->vsub = 0;
+    } else if (c->srcFormat == AV_PIX_FMT_P010LE) {
+        /* ... of mi355_sws_describe_p010 */
+        layout = MI355_SWS_SRC_P010;
+        if (c->chrSrcHSubSample != 1 || c->chrSrcVSubSample != 1 || c->srcBpc != 10 || p010_probe(c) != 0) return -1;
+        memset(s, 0, sizeof(*s));
+        s->depth = 10; s->hsub = 1; s->vsub = 1;
+    } else if (c->srcFormat == AV_PIX_FMT_RGB24 || c->srcFormat == AV_PIX_FMT_BGR24) {
+        /* ... of fmt_format_r: both input converters, the chroma one by the context's chrSrcHSubSample */
+        layout = c->srcFormat == AV_PIX_FMT_RGB24 ? MI355_SWS_SRC_RGB24 : MI355_SWS_SRC_BGR24;
+        if (c->chrSrcVSubSample != 0 || (c->chrSrcHSubSample & ~1) || c->srcBpc != 8 || !c->lumToYV12 || !c->chrToYV12) return -1;
+        memset(s, 0, sizeof(*s));
+        s->depth = 8; s->hsub = c->chrSrcHSubSample; s->vsub = 0;
+    } else if (c->srcFormat == AV_PIX_FMT_NV12 || c->srcFormat == AV_PIX_FMT_NV21) {
+        /* ... of fmt_format_r: the chroma converter alone */
+        layout = c->srcFormat == AV_PIX_FMT_NV12 ? MI355_SWS_SRC_NV12 : MI355_SWS_SRC_NV21;
+        if (c->chrSrcHSubSample != 1 || c->chrSrcVSubSample != 1 || c->srcBpc != 8 || c->lumToYV12 || !c->chrToYV12) return -1;
+        memset(s, 0, sizeof(*s));
+        s->depth = 8; s->hsub = 1; s->vsub = 1;
+    } else {
+        /* ... of src_format_r: three planes, no input converter */
+        if (source_of(c, s) != 0 || c->lumToYV12 || c->chrToYV12) return -1;
+    }
+    if (gbrp_probe(c) != 0) return -1;
+    memcpy(s->dither, ff_dither_8x8_128, sizeof(s->dither));      /* (part of the source record; this destination does not dither) */
+    memset(d, 0, sizeof(*d));
+    d->srcW = c->srcW; d->srcH = c->srcH; d->dstW = c->dstW; d->dstH = c->dstH;
+    d->chrSrcW = c->chrSrcW; d->chrSrcH = c->chrSrcH; d->chrDstW = c->chrDstW;
+    d->hLum = (mi355_sws_filter){ c->hLumFilter, c->hLumFilterPos, c->hLumFilterSize, c->dstW };
+    d->hChr = (mi355_sws_filter){ c->hChrFilter, c->hChrFilterPos, c->hChrFilterSize, c->chrDstW };
+    d->vLum = (mi355_sws_filter){ c->vLumFilter, c->vLumFilterPos, c->vLumFilterSize, c->dstH };
+    d->vChr = (mi355_sws_filter){ c->vChrFilter, c->vChrFilterPos, c->vChrFilterSize, c->dstH };
+    *src_layout = layout;
+    coefs_of(c, coefs);
+    return 0;
+}
+
 #ifndef MI355_SWS_DESCRIBE_ONLY
 static void t1_hscale16(SwsContext *c, int16_t *dst, int dstW, const uint8_t *src, const int16_t *filter, const int32_t *filterPos, int filterSize)
 {
@@ -1178,9 +1277,29 @@ static void t1_hyscale_fast(SwsContext *c, int16_t *dst, int dstWidth, const uin
 static void t1_hcscale_fast(SwsContext *c, int16_t *dst1, int16_t *dst2, int dstWidth, const uint8_t *src1, const uint8_t *src2, int srcW, int xInc)
 { (void)c; n_calls++; mi355_sws_hcscale_fast(dst1, dst2, dstWidth, src1, src2, srcW, xInc); }
 
+/* ... of a gbrp context (yuv2gbrp_full_X_c): the three destination lines through one entry, the coefficients the context holds at the call */
+static void t1_gbrpX(SwsContext *c, const int16_t *lumFilter, const int16_t **lumSrc, int lumFilterSize, const int16_t *chrFilter, const int16_t **chrUSrc,
+                     const int16_t **chrVSrc, int chrFilterSize, const int16_t **alpSrc, uint8_t **dest, int dstW, int y)
+{
+    mi355_sws_rgb_coefs k;
+    (void)alpSrc; (void)y;
+    coefs_of(c, &k);
+    n_calls++;
+    mi355_sws_yuv2gbrp_full_X(&k, lumFilter, lumSrc, lumFilterSize, chrFilter, chrUSrc, chrVSrc, chrFilterSize, dest, dstW);
+}
+
 static void init_loops(SwsContext *c);
 void ff_sws_init_mi355x(SwsContext *c)
 {
+    if (c->dstFormat == AV_PIX_FMT_GBRP) {
+        /* a gbrp context mi355_sws_describe_gbrp takes: its output function alone (the other loops stay the reference's); any other stays as it is */
+        mi355_sws_desc d;
+        mi355_sws_src s;
+        mi355_sws_rgb_coefs k;
+        int layout;
+        if (mi355_sws_describe_gbrp(c, &d, &s, &layout, &k) == 0 && device_ready()) c->yuv2anyX = t1_gbrpX;
+        return;
+    }
     if (c->hyscale_fast || c->hcscale_fast) {
         /* a fast-bilinear context mi355_sws_describe_fast takes: the other loops as for the same context without the two fast functions (the range
          * converters, the vertical loops), then the two fast functions themselves; any other context with them stays the reference's */
@@ -1270,8 +1389,11 @@ typedef struct Bound {
                                    * 3: a packed 4:2:2 DESTINATION from any source (mi355_sws_describe_yuy2dst, the same fields; packed is its format, no tables);
                                    * 4: a p010le source to any destination (mi355_sws_describe_p010, the same fields; TWO source planes; never alpha);
                                    * 5: a fast-bilinear context of a planar 8-bit source (mi355_sws_describe_fast, the same fields and the two increments below;
-                                   *    built by mi355_sws_create_fast_bilinear) */
+                                   *    built by mi355_sws_create_fast_bilinear);
+                                   * 6: a gbrp destination from any source (mi355_sws_describe_gbrp: layout as it gave it, planar is MI355_SWS_DST_GBRP; built by
+                                   *    mi355_sws_create_gbrp from the coefficients below) */
     int lumXInc, chrXInc;         /* ... the increments it was bound with */
+    mi355_sws_rgb_coefs coefs;    /* ... the six coefficients the device context was built from (sws_setColorspaceDetails rewrites the context's: built anew then) */
     int alpha;                    /* ... whose alpha goes to the 32-bit destination (mi355_sws_create_src_layout_alpha) */
     mi355_sws_ctx *dev;
     int failed;                   /* the device side does not take this context: the reference's function from now on */
@@ -1321,6 +1443,14 @@ static SwsFunc bind(SwsContext *c, SwsFunc real, int special)
 {
     int planar = special ? 0 : planar_format(c), other = 0, layout = MI355_SWS_SRC_PLANAR, range = MI355_SWS_RANGE_NONE, depth = 8, packed = 0;
     int rgb32 = 0, alpha = 0, lum_inc = 0, chr_inc = 0;
+    if (c->dstFormat == AV_PIX_FMT_GBRP) {
+        /* a gbrp destination: one describer for every source it comes from, asked before every branch below (none of them takes the format) */
+        mi355_sws_desc d;
+        mi355_sws_src s;
+        mi355_sws_rgb_coefs k;
+        if (special || mi355_sws_describe_gbrp(c, &d, &s, &layout, &k) != 0) return real;
+        rgb32 = 6; other = 1; planar = MI355_SWS_DST_GBRP;
+    } else
     if (!special && (c->hyscale_fast || c->hcscale_fast)) {
         /* a fast-bilinear context: asked FIRST, before every branch below, and built through its own creator.  The ten describers behind those branches
          * decline such a context anyway, but taken() — mi355_sws_describe's test — looks at the two formats alone and would hand yuv420p -> rgb24 to the
@@ -1423,7 +1553,11 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
     mi355_sws_desc d32;
     mi355_sws_src s32;
     int l32 = 0, f32 = 0, r32 = 0, dp32 = 8, a32 = 0, li32 = 0, ci32 = 0;
-    const int rgb32_ok = b && b->rgb32 && (b->rgb32 == 5 ? mi355_sws_describe_fast(c, &d32, &s32, &f32, &r32, &dp32, &li32, &ci32) == 0 && li32 == b->lumXInc && ci32 == b->chrXInc :
+    mi355_sws_rgb_coefs k32;
+    memset(&k32, 0, sizeof(k32));
+    if (b && b->rgb32 == 6) f32 = MI355_SWS_DST_GBRP;              /* (its describer has no format, range or depth to give: a gbrp context has one of each) */
+    const int rgb32_ok = b && b->rgb32 && (b->rgb32 == 6 ? mi355_sws_describe_gbrp(c, &d32, &s32, &l32, &k32) == 0 :
+                                           b->rgb32 == 5 ? mi355_sws_describe_fast(c, &d32, &s32, &f32, &r32, &dp32, &li32, &ci32) == 0 && li32 == b->lumXInc && ci32 == b->chrXInc :
                                            b->rgb32 == 4 ? mi355_sws_describe_p010(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 :
                                            b->rgb32 == 3 ? mi355_sws_describe_yuy2dst(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 && !d32.unscaled_special :
                                            b->rgb32 == 2 ? mi355_sws_describe_yuy2(c, &d32, &s32, &l32, &f32, &r32, &dp32) == 0 && !d32.unscaled_special
@@ -1448,12 +1582,16 @@ static int mi355_swsfunc(SwsContext *c, const uint8_t *src[], int srcStride[], i
             luts_packed(c, b->packed, &now);
             if (memcmp(b->y_table, now.y_table, 1024) || b->gv0 != c->table_gV[0]) { mi355_sws_destroy(b->dev); b->dev = NULL; }
         }
+        /* a gbrp context whose coefficients changed since its device side was built */
+        if (b->dev && !b->busy && b->rgb32 == 6 && rgb32_ok && memcmp(&b->coefs, &k32, sizeof(k32))) { mi355_sws_destroy(b->dev); b->dev = NULL; }
         if (!b->dev) {
             mi355_sws_desc d;
             int fmt;
             if (b->rgb32) {
                 if (device_ready() && rgb32_ok) {
-                    b->dev = b->rgb32 == 5 ? mi355_sws_create_fast_bilinear(&d32, &s32, f32, r32, dp32, li32, ci32) :
+                    b->coefs = k32;
+                    b->dev = b->rgb32 == 6 ? mi355_sws_create_gbrp(&d32, &s32, l32, &k32) :
+                             b->rgb32 == 5 ? mi355_sws_create_fast_bilinear(&d32, &s32, f32, r32, dp32, li32, ci32) :
                              a32 ? mi355_sws_create_src_layout_alpha(&d32, &s32, l32, f32, 1) : mi355_sws_create_src_layout_range_depth(&d32, &s32, l32, f32, r32, dp32);
                     d = d32;
                 }

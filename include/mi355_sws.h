@@ -16,7 +16,8 @@
  * (yuv422pToYuy2Wrapper, yuv422pToUyvyWrapper, planarToYuy2Wrapper, planarToUyvyWrapper swscale_unscaled.c:179-225); and from p010le sources
  * (p010LEToY_c / p010LEToUV_c input.c:499-524 in front of hScale16To15_c, depth 10) to every destination the yuv420p10le source takes; and
  * SWS_FAST_BILINEAR contexts of the planar 8-bit sources (hyscale_fast_c / hcscale_fast_c swscale.c:238-301 in place of hyScale / hcScale:
- * mi355_sws_create_fast_bilinear) to every destination those sources take.
+ * mi355_sws_create_fast_bilinear) to every destination those sources take; and TO planar RGB, gbrp (the arithmetic path yuv2gbrp_full_X_c
+ * output.c:1275-1355 with six integer coefficients in place of the LUTs: mi355_sws_create_gbrp), from every source layout.
  *
  * The reference keeps these behind function pointers of the (private) SwsContext
  * (libswscale/swscale_internal.h:253-540): hyScale/hcScale :526-531, yuv2plane1/yuv2planeX/
@@ -369,8 +370,9 @@ int mi355_sws_dest_depth(const mi355_sws_ctx *ctx);   /* 8 / 9 / 10, -1 bad argu
  * (24-bit only) single-byte pieces as pointer, stride and row length allow, and the other two kernels write it pair by pair.
  * mi355_sws_destination reports the format, planes = 1 and chr_bytes = chr_rows = 0; mi355_sws_dest_depth 8; mi355_sws_range 0; mi355_sws_plan the
  * twin's values — there is no MI355_SWS_K_* of these destinations: the twin's value with the destination's format names the kernel.
- * Not taken (the reference's): 15 / 16-bit and lower RGB (dithered, other tables), rgb48 / rgba64, planar GBR, alpha from a YUVA source,
- * SWS_FULL_CHR_H_INT, rgbToRgbWrapper, and a range or a 9 / 10-bit depth with these destinations. */
+ * Not taken (the reference's): 15 / 16-bit and lower RGB (dithered, other tables), rgb48 / rgba64, planar GBR of 9 / 10 / 12 / 16 bits and gbrap
+ * (8-bit gbrp: mi355_sws_create_gbrp below), alpha from a YUVA source, SWS_FULL_CHR_H_INT to THESE destinations (the reference forces it for gbrp
+ * alone), rgbToRgbWrapper, and a range or a 9 / 10-bit depth with these destinations. */
 enum { MI355_SWS_DST_BGR24 = 32, MI355_SWS_DST_RGBA = 33, MI355_SWS_DST_BGRA = 34, MI355_SWS_DST_ARGB = 35, MI355_SWS_DST_ABGR = 36 };
 
 /* ---- packed 4:2:2 destinations: yuyv422 / uyvy422 / yvyu422 (what capture, SDI and display pipelines take back; yuv2422_X / _2 / _1_c_template
@@ -417,7 +419,7 @@ enum { MI355_SWS_DST_BGR24 = 32, MI355_SWS_DST_RGBA = 33, MI355_SWS_DST_BGRA = 3
  * A packed 4:2:2 source to ANOTHER packed 4:2:2 order at equal size is a context of the reference's scaler (banks of one tap each: it has no converter
  * between the orders) and has its twin's plan, MI355_SWS_K_IDENT1_1 straight from the packed bytes; to the SAME order the reference copies.
  * Not taken (the reference's): 9 / 10 / 16-bit packed YUV (y210 and kin), a YUVA source's alpha, SWS_FAST_BILINEAR scaled contexts of any source but the
- * planar 8-bit ones (those: mi355_sws_create_fast_bilinear below) and the plain copy. */
+ * planar 8-bit ones (those: mi355_sws_create_fast_bilinear below), gbrp / gbrap SOURCES, and the plain copy. */
 enum { MI355_SWS_DST_YUYV422 = 48, MI355_SWS_DST_UYVY422 = 49, MI355_SWS_DST_YVYU422 = 50 };
 
 /* ---- SWS_FAST_BILINEAR contexts: the reference's cheap scaler (c->hyscale_fast / c->hcscale_fast = hyscale_fast_c / hcscale_fast_c, swscale.c:238-249,
@@ -456,6 +458,44 @@ mi355_sws_ctx *mi355_sws_create_fast_bilinear(const mi355_sws_desc *desc, const 
                                               int lumXInc, int chrXInc);
 int mi355_sws_fast_bilinear(const mi355_sws_ctx *ctx, int *lumXInc, int *chrXInc);   /* 1 / 0 (the increments: 0 then), -1 bad argument; either pointer may be NULL */
 
+/* ---- planar RGB destinations: gbrp (AV_PIX_FMT_GBRP, three planes of bytes: G, B, R) ----
+ * The one destination that runs the reference's ARITHMETIC yuv -> rgb path, yuv2gbrp_full_X_c (output.c:1275-1355, c->yuv2anyX reached at
+ * swscale.c:683-689).  The reference forces SWS_FULL_CHR_H_INT for it (utils.c:986-994): chrDstHSubSample = chrDstVSubSample = 0, so chroma is filtered
+ * horizontally to the full width and the chroma bank is indexed by dstY; no LUT is read, there is no dither (whatever the source's depth) and no range
+ * step here (this version of the reference sets its range converters, swscale.c:748-766, for a gbrp destination whose range differs from the
+ * source's — its isAnyRGB() does not know planar RGB — in front of coefficients that already carry the range: such a context is not created here,
+ * the binding declines it) — range and colourspace live in six integers, c->yuv2rgb_y_offset, _y_coeff, _v2r_coeff, _v2g_coeff, _u2g_coeff,
+ * _u2b_coeff AS THE REFERENCE'S INIT LEFT THEM (yuv2rgb.c:735-740; sws_setColorspaceDetails changes them): the binding hands them over, nothing here
+ * recomputes them.  The vertical form is always the X form, also with one tap.  Per pixel, in 32 bits:
+ *   Y = (1 << 9) + sum lum[j][i] * lumFilter[j];   U, V = (1 << 9) - (128 << 19) + sum chr[j][i] * chrFilter[j];   Y >>= 10; U >>= 10; V >>= 10
+ *   Y = (Y - y_offset) * y_coeff + (1 << 21);   R = Y + V * v2r;   G = Y + V * v2g + U * u2g;   B = Y + U * u2b
+ *   if ((R | G | B) & 0xC0000000) each = av_clip_uintp2(each, 30);   dst[0] = G >> 22, dst[1] = B >> 22, dst[2] = R >> 22
+ * The three sums are computed modulo 2^32, as the reference's compiled code computes them: on content the format allows they leave int32 (BT.601
+ * limited range, Y = 255 with U = 255: B near 2.24e9) and wrap, and the clip reads the wrapped bits.
+ * Source: every layout — MI355_SWS_SRC_PLANAR at 8 / 9 / 10 bits and 4:2:0 / 4:2:2 / 4:4:4, NV12 / NV21, rgb24 / bgr24, the four 32-bit orders, the three
+ * packed 4:2:2 orders, P010 — each with its own read extents and alignment rules, unchanged.
+ * Descriptor: the reference's for that context: chrDstW = dstW, vChr.n = dstH.  desc->luts is not read.
+ * Twin rule: the twin is mi355_sws_create_src_layout_range_depth(desc, src, src_layout, MI355_SWS_DST_YUV444P, MI355_SWS_RANGE_NONE, 8).  A gbrp context
+ * has the twin's banks, plan (MI355_SWS_K_PLANAR_A .. C by lum_lines / chr_lines), th, narrow / hstage / hstaged report and refusals: it is refused
+ * exactly where the twin's tiles cannot hold the lines (and where the twin refuses the source).  It is never a packer, a splitter or IDENT1_*: at
+ * equal size the reference has no special converter from a YUV source to gbrp (ff_yuv2rgb_get_func_ptr has no such case) and runs its scaler with
+ * one-tap banks; from an 8-bit packed RGB source at equal size it takes rgbToPlanarRgbWrapper (swscale_unscaled.c:1090-1092), which stays the
+ * reference's.
+ * Also NULL and a message for: desc->unscaled_special; coefs == NULL; a coefficient of magnitude 2^23 or more or a y_offset of 2^22 or more (the device
+ * multiplies 24-bit operands; the reference's are int16 coefficients and a y_offset below 2^16).  The other operand needs no rule of its own, whatever
+ * the vertical banks: a tap sum is an int32 (the reference's too; banks whose sums leave int32 overflow there as here), so a sum >> 10 lies inside
+ * +-2^21 and Y - y_offset inside +-(2^21 + 2^22) — both fit 24 signed bits, and the 24-bit product's low 32 bits are the 32-bit product's.  There is no alpha: the creator has no such argument,
+ * mi355_sws_alpha is 0, a 32-bit source's alpha byte is dropped as the reference drops it, and gbrap stays the reference's.
+ * Frames are mi355_sws_planar_frame through mi355_sws_scale_planar_frames_dev / mi355_sws_scale_planar with dst[0..2] = G, B, R: exactly dstW bytes of
+ * each of the dstH rows of each plane are written, a destination plane needs no alignment (rows on 8-byte multiples are stored eight bytes at a time).
+ * mi355_sws_destination reports format MI355_SWS_DST_GBRP, 3 planes, chr_bytes = dstW, chr_rows = dstH; mi355_sws_range is 0, mi355_sws_dest_depth 8.
+ * Not taken (the reference's): gbrp of 9 / 10 / 12 / 16 bits, gbrap, gbrp SOURCES, SWS_FULL_CHR_H_INT to the packed RGB destinations, and
+ * SWS_FAST_BILINEAR contexts to gbrp (mi355_sws_create_fast_bilinear refuses the format). */
+enum { MI355_SWS_DST_GBRP = 64 };
+typedef struct mi355_sws_rgb_coefs { int y_offset, y_coeff, v2r, v2g, u2g, u2b; } mi355_sws_rgb_coefs;
+mi355_sws_ctx *mi355_sws_create_gbrp(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, const mi355_sws_rgb_coefs *coefs);
+int mi355_sws_rgb_coefs_of(const mi355_sws_ctx *ctx, mi355_sws_rgb_coefs *coefs);   /* 1: a gbrp context (*coefs: its six) / 0 (*coefs: zeros), -1 bad argument; coefs may be NULL */
+
 /* ---- the individual inner loops (Tier 1, host pointers), argument lists of the reference's
  * function-pointer types minus the SwsContext ------------------------------------------------ */
 /* hScale8To15_c swscale.c:133-147 (c->hyScale / c->hcScale) */
@@ -489,6 +529,11 @@ void mi355_sws_p010ToUV(uint16_t *dstU, uint16_t *dstV, const uint8_t *src, int 
  * whatever srcW says (srcW is not looked at); nothing is done for dstWidth <= 0, xInc <= 0 or a last position that does not fit 32 bits */
 void mi355_sws_hyscale_fast(int16_t *dst, int dstWidth, const uint8_t *src, int srcW, int xInc);
 void mi355_sws_hcscale_fast(int16_t *dst1, int16_t *dst2, int dstWidth, const uint8_t *src1, const uint8_t *src2, int srcW, int xInc);
+/* yuv2gbrp_full_X_c output.c:1275-1355 (c->yuv2anyX of an 8-bit gbrp destination without alpha): `dstW` bytes to each of dest[0] = G, dest[1] = B,
+ * dest[2] = R by the formula above mi355_sws_create_gbrp; nothing is done for dstW <= 0, a filter size below 1 or a NULL argument */
+void mi355_sws_yuv2gbrp_full_X(const mi355_sws_rgb_coefs *coefs, const int16_t *lumFilter, const int16_t **lumSrc, int lumFilterSize,
+                               const int16_t *chrFilter, const int16_t **chrUSrc, const int16_t **chrVSrc, int chrFilterSize,
+                               uint8_t *const dest[3], int dstW);
 /* lumRangeFromJpeg_c / lumRangeToJpeg_c and chrRangeFromJpeg_c / chrRangeToJpeg_c swscale.c:168-198 (c->lumConvertRange / c->chrConvertRange):
  * `width` int16 samples converted in place, any int16 value (a result outside int16 is stored truncated, as the reference stores it) */
 void mi355_sws_lumConvertRange(int16_t *dst, int width, int to_jpeg);

@@ -15,7 +15,9 @@
  * plane of word pairs, the sample word >> 6 — p010LEToY_c / p010LEToUV_c input.c:499-524) to every destination the yuv420p10le source takes (their tile
  * instances, line kernels and the line entries mi355_sws_p010ToY / _p010ToUV are sws_p010.hip's); and SWS_FAST_BILINEAR contexts of the planar 8-bit
  * sources (mi355_sws_create_fast_bilinear: hyscale_fast_c / hcscale_fast_c swscale.c:238-301 in place of the bank-driven horizontal pass; the tile kernels
- * k_sws_fbl_generic / k_sws_fbl_planar and the line entries mi355_sws_hyscale_fast / _hcscale_fast are sws_fastbl.hip's).  This file:
+ * k_sws_fbl_generic / k_sws_fbl_planar and the line entries mi355_sws_hyscale_fast / _hcscale_fast are sws_fastbl.hip's); and planar RGB (gbrp)
+ * destinations from every source (mi355_sws_create_gbrp: yuv2gbrp_full_X_c output.c:1275-1355; the tile kernel k_sws_gbrp and the line entry
+ * mi355_sws_yuv2gbrp_full_X are sws_gbrp.hip's).  This file:
  * the context, the plan (which kernel a context gets) and the entry points of include/mi355_sws.h.  The device side is sws_dev.h:
  * k_sws_generic, k_sws_planar, k_sws_c24, k_sws_ident1, k_sws_nv12_pack, k_sws_nv12_split and the k_sws_line_* kernels of the Tier-1 entry points.
  * Filter banks and LUTs are inputs (built by the reference's init code, see include/mi355_sws.h).
@@ -47,6 +49,10 @@ struct mi355_sws_ctx {
     /* a SWS_FAST_BILINEAR context (mi355_sws_create_fast_bilinear): the horizontal pass reads no bank — the reference's two 16.16 increments, as its init
      * left them; the tile kernels are sws_fastbl.hip's k_sws_fbl_generic / k_sws_fbl_planar under the twin's key */
     int fast_bilinear = 0, lumXInc = 0, chrXInc = 0;
+    /* a gbrp context (mi355_sws_create_gbrp): created as its yuv444p twin (h.planar stays MI355_SWS_DST_YUV444P: the same tiles, the same three planes of
+     * dstW x dstH bytes) and marked; the vertical pass is sws_gbrp.hip's k_sws_gbrp under the twin's key, with the reference's six coefficients */
+    int gbrp = 0;
+    mi355_sws_rgb_coefs coefs = {};
 };
 
 template <typename T> static const T *upload_bank(mi355_sws_ctx *c, int slot, const T *host, size_t n)
@@ -567,6 +573,44 @@ extern "C" int mi355_sws_fast_bilinear(const mi355_sws_ctx *c, int *lumXInc, int
     return c->fast_bilinear;
 }
 
+/* ---- planar RGB destinations: gbrp, the reference's yuv2gbrp_full_X_c with six coefficients in place of the LUTs -------------------------------
+ * Everything but the vertical pass is the yuv444p twin's — the context of the same descriptor and source to an 8-bit 4:4:4 destination without range
+ * conversion: it is created as that twin (the source checks of every layout, the vertical banks against the FULL tiles, the plan, hfit) and then
+ * marked.  A 9 / 10-bit source's twin dithers; this destination does not (k_sws_gbrp reads no dither table). */
+extern "C" mi355_sws_ctx *mi355_sws_create_gbrp(const mi355_sws_desc *desc, const mi355_sws_src *src, int src_layout, const mi355_sws_rgb_coefs *coefs)
+{
+    const char *const who = "mi355_sws_create_gbrp";
+    if (!creator_args(who, desc, src)) return nullptr;
+    if (!coefs) {
+        std::fprintf(stderr, "mi355dsp: %s: no coefficients (c->yuv2rgb_* of the reference's context)\n", who);
+        return nullptr;
+    }
+    if (desc->unscaled_special) {
+        std::fprintf(stderr, "mi355dsp: %s: an unscaled special converter to gbrp (rgbToPlanarRgbWrapper) is not a context of the scaler\n", who);
+        return nullptr;
+    }
+    /* the device multiplies 24-bit operands (sws_dev.h: gbrp_pixel) */
+    auto fits = [](int v, int bits) { return v > -(1 << bits) && v < (1 << bits); };
+    if (!fits(coefs->y_offset, 22) || !fits(coefs->y_coeff, 23) || !fits(coefs->v2r, 23) || !fits(coefs->v2g, 23) || !fits(coefs->u2g, 23) || !fits(coefs->u2b, 23)) {
+        std::fprintf(stderr, "mi355dsp: %s: coefficients %d / %d / %d / %d / %d / %d do not fit 24 bits\n", who, coefs->y_offset, coefs->y_coeff, coefs->v2r, coefs->v2g,
+                     coefs->u2g, coefs->u2b);
+        return nullptr;
+    }
+    mi355_sws_ctx *c = mi355_sws_create_src_layout_range_depth(desc, src, src_layout, MI355_SWS_DST_YUV444P, MI355_SWS_RANGE_NONE, 8);
+    if (!c) {
+        std::fprintf(stderr, "mi355dsp: %s: the yuv444p context of this descriptor and source is refused (above)\n", who);
+        return nullptr;
+    }
+    c->gbrp = 1; c->coefs = *coefs;
+    return c;
+}
+extern "C" int mi355_sws_rgb_coefs_of(const mi355_sws_ctx *c, mi355_sws_rgb_coefs *coefs)
+{
+    if (!c) return -1;
+    if (coefs) *coefs = c->coefs;
+    return c->gbrp;
+}
+
 extern "C" void mi355_sws_destroy(mi355_sws_ctx *c)
 {
     if (!c) return;
@@ -640,6 +684,7 @@ extern "C" int mi355_sws_destination(const mi355_sws_ctx *c, mi355_sws_dest_info
     /* the packed-4:2:2 splitter rounds the width UP and, to yuv420p, the rows down (yuyvtoyuv420_c); to yuv422p every row has chroma */
     if (h.special && yuy2_src(h)) { p->chr_bytes = yuy2_chr_bytes(h); p->chr_rows = yuy2_chr_rows(h); }
     if (h.dst_bits > 8) p->chr_bytes = 2 * h.chrDstW;       /* 16-bit samples (mi355_sws_dest_depth) */
+    if (c->gbrp) p->format = MI355_SWS_DST_GBRP;            /* (planes, chr_bytes = dstW and chr_rows = dstH are the yuv444p twin's) */
     return 0;
 }
 
@@ -692,9 +737,9 @@ static int ctx_launch(const mi355_sws_ctx *c, int k, const void *d_frames, int n
 {
     const SwsDev &h = c->h;
     const SwsKey key = sws_key(c, k);
-    const SwsOperands op{ key_grid(key, h, nframes), s, &h, c->d, d_frames, &c->d->luts, h.dstW, h.srcH, h.dst_sel, nullptr, (uint32_t)c->lumXInc, (uint32_t)c->chrXInc };
-    /* a fast-bilinear context: the twin's key names its instance of the bank-free tile kernels */
-    if (!(c->fast_bilinear ? mi355_sws_launch_fastbl(key, op) : sws_run(key, op))) return -2;
+    const SwsOperands op{ key_grid(key, h, nframes), s, &h, c->d, d_frames, &c->d->luts, h.dstW, h.srcH, h.dst_sel, nullptr, (uint32_t)c->lumXInc, (uint32_t)c->chrXInc, &c->coefs };
+    /* a fast-bilinear context: the twin's key names its instance of the bank-free tile kernels; a gbrp context: the yuv444p twin's key its instance of k_sws_gbrp */
+    if (!(c->gbrp ? mi355_sws_launch_gbrp(key, op) : c->fast_bilinear ? mi355_sws_launch_fastbl(key, op) : sws_run(key, op))) return -2;
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -28,6 +28,8 @@
  *   k_sws_fbl_generic / k_sws_fbl_planar   the two tile kernels again for SWS_FAST_BILINEAR contexts (compiled in sws_fastbl.hip): the horizontal pass
  *                   reads no filter bank (hscale_tile_fbl: hyscale_fast_c / hcscale_fast_c swscale.c:238-301), the range step and the vertical pass are
  *                   the device functions of the two kernels above.  Kernels of their own names: k_sws_generic / k_sws_planar gain no instance.
+ *   k_sws_gbrp      k_sws_planar's FULL tile with the vertical pass of a planar RGB destination (compiled in sws_gbrp.hip): yuv2gbrp_full_X_c
+ *                   output.c:1275-1355, the arithmetic yuv -> rgb path with six integer coefficients, no LUT.  A kernel of its own name too.
  *   k_sws_line_*    the individual inner loops for the Tier-1 entry points.
  * Execution model: 256-thread workgroups (4 waves) sharing one LDS tile; integer only, no MFMA.
  */
@@ -2236,6 +2238,77 @@ __device__ __forceinline__ void range_lines(int16_t *lines, int nvec, const SwsR
     }
 }
 
+/* The horizontal pass of a planar workgroup's tile, up to (not including) its barrier: luma lines llo .. lhi into s_lum, the chroma lines the rows
+ * cy0 .. cy1 need into s_chr (U | V side by side, CW samples each), by the staging round of the source class (ST / NV / RGB as k_sws_planar's).
+ * clo: the first chroma line held, nchr: their count (0: the tile has no chroma row).  This is k_sws_planar's own text up to its barrier, stated
+ * again for k_sws_gbrp: with that kernel calling this function instead, 150 of its instances came out with another register allocation
+ * (tools/isa_kernel_hash.py), so k_sws_planar keeps its text and a change to either goes to both. */
+template <int CW, typename ST, bool NV, bool RGB>
+__device__ __forceinline__ void planar_hscale(const SwsDev &c, const mi355_sws_planar_frame &fr, int16_t (*s_lum)[TW], int16_t (*s_chr)[2 * CW], uint32_t *s_stage, int tid,
+                                              int x0, int hs, int llo, int lhi, int cy0, int cy1, int &clo, int &nchr)
+{
+    const int cs = c.vcs;
+    if constexpr (std::is_same<ST, SwsPxP010>::value) {
+        static_assert(NV && !RGB, "a P010 source is a luma plane and a plane of pairs");
+        hscale_tile_p010<TW, TW, 1>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi, s_stage, tid, false,
+                                    c.hstage != 0, c.hident_l != 0);
+    } else
+    if constexpr (std::is_same<ST, SwsPxYuy2>::value) {
+        static_assert(RGB && !NV, "packed 4:2:2 sources have one plane");
+        hscale_tile_rgb<TW, TW, 1, 2>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.srcW, false, false, c.hLumP, c.hLumC, c.hls, x0, c.dstW,
+                                      llo, lhi, s_stage, tid, false, c.hstage != 0, c.hident_l != 0, (uint32_t)c.src_layout);
+    } else
+    if constexpr (RGB && sizeof(ST) == 4) {
+        static_assert(!NV, "packed RGB sources have one plane");
+        hscale_tile_rgb<TW, TW, 1, 4>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.srcW, false, sws_src_bgr(c.src_layout), c.hLumP, c.hLumC, c.hls, x0, c.dstW,
+                                      llo, lhi, s_stage, tid, false, c.hstage != 0, c.hident_l != 0, sws_src_ash(c.src_layout));
+    } else
+    if constexpr (RGB) {
+        static_assert(sizeof(ST) == 1 && !NV, "packed RGB sources are 8 bit");
+        hscale_tile_rgb<TW, TW, 1>(s_lum, nullptr, fr.src[0], fr.src_stride[0], c.srcW, c.srcW, false, c.src_layout == MI355_SWS_SRC_BGR24, c.hLumP, c.hLumC, c.hls, x0, c.dstW,
+                                   llo, lhi, s_stage, tid, false, c.hstage != 0, c.hident_l != 0);
+    } else
+    hscale_tile<TW, TW, ST>(s_lum, fr.src[0], fr.src_stride[0], c.srcW, c.hLumP, c.hLumC, c.hls, x0, c.dstW, llo, lhi, s_stage, tid, false, c.hstage != 0, c.hident_l != 0, c.depth);
+    clo = 0; nchr = 0;
+    if (cy0 <= cy1) {
+        clo = clampi(imax(1 - cs, c.vChrP[cy0]), 0, c.chrSrcH - 1);
+        const int chi = clampi(imax(1 - cs, c.vChrP[cy1]) + cs - 1, 0, c.chrSrcH - 1);
+        nchr = chi - clo + 1;
+        if constexpr (std::is_same<ST, SwsPxP010>::value) {
+            int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
+            hscale_tile_p010<CW, 2 * CW, 2>(s_u, s_v, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false,
+                                            c.hstage != 0, c.hident_c != 0);
+        } else
+        if constexpr (std::is_same<ST, SwsPxYuy2>::value) {
+            int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
+            hscale_tile_rgb<CW, 2 * CW, 2, 2>(s_u, s_v, fr.src[0], fr.src_stride[0], c.srcW, c.chrSrcW, true, false, c.hChrP, c.hChrC, c.hcs,
+                                              x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, (uint32_t)c.src_layout);
+        } else
+        if constexpr (RGB && sizeof(ST) == 4) {
+            int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
+            hscale_tile_rgb<CW, 2 * CW, 2, 4>(s_u, s_v, fr.src[0], fr.src_stride[0], c.srcW, c.chrSrcW, c.src_hsub != 0, sws_src_bgr(c.src_layout), c.hChrP, c.hChrC, c.hcs,
+                                              x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, sws_src_ash(c.src_layout));
+        } else
+        if constexpr (RGB) {
+            int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
+            hscale_tile_rgb<CW, 2 * CW, 2>(s_u, s_v, fr.src[0], fr.src_stride[0], c.srcW, c.chrSrcW, c.src_hsub != 0, c.src_layout == MI355_SWS_SRC_BGR24, c.hChrP, c.hChrC, c.hcs,
+                                           x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0);
+        } else
+        if constexpr (NV) {
+            static_assert(sizeof(ST) == 1, "NV12 / NV21 sources are 8 bit");
+            int16_t (*const s_u)[2 * CW] = s_chr, (*const s_v)[2 * CW] = reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]);
+            const bool vu = c.src_layout == MI355_SWS_SRC_NV21;
+            hscale_tile_nv<CW, 2 * CW>(vu ? s_v : s_u, vu ? s_u : s_v, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> hs, c.chrDstW, clo, chi,
+                                       s_stage, tid, c.hstage != 0, c.hident_c != 0);
+        } else {
+        hscale_tile<CW, 2 * CW, ST>(s_chr, fr.src[1], fr.src_stride[1], c.chrSrcW, c.hChrP, c.hChrC, c.hcs, x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false,
+                                    c.hstage != 0, c.hident_c != 0, c.depth);
+        hscale_tile<CW, 2 * CW, ST>(reinterpret_cast<int16_t (*)[2 * CW]>(&s_chr[0][CW]), fr.src[2], fr.src_stride[2], c.chrSrcW, c.hChrP, c.hChrC, c.hcs,
+                                    x0 >> hs, c.chrDstW, clo, chi, s_stage, tid, false, c.hstage != 0, c.hident_c != 0, c.depth);
+        }
+    }
+}
+
 /* One workgroup per output tile of TW luma columns x th luma rows (blockIdx.z: the picture of the batch).  The tile's chroma is CW = TW >> hshift
  * columns and the chroma rows cy with cy << vshift inside the tile's rows (swscale.c:618-645: a chroma row is written with the luma row
  * cy << vshift, chrSkipMask).  Horizontal pass of the source lines the tile needs into LDS (hscale_tile, as k_sws_generic), then the
@@ -2552,6 +2625,144 @@ __global__ void __launch_bounds__(NT) k_sws_fbl_planar(const SwsDev *cp, uint32_
     if (cy0 <= cy1)
         planar_pass<CW / 8, 2, false>(&s_chr[0][0], clo, c.chrSrcH - 1, c.vChrC, c.vChrP, cs, cy0, cy1 - cy0 + 1, x0 >> hs, c.chrDstW,
                                       fr.dst[1] + (size_t)cy0 * fr.dst_stride[1], fr.dst_stride[1], fr.dst[2] + (size_t)cy0 * fr.dst_stride[2], fr.dst_stride[2], tid, nullptr);
+}
+
+/* ---- planar RGB destinations: gbrp (compiled in sws_gbrp.hip) -----------------------------------------------------------------------------------
+ * The reference's arithmetic yuv -> rgb path, yuv2gbrp_full_X_c (output.c:1275-1355; c->yuv2anyX, swscale.c:683-689).  It forces SWS_FULL_CHR_H_INT
+ * for this destination (utils.c:986-994): chroma is filtered to the full width (chrDstW = dstW, the chroma bank indexed by dstY), there is no LUT, no
+ * dither and no range step — range and colourspace are the six integers of mi355_sws_rgb_coefs (c->yuv2rgb_*, yuv2rgb.c:735-740), a kernel argument
+ * here.  Always the X form, also with one tap: the tap is multiplied by its coefficient.  Per pixel, in 32 bits:
+ *   Y = (1 << 9) + sum lum_j * f_j;   U, V = (1 << 9) - (128 << 19) + sum chr_j * f_j;   Y >>= 10; U >>= 10; V >>= 10
+ *   Y = (Y - y_offset) * y_coeff + (1 << 21);   R = Y + V * v2r;   G = Y + V * v2g + U * u2g;   B = Y + U * u2b
+ *   a sum with bit 30 or 31 set is clipped to 0 .. 2^30 - 1 (av_clip_uintp2(, 30): negative -> 0);   plane 0 = G >> 22, plane 1 = B >> 22, plane 2 = R >> 22
+ * The matrix runs in uint32_t: the reference's sums leave int32 on content the format allows (BT.601 limited range, Y = 255 with U = 255: B near
+ * 2.24e9) and its compiled code wraps; the clip then reads the wrapped bits.  The reference tests (R | G | B) & 0xC0000000 once and clips all three:
+ * clipping a sum without those bits is the identity, so each sum is clipped on its own bits here.
+ * The multiplies: both operands fit 24 signed bits whatever the banks — a tap sum is an int32, so a sum >> 10 lies inside +-2^21 and Y - y_offset
+ * inside +-(2^21 + 2^22) (mi355_sws_create_gbrp refuses a y_offset of 2^22 or more), and it refuses coefficients of 2^23 or more — so they are __mul24 (v_mul_i32_i24 / v_mad_i32_i24: the low 32
+ * bits of the product, which is the wrapped product).  The two kernel guides give no issue rate for either integer multiply on gfx950; the 24-bit
+ * form is the one range_one already uses on the same grounds, and it can fold the add that follows. */
+__device__ __forceinline__ uint32_t gbrp_clip30(uint32_t v) { return (v & 0xC0000000u) ? ((v >> 31) ? 0u : 0x3FFFFFFFu) : v; }
+/* the three bytes of one pixel from its three sums >> 10 */
+__device__ __forceinline__ void gbrp_pixel(const mi355_sws_rgb_coefs &k, int y, int u, int v, uint32_t &g, uint32_t &b, uint32_t &r)
+{
+    const uint32_t Y = (uint32_t)__mul24(y - k.y_offset, k.y_coeff) + (1u << 21);
+    r = gbrp_clip30(Y + (uint32_t)__mul24(v, k.v2r)) >> 22;
+    g = gbrp_clip30(Y + (uint32_t)__mul24(v, k.v2g) + (uint32_t)__mul24(u, k.u2g)) >> 22;
+    b = gbrp_clip30(Y + (uint32_t)__mul24(u, k.u2b)) >> 22;
+}
+constexpr int GBRP_LUM_SEED = 1 << 9, GBRP_CHR_SEED = (1 << 9) - (128 << 19);
+/* eight neighbouring samples of NP planes that lie side by side in an LDS line (`pw` samples apart, `pitch` samples a line) through one row of a
+ * vertical bank: seed + sum line_j * f_j, not shifted.  f: the row's fs coefficients; first: its first line, lines clamped to 0 .. maxl as the
+ * reference's ring buffer repeats them.  NTAP 2 / 4 / 8: the taps in registers, two at a time through sws_dot2 as planar_rows16 (taps past fs carry a
+ * zero coefficient — ONE tap is a pair with a zero, never a shortcut); 0: fs taps read as it goes. */
+template <int NTAP, int NP>
+__device__ __forceinline__ void gbrp_taps(const int16_t *col, int pitch, int pw, int lo, int maxl, const int16_t *f, int first, int fs, int seed, int (*v)[8])
+{
+    auto line = [&](int j, int p) { return *reinterpret_cast<const sws_u32x4 *>(col + (size_t)(clampi(first + j, 0, maxl) - lo) * pitch + p * pw); };
+#pragma unroll
+    for (int p = 0; p < NP; p++)
+#pragma unroll
+        for (int k = 0; k < 8; k++) v[p][k] = seed;
+    if (NTAP == 0) {
+        for (int j = 0; j < fs; j++) {
+            const int c = f[j];
+#pragma unroll
+            for (int p = 0; p < NP; p++) {
+                const sws_u32x4 a = line(j, p);
+#pragma unroll
+                for (int k = 0; k < 8; k++) v[p][k] += lane16(a, k) * c;
+            }
+        }
+    } else {
+        constexpr int N = NTAP > 1 ? NTAP : 2;
+        int lf[N];
+#pragma unroll
+        for (int j = 0; j < N; j++) lf[j] = f[j < fs ? j : 0];      /* unconditional: in flight together */
+#pragma unroll
+        for (int j = 0; j < N; j += 2) {
+            const uint32_t cp = (j < fs ? (uint32_t)lf[j] & 0xFFFFu : 0u) | (j + 1 < fs ? (uint32_t)lf[j + 1] << 16 : 0u);
+#pragma unroll
+            for (int p = 0; p < NP; p++) {
+                const sws_u32x4 la = line(j < fs ? j : 0, p), lb = line(j + 1 < fs ? j + 1 : 0, p);
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    v[p][2 * q] = sws_dot2(sws_lo2(la[q], lb[q]), cp, v[p][2 * q]);
+                    v[p][2 * q + 1] = sws_dot2(sws_hi2(la[q], lb[q]), cp, v[p][2 * q + 1]);
+                }
+            }
+        }
+    }
+}
+/* ... its tap count rounded up to 2 / 4 / 8, more from memory */
+template <int NP>
+__device__ __forceinline__ void gbrp_bank(const int16_t *col, int pitch, int pw, int lo, int maxl, const int16_t *f, int first, int fs, int seed, int (*v)[8])
+{
+    if (fs <= 2) gbrp_taps<2, NP>(col, pitch, pw, lo, maxl, f, first, fs, seed, v);
+    else if (fs <= 4) gbrp_taps<4, NP>(col, pitch, pw, lo, maxl, f, first, fs, seed, v);
+    else if (fs <= 8) gbrp_taps<8, NP>(col, pitch, pw, lo, maxl, f, first, fs, seed, v);
+    else gbrp_taps<0, NP>(col, pitch, pw, lo, maxl, f, first, fs, seed, v);
+}
+/* the vertical pass of a tile to the three planes: a thread takes eight neighbouring columns of a row — Y from s_lum, U | V from the two halves of
+ * an s_chr line (one ds_read_b128 per tap and plane; sixteen lanes cover a line's 256 bytes) — and stores eight bytes to each plane at once where
+ * the row address is a multiple of 8 and the group lies inside the picture, byte by byte at the right edge or on an unaligned row.  The bytes pass
+ * sws_opaque before they are packed, as in planar_rows (v_ashr_pk_u8_i32) */
+__device__ __forceinline__ void gbrp_rows(const SwsDev &c, const mi355_sws_rgb_coefs &k, const int16_t *s_lum, const int16_t *s_chr, int llo, int clo, int y0, int nrows,
+                                          int x0, uint8_t *const dst[3], const int dst_stride[3], int tid)
+{
+    constexpr int G = TW / 8;
+    const int ls = c.vls, cs = c.vcs;
+    for (int t = tid; t < nrows * G; t += NT) {
+        const int r = t / G, g = t % G, gx = x0 + 8 * g, y = y0 + r;
+        if (gx >= c.dstW) continue;
+        int yv[1][8], cv[2][8];
+        gbrp_bank<1>(s_lum + 8 * g, TW, 0, llo, c.srcH - 1, c.vLumC + (size_t)y * ls, imax(1 - ls, c.vLumP[y]), ls, GBRP_LUM_SEED, yv);
+        gbrp_bank<2>(s_chr + 8 * g, 2 * TW, TW, clo, c.chrSrcH - 1, c.vChrC + (size_t)y * cs, imax(1 - cs, c.vChrP[y]), cs, GBRP_CHR_SEED, cv);
+        uint32_t w[3][2] = { { 0, 0 }, { 0, 0 }, { 0, 0 } };
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            uint32_t pg, pb, pr;
+            gbrp_pixel(k, yv[0][i] >> 10, cv[0][i] >> 10, cv[1][i] >> 10, pg, pb, pr);
+            w[0][i >> 2] |= sws_opaque(pg) << (8 * (i & 3));
+            w[1][i >> 2] |= sws_opaque(pb) << (8 * (i & 3));
+            w[2][i >> 2] |= sws_opaque(pr) << (8 * (i & 3));
+        }
+#pragma unroll
+        for (int p = 0; p < 3; p++) {
+            uint8_t *d = dst[p] + (size_t)y * dst_stride[p] + gx;
+            if (gx + 8 <= c.dstW && (reinterpret_cast<uintptr_t>(d) & 7) == 0) {
+                *reinterpret_cast<sws_u32x2 *>(d) = sws_u32x2{ w[p][0], w[p][1] };
+            } else {                                   /* the picture's right edge, or a row that is not 8-byte aligned */
+                const int n = imin(8, c.dstW - gx);
+                for (int i = 0; i < n; i++) d[i] = (uint8_t)(w[p][i >> 2] >> (8 * (i & 3)));
+            }
+        }
+    }
+}
+
+/* k_sws_planar's FULL tile (LCAP / CCAP / ST / NV / RGB as there; CW = TW: the tile of a 4:4:4 destination holds exactly the lines this one needs)
+ * up to the barrier — the source class's own staging round, the same LDS and workgroups per CU as the yuv444p twin — then gbrp_rows.  No dither
+ * whatever the source's depth, no range step.  k: the context's six coefficients */
+template <int LCAP, int CCAP, typename ST = uint8_t, bool NV = false, bool RGB = false>
+#ifndef MI355_HIP_EMU_H
+__attribute__((amdgpu_waves_per_eu(sws_planar_waves(LCAP, CCAP, TW, stage_bytes<ST>()), sws_planar_waves(LCAP, CCAP, TW, stage_bytes<ST>()))))
+#endif
+__global__ void __launch_bounds__(NT) k_sws_gbrp(const SwsDev *cp, mi355_sws_rgb_coefs k, const mi355_sws_planar_frame *frames)
+{
+    __shared__ __attribute__((aligned(16))) int16_t s_lum[LCAP][TW];
+    __shared__ __attribute__((aligned(16))) int16_t s_chr[CCAP][2 * TW];
+    __shared__ __attribute__((aligned(16))) uint32_t s_stage[stage_bytes<ST>() / 4];
+    const SwsDev c = sws_dev(cp);
+    mi355_sws_planar_frame fr = frames[blockIdx.z];
+    for (int p = 0; p < 3; p++) { fr.src[p] = mi355_global(fr.src[p]); fr.dst[p] = mi355_global(fr.dst[p]); }
+    const int tid = threadIdx.x, th = c.th;
+    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * th, y1 = imin(y0 + th, c.dstH) - 1;
+    const int ls = c.vls;
+    const int llo = clampi(imax(1 - ls, c.vLumP[y0]), 0, c.srcH - 1), lhi = clampi(imax(1 - ls, c.vLumP[y1]) + ls - 1, 0, c.srcH - 1);
+    int clo = 0, nchr = 0;
+    planar_hscale<TW, ST, NV, RGB>(c, fr, s_lum, s_chr, s_stage, tid, x0, 0, llo, lhi, y0, y1, clo, nchr);      /* every row has chroma: cy = y */
+    __syncthreads();
+    gbrp_rows(c, k, &s_lum[0][0], &s_chr[0][0], llo, clo, y0, y1 - y0 + 1, x0, fr.dst, fr.dst_stride, tid);
 }
 
 /* MI355_SWS_TILE_KERNELS_ONLY (sws_deep.hip): the kernels that are no templates — the packer, the splitter, the line kernels — are sws.hip's
@@ -3204,6 +3415,7 @@ struct SwsOperands {
     uint32_t sel;
     const SwsLine *line;
     uint32_t lum_inc, chr_inc;     /* a fast-bilinear context's lumXInc / chrXInc (mi355_sws_launch_fastbl alone reads them) */
+    const mi355_sws_rgb_coefs *coefs;      /* a gbrp context's six coefficients, on the host (mi355_sws_launch_gbrp alone reads them) */
 };
 /* one launch function a file: false for a key the file has no instance for */
 bool mi355_sws_launch_deep(const SwsKey &key, const SwsOperands &op);       /* sws_deep.hip: the DEEP instances of the four classic source classes */
@@ -3212,6 +3424,7 @@ bool mi355_sws_launch_rgb32(const SwsKey &key, const SwsOperands &op);      /* s
 bool mi355_sws_launch_yuy2(const SwsKey &key, const SwsOperands &op);       /* sws_yuy2.hip: every tile instance of SWS_SRC_YUY2, k_sws_ident1_yuy2, k_sws_yuy2_split */
 bool mi355_sws_launch_p010(const SwsKey &key, const SwsOperands &op);       /* sws_p010.hip: every tile instance of SWS_SRC_P010, DST_YUY2 included */
 bool mi355_sws_launch_fastbl(const SwsKey &key, const SwsOperands &op);     /* sws_fastbl.hip: every instance of k_sws_fbl_generic / k_sws_fbl_planar (a fast-bilinear context's key is its twin's) */
+bool mi355_sws_launch_gbrp(const SwsKey &key, const SwsOperands &op);       /* sws_gbrp.hip: every instance of k_sws_gbrp (a gbrp context's key is its yuv444p twin's: PLANAR, FULL, PLAIN) */
 bool mi355_sws_launch_yuy2dst(const SwsKey &key, const SwsOperands &op);    /* sws_yuy2dst.hip: DST_YUY2 of k_sws_generic, k_sws_ident1, k_sws_ident1_yuy2, k_sws_line_packed from every source class; k_sws_yuy2_pack */
 
 namespace {

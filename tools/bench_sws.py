@@ -82,6 +82,11 @@ def main():
                          "kernels and (b) the same arithmetic restated as two-tap banks for the existing creator: 2160p -> 1080p and 1080p -> 2160p yuv420p to "
                          "rgb24 and to yuv420p; (a) a second time in another allocation (A/A); 32 and 512 pictures per launch, 3 warm-up + --steps launches a "
                          "round, alternating, median of --rounds rounds")
+    ap.add_argument("--gbrp", action="store_true",
+                    help="gbrp destinations (mi355_sws_create_gbrp) from yuv420p beside (a) the yuv444p twin of the same descriptor — the same passes, LDS and bytes "
+                         "written, no matrix — and (b) the rgb24 destination of the same geometry: 2160p -> 1080p, 1080p -> 2160p and 1080p -> 640x360; (a) a "
+                         "second time in another allocation (A/A); 32 and 512 pictures per launch, 3 warm-up + --steps launches a round, alternating, median of "
+                         "--rounds rounds")
     ap.add_argument("--other-lib", default=None,
                     help="--nv12 / --nvsrc / --rgbsrc / --range / --rgb32src / --p010: a second build of libmi355dsp.so (the parent commit's): the contexts it can build are timed on it too, alternating")
     ap.add_argument("--rounds", type=int, default=5, help="--planar / --sources / --yuy2src / --yuy2dst: alternating rounds (the median is reported)")
@@ -116,6 +121,8 @@ def main():
         return p010_points(a, lib)
     if a.fast_bilinear:
         return fastbl_points(a, lib)
+    if a.gbrp:
+        return gbrp_points(a, lib)
     orc = S.oracle_backend(providers.oracle())
     for name in a.configs.split(","):
         ctx = S.load_context(name)
@@ -1236,6 +1243,66 @@ def fastbl_points(a, lib, points=None, frame_counts=(32, 512)):
     miss = ["%s@%d %+.1f%% (spread %+.1f%%)" % (r["workload"], r["frames_per_launch"], 100 * r["vs_bilinear"], 100 * r["aa_spread"])
             for r in rows if r["workload"].endswith(":fast") and r["vs_bilinear"] > r["aa_spread"]]
     print(json.dumps({"summary": "fast_bilinear", "aa_session": aa, "points": len(rows), "miss": miss}), flush=True)
+
+
+def gbrp_points(a, lib, points=None, frame_counts=(32, 512)):
+    """A gbrp destination (mi355_sws_create_gbrp: k_sws_gbrp, the arithmetic yuv -> rgb pass) from yuv420p beside two yardsticks of the same geometry and
+    source bytes, both code the parent commit already had: `yuv444p` — the twin, the SAME descriptor through the existing creator to an 8-bit yuv444p
+    destination (the same staging rounds, LDS and bytes written, no matrix: the difference is the new pass), `yuv444p#2` the same a second time with
+    its own buffers: the session's A/A spread; `rgb24` — the reference's rgb24 context of the same sizes and flags on k_sws_generic (what a caller
+    takes today, before a de-interleave of its own; the same number of bytes written, chroma at half width through the LUTs).  The contexts come from
+    the reference's libswscale at run time (oracle/_ref/libswsref.so: mi355_sws_describe_gbrp and the existing describer) — no full-size context is
+    committed.  One process, the batches of a point alternating: 3 warm-up + --steps launches a round, median of --rounds rounds, at 32 and 512
+    pictures per launch.  Algorithmic bytes: the source planes read once + the destination planes written once.  The last line sums the session up:
+    `aa_session` and, under `miss`, every gbrp row slower than its twin by more than the point's spread."""
+    import statistics
+    import numpy as np
+    import sws_planar as P
+    import sws_fastbl as F
+    import sws_gbrp as B
+    ref = B.Ref(P.bind(B.REF_LIB))
+    points = points or [("uhd_to_hd", 3840, 2160, 1920, 1080), ("hd_to_uhd", 1920, 1080, 3840, 2160), ("hd_to_360p", 1920, 1080, 640, 360)]
+    rows = []
+    for frames in frame_counts:
+        for point, sw, sh, dw, dh in points:
+            row = (sw, sh, dw, dh, "yuv420p", 1, 0, None)               # a row of tests/sws_gbrp.py's form, not entered into its table
+            c = ref.open(row)
+            e = ref.describe_gbrp(c)
+            ref.free(c)
+            c = ref.open(row, dst=b"rgb24")
+            t = ref.describe_fmt(c)
+            ref.free(c)
+            assert e is not None and t is not None, point
+            rgb = F.Entry(t.ctx, t.hsub, t.vsub, t.fmt, 0, 8, 0, 0)
+            noise = B.frames(row)
+            pics = [[np.ascontiguousarray(pl[:, :w]) for pl, (w, _) in zip(noise[f], F.plane_dims((sw, sh, dw, dh, "420", 0, "444", 0)))] for f in (0, 2)]      # tightly pitched planes
+            batches = {"gbrp": PlaneBatch(lib, B.create(lib, e), pics, e.out_sizes(), frames),
+                       "yuv444p": PlaneBatch(lib, B.create_twin(lib, e), pics, e.out_sizes(), frames),
+                       "yuv444p#2": PlaneBatch(lib, B.create_twin(lib, e), pics, e.out_sizes(), frames),
+                       "rgb24": SourceBatch(lib, None, rgb, pics, frames, create=F.create_banked, bpp=3)}
+            plans = {k: F.plan_of(lib, b.handle) for k, b in batches.items()}
+            times = {k: [] for k in batches}
+            for _ in range(a.rounds):
+                for k, b in batches.items():
+                    times[k].append(time_ms(lib, b.run, a.steps))
+            base, packed = statistics.median(times["yuv444p"]), statistics.median(times["rgb24"])
+            spread = abs(statistics.median(times["yuv444p#2"]) / base - 1.0)
+            for k, b in batches.items():
+                ms = statistics.median(times[k])
+                us = ms * 1e3 / frames
+                nb = b.src_bytes + b.dst_bytes
+                out = {"workload": point + ":" + k, "frames_per_launch": frames, "ms_per_launch": ms, "us_per_picture": us, "frames_per_s": 1e6 / us,
+                       "algorithmic_bytes_per_frame": nb, "achieved_GBps": nb / us * 1e-3, "frac_of_8TBps": nb / us * 1e-3 / 8000.0,
+                       "vs_yuv444p": ms / base - 1.0, "vs_rgb24": ms / packed - 1.0, "aa_spread": spread, "kernel": plans[k]["kernel"],
+                       "hstage": plans[k]["hstage"], "hstaged": plans[k]["hstaged"], "ms_rounds": [round(x, 4) for x in times[k]]}
+                rows.append(out)
+                print(json.dumps(out), flush=True)
+            for b in batches.values():
+                b.close()
+    aa = max(r["aa_spread"] for r in rows)
+    miss = ["%s@%d %+.1f%% (spread %+.1f%%)" % (r["workload"], r["frames_per_launch"], 100 * r["vs_yuv444p"], 100 * r["aa_spread"])
+            for r in rows if r["workload"].endswith(":gbrp") and r["vs_yuv444p"] > r["aa_spread"]]
+    print(json.dumps({"summary": "gbrp", "aa_session": aa, "points": len(rows), "miss": miss}), flush=True)
 
 
 if __name__ == "__main__":
